@@ -1,7 +1,16 @@
 #!/usr/bin/env python
 """bench.py - headline benchmark of the CenterCLIP retrieval hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times exactly K steps in one window, writes the last step's outputs if
+--dump-outputs is given and prints the result line: nothing else.  --full adds everything else the benchmark measures
+(repeated timing windows, the side measurements, roofline, CPU baseline, the detail file); the options that tune those
+(--min-seconds, --no-extras, --no-cpu-baseline, --pmc, --detail-json) act only together with --full.
+
+--dump-outputs DIR: after the timed steps, the arrays the timed step hands its caller in its last step (rank 0's
+similarity logits; at N = 1 also the text and video features) as DIR/<name>.npy in float32.  Weights and inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1 without WORLD_SIZE in the environment: this script launches itself under torch.distributed.run with N ranks (one
 per GPU, RCCL) and refuses - exit code 2 - when fewer than N GPUs are visible.  Launched by torch.distributed.run it
@@ -18,12 +27,13 @@ One step = one pass of the hot path over one batch that is already resident in H
 Weak scaling: every rank owns its own 16 clips; value = all ranks' clips / max-over-ranks time.
 
 Timing: W untimed warm-up steps, then windows of EXACTLY K steps, each bracketed by barrier + synchronize on both
-sides, repeated until >= --min-seconds of timed work have run (DVFS steady state; the first window alone is ~40 ms).
-`ms_per_step` / `value` are the MEDIAN window (max over ranks per window); the first window is reported next to it.
+sides.  A plain run times one window.  With --full the windows repeat until >= --min-seconds (default 2) of timed work
+have run (DVFS steady state; the first window alone is ~40 ms).  `ms_per_step` / `value` are the MEDIAN window (max
+over ranks per window); the first window is reported next to it.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` for the kernel symbol with the
-largest share of the step (measured live with HIP events on the launch stream) and `cpu_baseline` (the oracle = the
-plain-PyTorch CPU restatement of the reference path, timed on this host on a bounded sample).
+Prints ONE JSON line on rank 0.  With --full it includes `roofline` for the kernel symbol with the largest share of the
+step (measured live with HIP events on the launch stream) and `cpu_baseline` (the oracle = the plain-PyTorch CPU
+restatement of the reference path, timed on this host on a bounded sample); a plain run reports both as null.
 """
 import argparse
 import json
@@ -106,6 +116,43 @@ def compact_line(res, detail_path=None):
     return line
 
 
+def headline(a, c, world, windows, total, graph):
+    """The result dict of the timed steps alone (windows: seconds per K-step window; the median one is the statistic)."""
+    elapsed = statistics.median(windows)
+    ms_per_step = elapsed / a.steps * 1e3
+    clips = c["B"] * world * a.steps
+    return {"metric": "clips/sec (ViT-B/32, 12f)", "value": round(clips / elapsed, 2), "unit": "clips/s",
+            "n_gpus": world, "collective_backend": (dist.get_backend() if world > 1 else None),
+            "ranks_in_communicator": (dist.get_world_size() if world > 1 else 1),
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE,
+            "data": "synthetic (N(0,1) frames, random token ids, random-init weights with CLIP init statistics rounded through fp16)",
+            "timing": {"windows": len(windows), "steps_per_window": a.steps, "statistic": "median window (max over ranks per window)",
+                       "first_window_ms_per_step": round(windows[0] / a.steps * 1e3, 3),
+                       "min_window_ms_per_step": round(min(windows) / a.steps * 1e3, 3),
+                       "max_window_ms_per_step": round(max(windows) / a.steps * 1e3, 3),
+                       "timed_seconds": round(total, 3)},
+            "launch": ("two hipGraphs replayed alternately on two streams (two batches in flight, --in-flight 2)" if a.in_flight == 2 else
+                       ("hipGraph replay" if world == 1 else "hipGraph replay (towers) + eager all-gather / similarity") if graph is not None else "eager launches"),
+            "config": {"workload": c["name"], "global_batch": c["B"] * world,
+                       "parallelism": "dp%d (clips sharded, one RCCL all-gather of preallocated feature records)" % world if world > 1 else "single GPU"}}
+
+
+def print_line(line):
+    s = json.dumps(line, separators=(",", ":"))
+    assert len(s) < LINE_LIMIT, len(s)
+    sys.stdout.flush()
+    print(s, flush=True)
+
+
+def dump_outputs(outs, dirname):
+    """--dump-outputs: each output tensor of the last timed step as <dirname>/<name>.npy, float32 (about 130 KB at cfg 2)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in outs.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().float().cpu().numpy())
+
+
 def self_launch(a):
     """`python bench.py --gpus N` with N > 1 outside torch.distributed.run: start N ranks on this node."""
     share = os.environ.get("CC_BENCH_SHARE_GPU") == "1"
@@ -128,7 +175,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="keep timing K-step windows until this much timed work ran")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: repeated timing windows, side measurements, roofline, CPU "
+                         "baseline, detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
+    ap.add_argument("--min-seconds", type=float, default=2.0,
+                    help="with --full: keep timing K-step windows until this much timed work ran")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of a captured hipGraph replay")
     ap.add_argument("--no-extras", action="store_true", help="skip the roofline / cluster / similarity side measurements")
@@ -149,6 +202,8 @@ def main():
     a = ap.parse_args()
     if a.workload != "cfg2":             # a profiling aid: the step alone (the side measurements are cfg2's)
         a.no_extras = a.no_cpu_baseline = True
+    if not a.full:                       # a plain run times one window of exactly --steps steps
+        a.min_seconds = 0.0
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(a)
@@ -187,23 +242,23 @@ def main():
     def step1():                                         # single GPU: the reference's call sequence (main.py:444,518)
         out = model(ids, token_type, amask, video, vmask)
         logits, *_ = model.get_similarity_logits(out["sequence_output"], out["visual_output"], amask, vmask)
-        return logits
+        return {"logits": logits, "sequence_output": out["sequence_output"], "visual_output": out["visual_output"]}
 
     def towers_n():                                      # N GPUs: both towers write into the preallocated record
         model.encode_into(sink, ids, video, vmask)
 
     def tail_n():                                        # exchange step (ONE all-gather) + this rank's row block
         sink.gather()
-        return sink.logits(sink.seq, scale)
+        return {"logits": sink.logits(sink.seq, scale)}
 
     graph = None
     with torch.no_grad():
         for _ in range(max(a.warmup, 1)):
             if world == 1:
-                logits = step1()
+                outs = step1()
             else:
                 towers_n()
-                logits = tail_n()
+                outs = tail_n()
         torch.cuda.synchronize()
         if not a.no_graph:
             # capture into a hipGraph: removes ~70 host launches per step from the critical path.  Inputs stay
@@ -233,7 +288,7 @@ def main():
                 turn[0] += 1
                 with torch.cuda.stream(flight[2][i]):
                     flight[1][i].replay()
-                return flight[0][i][-1]
+                return {"logits": flight[0][i][-1]}
         if flight is not None:
             run = run_two
         elif world == 1:
@@ -255,7 +310,7 @@ def main():
             for _ in range(a.steps):
                 out_ = run()
                 if out_ is not None:
-                    logits = out_
+                    outs = out_
             torch.cuda.synchronize()
             if world > 1:
                 dist.barrier()
@@ -269,8 +324,18 @@ def main():
             total += el
             if total >= a.min_seconds or len(windows) >= 400:
                 break
+    logits = outs["logits"]
     assert logits.shape == (c["B"], c["B"] * world) and bool(torch.isfinite(logits).all())
     elapsed = statistics.median(windows)
+    if a.dump_outputs and rank == 0:     # before the side measurements, which run the step again
+        dump_outputs(outs, a.dump_outputs)
+    if not a.full:
+        if rank == 0:
+            print_line(compact_line(headline(a, c, world, windows, total, graph)))
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     extras = {}
     if world > 1:                        # always reported at N > 1: how many ranks RCCL carried and what the exchange step cost
@@ -299,22 +364,7 @@ def main():
                 extras["forward_other_configs"] = {k: side.forward_config_bench(k, device) for k in ("cfg3", "cfg4", "cfg5")}
     if rank == 0:
         ms_per_step = elapsed / a.steps * 1e3
-        clips = c["B"] * world * a.steps
-        res = {"metric": "clips/sec (ViT-B/32, 12f)", "value": round(clips / elapsed, 2), "unit": "clips/s",
-               "n_gpus": world, "collective_backend": (dist.get_backend() if world > 1 else None),
-               "ranks_in_communicator": (dist.get_world_size() if world > 1 else 1),
-               "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3),
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE,
-               "data": "synthetic (N(0,1) frames, random token ids, random-init weights with CLIP init statistics rounded through fp16)",
-               "timing": {"windows": len(windows), "steps_per_window": a.steps, "statistic": "median window (max over ranks per window)",
-                          "first_window_ms_per_step": round(windows[0] / a.steps * 1e3, 3),
-                          "min_window_ms_per_step": round(min(windows) / a.steps * 1e3, 3),
-                          "max_window_ms_per_step": round(max(windows) / a.steps * 1e3, 3),
-                          "timed_seconds": round(total, 3)},
-               "launch": ("two hipGraphs replayed alternately on two streams (two batches in flight, --in-flight 2)" if a.in_flight == 2 else
-                          ("hipGraph replay" if world == 1 else "hipGraph replay (towers) + eager all-gather / similarity") if graph is not None else "eager launches"),
-               "config": {"workload": c["name"], "global_batch": c["B"] * world,
-                          "parallelism": "dp%d (clips sharded, one RCCL all-gather of preallocated feature records)" % world if world > 1 else "single GPU"}}
+        res = headline(a, c, world, windows, total, graph)
         res.update(extras)
         if "token_cluster" in res:
             roofc = res["token_cluster"]["cfg2"]["roofline"]
@@ -350,11 +400,7 @@ def main():
         except OSError as exc:
             sys.stderr.write("bench detail not written (%s)\n" % exc)
             detail_path = None
-        line = compact_line(res, detail_path)
-        s = json.dumps(line, separators=(",", ":"))
-        assert len(s) < LINE_LIMIT, len(s)
-        sys.stdout.flush()
-        print(s, flush=True)
+        print_line(compact_line(res, detail_path))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -217,13 +217,20 @@ def test_n4_variant_oracle_gradients_reproduce_reference(tag):
 @pytest.mark.parametrize("n,C", [(1, 64), (3, 32), (5, 40), (16, 64), (17, 96), (33, 64), (196, 768), (257, 64), (588, 32),
                                  (640, 100)])
 def test_aten_outer_sum_association_restatement(n, C):
-    """oracle.aten_outer_sums restates ATen's sum over a non-innermost dimension (segment / cluster means)."""
+    """oracle.aten_outer_sums restates ATen's sum over a non-innermost dimension (segment / cluster means), in its serial
+    association: at some thread counts (12, 16, 32 for [3, 640, 100]) ATen also splits the reduced dimension across threads,
+    so the torch side runs on one thread."""
     M = fullmant(500 + n, (n, C))
     masked = M * (np.random.default_rng(n).random((n, 1)) < 0.2)
-    for m in (M, masked.astype(np.float32)):
-        tt = t(m).reshape(1, n, C).repeat(3, 1, 1)
-        assert np.array_equal(co.aten_outer_sums(m), tt.sum(dim=1)[1].numpy())
-        assert np.array_equal(co.aten_outer_sums(m) / np.float32(n), tt.mean(dim=1)[2].numpy())
+    threads = torch.get_num_threads()
+    torch.set_num_threads(1)
+    try:
+        for m in (M, masked.astype(np.float32)):
+            tt = t(m).reshape(1, n, C).repeat(3, 1, 1)
+            assert np.array_equal(co.aten_outer_sums(m), tt.sum(dim=1)[1].numpy())
+            assert np.array_equal(co.aten_outer_sums(m) / np.float32(n), tt.mean(dim=1)[2].numpy())
+    finally:
+        torch.set_num_threads(threads)
 
 
 @pytest.mark.parametrize("tag", ["p1n_ragged", "p1n_b16_64f"])

@@ -722,7 +722,7 @@ def test_bench_line_contract_one_and_two_ranks():
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, "bench.py", "--steps", "5", "--warmup", "1", "--min-seconds", "0.1"], cwd=root, env=env,
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "5", "--warmup", "1", "--min-seconds", "0.1"], cwd=root, env=env,
                          capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     assert len(out.stdout) < 4096 and len(out.stdout.strip().splitlines()) == 1      # ONE compact line, nothing else on stdout
@@ -736,7 +736,7 @@ def test_bench_line_contract_one_and_two_ranks():
     assert d["roofline"]["bound"] == "mfma" and 0 < d["roofline"]["frac"] < 1 and d["cpu_baseline"]["kind"] == "port"
     assert "workload" in d["config"] and abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
     env2 = dict(env, CC_BENCH_SHARE_GPU="1")
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--steps", "5", "--warmup", "1", "--min-seconds", "0.1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--steps", "5", "--warmup", "1", "--min-seconds", "0.1",
                           "--no-cpu-baseline"], cwd=root, env=env2, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     d2 = json.loads(out.stdout.strip().splitlines()[-1])
@@ -746,3 +746,25 @@ def test_bench_line_contract_one_and_two_ranks():
     detail2 = json.load(open(os.path.join(root, d2["detail"])))
     assert "mtokens_per_s_all_ranks" in detail2["token_cluster"]["cfg2"]
     assert d2["token_cluster_mtokens_per_s"] == detail2["token_cluster"]["cfg2"]["mtokens_per_s_all_ranks"]
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): one window of exactly --steps steps, the headline line with roofline / cpu_baseline
+    null and no detail file, and --dump-outputs writes the last step's logits and features as float32 .npy files."""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "7", "--warmup", "1", "--dump-outputs", str(tmp_path)], cwd=root,
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    assert len(out.stdout.strip().splitlines()) == 1
+    d = json.loads(out.stdout)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 7 and d["timing"]["windows"] == 1 and d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["detail"] is None and abs(d["value"] - 16 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+    shapes = {"logits": (16, 16), "sequence_output": (16, 1, 512), "visual_output": (16, 3, 512)}
+    assert sorted(os.listdir(tmp_path)) == sorted(n + ".npy" for n in shapes)
+    for name, shape in shapes.items():
+        x = np.load(os.path.join(tmp_path, name + ".npy"))
+        assert x.dtype == np.float32 and x.shape == shape and np.isfinite(x).all(), (name, x.dtype, x.shape)

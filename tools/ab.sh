@@ -6,7 +6,7 @@ a=$1; b=$2; n=${3:-3}
 for i in $(seq $n); do
   for v in $a $b; do
     echo -n "$v "
-    CENTERCLIP_HIP_LIB=$PWD/abx/lib_$v.so python bench.py --steps 40 --warmup 3 --no-cpu-baseline --no-extras $AB_ARGS 2>/dev/null | tail -1 |
+    CENTERCLIP_HIP_LIB=$PWD/abx/lib_$v.so python bench.py --full --steps 40 --warmup 3 --no-cpu-baseline --no-extras $AB_ARGS 2>/dev/null | tail -1 |
       python -c "import sys,json; print(json.loads(sys.stdin.read())['ms_per_step'])"
   done
 done

@@ -8,7 +8,7 @@ out=$root/gpurun_out/insitu_$name
 mkdir -p $out
 cd $root
 [ -n "$lib" ] && export CENTERCLIP_HIP_LIB=$lib
-rocprofv3 --kernel-trace -d $out -o t --output-format csv -- python bench.py --steps 10 --warmup 2 --min-seconds 0.2 --no-cpu-baseline --no-extras > $out/run.log 2>&1
+rocprofv3 --kernel-trace -d $out -o t --output-format csv -- python bench.py --full --steps 10 --warmup 2 --min-seconds 0.2 --no-cpu-baseline --no-extras > $out/run.log 2>&1
 f=$(find $out -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY' | tee $root/gpurun_out/insitu_$name.txt
 import csv, sys, collections, re
