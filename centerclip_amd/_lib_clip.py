@@ -153,6 +153,18 @@ def declare(lib):
     lib.cc_bertadam_multi_large_f32.restype = c.c_int
     lib.cc_bertadam_step_f32.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, sz, vp]
     lib.cc_bertadam_step_f32.restype = c.c_int
+    lib.cc_adamw_blocks.argtypes = [i64]
+    lib.cc_adamw_blocks.restype = i32
+    lib.cc_adamw_multi_f32.argtypes = [vp, i32, i32, vp, vp, vp]
+    lib.cc_adamw_multi_f32.restype = c.c_int
+    lib.cc_grad_norm_workspace_bytes.argtypes = [i32]
+    lib.cc_grad_norm_workspace_bytes.restype = sz
+    lib.cc_grad_norm_partials_f32.argtypes = [vp, i32, i32, vp, sz, vp]
+    lib.cc_grad_norm_partials_f32.restype = c.c_int
+    lib.cc_grad_clip_coef_f32.argtypes = [vp, i32, f32, vp, vp]
+    lib.cc_grad_clip_coef_f32.restype = c.c_int
+    lib.cc_grad_scale_f32.argtypes = [vp, i32, i32, vp, vp]
+    lib.cc_grad_scale_f32.restype = c.c_int
     lib.cc_similarity_plane_row_bytes.argtypes = [i32]
     lib.cc_similarity_plane_row_bytes.restype = sz
     lib.cc_similarity_padded_rows.argtypes = [i32]

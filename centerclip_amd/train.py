@@ -620,9 +620,326 @@ class BertAdam(torch.optim.Optimizer):
                     self.state[p]['step'] += 1
 
 
+# ================================================================================================ AdamW + global clipping
+# torch.optim.AdamW and torch.nn.utils.clip_grad_norm_ (main.py:168-175, 316-333) on the multi-tensor kernels of
+# csrc/adamw.hip: one record per tensor (cc_adamw_item), every tensor of a step in one launch.
+_ADAMW_ITEM = None
+_adamw_blocks_cache = {}
+
+
+def _adamw_item_dtype():
+    global _ADAMW_ITEM
+    if _ADAMW_ITEM is None:
+        import numpy as np
+        _ADAMW_ITEM = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('n', '<i8'), ('blk0', '<i4'),
+                                ('blocks', '<i4'), ('scal', '<i4'), ('pad', '<i4')])
+    return _ADAMW_ITEM
+
+
+def _adamw_table(entries):
+    """entries: (param, grad, exp_avg or None, exp_avg_sq or None, scalar index) -> (cc_adamw_item records as bytes, count,
+    total blocks).  Empty tensors get no record."""
+    import numpy as np
+    lib = L.lib()
+    entries = [e for e in entries if e[0].numel() > 0]
+    rec = np.zeros(len(entries), dtype=_adamw_item_dtype())
+    blk0 = 0
+    for i, (p, g, m, v, si) in enumerate(entries):
+        n = p.numel()
+        nb = _adamw_blocks_cache.get(n)
+        if nb is None:
+            nb = _adamw_blocks_cache[n] = int(lib.cc_adamw_blocks(n))
+        rec[i] = (p.data_ptr(), g.data_ptr(), 0 if m is None else m.data_ptr(), 0 if v is None else v.data_ptr(), n, blk0, nb,
+                  si, 0)
+        blk0 += nb
+    return rec.tobytes(), len(entries), blk0
+
+
+class _Staged:
+    """A small host-built table in device memory (the cc_adamw_item records, the per-class scalars): uploaded through pinned
+    memory when its bytes change.  A captured step stages its own copy - the graph replays that host-to-device copy from a
+    pinned buffer set aside during the eager warm-up, so later eager uploads never touch what the graph reads."""
+
+    def __init__(self, who):
+        self.who, self.raw, self.dev, self.spare, self.keep = who, None, None, None, []
+
+    def upload(self, raw, device, capturing):
+        if capturing:
+            host, dev = self.spare if self.spare is not None else (None, None)
+            self.spare = None
+            if host is None or host.numel() != len(raw):
+                raise RuntimeError("%s: run one eager step with the same parameters before capturing (staging buffers)" % self.who)
+            host.copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+            dev.copy_(host, non_blocking=True)
+            self.keep.append((host, dev))                     # the graph reads both on every replay
+            return dev
+        if self.raw != raw:
+            host = torch.frombuffer(bytearray(raw), dtype=torch.uint8).pin_memory()
+            if self.dev is None or self.dev.numel() != len(raw) or self.dev.device != device:
+                self.dev = torch.empty(len(raw), dtype=torch.uint8, device=device)
+            self.dev.copy_(host, non_blocking=True)
+            self.raw = raw
+        if self.spare is None or self.spare[0].numel() != len(raw):
+            self.spare = (torch.empty(len(raw), dtype=torch.uint8).pin_memory(),
+                          torch.empty(len(raw), dtype=torch.uint8, device=device))
+        return self.dev
+
+
+def _clip_launches(table, count, nblk, max_norm, device, coef_only=False):
+    """||g|| over the table's gradients and the clip coefficient -> a [2] device float tensor (norm, coef); unless coef_only,
+    the gradients are multiplied by the coefficient in place (cc_grad_scale_f32)."""
+    lib = L.lib()
+    out = torch.empty(2, dtype=torch.float32, device=device)
+    ws = L.workspace(lib.cc_grad_norm_workspace_bytes(nblk), device)
+    st = _st(out)
+    _check(lib.cc_grad_norm_partials_f32(L.ptr(table), count, nblk, L.ptr(ws), ws.numel(), st), "cc_grad_norm_partials_f32")
+    _check(lib.cc_grad_clip_coef_f32(L.ptr(ws), nblk, float(max_norm), L.ptr(out), st), "cc_grad_clip_coef_f32")
+    if not coef_only:
+        _check(lib.cc_grad_scale_f32(L.ptr(table), count, nblk, L.ptr(out[1:]), st), "cc_grad_scale_f32")
+    return out
+
+
+_clip_staged = {}
+
+
+def _capturing():
+    return torch.cuda.is_available() and torch.cuda.is_current_stream_capturing()
+
+
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
+    """torch.nn.utils.clip_grad_norm_ (L2): the gradients are scaled in place by min(1, max_norm / (||g|| + 1e-6)), and the
+    total norm comes back as a 0-d device tensor.  HIP kernels only (cc_grad_norm_partials_f32 -> cc_grad_clip_coef_f32 ->
+    cc_grad_scale_f32): no host synchronisation, capturable.  The fp64 partial sums are added in the order of `parameters`,
+    so the same parameters in the same order give the same bits."""
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    if float(norm_type) != 2.0:
+        raise NotImplementedError("clip_grad_norm_ (HIP): only the L2 norm (norm_type=2), as main.py uses it")
+    grads = [p.grad for p in parameters if p.grad is not None]
+    if not grads:
+        return torch.tensor(0.0)
+    dev = grads[0].device
+    for g in grads:
+        L.require_device(g)
+        if g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
+            raise RuntimeError("clip_grad_norm_ (HIP): fp32 contiguous gradients on one device")
+    raw, count, nblk = _adamw_table([(g, g, None, None, 0) for g in grads])
+    if count == 0:
+        return torch.zeros((), dtype=torch.float32, device=dev)
+    capturing = _capturing()
+    slot = _clip_staged.setdefault((dev, len(raw)), _Staged("clip_grad_norm_"))
+    table = slot.upload(raw, dev, capturing)
+    return _clip_launches(table, count, nblk, max_norm, dev)[0]
+
+
+class AdamW(torch.optim.Optimizer):
+    """torch.optim.AdamW (the optimizer main.py:168-175 builds for --optim AdamW): same constructor and validation, same state
+    names ('step', 'exp_avg', 'exp_avg_sq': a state_dict loads into torch.optim.AdamW and back), the reference's extra group
+    keys ('lr_mult', 'decay_mult', written by lr_scheduler) pass through.  A step is ONE cc_adamw_multi_f32 launch over every
+    tensor with a gradient; the per-(group, step count) scalars (1 - lr wd, lr / (1 - b1^t), sqrt(1 - b2^t), ...) are host
+    arithmetic in double, as torch computes them, and reach the kernel through a small device array.
+
+    capturable=True: the record table and the scalars are staged so that a step captured into a hipGraph can be replayed -
+    refresh_lr() before a replay writes the scalars for the groups' current lr / weight_decay and the next step count,
+    advance() after it counts the step (the protocol of BertAdam, used by GraphedTrainStep)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False, *, maximize=False,
+                 capturable=False):
+        if amsgrad:
+            raise ValueError("AdamW (HIP): amsgrad=True is not supported (the reference trains without it)")
+        if maximize:
+            raise ValueError("AdamW (HIP): maximize=True is not supported (the reference trains without it)")
+        if isinstance(lr, torch.Tensor) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if not 0.0 <= betas[0] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 0: {betas[0]}")
+        if not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid beta parameter at index 1: {betas[1]}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        self.capturable = bool(capturable)
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False))
+
+    def load_state_dict(self, state_dict):
+        """Also takes torch.optim.AdamW's state (a tensor-valued 'step', its extra group keys)."""
+        super().load_state_dict(state_dict)
+        for st in self.state.values():
+            if torch.is_tensor(st.get('step')):
+                st['step'] = int(st['step'].item())
+
+    @staticmethod
+    def _scalars(group, t):
+        """cc_adamw_scalars of a group at step count t (after the step), in torch's double arithmetic."""
+        b1, b2 = (float(b) for b in group['betas'])
+        lr, wd = float(group['lr']), float(group['weight_decay'])
+        bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
+        return (1 - lr * wd, b1, 1 - b1, b2, 1 - b2, lr / bc1, bc2 ** 0.5, float(group['eps']))
+
+    def _upload_scalars(self, rows, device):
+        import numpy as np
+        arr = np.asarray(rows, dtype=np.float64).astype(np.float32).reshape(-1)
+        host = torch.from_numpy(arr).pin_memory()
+        dev = getattr(self, "_scal_dev", None)
+        if dev is None or dev.numel() < arr.size or dev.device != device:
+            if getattr(self, "_cap", None) is not None:
+                raise RuntimeError("AdamW: more (group, step count) classes than when the step was captured")
+            dev = self._scal_dev = torch.zeros(max(arr.size, 8 * 16), dtype=torch.float32, device=device)
+        dev[:arr.size].copy_(host, non_blocking=True)
+        return dev
+
+    def _prepare(self):
+        """-> (device, table, count, total blocks, scalars) for the parameters that have a gradient; advances the step counts
+        unless a capture is running."""
+        capturing = _capturing()
+        if capturing and not self.capturable:
+            raise RuntimeError("AdamW: build it with capturable=True to capture its step")
+        entries, classes, dev = [], {}, None
+        for gi, group in enumerate(self.param_groups):
+            if group.get('amsgrad') or group.get('maximize'):
+                raise ValueError("AdamW (HIP): amsgrad / maximize are not supported")
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                if p.grad.is_sparse:
+                    raise RuntimeError("AdamW (HIP): sparse gradients are not supported")
+                if p.dtype != torch.float32 or not p.is_contiguous():
+                    raise RuntimeError("AdamW (HIP): fp32 contiguous parameters (the master weights)")
+                L.require_device(p)
+                if dev is None:
+                    dev = p.device
+                elif p.device != dev:
+                    raise RuntimeError("AdamW (HIP): all parameters on one device")
+                if p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
+                    p.grad = p.grad.float().contiguous()
+                state = self.state[p]
+                if len(state) == 0:
+                    state['step'] = 0
+                    state['exp_avg'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state['exp_avg_sq'] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                elif torch.is_tensor(state['step']):
+                    state['step'] = int(state['step'].item())
+                t = state['step'] + 1
+                ci = classes.setdefault((gi, t), (len(classes), p))[0]
+                entries.append((p, p.grad, state['exp_avg'], state['exp_avg_sq'], ci))
+                if not capturing:
+                    state['step'] = t
+        if not entries:
+            return None
+        raw, count, nblk = _adamw_table(entries)
+        if not hasattr(self, "_staged"):
+            self._staged = {}
+        table = self._staged.setdefault(len(raw), _Staged("AdamW")).upload(raw, dev, capturing)
+        ordered = sorted(classes.items(), key=lambda kv: kv[1][0])
+        if capturing:
+            # what refresh_lr / advance need: per class its group and one of its parameters (whose step count is the class's)
+            if getattr(self, "_scal_dev", None) is None or self._scal_dev.numel() < 8 * len(ordered):
+                raise RuntimeError("AdamW: run one eager step with the same parameters before capturing (scalars)")
+            self._cap = dict(classes=[(gi, p) for (gi, _), (_, p) in ordered], params=[e[0] for e in entries])
+            scal = self._scal_dev
+        else:
+            scal = self._upload_scalars([self._scalars(self.param_groups[gi], t) for (gi, t), _ in ordered], dev)
+        return dev, table, count, nblk, scal
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        prep = self._prepare()
+        if prep is not None:
+            dev, table, count, nblk, scal = prep
+            _check(L.lib().cc_adamw_multi_f32(L.ptr(table), count, nblk, L.ptr(scal), None, _st(scal)), "cc_adamw_multi_f32")
+        return loss
+
+    @torch.no_grad()
+    def clip_and_step(self, max_norm):
+        """clip_grad_norm_(the parameters with a gradient, max_norm) followed by step(), fused: the step launch multiplies each
+        gradient by the device-side clip coefficient as it loads it and writes the clipped gradient back (one read-modify-write
+        pass over the gradients less).  Bit for bit clip_grad_norm_ over the same parameters in group order + step().
+        -> the total norm before clipping (0-d device tensor)."""
+        prep = self._prepare()
+        if prep is None:
+            return torch.tensor(0.0)
+        dev, table, count, nblk, scal = prep
+        out = _clip_launches(table, count, nblk, max_norm, dev, coef_only=True)
+        _check(L.lib().cc_adamw_multi_f32(L.ptr(table), count, nblk, L.ptr(scal), L.ptr(out[1:]), _st(scal)),
+               "cc_adamw_multi_f32")
+        return out[0]
+
+    def refresh_lr(self):
+        """capturable: write the captured step's scalars (each group's current lr / weight_decay, the next step count) into
+        their device array - call before replaying a captured step."""
+        cap = getattr(self, "_cap", None)
+        if cap is None:
+            return
+        rows = [self._scalars(self.param_groups[gi], self.state[p]['step'] + 1) for gi, p in cap['classes']]
+        self._upload_scalars(rows, self._scal_dev.device)
+
+    def advance(self):
+        """capturable: count one replayed step for every parameter the captured step updates."""
+        cap = getattr(self, "_cap", None)
+        for p in (cap['params'] if cap is not None else ()):
+            self.state[p]['step'] += 1
+
+
+class lr_scheduler:
+    """The reference's per-iteration learning-rate scheduler (utils/lr_scheduler.py, main.py:171-174 with mode 'cos'), written
+    to its interface: a linear slow start from slow_start_lr over slow_start_iters iterations, then
+      cos   lr = init_lr / 2 (1 + cos(pi T / total))            poly  lr = init_lr (1 - T / total)^0.9
+      HTD   lr = init_lr / 2 (1 - tanh(lower + (upper - lower) T / total))
+      step  lr = init_lr multiplier^(epoch // lr_step), or ^(number of milestones passed)
+    with T counted from the end of the slow start and total = all_iters - slow_start_iters, clamped below at end_lr.  A call
+    writes lr * lr_mult and weight_decay * decay_mult into every parameter group.  Host arithmetic only."""
+
+    def __init__(self, mode='cos', init_lr=0.1, all_iters=300, lr_milestones=None, lr_step=100, lr_step_multiplier=0.1,
+                 slow_start_iters=0, slow_start_lr=1e-8, end_lr=1e-8, lower_bound=-6.0, upper_bound=3.0, weight_decay=1e-4,
+                 iters_per_epoch=None):
+        if mode not in ('cos', 'poly', 'HTD', 'step'):
+            raise ValueError("lr_scheduler: mode must be one of 'cos', 'poly', 'HTD', 'step', got %r" % (mode,))
+        self.mode, self.init_lr, self.now_lr, self.end_lr = mode, init_lr, init_lr, end_lr
+        self.slow_start_iters, self.slow_start_lr = slow_start_iters, slow_start_lr
+        self.total_iters = all_iters - slow_start_iters
+        self.lr_step, self.lr_milestones, self.lr_step_multiplier = lr_step, lr_milestones, lr_step_multiplier
+        self.lower_bound, self.upper_bound = lower_bound, upper_bound
+        self.weight_decay = weight_decay
+        self.iters_per_epoch = iters_per_epoch             # (only for calls without global_step)
+
+    def lr_at(self, T, epoch=None):
+        """The learning rate at iteration T (epoch: for mode 'step')."""
+        import math
+        if self.slow_start_iters > 0 and T <= self.slow_start_iters:
+            lr = (1.0 * T / self.slow_start_iters) * (self.init_lr - self.slow_start_lr)
+            lr = min(lr + self.slow_start_lr, self.init_lr)
+        elif self.mode == 'cos':
+            lr = 0.5 * self.init_lr * (1.0 + math.cos(1.0 * (T - self.slow_start_iters) / self.total_iters * math.pi))
+        elif self.mode == 'poly':
+            lr = self.init_lr * pow(1.0 - 1.0 * (T - self.slow_start_iters) / self.total_iters, 0.9)
+        elif self.mode == 'HTD':
+            ratio = 1.0 * (T - self.slow_start_iters) / self.total_iters
+            lr = 0.5 * self.init_lr * (1.0 - math.tanh(self.lower_bound + (self.upper_bound - self.lower_bound) * ratio))
+        elif self.lr_milestones is None:
+            lr = self.init_lr * (self.lr_step_multiplier ** (epoch // self.lr_step))
+        else:
+            lr = self.init_lr * (self.lr_step_multiplier ** sum(1 for mile in self.lr_milestones if epoch >= mile))
+        return max(lr, self.end_lr)
+
+    def __call__(self, optimizer, i=None, epoch=None, global_step=None):
+        T = (epoch * self.iters_per_epoch + i) if global_step is None else global_step
+        lr = self.now_lr = self.lr_at(T, epoch)
+        for group in optimizer.param_groups:
+            group['lr'] = lr * group['lr_mult']
+            group['weight_decay'] = self.weight_decay * group['decay_mult']
+
+
 def prep_optim_params_groups(args, model, coef_lr=1.):
-    """utils/optimization.py:173-208 (BertAdam branch): CLIP parameters at lr * coef_lr, newly added modules at lr, no weight
-    decay for biases / LayerNorm."""
+    """utils/optimization.py:173-222: CLIP parameters at lr * coef_lr, newly added modules at lr, no weight decay for biases /
+    LayerNorm.  BertAdam (the default): 'lr' / 'weight_decay' per group; args.optim == 'AdamW': every group at args.lr with
+    the 'lr_mult' / 'decay_mult' keys that lr_scheduler applies."""
     model = getattr(model, 'module', model)
     named = list(model.named_parameters())
     no_decay = ['bias', 'LayerNorm.bias', 'LayerNorm.weight']
@@ -630,6 +947,15 @@ def prep_optim_params_groups(args, model, coef_lr=1.):
     dec = [(n, p) for n, p in named if not any(nd in n for nd in no_decay)]
     nodec = [(n, p) for n, p in named if any(nd in n for nd in no_decay)]
     is_clip = lambda n: "clip." in n and not any(nd in n for nd in no_clip)
+    if getattr(args, 'optim', 'BertAdam') == 'AdamW':
+        return [{'params': [p for n, p in dec if is_clip(n)], 'weight_decay': args.wd, 'lr': args.lr, 'lr_mult': coef_lr,
+                 'decay_mult': 1},
+                {'params': [p for n, p in nodec if is_clip(n)], 'weight_decay': 0.0, 'lr': args.lr, 'lr_mult': coef_lr,
+                 'decay_mult': 0.0},
+                {'params': [p for n, p in dec if not is_clip(n)], 'weight_decay': args.wd, 'lr': args.lr, 'lr_mult': 1.0,
+                 'decay_mult': 1.0},
+                {'params': [p for n, p in nodec if not is_clip(n)], 'weight_decay': 0.0, 'lr': args.lr, 'lr_mult': 1.0,
+                 'decay_mult': 0.0}]
     return [{'params': [p for n, p in dec if is_clip(n)], 'weight_decay': args.wd, 'lr': args.lr * coef_lr},
             {'params': [p for n, p in nodec if is_clip(n)], 'weight_decay': 0.0, 'lr': args.lr * coef_lr},
             {'params': [p for n, p in dec if not is_clip(n)], 'weight_decay': args.wd},
@@ -696,20 +1022,36 @@ class GraphedTrainStep:
     parameters, moments and step counts are put back before the one replay that counts, so that EVERY call, the first
     included, is exactly one optimizer step (main.py:300-340) and the schedule position equals the caller's step count."""
 
-    def __init__(self, model, optimizer, gradient_accumulation_steps=1):
+    def __init__(self, model, optimizer, gradient_accumulation_steps=1, scheduler=None, clip_grad_norm=None, global_step=0):
+        """scheduler (e.g. lr_scheduler): called as scheduler(optimizer, global_step=k) on the host before every step, k = the
+        number of calls made so far + global_step (main.py:302); its lr reaches the captured step through refresh_lr().
+        clip_grad_norm: global gradient clipping inside the captured step, before the optimizer (main.py:327-333) -
+        AdamW.clip_and_step, or clip_grad_norm_ then step() for BertAdam."""
         if not getattr(optimizer, "capturable", False):
-            raise ValueError("GraphedTrainStep needs BertAdam(..., capturable=True)")
+            raise ValueError("GraphedTrainStep needs BertAdam(..., capturable=True) or AdamW(..., capturable=True)")
         if gradient_accumulation_steps != 1:
             raise NotImplementedError("GraphedTrainStep: gradient accumulation is not built")
         self.model, self.optimizer = model, optimizer
+        self.scheduler, self.clip_grad_norm, self.global_step = scheduler, clip_grad_norm, int(global_step)
+        self._moments = ('exp_avg', 'exp_avg_sq') if isinstance(optimizer, AdamW) else ('next_m', 'next_v')
         self.graph = self.static = self.loss = None
+
+    def _schedule(self):
+        if self.scheduler is not None:
+            self.scheduler(self.optimizer, global_step=self.global_step)
 
     def _step(self):
         self.optimizer.zero_grad(set_to_none=True)       # (captured: the gradients live in the graph's pool, no fill + accumulate)
         out = self.model(self.static[0], self.static[2], self.static[1], self.static[3], self.static[4])
         loss = out['loss'].mean()
         loss.backward()
-        self.optimizer.step()
+        if self.clip_grad_norm is None:
+            self.optimizer.step()
+        elif isinstance(self.optimizer, AdamW):
+            self.optimizer.clip_and_step(self.clip_grad_norm)
+        else:
+            clip_grad_norm_([p for g in self.optimizer.param_groups for p in g['params']], self.clip_grad_norm)
+            self.optimizer.step()
         with torch.no_grad():
             self.model.clip.logit_scale.clamp_(0.1, 4.6052)
         return loss.detach()
@@ -723,26 +1065,29 @@ class GraphedTrainStep:
         return out
 
     def _snapshot(self):
-        """Copies of everything a step changes: every parameter, and per parameter the optimizer's (step, next_m, next_v)."""
+        """Copies of everything a step changes: every parameter, and per parameter the optimizer's (step, first moment, second
+        moment) - next_m / next_v for BertAdam, exp_avg / exp_avg_sq for AdamW."""
         snap = []
+        km, kv = self._moments
         for p in self._tensors():
             st = self.optimizer.state.get(p, {})
-            snap.append((p, p.detach().clone(), st.get('step'), st['next_m'].clone() if 'next_m' in st else None,
-                         st['next_v'].clone() if 'next_v' in st else None))
+            snap.append((p, p.detach().clone(), st.get('step'), st[km].clone() if km in st else None,
+                         st[kv].clone() if kv in st else None))
         return snap
 
     @torch.no_grad()
     def _restore(self, snap):
         """In place (the captured graph holds the addresses of the parameters and of the moments the warm-up created);
         Tensor.copy_ bumps the version counter, so cached fp16 / folded copies of the weights refresh."""
+        km, kv = self._moments
         for p, value, step, m, v in snap:
             p.copy_(value)
             st = self.optimizer.state.get(p)
             if not st:
                 continue
             st['step'] = 0 if step is None else step
-            st['next_m'].zero_() if m is None else st['next_m'].copy_(m)
-            st['next_v'].zero_() if v is None else st['next_v'].copy_(v)
+            st[km].zero_() if m is None else st[km].copy_(m)
+            st[kv].zero_() if v is None else st[kv].copy_(v)
 
     def __call__(self, batch):
         """batch = (input_ids, input_mask, segment_ids, video, video_mask) as the dataloaders yield it -> the step's loss (a
@@ -753,19 +1098,24 @@ class GraphedTrainStep:
             self.static = [t.to(dev).clone() for t in batch]
             snap = self._snapshot()
             for _ in range(2):                                    # allocator / staging-buffer warm-up (the optimizer's records)
+                self._schedule()
                 self._step()
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):                    # (the capture pass does not execute)
                 self.loss = self._step()
             self._restore(snap)                                   # the two warm-up steps never happened
+            self._schedule()
             self.optimizer.refresh_lr()
             self.graph.replay()
             self.optimizer.advance()
+            self.global_step += 1
             return self.loss
         for dst, src in zip(self.static, batch):
             dst.copy_(src, non_blocking=True)
+        self._schedule()
         self.optimizer.refresh_lr()
         self.graph.replay()
         self.optimizer.advance()
+        self.global_step += 1
         return self.loss

@@ -2,11 +2,16 @@
 
     model = CLIP4Clip.from_pretrained(...); optimizer = BertAdam(prep_optim_params_groups(...)); train_epoch(...)
 
+or, with --optim AdamW, the recipe every shipped launcher uses (main.py:168-175, 316-333): AdamW(betas=(0.9, 0.98), eps=1e-6,
+weight_decay=0.2) over the reference's lr_mult / decay_mult groups, the per-iteration 'cos' lr_scheduler with a 10 % slow start
+and global gradient clipping at 1.0.  --optim-timing 1 times the optimizer step alone (HIP AdamW, clip_and_step and
+torch.optim.AdamW(fused=True) + torch's clip over the same parameters).
+
 with random-init ViT-B/32 weights at the cfg-2 shape (12 frames -> 3 segments at block 7, K = 49, batch 16) and fp32 master
 weights.  Forward and backward of the towers, the loss and the optimizer step run in the HIP library (centerclip_amd.train);
 the path is a correctness slice - per-op launches from Python, nothing fused or tuned - and the printed step time says so.
 
-    python examples/train_synthetic.py [--steps 4] [--batch 16]
+    python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
 import argparse
@@ -20,7 +25,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from centerclip_amd.clip4clip import CLIP4Clip              # noqa: E402
-from centerclip_amd.train import BertAdam, prep_optim_params_groups, train_epoch   # noqa: E402
+from centerclip_amd.train import AdamW, BertAdam, lr_scheduler, prep_optim_params_groups, train_epoch   # noqa: E402
 from centerclip_amd import dist as ccdist                   # noqa: E402
 import bench                                                # noqa: E402
 from eval_synthetic import SyntheticRetrieval               # noqa: E402
@@ -33,6 +38,8 @@ def main():
     ap.add_argument("--graph", type=int, default=1, help="also time the step captured into a hipGraph")
     ap.add_argument("--b16", type=int, default=0, help="ViT-B/16 instead (cfg-5 shape: 197 tokens per frame, 12 frames -> 4 segments, "
                                                        "K = 100; the attention backward's two-launch form)")
+    ap.add_argument("--optim", choices=["BertAdam", "AdamW"], default="BertAdam")
+    ap.add_argument("--optim-timing", type=int, default=0, help="also time the optimizer step alone (AdamW)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -46,9 +53,20 @@ def main():
     args = bench.task_config(c)
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), args).float().to(device)
     targs = Namespace(lr=1e-7, wd=0.2, new_added_modules=["Cross", "cluster_embed"], gradient_accumulation_steps=1,
-                      clip_grad_norm=None)
-    opt = BertAdam(prep_optim_params_groups(targs, model, coef_lr=1e-3), lr=targs.lr, warmup=0.1, t_total=100 * a.steps,
-                   schedule='warmup_cosine', b1=0.9, b2=0.98, e=1e-6, max_grad_norm=1.0)
+                      clip_grad_norm=None, optim=a.optim)
+    total = 100 * a.steps
+
+    def make_opt(capturable=False):
+        """-> (optimizer, scheduler) of main.py:168-175 for --optim"""
+        groups = prep_optim_params_groups(targs, model, coef_lr=1e-3)
+        if a.optim == "AdamW":
+            return (AdamW(groups, lr=targs.lr, betas=(0.9, 0.98), eps=1e-6, weight_decay=targs.wd, capturable=capturable),
+                    lr_scheduler('cos', init_lr=targs.lr, all_iters=total, slow_start_iters=0.1 * total, weight_decay=targs.wd))
+        return BertAdam(groups, lr=targs.lr, warmup=0.1, t_total=total, schedule='warmup_cosine', b1=0.9, b2=0.98, e=1e-6,
+                        max_grad_norm=1.0, capturable=capturable), None
+    if a.optim == "AdamW":
+        targs.clip_grad_norm = 1.0                          # main.py's default --clip_grad_norm
+    opt, sched = make_opt()
     buckets = ccdist.GradientBuckets(model.parameters()) if world > 1 else None
     data = SyntheticRetrieval(a.batch * a.steps, seed=rank)
     loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False)
@@ -59,7 +77,7 @@ def main():
         t.append(time.time())
         if rank == 0:
             print("step %d  loss %.4f  %.0f ms" % (gs, loss, (t[-1] - t[-2]) * 1e3), flush=True)
-    train_epoch(0, targs, model, loader, device, opt, 0, buckets=buckets, log=log)
+    train_epoch(0, targs, model, loader, device, opt, 0, scheduler=sched, buckets=buckets, log=log)
     if rank == 0:
         steady = (t[-1] - t[2]) / max(len(t) - 3, 1) if len(t) > 3 else float("nan")
         print("steady step %.0f ms = %.1f clips/s per rank (unfused per-op training path, launched op by op)" % (steady * 1e3, a.batch / steady))
@@ -67,9 +85,8 @@ def main():
         # the same step (forward, backward, optimizer, clamp) as ONE hipGraph on static input buffers (train.GraphedTrainStep):
         # no op of it synchronises with the host, so what remains is the GPU time of the unfused kernels
         from centerclip_amd.train import GraphedTrainStep
-        gopt = BertAdam(prep_optim_params_groups(targs, model, coef_lr=1e-3), lr=targs.lr, warmup=0.1, t_total=100 * a.steps,
-                        schedule='warmup_cosine', b1=0.9, b2=0.98, e=1e-6, max_grad_norm=1.0, capturable=True)
-        stepper = GraphedTrainStep(model, gopt)
+        gopt, gsched = make_opt(capturable=True)
+        stepper = GraphedTrainStep(model, gopt, scheduler=gsched, clip_grad_norm=targs.clip_grad_norm)
         batch = next(iter(loader))
         gloss = stepper(batch)
         for _ in range(3):
@@ -80,9 +97,56 @@ def main():
             gloss = stepper(batch)
         torch.cuda.synchronize()
         ms = (time.time() - t0) / 10 * 1e3
-        print("captured step: %.1f ms = %.0f clips/s (loss %.4f)" % (ms, a.batch / ms * 1e3, float(gloss)))
+        print("captured step (%s): %.1f ms = %.0f clips/s (loss %.4f)" % (a.optim, ms, a.batch / ms * 1e3, float(gloss)))
+    if a.optim_timing and rank == 0:
+        optimizer_timing(model, device)
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def optimizer_timing(model, device, reps=20):
+    """The optimizer step alone over the model's parameters (fp32 master weights, random gradients), each captured into a
+    hipGraph and replayed (no host time inside the measurement), median of `reps` by device events: HIP AdamW.step, HIP
+    AdamW.clip_and_step, torch.optim.AdamW(fused=True).step alone and after torch.nn.utils.clip_grad_norm_."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    n = sum(p.numel() for p in params)
+    for p in params:
+        p.grad = torch.randn_like(p) * 1e-3
+    hp = dict(lr=1e-7, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.2)
+    ours = AdamW(params, capturable=True, **hp)
+    fused = torch.optim.AdamW(params, fused=True, capturable=True, **hp)
+
+    def timed(fn):
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):                          # eager warm-up (staging buffers, torch's state)
+            fn()
+            fn()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            fn()
+        g.replay()
+        ts = []
+        for _ in range(reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return sorted(ts)[len(ts) // 2]
+    t_step = timed(ours.step)
+    t_clip = timed(lambda: ours.clip_and_step(1.0))
+    t_torch_step = timed(fused.step)
+    t_torch = timed(lambda: (torch.nn.utils.clip_grad_norm_(params, 1.0), fused.step()))
+    gb = 28.0 * n / 1e9                                     # p, m, v read + written, g read (fp32)
+    print("optimizer over %d tensors, %.1f M parameters (%.2f GB per AdamW step), captured + replayed:" % (len(params), n / 1e6, gb))
+    print("  HIP AdamW.step               %.3f ms  (%.2f TB/s)" % (t_step, gb / t_step))
+    print("  HIP AdamW.clip_and_step      %.3f ms" % t_clip)
+    print("  torch AdamW(fused=True).step %.3f ms  (%.2f TB/s)" % (t_torch_step, gb / t_torch_step))
+    print("  torch clip_grad_norm_ + torch AdamW(fused=True).step %.3f ms" % t_torch)
 
 
 if __name__ == "__main__":

@@ -768,6 +768,51 @@ int cc_bertadam_multi_large_f32(const void* items_dev, int32_t count, int32_t to
                                 float b1, float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes, void* stream);
 
 /* ==========================================================================================
+ * AdamW (torch.optim.AdamW, the optimizer main.py:168-175 builds for --optim AdamW) and global gradient clipping
+ * (torch.nn.utils.clip_grad_norm_, main.py:316-333), multi-tensor.  csrc/adamw.hip.
+ *
+ * One table of `count` cc_adamw_item records in device memory drives every entry point below.  Records are ordered, blk0 is
+ * the running sum of blocks = cc_adamw_blocks(n), total_blocks = the sum of all blocks; each workgroup finds its tensor by
+ * bisection over blk0.  The records hold device pointers: the caller keeps them valid until the launches have run
+ * (centerclip_amd.train stages the table through pinned memory).  All tensors fp32; float4 access where all of a record's
+ * pointers are 16-byte aligned, a scalar tail for n % 4 != 0 (and for unaligned views).
+ *
+ * Arithmetic (per element, compiled WITHOUT fp contraction: every operation rounds on its own, in this order):
+ *     g *= coef (only with coef_dev; the clipped g is written back)
+ *     p = p * decay
+ *     m = m + omb1 * (g - m)   (omb1 >= 0.5: g - (g - m) * (1 - omb1)) - torch's lerp_(g, 1 - b1), i.e. b1 m + (1 - b1) g
+ *     v = b2 * v + (omb2 * g) * g
+ *     p = p - step_size * (m / (sqrt(v) / bc2_sqrt + eps))
+ * with the per-class scalars (cc_adamw_scalars, index scalar_index) computed on the host in double and rounded to float:
+ * decay = 1 - lr wd, omb1 = 1 - b1, omb2 = 1 - b2, step_size = lr / (1 - b1^t), bc2_sqrt = sqrt(1 - b2^t), t = the step
+ * count after this step.  The elements are independent, so a launch over many tensors gives the bits of one launch per tensor.
+ * ========================================================================================== */
+typedef struct cc_adamw_item {
+    float* param; float* grad; float* exp_avg; float* exp_avg_sq;
+    int64_t n;
+    int32_t blk0, blocks;
+    int32_t scalar_index;                                      /* into the scalars_dev array */
+    int32_t reserved;
+} cc_adamw_item;                                               /* 56 bytes */
+typedef struct cc_adamw_scalars {
+    float decay, beta1, one_minus_beta1, beta2, one_minus_beta2, step_size, bc2_sqrt, eps;
+} cc_adamw_scalars;                                            /* 32 bytes */
+int32_t cc_adamw_blocks(int64_t n);
+/* One AdamW step of every record.  coef_dev (may be null): a device float the gradients are multiplied by first (the clip
+ * coefficient of cc_grad_clip_coef_f32) - bit for bit cc_grad_scale_f32 followed by the step without it. */
+int cc_adamw_multi_f32(const void* items_dev, int32_t count, int32_t total_blocks, const void* scalars_dev, const float* coef_dev,
+                       void* stream);
+/* Global L2 norm of the records' gradients: cc_grad_norm_partials_f32 writes one fp64 sum of squares per workgroup into ws
+ * (>= cc_grad_norm_workspace_bytes(total_blocks)); cc_grad_clip_coef_f32 adds them in a fixed order (no atomics: the same bits
+ * on every run) and writes norm_coef[0] = ||g|| and norm_coef[1] = min(1, max_norm / (||g|| + 1e-6)) in fp32.  No host
+ * synchronisation: both can be captured into a hipGraph. */
+size_t cc_grad_norm_workspace_bytes(int32_t total_blocks);
+int cc_grad_norm_partials_f32(const void* items_dev, int32_t count, int32_t total_blocks, void* ws, size_t ws_bytes, void* stream);
+int cc_grad_clip_coef_f32(const void* ws, int32_t total_blocks, float max_norm, float* norm_coef, void* stream);
+/* g *= *coef_dev for every record's gradient (the in-place scaling of clip_grad_norm_). */
+int cc_grad_scale_f32(const void* items_dev, int32_t count, int32_t total_blocks, const float* coef_dev, void* stream);
+
+/* ==========================================================================================
  * Diagnostics (not on the product path; process-wide state, not thread-safe).
  * While armed, every launch of the tiled GEMM kernel is issued with a start / stop event pair that receives the dispatch's
  * own begin / end timestamps (what rocprofv3 --kernel-trace reads), so a kernel symbol can be timed IN SITU, inside an
