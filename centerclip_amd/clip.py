@@ -137,8 +137,14 @@ class ResidualAttentionBlock(nn.Module):
         h = (xin if res_x is None else res_x.float().contiguous().view(M, W)).clone()
         qkv = ops.linear_ln_f16(h16, w["in_w"], w["in_c1"], w["in_c2"], st, 1, eps=self.ln_1.eps)
         att = ops.attention_f16(qkv, N, Lq, self.n_head, causal=self.attn_mask is not None, seq_rows=1, tok_rows=N)
-        h16, st1, slots1, _ = ops.linear_resid_stats_f16(att, w["out_w"], w["out_b"], h, shift_in=sh,
-                                                         stats_in=st.view(M, 1, 2))
+        h16, st1, slots1, sh1 = ops.linear_resid_stats_f16(att, w["out_w"], w["out_b"], h, shift_in=sh,
+                                                           stats_in=st.view(M, 1, 2))
+        tc = self.tokencluster_inter
+        if tc is not None and tc.algorithm == 'token_shift':
+            # clip.py:246-248: x = S(x) again before ln_2 - the CLS rows (rows 0..N-1 of the LND rows) in place, with the
+            # fp16 copy and statistics ln_2 reads
+            torch.ops.centerclip.token_shift_rows(h, N, 1, N, Lq, tc.original_frame, tc.shift_fold_div, T.SHIFT_MODES['token_shift'],
+                                                  h16, st1, slots1, sh1)
         u = ops.linear_ln_f16(h16, w["fc_w"], w["fc_c1"], w["fc_c2"], st1, slots1, gelu=True, eps=self.ln_2.eps)
         ops.linear_f16(u, w["proj_w"], w["proj_b"], "f32_resid", out=h)
         return (h.view(Lq, N, W).type(x.dtype), video_frame, cluster_loss)
@@ -272,7 +278,14 @@ class VisualTransformer(nn.Module):
         dev = self.proj.device
         for i, blk in enumerate(self.transformer.resblocks):
             tc = blk.tokencluster_inter
-            if tc is not None:
+            if tc is not None and tc.is_shift:
+                # frames and tokens kept; encode() runs shift plans with T = original_frame frames per "clip" (the shift
+                # segments the batch's frames in groups of original_frame, whatever the caller's video_frame)
+                m.cluster_frames[i], m.cluster_tokens[i] = tc.original_frame, tokens
+                variants[i], keep = tc.variant(tokens, dev)
+                pk.keep.extend(keep)
+                any_variant = True
+            elif tc is not None:
                 m.cluster_frames[i], m.cluster_tokens[i] = tc.after_block_frames, tc.cluster_num
                 if tc.algorithm == 'pooling' and tc.cluster_num != tokens:
                     raise ValueError("'pooling' keeps the token count: cluster_num_blocks[%d] must be %d" % (i, tokens))
@@ -305,7 +318,7 @@ class VisualTransformer(nn.Module):
         for blk in self.transformer.resblocks:
             tc = blk.tokencluster_inter
             if tc is not None and tc.algorithm in ('kmediods++', 'spectral'):
-                med = (tc.after_block_frames, tc.cluster_num)
+                med = (tc.after_block_frames, tc.cluster_num)         # (shift blocks report no ids)
         return frames, ltok, med
 
     def final_shape(self, video_frame):
@@ -313,9 +326,34 @@ class VisualTransformer(nn.Module):
         frames, tokens = video_frame, (self.input_resolution // self.patch_size) ** 2
         for blk in self.transformer.resblocks:
             tc = blk.tokencluster_inter
-            if tc is not None:
+            if tc is not None and not tc.is_shift:             # the shift algorithms keep frames and tokens
                 frames, tokens = tc.after_block_frames, tc.cluster_num
         return frames, tokens + 1
+
+    def shift_segment(self):
+        """original_frame of the tower's shift modules (temporal_shift / token_shift), or None."""
+        for blk in self.transformer.resblocks:
+            tc = blk.tokencluster_inter
+            if tc is not None and tc.is_shift:
+                return tc.original_frame
+        return None
+
+    def frames_per_call(self, BT, video_frame):
+        """T the fused encoder runs with for BT frames: video_frame ('3d' patches, cluster plans), 1 (plain towers) or, for
+        shift plans, original_frame - the shift segments the batch's frames in groups of original_frame (shift.py:23)."""
+        T_ = video_frame if video_frame and video_frame > 0 else 1
+        seg = self.shift_segment()
+        if seg is not None:
+            assert video_frame and video_frame > 0, "cluster_algo temporal_shift / token_shift needs video_frame (shift.py:23)"
+            assert BT % seg == 0, "%d frames are not a multiple of original_frame %d" % (BT, seg)
+            if self.linear_patch == '3d' and video_frame != seg:
+                raise NotImplementedError("linear_patch='3d' with a shift module needs video_frame == original_frame")
+            return seg
+        if self.linear_patch == '3d':
+            assert video_frame and video_frame > 0, "linear_patch='3d' needs video_frame (clip.py:307)"
+        elif not any(b.tokencluster_inter is not None for b in self.transformer.resblocks):
+            T_ = 1
+        return T_
 
     def encode(self, x, video_frame=-1, want_hidden=False, want_medoids=False, forced_medoids=None):
         """[B*T, 3, H, W] -> (features [B*T_final, output_dim], hidden [B*T_final, L, W] | None).  With want_medoids the
@@ -325,12 +363,8 @@ class VisualTransformer(nn.Module):
             x = x.float()
         x = x.contiguous()
         BT = x.shape[0]
-        T_ = video_frame if video_frame and video_frame > 0 else 1
         has_cluster = any(b.tokencluster_inter is not None for b in self.transformer.resblocks)
-        if self.linear_patch == '3d':
-            assert video_frame and video_frame > 0, "linear_patch='3d' needs video_frame (clip.py:307)"
-        elif not has_cluster:
-            T_ = 1
+        T_ = self.frames_per_call(BT, video_frame)
         assert BT % T_ == 0
         if forced_medoids is not None:
             # one id tensor [B * T_new, K] per cluster block (a list / tuple for plans with several blocks): back to back
@@ -468,11 +502,7 @@ class CLIP(nn.Module):
             image = image.float()
         image = image.contiguous()
         ids = text.to(torch.long).contiguous()
-        T_ = video_frame if video_frame and video_frame > 0 else 1
-        if vis.linear_patch == '3d':
-            assert video_frame and video_frame > 0, "linear_patch='3d' needs video_frame (clip.py:307)"
-        elif not any(b.tokencluster_inter is not None for b in vis.transformer.resblocks):
-            T_ = 1
+        T_ = vis.frames_per_call(image.shape[0], video_frame)
         B = image.shape[0] // T_
         forced = getattr(vis, "forced_medoids", None)       # test hook ("given identical medoid sets")
         keep = getattr(vis, "keep_medoids", False)

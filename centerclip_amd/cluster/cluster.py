@@ -1,12 +1,15 @@
 """Mirror of modules/cluster/cluster.py: get_cluster_inter (:15-63) and TokenClusterInter (:66-352) for the
 algorithms 'kmediods++' and 'spectral' (aggregation None or mean, cluster_embedding, adaptive_cls), 'pooling' and
-'sparse_sampling' (eval: fixed ids; training: the reference's random ids), mean_residual.  Differentiable with respect to x, cluster_embed and cls_multiplier
-(torch.ops.centerclip.token_cluster_train / token_cluster_backward, cc_token_cluster_backward_f32)."""
+'sparse_sampling' (eval: fixed ids; training: the reference's random ids), mean_residual.  Differentiable with respect to x,
+cluster_embed and cls_multiplier (torch.ops.centerclip.token_cluster_train / token_cluster_backward,
+cc_token_cluster_backward_f32).  The shift algorithms 'temporal_shift' / 'token_shift' (cluster.py:343-347) are built by
+shift.TokenShiftInter, which get_cluster_inter returns for them."""
 import numpy as np
 import torch
 
 from .. import _lib as L
 from .. import torch_ops  # noqa: F401  (registers torch.ops.centerclip)
+from .shift import SHIFT_ALGORITHMS, TokenShiftInter
 
 
 def get_cluster_inter(width, block_id, args=None):
@@ -22,23 +25,25 @@ def get_cluster_inter(width, block_id, args=None):
         (before_frames > after_frames or before_cluster_num > cluster_num)
     if not fires:
         return None
-    return TokenClusterInter(algorithm=args.cluster_algo, block_id=block_id,
-                             before_cluster_num=before_cluster_num, cluster_num=cluster_num,
-                             before_block_frames=before_frames, after_block_frames=after_frames,
-                             original_frame=args.max_frames, distance=args.cluster_distance,
-                             threshold=args.cluster_threshold, iter_limit=args.cluster_iter_limit,
-                             id_sort=True, norm_p=args.minkowski_norm_p,
-                             aggregation=getattr(args, 'aggregation', None),
-                             split_size=4 if args.pretrained_clip_name == 'ViT-B/16' else 16,
-                             cluster_embedding=getattr(args, 'cluster_embedding', False),
-                             cluster_frame_embedding=getattr(args, 'cluster_frame_embedding', False),
-                             adaptive_cls=False,          # hard-coded in the reference too (cluster.py:59)
-                             spectral_sigma=getattr(args, 'spectral_sigma', 2.0),
-                             spectral_graph=getattr(args, 'spectral_graph', 'HeatKernel'),
-                             spectral_knn_k=getattr(args, 'spectral_knn_k', 1),
-                             spectral_spatial_temporal_graph=getattr(args, 'spectral_spg', 0),
-                             svd_correct_sign=getattr(args, 'svd_correct_sign', 1),
-                             transformer_width=width, pre_norm=getattr(args, 'pre_norm', False))
+    # the shift algorithms keep frames and tokens and share nothing else with the clustering: a module of their own
+    cls = TokenShiftInter if args.cluster_algo in SHIFT_ALGORITHMS else TokenClusterInter
+    return cls(algorithm=args.cluster_algo, block_id=block_id,
+               before_cluster_num=before_cluster_num, cluster_num=cluster_num,
+               before_block_frames=before_frames, after_block_frames=after_frames,
+               original_frame=args.max_frames, distance=args.cluster_distance,
+               threshold=args.cluster_threshold, iter_limit=args.cluster_iter_limit,
+               id_sort=True, norm_p=args.minkowski_norm_p,
+               aggregation=getattr(args, 'aggregation', None),
+               split_size=4 if args.pretrained_clip_name == 'ViT-B/16' else 16,
+               cluster_embedding=getattr(args, 'cluster_embedding', False),
+               cluster_frame_embedding=getattr(args, 'cluster_frame_embedding', False),
+               adaptive_cls=False,          # hard-coded in the reference too (cluster.py:59)
+               spectral_sigma=getattr(args, 'spectral_sigma', 2.0),
+               spectral_graph=getattr(args, 'spectral_graph', 'HeatKernel'),
+               spectral_knn_k=getattr(args, 'spectral_knn_k', 1),
+               spectral_spatial_temporal_graph=getattr(args, 'spectral_spg', 0),
+               svd_correct_sign=getattr(args, 'svd_correct_sign', 1),
+               transformer_width=width, pre_norm=getattr(args, 'pre_norm', False))
 
 
 class _GatherGiven(torch.autograd.Function):
@@ -73,8 +78,10 @@ class TokenClusterInter(torch.nn.Module):
     batched Jacobi eigensolver, k-medoids on the embedding - all on the device, cluster/spectral.py), the rest is shared.
     'sparse_sampling' in training mode draws the reference's random ids (same NumPy calls, per segment).  mean_residual
     (not reachable from the reference's arguments) is built for the module / block-level forwards.  The shift algorithms
-    raise NotImplementedError at construction.
+    raise NotImplementedError here: shift.TokenShiftInter builds them (get_cluster_inter returns it).
     """
+
+    is_shift = False
 
     def __init__(self, algorithm='kmediods++', block_id=1, before_cluster_num=49, cluster_num=49,
                  before_block_frames=12, after_block_frames=12, original_frame=12, distance='euclidean',
@@ -85,9 +92,9 @@ class TokenClusterInter(torch.nn.Module):
                  svd_correct_sign=1, pre_norm=False):
         super().__init__()
         assert algorithm in ['kmediods++', 'pooling', 'sparse_sampling', 'spectral', 'temporal_shift', 'token_shift']
-        if algorithm not in ('kmediods++', 'pooling', 'sparse_sampling', 'spectral'):
-            raise NotImplementedError("centerclip_amd builds cluster_algo 'kmediods++', 'spectral', 'pooling' and "
-                                      "'sparse_sampling' (got %r)" % algorithm)
+        if algorithm in SHIFT_ALGORITHMS:
+            raise NotImplementedError("TokenClusterInter builds the clustering algorithms; cluster_algo %r is built by "
+                                      "centerclip_amd.cluster.TokenShiftInter (get_cluster_inter returns it)" % algorithm)
         kmed = algorithm in ('kmediods++', 'spectral')                            # cluster.py:240 (shared branch)
         self.cluster_embedding = bool(cluster_embedding) if kmed else False      # cluster.py:154-156
         self.adaptive_cls = bool(adaptive_cls) if kmed else False

@@ -11,6 +11,10 @@
 
 namespace {
 
+bool is_shift(const cc_cluster_variant* var) {
+    return var && (var->algorithm == CC_CLUSTER_TEMPORAL_SHIFT || var->algorithm == CC_CLUSTER_TOKEN_SHIFT);
+}
+
 struct Carver {
     char* base;
     size_t off = 0;
@@ -60,7 +64,7 @@ VitWs carve_vit(const cc_vit_model* m, int B, int T, void* ws) {
     size_t cb = 0;
     int frames = T, tokens = n;
     for (int i = 0; i < m->layers; ++i) {
-        if (m->cluster_tokens[i] > 0) {
+        if (m->cluster_tokens[i] > 0 && !is_shift(m->cluster_variants ? &m->cluster_variants[i] : nullptr)) {
             const int Tn = m->cluster_frames[i];
             if (Tn > 0 && frames % Tn == 0) {
                 size_t need = cc_cluster_workspace_bytes(B * Tn, (frames / Tn) * tokens, W, m->cluster_pre_norm);
@@ -98,6 +102,9 @@ struct BlockCtx {          // one tower's activations for the current block
     // m -> sel_map ? sel_map[m] : m * sel_step), so everything after the attention runs on those rows in place
     int sel_rows, sel_step;
     const int* sel_map;
+    // token_shift (clip.py:246-248): the CLS rows are shifted again between the out_proj residual and ln_2 - mode
+    // CC_CLUSTER_TOKEN_SHIFT, segment, fold divisor; mid_shift 0 = none
+    int mid_shift, mid_seg, mid_div;
 };
 
 // One ResidualAttentionBlock for up to two towers at once (modules/clip.py:240,251).  Every phase is
@@ -205,6 +212,14 @@ int run_block_pair(const cc_block_weights* w0, BlockCtx* c0, const cc_block_weig
         if (rc) return rc;
         c0->slots1 = slots[0];
         if (c1) c1->slots1 = slots[1];
+    }
+    // ---- token_shift: x = S(x) on the CLS rows (the rows a last block with sel_rows computed), + their fp16 copy and
+    // statistics for ln_2 in the slot layout out_proj left
+    for (BlockCtx* c : {c0, c1}) {
+        if (!c || !c->mid_shift) continue;
+        rc = cc_token_shift_rows_f32(c->h, 1, c->L, c->nseq, c->L, c->W, c->mid_seg, c->mid_div, c->mid_shift, c->h16, c->st1,
+                                     c->slots1, c->sh1, st);
+        if (rc) return rc;
     }
     // ---- u = QuickGELU(c_fc(ln_2(x)))   [LayerNorm folded]
     {
@@ -363,7 +378,23 @@ int encode_towers(const cc_vit_model* vm, const cc_frames* video, int B, int T, 
     for (int i = 0; i < vl || ti < tl; ++i) {
         const bool hv = i < vl;
         if (hv) {
-            if (vm->cluster_tokens[i] > 0) {        // token cluster before the attention of this block (clip.py:236-242)
+            const cc_cluster_variant* shv =
+                vm->cluster_tokens[i] > 0 && vm->cluster_variants && is_shift(&vm->cluster_variants[i]) ? &vm->cluster_variants[i]
+                                                                                                        : nullptr;
+            cv.mid_shift = 0;
+            if (shv) {                              // temporal / token shift before ln_1 (clip.py:236-242): frames and tokens stay
+                if (vm->cluster_frames[i] != frames || vm->cluster_tokens[i] != tokens) return CC_ERR_INVALID;
+                if (shv->shift_segment <= 0 || (B * frames) % shv->shift_segment || shv->shift_fold_div <= 0)
+                    return CC_ERR_INVALID;
+                // temporal_shift rewrites every row's statistics (one slot); token_shift the CLS rows' in the current layout
+                const bool temporal = shv->algorithm == CC_CLUSTER_TEMPORAL_SHIFT;
+                rc = cc_token_shift_rows_f32(h, 1, tokens + 1, B * frames, tokens + 1, W, shv->shift_segment,
+                                             shv->shift_fold_div, shv->algorithm, v.h16, v.st0, temporal ? 1 : cv.slots0, v.sh0,
+                                             st);
+                if (rc) return rc;
+                if (temporal) cv.slots0 = 1;
+                else cv.mid_shift = CC_CLUSTER_TOKEN_SHIFT, cv.mid_seg = shv->shift_segment, cv.mid_div = shv->shift_fold_div;
+            } else if (vm->cluster_tokens[i] > 0) {        // token cluster before the attention of this block (clip.py:236-242)
                 const int Tn = vm->cluster_frames[i], K = vm->cluster_tokens[i];
                 if (Tn <= 0 || frames % Tn) return CC_ERR_INVALID;
                 const cc_cluster_variant* var = vm->cluster_variants ? &vm->cluster_variants[i] : nullptr;
@@ -460,7 +491,8 @@ int64_t cc_vit_forced_medoids_count(const cc_vit_model* m, int32_t B) {
     if (!m || B <= 0 || m->layers < 0 || m->layers > CC_MAX_LAYERS) return CC_ERR_INVALID;
     int64_t n = 0;
     for (int i = 0; i < m->layers; ++i)
-        if (m->cluster_tokens[i] > 0) n += (int64_t)B * m->cluster_frames[i] * m->cluster_tokens[i];
+        if (m->cluster_tokens[i] > 0 && !is_shift(m->cluster_variants ? &m->cluster_variants[i] : nullptr))
+            n += (int64_t)B * m->cluster_frames[i] * m->cluster_tokens[i];
     return n;
 }
 

@@ -437,6 +437,43 @@ def _token_cluster_bwd(ctx, grad_out, _gmed, _gassign):
 token_cluster_train.register_autograd(_token_cluster_bwd, setup_context=_token_cluster_setup)
 
 
+SHIFT_MODES = {'temporal_shift': 4, 'token_shift': 5}      # CC_CLUSTER_TEMPORAL_SHIFT / CC_CLUSTER_TOKEN_SHIFT
+
+
+@custom_op(NS + "::token_shift", mutates_args=(), device_types="cuda")
+def token_shift(x: torch.Tensor, frame_major: bool, segment: int, fold_div: int, mode: int, adjoint: bool) -> torch.Tensor:
+    """temporal_shift_wo_cls / token_shift (modules/cluster/shift.py) of x [L, F, W] (LND) or [F, L, W] (frame_major) over
+    segments of ``segment`` consecutive frames; adjoint=True applies the transpose (the backward).  Bit exact."""
+    x = x.contiguous()
+    F, Lt, W, ts, fs = _cluster_strides(x.shape, frame_major)
+    out = torch.empty_like(x)
+    L.check(L.lib().cc_token_shift_f32(L.ptr(x), ts, fs, F, Lt, W, int(segment), int(fold_div), int(mode), int(bool(adjoint)),
+                                       L.ptr(out), ts, fs, _st(x)), "cc_token_shift_f32")
+    return out
+
+
+@token_shift.register_fake
+def _(x, frame_major, segment, fold_div, mode, adjoint):
+    return torch.empty_like(x)
+
+
+@custom_op(NS + "::token_shift_rows", mutates_args=("h", "h16", "stats", "shift"), device_types="cuda")
+def token_shift_rows(h: torch.Tensor, tok_rows: int, frame_rows: int, F: int, L_tok: int, segment: int, fold_div: int,
+                     mode: int, h16: torch.Tensor, stats: torch.Tensor, slots: int, shift: torch.Tensor) -> None:
+    """The shift in place on the contiguous fp32 rows h [M, W] (row of frame f, token j = f * frame_rows + j * tok_rows), with
+    the fp16 copy h16, the statistics (slot 0 of stats [M, slots, 2], zeros in the others) and the centre ``shift`` [M] of
+    every row it rewrites (cc_token_shift_rows_f32: what the next LayerNorm-folded GEMM reads)."""
+    M, W = h.shape
+    L.check(L.lib().cc_token_shift_rows_f32(L.ptr(h), int(tok_rows), int(frame_rows), int(F), int(L_tok), W, int(segment),
+                                            int(fold_div), int(mode), L.ptr(h16), L.ptr(stats), int(slots), L.ptr(shift), _st(h)),
+            "cc_token_shift_rows_f32")
+
+
+@token_shift_rows.register_fake
+def _(h, tok_rows, frame_rows, F, L_tok, segment, fold_div, mode, h16, stats, slots, shift):
+    return None
+
+
 @custom_op(NS + "::batch_kmedoids", mutates_args=(), device_types="cuda")
 def batch_kmedoids(x: torch.Tensor, K: int, metric: int, norm_p: float, threshold: float, iter_limit: int, id_sort: bool,
                    split_size: int, pre_norm: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:

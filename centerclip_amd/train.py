@@ -196,8 +196,17 @@ def _grad_linear(dy32, x16, w16_t, need_dx=True, amax=None, need_dw=True):
     return dx, dw, db
 
 
-def block_forward_train(block, x_lnd):
-    """-> (z [L, N, W] fp32, saved dict).  ``block``: a centerclip_amd.clip.ResidualAttentionBlock without a cluster module."""
+def _token_shift_rows(y, N, Lt, mid_shift, adjoint):
+    """token_shift (or its transpose) of the frame-major rows y [N * Lt, W]: the CLS rows, segments of mid_shift[0] frames."""
+    seg, div = mid_shift
+    W = y.shape[1]
+    return torch.ops.centerclip.token_shift(y.view(N, Lt, W), True, seg, div, 5, adjoint).view(N * Lt, W)
+
+
+def block_forward_train(block, x_lnd, mid_shift=None):
+    """-> (z [L, N, W] fp32, saved dict).  ``block``: a centerclip_amd.clip.ResidualAttentionBlock without a cluster module.
+    ``mid_shift`` (segment, fold_div): token_shift's second shift between the attention residual and ln_2 (clip.py:246-248),
+    y' = S(y); None (default): the plain block."""
     if block.tokencluster_inter is not None:
         raise NotImplementedError("block backward: blocks with a token-cluster module are not covered by this slice")
     L.require_device(x_lnd)
@@ -212,13 +221,16 @@ def block_forward_train(block, x_lnd):
     qkv = ops.linear_f16(n1, wq[0], f32(block.attn.in_proj_bias), "f16")
     att = ops.attention_f16(qkv, N, Lt, block.n_head, causal=causal)
     y = _linear_resid(att, wo[0], f32(block.attn.out_proj.bias), x)           # x + out_proj(att): x itself is kept for the backward
+    if mid_shift is not None:
+        y = _token_shift_rows(y, N, Lt, mid_shift, False)                      # y' = S(y): what ln_2 and the residual read
     n2 = ops.layernorm(y, f32(block.ln_2.weight), f32(block.ln_2.bias), eps=block.ln_2.eps, out_f16=True)
     u_pre = ops.linear_f16(n2, wf[0], f32(block.mlp["c_fc"].bias), "f16")
     u = torch.empty_like(u_pre)
     _check(L.lib().cc_quick_gelu_f16(L.ptr(u_pre), L.ptr(u), u.numel(), _st(u)), "cc_quick_gelu_f16")
     z = _linear_resid(u, wp[0], f32(block.mlp["c_proj"].bias), y)
     wt = dict(in_proj=wq[1], out_proj=wo[1], c_fc=wf[1], c_proj=wp[1])                  # W^T of the same read, for the dgrads
-    saved = dict(x=x, n1=n1, qkv=qkv, att=att, y=y, n2=n2, u_pre=u_pre, u=u, shape=(Lt, N, W), causal=causal, wt=wt)
+    saved = dict(x=x, n1=n1, qkv=qkv, att=att, y=y, n2=n2, u_pre=u_pre, u=u, shape=(Lt, N, W), causal=causal, wt=wt,
+                 mid_shift=mid_shift)
     # (a VIEW of the frame-major rows: the next block's permute + contiguous then costs nothing - a chain of plain blocks never
     # copies its activations between the two layouts)
     return z.view(N, Lt, W).permute(1, 0, 2), saved
@@ -248,6 +260,10 @@ def block_backward(block, saved, dz_lnd, need=None):
     # u_pre = c_fc(ln_2(y))
     dn2, g["mlp.c_fc.weight"], g["mlp.c_fc.bias"] = _grad_linear(du_pre, saved["n2"], f16t(block.mlp["c_fc"].weight, "c_fc"), amax=am[0], need_dw=nw("mlp.c_fc.weight"))
     dy, g["ln_2.weight"], g["ln_2.bias"] = _ln_backward(saved["y"], f32(block.ln_2.weight), dn2, dz, eps=block.ln_2.eps, amax=am[1])   # + the residual branch
+    if saved.get("mid_shift") is not None:
+        # y' = S(y): dy = S^T dy' (the CLS rows' opposite shift; the largest magnitude am[1] the LayerNorm backward published
+        # still bounds it - S^T only moves and zeroes values)
+        dy = _token_shift_rows(dy, N, Lt, saved["mid_shift"], True)
     # y = x + out_proj(att)
     datt, g["attn.out_proj.weight"], g["attn.out_proj.bias"] = _grad_linear(dy, saved["att"], f16t(block.attn.out_proj.weight, "out_proj"), amax=am[1], need_dw=nw("attn.out_proj.weight"))
     dqkv = torch.empty(M, 3 * W, device=dz.device, dtype=torch.float32)
@@ -272,7 +288,7 @@ class ResidualAttentionBlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, block, x, *params):
-        z, saved = block_forward_train(block, x)
+        z, saved = block_forward_train(block, x, mid_shift=getattr(block, "mid_shift", None))
         ctx.block, ctx.saved = block, saved
         # (the activations and the forward-time W^T copies live in ctx.saved, outside autograd's version tracking: remember the
         #  parameters' versions, so that a weight changed in place between forward and backward is an error, as it is for
@@ -349,11 +365,13 @@ def _layernorm(ln, x2d):
 def _blocks(transformer, x_lnd):
     """The resblocks on LND activations; a block's token-cluster module runs in front of it (clip.py:236-242)."""
     for blk in transformer.resblocks:
-        if blk.tokencluster_inter is not None:
-            if getattr(blk.tokencluster_inter, "mean_residual", False):
+        tc = blk.tokencluster_inter
+        if tc is not None:
+            if getattr(tc, "mean_residual", False):
                 raise NotImplementedError("training towers: mean_residual is not built")
-            x_lnd, _ = blk.tokencluster_inter(x_lnd)
-            x_lnd = _plain(blk, x_lnd)
+            x_lnd, _ = tc(x_lnd)
+            # token_shift shifts the CLS rows again behind the attention (clip.py:246-248)
+            x_lnd = _plain(blk, x_lnd, (tc.original_frame, tc.shift_fold_div) if tc.algorithm == 'token_shift' else None)
         else:
             x_lnd = block_apply(blk, x_lnd)
     return x_lnd
@@ -361,18 +379,19 @@ def _blocks(transformer, x_lnd):
 
 class _NoCluster:
     """A view of a block without its cluster module (block_forward_train refuses blocks that carry one: here the module has
-    already run)."""
+    already run); ``mid_shift``: token_shift's second shift, which the block itself applies."""
 
-    def __init__(self, blk):
+    def __init__(self, blk, mid_shift=None):
         self._blk = blk
         self.tokencluster_inter = None
+        self.mid_shift = mid_shift
 
     def __getattr__(self, name):
         return getattr(self._blk, name)
 
 
-def _plain(blk, x_lnd):
-    view = _NoCluster(blk)
+def _plain(blk, x_lnd, mid_shift=None):
+    view = _NoCluster(blk, mid_shift)
     named = dict(blk.named_parameters())
     return ResidualAttentionBlockFunction.apply(view, x_lnd, *[named[k] for k in _PARAM_ORDER])
 

@@ -42,17 +42,29 @@ class SyntheticRetrieval(torch.utils.data.Dataset):
         return self.ids[i], self.mask[i], torch.zeros_like(self.ids[i]), self.video[i], self.vmask[i]
 
 
+def shift_plan(args):
+    """The plan of scripts/activitynet.sh case 04: a shift module in every block (the frame count drops at block 1, the
+    token count at every later block - the shift itself keeps both)."""
+    args.target_frames_blocks = [args.max_frames - 1] * 12
+    args.cluster_num_blocks = [55, 54, 53, 52, 51, 50, 48, 47, 46, 45, 44, 43]
+    return args
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=64)
     ap.add_argument("--batch", type=int, default=16)
-    ap.add_argument("--algo", default="kmediods++", choices=["kmediods++", "spectral", "pooling", "sparse_sampling"])
+    ap.add_argument("--algo", default="kmediods++", choices=["kmediods++", "spectral", "pooling", "sparse_sampling",
+                                                             "token_shift", "temporal_shift"],
+                    help="cluster_algo; the shift algorithms get a module in every block (scripts/activitynet.sh case 04)")
     ap.add_argument("--in-flight", type=int, default=None, help="batches in flight (model instances / streams); default: eval_epoch's own (2 on a GPU)")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
     args = bench.task_config(c)                              # cfg 2: 12 frames -> 3 segments at block 7, K = 49
     args.cluster_algo = a.algo
+    if a.algo in ("token_shift", "temporal_shift"):
+        shift_plan(args)
     vars(args).update(spectral_sigma=2.0, spectral_graph="HeatKernel", spectral_knn_k=1, spectral_spg=0, svd_correct_sign=1)
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), args).to(device).eval()
     loader = torch.utils.data.DataLoader(SyntheticRetrieval(a.clips), batch_size=a.batch, shuffle=False)

@@ -31,6 +31,14 @@ import bench                                                # noqa: E402
 from eval_synthetic import SyntheticRetrieval               # noqa: E402
 
 
+def shift_plan(args):
+    """The plan of scripts/activitynet.sh case 04: a shift module in every block (the frame count drops at block 1, the
+    token count at every later block - the shift itself keeps both)."""
+    args.target_frames_blocks = [args.max_frames - 1] * 12
+    args.cluster_num_blocks = [55, 54, 53, 52, 51, 50, 48, 47, 46, 45, 44, 43]
+    return args
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=4)
@@ -39,6 +47,8 @@ def main():
     ap.add_argument("--b16", type=int, default=0, help="ViT-B/16 instead (cfg-5 shape: 197 tokens per frame, 12 frames -> 4 segments, "
                                                        "K = 100; the attention backward's two-launch form)")
     ap.add_argument("--optim", choices=["BertAdam", "AdamW"], default="BertAdam")
+    ap.add_argument("--algo", default="kmediods++", choices=["kmediods++", "token_shift", "temporal_shift"],
+                    help="cluster_algo; the shift algorithms get a module in every block (scripts/activitynet.sh case 04)")
     ap.add_argument("--optim-timing", type=int, default=0, help="also time the optimizer step alone (AdamW)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -51,6 +61,9 @@ def main():
     if a.b16:
         c = dict(c, name="cfg5-shaped: ViT-B/16", patch=16, T_new=4, K=100)
     args = bench.task_config(c)
+    if a.algo != "kmediods++":
+        args.cluster_algo = a.algo
+        shift_plan(args)
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), args).float().to(device)
     targs = Namespace(lr=1e-7, wd=0.2, new_added_modules=["Cross", "cluster_embed"], gradient_accumulation_steps=1,
                       clip_grad_norm=None, optim=a.optim)

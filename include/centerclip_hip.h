@@ -164,6 +164,8 @@ int cc_token_cluster_f32(const float* x, int64_t in_tok_stride, int64_t in_frame
 #define CC_CLUSTER_POOLING  1
 #define CC_CLUSTER_SPECTRAL 3          /* spectral clustering picks the medoids / the assignment (cluster_algo 'spectral') */
 #define CC_CLUSTER_SPARSE_SAMPLING 2   /* fixed_ids [K]: token_sparse_sampling(K, fd*n, random_shift=False) */
+#define CC_CLUSTER_TEMPORAL_SHIFT 4    /* temporal_shift_wo_cls (shift.py:15-37), see cc_token_shift_f32 */
+#define CC_CLUSTER_TOKEN_SHIFT 5       /* token_shift (shift.py:40-61): the CLS rows only */
 #define CC_AGGREGATE_MEDOID 0
 #define CC_AGGREGATE_MEAN   1
 typedef struct cc_cluster_variant {
@@ -188,7 +190,38 @@ typedef struct cc_cluster_variant {
      * assert).  The module-level entry points return the clustered tokens only; their caller forms the means with
      * algorithm = CC_CLUSTER_POOLING on the same input. */
     int32_t mean_residual;
+    /* CC_CLUSTER_TEMPORAL_SHIFT / CC_CLUSTER_TOKEN_SHIFT - read by the fused encoders: fold = W / shift_fold_div (the
+     * reference's 8), frames shifted within segments of shift_segment consecutive frames of the batch (original_frame =
+     * max_frames).  The block keeps its frame and token counts (cluster_frames[i] / cluster_tokens[i] must equal the incoming
+     * ones); the shift runs in place before ln_1 and, for token_shift, again between the out_proj residual and ln_2
+     * (clip.py:236-248).  Shift blocks take no forced_medoids ids. */
+    int32_t shift_fold_div;
+    int32_t shift_segment;
 } cc_cluster_variant;
+
+/* cluster_algo 'temporal_shift' / 'token_shift' (modules/cluster/shift.py, cluster.py:343-347) on F frames of L tokens
+ * (token 0 = CLS) of width W, element (f, j, c) at f * frame_stride + j * tok_stride + c: within each segment of `segment`
+ * consecutive frames, channels [0, fold) of a shifted row take the next frame's value (zero in the segment's last frame),
+ * channels [fold, 2 fold) the previous frame's (zero in the first), channels >= 2 fold are copied; fold = W / fold_div
+ * (fold 0 = a copy).  mode CC_CLUSTER_TEMPORAL_SHIFT shifts tokens 1..L-1, CC_CLUSTER_TOKEN_SHIFT token 0; the other rows
+ * are copied.  adjoint = 1 applies the transpose (the backward: the two directions swapped, zero fill).  Bit exact.
+ * out == x with the same strides runs in place (only the shifted channels of the shifted rows are read and written);
+ * otherwise out must not overlap x.  Both layouts must be alias free (LND [L, N, W]: tok_stride = N W, frame_stride = W;
+ * frame-major [N, L, W]: tok_stride = W, frame_stride = L W).  CC_ERR_INVALID for F % segment != 0 or bad strides / sizes. */
+int cc_token_shift_f32(const float* x, int64_t tok_stride, int64_t frame_stride, int32_t F, int32_t L, int32_t W,
+                       int32_t segment, int32_t fold_div, int32_t mode, int32_t adjoint, float* out,
+                       int64_t out_tok_stride, int64_t out_frame_stride, void* stream);
+
+/* The forward shift in place on contiguous fp32 rows h [*, W] (row of frame f, token j = f * frame_rows + j * tok_rows),
+ * with what the next LayerNorm-folded GEMM reads for every row it rewrites: h16 [*, W] fp16 = h - c (c = the row mean,
+ * written to shift[row]), stats [row][slots][2] = (sum, sum of squares) of that copy in slot 0 and zeros in the other
+ * slots.  token_shift rewrites the F CLS rows only (the others keep their statistics in any slot layout); temporal_shift
+ * rewrites every row, CLS rows included, so the caller may pass slots = 1.  W % 4 == 0, W <= 1024, slots <= 32,
+ * segment * min(2 fold, W) * 4 bytes <= 64 KiB (else CC_ERR_UNSUPPORTED).  One launch. */
+int cc_token_shift_rows_f32(float* h, int64_t tok_rows, int64_t frame_rows, int32_t F, int32_t L, int32_t W,
+                            int32_t segment, int32_t fold_div, int32_t mode, void* h16, float* stats, int32_t slots,
+                            float* shift, void* stream);
+size_t cc_token_shift_rows_lds_bytes(int32_t segment, int32_t W, int32_t fold_div);
 /* The aggregation step of CC_AGGREGATE_MEAN alone, from a given assignment [T_new*B, fd*n] int64 (values 0..K-1;
  * problem p = s*B + b as everywhere) - the counterpart of cc_token_gather_f32 for cluster means
  * (cluster.py:291-310).  variant may be NULL; only its cluster_embed / cls_multiplier are used. */
@@ -461,6 +494,7 @@ size_t cc_vit_workspace_bytes(const cc_vit_model* m, int32_t B, int32_t T);
 
 /* Number of int64 ids the forced_medoids argument of cc_vit_encode* / cc_clip_encode* must hold for a batch of B clips: the
  * sum over the tower's cluster blocks of B x cluster_frames[i] x cluster_tokens[i] (0: no cluster block, < 0: bad arguments).
+ * Shift blocks (CC_CLUSTER_TEMPORAL_SHIFT / CC_CLUSTER_TOKEN_SHIFT) take no ids and are not counted.
  * The pointer carries no length - a host-side caller checks its buffer against this before the call. */
 int64_t cc_vit_forced_medoids_count(const cc_vit_model* m, int32_t B);
 
