@@ -110,18 +110,28 @@ def bertadam_step64(p, g, m, v, lr_scheduled, b1, b2, e, weight_decay, max_grad_
 
 
 def visual_forward(sd, video, T, cluster_plan=None, cluster_cfg=None, forced_medoids=None, return_hidden=False,
-                   linear_patch='2d', mean_residual=()):
+                   linear_patch='2d', mean_residual=(), native=False, return_medoids=False):
     """VisualTransformer.forward + the ln_post/proj tail of CLIP.encode_image
     (clip.py:304-349,460-469).  video [B*T,3,H,W]; cluster_plan {block_index(0-based): (T_new, K)};
     cluster_cfg dict(distance, threshold, iter_limit, norm_p, split_size, pre_norm[, algorithm, aggregation]).
     forced_medoids {block_index: int64 [T_new*B, K]} replaces the k-medoids result (to compare
     embeddings "given identical medoid sets").  mean_residual: block indices whose cluster module has
     mean_residual set (cluster.py:228-235: residual = the mean over each segment's frames of EVERY token, CLS included; the
-    token count must not change).  Returns features [B*T_final, E] (and the hidden state [B*T_final, L, W])."""
+    token count must not change).  Returns features [B*T_final, E] (and the hidden state [B*T_final, L, W]).
+    return_medoids: also return {block_index: medoid ids [T_new*B, K]} (last item): the selections the default k-medoids
+    blocks made here, and in native mode the forced ones.
+    native: the whole tower in video's dtype and on its device, differentiable with respect to every tensor of sd (a
+    float64 reference of the training backward); the conv1 patch embedding is the equal reshape + GEMM, and every
+    k-medoids block must be given its selection in forced_medoids (the reference selects under no_grad, fast_kmeans.py:13,44:
+    the selection is a constant of the backward).  Only linear_patch '2d' with plain medoid gathers."""
     W = sd["visual.conv1.weight"].shape[0]
     p = sd["visual.conv1.weight"].shape[-1]
     heads = W // 64
     layers = len([k for k in sd if k.startswith("visual.") and k.endswith(".attn.in_proj_weight")])
+    if native:
+        return _visual_forward_native(sd, video, T, cluster_plan or {}, forced_medoids or {}, return_hidden, return_medoids,
+                                      W, p, heads, layers, linear_patch, cluster_cfg, mean_residual)
+    picked_ids = {}
     if linear_patch == '3d':                                                           # clip.py:306-319
         x3 = video.float().reshape(-1, T, video.shape[-3], video.shape[-2], video.shape[-1]).permute(0, 2, 1, 3, 4)
         x3 = F.conv3d(x3, sd["visual.conv2.weight"].float(), stride=(1, p, p), padding=(1, 0, 0)).permute(0, 2, 1, 3, 4)
@@ -157,46 +167,92 @@ def visual_forward(sd, video, T, cluster_plan=None, cluster_cfg=None, forced_med
                                                          c.get("split_size", 16), c.get("pre_norm", False))
             else:
                 c = cluster_cfg or {}
-                x_lnd = co.literal_token_cluster(x_lnd, frames, T_new, K, c.get("distance", "euclidean"),
-                                                 c.get("threshold", 1e-6), c.get("iter_limit", 100),
-                                                 c.get("norm_p", 2.0), c.get("split_size", 16),
-                                                 c.get("pre_norm", False))
+                x_lnd, picked_ids[i], _ = co.literal_token_cluster(x_lnd, frames, T_new, K, c.get("distance", "euclidean"),
+                                                                   c.get("threshold", 1e-6), c.get("iter_limit", 100),
+                                                                   c.get("norm_p", 2.0), c.get("split_size", 16),
+                                                                   c.get("pre_norm", False), return_ids=True)
             x = x_lnd.permute(1, 0, 2).contiguous()
             frames = T_new
         x = resblock(x, sd, "visual.transformer.resblocks.%d." % i, heads, causal=False, res_x=res_x)
     feat = layer_norm(x[:, 0, :], sd["visual.ln_post.weight"], sd["visual.ln_post.bias"]) @ sd["visual.proj"].float()
-    return (feat, x) if return_hidden else feat
+    out = (feat, x) if return_hidden else (feat,)
+    if return_medoids:
+        out = out + (picked_ids,)
+    return out if len(out) > 1 else out[0]
 
 
-def gather_with_medoids(x_lnd, T, T_new, medoids):
+def _visual_forward_native(sd, video, T, cluster_plan, forced_medoids, return_hidden, return_medoids, W, p, heads, layers,
+                           linear_patch, cluster_cfg, mean_residual):
+    """visual_forward(native=True): the same op sequence in video's dtype, on its device."""
+    if linear_patch != '2d' or mean_residual:
+        raise NotImplementedError("native visual_forward: linear_patch '2d' without mean_residual only")
+    c = cluster_cfg or {}
+    if c.get("algorithm", "kmediods++") != "kmediods++" or c.get("aggregation") not in [None, "None"]:
+        raise NotImplementedError("native visual_forward: k-medoids with medoid gathers only")
+    cv = lambda t: t.to(video)
+    F_, g = video.shape[0], video.shape[-1] // p
+    # conv1 (kernel = stride = p, no bias, clip.py:324) as the GEMM over the (c, kh, kw) patch rows it is
+    a = video.reshape(F_, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(F_, g * g, 3 * p * p)
+    x = a @ cv(sd["visual.conv1.weight"]).reshape(W, -1).t()                            # [BT, n, W]
+    cls = cv(sd["visual.class_embedding"]).expand(x.shape[0], 1, W)
+    x = torch.cat([cls, x], dim=1) + cv(sd["visual.positional_embedding"])             # :334-336
+    x = layer_norm(x, sd["visual.ln_pre.weight"], sd["visual.ln_pre.bias"], native=True)
+    frames, picked_ids = T, {}
+    for i in range(layers):
+        if i in cluster_plan:
+            T_new, K = cluster_plan[i]
+            if i not in forced_medoids:
+                raise ValueError("native visual_forward: block %d clusters; give its selection in forced_medoids" % i)
+            med = forced_medoids[i].to(device=video.device, dtype=torch.long)
+            assert tuple(med.shape) == (T_new * (x.shape[0] // frames), K), (tuple(med.shape), T_new, K)
+            x = gather_with_medoids(x.permute(1, 0, 2), frames, T_new, med, native=True).permute(1, 0, 2)
+            picked_ids[i] = med
+            frames = T_new
+        x = resblock(x, sd, "visual.transformer.resblocks.%d." % i, heads, causal=False, native=True)
+    feat = layer_norm(x[:, 0, :], sd["visual.ln_post.weight"], sd["visual.ln_post.bias"], native=True) @ cv(sd["visual.proj"])
+    out = (feat, x) if return_hidden else (feat,)
+    if return_medoids:
+        out = out + (picked_ids,)
+    return out if len(out) > 1 else out[0]
+
+
+def gather_with_medoids(x_lnd, T, T_new, medoids, native=False):
     """The gather / CLS-mean half of TokenClusterInter.forward with given medoid ids
-    (modules/cluster/cluster.py:287-289,303-310)."""
+    (modules/cluster/cluster.py:287-289,303-310).  native: the row index is made on x's device (differentiable either way)."""
     tokens, cls = co.regroup_segments(x_lnd, T, T_new)
     P, _, W = tokens.shape
     B, fd, K = P // T_new, T // T_new, medoids.shape[1]
-    picked = tokens[torch.arange(P).unsqueeze(-1), medoids]
+    rows = torch.arange(P, device=tokens.device) if native else torch.arange(P)
+    picked = tokens[rows.unsqueeze(-1), medoids.to(tokens.device) if native else medoids]
     picked = picked.reshape(T_new, B, K, W).permute(1, 0, 2, 3).reshape(B * T_new, K, W)
     seg_cls = torch.stack([c.mean(dim=1) for c in torch.split(cls, fd, dim=1)], dim=1).reshape(B * T_new, 1, W)
     return torch.cat([seg_cls, picked], dim=1).permute(1, 0, 2).contiguous()
 
 
-def text_forward(sd, ids):
+def text_forward(sd, ids, native=False):
     """CLIP.encode_text (clip.py:471-496): embed + positional, 12 causal blocks, ln_final,
-    text_projection, row at the first argmax of the ids."""
+    text_projection, row at the first argmax of the ids.  native: in the dtype of sd's token embedding and on its device
+    (ids are moved there), differentiable with respect to every tensor of sd."""
     W = sd["ln_final.weight"].shape[0]
     heads = W // 64
     layers = len(set(k.split(".")[2] for k in sd if k.startswith("transformer.resblocks")))
-    x = sd["token_embedding.weight"].float()[ids] + sd["positional_embedding"].float()[:ids.shape[1]]
+    if native:
+        emb = sd["token_embedding.weight"]
+        ids = ids.to(emb.device)
+        x = emb[ids] + sd["positional_embedding"].to(emb)[:ids.shape[1]]
+    else:
+        x = sd["token_embedding.weight"].float()[ids] + sd["positional_embedding"].float()[:ids.shape[1]]
     for i in range(layers):
-        x = resblock(x, sd, "transformer.resblocks.%d." % i, heads, causal=True)
-    x = layer_norm(x, sd["ln_final.weight"], sd["ln_final.bias"]) @ sd["text_projection"].float()
-    return x[torch.arange(x.shape[0]), ids.argmax(dim=-1)]
+        x = resblock(x, sd, "transformer.resblocks.%d." % i, heads, causal=True, native=native)
+    proj = sd["text_projection"].to(x) if native else sd["text_projection"].float()
+    x = layer_norm(x, sd["ln_final.weight"], sd["ln_final.bias"], native=native) @ proj
+    return x[torch.arange(x.shape[0], device=x.device if native else None), ids.argmax(dim=-1)]
 
 
 def video_mask_after_cluster(video_mask, max_frames, final_frames):
     """clip4clip.py:436-447: a segment inherits the mask of its last frame."""
     fd = max_frames // final_frames
-    inds = torch.arange(fd - 1, video_mask.shape[-1], video_mask.shape[-1] // final_frames)
+    inds = torch.arange(fd - 1, video_mask.shape[-1], video_mask.shape[-1] // final_frames, device=video_mask.device)
     return video_mask[:, inds]
 
 
@@ -258,22 +314,53 @@ def clip4clip_train_loss(sd, ids, video, video_mask, max_frames, final_frames, c
     return (cross_en(sim) + cross_en(sim.t())) / 2
 
 
-def contrastive_loss_and_grads(sequence_output, visual_output, video_mask, logit_scale):
-    """The training branch's loss (clip4clip.py:245-262) and torch.autograd's gradients of it with respect to
-    sequence_output, visual_output and logit_scale -> (loss3 [CrossEn(S), CrossEn(S^T), mean], d_seq, d_vis, d_logit_scale)."""
-    seq = sequence_output.detach().clone().float().requires_grad_(True)
-    vis = visual_output.detach().clone().float().requires_grad_(True)
-    ls = torch.tensor(float(logit_scale), requires_grad=True)
-    v = vis / vis.norm(dim=-1, keepdim=True)
-    m = video_mask.to(torch.float).unsqueeze(-1)
-    den = torch.sum(m, dim=1, dtype=torch.float)
+def clip4clip_train_loss_native(sd, ids, video, video_mask, max_frames, final_frames, cluster_plan, forced_medoids=None):
+    """clip4clip_train_loss with native towers (visual_forward / text_forward native=True): in video's dtype and on its
+    device, differentiable with respect to every tensor of sd, logit_scale (sd['logit_scale']) included; each k-medoids
+    block's selection is given in forced_medoids.  ids [B, L], video [B, 1, T, 3, H, W], video_mask [B, 1, T] ->
+    (loss, sequence_output [B, 1, E], visual_output [B, T', E])."""
+    ids = ids.view(-1, ids.shape[-1])
+    T = video.shape[2]
+    v = video.reshape((-1,) + tuple(video.shape[3:]))
+    vmask = video_mask.view(-1, video_mask.shape[-1]).to(video.device)
+    if cluster_plan:
+        vmask = video_mask_after_cluster(vmask, max_frames, final_frames)
+    seq = text_forward(sd, ids, native=True).view(ids.shape[0], 1, -1)
+    vis = visual_forward(sd, v, T, cluster_plan=cluster_plan, forced_medoids=forced_medoids, native=True)
+    vis = vis.view(vmask.shape[0], -1, seq.shape[-1])
+    _, _, loss = contrastive_loss_native(seq, vis, vmask, sd["logit_scale"].to(v))
+    return loss, seq, vis
+
+
+def _cross_en_native(sim):
+    """cross_en in sim's own dtype."""
+    return -torch.diag(F.log_softmax(sim, dim=-1)).mean()
+
+
+def contrastive_loss_native(sequence_output, visual_output, video_mask, logit_scale):
+    """The training branch's loss (clip4clip.py:245-262: the meanP similarity of :357-366, CrossEn both ways) in the
+    features' dtype and on their device, differentiable in the features and in logit_scale (a tensor) ->
+    (CrossEn(S), CrossEn(S^T), their mean)."""
+    v = visual_output / visual_output.norm(dim=-1, keepdim=True)
+    m = video_mask.to(device=v.device, dtype=v.dtype).unsqueeze(-1)
+    den = torch.sum(m, dim=1)
     den = torch.where(den == 0., torch.ones_like(den), den)
     v = torch.sum(v * m, dim=1) / den
     v = v / v.norm(dim=-1, keepdim=True)
-    t = seq.reshape(seq.shape[0], -1)
+    t = sequence_output.reshape(sequence_output.shape[0], -1)
     t = t / t.norm(dim=-1, keepdim=True)
-    sim = ls.exp() * torch.matmul(t, v.t())
-    l1, l2 = cross_en(sim), cross_en(sim.t())
-    loss = (l1 + l2) / 2
+    sim = logit_scale.exp() * torch.matmul(t, v.t())
+    l1, l2 = _cross_en_native(sim), _cross_en_native(sim.t())
+    return l1, l2, (l1 + l2) / 2
+
+
+def contrastive_loss_and_grads(sequence_output, visual_output, video_mask, logit_scale, dtype=torch.float32):
+    """The training branch's loss (clip4clip.py:245-262) and torch.autograd's gradients of it with respect to
+    sequence_output, visual_output and logit_scale, evaluated in dtype on the features' device (float64: the reference of
+    the GPU tests at training batch sizes) -> (loss3 [CrossEn(S), CrossEn(S^T), mean], d_seq, d_vis, d_logit_scale)."""
+    seq = sequence_output.detach().clone().to(dtype).requires_grad_(True)
+    vis = visual_output.detach().clone().to(dtype).requires_grad_(True)
+    ls = torch.tensor(float(logit_scale), dtype=dtype, device=seq.device, requires_grad=True)
+    l1, l2, loss = contrastive_loss_native(seq, vis, video_mask, ls)
     loss.backward()
     return torch.stack([l1.detach(), l2.detach(), loss.detach()]), seq.grad, vis.grad, ls.grad
