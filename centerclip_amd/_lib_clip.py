@@ -121,6 +121,15 @@ def declare(lib):
     lib.cc_attention_backward_workspace_bytes.argtypes = [i32, i32, i32]
     lib.cc_attention_backward_workspace_bytes.restype = sz
     lib.cc_attention_backward_f16.restype = c.c_int
+    lib.cc_key_masked_attention_f16.argtypes = [vp, vp, i32, i32, i32, i32, vp, i64, i64, vp]
+    lib.cc_key_masked_attention_f16.restype = c.c_int
+    lib.cc_key_masked_attention_backward_f16.argtypes = [vp, vp, i64, i64, vp, vp, i32, i32, i32, i32, vp, vp]
+    lib.cc_key_masked_attention_backward_f16.restype = c.c_int
+    lib.cc_seqtransf_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.cc_seqtransf_workspace_bytes.restype = sz
+    lib.cc_seqtransf_forward_f32.argtypes = [vp, vp, i64, i64, vp, c.POINTER(BlockWeights), i32, i32, i32, i32, i32, vp, vp, sz,
+                                             vp]
+    lib.cc_seqtransf_forward_f32.restype = c.c_int
     lib.cc_column_sums_workspace_bytes.argtypes = [i32, i32]
     lib.cc_column_sums_workspace_bytes.restype = sz
     lib.cc_column_sums_f32.argtypes = [vp, i32, i32, vp, vp, sz, vp]

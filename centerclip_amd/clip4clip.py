@@ -6,7 +6,10 @@ get_similarity_logits, _loose_similarity, get_video_mask_after_cluster - same si
 Training mode returns the reference's loss (feature all-gather -> logits -> symmetric CrossEn, clip4clip.py:245-262),
 differentiable with respect to the features and logit_scale; the towers have no backward (encoder backward,
 DDP gradient all-reduce and the optimiser are out of scope).
-Not built: seqTransf / tightTransf heads, weight download.
+sim_header 'seqTransf' (clip4clip.py:335-349): frame_position_embeddings + transformerClip under the reference's names,
+applied to the per-segment features before the pooling (eval: cc_seqtransf_forward_f32 in one enqueue; training: the blocks'
+HIP forward / backward with the key mask, centerclip_amd.train.seq_head_train).
+Not built: tightTransf / seqLSTM (the reference cannot run them either), weight download.
 """
 import torch
 from torch import nn
@@ -14,7 +17,7 @@ from torch import nn
 from . import _lib as L
 from . import ops
 from . import torch_ops as T
-from .clip import build_clip_model, load_clip_state_dict, zero_scalar
+from .clip import Transformer, _Pack, build_clip_model, load_clip_state_dict, zero_scalar
 from . import dist as ccdist
 from .dist import AllGather, PackedAllGather, all_gather
 from .losses import contrastive_loss
@@ -29,8 +32,10 @@ class CLIP4Clip(nn.Module):
         self.sim_header = getattr(task_config, "sim_header", 'meanP')
         if self.linear_patch not in ('2d', '3d'):
             raise ValueError("linear_patch must be '2d' or '3d'")
-        if self.sim_header != "meanP" or not self.loose_type:
-            raise NotImplementedError("only sim_header='meanP' with loose_type is built (all shipped scripts use it)")
+        if self.sim_header not in ("meanP", "seqTransf") or not self.loose_type:
+            # (clip4clip.py:332-333,426-427: the reference raises NotImplementedError for seqLSTM and the tight head too)
+            raise NotImplementedError("only sim_header 'meanP' and 'seqTransf' with loose_type are built (the reference runs no "
+                                      "other head)")
         self.cluster_inter = getattr(task_config, "cluster_inter", 0)
         self.cluster_algo = getattr(task_config, "cluster_algo", None)
         self.deep_cluster = getattr(task_config, "deep_cluster", 0)
@@ -42,11 +47,32 @@ class CLIP4Clip(nn.Module):
                                                        linear_patch=self.linear_patch, cut_top_layer=0,
                                                        load_state_dict=True, is_eval=False,
                                                        video_frames=self.video_frames, args=task_config)
+        if self.sim_header == "seqTransf":
+            if self.pre_visual_pooling:
+                # (the reference would pool first and then index position 512 of the 77-row table)
+                raise ValueError("sim_header='seqTransf' needs the per-segment features: pre_visual_pooling is not supported")
+            cfg = self.clip_config
+            width = cfg['transformer_width']
+            if cfg['embed_dim'] != width:
+                raise ValueError("sim_header='seqTransf': the head runs on the visual features, so embed_dim (%d) must equal "
+                                 "transformer_width (%d)" % (cfg['embed_dim'], width))
+            # clip4clip.py:178,187-192: an embedding of context_length rows and module_cross.Transformer (fp32 parameters)
+            self.frame_position_embeddings = nn.Embedding(cfg['context_length'], width)
+            self.transformerClip = Transformer(width=width, layers=int(getattr(task_config, "cross_num_hidden_layers", 4)),
+                                               heads=cfg['transformer_heads'])
+            for blk in self.transformerClip.resblocks:    # nn.MultiheadAttention's own initialisation of the packed in_proj
+                nn.init.xavier_uniform_(blk.attn.in_proj_weight)
+            self._head_pack = None
 
     @classmethod
     def from_state_dict(cls, clip_state_dict, task_config):
-        """Build from an OpenAI-CLIP style state dict (keys without the 'clip.' prefix)."""
-        return cls(clip_state_dict, task_config)
+        """Build from an OpenAI-CLIP style state dict (keys without the 'clip.' prefix).  seqTransf: the head starts from the
+        reference's initialisation trick (seq_head_init), as from_pretrained does without a fine-tuned head."""
+        model = cls(clip_state_dict, task_config)
+        if model.sim_header == "seqTransf":
+            with torch.no_grad():
+                model.load_state_dict(cls.seq_head_init(clip_state_dict, model.transformerClip.layers), strict=False)
+        return model
 
     def replica(self):
         """A second instance with the same configuration and a copy of the weights, on the same device and in the same mode.
@@ -80,10 +106,77 @@ class CLIP4Clip(nn.Module):
             override["visual.conv2.weight"] = w2
         if override:
             model.clip.load_state_dict(override, strict=False)
+        if model.sim_header == "seqTransf":
+            head = {k: v for k, v in state_dict.items() if k.startswith(("frame_position_embeddings.", "transformerClip."))}
+            if not any(k.startswith("frame_position_embeddings") for k in state_dict):
+                head.update(cls.seq_head_init(clip_state_dict, model.transformerClip.layers))
+            if head:
+                with torch.no_grad():
+                    model.load_state_dict(head, strict=False)
         if getattr(task_config, "temperature_new", 0.0) > 1.0:
             with torch.no_grad():                    # (tracked by the packs' version keys, unlike a .data write)
                 model.clip.logit_scale.fill_(task_config.temperature_new)
         return model
+
+    @staticmethod
+    def seq_head_init(clip_state_dict, layers):
+        """The reference's initialisation trick for the seqTransf head (clip4clip.py:97-113), applied when the fine-tuned
+        state dict has no frame_position_embeddings: the position rows from CLIP's positional_embedding, block i < layers of
+        transformerClip from the text transformer's block i.  -> {name: tensor} under the reference's names."""
+        out = {"frame_position_embeddings.weight": clip_state_dict["positional_embedding"].clone()}
+        for k, v in clip_state_dict.items():
+            if k.startswith("transformer.resblocks.") and int(k.split(".")[2]) < layers:
+                out[k.replace("transformer.", "transformerClip.", 1)] = v.clone()
+        return out
+
+    # ------------------------------------------------------------------ sim_header 'seqTransf' (clip4clip.py:335-349)
+    def _head_weights(self):
+        """fp32 position rows + the 12 tensors per block cc_seqtransf_forward_f32 reads (fp16 GEMM weights), rebuilt when a
+        parameter's version changes (an in-place write under no_grad is seen; a write through .data needs invalidate())."""
+        key = _Pack.signature(self.frame_position_embeddings) + _Pack.signature(self.transformerClip)
+        if self._head_pack is None or self._head_pack[0] != key:
+            f16 = lambda t: t.detach().to(torch.float16).contiguous()
+            f32 = lambda t: t.detach().float().contiguous()
+            ws = []
+            for blk in self.transformerClip.resblocks:
+                ws += [f32(blk.ln_1.weight), f32(blk.ln_1.bias), f16(blk.attn.in_proj_weight), f32(blk.attn.in_proj_bias),
+                       f16(blk.attn.out_proj.weight), f32(blk.attn.out_proj.bias), f32(blk.ln_2.weight), f32(blk.ln_2.bias),
+                       f16(blk.mlp["c_fc"].weight), f32(blk.mlp["c_fc"].bias), f16(blk.mlp["c_proj"].weight),
+                       f32(blk.mlp["c_proj"].bias)]
+            self._head_pack = (key, f32(self.frame_position_embeddings.weight), ws)
+        return self._head_pack[1], self._head_pack[2]
+
+    def _check_head_input(self, visual_output, video_mask):
+        if visual_output.dim() != 3:
+            raise ValueError("sim_header='seqTransf' needs the per-segment features [B, T, D]")
+        T = visual_output.shape[1]
+        if T > self.frame_position_embeddings.num_embeddings:
+            raise ValueError("sim_header='seqTransf': %d segments, the frame position table has %d rows"
+                             % (T, self.frame_position_embeddings.num_embeddings))
+        if tuple(video_mask.shape) != tuple(visual_output.shape[:2]):
+            raise ValueError("sim_header='seqTransf': mask %s for features %s" % (tuple(video_mask.shape),
+                                                                                 tuple(visual_output.shape)))
+
+    def seq_head(self, visual_output, video_mask):
+        """visual_output [B, T, D] + video_mask [B, T] (any strides) -> the head's output [B, T, D] fp32, without gradients
+        (clip4clip.py:335-349: + position rows, transformerClip with the key mask, + visual_output).  meanP: the input."""
+        if self.sim_header != "seqTransf":
+            return visual_output
+        self._check_head_input(visual_output, video_mask)
+        L.require_device(visual_output, video_mask)
+        pos, ws = self._head_weights()
+        return torch.ops.centerclip.seqtransf_forward(visual_output.detach().float().contiguous(), video_mask.to(torch.long),
+                                                      pos, ws, self.transformerClip.heads)
+
+    def _seq_head_any(self, visual_output, video_mask):
+        """The head with gradients when autograd records (training), else seq_head."""
+        if self.sim_header != "seqTransf":
+            return visual_output
+        if torch.is_grad_enabled() and self.training:
+            from . import train as cctrain
+            self._check_head_input(visual_output, video_mask)
+            return cctrain.seq_head_train(self, visual_output, video_mask)
+        return self.seq_head(visual_output, video_mask)
 
     # ------------------------------------------------------------------ forward (clip4clip.py:199-263)
     def forward(self, input_ids=None, token_type_ids=None, attention_mask=None, video=None, video_mask=None,
@@ -131,7 +224,10 @@ class CLIP4Clip(nn.Module):
             # the reference's training branch (clip4clip.py:245-262): features of all ranks -> logits -> symmetric CrossEn.
             # The loss is differentiable with respect to the features and logit_scale (losses.contrastive_loss: forward and
             # gradient in one kernel chain); the features come from the differentiable towers above.
-            seq, vis, vmask = sequence_output.contiguous(), visual_output.contiguous(), video_mask.contiguous()
+            # seqTransf: the head runs on the local batch, before the exchange (clip4clip.py:340-355)
+            seq = sequence_output.contiguous()
+            vis = self._seq_head_any(visual_output, video_mask).contiguous()
+            vmask = video_mask.contiguous()
             if ccdist.world_size() > 1:              # ONE collective for the three tensors, gradient slices of the own shard back
                 vis, vmask, seq = PackedAllGather.apply(vis, vmask, seq)
             # (logit_scale is read on the device: the optimizer changes it every step, and a host copy would be a synchronisation)
@@ -145,6 +241,9 @@ class CLIP4Clip(nn.Module):
         """The multi-GPU step's producer: forward()'s two towers with the features written straight into a
         dist.PackedFeatures record (sink.vis / sink.seq; the segment mask is copied into sink.mask), so that the exchange
         of clip4clip.py:351-355 is ONE all_gather_into_tensor of preallocated buffers with no packing step."""
+        if self.sim_header != "meanP":
+            raise NotImplementedError("encode_into: the feature records carry the pooled meanP operands; sim_header=%r runs "
+                                      "its head in forward() / get_similarity_logits" % self.sim_header)
         input_ids = input_ids.view(-1, input_ids.shape[-1])
         video = torch.as_tensor(video)
         if video.dtype != torch.uint8:
@@ -161,6 +260,7 @@ class CLIP4Clip(nn.Module):
     def invalidate(self):
         """After a write through ``.data`` (not version-tracked): drop every cached copy of the parameters."""
         self._ls_key = None
+        self._head_pack = None
         self.clip.invalidate()
 
     def _logit_scale_value(self):
@@ -196,6 +296,8 @@ class CLIP4Clip(nn.Module):
         """exp(logit_scale) * t_hat @ v_bar^T   (clip4clip.py:324-367).  In training mode the features of all ranks are
         gathered first (:351-355) - one packed RCCL all-gather instead of three + a barrier."""
         sequence_output, visual_output = sequence_output.contiguous(), visual_output.contiguous()
+        if self.sim_header == "seqTransf":
+            visual_output = self._seq_head_any(visual_output, video_mask)
         if self.training:
             visual_output, video_mask, sequence_output = all_gather(visual_output, video_mask.contiguous(),
                                                                     sequence_output)
@@ -214,5 +316,5 @@ class CLIP4Clip(nn.Module):
             video_mask = video_mask.view(-1, video_mask.shape[-1])
         if visual_output.ndim == 3 and video_mask.shape[1] != visual_output.shape[1]:
             video_mask = self.get_video_mask_after_cluster(video_mask)
-        assert self.sim_header in ["meanP"]
+        assert self.sim_header in ["meanP", "seqTransf"]
         return self._loose_similarity(sequence_output, visual_output, attention_mask, video_mask), ()

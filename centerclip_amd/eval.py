@@ -117,6 +117,10 @@ def _video_operand(core, visual_output, video_mask, be):
     vm = video_mask.view(-1, video_mask.shape[-1])
     if vm.shape[1] != visual_output.shape[1]:
         vm = core.get_video_mask_after_cluster(vm)
+    if getattr(core, "sim_header", "meanP") == "seqTransf":
+        # the head depends on the video side alone: once per cached batch equals the reference's application inside every
+        # get_similarity_logits call (main.py:502-534)
+        visual_output = core.seq_head(visual_output, vm)
     return be.video_operand(visual_output.contiguous(), vm.contiguous())
 
 
@@ -245,6 +249,8 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
     positions, n_items = _item_positions(test_dataloader, world, rank, shard)
     cache = _Cache()
     model.eval()
+    if getattr(core, "sim_header", "meanP") == "seqTransf":
+        core._head_weights()                   # (the head's fp16 weights, built on this stream before any lane reads them)
     lanes = None                               # in_flight > 1: [(model instance, stream)], batch b on lane b % in_flight
     if in_flight > 1:
         if not (torch.cuda.is_available() and torch.device(device).type == "cuda"):

@@ -14,7 +14,7 @@ calls the ctypes layer for compute.  The encoders take their weights through an 
 """
 import ctypes
 import math
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 from torch.library import custom_op
@@ -115,6 +115,81 @@ def attention_f16(qkv: torch.Tensor, nseq: int, L_tok: int, heads: int, causal: 
 @attention_f16.register_fake
 def _(qkv, nseq, L_tok, heads, causal, seq_rows, tok_rows):
     return qkv.new_empty((nseq * L_tok, qkv.shape[1] // 3))
+
+
+# ------------------------------------------------------------------------------------------ sim_header 'seqTransf'
+def _mask_i64(mask):
+    if mask.dtype != torch.long or mask.dim() != 2:
+        raise ValueError("the key mask must be an int64 [nseq, L] tensor (any strides)")
+    return mask
+
+
+@custom_op(NS + "::key_masked_attention", mutates_args=(), device_types="cuda")
+def key_masked_attention(qkv: torch.Tensor, mask: torch.Tensor, nseq: int, L_tok: int, heads: int) -> torch.Tensor:
+    """softmax(q k^T / 8 + (1 - mask[key]) * -1e6) v per head (module_cross.py:102-104) of frame-major qkv [nseq * L, 3W] fp16;
+    mask [nseq, L] int64, any strides -> [nseq * L, W] fp16."""
+    W = qkv.shape[1] // 3
+    _mask_i64(mask)
+    out = _e(nseq * L_tok, W, like=qkv, dtype=torch.float16)
+    L.check(L.lib().cc_key_masked_attention_f16(L.ptr(qkv), L.ptr(out), nseq, L_tok, heads, W, L.ptr(mask), mask.stride(0),
+                                                mask.stride(1), _st(qkv)), "cc_key_masked_attention_f16")
+    return out
+
+
+@key_masked_attention.register_fake
+def _(qkv, mask, nseq, L_tok, heads):
+    return qkv.new_empty((nseq * L_tok, qkv.shape[1] // 3))
+
+
+@custom_op(NS + "::key_masked_attention_backward", mutates_args=("amax",), device_types="cuda")
+def key_masked_attention_backward(qkv: torch.Tensor, mask: torch.Tensor, d_out: torch.Tensor, nseq: int, L_tok: int, heads: int,
+                                  amax: Optional[torch.Tensor]) -> torch.Tensor:
+    """d_out [nseq * L, W] fp32 -> d_qkv [nseq * L, 3W] fp32; amax (optional, one device float): max(it, largest |d_qkv|)."""
+    W = qkv.shape[1] // 3
+    _mask_i64(mask)
+    d_qkv = _e(nseq * L_tok, 3 * W, like=qkv, dtype=torch.float32)
+    L.check(L.lib().cc_key_masked_attention_backward_f16(L.ptr(qkv), L.ptr(mask), mask.stride(0), mask.stride(1), L.ptr(d_out),
+                                                         L.ptr(d_qkv), nseq, L_tok, heads, W, L.ptr(amax), _st(qkv)),
+            "cc_key_masked_attention_backward_f16")
+    return d_qkv
+
+
+@key_masked_attention_backward.register_fake
+def _(qkv, mask, d_out, nseq, L_tok, heads, amax):
+    return qkv.new_empty((nseq * L_tok, qkv.shape[1]), dtype=torch.float32)
+
+
+SEQTRANSF_BLOCK_FIELDS = ("ln_1_weight", "ln_1_bias", "in_proj_weight_f16", "in_proj_bias", "out_proj_weight_f16", "out_proj_bias",
+                          "ln_2_weight", "ln_2_bias", "c_fc_weight_f16", "c_fc_bias", "c_proj_weight_f16", "c_proj_bias")
+
+
+@custom_op(NS + "::seqtransf_forward", mutates_args=(), device_types="cuda")
+def seqtransf_forward(feat: torch.Tensor, mask: torch.Tensor, pos: torch.Tensor, weights: List[torch.Tensor],
+                      heads: int) -> torch.Tensor:
+    """The seqTransf head (clip4clip.py:335-349): feat [B, T, D] fp32 + pos[0:T] -> blocks with the key mask [B, T] int64 (any
+    strides) -> + feat.  ``weights``: per block the 12 tensors of SEQTRANSF_BLOCK_FIELDS (fp16 for *_f16, fp32 otherwise)."""
+    from ._lib_clip import BlockWeights
+    B, T, D = feat.shape
+    _mask_i64(mask)
+    nf = len(SEQTRANSF_BLOCK_FIELDS)
+    if len(weights) % nf:
+        raise ValueError("seqtransf_forward: %d weight tensors per block" % nf)
+    layers = len(weights) // nf
+    arr = (BlockWeights * max(layers, 1))()
+    for i in range(layers):
+        for k, name in enumerate(SEQTRANSF_BLOCK_FIELDS):
+            setattr(arr[i], name, L.ptr(weights[i * nf + k]))
+    out = torch.empty_like(feat)
+    lib = L.lib()
+    ws = L.workspace(lib.cc_seqtransf_workspace_bytes(B, T, D), feat.device)
+    L.check(lib.cc_seqtransf_forward_f32(L.ptr(feat), L.ptr(mask), mask.stride(0), mask.stride(1), L.ptr(pos), arr, layers, B, T, D,
+                                         heads, L.ptr(out), L.ptr(ws), ws.numel(), _st(feat)), "cc_seqtransf_forward_f32")
+    return out
+
+
+@seqtransf_forward.register_fake
+def _(feat, mask, pos, weights, heads):
+    return torch.empty_like(feat)
 
 
 @custom_op(NS + "::fold_layernorm_linear", mutates_args=(), device_types="cuda")
@@ -1070,7 +1145,7 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "pairwise_distance", "pairwise_distance_cross", "token_norms", "vit_encode", "text_encode", "clip_encode_out", "clip_encode",
        "loose_similarity", "video_pool_normalize", "normalize_rows", "scaled_dot_nt", "scaled_dot_nt_out", "rank_counts",
        "rank_counts_cols", "rank_counts_ref", "group_max_rows", "normalize_rows_planes", "video_pool_normalize_planes",
-       "scaled_dot_planes")
+       "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward")
 
 
 def logit_multiplier(logit_scale):

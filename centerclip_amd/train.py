@@ -203,10 +203,11 @@ def _token_shift_rows(y, N, Lt, mid_shift, adjoint):
     return torch.ops.centerclip.token_shift(y.view(N, Lt, W), True, seg, div, 5, adjoint).view(N * Lt, W)
 
 
-def block_forward_train(block, x_lnd, mid_shift=None):
+def block_forward_train(block, x_lnd, mid_shift=None, key_mask=None):
     """-> (z [L, N, W] fp32, saved dict).  ``block``: a centerclip_amd.clip.ResidualAttentionBlock without a cluster module.
     ``mid_shift`` (segment, fold_div): token_shift's second shift between the attention residual and ln_2 (clip.py:246-248),
-    y' = S(y); None (default): the plain block."""
+    y' = S(y); None (default): the plain block.  ``key_mask`` [N, L] int64 (any strides): the seqTransf head's additive
+    (1 - mask[key]) * -1e6 on every key of sequence n (module_cross.py:102-104, cc_key_masked_attention_f16)."""
     if block.tokencluster_inter is not None:
         raise NotImplementedError("block backward: blocks with a token-cluster module are not covered by this slice")
     L.require_device(x_lnd)
@@ -219,7 +220,12 @@ def block_forward_train(block, x_lnd, mid_shift=None):
                                              block.mlp["c_proj"].weight))
     n1 = ops.layernorm(x, f32(block.ln_1.weight), f32(block.ln_1.bias), eps=block.ln_1.eps, out_f16=True)
     qkv = ops.linear_f16(n1, wq[0], f32(block.attn.in_proj_bias), "f16")
-    att = ops.attention_f16(qkv, N, Lt, block.n_head, causal=causal)
+    if key_mask is not None:
+        if causal:
+            raise ValueError("block_forward_train: a key mask and a causal mask together are not built")
+        att = torch.ops.centerclip.key_masked_attention(qkv, key_mask, N, Lt, block.n_head)
+    else:
+        att = ops.attention_f16(qkv, N, Lt, block.n_head, causal=causal)
     y = _linear_resid(att, wo[0], f32(block.attn.out_proj.bias), x)           # x + out_proj(att): x itself is kept for the backward
     if mid_shift is not None:
         y = _token_shift_rows(y, N, Lt, mid_shift, False)                      # y' = S(y): what ln_2 and the residual read
@@ -230,7 +236,7 @@ def block_forward_train(block, x_lnd, mid_shift=None):
     z = _linear_resid(u, wp[0], f32(block.mlp["c_proj"].bias), y)
     wt = dict(in_proj=wq[1], out_proj=wo[1], c_fc=wf[1], c_proj=wp[1])                  # W^T of the same read, for the dgrads
     saved = dict(x=x, n1=n1, qkv=qkv, att=att, y=y, n2=n2, u_pre=u_pre, u=u, shape=(Lt, N, W), causal=causal, wt=wt,
-                 mid_shift=mid_shift)
+                 mid_shift=mid_shift, key_mask=key_mask)
     # (a VIEW of the frame-major rows: the next block's permute + contiguous then costs nothing - a chain of plain blocks never
     # copies its activations between the two layouts)
     return z.view(N, Lt, W).permute(1, 0, 2), saved
@@ -267,11 +273,17 @@ def block_backward(block, saved, dz_lnd, need=None):
     # y = x + out_proj(att)
     datt, g["attn.out_proj.weight"], g["attn.out_proj.bias"] = _grad_linear(dy, saved["att"], f16t(block.attn.out_proj.weight, "out_proj"), amax=am[1], need_dw=nw("attn.out_proj.weight"))
     dqkv = torch.empty(M, 3 * W, device=dz.device, dtype=torch.float32)
-    ab_bytes = L.lib().cc_attention_backward_workspace_bytes(N, Lt, block.n_head)       # (0 for Lt <= 64)
-    ab_ws = L.workspace(ab_bytes, dz.device) if ab_bytes else None
-    _check(L.lib().cc_attention_backward_f16(L.ptr(saved["qkv"]), L.ptr(datt), L.ptr(dqkv), N, Lt, block.n_head, W,
-                                             int(saved["causal"]), L.ptr(am[2]), L.ptr(ab_ws), ab_bytes, _st(dz)),
-           "cc_attention_backward_f16")
+    km = saved.get("key_mask")
+    if km is not None:
+        _check(L.lib().cc_key_masked_attention_backward_f16(L.ptr(saved["qkv"]), L.ptr(km), km.stride(0), km.stride(1), L.ptr(datt),
+                                                            L.ptr(dqkv), N, Lt, block.n_head, W, L.ptr(am[2]), _st(dz)),
+               "cc_key_masked_attention_backward_f16")
+    else:
+        ab_bytes = L.lib().cc_attention_backward_workspace_bytes(N, Lt, block.n_head)       # (0 for Lt <= 64)
+        ab_ws = L.workspace(ab_bytes, dz.device) if ab_bytes else None
+        _check(L.lib().cc_attention_backward_f16(L.ptr(saved["qkv"]), L.ptr(datt), L.ptr(dqkv), N, Lt, block.n_head, W,
+                                                 int(saved["causal"]), L.ptr(am[2]), L.ptr(ab_ws), ab_bytes, _st(dz)),
+               "cc_attention_backward_f16")
     dn1, g["attn.in_proj_weight"], g["attn.in_proj_bias"] = _grad_linear(dqkv, saved["n1"], f16t(block.attn.in_proj_weight, "in_proj"), amax=am[2], need_dw=nw("attn.in_proj_weight"))
     dx, g["ln_1.weight"], g["ln_1.bias"] = _ln_backward(saved["x"], f32(block.ln_1.weight), dn1, dy, eps=block.ln_1.eps)
     return dx.view(N, Lt, W).permute(1, 0, 2), g
@@ -288,7 +300,7 @@ class ResidualAttentionBlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, block, x, *params):
-        z, saved = block_forward_train(block, x, mid_shift=getattr(block, "mid_shift", None))
+        z, saved = block_forward_train(block, x, mid_shift=getattr(block, "mid_shift", None), key_mask=getattr(block, "key_mask", None))
         ctx.block, ctx.saved = block, saved
         # (the activations and the forward-time W^T copies live in ctx.saved, outside autograd's version tracking: remember the
         #  parameters' versions, so that a weight changed in place between forward and backward is an error, as it is for
@@ -388,6 +400,29 @@ class _NoCluster:
 
     def __getattr__(self, name):
         return getattr(self._blk, name)
+
+
+class _KeyMasked(_NoCluster):
+    """A block of the seqTransf head with its key mask (block_forward_train(key_mask=...))."""
+
+    def __init__(self, blk, key_mask):
+        super().__init__(blk)
+        self.key_mask = key_mask
+
+
+def seq_head_train(model, visual_output, video_mask):
+    """CLIP4Clip's seqTransf head (clip4clip.py:335-349) with gradients: visual_output [B, T, D] + video_mask [B, T] ->
+    [B, T, D].  The position rows are a slice of frame_position_embeddings.weight (rows >= T get exactly zero gradient), the
+    blocks run block_forward_train / block_backward with the key mask, the outer residual is an autograd add."""
+    L.require_device(visual_output)
+    B, T, D = visual_output.shape
+    mask = video_mask if video_mask.dtype == torch.long else video_mask.to(torch.long)
+    x = visual_output.float() + model.frame_position_embeddings.weight[:T].float().unsqueeze(0)
+    x = x.permute(1, 0, 2)                                                      # NLD -> LND (a view: the block reads it once)
+    for blk in model.transformerClip.resblocks:
+        named = dict(blk.named_parameters())
+        x = ResidualAttentionBlockFunction.apply(_KeyMasked(blk, mask), x, *[named[k] for k in _PARAM_ORDER])
+    return x.permute(1, 0, 2) + visual_output.float()
 
 
 def _plain(blk, x_lnd, mid_shift=None):

@@ -57,12 +57,16 @@ def main():
     ap.add_argument("--algo", default="kmediods++", choices=["kmediods++", "spectral", "pooling", "sparse_sampling",
                                                              "token_shift", "temporal_shift"],
                     help="cluster_algo; the shift algorithms get a module in every block (scripts/activitynet.sh case 04)")
+    ap.add_argument("--sim_header", default="meanP", choices=["meanP", "seqTransf"],
+                    help="similarity head (clip4clip.py:324-367); seqTransf starts from the reference's initialisation trick")
+    ap.add_argument("--cross_num_hidden_layers", type=int, default=4, help="blocks of the seqTransf head (params.py default 4)")
     ap.add_argument("--in-flight", type=int, default=None, help="batches in flight (model instances / streams); default: eval_epoch's own (2 on a GPU)")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
     args = bench.task_config(c)                              # cfg 2: 12 frames -> 3 segments at block 7, K = 49
     args.cluster_algo = a.algo
+    args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
     if a.algo in ("token_shift", "temporal_shift"):
         shift_plan(args)
     vars(args).update(spectral_sigma=2.0, spectral_graph="HeatKernel", spectral_knn_k=1, spectral_spg=0, svd_correct_sign=1)

@@ -46,6 +46,9 @@ def main():
     ap.add_argument("--graph", type=int, default=1, help="also time the step captured into a hipGraph")
     ap.add_argument("--b16", type=int, default=0, help="ViT-B/16 instead (cfg-5 shape: 197 tokens per frame, 12 frames -> 4 segments, "
                                                        "K = 100; the attention backward's two-launch form)")
+    ap.add_argument("--sim_header", default="meanP", choices=["meanP", "seqTransf"],
+                    help="similarity head (clip4clip.py:324-367); seqTransf starts from the reference's initialisation trick")
+    ap.add_argument("--cross_num_hidden_layers", type=int, default=4, help="blocks of the seqTransf head (params.py default 4)")
     ap.add_argument("--optim", choices=["BertAdam", "AdamW"], default="BertAdam")
     ap.add_argument("--algo", default="kmediods++", choices=["kmediods++", "token_shift", "temporal_shift"],
                     help="cluster_algo; the shift algorithms get a module in every block (scripts/activitynet.sh case 04)")
@@ -61,6 +64,7 @@ def main():
     if a.b16:
         c = dict(c, name="cfg5-shaped: ViT-B/16", patch=16, T_new=4, K=100)
     args = bench.task_config(c)
+    args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
     if a.algo != "kmediods++":
         args.cluster_algo = a.algo
         shift_plan(args)

@@ -847,6 +847,36 @@ int cc_grad_clip_coef_f32(const void* ws, int32_t total_blocks, float max_norm, 
 int cc_grad_scale_f32(const void* items_dev, int32_t count, int32_t total_blocks, const float* coef_dev, void* stream);
 
 /* ==========================================================================================
+ * sim_header 'seqTransf' (modules/clip4clip.py:335-349, the loose_type head the reference runs besides meanP).
+ *   visual_output [B, T, D] fp32 (per-segment features before pooling), video_mask [B, T] int64 read at
+ *   mask + b * mask_row_stride + t * mask_col_stride (elements; the strided segment mask needs no copy)
+ *   -> x = visual_output + frame_position_embeddings[0:T]; x = transformerClip(x, key mask); out = x + visual_output.
+ * The blocks are module_cross.ResidualAttentionBlock (module_cross.py:88-112): CLIP's block with the additive attention
+ * mask (1 - video_mask[b, j]) * -1e6 on KEY j, the same for every query and head.
+ *   cc_key_masked_attention_f16   qkv [nseq*L, 3W] fp16 (as cc_attention_f16), out [nseq*L, W] fp16; mask [nseq, L]
+ *                                 (strided).  Keys with mask 0 get weight exactly 0 and their k / v rows are never read; a
+ *                                 sequence whose keys are ALL masked gets the unmasked softmax (the exact value of the formula,
+ *                                 where every score moves by the same -1e6).  fp32 arithmetic, W = 64 * heads, L <= 80.
+ *   cc_key_masked_attention_backward_f16   cc_attention_backward_f16's conventions: d_out [nseq*L, W] fp32 -> d_qkv
+ *                                 [nseq*L, 3W] fp32, out_amax (may be null) as there.  The dk / dv rows of masked keys are
+ *                                 exactly 0.
+ *   cc_seqtransf_forward_f32      the whole head in one enqueue (position rows, `layers` blocks on the LayerNorm / GEMM kernels
+ *                                 of the encoders with the new attention, the outer residual): feat, out [B, T, D] fp32
+ *                                 contiguous (out may alias feat), pos [>= T, D] fp32, blocks[l] (the fields up to c_proj_bias;
+ *                                 LayerNorm eps 1e-5), D = 64 * heads <= 1024, D % 64 == 0, T <= 80.  ws >=
+ *                                 cc_seqtransf_workspace_bytes(B, T, D).  No host synchronisation (graph-capturable).
+ * ========================================================================================== */
+int cc_key_masked_attention_f16(const void* qkv_f16, void* out_f16, int32_t nseq, int32_t L, int32_t heads, int32_t W,
+                                const int64_t* mask, int64_t mask_row_stride, int64_t mask_col_stride, void* stream);
+int cc_key_masked_attention_backward_f16(const void* qkv_f16, const int64_t* mask, int64_t mask_row_stride,
+                                         int64_t mask_col_stride, const float* d_out, float* d_qkv, int32_t nseq, int32_t L,
+                                         int32_t heads, int32_t W, float* out_amax, void* stream);
+size_t cc_seqtransf_workspace_bytes(int32_t B, int32_t T, int32_t D);
+int cc_seqtransf_forward_f32(const float* feat, const int64_t* mask, int64_t mask_row_stride, int64_t mask_col_stride,
+                             const float* pos, const cc_block_weights* blocks, int32_t layers, int32_t B, int32_t T, int32_t D,
+                             int32_t heads, float* out, void* ws, size_t ws_bytes, void* stream);
+
+/* ==========================================================================================
  * Diagnostics (not on the product path; process-wide state, not thread-safe).
  * While armed, every launch of the tiled GEMM kernel is issued with a start / stop event pair that receives the dispatch's
  * own begin / end timestamps (what rocprofv3 --kernel-trace reads), so a kernel symbol can be timed IN SITU, inside an
