@@ -292,6 +292,34 @@ class CLIP4Clip(nn.Module):
             return video_mask[:, self.f_frame_duration - 1::video_mask.shape[-1] // self.final_frames]
         return video_mask
 
+    def freeze_cip_layers(self, freeze_layer_num):
+        """clip4clip.py:449-471 (main.py:102 calls it with --freeze_layer_num before the optimizer is built; every shipped
+        launcher passes 0): parameters of ``clip`` below layer ``freeze_layer_num`` stop requiring a gradient.
+          -1      nothing is frozen
+          k >= 0  everything under ``clip.`` except the heads (ln_final, text_projection, logit_scale, visual.ln_post,
+                  visual.proj) and the blocks with index >= k of either tower - so k = 0 freezes the patch / class / position
+                  embeddings, ln_pre and the token embedding; a block's token-cluster module lives under ``...resblocks.N.`` and
+                  follows block N.  The seqTransf head is not under ``clip.`` and always trains.
+        The training towers then run each tower's frozen prefix on the fused forward and compute no gradient for a frozen
+        tensor (centerclip_amd.train)."""
+        assert -1 <= freeze_layer_num <= 12
+        if freeze_layer_num == -1 or not hasattr(self, "clip"):
+            return
+        if self.linear_patch == '3d':
+            # As the reference behaves, not as its docstring reads: its '3d' exception tests ``name.find("conv2.")`` for truth,
+            # and str.find gives -1 (true) for a name without "conv2." and 7 (true) for "visual.conv2.weight" - so with
+            # linear_patch '3d' every parameter stays trainable.
+            return
+        heads = ("ln_final.", "text_projection", "logit_scale", "visual.ln_post.", "visual.proj")
+        towers = ("visual.transformer.resblocks.", "transformer.resblocks.")
+        for name, param in self.clip.named_parameters():
+            if name.startswith(heads):
+                continue
+            tower = next((t for t in towers if name.startswith(t)), None)
+            if tower is not None and int(name[len(tower):].split(".")[0]) >= freeze_layer_num:
+                continue
+            param.requires_grad = False
+
     def _loose_similarity(self, sequence_output, visual_output, attention_mask, video_mask):
         """exp(logit_scale) * t_hat @ v_bar^T   (clip4clip.py:324-367).  In training mode the features of all ranks are
         gathered first (:351-355) - one packed RCCL all-gather instead of three + a barrier."""

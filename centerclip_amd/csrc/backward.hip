@@ -1157,15 +1157,16 @@ size_t cc_layernorm_backward_workspace_bytes(int32_t rows, int32_t W) {
 int cc_layernorm_backward_f32(const float* x, int64_t x_stride, const float* gamma, const float* dy, const float* dres,
                               float* dx, float* dgamma, float* dbeta, int32_t rows, int32_t W, float eps, float* dx_amax,
                               void* ws, size_t ws_bytes, void* stream) {
-    if (!x || !gamma || !dy || !dx || !dgamma || !dbeta || rows <= 0 || W <= 0 || (W & 3) || W > 1024) return CC_ERR_INVALID;
+    if (!x || !gamma || !dy || !dx || (!dgamma != !dbeta) || rows <= 0 || W <= 0 || (W & 3) || W > 1024) return CC_ERR_INVALID;
     if (x_stride < W || (x_stride & 3)) return CC_ERR_INVALID;          // (rows of x are read as float4 quads)
     if (!ws || ws_bytes < cc_layernorm_backward_workspace_bytes(rows, W)) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int blocks = (rows + LNB_ROWS - 1) / LNB_ROWS;
     hipLaunchKernelGGL(layernorm_backward_kernel, dim3(blocks), dim3(256), 0, st, x, x_stride, gamma, dy, dres, dx,
                        static_cast<float*>(ws), rows, W, eps, reinterpret_cast<unsigned*>(dx_amax));
-    hipLaunchKernelGGL(column_reduce_kernel, dim3((2 * W + 31) / 32), dim3(256), 0, st, static_cast<const float*>(ws), blocks, 2 * W,
-                       dgamma, dbeta, W);
+    if (dgamma)                                   // (a frozen LayerNorm: the partial sums in ws are not reduced - one launch less)
+        hipLaunchKernelGGL(column_reduce_kernel, dim3((2 * W + 31) / 32), dim3(256), 0, st, static_cast<const float*>(ws), blocks,
+                           2 * W, dgamma, dbeta, W);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }

@@ -8,6 +8,7 @@
 // ResidualAttentionBlock.forward (modules/clip.py:460-469, 304-349, 256-269, 228-253).
 #include "cc_kernels.h"
 #include <cstdlib>
+#include <cstdint>
 
 namespace {
 
@@ -302,7 +303,10 @@ bool text_ok(const cc_text_model* m, int Lt) {
 // Both towers, block i of the one paired with block i of the other (either may be absent).
 int encode_towers(const cc_vit_model* vm, const cc_frames* video, int B, int T, float* vfeat, float* hidden_out,
                   int64_t* medoids_out, const int64_t* forced_medoids, const cc_text_model* tm, const int64_t* ids,
-                  int Bt, int Lt, float* tfeat, float* text_hidden_out, void* ws, size_t ws_bytes, hipStream_t st) {
+                  int Bt, int Lt, float* tfeat, float* text_hidden_out, void* ws, size_t ws_bytes, hipStream_t st,
+                  int vstop = -1, int tstop = -1) {
+    // vstop / tstop >= 0 (cc_*_encode_prefix*): the tower stops behind that many blocks and hands over its residual stream
+    // (hidden_out / text_hidden_out) - no projection head; the last block it runs computes every row, the caller reads them
     VitWs v{};
     TextWs t{};
     size_t off = 0;
@@ -313,7 +317,8 @@ int encode_towers(const cc_vit_model* vm, const cc_frames* video, int B, int T, 
     float* h = nullptr;
     float* hother = nullptr;
     int frames = T, tokens = 0, W = 0;
-    const int vl = vm ? vm->layers : 0, tl = tm ? tm->layers : 0;
+    const int vl = vm ? (vstop >= 0 ? vstop : vm->layers) : 0, tl = tm ? (tstop >= 0 ? tstop : tm->layers) : 0;
+    const bool prefix = vstop >= 0 || tstop >= 0;
     // Caption compaction (see TextEmbedArgs): the text tower runs on the rows up to each caption's EOT only - the launches
     // are sized for Bt * Lt rows, the kernels read the real count from the device, so nothing synchronises and a
     // captured graph stays valid for any batch.  Off when the caller wants the full hidden state.
@@ -463,12 +468,14 @@ int encode_towers(const cc_vit_model* vm, const cc_frames* video, int B, int T, 
     }
     // ln_post + proj on the CLS rows only (clip.py:463-464); ln_final + text_projection on the EOT rows only
     // (clip.py:480-484) - one launch for both heads
-    HeadArgs hv{}, ht{};
-    if (vm) hv = HeadArgs{h, tokens + 1, nullptr, vm->ln_post_weight, vm->ln_post_bias, vm->proj, vfeat, B * frames, W, vm->embed_dim};
-    // (compacted captions: eot[b] is already the absolute row of the EOT token)
-    if (tm) ht = HeadArgs{t.h, compact ? 0 : Lt, t.eot, tm->ln_final_weight, tm->ln_final_bias, tm->text_projection, tfeat, Bt, tm->width, tm->embed_dim};
-    rc = cc_launch_head_project2(vm ? hv : ht, (vm && tm) ? &ht : nullptr, st);
-    if (rc) return rc;
+    if (!prefix) {
+        HeadArgs hv{}, ht{};
+        if (vm) hv = HeadArgs{h, tokens + 1, nullptr, vm->ln_post_weight, vm->ln_post_bias, vm->proj, vfeat, B * frames, W, vm->embed_dim};
+        // (compacted captions: eot[b] is already the absolute row of the EOT token)
+        if (tm) ht = HeadArgs{t.h, compact ? 0 : Lt, t.eot, tm->ln_final_weight, tm->ln_final_bias, tm->text_projection, tfeat, Bt, tm->width, tm->embed_dim};
+        rc = cc_launch_head_project2(vm ? hv : ht, (vm && tm) ? &ht : nullptr, st);
+        if (rc) return rc;
+    }
     if (vm && hidden_out && hipMemcpyAsync(hidden_out, h, (size_t)B * frames * (tokens + 1) * W * sizeof(float),
                                            hipMemcpyDeviceToDevice, st) != hipSuccess)
         return CC_ERR_HIP;
@@ -505,6 +512,28 @@ int cc_vit_encode_frames(const cc_vit_model* m, const cc_frames* frames, int32_t
                          nullptr, nullptr, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
+// The patch gathers read uint8 frames in 8-byte pieces and fp32 frames as float4: a base address off that grid is refused
+static bool frames_base_ok(const cc_frames* fr) {
+    if (fr->format == CC_FRAMES_U8_CHW || fr->format == CC_FRAMES_U8_HWC) return (reinterpret_cast<uintptr_t>(fr->data) & 7) == 0;
+    return fr->format == CC_FRAMES_F32_CHW && (reinterpret_cast<uintptr_t>(fr->data) & 15) == 0;
+}
+
+int cc_vit_encode_prefix_frames(const cc_vit_model* m, const cc_frames* frames, int32_t B, int32_t T, int32_t n_blocks,
+                                float* hidden_out, const int64_t* forced_medoids, void* ws, size_t ws_bytes, void* stream) {
+    if (!m || !frames || !frames->data || !hidden_out || B <= 0 || T <= 0) return CC_ERR_INVALID;
+    if (n_blocks < 0 || n_blocks > m->layers || (n_blocks > 0 && !m->blocks)) return CC_ERR_INVALID;
+    if (!vit_ok(m)) return CC_ERR_UNSUPPORTED;
+    if (!frames_base_ok(frames)) return CC_ERR_INVALID;
+    return encode_towers(m, frames, B, T, nullptr, hidden_out, nullptr, forced_medoids, nullptr, nullptr, 0, 0, nullptr,
+                         nullptr, ws, ws_bytes, static_cast<hipStream_t>(stream), n_blocks, -1);
+}
+
+int cc_patch_gather_f16(const cc_frames* frames, int32_t F, int32_t resolution, int32_t patch, void* out_f16, void* stream) {
+    if (!frames || !frames->data || !out_f16 || F <= 0 || patch <= 0 || resolution <= 0) return CC_ERR_INVALID;
+    if ((patch & 7) || resolution % patch || !frames_base_ok(frames)) return CC_ERR_INVALID;
+    return cc_launch_im2col(*frames, static_cast<_Float16*>(out_f16), F, resolution, patch, static_cast<hipStream_t>(stream));
+}
+
 int cc_vit_encode(const cc_vit_model* m, const float* video, int32_t B, int32_t T, float* features,
                   float* hidden_out, int64_t* medoids_out, const int64_t* forced_medoids, void* ws, size_t ws_bytes,
                   void* stream) {
@@ -526,6 +555,15 @@ int cc_text_encode_hidden(const cc_text_model* m, const int64_t* ids, int32_t Bt
     if (!text_ok(m, Lt)) return CC_ERR_UNSUPPORTED;
     return encode_towers(nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, m, ids, Bt, Lt, features, hidden_out,
                          ws, ws_bytes, static_cast<hipStream_t>(stream));
+}
+
+int cc_text_encode_prefix(const cc_text_model* m, const int64_t* ids, int32_t Bt, int32_t Lt, int32_t n_blocks,
+                          float* hidden_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!m || !ids || !hidden_out || Bt <= 0 || Lt <= 0 || Lt > m->context_length) return CC_ERR_INVALID;
+    if (n_blocks < 0 || n_blocks > m->layers || (n_blocks > 0 && !m->blocks)) return CC_ERR_INVALID;
+    if (!text_ok(m, Lt)) return CC_ERR_UNSUPPORTED;
+    return encode_towers(nullptr, nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr, m, ids, Bt, Lt, nullptr, hidden_out, ws,
+                         ws_bytes, static_cast<hipStream_t>(stream), -1, n_blocks);
 }
 
 int cc_text_encode(const cc_text_model* m, const int64_t* ids, int32_t Bt, int32_t Lt, float* features, void* ws,

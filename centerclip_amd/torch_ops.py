@@ -816,6 +816,75 @@ def _(ids, handle, want_hidden):
             ids.new_empty((Bt if want_hidden else 0, Lt, meta["width"]), dtype=torch.float32))
 
 
+@custom_op(NS + "::vit_encode_prefix", mutates_args=(), device_types="cuda")
+def vit_encode_prefix(frames: torch.Tensor, handle: int, B: int, T: int, n_blocks: int,
+                      forced_medoids: Optional[torch.Tensor]) -> torch.Tensor:
+    """The frozen prefix of the visual tower in training (cc_vit_encode_prefix_frames): frames as vit_encode -> the residual
+    stream behind n_blocks blocks, [B*T_n, L_n, W] fp32 frame-major, in one enqueue.  forced_medoids: the ids of the cluster
+    blocks among the first n_blocks, back to back.  The handle's meta["prefix"](T, n_blocks) gives (T_n, L_n, id count per clip)."""
+    from .clip import frames_descriptor
+    m, meta, _keep = _model(handle)
+    fr, frames = frames_descriptor(frames)
+    frames_out, ltok, ids_per_clip = meta["prefix"](T, n_blocks)
+    if forced_medoids is not None and (forced_medoids.dtype != torch.long or not forced_medoids.is_contiguous()
+                                       or forced_medoids.numel() != B * ids_per_clip):
+        raise ValueError(f"forced_medoids: {B * ids_per_clip} contiguous int64 ids expected (the cluster blocks among the first "
+                         f"{n_blocks} blocks, back to back), got {forced_medoids.numel()} of {forced_medoids.dtype}")
+    lib = L.lib()
+    hidden = _e(B * frames_out, ltok, meta["width"], like=frames, dtype=torch.float32)
+    ws = L.workspace(lib.cc_vit_workspace_bytes(ctypes.byref(m), B, T), frames.device)
+    L.check(lib.cc_vit_encode_prefix_frames(ctypes.byref(m), ctypes.byref(fr), B, T, int(n_blocks), L.ptr(hidden),
+                                            L.ptr(forced_medoids), L.ptr(ws), ws.numel(), _st(frames)),
+            "cc_vit_encode_prefix_frames")
+    return hidden
+
+
+@vit_encode_prefix.register_fake
+def _(frames, handle, B, T, n_blocks, forced_medoids):
+    _m, meta, _keep = _model(handle)
+    frames_out, ltok, _ids = meta["prefix"](T, n_blocks)
+    return frames.new_empty((B * frames_out, ltok, meta["width"]), dtype=torch.float32)
+
+
+@custom_op(NS + "::text_encode_prefix", mutates_args=(), device_types="cuda")
+def text_encode_prefix(ids: torch.Tensor, handle: int, n_blocks: int) -> torch.Tensor:
+    """The frozen prefix of the text tower in training (cc_text_encode_prefix): ids [B, n_ctx] int64 -> the residual stream
+    behind n_blocks blocks, [B, n_ctx, W] fp32, every row."""
+    m, meta, _keep = _model(handle)
+    Bt, Lt = ids.shape
+    lib = L.lib()
+    hidden = _e(Bt, Lt, meta["width"], like=ids, dtype=torch.float32)
+    ws = L.workspace(lib.cc_text_workspace_bytes(ctypes.byref(m), Bt, Lt), ids.device)
+    L.check(lib.cc_text_encode_prefix(ctypes.byref(m), L.ptr(ids), Bt, Lt, int(n_blocks), L.ptr(hidden), L.ptr(ws), ws.numel(),
+                                      _st(ids)), "cc_text_encode_prefix")
+    return hidden
+
+
+@text_encode_prefix.register_fake
+def _(ids, handle, n_blocks):
+    _m, meta, _keep = _model(handle)
+    return ids.new_empty((ids.shape[0], ids.shape[1], meta["width"]), dtype=torch.float32)
+
+
+@custom_op(NS + "::patch_gather", mutates_args=(), device_types="cuda")
+def patch_gather(frames: torch.Tensor, resolution: int, patch: int) -> torch.Tensor:
+    """The encoders' patch gather on its own (cc_patch_gather_f16): frames [F,3,H,W] fp32 (normalised) or uint8
+    ([F,3,H,W] / [F,H,W,3], the loader's u8/255 -> (x - mean)/std inside) -> the fp16 patch matrix [F * g * g, 3 * p * p]."""
+    from .clip import frames_descriptor
+    fr, frames = frames_descriptor(frames)
+    F, g = frames.shape[0], resolution // patch
+    out = _e(F * g * g, 3 * patch * patch, like=frames, dtype=torch.float16)
+    L.check(L.lib().cc_patch_gather_f16(ctypes.byref(fr), F, int(resolution), int(patch), L.ptr(out), _st(frames)),
+            "cc_patch_gather_f16")
+    return out
+
+
+@patch_gather.register_fake
+def _(frames, resolution, patch):
+    g = resolution // patch
+    return frames.new_empty((frames.shape[0] * g * g, 3 * patch * patch), dtype=torch.float16)
+
+
 @custom_op(NS + "::clip_encode_out", mutates_args=("vfeat", "tfeat", "medoids_out"), device_types="cuda")
 def clip_encode_out(frames: torch.Tensor, ids: torch.Tensor, vhandle: int, thandle: int, B: int, T: int,
                     vfeat: torch.Tensor, tfeat: torch.Tensor, medoids_out: Optional[torch.Tensor],

@@ -145,10 +145,12 @@ def _column_sums(x32):
     return out
 
 
-def _ln_backward(x, gamma, dy, dres, eps=1e-5, amax=None):
+def _ln_backward(x, gamma, dy, dres, eps=1e-5, amax=None, need_params=True):
+    """need_params False (a frozen LayerNorm): dg = db = None and the launch that reduces the per-workgroup gamma / beta
+    partial sums does not run (the dx kernel still leaves those partials in the workspace)."""
     rows, W = x.shape
     dx = torch.empty_like(x)
-    dg, db = torch.empty(W, device=x.device), torch.empty(W, device=x.device)
+    dg, db = (torch.empty(W, device=x.device), torch.empty(W, device=x.device)) if need_params else (None, None)
     lib = L.lib()
     ws = L.workspace(lib.cc_layernorm_backward_workspace_bytes(rows, W), x.device)
     _check(lib.cc_layernorm_backward_f32(L.ptr(x), W, L.ptr(gamma), L.ptr(dy), L.ptr(dres), L.ptr(dx), L.ptr(dg), L.ptr(db),
@@ -175,19 +177,28 @@ def _w16_pair(w):
     return w16, (wt if wt.shape[1] == N else wt[:, :N].contiguous())
 
 
-def _grad_linear(dy32, x16, w16_t, need_dx=True, amax=None, need_dw=True):
+def _grad_linear(dy32, x16, w16_t, need_dx=True, amax=None, need_dw=True, need_db=True):
     """Gradients of y = x W^T + b for dy [M, N] fp32, x [M, K] fp16, W^T [K, N] fp16 -> (dx [M, K], dW [N, K], db [N]) fp32.
     The gradient is read ONCE for its two fp16 layouts (row-major for dX = dY W, transposed + padded for dW = dY^T X).
-    need_dw False (a frozen layer, main.py's freeze_layer_num): no transposed copies, no wgrad GEMM, dW = None."""
+    need_dw False (a frozen layer, main.py's freeze_layer_num): no transposed copies, no wgrad GEMM, dW = None; need_db False:
+    no column sums, db = None; nothing needed at all: (None, None, None) without a launch."""
+    if not (need_dx or need_dw or need_db):
+        return None, None, None
     # round 5: the weight gradient multiplies dY and X as they lie in memory (cc_wgrad_tn_f16: LDS transposing reads) wherever both
     # widths are multiples of its 128-wide tile - every layer of the CLIP towers; other widths keep the transposed copies
     M, N1 = dy32.shape
     tn = need_dw and N1 % 128 == 0 and x16.shape[1] % 128 == 0
-    dy16, dy16_t, scale, db = _cast_transpose(dy32, scaled=True, col_sums=True, amax=amax,   # (+ the bias gradient, same read)
-                                              want_t=need_dw and not tn, col_partials=tn)
+    if need_db:
+        dy16, dy16_t, scale, db = _cast_transpose(dy32, scaled=True, col_sums=True, amax=amax,   # (+ the bias gradient, same read)
+                                                  want_t=need_dw and not tn, col_partials=tn)
+    else:
+        dy16, dy16_t, scale = _cast_transpose(dy32, scaled=True, amax=amax, want_t=need_dw and not tn)
+        db = None
     dw = None
-    if tn:
+    if tn and need_db:
         dw, db = _wgrad_tn(dy16, x16, scale, col_partial=db)                                  # dY^T X (+ the bias sums' last step)
+    elif tn:
+        dw = _wgrad_tn(dy16, x16, scale)
     elif need_dw:
         _, x16_t, _ = _cast_transpose(x16, scaled=False)
         dw = _linear_unscaled(dy16_t, x16_t, scale)                                           # dY^T X
@@ -242,11 +253,16 @@ def block_forward_train(block, x_lnd, mid_shift=None, key_mask=None):
     return z.view(N, Lt, W).permute(1, 0, 2), saved
 
 
-def block_backward(block, saved, dz_lnd, need=None):
+def block_backward(block, saved, dz_lnd, need=None, need_dx=True):
     """dz [L, N, W] -> (dx [L, N, W], {parameter name: gradient}) for the forward that produced ``saved``.  ``need``
-    (optional): {parameter name: bool} - weight gradients that nobody asked for (frozen layers) are not computed (None)."""
+    (optional): {parameter name: bool} - parameter gradients that nobody asked for (frozen layers) are not computed (None):
+    no wgrad GEMM, no bias column sums, no launch reducing the gamma / beta partial sums.  ``need_dx`` False (the first trainable block of a tower
+    behind a frozen prefix: nothing below can receive a gradient): dx = None, the in_proj dgrad and - with a frozen ln_1 - the
+    ln_1 backward do not run; with in_proj frozen as well the backward stops behind out_proj."""
     need = need or {}
     nw = lambda key: bool(need.get(key, True))
+    ln1 = nw("ln_1.weight") or nw("ln_1.bias")
+    ln2 = nw("ln_2.weight") or nw("ln_2.bias")
     Lt, N, W = saved["shape"]
     M = N * Lt
     wt = saved.get("wt", {})
@@ -255,7 +271,7 @@ def block_backward(block, saved, dz_lnd, need=None):
     dz = dz_lnd.detach().float().permute(1, 0, 2).contiguous().view(M, W)
     g = {}
     # z = y + c_proj(u)
-    du, g["mlp.c_proj.weight"], g["mlp.c_proj.bias"] = _grad_linear(dz, saved["u"], f16t(block.mlp["c_proj"].weight, "c_proj"), need_dw=nw("mlp.c_proj.weight"))
+    du, g["mlp.c_proj.weight"], g["mlp.c_proj.bias"] = _grad_linear(dz, saved["u"], f16t(block.mlp["c_proj"].weight, "c_proj"), need_dw=nw("mlp.c_proj.weight"), need_db=nw("mlp.c_proj.bias"))
     # u = QuickGELU(u_pre)
     # (the three gradients this function produces AND multiplies publish their largest magnitude from the producing kernel:
     #  the fp16 cast of each then needs no pass of its own to choose the scale)
@@ -264,14 +280,18 @@ def block_backward(block, saved, dz_lnd, need=None):
     _check(L.lib().cc_quick_gelu_backward_f16(L.ptr(saved["u_pre"]), L.ptr(du), L.ptr(du_pre), du.numel(), L.ptr(am[0]), _st(du)),
            "cc_quick_gelu_backward_f16")
     # u_pre = c_fc(ln_2(y))
-    dn2, g["mlp.c_fc.weight"], g["mlp.c_fc.bias"] = _grad_linear(du_pre, saved["n2"], f16t(block.mlp["c_fc"].weight, "c_fc"), amax=am[0], need_dw=nw("mlp.c_fc.weight"))
-    dy, g["ln_2.weight"], g["ln_2.bias"] = _ln_backward(saved["y"], f32(block.ln_2.weight), dn2, dz, eps=block.ln_2.eps, amax=am[1])   # + the residual branch
+    dn2, g["mlp.c_fc.weight"], g["mlp.c_fc.bias"] = _grad_linear(du_pre, saved["n2"], f16t(block.mlp["c_fc"].weight, "c_fc"), amax=am[0], need_dw=nw("mlp.c_fc.weight"), need_db=nw("mlp.c_fc.bias"))
+    dy, g["ln_2.weight"], g["ln_2.bias"] = _ln_backward(saved["y"], f32(block.ln_2.weight), dn2, dz, eps=block.ln_2.eps, amax=am[1], need_params=ln2)   # + the residual branch
     if saved.get("mid_shift") is not None:
         # y' = S(y): dy = S^T dy' (the CLS rows' opposite shift; the largest magnitude am[1] the LayerNorm backward published
         # still bounds it - S^T only moves and zeroes values)
         dy = _token_shift_rows(dy, N, Lt, saved["mid_shift"], True)
     # y = x + out_proj(att)
-    datt, g["attn.out_proj.weight"], g["attn.out_proj.bias"] = _grad_linear(dy, saved["att"], f16t(block.attn.out_proj.weight, "out_proj"), amax=am[1], need_dw=nw("attn.out_proj.weight"))
+    datt, g["attn.out_proj.weight"], g["attn.out_proj.bias"] = _grad_linear(dy, saved["att"], f16t(block.attn.out_proj.weight, "out_proj"), amax=am[1], need_dw=nw("attn.out_proj.weight"), need_db=nw("attn.out_proj.bias"))
+    if not (need_dx or ln1 or nw("attn.in_proj_weight") or nw("attn.in_proj_bias")):
+        for k in ("attn.in_proj_weight", "attn.in_proj_bias", "ln_1.weight", "ln_1.bias"):
+            g[k] = None
+        return None, g
     dqkv = torch.empty(M, 3 * W, device=dz.device, dtype=torch.float32)
     km = saved.get("key_mask")
     if km is not None:
@@ -284,9 +304,14 @@ def block_backward(block, saved, dz_lnd, need=None):
         _check(L.lib().cc_attention_backward_f16(L.ptr(saved["qkv"]), L.ptr(datt), L.ptr(dqkv), N, Lt, block.n_head, W,
                                                  int(saved["causal"]), L.ptr(am[2]), L.ptr(ab_ws), ab_bytes, _st(dz)),
                "cc_attention_backward_f16")
-    dn1, g["attn.in_proj_weight"], g["attn.in_proj_bias"] = _grad_linear(dqkv, saved["n1"], f16t(block.attn.in_proj_weight, "in_proj"), amax=am[2], need_dw=nw("attn.in_proj_weight"))
-    dx, g["ln_1.weight"], g["ln_1.bias"] = _ln_backward(saved["x"], f32(block.ln_1.weight), dn1, dy, eps=block.ln_1.eps)
-    return dx.view(N, Lt, W).permute(1, 0, 2), g
+    dn1, g["attn.in_proj_weight"], g["attn.in_proj_bias"] = _grad_linear(
+        dqkv, saved["n1"], f16t(block.attn.in_proj_weight, "in_proj") if (need_dx or ln1) else None, need_dx=need_dx or ln1,
+        amax=am[2], need_dw=nw("attn.in_proj_weight"), need_db=nw("attn.in_proj_bias"))
+    if not (need_dx or ln1):
+        g["ln_1.weight"] = g["ln_1.bias"] = None
+        return None, g
+    dx, g["ln_1.weight"], g["ln_1.bias"] = _ln_backward(saved["x"], f32(block.ln_1.weight), dn1, dy, eps=block.ln_1.eps, need_params=ln1)
+    return (dx.view(N, Lt, W).permute(1, 0, 2) if need_dx else None), g
 
 
 _PARAM_ORDER = ("attn.in_proj_weight", "attn.in_proj_bias", "attn.out_proj.weight", "attn.out_proj.bias", "ln_1.weight",
@@ -301,7 +326,8 @@ class ResidualAttentionBlockFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, block, x, *params):
         z, saved = block_forward_train(block, x, mid_shift=getattr(block, "mid_shift", None), key_mask=getattr(block, "key_mask", None))
-        ctx.block, ctx.saved = block, saved
+        # (nothing of this call can receive a gradient - a frozen block on an input without one: keep nothing for a backward)
+        ctx.block, ctx.saved = block, (saved if any(ctx.needs_input_grad) else None)
         # (the activations and the forward-time W^T copies live in ctx.saved, outside autograd's version tracking: remember the
         #  parameters' versions, so that a weight changed in place between forward and backward is an error, as it is for
         #  tensors kept with save_for_backward, and not a silently stale W^T)
@@ -315,7 +341,7 @@ class ResidualAttentionBlockFunction(torch.autograd.Function):
             raise RuntimeError("ResidualAttentionBlockFunction: a parameter of the block was modified in place between forward "
                                "and backward (the saved W^T copies are those of the forward)")
         need = {k: bool(ctx.needs_input_grad[2 + i]) for i, k in enumerate(_PARAM_ORDER)}
-        dx, g = block_backward(ctx.block, ctx.saved, dz, need=need)
+        dx, g = block_backward(ctx.block, ctx.saved, dz, need=need, need_dx=bool(ctx.needs_input_grad[1]))
         return (None, dx) + tuple((g[k].view_as(named[k]).to(named[k].dtype) if (need[k] and g[k] is not None) else None)
                                   for k in _PARAM_ORDER)
 
@@ -335,22 +361,29 @@ def block_apply(block, x_lnd):
 # and positional embeddings, the embedding-table gather with its scatter-add gradient, the EOT row gather.
 
 class LinearFunction(torch.autograd.Function):
-    """y [M, N] fp32 = x [M, K] @ w[N, K]^T (+ b): fp16 MFMA operands, fp32 accumulate; gradients as _grad_linear."""
+    """y [M, N] fp32 = x [M, K] @ w[N, K]^T (+ b): fp16 MFMA operands, fp32 accumulate; gradients as _grad_linear, each one
+    only where autograd asks for it.  An fp16 x (the patch gather's output) is the GEMM operand and the saved activation as
+    it is - no copy."""
 
     @staticmethod
     def forward(ctx, x, w, b):
         x16 = x.detach().to(torch.float16).contiguous()
-        ctx.save_for_backward(x16, w)
+        if any(ctx.needs_input_grad[1:]):                     # (x itself is only needed for the weight gradient)
+            ctx.save_for_backward(x16, w)
+        else:
+            ctx.save_for_backward(None, w)
         ctx.has_bias = b is not None
-        ctx.need_dx = x.requires_grad
         return ops.linear_f16(x16, w.detach().to(torch.float16).contiguous(), None if b is None else b.detach().float().contiguous(),
                               "f32")
 
     @staticmethod
     def backward(ctx, dy):
         x16, w = ctx.saved_tensors
-        dx, dw, db = _grad_linear(dy.contiguous().float(), x16, _wt16(w) if ctx.need_dx else None, need_dx=ctx.need_dx)
-        return dx, dw.to(w.dtype), (db if ctx.has_bias else None)
+        need_dx, need_dw = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        need_db = ctx.has_bias and bool(ctx.needs_input_grad[2])
+        dx, dw, db = _grad_linear(dy.contiguous().float(), x16, _wt16(w) if need_dx else None, need_dx=need_dx, need_dw=need_dw,
+                                  need_db=need_db)
+        return dx, (dw.to(w.dtype) if need_dw else None), db
 
 
 class LayerNormFunction(torch.autograd.Function):
@@ -366,17 +399,21 @@ class LayerNormFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, gamma = ctx.saved_tensors
-        dx, dg, db = _ln_backward(x, gamma.detach().float().contiguous(), dy.contiguous().float(), None, ctx.eps)
-        return dx, dg.to(gamma.dtype), db.to(gamma.dtype), None
+        need_g, need_b = bool(ctx.needs_input_grad[1]), bool(ctx.needs_input_grad[2])
+        dx, dg, db = _ln_backward(x, gamma.detach().float().contiguous(), dy.contiguous().float(), None, ctx.eps,
+                                  need_params=need_g or need_b)
+        return (dx if ctx.needs_input_grad[0] else None), (dg.to(gamma.dtype) if need_g else None), \
+            (db.to(gamma.dtype) if need_b else None), None
 
 
 def _layernorm(ln, x2d):
     return LayerNormFunction.apply(x2d, ln.weight, ln.bias, ln.eps)
 
 
-def _blocks(transformer, x_lnd):
-    """The resblocks on LND activations; a block's token-cluster module runs in front of it (clip.py:236-242)."""
-    for blk in transformer.resblocks:
+def _blocks(transformer, x_lnd, start=0):
+    """The resblocks from block ``start`` on, on LND activations; a block's token-cluster module runs in front of it
+    (clip.py:236-242)."""
+    for blk in list(transformer.resblocks)[start:]:
         tc = blk.tokencluster_inter
         if tc is not None:
             if getattr(tc, "mean_residual", False):
@@ -431,22 +468,74 @@ def _plain(blk, x_lnd, mid_shift=None):
     return ResidualAttentionBlockFunction.apply(view, x_lnd, *[named[k] for k in _PARAM_ORDER])
 
 
+# The frozen prefix of a tower (clip4clip.py:449-471 freeze_cip_layers, called by main.py:102 in every shipped launcher): the
+# leading run of stages in which no parameter requires a gradient - the front end (visual: patch / class / position embedding +
+# ln_pre; text: token + position embedding), then blocks 0, 1, ...  Nothing in it needs activations for a backward, so it runs
+# under no_grad in ONE enqueue of the inference path's kernels (cc_vit_encode_prefix_frames / cc_text_encode_prefix) and hands the
+# first trainable block the fp32 residual stream.
+_GLUE_FRONT = False      # private, for the tests: True = the towers' fronts as torch glue + per-op launches whatever is frozen
+
+
+def _none_trainable(params):
+    return not any(p.requires_grad for p in params)
+
+
+def _prefix_blocks(transformer):
+    n = 0
+    for blk in transformer.resblocks:
+        tc = blk.tokencluster_inter
+        if not _none_trainable(blk.parameters()) or (tc is not None and getattr(tc, "mean_residual", False)):
+            break
+        n += 1
+    return n
+
+
+def visual_prefix_blocks(vis):
+    """Number of leading blocks in the visual tower's frozen prefix (0: the front end alone), None: no frozen prefix."""
+    if _GLUE_FRONT or vis.linear_patch != '2d' or not _none_trainable(vis.prefix_parameters(0)):
+        return None
+    return _prefix_blocks(vis.transformer)
+
+
+def text_prefix_blocks(clip):
+    """The text tower's counterpart of visual_prefix_blocks."""
+    if _GLUE_FRONT or not _none_trainable(clip.text_prefix_parameters(0)):
+        return None
+    return _prefix_blocks(clip.transformer)
+
+
 def encode_image_train(clip, video, video_frame):
     """CLIP.encode_image (modules/clip.py:460-469 with VisualTransformer.forward :320-345, linear_patch '2d') with gradients:
-    video [F, 3, H, W] fp32 -> (features [F', embed_dim], cluster_loss)."""
+    video [F, 3, H, W] fp32, or the loader's uint8 frames [F, 3, H, W] / [F, H, W, 3] (the patch gather applies
+    dataloaders/transforms.py's u8/255 -> (x - mean)/std) -> (features [F', embed_dim], cluster_loss)."""
     vis = clip.visual
     if vis.linear_patch != '2d':
         raise NotImplementedError("training towers: linear_patch='3d' is not built")
     L.require_device(video)
     F, p, W = video.shape[0], vis.patch_size, vis.width
     g = vis.input_resolution // p
-    # conv1 (kernel = stride = p, no bias) as a GEMM over the patch rows (c, kh, kw) - a reshape of the frames, no gather
-    a = video.float().view(F, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(F * g * g, 3 * p * p)
-    x = LinearFunction.apply(a, vis.conv1.weight.view(W, -1), None).view(F, g * g, W)
-    cls = vis.class_embedding.to(x.dtype) + torch.zeros(F, 1, W, dtype=x.dtype, device=x.device)
-    x = torch.cat([cls, x], dim=1) + vis.positional_embedding.to(x.dtype)
-    x = _layernorm(vis.ln_pre, x.reshape(F * (g * g + 1), W)).view(F, g * g + 1, W)
-    x = _blocks(vis.transformer, x.permute(1, 0, 2).contiguous()).permute(1, 0, 2)          # NLD -> LND -> NLD
+    n = visual_prefix_blocks(vis)
+    if n is not None:
+        with torch.no_grad():
+            x = vis.encode_prefix(video, video_frame, n, forced_medoids=getattr(vis, "forced_medoids", None))
+        # (frame-major rows: the first trainable block's own permute back finds them contiguous, no copy)
+        x = _blocks(vis.transformer, x.permute(1, 0, 2), start=n).permute(1, 0, 2)
+    else:
+        if _GLUE_FRONT or (p % 8 and video.dtype != torch.uint8):
+            # (a patch size off the gather's 8-wide grid - no CLIP tower has one - keeps the reshape, as before)
+            if video.dtype == torch.uint8:
+                raise ValueError("the torch-glue front takes normalised float frames")
+            # conv1 (kernel = stride = p, no bias) as a GEMM over the patch rows (c, kh, kw) - a reshape of the frames
+            a = video.float().view(F, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(F * g * g, 3 * p * p)
+        else:
+            # the encoders' patch gather: the fp16 patch matrix straight from the frames - LinearFunction's operand and saved
+            # activation (no fp32 permute-copy of the patches, no separate cast)
+            a = torch.ops.centerclip.patch_gather(video if video.dtype == torch.uint8 else video.float(), vis.input_resolution, p)
+        x = LinearFunction.apply(a, vis.conv1.weight.view(W, -1), None).view(F, g * g, W)
+        cls = vis.class_embedding.to(x.dtype) + torch.zeros(F, 1, W, dtype=x.dtype, device=x.device)
+        x = torch.cat([cls, x], dim=1) + vis.positional_embedding.to(x.dtype)
+        x = _layernorm(vis.ln_pre, x.reshape(F * (g * g + 1), W)).view(F, g * g + 1, W)
+        x = _blocks(vis.transformer, x.permute(1, 0, 2).contiguous()).permute(1, 0, 2)          # NLD -> LND -> NLD
     cls_rows = x[:, 0, :].contiguous()                        # ln_post(x) @ proj, of which encode_image keeps the CLS row
     feats = LinearFunction.apply(_layernorm(vis.ln_post, cls_rows), vis.proj.t(), None)
     return feats, torch.zeros((), device=video.device)
@@ -457,8 +546,15 @@ def encode_text_train(clip, ids):
     L.require_device(ids)
     B, n_ctx = ids.shape
     W = clip.transformer.width
-    x = clip.token_embedding(ids).float() + clip.positional_embedding[:n_ctx].float()
-    x = _blocks(clip.transformer, x.permute(1, 0, 2).contiguous()).permute(1, 0, 2).contiguous()
+    n = text_prefix_blocks(clip)
+    if n is not None:
+        with torch.no_grad():
+            x = clip.encode_text_prefix(ids, n)
+        x = _blocks(clip.transformer, x.permute(1, 0, 2), start=n).permute(1, 0, 2).contiguous()
+    else:
+        # (autograd records nothing for a tensor that does not require a gradient: a frozen token_embedding gets no scatter-add)
+        x = clip.token_embedding(ids).float() + clip.positional_embedding[:n_ctx].float()
+        x = _blocks(clip.transformer, x.permute(1, 0, 2).contiguous()).permute(1, 0, 2).contiguous()
     eot = x[torch.arange(B, device=x.device), ids.argmax(dim=-1)]                             # the EOT token has the largest id
     return LinearFunction.apply(_layernorm(clip.ln_final, eot.contiguous()), clip.text_projection.t(), None)
 
@@ -1111,9 +1207,11 @@ class GraphedTrainStep:
         return loss.detach()
 
     def _tensors(self):
+        # (a frozen parameter cannot change in a step: it is neither copied nor written back - the packed copies of a frozen
+        #  prefix, whose addresses the captured graph holds, stay valid)
         seen, out = set(), []
         for p in list(self.model.parameters()) + [p for g in self.optimizer.param_groups for p in g['params']]:
-            if id(p) not in seen:
+            if id(p) not in seen and p.requires_grad:
                 seen.add(id(p))
                 out.append(p)
         return out

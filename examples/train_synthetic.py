@@ -11,7 +11,12 @@ with random-init ViT-B/32 weights at the cfg-2 shape (12 frames -> 3 segments at
 weights.  Forward and backward of the towers, the loss and the optimizer step run in the HIP library (centerclip_amd.train);
 the path is a correctness slice - per-op launches from Python, nothing fused or tuned - and the printed step time says so.
 
+--freeze_layer_num K is handed to model.freeze_cip_layers as main.py:102 does (every shipped launcher passes 0; default -1:
+nothing frozen): the frozen prefix of each tower then runs on the fused forward and gets no gradient work.  --uint8 1 draws
+uint8 frames, as the loader yields them before its transform; the patch gather normalises them.
+
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1]
+                                       [--freeze_layer_num 0] [--uint8 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
 import argparse
@@ -53,6 +58,11 @@ def main():
     ap.add_argument("--algo", default="kmediods++", choices=["kmediods++", "token_shift", "temporal_shift"],
                     help="cluster_algo; the shift algorithms get a module in every block (scripts/activitynet.sh case 04)")
     ap.add_argument("--optim-timing", type=int, default=0, help="also time the optimizer step alone (AdamW)")
+    ap.add_argument("--freeze_layer_num", type=int, default=-1, help="main.py's --freeze_layer_num (the launchers pass 0)")
+    ap.add_argument("--uint8", type=int, default=0, help="uint8 frames [T, 3, H, W], normalised inside the patch gather")
+    ap.add_argument("--lr", type=float, default=1e-7, help="learning rate of the new modules; the CLIP groups get lr * --coef_lr")
+    ap.add_argument("--coef_lr", type=float, default=1e-3, help="main.py's --coef_lr")
+    ap.add_argument("--same_batch", type=int, default=0, help="train every step on the first batch (shows the loss going down)")
     a = ap.parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -69,13 +79,14 @@ def main():
         args.cluster_algo = a.algo
         shift_plan(args)
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), args).float().to(device)
-    targs = Namespace(lr=1e-7, wd=0.2, new_added_modules=["Cross", "cluster_embed"], gradient_accumulation_steps=1,
+    model.freeze_cip_layers(a.freeze_layer_num)             # (main.py:102, before the optimizer is built)
+    targs = Namespace(lr=a.lr, wd=0.2, new_added_modules=["Cross", "cluster_embed"], gradient_accumulation_steps=1,
                       clip_grad_norm=None, optim=a.optim)
     total = 100 * a.steps
 
     def make_opt(capturable=False):
         """-> (optimizer, scheduler) of main.py:168-175 for --optim"""
-        groups = prep_optim_params_groups(targs, model, coef_lr=1e-3)
+        groups = prep_optim_params_groups(targs, model, coef_lr=a.coef_lr)
         if a.optim == "AdamW":
             return (AdamW(groups, lr=targs.lr, betas=(0.9, 0.98), eps=1e-6, weight_decay=targs.wd, capturable=capturable),
                     lr_scheduler('cos', init_lr=targs.lr, all_iters=total, slow_start_iters=0.1 * total, weight_decay=targs.wd))
@@ -86,7 +97,11 @@ def main():
     opt, sched = make_opt()
     buckets = ccdist.GradientBuckets(model.parameters()) if world > 1 else None
     data = SyntheticRetrieval(a.batch * a.steps, seed=rank)
+    if a.uint8:
+        data.video = torch.randint(0, 256, data.video.shape, dtype=torch.uint8, generator=torch.Generator().manual_seed(rank))
     loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False)
+    if a.same_batch:
+        loader = [next(iter(loader))] * a.steps
     t = [time.time()]
 
     def log(epoch, step, loss, sim_loss, gs):

@@ -566,6 +566,33 @@ int cc_clip_encode_frames(const cc_vit_model* vm, const cc_frames* frames, int32
                           const cc_text_model* tm, const int64_t* ids, int32_t Bt, int32_t Lt,
                           float* text_features, void* ws, size_t ws_bytes, void* stream);
 
+/* The frozen prefix of a tower in training (main.py:102 freeze_cip_layers: every shipped launcher freezes at least the
+ * patch embedding and the token embedding): the launch sequence of cc_vit_encode_frames / cc_text_encode_hidden stopped
+ * behind n_blocks blocks, 0 <= n_blocks <= layers, returning the residual stream at that point and no projection head.
+ *   visual: hidden_out [B*T_n, L_n, W] fp32 frame-major (T_n segments and L_n tokens incl. CLS behind the cluster blocks among
+ *           the first n_blocks); n_blocks = 0 is gather -> patch GEMM with the position-embedding epilogue -> ln_pre.
+ *           forced_medoids: as cc_vit_encode, the ids of the cluster blocks among the first n_blocks only.
+ *   text:   hidden_out [Bt, Lt, W] fp32, every row (no caption compaction); n_blocks = 0 is token + position embedding.
+ * The last block run computes every row (the next block reads them all).  Only the first n_blocks entries of m->blocks, the
+ * front-end fields and the cluster plan are read: ln_post / proj / ln_final / text_projection may be NULL.
+ * Workspace: cc_vit_workspace_bytes / cc_text_workspace_bytes.  Errors, all found before anything is enqueued:
+ * CC_ERR_INVALID for n_blocks outside [0, layers], a NULL argument or a frame base off the gathers' read grid (uint8 frames
+ * are read in 8-byte pieces, fp32 frames as float4: 8- and 16-byte aligned); CC_ERR_WORKSPACE for a workspace that is too
+ * small. */
+int cc_vit_encode_prefix_frames(const cc_vit_model* m, const cc_frames* frames, int32_t B, int32_t T, int32_t n_blocks,
+                                float* hidden_out, const int64_t* forced_medoids, void* ws, size_t ws_bytes,
+                                void* stream);
+int cc_text_encode_prefix(const cc_text_model* m, const int64_t* ids, int32_t Bt, int32_t Lt, int32_t n_blocks,
+                          float* hidden_out, void* ws, size_t ws_bytes, void* stream);
+
+/* The patch gather of the encoders on its own (training with a trainable conv1): frames (cc_frames, F frames of
+ * resolution x resolution) -> out_f16 [F * (resolution/patch)^2, 3 * patch^2] fp16, rows (c, kh, kw) as conv1.weight is
+ * flattened; uint8 frames get the loader's three fp32 operations (see cc_frames).  patch % 8 == 0, resolution % patch == 0
+ * (uint8: resolution % 8 == 0; a power-of-two patch takes the strip kernel, any other the general gather), a uint8 base
+ * 8-byte aligned, an fp32 base 16-byte aligned - else CC_ERR_INVALID before any launch. */
+int cc_patch_gather_f16(const cc_frames* frames, int32_t F, int32_t resolution, int32_t patch, void* out_f16,
+                        void* stream);
+
 /* S2 - the meanP similarity tail, CLIP4Clip._loose_similarity (modules/clip4clip.py:357-366) with
  * _mean_pooling_for_similarity_visual (:305-316):
  *   v_hat = v/|v| per frame; v_bar = sum_t mask*v_hat / max(sum_t mask, 1 if 0); v_bar /= |v_bar|
@@ -697,7 +724,9 @@ int cc_group_max_rows_f32(const float* sim, int32_t rows, int32_t cols, int64_t 
  * (centerclip_amd/train.py); these entry points are the pieces that are not a GEMM.  fp32 arithmetic, fixed summation
  * orders (identical bits on every run).
  *   cc_layernorm_backward_f32   x [rows, W] (row stride x_stride), dy [rows, W] -> dx [rows, W] = dres (optional, the
- *                               residual branch's gradient) + LayerNorm backward; dgamma, dbeta [W].  W % 4 == 0, W <= 1024,
+ *                               residual branch's gradient) + LayerNorm backward; dgamma, dbeta [W] (both NULL: a frozen
+ *                               LayerNorm - the second launch, which reduces the per-workgroup partial sums to dgamma /
+ *                               dbeta, is skipped; the first still leaves those partials in ws).  W % 4 == 0, W <= 1024,
  *                               x_stride >= W, x_stride % 4 == 0.
  *   cc_quick_gelu_backward_f16  du_pre = du * d/dx [x sigmoid(1.702 x)] at x = u_pre (fp16, the c_fc output before the
  *                               activation, clip.py:192-194); n % 4 == 0

@@ -1,0 +1,486 @@
+"""Training with frozen CLIP layers (CLIP4Clip.freeze_cip_layers, main.py:102) and from the loader's uint8 frames, on the GPU:
+the trainable gradients against the reference's torch.autograd fixture (tr_* of r4_golden.npz, the bounds of
+tests/test_r4_gpu.py), the unfrozen step bit for bit, uint8 frames bit for bit against the loader transform, no launches for
+frozen tensors, frozen parameters under the three step drivers, and the new entry points' argument checks."""
+import ctypes
+import json
+import os
+from argparse import Namespace
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+DEV = "cuda:0"
+CC_ERR_INVALID, CC_ERR_WORKSPACE = -1, -3                    # include/centerclip_hip.h
+
+
+def relerr(a, b):
+    return float((a.double() - b.double()).abs().max() / b.double().abs().max().clamp_min(1e-30))
+
+
+def _golden_clip():
+    g = np.load(os.path.join(HERE, "golden", "clip_golden.npz"))
+    sd = {k[3:]: torch.from_numpy(g[k].astype(np.float32) if g[k].dtype == np.float16 else g[k]) for k in g.files
+          if k.startswith("sd/")}
+    return g, sd
+
+
+def _train_cfg(T):
+    return Namespace(cluster_inter=1, cluster_algo='kmediods++', max_frames=T, target_frames_blocks=[4, 2, 2],
+                     cluster_num_blocks=[16, 6, 6], cluster_distance='euclidean', cluster_threshold=1e-6, cluster_iter_limit=100,
+                     minkowski_norm_p=2.0, pretrained_clip_name='ViT-B/32', aggregation=None, pre_norm=False, loose_type=True,
+                     sim_header='meanP', linear_patch='2d')
+
+
+def _model_and_inputs():
+    from centerclip_amd.clip4clip import CLIP4Clip
+    g, sd = _golden_clip()
+    B, T = int(g["cfg"][10]), int(g["cfg"][11])
+    model = CLIP4Clip.from_state_dict(dict(sd), _train_cfg(T)).float().to(DEV).train()
+    video = torch.from_numpy(g["video"]).view(B, 1, T, 3, 64, 64).to(DEV)
+    ids = torch.from_numpy(g["t_ids"])[:B].to(DEV)
+    vmask = torch.ones(B, 1, T, dtype=torch.long, device=DEV)
+    return g, model, (ids, video, vmask)
+
+
+def _step(model, ids, video, vmask):
+    model.zero_grad(set_to_none=True)
+    out = model(ids, torch.zeros_like(ids), (ids > 0).long(), video, vmask)
+    out["loss"].backward()
+    torch.cuda.synchronize()
+    return out
+
+
+def _grads(model):
+    return {k: (None if p.grad is None else p.grad.detach().clone()) for k, p in model.clip.named_parameters()}
+
+
+# ----------------------------------------------------------------------------- 1. the gradients are the unfrozen ones
+@pytest.mark.parametrize("k", [0, 1, 2, 3])
+def test_frozen_step_gradients_against_reference_autograd(k):
+    """freeze_cip_layers(k) on the small reference model (3 visual blocks, 2 text blocks; the k-medoids module in front of
+    visual block index 1): frozen parameters get no gradient, every other one - all 74 minus the frozen - the loss and both
+    towers' features are compared with the reference's autograd values at test_r4_gpu's bounds.  k >= 2 puts the k-medoids block
+    inside the frozen prefix, where the selection runs on the fused path's activations: the fixture's medoids (the reference's,
+    tests/test_freeze_host.py checks them against the oracle) are imposed through the forced_medoids hook for those k."""
+    g, model, (ids, video, vmask) = _model_and_inputs()
+    r4 = np.load(os.path.join(HERE, "golden", "r4_golden.npz"))
+    with open(os.path.join(HERE, "golden", "freeze_golden.json")) as f:
+        frozen = {n[len("clip."):] for n in json.load(f)["%d|2d|meanP" % k]}
+    model.freeze_cip_layers(k)
+    if k >= 2:
+        model.clip.visual.forced_medoids = torch.from_numpy(g["v_medoids"])
+    out = _step(model, ids, video, vmask)
+    print("loss", float(out["loss"].detach()), "fixture", float(r4["tr_loss"]))
+    assert abs(float(out["loss"].detach()) - float(r4["tr_loss"])) < 2e-3 * max(1.0, abs(float(r4["tr_loss"])))
+    assert relerr(out["visual_output"].detach().reshape(-1, 64).cpu(), torch.from_numpy(r4["tr_vfeat"])) < 2e-3
+    assert relerr(out["sequence_output"].detach().reshape(-1, 64).cpu(), torch.from_numpy(r4["tr_tfeat"])) < 2e-3
+    named = dict(model.clip.named_parameters())
+    keys = [n[len("tr_grad/"):] for n in r4.files if n.startswith("tr_grad/")]
+    assert len(keys) == 74 and frozen <= set(keys)
+    worst, compared = (0.0, None), 0
+    for n in keys:
+        p = named[n]
+        if n in frozen:
+            assert p.grad is None and not p.requires_grad, n
+            continue
+        assert p.grad is not None, n
+        want = torch.from_numpy(r4["tr_grad/" + n])
+        e = relerr(p.grad.detach().float().cpu().reshape(want.shape), want)
+        worst = max(worst, (e, n))
+        compared += 1
+        assert e < 1e-2, (n, e)
+    print("freeze_layer_num", k, "compared", compared, "worst gradient error", worst)
+    assert compared == 74 - len(frozen)
+    assert {n for n, p in named.items() if p.grad is not None} == set(keys) - frozen
+
+
+# ----------------------------------------------------------------------------- 2. nothing frozen = the step as it was
+def test_nothing_frozen_is_bit_identical_to_the_glue_front():
+    """No call, freeze_cip_layers(-1) and the towers' earlier front (the patches as a torch reshape + cast, kept reachable under
+    train._GLUE_FRONT for this comparison - not stored bits of an earlier commit): the loss and all 74 gradients are the same
+    bits."""
+    from centerclip_amd import train as cctrain
+    runs = []
+    for mode in ("none", "minus1", "glue"):
+        g, model, inputs = _model_and_inputs()
+        if mode == "minus1":
+            model.freeze_cip_layers(-1)
+        cctrain._GLUE_FRONT = mode == "glue"
+        try:
+            out = _step(model, *inputs)
+        finally:
+            cctrain._GLUE_FRONT = False
+        runs.append((out["loss"].detach().clone(), _grads(model)))
+    assert sum(v is not None for v in runs[0][1].values()) == 74
+    for loss, grads in runs[1:]:
+        assert torch.equal(loss, runs[0][0])
+        for n, v in runs[0][1].items():
+            assert (v is None) == (grads[n] is None) and (v is None or torch.equal(v, grads[n])), n
+
+
+# ----------------------------------------------------------------------------- 4. uint8 frames in training
+@pytest.mark.parametrize("k", [0, -1])
+@pytest.mark.parametrize("channels_last", [False, True])
+def test_uint8_frames_train_like_the_loader_transform(k, channels_last):
+    """The loss and every gradient from uint8 frames equal, bit for bit, those from the float tensor the loader's three fp32
+    operations make of the same frames (oracle.clip_oracle.loader_normalize, as the N3 tests use it): k = 0 through the fused
+    front, k = -1 through the exposed patch gather feeding the trainable conv1."""
+    from oracle import clip_oracle as clo
+    g, model, (ids, _, vmask) = _model_and_inputs()
+    B, T = vmask.shape[0], vmask.shape[2]
+    gen = torch.Generator().manual_seed(7)
+    shape = (B * T, 64, 64, 3) if channels_last else (B * T, 3, 64, 64)
+    u8 = torch.randint(0, 256, shape, dtype=torch.uint8, generator=gen)
+    flt = clo.loader_normalize(u8, channels_last=channels_last)
+    assert flt.shape == (B * T, 3, 64, 64) and flt.dtype == torch.float32
+    model.freeze_cip_layers(k)
+    out_u8 = _step(model, ids, u8.view((B, 1, T) + shape[1:]).to(DEV), vmask)
+    loss_u8, grads_u8 = out_u8["loss"].detach().clone(), _grads(model)
+    out_f = _step(model, ids, flt.view(B, 1, T, 3, 64, 64).to(DEV), vmask)
+    assert torch.isfinite(loss_u8) and torch.equal(loss_u8, out_f["loss"].detach())
+    assert torch.equal(out_u8["visual_output"], out_f["visual_output"])
+    n_grads = 0
+    for n, p in model.clip.named_parameters():
+        assert (p.grad is None) == (grads_u8[n] is None), n
+        if p.grad is not None:
+            assert torch.equal(p.grad, grads_u8[n]), n
+            n_grads += 1
+    assert n_grads == (74 if k == -1 else 67)
+
+
+# ----------------------------------------------------------------------------- 5. no work for frozen tensors
+def test_no_launches_for_frozen_tensors():
+    """One step with freeze_layer_num = 0 under torch.profiler against the unfrozen step: no embedding_dense_backward, exactly
+    one layernorm_backward_kernel launch and one wgrad_tn_kernel launch fewer, no aten::cat.  The profiler's kernel names carry
+    no shapes: that the missing launches are ln_pre's and conv1's follows from these counts together with
+    test_frozen_step_gradients_against_reference_autograd, where every trainable tensor still gets its (checked) gradient and
+    only the frozen ones get none."""
+    from torch.profiler import profile, ProfilerActivity
+
+    def counts(k):
+        g, model, inputs = _model_and_inputs()
+        model.freeze_cip_layers(k)
+        _step(model, *inputs)                                           # warm-up (packs, workspaces)
+        with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+            _step(model, *inputs)
+        names = [e.name for e in prof.events()]
+        kernels = [e.name for e in prof.events() if "kernel" in e.name.lower()]
+        return dict(emb=sum("embedding_dense_backward" in n for n in names),
+                    ln_bwd=sum("layernorm_backward_kernel" in n for n in kernels),
+                    wgrad=sum("wgrad_tn_kernel" in n for n in kernels),
+                    cat=sum(n == "aten::cat" for n in names))
+    free, froz = counts(-1), counts(0)
+    print("unfrozen", free, "freeze_layer_num=0", froz)
+    assert free["emb"] >= 1 and froz["emb"] == 0
+    # 3 visual + 2 text blocks with two LayerNorms each, ln_post, ln_final = 12; unfrozen: + ln_pre
+    assert free["ln_bwd"] == froz["ln_bwd"] + 1
+    assert free["wgrad"] == froz["wgrad"] + 1                           # conv1 (768 x 128: both widths on the 128-wide tile)
+    assert froz["cat"] < free["cat"]                                    # the class-embedding concatenation is gone with the glue
+
+
+# ----------------------------------------------------------------------------- 6. frozen parameters do not move
+ARGS = Namespace(optim='AdamW', lr=1e-3, wd=0.2, new_added_modules=["ln_final", "text_projection"], gradient_accumulation_steps=1,
+                 clip_grad_norm=1.0)
+
+
+def _batch(g):
+    B, T = int(g["cfg"][10]), int(g["cfg"][11])
+    video = torch.from_numpy(g["video"]).view(B, 1, T, 3, 64, 64)
+    ids = torch.from_numpy(g["t_ids"])[:B]
+    return (ids, (ids > 0).long(), torch.zeros_like(ids), video, torch.ones(B, 1, T, dtype=torch.long))
+
+
+def _sched():
+    from centerclip_amd.train import lr_scheduler
+    return lr_scheduler('cos', init_lr=ARGS.lr, all_iters=10, slow_start_iters=1, weight_decay=ARGS.wd)
+
+
+def _check_frozen(model, init, opt, steps):
+    frozen = [n for n, p in model.named_parameters() if not p.requires_grad]
+    assert len(frozen) == 7
+    for n, p in model.named_parameters():
+        if n in frozen:
+            assert torch.equal(p.detach(), init[n]), n
+            assert p not in opt.state and p.grad is None, n
+        else:
+            assert not torch.equal(p.detach(), init[n]) or p.numel() == 1, n
+            assert opt.state[p]['step'] == steps, n
+
+
+@pytest.mark.parametrize("opt_name", ["BertAdam", "AdamW"])
+def test_train_epoch_leaves_frozen_parameters_alone(opt_name):
+    from centerclip_amd.train import AdamW, BertAdam, prep_optim_params_groups, train_epoch
+    g, model, _ = _model_and_inputs()
+    model.freeze_cip_layers(0)
+    init = {n: p.detach().clone() for n, p in model.named_parameters()}
+    args = Namespace(**dict(vars(ARGS), optim=opt_name, clip_grad_norm=1.0 if opt_name == "AdamW" else None))
+    if opt_name == "AdamW":
+        opt = AdamW(prep_optim_params_groups(args, model, coef_lr=0.5), lr=args.lr, betas=(0.9, 0.98), eps=1e-6, weight_decay=args.wd)
+        sched = _sched()
+    else:
+        opt = BertAdam(prep_optim_params_groups(args, model), lr=args.lr, warmup=0.2, t_total=20, schedule='warmup_linear', b1=0.9,
+                       b2=0.98, e=1e-6, max_grad_norm=1.0)
+        sched = None
+    assert sum(len(gr['params']) for gr in opt.param_groups) == len(init)        # the groups hold the frozen ones too
+    loss, gs = train_epoch(0, args, model, [_batch(g)] * 5, DEV, opt, 0, scheduler=sched)
+    torch.cuda.synchronize()
+    assert gs == 5 and np.isfinite(loss)
+    _check_frozen(model, init, opt, 5)
+
+
+@pytest.mark.parametrize("opt_name", ["AdamW", "BertAdam"])
+def test_graphed_step_with_frozen_layers_equals_eager(opt_name):
+    """GraphedTrainStep with freeze_layer_num = 0 (scheduler + clipping) against the eager loop of the same pieces: the same
+    bits after 5 steps, frozen tensors at their initial bits and without optimizer state in both."""
+    from centerclip_amd.train import AdamW, BertAdam, GraphedTrainStep, clip_grad_norm_, prep_optim_params_groups
+    g = _golden_clip()[0]
+    batch = _batch(g)
+    args = Namespace(**dict(vars(ARGS), optim=opt_name))
+
+    def build(capturable):
+        m = _model_and_inputs()[1]
+        m.freeze_cip_layers(0)
+        if opt_name == "AdamW":
+            o = AdamW(prep_optim_params_groups(args, m, coef_lr=0.5), lr=args.lr, betas=(0.9, 0.98), eps=1e-6, weight_decay=args.wd,
+                      capturable=capturable)
+            return m, o, _sched()
+        o = BertAdam(prep_optim_params_groups(args, m), lr=args.lr, warmup=0.2, t_total=20, schedule='warmup_linear', b1=0.9,
+                     b2=0.98, e=1e-6, max_grad_norm=1.0, capturable=capturable)
+        return m, o, None
+    m0, o0, s0 = build(False)
+    init = {n: p.detach().clone() for n, p in m0.named_parameters()}
+    dev_batch = [t.to(DEV) for t in batch]
+    for k in range(5):
+        o0.zero_grad(set_to_none=True)
+        if s0 is not None:
+            s0(o0, global_step=k)
+        out = m0(dev_batch[0], dev_batch[2], dev_batch[1], dev_batch[3], dev_batch[4])
+        out['loss'].mean().backward()
+        if opt_name == "AdamW":
+            o0.clip_and_step(1.0)
+        else:
+            clip_grad_norm_([p for gr in o0.param_groups for p in gr['params']], 1.0)
+            o0.step()
+        with torch.no_grad():
+            m0.clip.logit_scale.clamp_(0.1, 4.6052)
+    m1, o1, s1 = build(True)
+    stepper = GraphedTrainStep(m1, o1, scheduler=s1, clip_grad_norm=1.0)
+    for _ in range(5):
+        loss = stepper(batch)
+    torch.cuda.synchronize()
+    assert np.isfinite(float(loss)) and stepper.global_step == 5
+    for (n, a), (_, b) in zip(m0.named_parameters(), m1.named_parameters()):
+        assert torch.equal(a, b), n
+    _check_frozen(m0, init, o0, 5)
+    _check_frozen(m1, init, o1, 5)
+
+
+def test_global_norm_counts_trainable_gradients_only():
+    """clip_grad_norm_ / AdamW.clip_and_step over groups that hold the frozen parameters: the norm is the float64 norm of the
+    trainable gradients, within the 1e-6 of tests/test_adamw_gpu.py."""
+    from centerclip_amd.train import AdamW, clip_grad_norm_, prep_optim_params_groups
+    g, model, inputs = _model_and_inputs()
+    model.freeze_cip_layers(0)
+    _step(model, *inputs)
+    ps = list(model.parameters())
+    norm64 = float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in ps if p.grad is not None)))
+    assert sum(p.grad is None for p in ps) == 7
+    opt = AdamW(prep_optim_params_groups(ARGS, model, coef_lr=0.5), lr=ARGS.lr, betas=(0.9, 0.98), eps=1e-6, weight_decay=ARGS.wd)
+    n_fused = float(opt.clip_and_step(1e9))
+    n_plain = float(clip_grad_norm_(ps, 1e9))
+    print("norm64", norm64, "clip_and_step", n_fused, "clip_grad_norm_", n_plain)
+    assert abs(n_fused - norm64) <= 1e-6 * norm64 and abs(n_plain - norm64) <= 1e-6 * norm64
+    assert all(p not in opt.state for p in ps if not p.requires_grad)
+
+
+# ----------------------------------------------------------------------------- 7. the new entry points' argument checks
+def test_prefix_entry_points_reject_bad_arguments_before_any_launch():
+    """n_blocks outside [0, layers], a workspace that is too small and a uint8 frame base off the 8-byte grid: the documented
+    error code, and the output buffer keeps its sentinel."""
+    from centerclip_amd import _lib as L
+    from centerclip_amd import torch_ops as T
+    from centerclip_amd.clip import frames_descriptor
+    g, model, (ids, video, _) = _model_and_inputs()
+    vis, clip = model.clip.visual, model.clip
+    lib = L.lib()
+    vm = T._model(vis._prefix_model(1))[0]
+    tm = T._model(clip._text_prefix_model(1))[0]
+    F = video.shape[0] * video.shape[2]
+    frames = video.reshape(F, 3, 64, 64).contiguous()
+    fr, keep = frames_descriptor(frames)
+    st = L.stream_ptr(frames.device)
+    ws = L.workspace(lib.cc_vit_workspace_bytes(ctypes.byref(vm), F // 4, 4), frames.device)
+    out = torch.full((F * 17 * 128,), -7.0, device=DEV)
+    INVALID, WORKSPACE = CC_ERR_INVALID, CC_ERR_WORKSPACE
+    assert lib.cc_vit_encode_prefix_frames(ctypes.byref(vm), ctypes.byref(fr), F // 4, 4, 1, L.ptr(out), None, L.ptr(ws), 16,
+                                           st) == WORKSPACE
+    call = lambda n, nbytes: lib.cc_vit_encode_prefix_frames(ctypes.byref(vm), ctypes.byref(fr), F // 4, 4, n, L.ptr(out), None,
+                                                            L.ptr(ws), nbytes, st)
+    assert call(-1, ws.numel()) == INVALID and call(4, ws.numel()) == INVALID
+    u8 = torch.zeros(F * 3 * 64 * 64 + 8, dtype=torch.uint8, device=DEV)
+    fr8, keep8 = frames_descriptor(u8[:F * 3 * 64 * 64].view(F, 3, 64, 64))
+    fr8.data = u8.data_ptr() + 3                                                  # off the 8-byte grid
+    assert lib.cc_vit_encode_prefix_frames(ctypes.byref(vm), ctypes.byref(fr8), F // 4, 4, 0, L.ptr(out), None, L.ptr(ws),
+                                           ws.numel(), st) == INVALID
+    f32 = torch.zeros(F * 3 * 64 * 64 + 4, device=DEV)
+    fr4, keep4 = frames_descriptor(f32[:F * 3 * 64 * 64].view(F, 3, 64, 64))
+    fr4.data = f32.data_ptr() + 4                                                 # fp32 frames are read 16 bytes at a time
+    assert lib.cc_vit_encode_prefix_frames(ctypes.byref(vm), ctypes.byref(fr4), F // 4, 4, 0, L.ptr(out), None, L.ptr(ws),
+                                           ws.numel(), st) == INVALID
+    a16 = torch.full((F * 16, 768), -7.0, dtype=torch.float16, device=DEV)
+    assert lib.cc_patch_gather_f16(ctypes.byref(fr4), F, 64, 16, L.ptr(a16), st) == INVALID
+    assert lib.cc_patch_gather_f16(ctypes.byref(fr8), F, 64, 16, L.ptr(a16), st) == INVALID
+    assert lib.cc_patch_gather_f16(ctypes.byref(fr), F, 64, 12, L.ptr(a16), st) == INVALID       # patch % 8
+    # text
+    tws = L.workspace(lib.cc_text_workspace_bytes(ctypes.byref(tm), ids.shape[0], ids.shape[1]), ids.device)
+    tout = torch.full((ids.numel() * 128,), -7.0, device=DEV)
+    tcall = lambda n, nbytes: lib.cc_text_encode_prefix(ctypes.byref(tm), L.ptr(ids), ids.shape[0], ids.shape[1], n, L.ptr(tout),
+                                                       L.ptr(tws), nbytes, st)
+    assert tcall(-1, tws.numel()) == INVALID and tcall(3, tws.numel()) == INVALID and tcall(1, 16) == WORKSPACE
+    torch.cuda.synchronize()
+    assert bool((out == -7.0).all()) and bool((tout == -7.0).all()) and bool((a16 == -7.0).all())
+    # ... and the Python layer refuses a bad n before it reaches the library
+    with pytest.raises(ValueError):
+        vis.encode_prefix(frames, 4, 4)
+    with pytest.raises(ValueError):
+        clip.encode_text_prefix(ids, -1)
+
+
+def test_prefix_forward_agrees_with_the_training_forward_small_model():
+    """The hidden state the fused prefix hands the first trainable block against the per-op training forward's (the glue front
+    + block_forward_train) on the small model, for n = 0 and 1 blocks (in front of the cluster block): within 1e-3 of the
+    tensor's largest entry, the contract of the evaluation path's hidden state."""
+    from centerclip_amd import train as cctrain
+    g, model, (ids, video, _) = _model_and_inputs()
+    vis, clip = model.clip.visual, model.clip
+    F = video.shape[0] * video.shape[2]
+    frames = video.reshape(F, 3, 64, 64)
+    with torch.no_grad():
+        a = frames.view(F, 3, 4, 16, 4, 16).permute(0, 2, 4, 1, 3, 5).reshape(F * 16, 768)
+        x = cctrain.LinearFunction.apply(a, vis.conv1.weight.view(128, -1), None).view(F, 16, 128)
+        x = torch.cat([vis.class_embedding + torch.zeros(F, 1, 128, device=DEV), x], dim=1) + vis.positional_embedding
+        h0 = cctrain._layernorm(vis.ln_pre, x.reshape(F * 17, 128)).view(F, 17, 128)
+        h1 = cctrain.block_forward_train(vis.transformer.resblocks[0], h0.permute(1, 0, 2))[0].permute(1, 0, 2)
+        t0 = clip.token_embedding(ids).float() + clip.positional_embedding[:ids.shape[1]].float()
+        t1 = cctrain.block_forward_train(clip.transformer.resblocks[0], t0.permute(1, 0, 2))[0].permute(1, 0, 2)
+        for n, want in ((0, h0), (1, h1)):
+            got = vis.encode_prefix(frames, 4, n)
+            e = relerr(got, want)
+            print("visual prefix", n, "vs per-op forward", e)
+            assert got.shape == want.shape and e <= 1e-3
+        for n, want in ((0, t0), (1, t1)):
+            got = clip.encode_text_prefix(ids, n)
+            e = relerr(got, want)
+            print("text prefix", n, "vs per-op forward", e)
+            assert got.shape == want.shape and e <= 1e-3
+
+
+def test_frozen_step_allocates_less_at_cfg2():
+    """cfg-2 shape (ViT-B/32, 12 frames -> 3 segments, K = 49), B = 16: a step with freeze_layer_num = 6 keeps no activations
+    for the six frozen blocks of either tower - its peak allocation is below the unfrozen step's.  Only the ordering is
+    asserted; the byte counts are printed (profiles/freeze_train_step.txt records them)."""
+    import bench
+    from centerclip_amd.clip4clip import CLIP4Clip
+    c = bench.CFG2
+    gen = torch.Generator().manual_seed(0)
+    B, T = 16, 12
+    video = torch.randn(B, 1, T, 3, 224, 224, generator=gen).to(DEV)
+    ids = torch.randint(1, 49405, (B, 32), generator=gen)
+    ids[:, 0], ids[:, 20] = 49406, 49407
+    ids[:, 21:] = 0
+    ids = ids.to(DEV)
+    vmask = torch.ones(B, 1, T, dtype=torch.long, device=DEV)
+    peaks = {}
+    for k in (-1, 6):
+        model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), bench.task_config(c)).float().to(DEV).train()
+        model.freeze_cip_layers(k)
+        _step(model, ids, video, vmask)                                     # warm-up: packs and workspaces exist
+        model.zero_grad(set_to_none=True)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        _step(model, ids, video, vmask)
+        peaks[k] = torch.cuda.max_memory_allocated() - base
+        del model
+        torch.cuda.empty_cache()
+    print("peak bytes above the resident model, one step at cfg 2, B = 16:", peaks)
+    assert peaks[6] < peaks[-1]
+
+
+# ----------------------------------------------------------------------------- 3. the prefix forward at full width
+def _oracle_visual_hidden(sd, frames, T, n):
+    """oracle.clip_oracle's visual tower cut behind n blocks (the state dict without the later blocks: its block count is
+    read from the keys) -> the hidden state [F, L, W] fp32 in front of block n."""
+    from oracle import clip_oracle as clo
+    cut = {k: v for k, v in sd.items()
+           if not k.startswith("visual.transformer.resblocks.") or int(k.split(".")[3]) < n}
+    return clo.visual_forward(cut, frames, T, return_hidden=True)[1]
+
+
+def _oracle_text_hidden(sd, ids, n):
+    from oracle import clip_oracle as clo
+    x = sd["token_embedding.weight"].float()[ids] + sd["positional_embedding"].float()[:ids.shape[1]]
+    for i in range(n):
+        x = clo.resblock(x, sd, "transformer.resblocks.%d." % i, sd["ln_final.weight"].shape[0] // 64, causal=True)
+    return x
+
+
+def _per_op_hidden(clip, frames, ids, n):
+    """The per-op training forward the prefix replaces (the glue front, then block_forward_train n times), no gradients."""
+    from centerclip_amd import train as cctrain
+    vis = clip.visual
+    F, p, W = frames.shape[0], vis.patch_size, vis.width
+    g = vis.input_resolution // p
+    with torch.no_grad():
+        a = frames.view(F, 3, g, p, g, p).permute(0, 2, 4, 1, 3, 5).reshape(F * g * g, 3 * p * p)
+        x = cctrain.LinearFunction.apply(a, vis.conv1.weight.view(W, -1), None).view(F, g * g, W)
+        x = torch.cat([vis.class_embedding + torch.zeros(F, 1, W, device=x.device), x], dim=1) + vis.positional_embedding
+        x = cctrain._layernorm(vis.ln_pre, x.reshape(F * (g * g + 1), W)).view(F, g * g + 1, W).permute(1, 0, 2)
+        t = (clip.token_embedding(ids).float() + clip.positional_embedding[:ids.shape[1]].float()).permute(1, 0, 2)
+        for i in range(n):
+            x = cctrain.block_forward_train(vis.transformer.resblocks[i], x)[0]
+            t = cctrain.block_forward_train(clip.transformer.resblocks[i], t)[0]
+    return x.permute(1, 0, 2).contiguous(), t.permute(1, 0, 2).contiguous()
+
+
+@pytest.mark.parametrize("k", [0, 6])
+def test_prefix_forward_at_full_width_against_the_oracle(k):
+    """cfg-2 model (ViT-B/32, 12 frames -> 3 segments in front of block index 6, K = 49), B = 2, freeze_layer_num = k: the input
+    of the first trainable block of either tower, from the fused prefix and from the per-op training forward it replaces, each
+    against the fp32 oracle at the hidden state's contract (largest difference <= 1e-3 of the oracle's largest entry, as
+    tests/test_clip_gpu.py measures it).  With k in {0, 6} the k-medoids module (in front of block index 6, it follows that
+    block) lies behind the prefix, so no medoids are forced.  The fused-versus-per-op distance is printed, not asserted.
+    Measured on MI355X: k = 0 visual 2.35e-4 on both paths, text 0; k = 6 visual 2.66e-4 fused / 2.86e-4 per-op, text 6.66e-4
+    fused / 6.99e-4 per-op (fused against per-op: 2.28e-4 / 9.69e-4)."""
+    import bench
+    from centerclip_amd import train as cctrain
+    from centerclip_amd.clip4clip import CLIP4Clip
+    c = bench.CFG2
+    sd = bench.random_state_dict(c, seed=0)
+    model = CLIP4Clip.from_state_dict(dict(sd), bench.task_config(c)).float().to(DEV).train()
+    model.freeze_cip_layers(k)
+    clip, vis = model.clip, model.clip.visual
+    assert cctrain.visual_prefix_blocks(vis) == k and cctrain.text_prefix_blocks(clip) == k
+    gen = torch.Generator().manual_seed(3)
+    B, T = 2, c["T"]
+    frames = torch.randn(B * T, 3, c["res"], c["res"], generator=gen)
+    ids = torch.randint(1, 49405, (B, c["words"]), generator=gen)
+    ids[:, 0], ids[0, 20], ids[1, 31] = 49406, 49407, 49407
+    ids[0, 21:] = 0
+    want_v, want_t = _oracle_visual_hidden(sd, frames, T, k), _oracle_text_hidden(sd, ids, k)
+    fused_v = vis.encode_prefix(frames.to(DEV), T, k).cpu()
+    fused_t = clip.encode_text_prefix(ids.to(DEV), k).cpu()
+    perop_v, perop_t = (x.cpu() for x in _per_op_hidden(clip, frames.to(DEV), ids.to(DEV), k))
+    assert fused_v.shape == want_v.shape == perop_v.shape == (B * T, 50, 768)
+    assert fused_t.shape == want_t.shape == perop_t.shape == (B, c["words"], 512)
+    e = dict(visual_fused=relerr(fused_v, want_v), visual_per_op=relerr(perop_v, want_v), text_fused=relerr(fused_t, want_t),
+             text_per_op=relerr(perop_t, want_t))
+    print("freeze_layer_num", k, "vs oracle", {n: "%.3e" % v for n, v in e.items()},
+          "| fused vs per-op: visual %.3e text %.3e" % (relerr(fused_v, perop_v), relerr(fused_t, perop_t)))
+    for name, v in e.items():
+        assert v <= 1e-3, (name, v)
