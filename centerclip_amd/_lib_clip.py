@@ -180,6 +180,18 @@ def declare(lib):
     lib.cc_grad_clip_coef_f32.restype = c.c_int
     lib.cc_grad_scale_f32.argtypes = [vp, i32, i32, vp, vp]
     lib.cc_grad_scale_f32.restype = c.c_int
+    lib.cc_grad_scaler_stats_f32.argtypes = [vp, i32, vp, f32, vp, vp]
+    lib.cc_grad_scaler_stats_f32.restype = c.c_int
+    lib.cc_adamw_multi_scaled_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.cc_adamw_multi_scaled_f32.restype = c.c_int
+    lib.cc_grad_scaler_update_f32.argtypes = [vp, vp, vp, f32, f32, i32, vp]
+    lib.cc_grad_scaler_update_f32.restype = c.c_int
+    lib.cc_bertadam_step_scaled_f32.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, sz, vp, vp, vp]
+    lib.cc_bertadam_step_scaled_f32.restype = c.c_int
+    lib.cc_bertadam_multi_scaled_f32.argtypes = [vp, i32, f32, f32, f32, f32, vp, vp, vp]
+    lib.cc_bertadam_multi_scaled_f32.restype = c.c_int
+    lib.cc_bertadam_multi_large_scaled_f32.argtypes = [vp, i32, i32, i32, f32, f32, f32, f32, vp, sz, vp, vp, vp]
+    lib.cc_bertadam_multi_large_scaled_f32.restype = c.c_int
     lib.cc_similarity_plane_row_bytes.argtypes = [i32]
     lib.cc_similarity_plane_row_bytes.restype = sz
     lib.cc_similarity_padded_rows.argtypes = [i32]

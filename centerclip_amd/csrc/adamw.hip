@@ -57,10 +57,14 @@ __device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v
     p = p - s.step_size * (m / denom);                             // p -= lr / (1 - b1^t) * m / denom
 }
 
-template <bool SCALE>
+// SKIP (the loss-scaled step, cc_adamw_multi_scaled_f32): *found_inf != 0 -> the whole launch writes nothing (GradScaler.step
+// skipping optimizer.step()); coef_dev then holds inv_scale * clip coefficient (cc_grad_scaler_stats_f32)
+template <bool SCALE, bool SKIP>
 __global__ __launch_bounds__(AW_THREADS) void adamw_multi_kernel(const AdamWItem* __restrict__ items, int count,
                                                                  const AdamWScalars* __restrict__ scal,
-                                                                 const float* __restrict__ coef_dev) {
+                                                                 const float* __restrict__ coef_dev,
+                                                                 const float* __restrict__ found_inf) {
+    if (SKIP && *found_inf != 0.f) return;                         // (uniform over the grid)
     const int ii = adamw_find(items, count, blockIdx.x);
     const AdamWItem it = items[ii];
     const int64_t bid = (int64_t)blockIdx.x - it.blk0;
@@ -94,6 +98,61 @@ __global__ __launch_bounds__(AW_THREADS) void adamw_multi_kernel(const AdamWItem
         adamw_elem(p, g, m, v, s);
         P[i] = p; M[i] = m; V[i] = v;
     }
+}
+
+// the partials as grad_clip_coef_kernel adds them (same order, same bits) for gradients that still carry the loss scale S:
+// out[0] = ||g / S|| (fp64 scaling by inv_scale^2 before the root: exact for a power-of-two S, so the float norm is the one
+// of the divided gradients), out[1] = inv_scale * min(1, max_norm / (||g / S|| + 1e-6)) (max_norm < 0: inv_scale alone) - the
+// ONE multiplier the step applies - and out[2] = found_inf (1.f / 0.f): a sum of fp64 squares of fp32 values cannot overflow,
+// so it is non-finite exactly when an element is inf or NaN.
+__global__ __launch_bounds__(AW_FINISH_THREADS) void grad_scaler_stats_kernel(const double* __restrict__ partial, int nblocks,
+                                                                              const float* __restrict__ inv_scale_dev,
+                                                                              float max_norm, float* __restrict__ out) {
+    double t = 0.0;
+    for (int b = threadIdx.x; b < nblocks; b += AW_FINISH_THREADS) t += partial[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, CC_WAVE);
+    __shared__ double red[AW_FINISH_THREADS / CC_WAVE];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = t;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const double sumsq = (red[0] + red[1]) + (red[2] + red[3]);
+        const float inv = *inv_scale_dev;
+        const float total = (float)sqrt(sumsq * ((double)inv * (double)inv));
+        float c = 1.f;
+        if (max_norm >= 0.f) {
+            c = max_norm / (total + 1e-6f);
+            c = c > 1.f ? 1.f : c;
+        }
+        out[0] = total;
+        out[1] = inv * c;
+        out[2] = (sumsq - sumsq == 0.0) ? 0.f : 1.f;               // (x - x is 0 for every finite x, NaN for inf and NaN)
+    }
+}
+
+// GradScaler.update (torch's amp_update_scale kernel), one lane: scale2 = {scale, 1 / scale for the next step},
+// ctr = {growth tracker, steps taken, steps skipped}
+__global__ void grad_scaler_update_kernel(float* __restrict__ scale2, const float* __restrict__ found_inf,
+                                          int32_t* __restrict__ ctr, float growth, float backoff, int32_t interval) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float s = scale2[0];
+    int32_t tr = ctr[0];
+    if (*found_inf != 0.f) {
+        s = s * backoff;
+        tr = 0;
+        ctr[2] = ctr[2] + 1;
+    } else {
+        ctr[1] = ctr[1] + 1;
+        tr = tr + 1;
+        if (tr == interval) {
+            const float grown = s * growth;
+            if (grown - grown == 0.f) s = grown;                   // (torch keeps the scale when growing would overflow)
+            tr = 0;
+        }
+    }
+    scale2[0] = s;
+    scale2[1] = (float)(1.0 / (double)s);                          // torch: scale.double().reciprocal().float()
+    ctr[0] = tr;
 }
 
 // sum of squares of every record's gradient: one fp64 partial per workgroup (partial[blockIdx.x])
@@ -177,10 +236,41 @@ int cc_adamw_multi_f32(const void* items_dev, int32_t count, int32_t total_block
     hipStream_t st = static_cast<hipStream_t>(stream);
     const AdamWItem* items = static_cast<const AdamWItem*>(items_dev);
     const AdamWScalars* scal = static_cast<const AdamWScalars*>(scalars_dev);
+    const float* none = nullptr;
     if (coef_dev)
-        hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3(total_blocks), dim3(AW_THREADS), 0, st, items, (int)count, scal, coef_dev);
+        hipLaunchKernelGGL((adamw_multi_kernel<true, false>), dim3(total_blocks), dim3(AW_THREADS), 0, st, items, (int)count, scal,
+                           coef_dev, none);
     else
-        hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3(total_blocks), dim3(AW_THREADS), 0, st, items, (int)count, scal, coef_dev);
+        hipLaunchKernelGGL((adamw_multi_kernel<false, false>), dim3(total_blocks), dim3(AW_THREADS), 0, st, items, (int)count, scal,
+                           coef_dev, none);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+int cc_adamw_multi_scaled_f32(const void* items_dev, int32_t count, int32_t total_blocks, const void* scalars_dev,
+                              const float* mult_dev, const float* found_inf_dev, void* stream) {
+    if (!items_dev || !scalars_dev || !mult_dev || !found_inf_dev || count <= 0 || total_blocks < count) return CC_ERR_INVALID;
+    hipLaunchKernelGGL((adamw_multi_kernel<true, true>), dim3(total_blocks), dim3(AW_THREADS), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamWItem*>(items_dev), (int)count, static_cast<const AdamWScalars*>(scalars_dev), mult_dev,
+                       found_inf_dev);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+int cc_grad_scaler_stats_f32(const void* ws, int32_t total_blocks, const float* inv_scale_dev, float max_norm, float* out3,
+                             void* stream) {
+    if (!ws || !inv_scale_dev || !out3 || total_blocks <= 0) return CC_ERR_INVALID;
+    hipLaunchKernelGGL(grad_scaler_stats_kernel, dim3(1), dim3(AW_FINISH_THREADS), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const double*>(ws), (int)total_blocks, inv_scale_dev, max_norm, out3);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+int cc_grad_scaler_update_f32(float* scale2, const float* found_inf_dev, int32_t* counters3, float growth_factor,
+                              float backoff_factor, int32_t growth_interval, void* stream) {
+    if (!scale2 || !found_inf_dev || !counters3 || growth_interval <= 0) return CC_ERR_INVALID;
+    hipLaunchKernelGGL(grad_scaler_update_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), scale2, found_inf_dev,
+                       counters3, growth_factor, backoff_factor, growth_interval);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }

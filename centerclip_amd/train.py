@@ -19,7 +19,8 @@
 Round 4, later: the towers themselves (encode_image_train / encode_text_train below: patch embedding, ln_pre, the blocks with
 a token-cluster module in front, the heads), BertAdam (utils/optimization.py) on cc_bertadam_step_f32 and train_epoch
 (main.py:291-378) - CLIP4Clip.forward in training mode runs on them, so a training step reaches every parameter.  What is NOT
-here: linear_patch='3d' and mean_residual in training, and fusion (train_epoch takes the reference's GradScaler; the master
+here: linear_patch='3d' and mean_residual in training, and fusion (train_epoch takes the reference's GradScaler, or a
+DeviceGradScaler - the same recipe decided on the device, which GraphedTrainStep(scaler=...) captures; the master
 weights are fp32 and the HIP backward scales per tensor on the device) - per-op launches from Python, checked against torch.autograd on the
 reference model (tests/test_r4_gpu.py, fixture tests/golden/r4_golden.npz) to 1e-2 of each tensor's largest entry.
 Transposed fp16 copies (W^T, dY^T, X^T) come from cc_cast_transpose_f16 (one read per matrix); the scale of a gradient operand
@@ -654,6 +655,11 @@ class BertAdam(torch.optim.Optimizer):
                                  torch.empty(len(raw), dtype=torch.uint8, device=device))
             dev = slot["dev"]
         b1, b2, e, max_norm = hyper
+        sc = getattr(self, "_sc", None)
+        if sc is not None:
+            _check(L.lib().cc_bertadam_multi_scaled_f32(L.ptr(dev), len(items), b1, b2, e, max_norm, L.ptr(sc[0]), L.ptr(sc[1]),
+                                                        _st(dev)), "cc_bertadam_multi_scaled_f32")
+            return
         _check(L.lib().cc_bertadam_multi_f32(L.ptr(dev), len(items), b1, b2, e, max_norm, _st(dev)), "cc_bertadam_multi_f32")
 
     def _multi_large(self, items, hyper, capturing, device):
@@ -697,6 +703,12 @@ class BertAdam(torch.optim.Optimizer):
             dev = slot["dev"]
         b1, b2, e, max_norm = hyper
         part = slot["partial"]
+        sc = getattr(self, "_sc", None)
+        if sc is not None:
+            _check(lib.cc_bertadam_multi_large_scaled_f32(L.ptr(dev), len(items), nb0, sb0, b1, b2, e, max_norm, L.ptr(part),
+                                                          part.numel() * 8, L.ptr(sc[0]), L.ptr(sc[1]), _st(dev)),
+                   "cc_bertadam_multi_large_scaled_f32")
+            return
         _check(lib.cc_bertadam_multi_large_f32(L.ptr(dev), len(items), nb0, sb0, b1, b2, e, max_norm, L.ptr(part),
                                                part.numel() * 8, _st(dev)), "cc_bertadam_multi_large_f32")
 
@@ -709,6 +721,9 @@ class BertAdam(torch.optim.Optimizer):
             self._lr_dev = {}                                     # group index -> 1-element device tensor (not optimizer state)
             self._multi, self._multi_keep = {}, []
         small, large = {}, {}                                     # (b1, b2, e, max_grad_norm) -> records of the small / large tensors
+        sc = getattr(self, "_sc", None)                           # (multiplier, found_inf) device floats: DeviceGradScaler.step
+        if not capturing:
+            self._last = []                                       # the parameters this step counts (for _uncount)
         for gi, group in enumerate(self.param_groups):
             lr_set = False
             for p in group['params']:
@@ -741,6 +756,12 @@ class BertAdam(torch.optim.Optimizer):
                 elif self.capturable:
                     hyper = (float(group['b1']), float(group['b2']), float(group['e']), float(group['max_grad_norm']))
                     large.setdefault(hyper, []).append((p, grad, state['next_m'], state['next_v'], lr_dev, float(group['weight_decay'])))
+                elif sc is not None:
+                    _check(lib.cc_bertadam_step_scaled_f32(L.ptr(p), L.ptr(grad), L.ptr(state['next_m']), L.ptr(state['next_v']),
+                                                           p.numel(), float(self._lr(group, state['step'])), float(group['b1']),
+                                                           float(group['b2']), float(group['e']), float(group['weight_decay']),
+                                                           float(group['max_grad_norm']), L.ptr(lr_dev), L.ptr(ws), ws.numel(),
+                                                           L.ptr(sc[0]), L.ptr(sc[1]), _st(p)), "cc_bertadam_step_scaled_f32")
                 else:
                     _check(lib.cc_bertadam_step_f32(L.ptr(p), L.ptr(grad), L.ptr(state['next_m']), L.ptr(state['next_v']), p.numel(),
                                                     float(self._lr(group, state['step'])), float(group['b1']), float(group['b2']),
@@ -748,11 +769,44 @@ class BertAdam(torch.optim.Optimizer):
                                                     L.ptr(lr_dev), L.ptr(ws), ws.numel(), _st(p)), "cc_bertadam_step_f32")
                 if not capturing:
                     state['step'] += 1
+                    self._last.append(p)
         for hyper, items in small.items():
             self._multi_small(items, hyper, capturing, items[0][0].device)
         for hyper, items in large.items():
             self._multi_large(items, hyper, capturing, items[0][0].device)
         return loss
+
+    @torch.no_grad()
+    def _scaled_step(self, scaler, max_norm):
+        """DeviceGradScaler.step: the statistics over every gradient of the step (norm of the unscaled gradients, the
+        multiplier inv_scale * global clip coefficient, found_inf), then step() on the *_scaled_f32 launches."""
+        grads = []
+        for group in self.param_groups:
+            for p in group['params']:
+                if p.grad is None:
+                    continue
+                L.require_device(p)
+                if p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
+                    p.grad = p.grad.float().contiguous()
+                grads.append(p.grad)
+        if not grads:
+            return False
+        raw, count, nblk = _adamw_table([(g, g, None, None, 0) for g in grads])
+        if not hasattr(self, "_stat_staged"):
+            self._stat_staged = {}
+        table = self._stat_staged.setdefault(len(raw), _Staged("BertAdam")).upload(raw, grads[0].device, _capturing())
+        self._sc = scaler._stats(table, count, nblk, max_norm, grads[0].device)
+        try:
+            self.step()
+        finally:
+            self._sc = None
+        return True
+
+    def _uncount(self):
+        """The last eager step turned out to be skipped on the device (DeviceGradScaler): take its count back."""
+        for p in getattr(self, "_last", ()):
+            self.state[p]['step'] -= 1
+        self._last = []
 
     def refresh_lr(self):
         """capturable: write every group's scheduled learning rate (from the host-side step counts) into its device float -
@@ -977,6 +1031,8 @@ class AdamW(torch.optim.Optimizer):
                 entries.append((p, p.grad, state['exp_avg'], state['exp_avg_sq'], ci))
                 if not capturing:
                     state['step'] = t
+        if not capturing:
+            self._last = [e[0] for e in entries]                  # the parameters this step counts (for _uncount)
         if not entries:
             return None
         raw, count, nblk = _adamw_table(entries)
@@ -1020,6 +1076,26 @@ class AdamW(torch.optim.Optimizer):
         _check(L.lib().cc_adamw_multi_f32(L.ptr(table), count, nblk, L.ptr(scal), L.ptr(out[1:]), _st(scal)),
                "cc_adamw_multi_f32")
         return out[0]
+
+    @torch.no_grad()
+    def _scaled_step(self, scaler, max_norm):
+        """DeviceGradScaler.step: norm partials -> cc_grad_scaler_stats_f32 (norm of the unscaled gradients, the multiplier
+        inv_scale * clip coefficient, found_inf) -> cc_adamw_multi_scaled_f32, which applies the multiplier as it loads each
+        gradient and writes nothing when found_inf is set.  No pass unscales the gradients."""
+        prep = self._prepare()
+        if prep is None:
+            return False
+        dev, table, count, nblk, scal = prep
+        mult, found = scaler._stats(table, count, nblk, max_norm, dev)
+        _check(L.lib().cc_adamw_multi_scaled_f32(L.ptr(table), count, nblk, L.ptr(scal), L.ptr(mult), L.ptr(found), _st(scal)),
+               "cc_adamw_multi_scaled_f32")
+        return True
+
+    def _uncount(self):
+        """The last eager step turned out to be skipped on the device (DeviceGradScaler): take its count back."""
+        for p in getattr(self, "_last", ()):
+            self.state[p]['step'] -= 1
+        self._last = []
 
     def refresh_lr(self):
         """capturable: write the captured step's scalars (each group's current lr / weight_decay, the next step count) into
@@ -1112,6 +1188,265 @@ def prep_optim_params_groups(args, model, coef_lr=1.):
             {'params': [p for n, p in nodec if not is_clip(n)], 'weight_decay': 0.0}]
 
 
+# ================================================================================================ loss scaling on the device
+class DeviceGradScaler:
+    """torch.amp.GradScaler's recipe (main.py:160, 320-328: scale(loss).backward(), unscale_, clip, step, update) with every
+    decision on the device, so that the same object runs eagerly in train_epoch and inside a captured GraphedTrainStep:
+
+        scale(loss)            loss * scale (the device float; the HIP backward passes a power of two through exactly)
+        unscale_(optimizer)    launches NOTHING: the gradients stay scaled in memory until step() - no pass over them exists
+        clip_grad_norm_(optimizer, max_norm)   (after unscale_) asks step() for global clipping of the unscaled gradients
+        step(optimizer)        the norm partials of every gradient -> cc_grad_scaler_stats_f32 (norm of the unscaled
+                               gradients, ONE multiplier inv_scale * clip coefficient, found_inf) -> the optimizer's
+                               *_scaled_f32 launches, which apply the multiplier as they load a gradient (and store that
+                               value back) and write nothing at all when found_inf is set.  Only centerclip_amd.train.AdamW /
+                               BertAdam have such launches: any other optimizer raises.
+        update(new_scale=None) cc_grad_scaler_update_f32, GradScaler.update's rule (backoff on found_inf, growth after
+                               growth_interval clean steps in a row), plus two device counters: steps taken / skipped.
+
+    The state_dict has torch's keys (scale, growth_factor, backoff_factor, growth_interval, _growth_tracker): a checkpoint
+    written from either class loads into the other.
+
+    Step counts.  A skipped step must not advance the optimizer's state['step'] (bias correction, BertAdam's schedule), and
+    whether a step was skipped is known on the device only.  Design: the flag is copied into a pinned host word right behind
+    the optimizer launch (inside the graph when captured), and the count of step k is settled at the START of step k + 1 -
+    sync() waits for step k's event and then either takes back the count an eager step() advanced, or lets a captured step's
+    optimizer advance().  Nothing waits between enqueueing a step's work and its end.  The alternative - counts and the
+    per-class scalars (1 - b1^t, the schedules) on the device - would have to restate torch's double-precision host arithmetic
+    there, bit for bit, for both optimizers; the deferred count keeps that arithmetic where it is.  Call sync() (or
+    GraphedTrainStep.sync()) before reading optimizer.state_dict()."""
+
+    def __init__(self, init_scale=2.0 ** 16, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000, enabled=True):
+        self._enabled = bool(enabled)
+        if self._enabled:
+            if not float(init_scale) > 0.0:
+                raise ValueError("DeviceGradScaler: init_scale must be > 0, got %r" % (init_scale,))
+            if not float(growth_factor) > 1.0:
+                raise ValueError("DeviceGradScaler: the growth factor must be > 1.0, got %r" % (growth_factor,))
+            if not 0.0 < float(backoff_factor) < 1.0:
+                raise ValueError("DeviceGradScaler: the backoff factor must be in (0, 1), got %r" % (backoff_factor,))
+            if int(growth_interval) != growth_interval or int(growth_interval) < 1:
+                raise ValueError("DeviceGradScaler: growth_interval must be a positive integer, got %r" % (growth_interval,))
+        self._init_scale, self._growth_factor = float(init_scale), float(growth_factor)
+        self._backoff_factor, self._growth_interval = float(backoff_factor), int(growth_interval)
+        self._init_growth_tracker = 0
+        self._f = None            # device float32 [8]: scale, 1 / scale, norm, multiplier, found_inf
+        self._c = None            # device int32 [4]: growth tracker, steps taken, steps skipped
+        self._pin = self._event = self._pending = None
+        self._unscaled, self._max_norm, self._stepped = set(), {}, False
+
+    # ------------------------------------------------------------------------------------------------ state
+    def _ensure(self, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise L.CenterClipHipError("DeviceGradScaler runs on MI355X only: got a %s tensor (no CPU fallback)" % device)
+        if self._f is None:
+            self._f = torch.zeros(8, dtype=torch.float32, device=device)
+            self._c = torch.zeros(4, dtype=torch.int32, device=device)
+            self._pin = torch.zeros(1, dtype=torch.float32).pin_memory()
+            self._event = torch.cuda.Event()
+            self._set_scale(self._init_scale)
+            self._c[0] = self._init_growth_tracker
+        elif self._f.device != device:
+            raise RuntimeError("DeviceGradScaler: one device per scaler (%s, then %s)" % (self._f.device, device))
+
+    def _set_scale(self, value):
+        if torch.is_tensor(value):
+            if value.numel() != 1 or value.requires_grad:
+                raise ValueError("DeviceGradScaler.update: new_scale must be a float or a 1-element tensor without a gradient")
+            self._f[0:1].copy_(value.detach().reshape(1).to(torch.float32))
+        else:
+            self._f[0:1].fill_(float(value))
+        self._f[1:2].copy_(self._f[0:1].double().reciprocal().float())        # as GradScaler._unscale_grads_ computes it
+
+    def is_enabled(self):
+        return self._enabled
+
+    def get_scale(self):
+        if not self._enabled:
+            return 1.0
+        return self._init_scale if self._f is None else float(self._f[0])
+
+    def get_growth_factor(self):
+        return self._growth_factor
+
+    def get_backoff_factor(self):
+        return self._backoff_factor
+
+    def get_growth_interval(self):
+        return self._growth_interval
+
+    def counters(self):
+        """-> (steps taken, steps skipped) as update() has counted them on the device (reads the device: synchronises)."""
+        if self._c is None:
+            return 0, 0
+        c = self._c.tolist()
+        return int(c[1]), int(c[2])
+
+    def state_dict(self):
+        if not self._enabled:
+            return {}
+        tracker = self._init_growth_tracker if self._c is None else int(self._c[0])
+        return {"scale": self.get_scale(), "growth_factor": self._growth_factor, "backoff_factor": self._backoff_factor,
+                "growth_interval": self._growth_interval, "_growth_tracker": tracker}
+
+    def load_state_dict(self, state_dict):
+        if not self._enabled:
+            return
+        if len(state_dict) == 0:
+            raise RuntimeError("The source state dict is empty, possibly because it was saved from a disabled instance of "
+                               "GradScaler.")
+        self._init_scale = float(state_dict["scale"])
+        self._growth_factor, self._backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
+        self._growth_interval = int(state_dict["growth_interval"])
+        self._init_growth_tracker = int(state_dict["_growth_tracker"])
+        if self._f is not None:
+            self._set_scale(self._init_scale)
+            self._c[0:1].fill_(self._init_growth_tracker)
+
+    def _snapshot(self):
+        return self._f.clone(), self._c.clone()
+
+    def _restore(self, snap):
+        self._f.copy_(snap[0])
+        self._c.copy_(snap[1])
+        self._pending, self._stepped = None, False
+        self._unscaled.clear()
+        self._max_norm.clear()
+
+    # ------------------------------------------------------------------------------------------------ the protocol
+    def scale(self, outputs):
+        if not self._enabled:
+            return outputs
+        if not torch.is_tensor(outputs):
+            return type(outputs)(self.scale(o) for o in outputs)
+        self._ensure(outputs.device)
+        return outputs * self._f[0]
+
+    @staticmethod
+    def _ours(optimizer, what):
+        if not isinstance(optimizer, (AdamW, BertAdam)):
+            raise TypeError("DeviceGradScaler.%s: centerclip_amd.train.AdamW or BertAdam (the optimizers with launches that can "
+                            "be skipped on the device), got %s" % (what, type(optimizer).__name__))
+
+    def unscale_(self, optimizer):
+        """Marks the optimizer's gradients as to be read unscaled; launches nothing - step() applies inv_scale together with
+        the clip coefficient, so p.grad still holds the SCALED values until then (and the unscaled, clipped ones after)."""
+        if not self._enabled:
+            return
+        self._ours(optimizer, "unscale_")
+        if id(optimizer) in self._unscaled:
+            raise RuntimeError("unscale_() has already been called on this optimizer since the last update().")
+        self._unscaled.add(id(optimizer))
+
+    def clip_grad_norm_(self, optimizer, max_norm):
+        """torch.nn.utils.clip_grad_norm_ over the optimizer's parameters, on the UNSCALED gradients (call unscale_ first,
+        main.py:324-326): deferred into step(), where it costs no launch of its own."""
+        if not self._enabled:
+            return
+        self._ours(optimizer, "clip_grad_norm_")
+        if id(optimizer) not in self._unscaled:
+            raise RuntimeError("DeviceGradScaler.clip_grad_norm_: call unscale_(optimizer) first")
+        if not float(max_norm) >= 0.0:
+            raise ValueError("DeviceGradScaler.clip_grad_norm_: max_norm must be >= 0")
+        self._max_norm[id(optimizer)] = float(max_norm)
+
+    def _stats(self, table, count, nblk, max_norm, device):
+        """-> (multiplier, found_inf): 1-element views of the device state, written by cc_grad_scaler_stats_f32."""
+        self._ensure(device)
+        lib = L.lib()
+        ws = L.workspace(lib.cc_grad_norm_workspace_bytes(nblk), self._f.device)
+        st = _st(self._f)
+        _check(lib.cc_grad_norm_partials_f32(L.ptr(table), count, nblk, L.ptr(ws), ws.numel(), st), "cc_grad_norm_partials_f32")
+        _check(lib.cc_grad_scaler_stats_f32(L.ptr(ws), nblk, L.ptr(self._f[1:2]), float(max_norm), L.ptr(self._f[2:5]), st),
+               "cc_grad_scaler_stats_f32")
+        return self._f[3:4], self._f[4:5]
+
+    def grad_norm(self):
+        """The norm of the unscaled gradients the last step() measured (0-d device tensor)."""
+        return self._f[2]
+
+    def step(self, optimizer, *args, **kwargs):
+        if not self._enabled:
+            return optimizer.step(*args, **kwargs)
+        self._ours(optimizer, "step")
+        if "closure" in kwargs or args:
+            raise RuntimeError("Closure use is not currently supported if GradScaler is enabled.")
+        capturing = _capturing()
+        if not capturing:
+            self.sync()                                           # the previous step's count, before this one's host arithmetic
+        max_norm = self._max_norm.pop(id(optimizer), -1.0)
+        ran = optimizer._scaled_step(self, max_norm)
+        if not ran:                                               # (no gradient anywhere: nothing to skip)
+            for p in (p for g in optimizer.param_groups for p in g['params']):
+                self._ensure(p.device)
+                break
+            if self._f is None:
+                raise RuntimeError("DeviceGradScaler.step: the optimizer has no parameters")
+            self._f[4:5].zero_()
+        self._pin.copy_(self._f[4:5], non_blocking=True)          # (captured: a copy node of the graph)
+        if not capturing and ran:
+            self._mark(optimizer, "eager")
+        self._stepped = True
+        return None
+
+    def _mark(self, optimizer, mode):
+        self._event.record()
+        self._pending = (optimizer, mode)
+
+    def sync(self):
+        """Settle the last step's count (see the class docstring): waits for that step, no-op when nothing is pending."""
+        if self._pending is None:
+            return
+        optimizer, mode = self._pending
+        self._pending = None
+        self._event.synchronize()
+        skipped = float(self._pin[0]) != 0.0
+        if mode == "eager" and skipped:
+            optimizer._uncount()
+        elif mode == "graph" and not skipped:
+            optimizer.advance()
+
+    def update(self, new_scale=None):
+        if not self._enabled:
+            return
+        if new_scale is not None:
+            if _capturing():
+                raise RuntimeError("DeviceGradScaler.update(new_scale=...) inside a capture")
+            if self._f is None:
+                if torch.is_tensor(new_scale):
+                    self._ensure(new_scale.device)
+                    self._set_scale(new_scale)
+                else:
+                    self._init_scale = float(new_scale)
+            else:
+                self._set_scale(new_scale)
+        else:
+            if not self._stepped:
+                raise RuntimeError("No inf checks were recorded prior to update.")
+            _check(L.lib().cc_grad_scaler_update_f32(L.ptr(self._f[0:2]), L.ptr(self._f[4:5]), L.ptr(self._c), self._growth_factor,
+                                                     self._backoff_factor, self._growth_interval, _st(self._f)),
+                   "cc_grad_scaler_update_f32")
+        self._stepped = False
+        self._unscaled.clear()
+        self._max_norm.clear()
+
+
+def _device_scaler(scaler):
+    """GraphedTrainStep's scaler argument -> (DeviceGradScaler or None, the torch GradScaler it was copied from or None)."""
+    if scaler is None:
+        return None, None
+    if isinstance(scaler, DeviceGradScaler):
+        return (scaler if scaler.is_enabled() else None), None
+    if isinstance(scaler, torch.amp.GradScaler):
+        if not scaler.is_enabled():
+            return None, None
+        dev = DeviceGradScaler()
+        dev.load_state_dict(scaler.state_dict())
+        return dev, scaler
+    raise TypeError("GraphedTrainStep: scaler must be a DeviceGradScaler or a torch.amp.GradScaler, got %s" % type(scaler).__name__)
+
+
 # ================================================================================================ train_epoch
 def train_epoch(epoch, args, model, train_dataloader, device, optimizer, global_step, scheduler=None, buckets=None,
                 log=None, scaler=None):
@@ -1124,7 +1459,9 @@ def train_epoch(epoch, args, model, train_dataloader, device, optimizer, global_
     and keeps fp32 master weights - what ``autocast`` gives the reference - so the branch adds what the scaler itself does:
     the loss is multiplied by the scale before backward (the HIP backward picks a power-of-two scale per gradient tensor on
     the device, so the factor passes through exactly), gradients are unscaled (and averaged over the ranks) before clipping,
-    a step whose gradients hold an inf / NaN is skipped and the scale backed off, as GradScaler.step / update do."""
+    a step whose gradients hold an inf / NaN is skipped and the scale backed off, as GradScaler.step / update do.
+    A ``DeviceGradScaler`` runs the same branch without a host decision (no unscaling pass, no .item() on found_inf); its
+    clipping is its own clip_grad_norm_ over the optimizer's parameters, folded into the step's one multiplier."""
     model.train()
     total_loss, nb = 0.0, 0
     for step, batch in enumerate(train_dataloader):
@@ -1146,7 +1483,10 @@ def train_epoch(epoch, args, model, train_dataloader, device, optimizer, global_
             if scaler is not None:
                 if getattr(args, "clip_grad_norm", None) is not None:
                     scaler.unscale_(optimizer)           # (clipping sees the true gradients, main.py:324-326)
-                    torch.nn.utils.clip_grad_norm_(model.parameters(), args.clip_grad_norm)
+                    if isinstance(scaler, DeviceGradScaler) and scaler.is_enabled():
+                        scaler.clip_grad_norm_(optimizer, args.clip_grad_norm)     # (fused into step(): one multiplier)
+                    else:
+                        torch.nn.utils.clip_grad_norm_(model.parameters(), args.clip_grad_norm)
                 scaler.step(optimizer)                   # skipped when a gradient holds an inf / NaN
                 scaler.update()
             else:
@@ -1160,6 +1500,8 @@ def train_epoch(epoch, args, model, train_dataloader, device, optimizer, global_
             log(epoch, step, float(loss.detach()), float(output['sim_loss'].detach()), global_step)
         total_loss += float(loss.detach())
         nb += 1
+    if isinstance(scaler, DeviceGradScaler):
+        scaler.sync()                                            # the last step's count
     return total_loss / max(nb, 1), global_step
 
 
@@ -1172,8 +1514,16 @@ class GraphedTrainStep:
     parameters, moments and step counts are put back before the one replay that counts, so that EVERY call, the first
     included, is exactly one optimizer step (main.py:300-340) and the schedule position equals the caller's step count."""
 
-    def __init__(self, model, optimizer, gradient_accumulation_steps=1, scheduler=None, clip_grad_norm=None, global_step=0):
-        """scheduler (e.g. lr_scheduler): called as scheduler(optimizer, global_step=k) on the host before every step, k = the
+    def __init__(self, model, optimizer, gradient_accumulation_steps=1, scheduler=None, clip_grad_norm=None, global_step=0,
+                 scaler=None):
+        """scaler: a DeviceGradScaler - the launchers' precision=amp recipe (main.py:320-328) inside the captured step: scale
+        the loss, backward, gradient statistics, clip-and-step or step (skipped on the device when a gradient holds an inf /
+        NaN), scale update, logit_scale clamp.  A torch.amp.GradScaler is accepted too: its hyper-parameters and state are
+        copied into a DeviceGradScaler (self.scaler), and write_back_scaler() copies the state back.  None or a disabled
+        scaler: exactly the graph without one.  A skipped step does not advance the optimizer's state['step'] while
+        global_step advances (main.py:344-345); the count of call k is settled at the start of call k + 1 (the flag arrives in
+        a pinned word the graph writes; see DeviceGradScaler) - call sync() before optimizer.state_dict().
+        scheduler (e.g. lr_scheduler): called as scheduler(optimizer, global_step=k) on the host before every step, k = the
         number of calls made so far + global_step (main.py:302); its lr reaches the captured step through refresh_lr().
         clip_grad_norm: global gradient clipping inside the captured step, before the optimizer (main.py:327-333) -
         AdamW.clip_and_step, or clip_grad_norm_ then step() for BertAdam."""
@@ -1184,7 +1534,22 @@ class GraphedTrainStep:
         self.model, self.optimizer = model, optimizer
         self.scheduler, self.clip_grad_norm, self.global_step = scheduler, clip_grad_norm, int(global_step)
         self._moments = ('exp_avg', 'exp_avg_sq') if isinstance(optimizer, AdamW) else ('next_m', 'next_v')
+        self.scaler, self._torch_scaler = _device_scaler(scaler)
         self.graph = self.static = self.loss = None
+
+    def sync(self):
+        """Settle the last call's step count (with a scaler it is known only once that call has run): waits for it."""
+        if self.scaler is not None:
+            self.scaler.sync()
+
+    def write_back_scaler(self):
+        """Copy the device scaler's state (scale, growth tracker, hyper-parameters) into the torch.amp.GradScaler this step
+        was built from, e.g. before a checkpoint saves that object's state_dict (main.py:262-272); -> that GradScaler.
+        Without one (a DeviceGradScaler was passed: it IS the state) -> None."""
+        if self._torch_scaler is None:
+            return None
+        self._torch_scaler.load_state_dict(self.scaler.state_dict())
+        return self._torch_scaler
 
     def _schedule(self):
         if self.scheduler is not None:
@@ -1194,6 +1559,17 @@ class GraphedTrainStep:
         self.optimizer.zero_grad(set_to_none=True)       # (captured: the gradients live in the graph's pool, no fill + accumulate)
         out = self.model(self.static[0], self.static[2], self.static[1], self.static[3], self.static[4])
         loss = out['loss'].mean()
+        if self.scaler is not None:
+            sc = self.scaler
+            sc.scale(loss).backward()
+            if self.clip_grad_norm is not None:
+                sc.unscale_(self.optimizer)
+                sc.clip_grad_norm_(self.optimizer, self.clip_grad_norm)
+            sc.step(self.optimizer)
+            sc.update()
+            with torch.no_grad():
+                self.model.clip.logit_scale.clamp_(0.1, 4.6052)
+            return loss.detach()
         loss.backward()
         if self.clip_grad_norm is None:
             self.optimizer.step()
@@ -1249,25 +1625,35 @@ class GraphedTrainStep:
             self.model.train()
             self.static = [t.to(dev).clone() for t in batch]
             snap = self._snapshot()
+            if self.scaler is not None:
+                self.scaler.sync()                                # (an eager step the caller made with it before)
+                self.scaler._ensure(dev)
+                sc_snap = self.scaler._snapshot()
             for _ in range(2):                                    # allocator / staging-buffer warm-up (the optimizer's records)
                 self._schedule()
                 self._step()
+            if self.scaler is not None:
+                self.scaler.sync()                                # (no host wait may fall into the capture)
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):                    # (the capture pass does not execute)
                 self.loss = self._step()
             self._restore(snap)                                   # the two warm-up steps never happened
-            self._schedule()
-            self.optimizer.refresh_lr()
-            self.graph.replay()
-            self.optimizer.advance()
-            self.global_step += 1
-            return self.loss
+            if self.scaler is not None:
+                self.scaler._restore(sc_snap)                     # ... nor did their scale updates and counters
+            return self._replay()
+        self.sync()                                               # the previous call's count, BEFORE this call's work is enqueued
         for dst, src in zip(self.static, batch):
             dst.copy_(src, non_blocking=True)
+        return self._replay()
+
+    def _replay(self):
         self._schedule()
         self.optimizer.refresh_lr()
         self.graph.replay()
-        self.optimizer.advance()
+        if self.scaler is not None:
+            self.scaler._mark(self.optimizer, "graph")            # counted (or not) by the next sync()
+        else:
+            self.optimizer.advance()
         self.global_step += 1
         return self.loss

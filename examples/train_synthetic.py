@@ -15,7 +15,11 @@ the path is a correctness slice - per-op launches from Python, nothing fused or 
 nothing frozen): the frozen prefix of each tower then runs on the fused forward and gets no gradient work.  --uint8 1 draws
 uint8 frames, as the loader yields them before its transform; the patch gather normalises them.
 
-    python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1]
+--precision amp is the launchers' setting (main.py:160 builds a GradScaler, train_epoch takes its scaler branch :320-328):
+here a train.DeviceGradScaler - loss scaling, inf / NaN check, step skipping and the scale update all on the device - drives
+the eager loop and, inside the graph, the captured step; the taken / skipped counters are printed at the end.
+
+    python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
                                        [--freeze_layer_num 0] [--uint8 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
@@ -30,7 +34,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from centerclip_amd.clip4clip import CLIP4Clip              # noqa: E402
-from centerclip_amd.train import AdamW, BertAdam, lr_scheduler, prep_optim_params_groups, train_epoch   # noqa: E402
+from centerclip_amd.train import (AdamW, BertAdam, DeviceGradScaler, lr_scheduler, prep_optim_params_groups,   # noqa: E402
+                                  train_epoch)
 from centerclip_amd import dist as ccdist                   # noqa: E402
 import bench                                                # noqa: E402
 from eval_synthetic import SyntheticRetrieval               # noqa: E402
@@ -60,6 +65,8 @@ def main():
     ap.add_argument("--optim-timing", type=int, default=0, help="also time the optimizer step alone (AdamW)")
     ap.add_argument("--freeze_layer_num", type=int, default=-1, help="main.py's --freeze_layer_num (the launchers pass 0)")
     ap.add_argument("--uint8", type=int, default=0, help="uint8 frames [T, 3, H, W], normalised inside the patch gather")
+    ap.add_argument("--precision", choices=["fp32", "amp"], default="fp32",
+                    help="amp: the launchers' GradScaler recipe on train.DeviceGradScaler, eager and captured")
     ap.add_argument("--lr", type=float, default=1e-7, help="learning rate of the new modules; the CLIP groups get lr * --coef_lr")
     ap.add_argument("--coef_lr", type=float, default=1e-3, help="main.py's --coef_lr")
     ap.add_argument("--same_batch", type=int, default=0, help="train every step on the first batch (shows the loss going down)")
@@ -109,7 +116,10 @@ def main():
         t.append(time.time())
         if rank == 0:
             print("step %d  loss %.4f  %.0f ms" % (gs, loss, (t[-1] - t[-2]) * 1e3), flush=True)
-    train_epoch(0, targs, model, loader, device, opt, 0, scheduler=sched, buckets=buckets, log=log)
+    scaler = DeviceGradScaler() if a.precision == "amp" else None          # (main.py:160: GradScaler(), init_scale 2^16)
+    train_epoch(0, targs, model, loader, device, opt, 0, scheduler=sched, buckets=buckets, log=log, scaler=scaler)
+    if scaler is not None and rank == 0:
+        print("eager, DeviceGradScaler: %d steps taken, %d skipped, scale %g" % (scaler.counters() + (scaler.get_scale(),)))
     if rank == 0:
         steady = (t[-1] - t[2]) / max(len(t) - 3, 1) if len(t) > 3 else float("nan")
         print("steady step %.0f ms = %.1f clips/s per rank (unfused per-op training path, launched op by op)" % (steady * 1e3, a.batch / steady))
@@ -118,7 +128,8 @@ def main():
         # no op of it synchronises with the host, so what remains is the GPU time of the unfused kernels
         from centerclip_amd.train import GraphedTrainStep
         gopt, gsched = make_opt(capturable=True)
-        stepper = GraphedTrainStep(model, gopt, scheduler=gsched, clip_grad_norm=targs.clip_grad_norm)
+        gscaler = DeviceGradScaler() if a.precision == "amp" else None
+        stepper = GraphedTrainStep(model, gopt, scheduler=gsched, clip_grad_norm=targs.clip_grad_norm, scaler=gscaler)
         batch = next(iter(loader))
         gloss = stepper(batch)
         for _ in range(3):
@@ -130,6 +141,9 @@ def main():
         torch.cuda.synchronize()
         ms = (time.time() - t0) / 10 * 1e3
         print("captured step (%s): %.1f ms = %.0f clips/s (loss %.4f)" % (a.optim, ms, a.batch / ms * 1e3, float(gloss)))
+        if gscaler is not None:
+            stepper.sync()                                  # the last call's step count (settled one call late)
+            print("captured, DeviceGradScaler: %d steps taken, %d skipped, scale %g" % (gscaler.counters() + (gscaler.get_scale(),)))
     if a.optim_timing and rank == 0:
         optimizer_timing(model, device)
     if world > 1:

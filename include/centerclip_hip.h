@@ -829,6 +829,19 @@ int32_t cc_bertadam_norm_blocks(int64_t n);
 int32_t cc_bertadam_step_blocks(int64_t n);
 int cc_bertadam_multi_large_f32(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks,
                                 float b1, float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes, void* stream);
+/* The three forms above under a device-side loss scale (see "Loss scaling on the device" below): the gradients still carry
+ * the scale; every gradient is multiplied by *mult_dev as it is loaded (and that value is what is written back), so the
+ * result is bit for bit the plain entry point on gradients multiplied by *mult_dev first - for a power-of-two scale, on the
+ * gradients divided by it.  *found_inf_dev != 0: the launches write nothing - parameters, moments and gradients keep their
+ * bits (GradScaler.step skipping optimizer.step()).  Both words are device floats that cc_grad_scaler_stats_f32 wrote. */
+int cc_bertadam_step_scaled_f32(float* param, float* grad, float* next_m, float* next_v, int64_t n, float lr_scheduled, float b1,
+                                float b2, float e, float weight_decay, float max_grad_norm, const float* lr_dev, void* ws,
+                                size_t ws_bytes, const float* mult_dev, const float* found_inf_dev, void* stream);
+int cc_bertadam_multi_scaled_f32(const void* items_dev, int32_t count, float b1, float b2, float e, float max_grad_norm,
+                                 const float* mult_dev, const float* found_inf_dev, void* stream);
+int cc_bertadam_multi_large_scaled_f32(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks,
+                                       float b1, float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes,
+                                       const float* mult_dev, const float* found_inf_dev, void* stream);
 
 /* ==========================================================================================
  * AdamW (torch.optim.AdamW, the optimizer main.py:168-175 builds for --optim AdamW) and global gradient clipping
@@ -874,6 +887,25 @@ int cc_grad_norm_partials_f32(const void* items_dev, int32_t count, int32_t tota
 int cc_grad_clip_coef_f32(const void* ws, int32_t total_blocks, float max_norm, float* norm_coef, void* stream);
 /* g *= *coef_dev for every record's gradient (the in-place scaling of clip_grad_norm_). */
 int cc_grad_scale_f32(const void* items_dev, int32_t count, int32_t total_blocks, const float* coef_dev, void* stream);
+
+/* Loss scaling on the device (torch.amp.GradScaler's recipe, main.py:320-328, without a host decision: capturable).
+ * The gradients carry the loss scale S; nothing ever unscales them in a pass of its own.
+ *   cc_grad_scaler_stats_f32   the successor of cc_grad_clip_coef_f32 (one workgroup, the same fixed order over the partial
+ *       sums of cc_grad_norm_partials_f32): out3[0] = ||g / S||, out3[1] = the multiplier inv_scale * min(1, max_norm /
+ *       (||g / S|| + 1e-6)) (max_norm < 0: no clipping, the multiplier is inv_scale), out3[2] = found_inf (1.f when a gradient
+ *       element is inf or NaN - the fp64 sum of squares of fp32 values is non-finite exactly then - else 0.f).  For a
+ *       power-of-two S, out3[0] and the clip coefficient are bit for bit what cc_grad_clip_coef_f32 gives on g / S.
+ *   cc_adamw_multi_scaled_f32  cc_adamw_multi_f32 with the multiplier as its coef_dev and the flag: *found_inf_dev != 0 ->
+ *       the launch writes nothing; otherwise bit for bit cc_adamw_multi_f32(coef_dev = mult_dev).
+ *   cc_grad_scaler_update_f32  GradScaler.update on one lane.  scale2 = {scale, 1 / scale}; counters3 = {growth tracker,
+ *       steps taken, steps skipped}.  found_inf: scale *= backoff, tracker = 0, skipped += 1; else taken += 1, tracker += 1
+ *       and at tracker == growth_interval: scale *= growth (kept if that is not finite), tracker = 0.  scale2[1] is renewed. */
+int cc_grad_scaler_stats_f32(const void* ws, int32_t total_blocks, const float* inv_scale_dev, float max_norm, float* out3,
+                             void* stream);
+int cc_adamw_multi_scaled_f32(const void* items_dev, int32_t count, int32_t total_blocks, const void* scalars_dev,
+                              const float* mult_dev, const float* found_inf_dev, void* stream);
+int cc_grad_scaler_update_f32(float* scale2, const float* found_inf_dev, int32_t* counters3, float growth_factor,
+                              float backoff_factor, int32_t growth_interval, void* stream);
 
 /* ==========================================================================================
  * sim_header 'seqTransf' (modules/clip4clip.py:335-349, the loose_type head the reference runs besides meanP).
