@@ -448,3 +448,64 @@ def test_bertadam_multi_tensor_launches_equal_per_tensor_steps(sizes):
         for j in range(len(ns)):
             assert torch.equal(pa[j], pb[j]), (it, j, ns[j])
             assert torch.equal(oa.state[pa[j]]['next_v'], ob.state[pb[j]]['next_v']) and torch.equal(pa[j].grad, pb[j].grad)
+
+
+def test_bertadam_captured_step_keeps_its_tables_through_eager_uploads():
+    """A captured capturable BertAdam step reads record tables of its own: an eager step in between - on fewer parameters,
+    then on all of them with gradients at other addresses, so that both tables (small: 1 and 8192 elements, large: 8193 and
+    20000) are uploaded afresh - changes nothing a replay reads.  After every step the parameters, next_m, next_v and the
+    host-side state['step'] equal, bit for bit, those of a non-capturable BertAdam taking one step per call."""
+    ns = [1, 8192, 8193, 20000]
+    g = _gen(4)
+    init = [torch.randn(n, device=DEV, generator=g) for n in ns]
+    pa = [torch.nn.Parameter(t.clone()) for t in init]
+    pb = [torch.nn.Parameter(t.clone()) for t in init]
+    oa, ob = _adam_groups(pa, 1.0)(False), _adam_groups(pb, 1.0)(True)
+    static = [torch.zeros(n, device=DEV) for n in ns]
+
+    def grads(use, static_b):
+        for j, n in enumerate(ns):
+            gr = torch.randn(n, device=DEV, generator=g) * (0.5 if j % 3 else 5.0) / math.sqrt(n)     # (clipped: tensors 0, 3)
+            if j not in use:
+                pa[j].grad = pb[j].grad = None
+                continue
+            pa[j].grad = gr.clone()
+            pb[j].grad = static[j] if static_b else gr.clone()
+            if static_b:
+                static[j].copy_(gr)
+
+    def same(what):
+        for j in range(len(ns)):
+            sa, sb = oa.state[pa[j]], ob.state[pb[j]]
+            assert torch.equal(pa[j], pb[j]), (what, j)
+            assert torch.equal(sa['next_m'], sb['next_m']) and torch.equal(sa['next_v'], sb['next_v']), (what, j)
+            assert sa['step'] == sb['step'], (what, j, sa['step'], sb['step'])
+
+    def replay(what):
+        grads(range(4), True)
+        oa.step()
+        ob.refresh_lr()
+        graph.replay()
+        ob.advance()
+        same(what)
+
+    grads(range(4), True)
+    oa.step()
+    ob.step()
+    same("eager")
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):                                   # (the capture pass does not execute)
+        ob.step()
+    replay("first replay")
+    grads((0, 3), False)                                            # other record bytes, small and large: fresh uploads
+    oa.step()
+    ob.step()
+    same("eager on a subset")
+    replay("replay after the subset")
+    grads(range(4), False)                                          # tables of the captured size, other gradient addresses
+    oa.step()
+    ob.step()
+    same("eager on other gradients")
+    replay("last replay")
+    assert [oa.state[p]['step'] for p in pa] == [6, 5, 5, 6]

@@ -102,9 +102,9 @@ def test_frozen_step_gradients_against_reference_autograd(k):
 # ----------------------------------------------------------------------------- 2. nothing frozen = the step as it was
 def test_nothing_frozen_is_bit_identical_to_the_glue_front():
     """No call, freeze_cip_layers(-1) and the towers' earlier front (the patches as a torch reshape + cast, kept reachable under
-    train._GLUE_FRONT for this comparison - not stored bits of an earlier commit): the loss and all 74 gradients are the same
-    bits."""
-    from centerclip_amd import train as cctrain
+    train.towers._GLUE_FRONT for this comparison - not stored bits of an earlier commit): the loss and all 74 gradients are the
+    same bits."""
+    from centerclip_amd.train import towers as cctrain
     runs = []
     for mode in ("none", "minus1", "glue"):
         g, model, inputs = _model_and_inputs()
