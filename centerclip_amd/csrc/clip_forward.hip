@@ -534,6 +534,14 @@ int cc_patch_gather_f16(const cc_frames* frames, int32_t F, int32_t resolution, 
     return cc_launch_im2col(*frames, static_cast<_Float16*>(out_f16), F, resolution, patch, static_cast<hipStream_t>(stream));
 }
 
+// linear_patch '3d': the gathers of the fused forward (im2col3d_f16_kernel, the P3D strip gather) on their own
+int cc_patch_gather3d_f16(const cc_frames* frames, int32_t F, int32_t T, int32_t resolution, int32_t patch, void* out_f16,
+                          void* stream) {
+    if (!frames || !frames->data || !out_f16 || F <= 0 || T <= 0 || patch <= 0 || resolution <= 0) return CC_ERR_INVALID;
+    if ((patch & 7) || resolution % patch || F % T || !frames_base_ok(frames)) return CC_ERR_INVALID;
+    return cc_launch_im2col3d(*frames, static_cast<_Float16*>(out_f16), F, T, resolution, patch, static_cast<hipStream_t>(stream));
+}
+
 int cc_vit_encode(const cc_vit_model* m, const float* video, int32_t B, int32_t T, float* features,
                   float* hidden_out, int64_t* medoids_out, const int64_t* forced_medoids, void* ws, size_t ws_bytes,
                   void* stream) {

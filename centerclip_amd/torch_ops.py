@@ -885,6 +885,26 @@ def _(frames, resolution, patch):
     return frames.new_empty((frames.shape[0] * g * g, 3 * patch * patch), dtype=torch.float16)
 
 
+@custom_op(NS + "::patch_gather3d", mutates_args=(), device_types="cuda")
+def patch_gather3d(frames: torch.Tensor, T: int, resolution: int, patch: int) -> torch.Tensor:
+    """The patch gather of linear_patch '3d' on its own (cc_patch_gather3d_f16): frames as patch_gather, clips of T frames ->
+    the fp16 patch matrix [F * g * g, 9 * p * p], columns (c, kt, kh, kw) as conv2.weight.view(width, -1) has them; tap kt of
+    frame f is frame f + kt - 1 of the same clip, zeros outside the clip (Conv3d padding (1, 0, 0), modules/clip.py:313-317)."""
+    from .clip import frames_descriptor
+    fr, frames = frames_descriptor(frames)
+    F, g = frames.shape[0], resolution // patch
+    out = _e(F * g * g, 9 * patch * patch, like=frames, dtype=torch.float16)
+    L.check(L.lib().cc_patch_gather3d_f16(ctypes.byref(fr), F, int(T), int(resolution), int(patch), L.ptr(out), _st(frames)),
+            "cc_patch_gather3d_f16")
+    return out
+
+
+@patch_gather3d.register_fake
+def _(frames, T, resolution, patch):
+    g = resolution // patch
+    return frames.new_empty((frames.shape[0] * g * g, 9 * patch * patch), dtype=torch.float16)
+
+
 @custom_op(NS + "::clip_encode_out", mutates_args=("vfeat", "tfeat", "medoids_out"), device_types="cuda")
 def clip_encode_out(frames: torch.Tensor, ids: torch.Tensor, vhandle: int, thandle: int, B: int, T: int,
                     vfeat: torch.Tensor, tfeat: torch.Tensor, medoids_out: Optional[torch.Tensor],

@@ -7,8 +7,9 @@
     loop     train_epoch and GraphedTrainStep (the step captured into a hipGraph)
 
 CLIP4Clip.forward in training mode runs on the towers, so a training step reaches every parameter; master weights are fp32,
-the matrix cores get fp16 operands with fp32 accumulation.  Not built: training with linear_patch='3d' or mean_residual, and
-gradient accumulation inside the captured step.
+the matrix cores get fp16 operands with fp32 accumulation.  linear_patch='3d' trains conv2 on the 3-d patch gather (conv1 takes
+no part and gets no gradient, as in the reference).  Not built: training with mean_residual, and gradient accumulation inside the
+captured step.
 """
 from .block import (LayerNormFunction, LinearFunction, ResidualAttentionBlockFunction, _PARAM_ORDER, _cast_scaled,  # noqa: F401
                     _cast_transpose, _column_sums, _grad_linear, _layernorm, _linear_resid, _linear_unscaled, _ln_backward,

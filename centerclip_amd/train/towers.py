@@ -79,22 +79,47 @@ def text_prefix_blocks(clip):
     return _prefix_blocks(clip.transformer)
 
 
+def _front(vis, x, F, g):
+    """The patch embedding's rows [F * g * g, W] -> class and position embedding, ln_pre, the blocks (clip.py:324-338)."""
+    W = vis.width
+    x = x.view(F, g * g, W)
+    cls = vis.class_embedding.to(x.dtype) + torch.zeros(F, 1, W, dtype=x.dtype, device=x.device)
+    x = torch.cat([cls, x], dim=1) + vis.positional_embedding.to(x.dtype)
+    x = _layernorm(vis.ln_pre, x.reshape(F * (g * g + 1), W)).view(F, g * g + 1, W)
+    return _blocks(vis.transformer, x.permute(1, 0, 2).contiguous()).permute(1, 0, 2)          # NLD -> LND -> NLD
+
+
 def encode_image_train(clip, video, video_frame):
-    """CLIP.encode_image (modules/clip.py:460-469 with VisualTransformer.forward :320-345, linear_patch '2d') with gradients:
+    """CLIP.encode_image (modules/clip.py:460-469 with VisualTransformer.forward :304-345) with gradients:
     video [F, 3, H, W] fp32, or the loader's uint8 frames [F, 3, H, W] / [F, H, W, 3] (the patch gather applies
-    dataloaders/transforms.py's u8/255 -> (x - mean)/std) -> (features [F', embed_dim], cluster_loss)."""
+    dataloaders/transforms.py's u8/255 -> (x - mean)/std) -> (features [F', embed_dim], cluster_loss).
+    linear_patch '3d' (clip.py:306-317): conv2 over clips of video_frame frames as a GEMM over the 3-d patch gather's rows;
+    conv1 takes no part and receives no gradient."""
     vis = clip.visual
-    if vis.linear_patch != '2d':
-        raise NotImplementedError("training towers: linear_patch='3d' is not built")
-    L.require_device(video)
     F, p, W = video.shape[0], vis.patch_size, vis.width
     g = vis.input_resolution // p
+    p3d = vis.linear_patch == '3d'
+    if p3d:
+        if not video_frame or video_frame <= 0 or F % video_frame:
+            raise ValueError("linear_patch='3d': video_frame %r must divide the %d frames (clip.py:307)" % (video_frame, F))
+        if p % 8:
+            raise ValueError("linear_patch='3d': patch size %d is off the patch gather's 8-wide grid" % p)
+        seg = vis.shift_segment()
+        if seg is not None and video_frame != seg:
+            raise NotImplementedError("linear_patch='3d' with a shift module needs video_frame == original_frame")
+    L.require_device(video)
     n = visual_prefix_blocks(vis)
     if n is not None:
         with torch.no_grad():
             x = vis.encode_prefix(video, video_frame, n, forced_medoids=getattr(vis, "forced_medoids", None))
         # (frame-major rows: the first trainable block's own permute back finds them contiguous, no copy)
         x = _blocks(vis.transformer, x.permute(1, 0, 2), start=n).permute(1, 0, 2)
+    elif p3d:
+        # conv2 (kernel (3, p, p), stride (1, p, p), zero padding 1 along t, no bias) as a GEMM over the 3-d patch rows
+        # (c, kt, kh, kw): the fp16 matrix is written once and is LinearFunction's operand and saved activation
+        a = torch.ops.centerclip.patch_gather3d(video if video.dtype == torch.uint8 else video.float(), int(video_frame),
+                                                vis.input_resolution, p)
+        x = _front(vis, LinearFunction.apply(a, vis.conv2.weight.view(W, -1), None), F, g)
     else:
         if _GLUE_FRONT or (p % 8 and video.dtype != torch.uint8):
             # (a patch size off the gather's 8-wide grid - no CLIP tower has one - keeps the reshape, as before)
@@ -106,11 +131,7 @@ def encode_image_train(clip, video, video_frame):
             # the encoders' patch gather: the fp16 patch matrix straight from the frames - LinearFunction's operand and saved
             # activation (no fp32 permute-copy of the patches, no separate cast)
             a = torch.ops.centerclip.patch_gather(video if video.dtype == torch.uint8 else video.float(), vis.input_resolution, p)
-        x = LinearFunction.apply(a, vis.conv1.weight.view(W, -1), None).view(F, g * g, W)
-        cls = vis.class_embedding.to(x.dtype) + torch.zeros(F, 1, W, dtype=x.dtype, device=x.device)
-        x = torch.cat([cls, x], dim=1) + vis.positional_embedding.to(x.dtype)
-        x = _layernorm(vis.ln_pre, x.reshape(F * (g * g + 1), W)).view(F, g * g + 1, W)
-        x = _blocks(vis.transformer, x.permute(1, 0, 2).contiguous()).permute(1, 0, 2)          # NLD -> LND -> NLD
+        x = _front(vis, LinearFunction.apply(a, vis.conv1.weight.view(W, -1), None), F, g)
     cls_rows = x[:, 0, :].contiguous()                        # ln_post(x) @ proj, of which encode_image keeps the CLS row
     feats = LinearFunction.apply(_layernorm(vis.ln_post, cls_rows), vis.proj.t(), None)
     return feats, torch.zeros((), device=video.device)

@@ -13,14 +13,15 @@ the path is a correctness slice - per-op launches from Python, nothing fused or 
 
 --freeze_layer_num K is handed to model.freeze_cip_layers as main.py:102 does (every shipped launcher passes 0; default -1:
 nothing frozen): the frozen prefix of each tower then runs on the fused forward and gets no gradient work.  --uint8 1 draws
-uint8 frames, as the loader yields them before its transform; the patch gather normalises them.
+uint8 frames, as the loader yields them before its transform; the patch gather normalises them.  --linear_patch 3d trains
+the Conv3d patch embedding (conv2) on the 3-d patch gather; the reference's freeze rule freezes nothing for such a model.
 
 --precision amp is the launchers' setting (main.py:160 builds a GradScaler, train_epoch takes its scaler branch :320-328):
 here a train.DeviceGradScaler - loss scaling, inf / NaN check, step skipping and the scale update all on the device - drives
 the eager loop and, inside the graph, the captured step; the taken / skipped counters are printed at the end.
 
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
-                                       [--freeze_layer_num 0] [--uint8 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
+                                       [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
 import argparse
@@ -49,7 +50,7 @@ def shift_plan(args):
     return args
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--batch", type=int, default=16)
@@ -70,7 +71,13 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-7, help="learning rate of the new modules; the CLIP groups get lr * --coef_lr")
     ap.add_argument("--coef_lr", type=float, default=1e-3, help="main.py's --coef_lr")
     ap.add_argument("--same_batch", type=int, default=0, help="train every step on the first batch (shows the loss going down)")
-    a = ap.parse_args()
+    ap.add_argument("--linear_patch", choices=["2d", "3d"], default="2d",
+                    help="params.py's --linear_patch; 3d: conv2 over (t, h, w) trains (random init), conv1 takes no part")
+    return ap
+
+
+def main():
+    a = build_parser().parse_args()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("LOCAL_RANK", "0"))
     device = torch.device("cuda", rank)
@@ -82,6 +89,7 @@ def main():
         c = dict(c, name="cfg5-shaped: ViT-B/16", patch=16, T_new=4, K=100)
     args = bench.task_config(c)
     args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
+    args.linear_patch = a.linear_patch
     if a.algo != "kmediods++":
         args.cluster_algo = a.algo
         shift_plan(args)

@@ -593,6 +593,16 @@ int cc_text_encode_prefix(const cc_text_model* m, const int64_t* ids, int32_t Bt
 int cc_patch_gather_f16(const cc_frames* frames, int32_t F, int32_t resolution, int32_t patch, void* out_f16,
                         void* stream);
 
+/* The same for linear_patch '3d' (training with conv2, modules/clip.py:296-317: Conv3d kernel (3, patch, patch), stride
+ * (1, patch, patch), padding (1, 0, 0) over clips of T frames): frames (F frames, F % T == 0, clip b = frames b*T .. b*T + T - 1)
+ * -> out_f16 [F * (resolution/patch)^2, 9 * patch^2] fp16, columns (c, kt, kh, kw) as conv2.weight is flattened.  Tap kt of
+ * frame f holds frame f + kt - 1 of the same clip, exact zeros where that frame lies outside the clip.  uint8 frames get the
+ * loader's three fp32 operations as above.  These are the gathers of the fused forward.  No allocation, no synchronisation.
+ * patch % 8 == 0, resolution % patch == 0, F % T == 0, a uint8 base 8-byte aligned, an fp32 base 16-byte aligned - else
+ * CC_ERR_INVALID before any launch; uint8 frames with a patch that is no power of two: CC_ERR_UNSUPPORTED. */
+int cc_patch_gather3d_f16(const cc_frames* frames, int32_t F, int32_t T, int32_t resolution, int32_t patch, void* out_f16,
+                          void* stream);
+
 /* S2 - the meanP similarity tail, CLIP4Clip._loose_similarity (modules/clip4clip.py:357-366) with
  * _mean_pooling_for_similarity_visual (:305-316):
  *   v_hat = v/|v| per frame; v_bar = sum_t mask*v_hat / max(sum_t mask, 1 if 0); v_bar /= |v_bar|
