@@ -74,6 +74,21 @@ def declare(lib):
     lib.cc_contrastive_loss_grad_f32.restype = c.c_int
     lib.cc_contrastive_loss_grad_dev_f32.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, sz, vp]
     lib.cc_contrastive_loss_grad_dev_f32.restype = c.c_int
+    lib.cc_contrastive_grad_dsl_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.cc_contrastive_grad_dsl_workspace_bytes.restype = sz
+    lib.cc_contrastive_loss_grad_dsl_f32.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
+    lib.cc_contrastive_loss_grad_dsl_f32.restype = c.c_int
+    lib.cc_contrastive_loss_grad_dsl_dev_f32.argtypes = [vp, vp, vp, i64, i64, i32, i32, i32, f32, vp, f32, vp, vp, vp, vp, vp, sz,
+                                                         vp]
+    lib.cc_contrastive_loss_grad_dsl_dev_f32.restype = c.c_int
+    lib.cc_dsl_col_stats_workspace_bytes.argtypes = [i32, i32]
+    lib.cc_dsl_col_stats_workspace_bytes.restype = sz
+    lib.cc_dsl_col_stats_f32.argtypes = [vp, i32, i32, i64, vp, vp, vp, sz, vp]
+    lib.cc_dsl_col_stats_f32.restype = c.c_int
+    lib.cc_dsl_rescale_stats_f32.argtypes = [vp, vp, vp, i32, vp]
+    lib.cc_dsl_rescale_stats_f32.restype = c.c_int
+    lib.cc_dsl_apply_f32.argtypes = [vp, i32, i32, i64, vp, vp, i32, vp]
+    lib.cc_dsl_apply_f32.restype = c.c_int
     lib.cc_normalize_rows_f32.argtypes = [vp, vp, i32, i32, vp]
     lib.cc_normalize_rows_f32.restype = c.c_int
     lib.cc_loose_similarity_grouped_f32.argtypes = [vp, vp, vp, i32, i64, i64, i64, i64, i32, i32, i32, i32, f32, vp, i32,

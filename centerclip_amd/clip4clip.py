@@ -43,6 +43,9 @@ class CLIP4Clip(nn.Module):
         self.final_frames = task_config.target_frames_blocks[-1]
         self.f_frame_duration = self.video_frames // self.final_frames
         self.pre_visual_pooling = getattr(task_config, "pre_visual_pooling", 0)
+        # CAMoE dual softmax (params.py:278; the reference stores the flag and keeps both uses commented out, clip4clip.py:430-432,
+        # main.py:526-532): logits S -> S * softmax(S, dim=0) * len(S), in get_similarity_logits, eval_epoch and the training loss
+        self.camoe_dsl = bool(getattr(task_config, "camoe_dsl", False))
         self.clip, self.clip_config = build_clip_model(clip_state_dict, convert_fp16=True,
                                                        linear_patch=self.linear_patch, cut_top_layer=0,
                                                        load_state_dict=True, is_eval=False,
@@ -231,7 +234,7 @@ class CLIP4Clip(nn.Module):
             if ccdist.world_size() > 1:              # ONE collective for the three tensors, gradient slices of the own shard back
                 vis, vmask, seq = PackedAllGather.apply(vis, vmask, seq)
             # (logit_scale is read on the device: the optimizer changes it every step, and a host copy would be a synchronisation)
-            sim_loss, _, _ = contrastive_loss(seq, vis, vmask, self.clip.logit_scale)
+            sim_loss, _, _ = contrastive_loss(seq, vis, vmask, self.clip.logit_scale, dsl=self.camoe_dsl)
             output_dict['loss'] = sim_loss + cluster_loss
             output_dict['cluster_loss'] = cluster_loss
             output_dict['sim_loss'] = sim_loss
@@ -345,4 +348,7 @@ class CLIP4Clip(nn.Module):
         if visual_output.ndim == 3 and video_mask.shape[1] != visual_output.shape[1]:
             video_mask = self.get_video_mask_after_cluster(video_mask)
         assert self.sim_header in ["meanP", "seqTransf"]
-        return self._loose_similarity(sequence_output, visual_output, attention_mask, video_mask), ()
+        logits = self._loose_similarity(sequence_output, visual_output, attention_mask, video_mask)
+        if self.camoe_dsl:                       # (clip4clip.py:430-432, over the rows this call was given)
+            logits = ops.dual_softmax(logits)
+        return logits, ()

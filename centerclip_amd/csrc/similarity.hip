@@ -833,6 +833,100 @@ __global__ __launch_bounds__(256) void ctr_grad_feat_kernel(const float* __restr
     }
 }
 
+// ---------------------------------------------------------------------------- camoe_dsl: the dual-softmax loss in the chain
+// loss = (CrossEn(D) + CrossEn(D^T)) / 2,  D = n S (.) P,  P_ij = exp(S_ij - m_j) / s_j  (softmax over the texts of a column).
+// With G = dL/dD (the formula above, on D) the gradient that reaches S is
+//   dS_ij = n P_ij (G_ij (1 + S_ij) - t_j),   t_j = sum_k G_kj S_kj P_kj
+// and d logit_scale = sum_ij dS_ij S_ij as before.  The rest of the chain (prepare, S, CrossEn, mean, the feature gradients)
+// is the plain loss's, fed with D and with dS in w.G.
+struct DslWs {
+    float* cm;     // [n]  column maxima of S
+    float* cs;     // [n]  column sums of exp(S - cm)
+    float* D;      // [n, n]
+    float* t;      // [n]
+    size_t total;
+};
+
+DslWs dsl_carve(void* ws, size_t base, int n) {
+    DslWs d{};
+    size_t off = base;
+    auto take = [&](size_t floats) {
+        float* p = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + off) : nullptr;
+        off += cc_align_up(floats * sizeof(float), 256);
+        return p;
+    };
+    d.cm = take(n); d.cs = take(n); d.D = take((size_t)n * n); d.t = take(n);
+    d.total = off;
+    return d;
+}
+
+__device__ __forceinline__ float dsl_p(float s_ij, float m_j, float sum_j) { return expf(s_ij - m_j) / sum_j; }
+
+// one wave per column j of S: (m_j, s_j)
+__global__ __launch_bounds__(256) void ctr_dsl_col_stats_kernel(CtrWs w, DslWs d, int n) {
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= n) return;
+    float mx = -INFINITY;
+    bool nan = false;
+    for (int i = lane; i < n; i += 64) {
+        const float x = w.S[(int64_t)i * n + j];
+        nan |= (x != x);
+        mx = fmaxf(mx, x);
+    }
+    mx = cc_wave_max(mx);
+    if (__any(nan)) mx = NAN;                                          // (fmaxf drops a NaN: torch.softmax keeps it)
+    float s = 0.f;
+    for (int i = lane; i < n; i += 64) s += expf(w.S[(int64_t)i * n + j] - mx);
+    s = cc_wave_sum(s);
+    if (lane == 0) { d.cm[j] = mx; d.cs[j] = s; }
+}
+
+// D_ij = n S_ij P_ij
+__global__ __launch_bounds__(256) void ctr_dsl_apply_kernel(CtrWs w, DslWs d, int n) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)n * n) return;
+    const int j = (int)(idx % n);
+    const float s = w.S[idx];
+    d.D[idx] = ((float)n * s) * dsl_p(s, d.cm[j], d.cs[j]);
+}
+
+// one wave per column j: G_ij (dL/dD) into w.G, t_j = sum_i G_ij S_ij P_ij
+__global__ __launch_bounds__(256) void ctr_dsl_grad_d_kernel(CtrWs w, DslWs d, int n, float g) {
+    const int lane = threadIdx.x & 63;
+    const int j = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= n) return;
+    const float lse_c = w.nce[n + j] + d.D[(int64_t)j * n + j];
+    const float k = g / (2.0f * (float)n);
+    const float mj = d.cm[j], sj = d.cs[j];
+    float acc = 0.f;
+    for (int i = lane; i < n; i += 64) {
+        const float dij = d.D[(int64_t)i * n + j], s = w.S[(int64_t)i * n + j];
+        const float lse_r = w.nce[i] + d.D[(int64_t)i * n + i];
+        const float gij = k * ((expf(dij - lse_r) + expf(dij - lse_c)) - (i == j ? 2.0f : 0.0f));
+        w.G[(int64_t)i * n + j] = gij;
+        acc += (gij * s) * dsl_p(s, mj, sj);
+    }
+    acc = cc_wave_sum(acc);
+    if (lane == 0) d.t[j] = acc;
+}
+
+// one wave per row i: w.G_ij <- dS_ij (in place: an element is read and written by the same lane), row partial of sum dS S
+__global__ __launch_bounds__(256) void ctr_dsl_grad_sim_kernel(CtrWs w, DslWs d, int n) {
+    const int lane = threadIdx.x & 63;
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    float acc = 0.f;
+    for (int j = lane; j < n; j += 64) {
+        const float s = w.S[(int64_t)i * n + j];
+        const float ds = ((float)n * dsl_p(s, d.cm[j], d.cs[j])) * (w.G[(int64_t)i * n + j] * (1.0f + s) - d.t[j]);
+        w.G[(int64_t)i * n + j] = ds;
+        acc += ds * s;
+    }
+    acc = cc_wave_sum(acc);
+    if (lane == 0) w.dls[i] = acc;
+}
+
 }  // namespace
 
 extern "C" size_t cc_contrastive_grad_workspace_bytes(int32_t n, int32_t Tn, int32_t E) {
@@ -878,6 +972,60 @@ extern "C" int cc_contrastive_loss_grad_dev_f32(const float* text, const float* 
     CC_LAUNCH_CHECK();
     hipLaunchKernelGGL(ctr_grad_feat_kernel, dim3((2 * n + 1 + 3) / 4), dim3(256), 0, st, visual, mk, mask_row_stride,
                        mask_col_stride, n, Tn, E, c, w, d_text, d_visual, d_logit_scale, logit_scale_dev);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+/* ---- camoe_dsl: the same chain with the dual softmax between S and the two CrossEn terms (see DslWs above) */
+extern "C" size_t cc_contrastive_grad_dsl_workspace_bytes(int32_t n, int32_t Tn, int32_t E) {
+    if (n <= 0 || Tn <= 0 || E <= 0) return 0;
+    return dsl_carve(nullptr, ctr_carve(nullptr, n, Tn, E).total, n).total;
+}
+
+extern "C" int cc_contrastive_loss_grad_dsl_f32(const float* text, const float* visual, const int64_t* video_mask,
+                                                int64_t mask_row_stride, int64_t mask_col_stride, int32_t n, int32_t Tn,
+                                                int32_t E, float logit_scale, float grad_scale, float* loss3, float* d_text,
+                                                float* d_visual, float* d_logit_scale, void* ws, size_t ws_bytes, void* stream) {
+    return cc_contrastive_loss_grad_dsl_dev_f32(text, visual, video_mask, mask_row_stride, mask_col_stride, n, Tn, E, logit_scale,
+                                                nullptr, grad_scale, loss3, d_text, d_visual, d_logit_scale, ws, ws_bytes, stream);
+}
+
+extern "C" int cc_contrastive_loss_grad_dsl_dev_f32(const float* text, const float* visual, const int64_t* video_mask,
+                                                    int64_t mask_row_stride, int64_t mask_col_stride, int32_t n, int32_t Tn,
+                                                    int32_t E, float logit_scale, const float* logit_scale_dev, float grad_scale,
+                                                    float* loss3, float* d_text, float* d_visual, float* d_logit_scale, void* ws,
+                                                    size_t ws_bytes, void* stream) {
+    if (!text || !visual || !video_mask || !loss3 || !d_text || !d_visual || !d_logit_scale) return CC_ERR_INVALID;
+    if (n <= 0 || Tn <= 0 || E <= 0) return CC_ERR_INVALID;
+    if (E > 1024) return CC_ERR_UNSUPPORTED;
+    const CtrWs w = ctr_carve(ws, n, Tn, E);
+    const DslWs d = dsl_carve(ws, w.total, n);
+    if (!ws || ws_bytes < d.total) return CC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const float c = expf(logit_scale);
+    const long long* mk = reinterpret_cast<const long long*>(video_mask);
+    const dim3 rows4((n + 3) / 4), blk(256);
+    hipLaunchKernelGGL(ctr_prepare_kernel, dim3((2 * n + 3) / 4), blk, 0, st, text, visual, mk, mask_row_stride, mask_col_stride,
+                       n, Tn, E, w);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctr_sim_kernel, dim3((unsigned)(((int64_t)n * n + 3) / 4)), blk, 0, st, w, n, E, c, logit_scale_dev);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctr_dsl_col_stats_kernel, rows4, blk, 0, st, w, d, n);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctr_dsl_apply_kernel, dim3((unsigned)(((int64_t)n * n + 255) / 256)), blk, 0, st, w, d, n);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cross_entropy_rows_kernel, rows4, blk, 0, st, d.D, n, (int64_t)n, (int64_t)1, w.nce);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cross_entropy_rows_kernel, rows4, blk, 0, st, d.D, n, (int64_t)1, (int64_t)n, w.nce + n);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(contrastive_mean_kernel, dim3(1), blk, 0, st, w.nce, n, loss3);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctr_dsl_grad_d_kernel, rows4, blk, 0, st, w, d, n, grad_scale);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctr_dsl_grad_sim_kernel, rows4, blk, 0, st, w, d, n);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(ctr_grad_feat_kernel, dim3((2 * n + 1 + 3) / 4), blk, 0, st, visual, mk, mask_row_stride, mask_col_stride,
+                       n, Tn, E, c, w, d_text, d_visual, d_logit_scale, logit_scale_dev);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }

@@ -89,6 +89,24 @@ class HipBackend:
     def group_max(sim, groups, n_groups):
         return torch.ops.centerclip.group_max_rows(sim.contiguous(), groups.to(torch.int32).contiguous(), int(n_groups))
 
+    # camoe_dsl (called only when the flag is set): the three steps of D = S * softmax(S, dim=0) * Nt on a row block
+    @staticmethod
+    def dsl_col_stats(sim):
+        """-> (m [cols], s [cols]) of the rows given; no rows: (-inf, 0)"""
+        return torch.ops.centerclip.dsl_col_stats(sim)
+
+    @staticmethod
+    def dsl_rescale_stats(s, m_local, m_global):
+        """s *= exp(m_local - m_global) in place"""
+        torch.ops.centerclip.dsl_rescale_stats_(s, m_local.contiguous(), m_global.contiguous())
+        return s
+
+    @staticmethod
+    def dsl_apply(sim, m, s, n_total):
+        """sim <- n_total * sim * exp(sim - m) / s in place"""
+        torch.ops.centerclip.dsl_apply_(sim, m.contiguous(), s.contiguous(), int(n_total))
+        return sim
+
 
 class _Cache:
     """Features of the items this process encoded, with their positions in the dataset."""
@@ -137,11 +155,26 @@ def _similarity_matrix(model, batch_list_t, batch_list_v, batch_sequence_output_
     return backend.dot_operands(text, video_all, n_video, mult)
 
 
+def _camoe_dsl(model, args=None, explicit=None):
+    """Whether the CAMoE dual softmax applies: the explicit argument, else ``args.camoe_dsl`` when args carries it, else the
+    model's attribute (CLIP4Clip reads it from its task config)."""
+    if explicit is not None:
+        return bool(explicit)
+    if args is not None and hasattr(args, "camoe_dsl"):
+        return bool(args.camoe_dsl)
+    core = model.module if hasattr(model, 'module') else model
+    return bool(getattr(core, "camoe_dsl", False))
+
+
 def _run_on_single_gpu(model, batch_list_t, batch_list_v, batch_sequence_output_list, batch_visual_output_list,
                        args=None):
-    """calculate the similarity between visual output and text output -> NumPy [Nt, Nv]   (main.py:502-534)"""
-    return _similarity_matrix(model, batch_list_t, batch_list_v, batch_sequence_output_list,
-                              batch_visual_output_list).cpu().detach().numpy()
+    """calculate the similarity between visual output and text output -> NumPy [Nt, Nv]   (main.py:502-534).
+    camoe_dsl (``args.camoe_dsl``, else the model's): the dual softmax once over the whole matrix (main.py:526-532)."""
+    sim = _similarity_matrix(model, batch_list_t, batch_list_v, batch_sequence_output_list, batch_visual_output_list)
+    if _camoe_dsl(model, args):
+        m, s_ = HipBackend.dsl_col_stats(sim)
+        HipBackend.dsl_apply(sim, m, s_, sim.shape[0])
+    return sim.cpu().detach().numpy()
 
 
 def _is_distributed_sampler(loader):
@@ -218,7 +251,7 @@ class _GraphedLane:
 
 
 def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False, backend=HipBackend, in_flight=None,
-               similarity_products=None, graphed=False):
+               similarity_products=None, graphed=False, camoe_dsl=None):
     """main.py:381-499 -> (R1, all_infer_time, info_str).  ``shard=True``: clip-sharded over the ranks of the default
     process group (module docstring) - every rank must call it and every rank returns the same numbers.
     ``in_flight`` (not in the reference; > 1 GPU only; default: 2 on a GPU, 1 on the CPU stand-in): n keeps n batches in flight -
@@ -231,7 +264,11 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
     inputs + ONE hipGraph launch per lane (captured on the first batch of each shape; a ragged last batch gets a graph of its
     own) instead of ~70 eager kernel launches - identical rows.  Measured (same loader): one lane 2.82 -> 2.41 ms per batch; with
     two or more lanes the eager launches already overlap and the graphs add nothing (2.15 vs 1.82 ms at two lanes), so it is
-    for the case where a second model instance is not wanted (``in_flight=1``)."""
+    for the case where a second model instance is not wanted (``in_flight=1``).
+    ``camoe_dsl`` (params.py:278; the reference keeps its use commented out, main.py:526-532): rank D = S * softmax(S, dim=0) * Nt
+    instead of S, in both directions.  None = ``args.camoe_dsl`` when ``args`` carries it, else the model's attribute.  Sharded:
+    every rank takes the column statistics of its row block, they are combined with an all-reduce MAX and an all-reduce SUM
+    (2 x Nv floats), and each block is rewritten in place - the matrix still never exists on one device."""
     log = log or (lambda s: None)
     if in_flight is None:
         in_flight = 2 if (torch.cuda.is_available() and torch.device(device).type == "cuda") else 1
@@ -328,7 +365,9 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
             return 0
         n_text = n_items if n_items is not None else total
         n_video = len(last_sentence) if multi else n_text
-        tv_metrics, vt_metrics, shape = _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world, be)
+        # (flag off: the call as it always was - tests replace _sharded_metrics with recorders of that signature)
+        dsl_kw = {"dsl": True} if _camoe_dsl(model, args, camoe_dsl) else {}
+        tv_metrics, vt_metrics, shape = _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world, be, **dsl_kw)
     if multi:
         log("sim matrix size: {} sentences x {} videos ({} groups)".format(shape[0], shape[1], n_video))
     else:
@@ -343,9 +382,10 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
     return tv_metrics['R1'], all_infer_time, info_str
 
 
-def _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world, be):
+def _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world, be, dsl=False):
     """Row block of the similarity matrix for this process' text rows + the rank metrics of both directions.  world == 1:
-    the block is the whole matrix and no collective runs.  -> (tv_metrics, vt_metrics, (Nt, Nv))."""
+    the block is the whole matrix and no collective runs.  -> (tv_metrics, vt_metrics, (Nt, Nv)).  ``dsl``: the block is
+    rewritten with the CAMoE dual softmax of the WHOLE matrix first and everything below ranks that."""
     text_pos = torch.cat(cache.text_pos) if cache.text_pos else torch.zeros(0, dtype=torch.long)
     video_pos = torch.cat(cache.video_pos) if cache.video_pos else torch.zeros(0, dtype=torch.long)
     # the cached rows are the backend's operand rows of the final product (HIP: split-fp16 planes, [rows, 3E] fp16)
@@ -353,10 +393,16 @@ def _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world,
     E = parts[0].shape[-1] if parts else 0
     dtype = parts[0].dtype if parts else torch.float32
     if world > 1:                                       # ranks must agree on the geometry before any payload moves
-        sizes = ccdist.all_gather_ints([n_text, n_video, E, len(text_pos), len(video_pos)], device)
+        # (+ the operand rows' dtype: a rank that received no item at all has no row to read it from, and a collective over
+        #  buffers of different element sizes aborts the process group)
+        kinds = [torch.float32, torch.float16, torch.bfloat16, torch.float64]
+        sizes = ccdist.all_gather_ints([n_text, n_video, E, len(text_pos), len(video_pos), kinds.index(dtype) if parts else -1],
+                                       device)
         if len({tuple(s[:2]) for s in sizes}) != 1:
             raise RuntimeError("eval_epoch(shard=True): ranks disagree on the dataset size %s" % (sizes,))
         E = max(s[2] for s in sizes)
+        if not parts and max(s[5] for s in sizes) >= 0:
+            dtype = kinds[max(s[5] for s in sizes)]
         if sum(s[3] for s in sizes) != n_text or sum(s[4] for s in sizes) != n_video:
             raise RuntimeError("eval_epoch(shard=True): the ranks' shards do not add up to the dataset (%s) - every rank "
                                "must iterate the same unsharded loader or a DistributedSampler(shuffle=False)" % (sizes,))
@@ -378,6 +424,21 @@ def _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world,
     mult = T.logit_multiplier(core._logit_scale_value())
     nloc = text.shape[0]
     block = be.dot_operands(text, video_all, n_video, mult) if nloc else torch.zeros(0, n_video, device=device)
+    if dsl:
+        # ---- camoe_dsl: column statistics of the local rows (none: the neutral (-inf, 0)), combined over the ranks, then
+        # D = S * softmax(S, dim=0) * Nt in place
+        col_m, col_s = be.dsl_col_stats(block)
+        if world > 1:
+            # a column that holds a NaN (a fully masked clip) has m = NaN, and a MAX all-reduce may drop or keep a NaN
+            # depending on the order of its operands: +inf is ordered and leaves the column NaN all the same (exp(x - inf) = 0
+            # over s = s * exp(inf - inf) = NaN)
+            m_all = torch.where(torch.isnan(col_m), torch.full_like(col_m, float("inf")), col_m)
+            ccdist.all_reduce_(m_all, "max")
+            be.dsl_rescale_stats(col_s, col_m, m_all)
+            ccdist.all_reduce_(col_s, "sum")
+            col_m = m_all
+        if nloc:
+            be.dsl_apply(block, col_m, col_s, n_text)
     # ---- text -> video: rank of the ground-truth column in every local row
     c3 = be.counts_cols(block, gt_cols.to(torch.int32)) if nloc else torch.zeros(0, 3, dtype=torch.int32, device=device)
     truth = block.gather(1, gt_cols.view(-1, 1)).squeeze(1) if nloc else torch.zeros(0, device=device)

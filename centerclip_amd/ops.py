@@ -101,6 +101,18 @@ def scaled_dot_nt(a, b, mult=1.0, out=None):
     return out
 
 
+def dual_softmax(sim, n_total=None):
+    """CAMoE dual softmax (camoe_dsl; clip4clip.py:430-432): sim * softmax(sim, dim=0) * n_total as a new [rows, cols] fp32
+    tensor; n_total = len(sim) unless given (a row block of a larger matrix whose statistics the caller combines uses
+    dsl_col_stats / dsl_rescale_stats_ / dsl_apply_ directly, as eval_epoch(shard=True) does)."""
+    L.require_device(sim)
+    _need(sim.dim() == 2 and sim.shape[1] > 0, "dual_softmax: sim [rows, cols]")
+    out = sim.float().clone(memory_format=torch.contiguous_format)
+    m, s = _ops.dsl_col_stats(out)
+    _ops.dsl_apply_(out, m, s, out.shape[0] if n_total is None else int(n_total))
+    return out
+
+
 def fold_layernorm_linear(weight, bias, gamma, beta):
     """-> (w' fp16 [N,K], c1 [N], c2 [N]): LN(x) W^T + b == rstd (x w'^T - mu c1) + c2."""
     L.require_device(weight, gamma, beta)

@@ -1178,6 +1178,92 @@ def _(text, visual, video_mask, logit_scale):
     return text.new_empty((3,)), torch.empty_like(text), torch.empty_like(visual), text.new_empty((1,))
 
 
+def _contrastive_grad_dsl(text, visual, video_mask, scale_value, scale_dev):
+    n, Tn, E = visual.shape
+    loss3 = _e(3, like=text, dtype=torch.float32)
+    d_text, d_visual = torch.empty_like(text), torch.empty_like(visual)
+    d_ls = _e(1, like=text, dtype=torch.float32)
+    ws = L.workspace(L.lib().cc_contrastive_grad_dsl_workspace_bytes(n, Tn, E), text.device)
+    head = (L.ptr(text), L.ptr(visual), L.ptr(video_mask), video_mask.stride(0), video_mask.stride(1), n, Tn, E)
+    tail = (1.0, L.ptr(loss3), L.ptr(d_text), L.ptr(d_visual), L.ptr(d_ls), L.ptr(ws), ws.numel(), _st(text))
+    if scale_dev is None:
+        L.check(L.lib().cc_contrastive_loss_grad_dsl_f32(*head, float(scale_value), *tail), "cc_contrastive_loss_grad_dsl_f32")
+    else:
+        L.check(L.lib().cc_contrastive_loss_grad_dsl_dev_f32(*head, 0.0, L.ptr(scale_dev), *tail),
+                "cc_contrastive_loss_grad_dsl_dev_f32")
+    return loss3, d_text, d_visual, d_ls
+
+
+@custom_op(NS + "::contrastive_loss_grad_dsl", mutates_args=(), device_types="cuda")
+def contrastive_loss_grad_dsl(text: torch.Tensor, visual: torch.Tensor, video_mask: torch.Tensor,
+                              logit_scale: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """contrastive_loss_grad with the CAMoE dual softmax between the logits and the two CrossEn terms (camoe_dsl):
+    D = n * S * softmax(S, dim=0); same arguments and results."""
+    return _contrastive_grad_dsl(text, visual, video_mask, logit_scale, None)
+
+
+@contrastive_loss_grad_dsl.register_fake
+def _(text, visual, video_mask, logit_scale):
+    return text.new_empty((3,)), torch.empty_like(text), torch.empty_like(visual), text.new_empty((1,))
+
+
+@custom_op(NS + "::contrastive_loss_grad_dsl_dev", mutates_args=(), device_types="cuda")
+def contrastive_loss_grad_dsl_dev(text: torch.Tensor, visual: torch.Tensor, video_mask: torch.Tensor,
+                                  logit_scale: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """contrastive_loss_grad_dsl with logit_scale read from the device (a 0-d / 1-element fp32 tensor: the parameter itself)."""
+    return _contrastive_grad_dsl(text, visual, video_mask, 0.0, logit_scale)
+
+
+@contrastive_loss_grad_dsl_dev.register_fake
+def _(text, visual, video_mask, logit_scale):
+    return text.new_empty((3,)), torch.empty_like(text), torch.empty_like(visual), text.new_empty((1,))
+
+
+@custom_op(NS + "::dsl_col_stats", mutates_args=(), device_types="cuda")
+def dsl_col_stats(sim: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """camoe_dsl: sim [rows, cols] fp32 (unit column stride) -> (m [cols] = column maxima, s [cols] = sum_i exp(sim_ij - m_j));
+    rows == 0 gives (-inf, 0), a NaN in a column makes its pair NaN.  Fixed summation order."""
+    rows, cols = sim.shape
+    m = _e(cols, like=sim, dtype=torch.float32)
+    s = _e(cols, like=sim, dtype=torch.float32)
+    nb = L.lib().cc_dsl_col_stats_workspace_bytes(rows, cols)
+    ws = L.workspace(nb, sim.device) if rows else None
+    L.check(L.lib().cc_dsl_col_stats_f32(L.ptr(sim) if rows else None, rows, cols, sim.stride(0) if rows else cols, L.ptr(m),
+                                         L.ptr(s), L.ptr(ws), ws.numel() if rows else 0, _st(sim)), "cc_dsl_col_stats_f32")
+    return m, s
+
+
+@dsl_col_stats.register_fake
+def _(sim):
+    return sim.new_empty((sim.shape[1],)), sim.new_empty((sim.shape[1],))
+
+
+@custom_op(NS + "::dsl_rescale_stats_", mutates_args=("s",), device_types="cuda")
+def dsl_rescale_stats_(s: torch.Tensor, m_local: torch.Tensor, m_global: torch.Tensor) -> None:
+    """camoe_dsl, row-sharded: s[j] *= exp(m_local[j] - m_global[j]) in place (0 stays 0) - [cols] contiguous fp32 each."""
+    L.check(L.lib().cc_dsl_rescale_stats_f32(L.ptr(m_local), L.ptr(m_global), L.ptr(s), s.numel(), _st(s)),
+            "cc_dsl_rescale_stats_f32")
+
+
+@dsl_rescale_stats_.register_fake
+def _(s, m_local, m_global):
+    return None
+
+
+@custom_op(NS + "::dsl_apply_", mutates_args=("sim",), device_types="cuda")
+def dsl_apply_(sim: torch.Tensor, m: torch.Tensor, s: torch.Tensor, n_total: int) -> None:
+    """camoe_dsl: sim[i, j] <- n_total * sim[i, j] * exp(sim[i, j] - m[j]) / s[j] in place (sim [rows, cols] fp32, unit column
+    stride; m, s [cols] contiguous fp32)."""
+    rows, cols = sim.shape
+    L.check(L.lib().cc_dsl_apply_f32(L.ptr(sim) if rows else None, rows, cols, sim.stride(0) if rows else cols, L.ptr(m),
+                                     L.ptr(s), int(n_total), _st(sim)), "cc_dsl_apply_f32")
+
+
+@dsl_apply_.register_fake
+def _(sim, m, s, n_total):
+    return None
+
+
 @custom_op(NS + "::rank_counts_ref", mutates_args=(), device_types="cuda")
 def rank_counts_ref(sim: torch.Tensor, ref_vals: torch.Tensor, transpose: bool) -> torch.Tensor:
     """(#greater, #equal) than ref_vals[i] per row of sim (per COLUMN with transpose=True, through the strides): the
@@ -1228,7 +1314,8 @@ def _(sim):
     return sim.new_empty((3,))
 
 
-OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev", "spectral_laplacian", "spectral_graph_laplacian", "spectral_embedding", "svd_sign_flip", "linear_f16", "linear_f16_out", "layernorm", "attention_f16", "fold_layernorm_linear", "row_stats",
+OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev", "contrastive_loss_grad_dsl",
+       "contrastive_loss_grad_dsl_dev", "dsl_col_stats", "dsl_rescale_stats_", "dsl_apply_", "spectral_laplacian", "spectral_graph_laplacian", "spectral_embedding", "svd_sign_flip", "linear_f16", "linear_f16_out", "layernorm", "attention_f16", "fold_layernorm_linear", "row_stats",
        "linear_ln_f16", "inproj_attention_f16", "linear_resid_stats_f16", "head_project", "token_cluster", "token_cluster_train", "token_cluster_backward", "token_apply_selection",
        "batch_kmedoids", "kmedoids_from_dist",
        "pairwise_distance", "pairwise_distance_cross", "token_norms", "vit_encode", "text_encode", "clip_encode_out", "clip_encode",

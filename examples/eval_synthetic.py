@@ -61,12 +61,15 @@ def main():
                     help="similarity head (clip4clip.py:324-367); seqTransf starts from the reference's initialisation trick")
     ap.add_argument("--cross_num_hidden_layers", type=int, default=4, help="blocks of the seqTransf head (params.py default 4)")
     ap.add_argument("--in-flight", type=int, default=None, help="batches in flight (model instances / streams); default: eval_epoch's own (2 on a GPU)")
+    ap.add_argument("--camoe_dsl", type=int, default=0,
+                    help="params.py's --camoe_dsl: rank the CAMoE dual softmax S * softmax(S, dim=0) * len(S) instead of S")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
     args = bench.task_config(c)                              # cfg 2: 12 frames -> 3 segments at block 7, K = 49
     args.cluster_algo = a.algo
     args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
+    args.camoe_dsl = a.camoe_dsl
     if a.algo in ("token_shift", "temporal_shift"):
         shift_plan(args)
     vars(args).update(spectral_sigma=2.0, spectral_graph="HeatKernel", spectral_knn_k=1, spectral_spg=0, svd_correct_sign=1)

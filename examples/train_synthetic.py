@@ -14,14 +14,15 @@ the path is a correctness slice - per-op launches from Python, nothing fused or 
 --freeze_layer_num K is handed to model.freeze_cip_layers as main.py:102 does (every shipped launcher passes 0; default -1:
 nothing frozen): the frozen prefix of each tower then runs on the fused forward and gets no gradient work.  --uint8 1 draws
 uint8 frames, as the loader yields them before its transform; the patch gather normalises them.  --linear_patch 3d trains
-the Conv3d patch embedding (conv2) on the 3-d patch gather; the reference's freeze rule freezes nothing for such a model.
+the Conv3d patch embedding (conv2) on the 3-d patch gather; the reference's freeze rule freezes nothing for such a model.  --camoe_dsl 1 trains on CAMoE's dual-softmax loss (the
+launchers' --camoe_dsl): same step, the loss chain gains the column softmax and its gradient, still without a host read.
 
 --precision amp is the launchers' setting (main.py:160 builds a GradScaler, train_epoch takes its scaler branch :320-328):
 here a train.DeviceGradScaler - loss scaling, inf / NaN check, step skipping and the scale update all on the device - drives
 the eager loop and, inside the graph, the captured step; the taken / skipped counters are printed at the end.
 
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
-                                       [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--lr 1e-3 --coef_lr 1 --same_batch 1]
+                                       [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
 import argparse
@@ -73,6 +74,8 @@ def build_parser():
     ap.add_argument("--same_batch", type=int, default=0, help="train every step on the first batch (shows the loss going down)")
     ap.add_argument("--linear_patch", choices=["2d", "3d"], default="2d",
                     help="params.py's --linear_patch; 3d: conv2 over (t, h, w) trains (random init), conv1 takes no part")
+    ap.add_argument("--camoe_dsl", type=int, default=0,
+                    help="params.py's --camoe_dsl: CAMoE's DSL loss - CrossEn on D = n * S * softmax(S, dim=0), both directions")
     return ap
 
 
@@ -90,6 +93,7 @@ def main():
     args = bench.task_config(c)
     args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
     args.linear_patch = a.linear_patch
+    args.camoe_dsl = a.camoe_dsl
     if a.algo != "kmediods++":
         args.cluster_algo = a.algo
         shift_plan(args)

@@ -697,6 +697,38 @@ int cc_contrastive_loss_grad_dev_f32(const float* text, const float* visual, con
                                      float* d_text, float* d_visual, float* d_logit_scale, void* ws, size_t ws_bytes,
                                      void* stream);
 
+/* camoe_dsl in training (CAMoE's dual-softmax loss; the reference keeps its line commented out at modules/clip4clip.py:430-432):
+ * the chain above with D = n * S (.) softmax(S, dim=0) between the logits and the two CrossEn terms,
+ * loss3 = (CrossEn(D), CrossEn(D^T), their mean), and the gradient carried through D back to the features and logit_scale:
+ *   dS_ij = n P_ij (G_ij (1 + S_ij) - t_j),  P = softmax over the rows of each column of S,  G = dL/dD,  t_j = sum_k G_kj S_kj P_kj.
+ * Same arguments, limits and determinism as cc_contrastive_loss_grad_f32 / _dev_f32; a workspace query of its own. */
+size_t cc_contrastive_grad_dsl_workspace_bytes(int32_t n, int32_t Tn, int32_t E);
+int cc_contrastive_loss_grad_dsl_f32(const float* text, const float* visual, const int64_t* video_mask,
+                                     int64_t mask_row_stride, int64_t mask_col_stride, int32_t n, int32_t Tn, int32_t E,
+                                     float logit_scale, float grad_scale, float* loss3, float* d_text, float* d_visual,
+                                     float* d_logit_scale, void* ws, size_t ws_bytes, void* stream);
+int cc_contrastive_loss_grad_dsl_dev_f32(const float* text, const float* visual, const int64_t* video_mask,
+                                         int64_t mask_row_stride, int64_t mask_col_stride, int32_t n, int32_t Tn, int32_t E,
+                                         float logit_scale, const float* logit_scale_dev, float grad_scale, float* loss3,
+                                         float* d_text, float* d_visual, float* d_logit_scale, void* ws, size_t ws_bytes,
+                                         void* stream);
+
+/* camoe_dsl at evaluation: D = sim * softmax(sim, dim=0) * n_total on a [rows, cols] fp32 matrix (texts as rows, row stride in
+ * elements, unit column stride), as three steps so that a row-sharded matrix can combine its blocks' statistics in between:
+ *   cc_dsl_col_stats_f32      m[j] = max_i sim[i,j], s[j] = sum_i exp(sim[i,j] - m[j]) over the rows given.  rows == 0 is legal
+ *                             (sim and ws may be null) and yields the neutral element (-inf, 0).  A column that holds a NaN gets
+ *                             m = s = NaN, as torch.softmax would.  Fixed summation order (row slabs merged in slab order, no
+ *                             atomics): the same bits on every run.  ws: cc_dsl_col_stats_workspace_bytes(rows, cols).
+ *   cc_dsl_rescale_stats_f32  s[j] <- s[j] * exp(m_local[j] - m_global[j]), and 0 where s[j] == 0: a block's sums brought to the
+ *                             maximum over all blocks (between an all-reduce MAX of m and an all-reduce SUM of s).
+ *   cc_dsl_apply_f32          sim[i,j] <- n_total * sim[i,j] * exp(sim[i,j] - m[j]) / s[j], in place. */
+size_t cc_dsl_col_stats_workspace_bytes(int32_t rows, int32_t cols);
+int cc_dsl_col_stats_f32(const float* sim, int32_t rows, int32_t cols, int64_t row_stride, float* m, float* s, void* ws,
+                         size_t ws_bytes, void* stream);
+int cc_dsl_rescale_stats_f32(const float* m_local, const float* m_global, float* s, int32_t cols, void* stream);
+int cc_dsl_apply_f32(float* sim, int32_t rows, int32_t cols, int64_t row_stride, const float* m, const float* s,
+                     int32_t n_total, void* stream);
+
 /* N1 - the rank extraction of compute_metrics (utils/metrics.py:11-26) on the device: for row i with
  * ground-truth column g = diag_offset + i, counts[2i] = #{j: sim[i,j] > sim[i,g]} and counts[2i+1] =
  * #{j: sim[i,j] == sim[i,g]} (>= 1).  The reference's rank list `ind` is the concatenation over rows of
