@@ -117,6 +117,10 @@ def declare(lib):
     lib.cc_text_encode_prefix.restype = c.c_int
     lib.cc_patch_gather_f16.argtypes = [c.POINTER(Frames), i32, i32, i32, vp, vp]
     lib.cc_patch_gather_f16.restype = c.c_int
+    lib.cc_attention_varlen_f16.argtypes = [vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]
+    lib.cc_attention_varlen_f16.restype = c.c_int
+    lib.cc_patch_gather_any_f16.argtypes = [c.POINTER(Frames), i32, i32, i32, vp, vp]
+    lib.cc_patch_gather_any_f16.restype = c.c_int
     lib.cc_patch_gather3d_f16.argtypes = [c.POINTER(Frames), i32, i32, i32, i32, vp, vp]
     lib.cc_patch_gather3d_f16.restype = c.c_int
     lib.cc_clip_encode_frames.argtypes = [c.POINTER(VitModel), c.POINTER(Frames), i32, i32, vp, vp, vp,

@@ -2,7 +2,7 @@
 same class / method names, forward signatures and state-dict keys, executed by
 the HIP encoders of libcenterclip_hip.so through the C ABI.  No PyTorch compute fallback.
 
-Built: VisualTransformer (ViT-B/32, ViT-B/16, linear_patch '2d' and '3d'), the text Transformer,
+Built: VisualTransformer (ViT-B/32, ViT-B/16, ViT-L/14; linear_patch '2d' and - patch % 8 == 0 - '3d'), the text Transformer,
 ResidualAttentionBlock.forward / Transformer.forward on LND activations (composed from the op-level
 entry points), CLIP.encode_image / encode_text (incl. return_hidden=True), CLIP.forward,
 build_clip_model, load_clip_state_dict (local files).  Not built (out of the hot path, SURVEY §2.1
@@ -47,6 +47,14 @@ def frames_descriptor(x, mean=PIXEL_MEAN, std=PIXEL_STD):
         fr.format = 0
     fr.data = x.data_ptr()
     return fr, x
+
+
+def pack_conv1_weight(weight):
+    """conv1.weight [W, 3, p, p] -> the GEMM operand [W, patch_cols(p)] fp16: columns (c, kh, kw) as the patch gather writes
+    them, zero columns behind 3 p^2 where that is no multiple of 64 (p = 14: 588 -> 640)."""
+    w = weight.detach().reshape(weight.shape[0], -1).to(torch.float16)
+    pad = T.patch_cols(weight.shape[-1]) - w.shape[1]
+    return (torch.nn.functional.pad(w, (0, pad)) if pad else w).contiguous()
 
 
 _ZERO = {}
@@ -287,7 +295,7 @@ class VisualTransformer(nn.Module):
         m.row_policy = ROWS_ALL_LAST_BLOCK if self.all_last_block_rows else 0
         m.layers, m.width, m.heads = self.transformer.layers, self.width, self.heads
         m.patch, m.resolution, m.embed_dim = self.patch_size, self.input_resolution, self.output_dim
-        m.conv1_weight_f16 = pk.f16(self.conv1.weight.reshape(self.width, -1))
+        m.conv1_weight_f16 = pk.f16(pack_conv1_weight(self.conv1.weight))
         if self.linear_patch == '3d':                # [W, 3(c), 3(t), p, p] flattened = the im2col row order of the 3-d gather
             m.conv2_weight_f16 = pk.f16(self.conv2.weight.reshape(self.width, -1))
         m.class_embedding, m.positional_embedding = pk.f32(self.class_embedding), pk.f32(self.positional_embedding)
@@ -639,7 +647,8 @@ class CLIP(nn.Module):
         return ops.scaled_dot_nt(img, txt, mult), ops.scaled_dot_nt(txt, img, mult)
 
 
-_PT_NAME = {"ViT-B/32": "ViT-B-32.pt", "ViT-B/16": "ViT-B-16.pt"}      # clip.py:29-36 (ViT entries)
+_PT_NAME = {"ViT-B/32": "ViT-B-32.pt", "ViT-B/16": "ViT-B-16.pt",      # clip.py:29-36 (ViT entries)
+            "ViT-L/14": "ViT-L-14.pt", "ViT-L/14@336px": "ViT-L-14-336px.pt"}     # OpenAI's file names of the L/14 releases
 
 
 def load_clip_state_dict(pretrained_clip_name="ViT-B/32", pretrained_dir=os.path.expanduser("~/models/pretrained")):

@@ -523,7 +523,8 @@ __global__ __launch_bounds__(256) void attention_backward_mfma_kernel(const _Flo
     if (amax_bits) publish_absmax(amo, amax_bits);
 }
 
-// ---- 64 < L <= 256 (ViT-B/16: 197 tokens per frame, 161 in its clustered blocks): the same arithmetic as two launches.
+// ---- 64 < L <= 320 (ViT-B/16: 197 tokens per frame, 161 in its clustered blocks; ViT-L/14 at 224 px: 257, NK64 = 5 - 40
+//      accumulators per lane for P and dS, 93 KB of LDS, one workgroup per CU): the same arithmetic as two launches.
 //   q side: one workgroup per (sequence, head, 64 queries); wave w holds its 16 queries' rows of S, P, dP and dS against ALL keys in
 //           registers (16 accumulators each at L = 256), writes dQ and, per query, log-sum-exp and D = sum_j P dP to `stats`
 //   k side: one workgroup per (sequence, head, 64 keys); loops over the query tiles, rebuilds P^T = exp(S^T / 8 - lse) and
@@ -1246,7 +1247,7 @@ size_t cc_attention_backward_workspace_bytes(int32_t nseq, int32_t L, int32_t he
 int cc_attention_backward_f16(const void* qkv_f16, const float* d_out, float* d_qkv, int32_t nseq, int32_t L, int32_t heads,
                               int32_t W, int32_t causal, float* out_amax, void* ws, size_t ws_bytes, void* stream) {
     if (!qkv_f16 || !d_out || !d_qkv || nseq <= 0 || L <= 0 || heads <= 0 || W != heads * AB_D) return CC_ERR_INVALID;
-    if (L > 256) return CC_ERR_UNSUPPORTED;
+    if (L > 320) return CC_ERR_UNSUPPORTED;                      // (five 64-key tiles: ViT-L/14 at 224 px has 257 tokens)
     if (L > AB_L) {
         if (!ws || ws_bytes < cc_attention_backward_workspace_bytes(nseq, L, heads)) return CC_ERR_WORKSPACE;
         const _Float16* q = static_cast<const _Float16*>(qkv_f16);
@@ -1255,7 +1256,8 @@ int cc_attention_backward_f16(const void* qkv_f16, const float* d_out, float* d_
         switch ((L + 63) / 64) {
             case 2: return launch_attention_backward_long<2>(q, d_out, d_qkv, static_cast<float*>(ws), nseq, L, heads, W, causal, am, st);
             case 3: return launch_attention_backward_long<3>(q, d_out, d_qkv, static_cast<float*>(ws), nseq, L, heads, W, causal, am, st);
-            default: return launch_attention_backward_long<4>(q, d_out, d_qkv, static_cast<float*>(ws), nseq, L, heads, W, causal, am, st);
+            case 4: return launch_attention_backward_long<4>(q, d_out, d_qkv, static_cast<float*>(ws), nseq, L, heads, W, causal, am, st);
+            default: return launch_attention_backward_long<5>(q, d_out, d_qkv, static_cast<float*>(ws), nseq, L, heads, W, causal, am, st);
         }
     }
     static bool configured = false;              // benign race (idempotent call)

@@ -125,6 +125,10 @@ struct AttArgs {
     const int* seq_len;
 };
 int cc_launch_attention2(const AttArgs& a0, const AttArgs* a1, hipStream_t st);
+// attention_long.hip: 256 < L <= CC_ATT_LONG_MAX_L, key tiles streamed through LDS with an online softmax (one problem per
+// launch); cc_launch_attention2 sends a problem there when its L is above the resident-K kernel's 256
+#define CC_ATT_LONG_MAX_L 640
+int cc_launch_attention_long(const AttArgs& a, hipStream_t st);
 // in_proj (LayerNorm folded) + attention in one launch (gemm.hip, EPI_ATTN_LN): g.A = centred fp16 rows, g.W / bias / ln_* as
 // for EPI_F16_LN, g.C = attention output [M, W] fp16; the att_* fields describe the sequences.  applies(): head width 64,
 // att_L <= 256 and the folded form available - otherwise the caller runs the two launches.
@@ -132,6 +136,10 @@ bool cc_gemm_attn_applies(const GemmArgs& g0, const GemmArgs* g1);
 int cc_gemm_attn_dispatch2(GemmArgs g0, const GemmArgs* g1, hipStream_t st);
 
 int cc_launch_im2col(const cc_frames& frames, _Float16* A, int F, int res, int p, hipStream_t st);
+// any patch size that divides the resolution: rows of cc_patch_cols(p) = roundup(3 p^2, 64) columns, those >= 3 p^2 zero;
+// p % 8 == 0 is cc_launch_im2col itself (3 p^2 is then a multiple of 64)
+static inline int cc_patch_cols(int p) { return (3 * p * p + 63) / 64 * 64; }
+int cc_launch_im2col_any(const cc_frames& frames, _Float16* A, int F, int res, int p, hipStream_t st);
 int cc_launch_im2col3d(const cc_frames& frames, _Float16* A, int F, int T, int res, int p, hipStream_t st);   // linear_patch '3d'
 
 // eig.hip: direct symmetric eigensolver for the K smallest eigenpairs (N <= 196, K <= 64, 2K <= N), see the file header

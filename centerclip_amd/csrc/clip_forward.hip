@@ -50,7 +50,7 @@ VitWs carve_vit(const cc_vit_model* m, int B, int T, void* ws) {
     Carver c(ws);
     const int g = m->resolution / m->patch, n = g * g, L0 = n + 1, W = m->width;
     const size_t F = (size_t)B * T, M0 = F * L0;
-    v.im2col = c.take<_Float16>(F * n * (m->conv2_weight_f16 ? 9 : 3) * m->patch * m->patch);
+    v.im2col = c.take<_Float16>(F * n * (m->conv2_weight_f16 ? (size_t)9 * m->patch * m->patch : (size_t)cc_patch_cols(m->patch)));
     v.h = c.take<float>(M0 * W);
     v.h2 = c.take<float>(M0 * W);
     v.h16 = c.take<_Float16>(M0 * W);
@@ -293,7 +293,8 @@ TextWs carve_text(const cc_text_model* m, int Bt, int Lt, void* ws) {
 
 bool vit_ok(const cc_vit_model* m) {
     if (m->layers <= 0 || m->layers > CC_MAX_LAYERS || m->width != m->heads * 64) return false;
-    return !(m->resolution % m->patch || (m->patch & 7) || (m->width % 64) || ((3 * m->patch * m->patch) % 64));
+    if (m->patch <= 0 || m->resolution % m->patch || (m->width % 64)) return false;
+    return !(m->conv2_weight_f16 && (m->patch & 7));           // linear_patch '3d': the 8-wide gather only
 }
 
 bool text_ok(const cc_text_model* m, int Lt) {
@@ -338,14 +339,14 @@ int encode_towers(const cc_vit_model* vm, const cc_frames* video, int B, int T, 
         // patch embedding: conv1 as im2col GEMM, + positional embedding, CLS row, ln_pre (clip.py:324-338)
         const bool patch3d = vm->conv2_weight_f16 != nullptr;      // linear_patch '3d' (clip.py:306-317)
         rc = patch3d ? cc_launch_im2col3d(*video, v.im2col, F, T, vm->resolution, vm->patch, st)
-                     : cc_launch_im2col(*video, v.im2col, F, vm->resolution, vm->patch, st);
+                     : cc_launch_im2col_any(*video, v.im2col, F, vm->resolution, vm->patch, st);
         if (rc) return rc;
         GemmArgs ga{};
         ga.A = v.im2col;
         ga.W = static_cast<const _Float16*>(patch3d ? vm->conv2_weight_f16 : vm->conv1_weight_f16);
         ga.C = v.h;
         ga.pos = vm->positional_embedding;
-        ga.M = F * n; ga.N = W; ga.K = (patch3d ? 9 : 3) * vm->patch * vm->patch; ga.ldc = W;
+        ga.M = F * n; ga.N = W; ga.K = patch3d ? 9 * vm->patch * vm->patch : cc_patch_cols(vm->patch); ga.ldc = W;
         ga.patch_n = n;
         rc = cc_gemm_dispatch(ga, EPI_F32_PATCH, 0, st);
         if (rc) return rc;
@@ -512,8 +513,13 @@ int cc_vit_encode_frames(const cc_vit_model* m, const cc_frames* frames, int32_t
                          nullptr, nullptr, ws, ws_bytes, static_cast<hipStream_t>(stream));
 }
 
-// The patch gathers read uint8 frames in 8-byte pieces and fp32 frames as float4: a base address off that grid is refused
-static bool frames_base_ok(const cc_frames* fr) {
+// The patch gathers read uint8 frames in 8-byte pieces and fp32 frames as float4: a base address off that grid is refused.
+// A patch size off the 8-wide grid (im2col_any_kernel) loads sample by sample: any uint8 address, any float address.
+static bool frames_base_ok(const cc_frames* fr, int patch = 8) {
+    if (patch & 7) {
+        if (fr->format == CC_FRAMES_U8_CHW || fr->format == CC_FRAMES_U8_HWC) return true;
+        return fr->format == CC_FRAMES_F32_CHW && (reinterpret_cast<uintptr_t>(fr->data) & 3) == 0;
+    }
     if (fr->format == CC_FRAMES_U8_CHW || fr->format == CC_FRAMES_U8_HWC) return (reinterpret_cast<uintptr_t>(fr->data) & 7) == 0;
     return fr->format == CC_FRAMES_F32_CHW && (reinterpret_cast<uintptr_t>(fr->data) & 15) == 0;
 }
@@ -523,7 +529,7 @@ int cc_vit_encode_prefix_frames(const cc_vit_model* m, const cc_frames* frames, 
     if (!m || !frames || !frames->data || !hidden_out || B <= 0 || T <= 0) return CC_ERR_INVALID;
     if (n_blocks < 0 || n_blocks > m->layers || (n_blocks > 0 && !m->blocks)) return CC_ERR_INVALID;
     if (!vit_ok(m)) return CC_ERR_UNSUPPORTED;
-    if (!frames_base_ok(frames)) return CC_ERR_INVALID;
+    if (!frames_base_ok(frames, m->patch)) return CC_ERR_INVALID;
     return encode_towers(m, frames, B, T, nullptr, hidden_out, nullptr, forced_medoids, nullptr, nullptr, 0, 0, nullptr,
                          nullptr, ws, ws_bytes, static_cast<hipStream_t>(stream), n_blocks, -1);
 }
@@ -532,6 +538,15 @@ int cc_patch_gather_f16(const cc_frames* frames, int32_t F, int32_t resolution, 
     if (!frames || !frames->data || !out_f16 || F <= 0 || patch <= 0 || resolution <= 0) return CC_ERR_INVALID;
     if ((patch & 7) || resolution % patch || !frames_base_ok(frames)) return CC_ERR_INVALID;
     return cc_launch_im2col(*frames, static_cast<_Float16*>(out_f16), F, resolution, patch, static_cast<hipStream_t>(stream));
+}
+
+// The patch gather of the encoders for ANY patch size that divides the resolution: out [F * g * g][roundup(3 p^2, 64)] fp16,
+// columns (c, kh, kw), columns >= 3 p^2 zero.  p % 8 == 0: cc_patch_gather_f16 itself (same kernels, same bits, same base
+// alignment rule); otherwise frames may start at any element.
+int cc_patch_gather_any_f16(const cc_frames* frames, int32_t F, int32_t resolution, int32_t patch, void* out_f16, void* stream) {
+    if (!frames || !frames->data || !out_f16 || F <= 0 || patch <= 0 || resolution <= 0) return CC_ERR_INVALID;
+    if (resolution % patch || !frames_base_ok(frames, patch)) return CC_ERR_INVALID;
+    return cc_launch_im2col_any(*frames, static_cast<_Float16*>(out_f16), F, resolution, patch, static_cast<hipStream_t>(stream));
 }
 
 // linear_patch '3d': the gathers of the fused forward (im2col3d_f16_kernel, the P3D strip gather) on their own

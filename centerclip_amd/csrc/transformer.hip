@@ -593,6 +593,52 @@ __global__ __launch_bounds__(256) void im2col_u8_f16_kernel(const unsigned char*
     }
 }
 
+// Any patch size that divides the resolution (p % 8 != 0: ViT-L/14, rows 14 pixels = 28 bytes of uint8 or 56 of fp32 apart, so
+// a patch row starts on no fixed alignment and the 8-wide loads of the gathers above do not hold).  Every sample is loaded on
+// its own - consecutive lanes still read neighbouring addresses - and only the store is a vector: a lane writes 8 consecutive
+// columns of A, whose rows are Kp = roundup(3 p^2, 64) halfs (16-byte aligned); columns >= 3 p^2 are exact zeros, so the conv1
+// GEMM sees an ordinary K.  Column order (c, kh, kw), values as the gathers above form them (fp32: one rounding to fp16;
+// uint8: the loader's three IEEE operations through the same 3 x 256 table).  FMT: CC_FRAMES_*.
+template <int FMT>
+__global__ __launch_bounds__(256) void im2col_any_kernel(const float* __restrict__ vf, const unsigned char* __restrict__ vu,
+                                                         _Float16* __restrict__ A, int F, int res, int p, int Kp,
+                                                         float m0, float m1, float m2, float s0, float s1, float s2) {
+    __shared__ _Float16 table[3][256];
+    if (FMT != CC_FRAMES_F32_CHW) {
+        const int u = threadIdx.x;                                   // blockDim.x == 256
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float mean = c == 0 ? m0 : (c == 1 ? m1 : m2), sd = c == 0 ? s0 : (c == 1 ? s1 : s2);
+            float v = (float)u / 255.0f;
+            v = v - mean;
+            v = v / sd;
+            table[c][u] = (_Float16)v;
+        }
+        __syncthreads();
+    }
+    const int g = res / p, n = g * g, pp = p * p, Kc = 3 * pp, groups = Kp / 8;
+    const int64_t total = (int64_t)F * n * groups;
+    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
+        const int64_t row = idx / groups;
+        const int k0 = (int)(idx - row * groups) * 8;
+        const int f = (int)(row / n), pi = (int)(row - (int64_t)f * n);
+        const int ph = pi / g, pw = pi - ph * g;
+        int c = k0 / pp, rem = k0 - c * pp, kh = rem / p, kw = rem - kh * p;
+        h8 o = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            if (k0 + e < Kc) {
+                const int y = ph * p + kh, x = pw * p + kw;
+                if (FMT == CC_FRAMES_F32_CHW) o[e] = (_Float16)vf[(((int64_t)f * 3 + c) * res + y) * res + x];
+                else if (FMT == CC_FRAMES_U8_CHW) o[e] = table[c][vu[(((int64_t)f * 3 + c) * res + y) * res + x]];
+                else o[e] = table[c][vu[(((int64_t)f * res + y) * res + x) * 3 + c]];
+            }
+            if (++kw == p) { kw = 0; if (++kh == p) { kh = 0; ++c; } }
+        }
+        *reinterpret_cast<h8*>(A + row * Kp + k0) = o;
+    }
+}
+
 // The same gather with the index arithmetic cut down to shifts (p a power of two: every CLIP patch size): the kernel above
 // spends ~300 instructions per 16 output bytes on two 64-bit divisions and five 32-bit ones - with 1 B/px coming in it was
 // instruction-bound, not HBM-bound (29 us, the time of the fp32 gather that reads 4x the bytes).  One workgroup per strip
@@ -897,7 +943,7 @@ int cc_layernorm_f32(const float* in, int64_t in_stride, const float* gamma, con
 int cc_attention_f16(const void* qkv_f16, void* out_f16, int32_t nseq, int32_t L, int32_t heads, int32_t W,
                      int32_t causal, void* stream) {
     if (!qkv_f16 || !out_f16 || nseq <= 0 || L <= 0 || heads <= 0 || W != heads * ATT_D) return CC_ERR_INVALID;
-    if (L > ATT_MAX_KT) return CC_ERR_UNSUPPORTED;
+    if (L > CC_ATT_LONG_MAX_L) return CC_ERR_UNSUPPORTED;
     AttArgs a{static_cast<const _Float16*>(qkv_f16), static_cast<_Float16*>(out_f16), nseq, L, heads, W, causal, 0, 0};
     return cc_launch_attention2(a, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -906,9 +952,19 @@ int cc_attention_strided_f16(const void* qkv_f16, void* out_f16, int32_t nseq, i
                              int32_t causal, int64_t seq_rows, int64_t tok_rows, void* stream) {
     if (!qkv_f16 || !out_f16 || nseq <= 0 || L <= 0 || heads <= 0 || W != heads * ATT_D) return CC_ERR_INVALID;
     if (seq_rows <= 0 || tok_rows <= 0) return CC_ERR_INVALID;
-    if (L > ATT_MAX_KT) return CC_ERR_UNSUPPORTED;
+    if (L > CC_ATT_LONG_MAX_L) return CC_ERR_UNSUPPORTED;
     AttArgs a{static_cast<const _Float16*>(qkv_f16), static_cast<_Float16*>(out_f16), nseq, L, heads, W, causal, seq_rows,
               tok_rows};
+    return cc_launch_attention2(a, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int cc_attention_varlen_f16(const void* qkv_f16, void* out_f16, int32_t nseq, int32_t L_max, int32_t heads, int32_t W,
+                            int32_t causal, const int32_t* seq_off, const int32_t* seq_len, void* stream) {
+    if (!qkv_f16 || !out_f16 || !seq_off || !seq_len || nseq <= 0 || L_max <= 0 || heads <= 0 || W != heads * ATT_D)
+        return CC_ERR_INVALID;
+    if (L_max > CC_ATT_LONG_MAX_L) return CC_ERR_UNSUPPORTED;
+    AttArgs a{static_cast<const _Float16*>(qkv_f16), static_cast<_Float16*>(out_f16), nseq, L_max, heads, W, causal, 0, 0,
+              seq_off, seq_len};
     return cc_launch_attention2(a, nullptr, static_cast<hipStream_t>(stream));
 }
 
@@ -979,7 +1035,13 @@ static size_t att_smem_bytes(int L) {
 }
 
 int cc_launch_attention2(const AttArgs& a0, const AttArgs* a1, hipStream_t st) {
-    if (a0.L > ATT_MAX_KT || (a1 && a1->L > ATT_MAX_KT)) return CC_ERR_UNSUPPORTED;
+    if (a0.L > ATT_MAX_KT || (a1 && a1->L > ATT_MAX_KT)) {
+        // above the resident-K kernels: the streaming kernel of attention_long.hip, every problem in a launch of its own
+        // (the partner, if it is short, keeps the kernel it has on its own)
+        int rc = a0.L > ATT_MAX_KT ? cc_launch_attention_long(a0, st) : cc_launch_attention2(a0, nullptr, st);
+        if (rc || !a1) return rc;
+        return a1->L > ATT_MAX_KT ? cc_launch_attention_long(*a1, st) : cc_launch_attention2(*a1, nullptr, st);
+    }
     AttPair pr{};
     pr.a[0] = a0;
     pr.a[1] = a1 ? *a1 : a0;
@@ -1062,6 +1124,32 @@ int cc_launch_im2col(const cc_frames& fr, _Float16* A, int F, int res, int p, hi
         else
             hipLaunchKernelGGL(im2col_u8_f16_kernel<false>, dim3(blocks), dim3(256), 0, st, v, A, F, res, p, fr.mean[0],
                                fr.mean[1], fr.mean[2], fr.std[0], fr.std[1], fr.std[2]);
+    } else {
+        return CC_ERR_INVALID;
+    }
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+int cc_launch_im2col_any(const cc_frames& fr, _Float16* A, int F, int res, int p, hipStream_t st) {
+    if (p <= 0 || res % p || !fr.data) return CC_ERR_INVALID;
+    if (!(p & 7)) return cc_launch_im2col(fr, A, F, res, p, st);           // the 8-wide gathers, as they were
+    const int Kp = cc_patch_cols(p);
+    const int64_t total = (int64_t)F * (res / p) * (res / p) * (Kp / 8);
+    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    if (fr.format == CC_FRAMES_F32_CHW) {
+        hipLaunchKernelGGL(im2col_any_kernel<CC_FRAMES_F32_CHW>, dim3(blocks), dim3(256), 0, st, static_cast<const float*>(fr.data),
+                           nullptr, A, F, res, p, Kp, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f);
+    } else if (fr.format == CC_FRAMES_U8_CHW || fr.format == CC_FRAMES_U8_HWC) {
+        for (int c = 0; c < 3; ++c)
+            if (!(fr.std[c] > 0.f)) return CC_ERR_INVALID;
+        const unsigned char* v = static_cast<const unsigned char*>(fr.data);
+        if (fr.format == CC_FRAMES_U8_HWC)
+            hipLaunchKernelGGL(im2col_any_kernel<CC_FRAMES_U8_HWC>, dim3(blocks), dim3(256), 0, st, nullptr, v, A, F, res, p, Kp,
+                               fr.mean[0], fr.mean[1], fr.mean[2], fr.std[0], fr.std[1], fr.std[2]);
+        else
+            hipLaunchKernelGGL(im2col_any_kernel<CC_FRAMES_U8_CHW>, dim3(blocks), dim3(256), 0, st, nullptr, v, A, F, res, p, Kp,
+                               fr.mean[0], fr.mean[1], fr.mean[2], fr.std[0], fr.std[1], fr.std[2]);
     } else {
         return CC_ERR_INVALID;
     }

@@ -866,23 +866,29 @@ def _(ids, handle, n_blocks):
     return ids.new_empty((ids.shape[0], ids.shape[1], meta["width"]), dtype=torch.float32)
 
 
+def patch_cols(patch):
+    """Columns of the patch matrix and of the packed conv1 weight: 3 p^2 rounded up to a multiple of 64 (the GEMMs' k-step)."""
+    return -(-3 * patch * patch // 64) * 64
+
+
 @custom_op(NS + "::patch_gather", mutates_args=(), device_types="cuda")
 def patch_gather(frames: torch.Tensor, resolution: int, patch: int) -> torch.Tensor:
-    """The encoders' patch gather on its own (cc_patch_gather_f16): frames [F,3,H,W] fp32 (normalised) or uint8
-    ([F,3,H,W] / [F,H,W,3], the loader's u8/255 -> (x - mean)/std inside) -> the fp16 patch matrix [F * g * g, 3 * p * p]."""
+    """The encoders' patch gather on its own (cc_patch_gather_any_f16): frames [F,3,H,W] fp32 (normalised) or uint8
+    ([F,3,H,W] / [F,H,W,3], the loader's u8/255 -> (x - mean)/std inside) -> the fp16 patch matrix [F * g * g, patch_cols(p)],
+    columns (c, kh, kw); patch_cols(p) = 3 p^2 for p % 8 == 0, else rounded up to a multiple of 64 with zero columns behind."""
     from .clip import frames_descriptor
     fr, frames = frames_descriptor(frames)
     F, g = frames.shape[0], resolution // patch
-    out = _e(F * g * g, 3 * patch * patch, like=frames, dtype=torch.float16)
-    L.check(L.lib().cc_patch_gather_f16(ctypes.byref(fr), F, int(resolution), int(patch), L.ptr(out), _st(frames)),
-            "cc_patch_gather_f16")
+    out = _e(F * g * g, patch_cols(patch), like=frames, dtype=torch.float16)
+    L.check(L.lib().cc_patch_gather_any_f16(ctypes.byref(fr), F, int(resolution), int(patch), L.ptr(out), _st(frames)),
+            "cc_patch_gather_any_f16")
     return out
 
 
 @patch_gather.register_fake
 def _(frames, resolution, patch):
     g = resolution // patch
-    return frames.new_empty((frames.shape[0] * g * g, 3 * patch * patch), dtype=torch.float16)
+    return frames.new_empty((frames.shape[0] * g * g, patch_cols(patch)), dtype=torch.float16)
 
 
 @custom_op(NS + "::patch_gather3d", mutates_args=(), device_types="cuda")

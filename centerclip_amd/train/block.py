@@ -27,6 +27,9 @@ def _check(rc, what):
 
 
 
+MAX_TRAIN_TOKENS = 320      # cc_attention_backward_f16: five 64-key tiles on the query side
+
+
 def _pad64(n):
     return -(-n // 64) * 64
 
@@ -215,6 +218,9 @@ def block_forward_train(block, x_lnd, mid_shift=None, key_mask=None, cluster_don
         raise NotImplementedError("block backward: blocks with a token-cluster module are not covered by this slice")
     L.require_device(x_lnd)
     Lt, N, W = x_lnd.shape
+    if Lt > MAX_TRAIN_TOKENS:
+        raise NotImplementedError("block training: %d tokens per sequence - the attention backward is built up to %d "
+                                  "(ViT-L/14 at 224 px has 257; 336 px, 577 tokens, is evaluation only)" % (Lt, MAX_TRAIN_TOKENS))
     M = N * Lt
     causal = block.attn_mask is not None
     f32 = lambda t: t.detach().float().contiguous()

@@ -9,6 +9,7 @@ EOT row gather.  A tower's frozen prefix (clip4clip.py:449-471 freeze_cip_layers
 import torch
 
 from .. import _lib as L
+from ..torch_ops import patch_cols
 from .block import LinearFunction, _layernorm, block_apply
 
 
@@ -121,8 +122,8 @@ def encode_image_train(clip, video, video_frame):
                                                 vis.input_resolution, p)
         x = _front(vis, LinearFunction.apply(a, vis.conv2.weight.view(W, -1), None), F, g)
     else:
-        if _GLUE_FRONT or (p % 8 and video.dtype != torch.uint8):
-            # (a patch size off the gather's 8-wide grid - no CLIP tower has one - keeps the reshape, as before)
+        w = vis.conv1.weight.view(W, -1)
+        if _GLUE_FRONT:
             if video.dtype == torch.uint8:
                 raise ValueError("the torch-glue front takes normalised float frames")
             # conv1 (kernel = stride = p, no bias) as a GEMM over the patch rows (c, kh, kw) - a reshape of the frames
@@ -131,7 +132,15 @@ def encode_image_train(clip, video, video_frame):
             # the encoders' patch gather: the fp16 patch matrix straight from the frames - LinearFunction's operand and saved
             # activation (no fp32 permute-copy of the patches, no separate cast)
             a = torch.ops.centerclip.patch_gather(video if video.dtype == torch.uint8 else video.float(), vis.input_resolution, p)
-        x = _front(vis, LinearFunction.apply(a, vis.conv1.weight.view(W, -1), None), F, g)
+        Kp = patch_cols(p)
+        if Kp != w.shape[1]:
+            # a patch size off the 8-wide grid (ViT-L/14): the rows are padded to a multiple of 64 columns - zeros in the patch
+            # matrix (the gather writes them), zeros appended to the weight; conv1's gradient is the first 3 p^2 columns of
+            # the product's (the pad's backward is that slice)
+            if a.shape[1] != Kp:
+                a = torch.nn.functional.pad(a, (0, Kp - a.shape[1]))
+            w = torch.nn.functional.pad(w, (0, Kp - w.shape[1]))
+        x = _front(vis, LinearFunction.apply(a, w, None), F, g)
     cls_rows = x[:, 0, :].contiguous()                        # ln_post(x) @ proj, of which encode_image keeps the CLS row
     feats = LinearFunction.apply(_layernorm(vis.ln_post, cls_rows), vis.proj.t(), None)
     return feats, torch.zeros((), device=video.device)

@@ -6,7 +6,7 @@ with random-init CLIP weights (no checkpoint / dataset access here) and a synthe
 Every compute step runs in the HIP library; swap the state dict for a real ViT-B/32 checkpoint and the loader for
 dataloaders/* to evaluate a trained model.
 
-    python examples/eval_synthetic.py [--clips 64] [--algo kmediods++|spectral|pooling]
+    python examples/eval_synthetic.py [--clips 64] [--algo kmediods++|spectral|pooling] [--l14 1 [--oracle-check 1]]
 """
 import argparse
 import os
@@ -42,6 +42,49 @@ class SyntheticRetrieval(torch.utils.data.Dataset):
         return self.ids[i], self.mask[i], torch.zeros_like(self.ids[i]), self.video[i], self.vmask[i]
 
 
+# ViT-L/14 at 224 px (OpenAI's ViT-L-14.pt geometry: width 1024, 24 layers, patch 14 -> 257 tokens per frame, embedding 768,
+# text width 768): 12 frames -> 4 segments at block 13, K = 128.  Blocks 1-12 run the streaming attention (L = 257), blocks
+# 13-24 the one-launch in_proj + attention form (L = 129).
+L14 = dict(bench.CFG2, name="ViT-L/14 224^2: 12 frames -> 4 segments @block 13, 256 tokens/frame, K=128, batch 16, 32 words",
+           patch=14, width=1024, layers=24, T_new=4, K=128, cluster_block=13)
+
+
+def l14_state_dict(c, seed):
+    """Random-init weights of the ViT-L/14 architecture (CLIP.initialize_parameters statistics, rounded through fp16)."""
+    from centerclip_amd.clip import CLIP
+    torch.manual_seed(seed)
+    m = CLIP(768, c["res"], c["layers"], c["width"], c["patch"], 77, 49408, 768, 12, 12, video_frames=c["T"], args=None)
+    with torch.no_grad():
+        for p in m.parameters():
+            p.copy_(p.half().float())
+    return {k: v.detach().clone() for k, v in m.state_dict().items()}
+
+
+def l14_task_config(c):
+    args = bench.task_config(c)
+    cb, n = c["cluster_block"], c["layers"]
+    args.target_frames_blocks = [c["T"]] * (cb - 1) + [c["T_new"]] * (n + 1 - cb)
+    args.cluster_num_blocks = [c["K"]] * n
+    args.pretrained_clip_name = 'ViT-L/14'
+    return args
+
+
+def oracle_check(sd, device, frames=2):
+    """Normalised embeddings of one short clip (no clustering) and one caption against the CPU oracle on the same
+    weights -> (max |delta| visual, text)."""
+    from centerclip_amd.clip import build_clip_model
+    from oracle import clip_oracle as clo
+    model, _ = build_clip_model(dict(sd), args=None)
+    model = model.to(device)
+    data = SyntheticRetrieval(1, frames=frames, seed=5)
+    video, ids = data.video[0, 0], data.ids[:1]
+    vfeat, tfeat = model.encode_pair(video.to(device), ids.to(device), video_frame=frames)
+    torch.cuda.synchronize()
+    vref, tref = clo.visual_forward(sd, video, frames), clo.text_forward(sd, ids)
+    nrm = lambda x: x / x.norm(dim=-1, keepdim=True)
+    return float((nrm(vfeat.cpu()) - nrm(vref)).abs().max()), float((nrm(tfeat.cpu()) - nrm(tref)).abs().max())
+
+
 def shift_plan(args):
     """The plan of scripts/activitynet.sh case 04: a shift module in every block (the frame count drops at block 1, the
     token count at every later block - the shift itself keeps both)."""
@@ -63,17 +106,22 @@ def main():
     ap.add_argument("--in-flight", type=int, default=None, help="batches in flight (model instances / streams); default: eval_epoch's own (2 on a GPU)")
     ap.add_argument("--camoe_dsl", type=int, default=0,
                     help="params.py's --camoe_dsl: rank the CAMoE dual softmax S * softmax(S, dim=0) * len(S) instead of S")
+    ap.add_argument("--l14", type=int, default=0, help="ViT-L/14 at 224 px instead (257 tokens per frame, width 1024, 24 layers)")
+    ap.add_argument("--oracle-check", type=int, default=0, help="--l14: also compare one 2-frame clip's embeddings with the CPU oracle")
     a = ap.parse_args()
     device = torch.device("cuda:0")
-    c = bench.CFG2
-    args = bench.task_config(c)                              # cfg 2: 12 frames -> 3 segments at block 7, K = 49
+    c = L14 if a.l14 else bench.CFG2
+    args = l14_task_config(c) if a.l14 else bench.task_config(c)     # cfg 2: 12 frames -> 3 segments at block 7, K = 49
     args.cluster_algo = a.algo
     args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
     args.camoe_dsl = a.camoe_dsl
     if a.algo in ("token_shift", "temporal_shift"):
         shift_plan(args)
     vars(args).update(spectral_sigma=2.0, spectral_graph="HeatKernel", spectral_knn_k=1, spectral_spg=0, svd_correct_sign=1)
-    model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), args).to(device).eval()
+    sd = l14_state_dict(c, seed=0) if a.l14 else bench.random_state_dict(c, seed=0)
+    if a.l14 and a.oracle_check:
+        print("ViT-L/14, 2 frames + 1 caption, max|delta| of normalised embeddings vs oracle: visual %.2e text %.2e" % oracle_check(sd, device))
+    model = CLIP4Clip.from_state_dict(sd, args).to(device).eval()
     loader = torch.utils.data.DataLoader(SyntheticRetrieval(a.clips), batch_size=a.batch, shuffle=False)
     r1, seconds, info = eval_epoch(model, loader, device, args, log=print, in_flight=a.in_flight)
     print("\n".join(info))

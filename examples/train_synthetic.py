@@ -22,7 +22,7 @@ here a train.DeviceGradScaler - loss scaling, inf / NaN check, step skipping and
 the eager loop and, inside the graph, the captured step; the taken / skipped counters are printed at the end.
 
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
-                                       [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
+                                       [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--l14 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
 import argparse
@@ -40,7 +40,7 @@ from centerclip_amd.train import (AdamW, BertAdam, DeviceGradScaler, lr_schedule
                                   train_epoch)
 from centerclip_amd import dist as ccdist                   # noqa: E402
 import bench                                                # noqa: E402
-from eval_synthetic import SyntheticRetrieval               # noqa: E402
+from eval_synthetic import SyntheticRetrieval, L14, l14_state_dict, l14_task_config   # noqa: E402
 
 
 def shift_plan(args):
@@ -58,6 +58,8 @@ def build_parser():
     ap.add_argument("--graph", type=int, default=1, help="also time the step captured into a hipGraph")
     ap.add_argument("--b16", type=int, default=0, help="ViT-B/16 instead (cfg-5 shape: 197 tokens per frame, 12 frames -> 4 segments, "
                                                        "K = 100; the attention backward's two-launch form)")
+    ap.add_argument("--l14", type=int, default=0, help="ViT-L/14 at 224 px instead (257 tokens per frame, width 1024, 24 layers, "
+                                                       "12 frames -> 4 segments at block 13, K = 128)")
     ap.add_argument("--sim_header", default="meanP", choices=["meanP", "seqTransf"],
                     help="similarity head (clip4clip.py:324-367); seqTransf starts from the reference's initialisation trick")
     ap.add_argument("--cross_num_hidden_layers", type=int, default=4, help="blocks of the seqTransf head (params.py default 4)")
@@ -90,14 +92,17 @@ def main():
     c = bench.CFG2
     if a.b16:
         c = dict(c, name="cfg5-shaped: ViT-B/16", patch=16, T_new=4, K=100)
-    args = bench.task_config(c)
+    if a.l14:
+        c = L14
+    args = l14_task_config(c) if a.l14 else bench.task_config(c)
     args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
     args.linear_patch = a.linear_patch
     args.camoe_dsl = a.camoe_dsl
     if a.algo != "kmediods++":
         args.cluster_algo = a.algo
         shift_plan(args)
-    model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), args).float().to(device)
+    sd = l14_state_dict(c, seed=0) if a.l14 else bench.random_state_dict(c, seed=0)
+    model = CLIP4Clip.from_state_dict(sd, args).float().to(device)
     model.freeze_cip_layers(a.freeze_layer_num)             # (main.py:102, before the optimizer is built)
     targs = Namespace(lr=a.lr, wd=0.2, new_added_modules=["Cross", "cluster_embed"], gradient_accumulation_steps=1,
                       clip_grad_norm=None, optim=a.optim)

@@ -403,7 +403,9 @@ int cc_linear_resid_stats_f16(const void* a_f16, const void* w_f16, const float*
 /* Multi-head self-attention core of nn.MultiheadAttention (modules/clip.py:220-226):
  * qkv [nseq*L, 3W] fp16 (row = seq*L + token; q | k | v, heads = contiguous 64-wide slices),
  * out [nseq*L, W] fp16 = softmax(q k^T / 8 + mask) v; causal != 0 adds the strict upper
- * triangular -inf mask of clip.py:448-454.  head_dim is 64 (W == 64*heads), L <= 256. */
+ * triangular -inf mask of clip.py:448-454.  head_dim is 64 (W == 64*heads).  L <= 256: K and V^T of a (sequence, head)
+ * resident in LDS; 256 < L <= 640 (ViT-L/14: 257 tokens at 224 px, 577 at 336 px): 64-key tiles streamed through LDS with
+ * an online softmax (attention_long.hip); L > 640: CC_ERR_UNSUPPORTED. */
 int cc_attention_f16(const void* qkv_f16, void* out_f16, int32_t nseq, int32_t L, int32_t heads,
                      int32_t W, int32_t causal, void* stream);
 /* The same for other row orders: token t of sequence s is row s*seq_rows + t*tok_rows of qkv / out.  The LND
@@ -411,6 +413,12 @@ int cc_attention_f16(const void* qkv_f16, void* out_f16, int32_t nseq, int32_t L
  * tok_rows = N; cc_attention_f16 is seq_rows = L, tok_rows = 1. */
 int cc_attention_strided_f16(const void* qkv_f16, void* out_f16, int32_t nseq, int32_t L, int32_t heads,
                              int32_t W, int32_t causal, int64_t seq_rows, int64_t tok_rows, void* stream);
+
+/* The same for sequences of different lengths packed back to back (the text tower's compacted captions): sequence s has
+ * seq_len[s] <= L_max tokens (device int32 [nseq], each >= 1) starting at row seq_off[s] of qkv / out; rows are W-strided as
+ * in cc_attention_f16.  L_max sizes the launch and picks the kernel (<= 640). */
+int cc_attention_varlen_f16(const void* qkv_f16, void* out_f16, int32_t nseq, int32_t L_max, int32_t heads, int32_t W,
+                            int32_t causal, const int32_t* seq_off, const int32_t* seq_len, void* stream);
 
 /* One ResidualAttentionBlock (state-dict keys resblocks.{i}.*) */
 typedef struct cc_block_weights {
@@ -592,6 +600,14 @@ int cc_text_encode_prefix(const cc_text_model* m, const int64_t* ids, int32_t Bt
  * 8-byte aligned, an fp32 base 16-byte aligned - else CC_ERR_INVALID before any launch. */
 int cc_patch_gather_f16(const cc_frames* frames, int32_t F, int32_t resolution, int32_t patch, void* out_f16,
                         void* stream);
+
+/* The same for ANY patch size that divides the resolution (ViT-L/14: patch 14): out_f16 [F * (resolution/patch)^2, Kp] fp16
+ * with Kp = roundup(3 * patch^2, 64); columns (c, kh, kw), columns >= 3 * patch^2 exact zeros - the conv1 weight is packed with
+ * the same zero columns and the GEMM sees an ordinary K.  patch % 8 == 0 (Kp = 3 * patch^2): cc_patch_gather_f16 itself, same
+ * bits, same alignment rule.  Otherwise every sample is loaded on its own: a uint8 base may be any address, an fp32 base any
+ * float address.  resolution % patch != 0: CC_ERR_INVALID. */
+int cc_patch_gather_any_f16(const cc_frames* frames, int32_t F, int32_t resolution, int32_t patch, void* out_f16,
+                            void* stream);
 
 /* The same for linear_patch '3d' (training with conv2, modules/clip.py:296-317: Conv3d kernel (3, patch, patch), stride
  * (1, patch, patch), padding (1, 0, 0) over clips of T frames): frames (F frames, F % T == 0, clip b = frames b*T .. b*T + T - 1)
@@ -776,7 +792,9 @@ int cc_group_max_rows_f32(const float* sim, int32_t rows, int32_t cols, int64_t 
  *                               (softmax(q k^T / 8 + mask) v per 64-wide head); fp16 MFMA operands (dO and dS scaled by
  *                               powers of two chosen on the device), fp32 accumulators.  L <= 64: one launch, a workgroup
  *                               per (sequence, head).  64 < L <= 256 (ViT-B/16): a query-side launch (dQ; log-sum-exp and
- *                               D = sum_j P dP per query into ws) and a key-side launch (dV, dK)
+ *                               D = sum_j P dP per query into ws) and a key-side launch (dV, dK);
+ *                               256 < L <= 320 (ViT-L/14 at 224 px: 257) the same pair with a fifth 64-key tile on the query
+ *                               side; L > 320: CC_ERR_UNSUPPORTED
  *   cc_column_sums_f32          out [cols] = column sums of in [rows, cols] (bias gradients)
  *   cc_cast_scaled_f16          fp32 -> fp16 with a power-of-two scale chosen on the device from the tensor's largest
  *                               magnitude (scale * max in [8192, 16384], scale <= 2^126: maxima below 2^-112 get 2^126);
