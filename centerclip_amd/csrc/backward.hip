@@ -185,142 +185,12 @@ __global__ __launch_bounds__(256) void column_reduce_kernel(const float* __restr
     }
 }
 
-// Attention backward, one workgroup per (sequence, head), head_dim 64, L <= 64.  q, k, v rows of qkv [nseq*L, 3W] fp16
-// (row = seq*L + token; heads are 64-wide slices), d_out [nseq*L, W] fp32 -> d_qkv [nseq*L, 3W] fp32.  Everything of a
-// head lives in LDS as fp32; thread (i, c) loops are plain dot products in index order.
-constexpr int AB_L = 64, AB_D = 64;
-constexpr int AB_SMEM = (4 * AB_L * (AB_D + 1) + 2 * AB_L * (AB_L + 1)) * 4;
-__global__ __launch_bounds__(256) void attention_backward_kernel(const _Float16* __restrict__ qkv, const float* __restrict__ d_out,
-                                                                 float* __restrict__ d_qkv, int L, int heads, int W, int causal,
-                                                                 unsigned* __restrict__ amax_bits) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char ab_smem[];          // AB_SMEM bytes (> the 64 KB static limit)
-    float (*Q)[AB_D + 1] = reinterpret_cast<float (*)[AB_D + 1]>(ab_smem);
-    float (*K)[AB_D + 1] = Q + AB_L;
-    float (*V)[AB_D + 1] = K + AB_L;
-    float (*dO)[AB_D + 1] = V + AB_L;
-    float (*P)[AB_L + 1] = reinterpret_cast<float (*)[AB_L + 1]>(dO + AB_L);
-    float (*dS)[AB_L + 1] = P + AB_L;
-    const int seq = blockIdx.x / heads, head = blockIdx.x % heads, tid = threadIdx.x;
-    const int64_t row0 = (int64_t)seq * L;
-    for (int idx = tid; idx < L * AB_D; idx += 256) {
-        const int t = idx / AB_D, d = idx % AB_D;
-        const _Float16* r = qkv + (row0 + t) * 3 * W + head * AB_D + d;
-        Q[t][d] = (float)r[0];
-        K[t][d] = (float)r[W];
-        V[t][d] = (float)r[2 * W];
-        dO[t][d] = d_out[(row0 + t) * W + head * AB_D + d];
-    }
-    __syncthreads();
-    // S = Q K^T / 8 (+ causal mask), P = softmax rows.  The products are register tiled - thread (bi, bj) owns the 4 x 4 block of
-    // rows 4 bi.. and columns 4 bj..: 8 LDS reads per 16 multiply-adds instead of 2 per multiply-add (the kernel is bound by its
-    // LDS reads); every element is still one dot product in d order.
-    const int bi = tid >> 4, bj = tid & 15;                    // 16 x 16 blocks of 4 x 4 cover 64 x 64
-    if (4 * bi < L && 4 * bj < L) {
-        float acc[4][4] = {};
-        for (int d = 0; d < AB_D; ++d) {
-            float qa[4], kb[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { qa[u] = Q[min(4 * bi + u, L - 1)][d]; kb[u] = K[min(4 * bj + u, L - 1)][d]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int w = 0; w < 4; ++w) acc[u][w] = fmaf(qa[u], kb[w], acc[u][w]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int i = 4 * bi + u, j = 4 * bj + w;
-                if (i < L && j < L) P[i][j] = (causal && j > i) ? -INFINITY : acc[u][w] * 0.125f;
-            }
-    }
-    __syncthreads();
-    // the row passes: four threads per row (adjacent lanes), every fourth column each, combined by two lane exchanges - one
-    // thread per row walked its 64 columns through LDS latency five times and was two thirds of the kernel
-    const int rr = tid >> 2, rs = tid & 3;
-    {
-        float mx = -INFINITY;
-        if (rr < L) for (int j = rs; j < L; j += 4) mx = fmaxf(mx, P[rr][j]);
-        mx = fmaxf(mx, __shfl_xor(mx, 1, 64)); mx = fmaxf(mx, __shfl_xor(mx, 2, 64));
-        float sum = 0.f;
-        if (rr < L) for (int j = rs; j < L; j += 4) { const float e = expf(P[rr][j] - mx); P[rr][j] = e; sum += e; }
-        sum += __shfl_xor(sum, 1, 64); sum += __shfl_xor(sum, 2, 64);
-        const float inv = 1.0f / sum;
-        if (rr < L) for (int j = rs; j < L; j += 4) P[rr][j] *= inv;
-    }
-    __syncthreads();
-    // dP = dO V^T ; dS = P (dP - sum_j dP P)
-    if (4 * bi < L && 4 * bj < L) {
-        float acc[4][4] = {};
-        for (int d = 0; d < AB_D; ++d) {
-            float oa[4], vb[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { oa[u] = dO[min(4 * bi + u, L - 1)][d]; vb[u] = V[min(4 * bj + u, L - 1)][d]; }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int w = 0; w < 4; ++w) acc[u][w] = fmaf(oa[u], vb[w], acc[u][w]);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                const int i = 4 * bi + u, j = 4 * bj + w;
-                if (i < L && j < L) dS[i][j] = acc[u][w];
-            }
-    }
-    __syncthreads();
-    {
-        float dot = 0.f;
-        if (rr < L) for (int j = rs; j < L; j += 4) dot = fmaf(dS[rr][j], P[rr][j], dot);
-        dot += __shfl_xor(dot, 1, 64); dot += __shfl_xor(dot, 2, 64);
-        if (rr < L) for (int j = rs; j < L; j += 4) dS[rr][j] = P[rr][j] * (dS[rr][j] - dot);
-    }
-    __syncthreads();
-    // dV = P^T dO ; dQ = dS K / 8 ; dK = dS^T Q / 8: thread (bt, bd) owns tokens 4 bt.. x features 4 bd..
-    float am = 0.f;
-    {
-        const int bt = tid >> 4, bd = tid & 15;
-        if (4 * bt < L) {
-            float dv[4][4] = {}, dq[4][4] = {}, dk[4][4] = {};
-            for (int j = 0; j < L; ++j) {
-                float pj[4], sj[4], st[4], od[4], kd[4], qd[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int t = min(4 * bt + u, L - 1);
-                    pj[u] = P[j][t]; sj[u] = dS[j][t]; st[u] = dS[t][j];
-                    od[u] = dO[j][4 * bd + u]; kd[u] = K[j][4 * bd + u]; qd[u] = Q[j][4 * bd + u];
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-#pragma unroll
-                    for (int w = 0; w < 4; ++w) {
-                        dv[u][w] = fmaf(pj[u], od[w], dv[u][w]);
-                        dq[u][w] = fmaf(st[u], kd[w], dq[u][w]);
-                        dk[u][w] = fmaf(sj[u], qd[w], dk[u][w]);
-                    }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int t = 4 * bt + u;
-                if (t < L) {
-                    float* o = d_qkv + (row0 + t) * 3 * W + head * AB_D + 4 * bd;
-                    *reinterpret_cast<float4*>(o) = make_float4(dq[u][0] * 0.125f, dq[u][1] * 0.125f, dq[u][2] * 0.125f, dq[u][3] * 0.125f);
-                    *reinterpret_cast<float4*>(o + W) = make_float4(dk[u][0] * 0.125f, dk[u][1] * 0.125f, dk[u][2] * 0.125f, dk[u][3] * 0.125f);
-                    *reinterpret_cast<float4*>(o + 2 * W) = make_float4(dv[u][0], dv[u][1], dv[u][2], dv[u][3]);
-#pragma unroll
-                    for (int w = 0; w < 4; ++w)
-                        am = fmaxf(fmaxf(am, fabsf(dv[u][w])), 0.125f * fmaxf(fabsf(dq[u][w]), fabsf(dk[u][w])));
-                }
-            }
-        }
-    }
-    if (amax_bits) publish_absmax(am, amax_bits);
-}
+constexpr int AB_L = 64, AB_D = 64;            // attention backward: head_dim, and the longest sequence of the one-launch form
 
-// Attention backward on the matrix cores (L <= 64, head_dim 64): the five 64 x 64 x 64 products of a head as fp16 MFMAs with fp32
-// accumulators instead of fp32 FMAs (the fp32 kernel above spends 95 us per ViT-B/32 block on 3.7 GFLOP of VALU work; the
-// tensors it moves are worth 30 us).  One workgroup per (sequence, head), wave w owns queries 16w..16w+15 for S / dP / dS / dQ
+// Attention backward on the matrix cores (L <= 64, head_dim 64).  q, k, v rows of qkv [nseq*L, 3W] fp16 (row = seq*L + token;
+// heads are 64-wide slices), d_out [nseq*L, W] fp32 -> d_qkv [nseq*L, 3W] fp32.  The five 64 x 64 x 64 products of a head as
+// fp16 MFMAs with fp32 accumulators instead of fp32 FMAs (an fp32 FMA kernel spent 95 us per ViT-B/32 block on 3.7 GFLOP of
+// VALU work; the tensors it moves are worth 30 us).  One workgroup per (sequence, head), wave w owns queries 16w..16w+15 for S / dP / dS / dQ
 // and keys 16w..16w+15 for dV / dK.  fp16 operands: q, k, v as stored; dO scaled by a power of two chosen from the head's own
 // largest |dO| (exact to apply and remove); P; dS scaled by a second power of two from the head's largest |dS| - the same
 // operand precision the dgrad / wgrad GEMMs around it have.  MFMA convention (transformer.hip): D[x row 4 lg + e][y row l15] =
@@ -1163,15 +1033,9 @@ template <int NK64>
 static int launch_attention_backward_long(const _Float16* qkv, const float* d_out, float* d_qkv, float* stats, int nseq, int L, int heads,
                                           int W, int causal, unsigned* amax, hipStream_t st) {
     constexpr int smem = (64 * (NK64 * 64 + 8) + 64 * ABM_S + 4 * 16 * (NK64 * 64 + 8)) * 2 + 64;
-    static bool configured = false;              // benign race (idempotent calls)
-    if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_backward_q_kernel<NK64>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(attention_backward_kv_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, ABK_SMEM) != hipSuccess)
-            return CC_ERR_HIP;
-        configured = true;
-    }
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(attention_backward_q_kernel<NK64>), smem) != CC_OK ||
+        cc_allow_dynamic_lds(reinterpret_cast<const void*>(attention_backward_kv_kernel), ABK_SMEM) != CC_OK)
+        return CC_ERR_HIP;
     const int QT = (L + 63) / 64;
     hipLaunchKernelGGL(attention_backward_q_kernel<NK64>, dim3(nseq * heads * QT), dim3(256), smem, st, qkv, d_out, d_qkv, stats, L, heads,
                        W, causal, amax);
@@ -1260,30 +1124,8 @@ int cc_attention_backward_f16(const void* qkv_f16, const float* d_out, float* d_
             default: return launch_attention_backward_long<5>(q, d_out, d_qkv, static_cast<float*>(ws), nseq, L, heads, W, causal, am, st);
         }
     }
-    static bool configured = false;              // benign race (idempotent call)
-    if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_backward_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, AB_SMEM) != hipSuccess)
-            return CC_ERR_HIP;
-        configured = true;
-    }
-#ifndef CC_ATTENTION_BACKWARD_FP32
-    {
-        static bool configured_m = false;        // benign race (idempotent call)
-        if (!configured_m) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_backward_mfma_kernel),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, ABM_SMEM) != hipSuccess)
-                return CC_ERR_HIP;
-            configured_m = true;
-        }
-        hipLaunchKernelGGL(attention_backward_mfma_kernel, dim3(nseq * heads), dim3(256), ABM_SMEM, static_cast<hipStream_t>(stream),
-                           static_cast<const _Float16*>(qkv_f16), d_out, d_qkv, L, heads, W, causal,
-                           reinterpret_cast<unsigned*>(out_amax));
-        CC_LAUNCH_CHECK();
-        return CC_OK;
-    }
-#endif
-    hipLaunchKernelGGL(attention_backward_kernel, dim3(nseq * heads), dim3(256), AB_SMEM, static_cast<hipStream_t>(stream),
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(attention_backward_mfma_kernel), ABM_SMEM) != CC_OK) return CC_ERR_HIP;
+    hipLaunchKernelGGL(attention_backward_mfma_kernel, dim3(nseq * heads), dim3(256), ABM_SMEM, static_cast<hipStream_t>(stream),
                        static_cast<const _Float16*>(qkv_f16), d_out, d_qkv, L, heads, W, causal, reinterpret_cast<unsigned*>(out_amax));
     CC_LAUNCH_CHECK();
     return CC_OK;

@@ -14,6 +14,14 @@
 
 __host__ __device__ static inline size_t cc_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Opt a kernel into more than the default 64 KB of dynamic LDS; nothing to do at or below it.  Called before every such
+// launch: the attribute is per device, the call is cheap and idempotent - a process-wide "configured" flag would leave every
+// device but the first one at the 64 KB default.
+static inline int cc_allow_dynamic_lds(const void* kernel, size_t bytes) {
+    if (bytes <= 64 * 1024) return CC_OK;
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? CC_OK : CC_ERR_HIP;
+}
+
 // The power of two a gradient enters the fp16 matrix cores with (exact to apply and to remove): 2^floor(log2(16384 / amax)),
 // i.e. scale * amax in [8192, 16384] (16384 where amax is a power of two); 1 for amax 0, inf or NaN.  amax is clamped to
 // 2^-112 from below first, so the scale is at most 2^126 and it and its inverse are normal floats - without the clamp

@@ -1549,21 +1549,12 @@ int run_distance(const float* x, cc_token_layout lay, int W, int metric, float p
     const int nt = (N + GT - 1) / GT;
     dim3 grid((unsigned)(((P + 7) / 8) * 8 * (nt * (nt + 1) / 2)));       // 1-D: problem p on XCD p % 8
     const size_t gram_smem = (size_t)2 * 2 * 2 * GT * GK * sizeof(_Float16) + 2 * GT * sizeof(float);   // 66,048 B
-    if (metric == CC_METRIC_COSINE || p == 2.0f) {
-        static bool configured = false;
-        if (!configured) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_COSINE>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_smem) != hipSuccess ||
-                hipFuncSetAttribute(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_EUCLIDEAN>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_smem) != hipSuccess)
-                return CC_ERR_HIP;
-            configured = true;
-        }
-    }
     if (metric == CC_METRIC_COSINE) {
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_COSINE>), gram_smem) != CC_OK) return CC_ERR_HIP;
         hipLaunchKernelGGL(gram_dist_kernel<CC_METRIC_COSINE>, grid, dim3(256), gram_smem, st, x, lay, N, W, c.sqn, c.nrm,
                            c.inv, own_norms ? 1 : 0, c.draw, c.tilemax, chunk, nt, P);
     } else if (p == 2.0f) {
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_EUCLIDEAN>), gram_smem) != CC_OK) return CC_ERR_HIP;
         hipLaunchKernelGGL(gram_dist_kernel<CC_METRIC_EUCLIDEAN>, grid, dim3(256), gram_smem, st, x, lay, N, W, c.sqn,
                            c.nrm, c.inv, own_norms ? 1 : 0, c.draw, c.tilemax, chunk, nt, P);
     } else if (p == 1.0f) {
@@ -1583,13 +1574,7 @@ int run_distance_sq(const float* x, cc_token_layout lay, int W, const ClusterWs&
     const int nt = (N + GT - 1) / GT;
     dim3 grid((unsigned)(((P + 7) / 8) * 8 * (nt * (nt + 1) / 2)));
     const size_t gram_smem = (size_t)2 * 2 * 2 * GT * GK * sizeof(_Float16) + 2 * GT * sizeof(float);
-    static bool configured = false;
-    if (!configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_SQL2>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_smem) != hipSuccess)
-            return CC_ERR_HIP;
-        configured = true;
-    }
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_SQL2>), gram_smem) != CC_OK) return CC_ERR_HIP;
     hipLaunchKernelGGL(gram_dist_kernel<CC_METRIC_SQL2>, grid, dim3(256), gram_smem, st, x, lay, N, W, c.sqn, c.nrm, c.inv,
                        1, c.draw, c.tilemax, P, nt, P);
     CC_LAUNCH_CHECK();
@@ -1611,9 +1596,7 @@ int run_select(const float* dist_in, float* dist_rw, const float* norms, const i
 #define SEL_LAUNCH(INLDS, NEV)                                                                                         \
     do {                                                                                                               \
         auto kern = kmedoids_select_kernel<INLDS, NEV>;                                                                \
-        if (smem > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                               \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) \
-            return CC_ERR_HIP;                                                                                         \
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kern), smem) != CC_OK) return CC_ERR_HIP;               \
         hipLaunchKernelGGL(kern, dim3(P), dim3(SEL_THREADS), smem, st, dist_in, dist_rw, norms, chunkmax, slots_pp, chunk, apply_shift, \
                            N, K, iter_limit, id_sort, med, assign, iters, gd, ss);                                    \
     } while (0)
@@ -2539,9 +2522,7 @@ int cc_spectral_embedding_solver_f32(const float* laplacian, int32_t P, int32_t 
 #define EIG_LAUNCH(MAXR, INLDS)                                                                                        \
     do {                                                                                                               \
         auto kern = sym_eig_jacobi_kernel<MAXR, INLDS>;                                                                \
-        if (smem > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                               \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) \
-            return CC_ERR_HIP;                                                                                         \
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kern), smem) != CC_OK) return CC_ERR_HIP;               \
         hipLaunchKernelGGL(kern, dim3(P), dim3(64 * EIG_WAVES), smem, st, laplacian, static_cast<float*>(ws), Q, eigenvalues, \
                            sweeps_out, N, K, ldq, correct_sign, max_sweeps, tol);                                     \
     } while (0)

@@ -1075,6 +1075,7 @@ int cc_launch_sym_eig_tridiag(const float* laplacian, int P, int N, int K, int c
 #define TDB_LAUNCH(G, MAXE, MAXQ, MULTI)                                                                                \
     do {                                                                                                               \
         auto kern = sym_eig_tridiag_big_kernel<G, MAXE, MAXQ, MULTI>;                                                   \
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kern), smem) != CC_OK) return CC_ERR_HIP;               \
         hipLaunchKernelGGL(kern, dim3(P), dim3(TD_THREADS), smem, st, laplacian, fw, dw, Q, evals, sweeps_out, N, K, KP, ldq, \
                            correct_sign, (long long)tdb_fstride(N), (long long)tdb_dstride(N, K), g_td_prof);                     \
     } while (0)
@@ -1104,9 +1105,7 @@ int cc_launch_sym_eig_tridiag(const float* laplacian, int P, int N, int K, int c
 #define TD_LAUNCH(MAXT)                                                                                                 \
     do {                                                                                                               \
         auto kern = sym_eig_tridiag_kernel<MAXT>;                                                                      \
-        if (smem > 64 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kern),                               \
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess) \
-            return CC_ERR_HIP;                                                                                         \
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kern), smem) != CC_OK) return CC_ERR_HIP;               \
         hipLaunchKernelGGL(kern, dim3(P), dim3(TD_THREADS), smem, st, laplacian, static_cast<double*>(ws), Q, evals,    \
                            sweeps_out, N, K, KP, ldq, correct_sign, areg, g_td_prof);                                        \
     } while (0)

@@ -31,11 +31,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // a stage are then issued TWO k-steps before its barrier instead of one, which is what an operand that comes from HBM
 // rather than the Infinity Cache needs (a launch inside the step reads what the launch before it has just written: c_proj
 // 55 us with its A operand left in the MALL by the previous launch of a loop, 65-75 us with it cold, tools/cold_operands.py).
-#ifdef CC_TWO_STAGES
-#define GEMM_NST(BM, BN, WAVES, BK) 2
-#else
 #define GEMM_NST(BM, BN, WAVES, BK) (((WAVES) == 8 && (BK) == 64 && 3 * ((BM) + (BN)) * (BK) * 2 <= 160 * 1024) ? 3 : 2)
-#endif
 
 // EPI_ATTN_LN epilogue LDS map (bytes): row statistics [256] x 8 | Q [256][72] | K [256][72] | V^T [64][328] (5 slots of 64
 // keys or 8 of 32) | P strips 8 x [16][72] | sequence table [16] | V^T column of every tile row [256]
@@ -46,11 +42,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define ATTN_SMEM (ATTN_TAB_OFF + 64 + 1024)
 
 // the rows a residual epilogue adds: GemmArgs::R, or the output rows themselves (in place)
-#ifdef CC_NO_RESID_SRC                      /* A/B: the round-4 form (always in place) */
-#define CC_RESID_SRC(g) (reinterpret_cast<const float*>((g).C))
-#else
 #define CC_RESID_SRC(g) ((g).R ? (g).R : reinterpret_cast<const float*>((g).C))
-#endif
 __device__ __forceinline__ void glds16(const _Float16* g, _Float16* l) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
                                      (__attribute__((address_space(3))) void*)l, 16, 0, 0);
@@ -319,11 +311,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     // - the co-resident workgroup already fills the LDS-latency gap.
         constexpr bool HALF_SHIFTED = (NWAVES == 8) || (BM == 64 && BN == 64);
     // residual rows requested from inside the three-stage loop (see there); the epilogue's row-major geometry
-#ifdef CC_NO_RESID_PREFETCH
-    constexpr bool RES_PREFETCH = false;
-#else
     constexpr bool RES_PREFETCH = RESID && NST == 3 && HALF_SHIFTED && BK == GEMM_BK;
-#endif
     constexpr int PF_LPRF = ((BN / WN) / 4 <= 8) ? 8 : 16, PF_RPP = 64 / PF_LPRF, PF_PASSES = 16 / PF_RPP;
     f32x4 resall[RES_PREFETCH ? MI : 1][RES_PREFETCH ? PF_PASSES : 1];
     constexpr bool res_have = RES_PREFETCH;
@@ -790,7 +778,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
 #pragma unroll
                     for (int dt = 0; dt < 4; ++dt) o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf[kb][dt], pf, o[dt], 0, 0, 0);
                 }
-#ifndef CC_ATT_OUT_PLAIN
                 // the 16 x 64 output tile goes back through the wave's strip (P has been consumed) so that a lane stores 16
                 // bytes and 8 lanes a whole 128-byte row segment of one head - written through (sc1): nothing of it is left
                 // dirty in the XCD's L2 for the write-back at the end of the launch (step 1.811 -> 1.802 ms in three same-
@@ -814,16 +801,6 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
                             *reinterpret_cast<h8*>(Cb + e) = ov;
                     }
                 }
-#else
-                if (q < L) {
-                    _Float16* dst = Cb + (int64_t)(row0 + off + q) * g.ldc + tn * 64;
-#pragma unroll
-                    for (int dt = 0; dt < 4; ++dt) {
-                        const h4 oh = {(_Float16)o[dt][0], (_Float16)o[dt][1], (_Float16)o[dt][2], (_Float16)o[dt][3]};
-                        *reinterpret_cast<h4*>(dst + dt * 16 + lg * 4) = oh;
-                    }
-                }
-#endif
                 __builtin_amdgcn_wave_barrier();
             }
         };
@@ -968,20 +945,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
             }
         };
         // (the lane's score registers: NQ x NKTM x 4 - two query tiles per item where that stays inside the wave's budget)
-#ifdef CC_ATTN_LONG_NQ1                                        // A/B arm: one query tile per item
-        constexpr int NQL = 1;
-#else
         constexpr int NQL = 2;
-#endif
         using std::integral_constant;
         using std::true_type;
         using std::false_type;
         const int nkt_all = (((g.att_L + 15) >> 4) + 1) & ~1;       // key tiles of a full-length sequence
-#ifdef CC_ATTN_LONG_GUARDED                                    // A/B arm: always the guarded (run-time key-tile count) form
-        const bool full_ok = false;
-#else
         const bool full_ok = !CAUSAL && !g.att_seq_off;
-#endif
         if (slot > 64 && full_ok && nkt_all == 14) run_items_long(integral_constant<int, 14>{}, integral_constant<int, NQL>{}, true_type{});
         else if (slot > 64 && full_ok && nkt_all == 8) run_items_long(integral_constant<int, 8>{}, integral_constant<int, NQL>{}, true_type{});
         else if (slot > 64 && full_ok && nkt_all == 12) run_items_long(integral_constant<int, 12>{}, integral_constant<int, NQL>{}, true_type{});
@@ -1055,11 +1024,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
                     // leaves the XCD's L2 while the launch runs instead of in the write-back at its end, and nobody re-reads
                     // it from this L2.  Measured per launch in situ (profiles/r04_store_policy.txt): c_fc 57.9 -> 55.6 us; the
                     // same policy on the in_proj output costs that launch 3.5 us, so it is keyed on the epilogue.
-#ifdef CC_PLAIN_F16_STORES
-                    constexpr bool wt_out = false;
-#else
                     const bool wt_out = GELU && (int64_t)g.M * g.ldc < (int64_t)0x3fffffff;   // (32-bit byte offset of the buffer form)
-#endif
                     if (wt_out)
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ov), wt_rsrc(Cb),
                                                                (int)(((int64_t)m * g.ldc + col0 + wc * WTN + lc) * 2), 0, 16);
@@ -1143,11 +1108,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
                 }
                 // write-through (sc1): the rows leave the XCD's L2 while the launch runs instead of in the write-back at its
                 // end (nobody re-reads them from this L2: the consumer is another launch); step 2.000 -> 1.990 ms in 3 A/B rounds
-#ifdef CC_PLAIN_RESID_STORES
-                constexpr bool wt_ok = false;
-#else
                 const bool wt_ok = (int64_t)g.M * g.ldc < (int64_t)0x1fffffff;     // (the buffer form takes a 32-bit byte offset)
-#endif
                 if (m < g.M) {
                     if (wt_ok)
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v.x, v.y, v.z, v.w}), wt_rsrc(g.C),
@@ -1250,15 +1211,7 @@ int launch_one(const GemmPair& pr, int total, hipStream_t st) {
     constexpr size_t smem_loop = (size_t)GEMM_NST(BMS, BN, WM * WN, BK) * (size_t)(BMS + BN) * BK * 2;
     constexpr size_t smem = (EPI == EPI_ATTN_LN && smem_loop < ATTN_SMEM) ? (size_t)ATTN_SMEM : smem_loop;
     auto kern = gemm_f16_kernel<BM, BN, WM, WN, EPI, BK>;
-    if (smem > 64 * 1024) {
-        static bool configured = false;      // per instantiation; benign race (idempotent call)
-        if (!configured) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem) != hipSuccess)
-                return CC_ERR_HIP;
-            configured = true;
-        }
-    }
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kern), smem) != CC_OK) return CC_ERR_HIP;
     const int tid = (g_timing.armed && g_timing.count < g_timing.cap) ? g_timing.count++ : -1;
     if (tid >= 0) {
         const bool two = total > pr.tiles0;
@@ -1274,19 +1227,19 @@ int launch_one(const GemmPair& pr, int total, hipStream_t st) {
     return CC_OK;
 }
 
-template <int BM, int BN, int WM, int WN, int BK = GEMM_BK>
-int launch_tile(GemmArgs g0, const GemmArgs* g1, int epi, hipStream_t st) {
+// the pair of a launch: tile counts of the carrier g0 and of the rider g1 (if any) -> workgroups of the launch
+GemmPair gemm_pair(GemmArgs g0, const GemmArgs* g1, int BM, int BN, int* total) {
     GemmPair pr{};
     g0.tiles_m = (g0.M + BM - 1) / BM;
     g0.tiles_n = g0.N / BN;
     pr.p[0] = g0;
     pr.tiles0 = g0.tiles_m * g0.tiles_n;
-    int total = pr.tiles0;
+    *total = pr.tiles0;
     if (g1) {
         pr.p[1] = *g1;
         pr.p[1].tiles_m = (g1->M + BM - 1) / BM;
         pr.p[1].tiles_n = g1->N / BN;
-        total += pr.p[1].tiles_m * pr.p[1].tiles_n;
+        *total += pr.p[1].tiles_m * pr.p[1].tiles_n;
         // single-round carriers (the clustered blocks): the rider's tiles spill into a second round, see the kernel
         // (2.172 vs 2.182 ms per step over 5 A/B rounds; dev builds: CC_RIDER_PRIO=0 switches it off, =2 applies it to every launch)
 #ifdef CC_DEV_KNOBS
@@ -1298,6 +1251,13 @@ int launch_tile(GemmArgs g0, const GemmArgs* g1, int epi, hipStream_t st) {
     } else {
         pr.p[1] = g0;
     }
+    return pr;
+}
+
+template <int BM, int BN, int WM, int WN, int BK = GEMM_BK>
+int launch_tile(const GemmArgs& g0, const GemmArgs* g1, int epi, hipStream_t st) {
+    int total;
+    const GemmPair pr = gemm_pair(g0, g1, BM, BN, &total);
     switch (epi) {
         case EPI_F16: return launch_one<BM, BN, WM, WN, EPI_F16, BK>(pr, total, st);
         case EPI_F16_GELU: return launch_one<BM, BN, WM, WN, EPI_F16_GELU, BK>(pr, total, st);
@@ -1313,29 +1273,9 @@ int launch_tile(GemmArgs g0, const GemmArgs* g1, int epi, hipStream_t st) {
 
 // tiles whose wave tile is 48 columns wide exist for the fp16-output epilogues and the plain fp32 one
 template <int BM, int BN, int WM, int WN>
-int launch_tile_f16(GemmArgs g0, const GemmArgs* g1, int epi, hipStream_t st) {
-    GemmPair pr{};
-    g0.tiles_m = (g0.M + BM - 1) / BM;
-    g0.tiles_n = g0.N / BN;
-    pr.p[0] = g0;
-    pr.tiles0 = g0.tiles_m * g0.tiles_n;
-    int total = pr.tiles0;
-    if (g1) {
-        pr.p[1] = *g1;
-        pr.p[1].tiles_m = (g1->M + BM - 1) / BM;
-        pr.p[1].tiles_n = g1->N / BN;
-        total += pr.p[1].tiles_m * pr.p[1].tiles_n;
-        // single-round carriers (the clustered blocks): the rider's tiles spill into a second round, see the kernel
-        // (2.172 vs 2.182 ms per step over 5 A/B rounds; dev builds: CC_RIDER_PRIO=0 switches it off, =2 applies it to every launch)
-#ifdef CC_DEV_KNOBS
-        static const int rp = [] { const char* e = getenv("CC_RIDER_PRIO"); return e ? atoi(e) : 1; }();
-#else
-        constexpr int rp = 1;
-#endif
-        pr.rider_prio = (rp == 2) || (rp == 1 && g0.M < 5000);
-    } else {
-        pr.p[1] = g0;
-    }
+int launch_tile_f16(const GemmArgs& g0, const GemmArgs* g1, int epi, hipStream_t st) {
+    int total;
+    const GemmPair pr = gemm_pair(g0, g1, BM, BN, &total);
     switch (epi) {
         case EPI_F16: return launch_one<BM, BN, WM, WN, EPI_F16>(pr, total, st);
         case EPI_F16_GELU: return launch_one<BM, BN, WM, WN, EPI_F16_GELU>(pr, total, st);
@@ -1386,9 +1326,7 @@ static int pick_resid_tile(int M, int N, int K) {
         // -> 1.914 ms, three same-session rounds), at M = 25,600 (600 tiles) it wins both ways (cfg 4 4.429 -> 4.349 ms)
         const long t10n = m128 * (N / 256);
         const double t10 = rounds(t10n, 256) * (11.3 + 0.0141 * K);
-#ifndef CC_NO_RESID_T10
         if (t10n > 256 && t10 < best) { best = t10; tile = 10; }
-#endif
     }
     return tile;
 }
@@ -1411,23 +1349,17 @@ static int pick_tile(const GemmArgs& g, int epi) {
         if (t192 >= 256 && (double)t192 / (double)((t192 + 255) / 256 * 256) >= 0.65 && (!ok256 || r192 * 10 < r256 * 9))
             return 7;
     }
-#ifndef CC_NO_RESID_TILE_MODEL
     if (epi == EPI_F32_RESID_STATS || epi == EPI_F32_RESID || epi == EPI_F32_PATCH) {
         const int t = pick_resid_tile(g.M, g.N, g.K);
         if (t) return t;
     }
-#endif
     if (ok256) return 5;
     // residual epilogue at N = 768: the 256x128 tile (8 waves, one workgroup per CU) when its grid is one nearly full
     // round of the 256 CUs - half the A-panel re-reads of the 128x128 tile (stand-alone c_proj 55.5 vs 58.7 us = 816
     // TFLOP/s, out_proj 24.9 vs 26.2; on the step 2.124 vs 2.128 ms over 3 same-session A/B rounds)
     // (round 4: the same tile for the patch embedding - its A operand, the im2col matrix, is 58 MB the launch before has just
     // written, and the 256x128 tile runs on three stage buffers)
-#ifdef CC_PATCH_TILE1
-    const bool patch6 = false;
-#else
     const bool patch6 = epi == EPI_F32_PATCH;
-#endif
     if ((epi == EPI_F32_RESID_STATS || patch6) && n128) {
         const long t6 = (long)((g.M + 255) / 256) * (g.N / 128);
         if (t6 >= 200 && t6 <= 256) return 6;
@@ -1512,9 +1444,6 @@ static bool attn_problem_ok(const GemmArgs& g) {
            g.ln_c1 && g.bias && !g.row_step && !g.row_map;
 }
 bool cc_gemm_attn_applies(const GemmArgs& g0, const GemmArgs* g1) {
-#ifdef CC_NO_FUSED_ATTENTION
-    return false;
-#endif
     return attn_problem_ok(g0) && (!g1 || attn_problem_ok(*g1));
 }
 // Row-tile height of the launch: 256 rows, or 224 (one 197-token ViT-B/16 frame owns 14 fragment
@@ -1528,9 +1457,6 @@ static int attn_spt(const GemmArgs& g, int bm) {
     return by_rows < by_slots ? by_rows : by_slots;
 }
 static int attn_tile_rows(const GemmArgs& g0, const GemmArgs* g1) {
-#ifdef CC_ATTN_BM256_ONLY                                      /* A/B arm: the round-5 form */
-    return 256;
-#else
     int best = 256;
     long best_cost = -1;
     const int cand[3] = {256, 224, 192};
@@ -1544,7 +1470,6 @@ static int attn_tile_rows(const GemmArgs& g0, const GemmArgs* g1) {
         if (best_cost < 0 || cost < best_cost) { best = bm; best_cost = cost; }
     }
     return best;
-#endif
 }
 int cc_gemm_attn_dispatch2(GemmArgs g0, const GemmArgs* g1, hipStream_t st) {
     if (!gemm_shape_ok(g0) || (g1 && !gemm_shape_ok(*g1)) || !cc_gemm_attn_applies(g0, g1)) return CC_ERR_INVALID;

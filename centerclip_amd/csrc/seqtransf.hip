@@ -194,12 +194,6 @@ __global__ __launch_bounds__(256) void add_rows_kernel(const float* __restrict__
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) out[i] = x[i] + feat[i];
 }
 
-// (set per call: the attribute is per device, the call is cheap and idempotent - a process-wide "configured" flag would leave
-//  every device but the first one at the 64 KB default, as wgrad.hip notes)
-int km_set_smem(const void* fn, size_t bytes) {
-    return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess ? CC_OK : CC_ERR_HIP;
-}
-
 int km_check(const void* qkv, const int64_t* mask, int nseq, int L, int heads, int W) {
     if (!qkv || !mask || nseq <= 0 || L <= 0 || heads <= 0 || W != heads * KM_D) return CC_ERR_INVALID;
     if (L > KM_MAX_L) return CC_ERR_UNSUPPORTED;
@@ -208,7 +202,7 @@ int km_check(const void* qkv, const int64_t* mask, int nseq, int L, int heads, i
 
 int km_launch_forward(const _Float16* qkv, _Float16* out, int nseq, int L, int heads, int W, const int64_t* mask, int64_t mrow,
                       int64_t mcol, hipStream_t st) {
-    const int rc = km_set_smem(reinterpret_cast<const void*>(key_masked_attention_kernel), km_fwd_smem(KM_MAX_L));
+    const int rc = cc_allow_dynamic_lds(reinterpret_cast<const void*>(key_masked_attention_kernel), km_fwd_smem(KM_MAX_L));
     if (rc != CC_OK) return rc;
     hipLaunchKernelGGL(key_masked_attention_kernel, dim3(nseq * heads), dim3(256), km_fwd_smem(L), st, qkv, out, mask, mrow, mcol,
                        L, heads, W);
@@ -237,7 +231,7 @@ int cc_key_masked_attention_backward_f16(const void* qkv_f16, const int64_t* mas
     int rc = km_check(qkv_f16, mask, nseq, L, heads, W);
     if (rc != CC_OK) return rc;
     if (!d_out || !d_qkv) return CC_ERR_INVALID;
-    rc = km_set_smem(reinterpret_cast<const void*>(key_masked_attention_backward_kernel), km_bwd_smem(KM_MAX_L));
+    rc = cc_allow_dynamic_lds(reinterpret_cast<const void*>(key_masked_attention_backward_kernel), km_bwd_smem(KM_MAX_L));
     if (rc != CC_OK) return rc;
     hipLaunchKernelGGL(key_masked_attention_backward_kernel, dim3(nseq * heads), dim3(256), km_bwd_smem(L),
                        static_cast<hipStream_t>(stream), static_cast<const _Float16*>(qkv_f16), mask, mask_row_stride,

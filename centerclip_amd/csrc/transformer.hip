@@ -1061,13 +1061,7 @@ int cc_launch_attention2(const AttArgs& a0, const AttArgs* a1, hipStream_t st) {
     }
     size_t smem = att_smem_bytes(a0.L);
     if (a1 && att_smem_bytes(a1->L) > smem) smem = att_smem_bytes(a1->L);
-    static size_t configured = 64 * 1024;
-    if (smem > configured) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)smem) != hipSuccess)
-            return CC_ERR_HIP;
-        configured = smem;
-    }
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(attention_kernel), smem) != CC_OK) return CC_ERR_HIP;
     hipLaunchKernelGGL(attention_kernel, dim3(total), dim3(256), smem, st, pr, 0.125f);
     CC_LAUNCH_CHECK();
     return CC_OK;

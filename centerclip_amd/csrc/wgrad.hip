@@ -283,10 +283,7 @@ int cc_wgrad_tn_f16(const void* dy_f16, const void* x_f16, float* dw, int32_t M,
     a.partial = static_cast<float*>(ws);
     const size_t tiles = (size_t)(N1 / WG_BN) * (N2 / WG_BN);
     constexpr int smem = WG_NST * 2 * WG_TILE_BYTES;
-    // (set per call: the attribute is per device, the call is cheap and idempotent - a process-wide "configured" flag would
-    //  leave every device but the first one at the 64 KB default)
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_tn_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess)
-        return CC_ERR_HIP;
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(wgrad_tn_kernel), smem) != CC_OK) return CC_ERR_HIP;
     hipStream_t st = static_cast<hipStream_t>(stream);
     hipLaunchKernelGGL(wgrad_tn_kernel, dim3((unsigned)(tiles * a.S)), dim3(256), smem, st, a);
     CC_LAUNCH_CHECK();

@@ -53,6 +53,36 @@ def test_library_exports_nothing_the_header_does_not_declare(libpath):
     assert not undeclared, "exported but not declared in the header: %s" % undeclared
 
 
+def _csrc():
+    d = os.path.join(ROOT, "centerclip_amd", "csrc")
+    return {f: open(os.path.join(d, f)).read() for f in sorted(os.listdir(d)) if f.endswith((".hip", ".h"))}
+
+
+def test_only_instrumentation_macros_are_conditional():
+    """What the shipped build compiles is what the source says: the only CC_ macros a preprocessor conditional may name are
+    the instrumentation switches tools/ builds with.  Measured A/B arms are recorded in profiles/HISTORY.md, not kept."""
+    allowed = {"CC_DEV_KNOBS", "CC_STAMP_WALL", "CC_ATTN_STAMP_AT", "CC_ATTN_STAMP_TID"}
+    seen = set()
+    for f, text in _csrc().items():
+        text = re.sub(r"\\\n", " ", text)                       # a conditional continued over several lines
+        for ln in text.splitlines():
+            m = re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b(.*)", ln)
+            if m:
+                names = set(re.findall(r"\bCC_[A-Za-z0-9_]*", m.group(2)))
+                assert names <= allowed, "%s: conditional on %s: %s" % (f, sorted(names - allowed), ln.strip())
+                seen |= names
+    assert "CC_DEV_KNOBS" in seen, "the scan found no conditional at all"
+
+
+def test_dynamic_lds_opt_in_is_spelled_once():
+    """Kernels that need more than 64 KB of dynamic LDS are opted in through cc_allow_dynamic_lds (cc_common.h), on every
+    call - the attribute is per device; no .hip file calls the runtime for it itself."""
+    src = _csrc()
+    assert "hipFuncSetAttribute" in src["cc_common.h"]
+    users = [f for f, text in src.items() if f.endswith(".hip") and "hipFuncSetAttribute" in text]
+    assert not users, "hipFuncSetAttribute outside cc_common.h: %s" % users
+
+
 def test_workspace_query_and_argument_validation_need_no_gpu(libpath):
     from centerclip_amd import _lib as L
     lib = L.lib()
