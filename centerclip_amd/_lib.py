@@ -40,6 +40,20 @@ class ClusterVariant(ctypes.Structure):
                 ("shift_fold_div", ctypes.c_int32), ("shift_segment", ctypes.c_int32)]
 
 
+class LinearProblem(ctypes.Structure):
+    """cc_linear_problem (include/centerclip_hip.h): one problem of cc_linear_pair_f16 / cc_linear_rows_pair_f16 /
+    cc_inproj_attention_pair_f16; the layout is checked against cc_linear_problem_size()."""
+    _fields_ = [("a", ctypes.c_void_p), ("w", ctypes.c_void_p), ("bias", ctypes.c_void_p), ("c", ctypes.c_void_p),
+                ("resid", ctypes.c_void_p), ("M", ctypes.c_int32), ("N", ctypes.c_int32), ("K", ctypes.c_int32),
+                ("ldc", ctypes.c_int32), ("ln_stats", ctypes.c_void_p), ("ln_slots", ctypes.c_int32),
+                ("ln_c1", ctypes.c_void_p), ("ln_eps", ctypes.c_float), ("stats_out", ctypes.c_void_p),
+                ("c16", ctypes.c_void_p), ("shift_in", ctypes.c_void_p), ("shift_stats", ctypes.c_void_p),
+                ("shift_slots", ctypes.c_int32), ("shift_out", ctypes.c_void_p), ("m_dev", ctypes.c_void_p),
+                ("row_step", ctypes.c_int32), ("row_map", ctypes.c_void_p), ("pos", ctypes.c_void_p),
+                ("patch_n", ctypes.c_int32), ("att_L", ctypes.c_int32), ("att_nseq", ctypes.c_int32),
+                ("att_causal", ctypes.c_int32), ("att_seq_off", ctypes.c_void_p), ("att_seq_len", ctypes.c_void_p)]
+
+
 def _declare(lib):
     c = ctypes
     vp, i32, i64, f32, sz = c.c_void_p, c.c_int32, c.c_int64, c.c_float, c.c_size_t
@@ -87,6 +101,15 @@ def _declare(lib):
     lib.cc_spectral_embedding_f32.restype = c.c_int
     lib.cc_spectral_laplacian_f32.restype = c.c_int
     lib.cc_svd_sign_flip_f32.restype = c.c_int
+    prob = c.POINTER(LinearProblem)
+    lib.cc_linear_problem_size.argtypes = []
+    lib.cc_linear_problem_size.restype = sz
+    lib.cc_linear_pair_f16.argtypes = [prob, prob, i32, i32, c.POINTER(i32), vp]
+    lib.cc_linear_pair_f16.restype = c.c_int
+    lib.cc_linear_rows_pair_f16.argtypes = [prob, prob, i32, c.POINTER(i32), vp]
+    lib.cc_linear_rows_pair_f16.restype = c.c_int
+    lib.cc_inproj_attention_pair_f16.argtypes = [prob, prob, vp]
+    lib.cc_inproj_attention_pair_f16.restype = c.c_int
     for name in ("cc_token_norms_f32", "cc_pairwise_distance_f32", "cc_kmedoids_from_dist_f32",
                  "cc_batch_kmedoids_f32", "cc_token_cluster_f32", "cc_token_cluster_variant_f32",
                  "cc_token_aggregate_f32"):

@@ -1854,6 +1854,77 @@ int cc_linear_resid_stats_f16(const void* a_f16, const void* w_f16, const float*
     return rc;
 }
 
+// ---- the launch forms of the encoders, one op at a time (cc_linear_problem = the caller-set fields of GemmArgs)
+static GemmArgs problem_args(const cc_linear_problem& p) {
+    GemmArgs g{};
+    g.A = static_cast<const _Float16*>(p.a);
+    g.W = static_cast<const _Float16*>(p.w);
+    g.bias = p.bias;
+    g.C = p.c;
+    g.R = p.resid;
+    g.M = p.M; g.N = p.N; g.K = p.K; g.ldc = p.ldc;
+    g.ln_stats = p.ln_stats; g.ln_slots = p.ln_slots; g.ln_c1 = p.ln_c1; g.ln_eps = p.ln_eps;
+    g.stats_out = p.stats_out;
+    g.c16 = static_cast<_Float16*>(p.c16);
+    g.shift_in = p.shift_in; g.shift_stats = p.shift_stats; g.shift_slots = p.shift_slots; g.shift_out = p.shift_out;
+    g.m_dev = p.m_dev;
+    g.row_step = p.row_step; g.row_map = p.row_map;
+    g.pos = p.pos; g.patch_n = p.patch_n;
+    g.att_L = p.att_L; g.att_nseq = p.att_nseq; g.att_causal = p.att_causal;
+    g.att_seq_off = p.att_seq_off; g.att_seq_len = p.att_seq_len;
+    return g;
+}
+// the operands the kernels dereference without a check of their own, per epilogue
+static bool problem_ok(const cc_linear_problem* p, int epi) {
+    if (!p->a || !p->w || !p->c || p->M <= 0 || p->N <= 0 || p->K <= 0) return false;
+    // (rows are stored in 16-byte pieces; the attention output is [M, K], checked by cc_gemm_attn_applies)
+    if (epi != EPI_ATTN_LN && (p->ldc < p->N || (p->ldc % 8))) return false;
+    const bool lnfold = epi == EPI_F16_LN || epi == EPI_F16_GELU_LN || epi == EPI_ATTN_LN;
+    if (lnfold && (!p->ln_stats || !p->ln_c1 || !p->bias || p->ln_slots <= 0 || p->ln_slots > CC_LN_MAX_SLOTS)) return false;
+    if (epi == EPI_F32_RESID_STATS) {
+        if (!p->c16 || !p->stats_out) return false;
+        if (p->shift_stats && (p->shift_slots <= 0 || p->shift_slots > CC_LN_MAX_SLOTS || !p->shift_out)) return false;
+    }
+    if (epi == EPI_F32_PATCH && (!p->pos || p->patch_n <= 0)) return false;
+    return true;
+}
+
+size_t cc_linear_problem_size(void) { return sizeof(cc_linear_problem); }
+
+int cc_linear_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, int32_t epilogue, int32_t tile,
+                       int32_t* slots_out, void* stream) {
+    if (!p0 || epilogue < EPI_F16 || epilogue > EPI_F32_RESID_STATS || (epilogue == EPI_F32_RESID_STATS && !slots_out))
+        return CC_ERR_INVALID;
+    for (const cc_linear_problem* p : {p0, p1})
+        if (p && (!problem_ok(p, epilogue) || p->row_step || p->row_map)) return CC_ERR_INVALID;
+    const GemmArgs g0 = problem_args(*p0), g1 = p1 ? problem_args(*p1) : GemmArgs{};
+    // (the dispatcher bounds the slot count whenever it is asked for one: only the statistics epilogue has slots)
+    int* slots = epilogue == EPI_F32_RESID_STATS ? slots_out : nullptr;
+    if (slots_out && !slots) slots_out[0] = slots_out[1] = 0;
+    return cc_gemm_dispatch2(g0, p1 ? &g1 : nullptr, epilogue, tile, static_cast<hipStream_t>(stream), slots);
+}
+
+int cc_linear_rows_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, int32_t epilogue, int32_t* slots_out,
+                            void* stream) {
+    if (!p0 || (epilogue == EPI_F32_RESID_STATS && !slots_out)) return CC_ERR_INVALID;
+    for (const cc_linear_problem* p : {p0, p1})       // (the few-rows kernel takes its row count from the host)
+        if (p && (!problem_ok(p, epilogue) || p->row_step < 0 || p->m_dev)) return CC_ERR_INVALID;
+    const GemmArgs g0 = problem_args(*p0), g1 = p1 ? problem_args(*p1) : GemmArgs{};
+    return cc_gemm_rows_dispatch2(g0, p1 ? &g1 : nullptr, epilogue, static_cast<hipStream_t>(stream), slots_out);
+}
+
+int cc_inproj_attention_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, void* stream) {
+    if (!p0) return CC_ERR_INVALID;
+    for (const cc_linear_problem* p : {p0, p1})
+        if (p && (!problem_ok(p, EPI_ATTN_LN) || p->att_nseq <= 0 || p->att_L <= 0 ||
+                  (p->att_seq_off == nullptr) != (p->att_seq_len == nullptr) ||
+                  (int64_t)p->M > (int64_t)p->att_nseq * p->att_L || (!p->att_seq_off && p->M != p->att_nseq * p->att_L)))
+            return CC_ERR_INVALID;
+    const GemmArgs g0 = problem_args(*p0), g1 = p1 ? problem_args(*p1) : GemmArgs{};
+    if (!cc_gemm_attn_applies(g0, p1 ? &g1 : nullptr)) return CC_ERR_UNSUPPORTED;
+    return cc_gemm_attn_dispatch2(g0, p1 ? &g1 : nullptr, static_cast<hipStream_t>(stream));
+}
+
 int cc_debug_gemm_timing_begin(int cap) {
     if (g_timing.ev) {
         for (int i = 0; i < 2 * g_timing.cap; ++i) (void)hipEventDestroy(g_timing.ev[i]);

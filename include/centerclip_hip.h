@@ -400,6 +400,68 @@ int cc_linear_resid_stats_f16(const void* a_f16, const void* w_f16, const float*
                               void* h16_out, float* stats_out, int32_t* slots_out, const float* shift_in,
                               const float* stats_in, int32_t slots_in, float* shift_out,
                               int32_t M, int32_t N, int32_t K, int32_t tile, void* stream);
+
+/* The launch forms the fused encoders use, one op at a time: up to TWO independent problems with the same epilogue in one
+ * launch (the text tower's tiles ride in the ViT's grid), the few-rows kernel of the last block, and every per-problem
+ * option of the entries above.  A problem is described by one struct; fields an epilogue does not read stay zero.
+ *   a / w / bias / c / resid, M N K ldc   as cc_linear_f16 (ldc >= N; resid NULL = c, the in-place residual add)
+ *   ln_stats [M][ln_slots][2], ln_c1 [N], ln_eps           LN-folded epilogues (5, 6): as cc_linear_ln_f16, c2 in `bias`
+ *   stats_out [M][slots][2], c16 [M][ldc] fp16             residual + statistics (7): as cc_linear_resid_stats_f16
+ *   shift_in [M], shift_stats [M][shift_slots][2], shift_out [M]     its row centring (shift_stats NULL: c = 0)
+ *   m_dev        device int32, may be NULL: the number of valid rows (<= M, which sizes the grid); rows behind it are
+ *                neither computed nor stored
+ *   row_step / row_map [M] (device int32)   cc_linear_rows_pair_f16 only: logical row m lives at physical row
+ *                row_map ? row_map[m] : m * row_step (0 = 1) of a / c / c16 / resid and of every per-row side array
+ *   pos [1 + patch_n][N], patch_n           CC_EPI_F32_PATCH: out row of patch row m = f * (patch_n + 1) + 1 + i with
+ *                f = m / patch_n, i = m % patch_n, value = a w^T + bias + pos[1 + i] (the class-token rows are not written)
+ *   att_*        cc_inproj_attention_pair_f16: as nseq / L / causal / seq_off / seq_len of cc_inproj_attention_f16
+ *                (N = 3 K, K = heads * 64, ldc = K, M = nseq * L, c = the attention output) */
+typedef struct cc_linear_problem {
+    const void* a;            /* [M, K] fp16 */
+    const void* w;            /* [N, K] fp16 */
+    const float* bias;
+    void* c;
+    const float* resid;
+    int32_t M, N, K, ldc;
+    const float* ln_stats;
+    int32_t ln_slots;
+    const float* ln_c1;
+    float ln_eps;
+    float* stats_out;
+    void* c16;
+    const float* shift_in;
+    const float* shift_stats;
+    int32_t shift_slots;
+    float* shift_out;
+    const int32_t* m_dev;
+    int32_t row_step;
+    const int32_t* row_map;
+    const float* pos;
+    int32_t patch_n;
+    int32_t att_L, att_nseq, att_causal;
+    const int32_t* att_seq_off;
+    const int32_t* att_seq_len;
+} cc_linear_problem;
+#define CC_EPI_F32_PATCH 3        /* patch embedding, see cc_linear_problem::pos */
+#define CC_EPI_F16_LN 5           /* C(fp16) = LN(h) W^T + b from the centred copy and its statistics */
+#define CC_EPI_F16_GELU_LN 6      /* ... with QuickGELU */
+#define CC_EPI_F32_RESID_STATS 7  /* C(fp32) += A W^T + b, + fp16 copy + partial row statistics */
+/* sizeof(cc_linear_problem) as the library was built (a binding checks its own layout against it) */
+size_t cc_linear_problem_size(void);
+/* p0 and, if non-NULL, p1 through the tile kernel in one launch; epilogue 0..7, tile as cc_linear_f16 (a forced tile must
+ * divide both problems; 0 = the choice for p0, narrowed until it divides p1).  slots_out [2] (required for epilogue 7,
+ * else may be NULL): statistics slots per row each problem wrote.  CC_ERR_INVALID - before anything is enqueued - for a
+ * NULL operand, an operand its epilogue needs, row_step / row_map, or a tile that does not divide a problem. */
+int cc_linear_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, int32_t epilogue, int32_t tile,
+                       int32_t* slots_out, void* stream);
+/* The same product for a FEW selected rows (row_step / row_map), in place on the physical rows: epilogues 6, 2 and 7;
+ * N % 32 == 0, K % 32 == 0 and, with statistics, N <= 1024 (N / 32 slots per row) - else CC_ERR_UNSUPPORTED. */
+int cc_linear_rows_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, int32_t epilogue,
+                            int32_t* slots_out, void* stream);
+/* cc_inproj_attention_f16 for one or two problems in one launch (the row-tile height is chosen over both);
+ * CC_ERR_UNSUPPORTED outside the one-launch form's range. */
+int cc_inproj_attention_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, void* stream);
+
 /* Multi-head self-attention core of nn.MultiheadAttention (modules/clip.py:220-226):
  * qkv [nseq*L, 3W] fp16 (row = seq*L + token; q | k | v, heads = contiguous 64-wide slices),
  * out [nseq*L, W] fp16 = softmax(q k^T / 8 + mask) v; causal != 0 adds the strict upper

@@ -40,7 +40,7 @@ def relerr(a, b):
 
 # ------------------------------------------------------------------------------- single ops
 @pytest.mark.parametrize("M,N,K", [(9600, 2304, 768), (2400, 768, 3072), (100, 128, 64), (513, 3072, 768), (77, 512, 2048)])
-@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 6, 8])
+@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 5, 6, 8, 10])
 def test_linear_f16_epilogues(M, N, K, tile):
     from centerclip_amd import ops
     gen = torch.Generator().manual_seed(M + N + K)
@@ -49,7 +49,7 @@ def test_linear_f16_epilogues(M, N, K, tile):
     bias = torch.randn(N, generator=gen)
     ref = a.double() @ w.double().t() + bias.double()
     ad, wd, bd = a.to(DEV), w.to(DEV), bias.to(DEV)
-    if (tile == 5 and N % 256) or (tile in (1, 3, 6) and N % 128) or (tile == 8 and K % 128):
+    if (tile in (5, 10) and N % 256) or (tile in (1, 3, 6) and N % 128) or (tile == 8 and K % 128):
         with pytest.raises(RuntimeError, match="invalid"):      # a forced tile that does not divide N is refused
             ops.linear_f16(ad, wd, bd, "f32", tile=tile)
         return
@@ -205,6 +205,11 @@ def _gemm_sweep():
         tiles = [t for t in (1, 2, 3, 4, 5, 6, 7, 8) if N % {1: 128, 2: 64, 3: 128, 4: 64, 5: 256, 6: 128, 7: 192, 8: 64}[t] == 0
                  and (t != 7 or epi.startswith("f16")) and (t != 8 or K % 128 == 0)]
         out.append((c, M, N, K, epi, int(rng.choice(tiles))))
+    # tile 10 (128 x 256, 8 waves) joins the forced tiles: cases of its own, drawn behind the ones above so that those keep
+    # their shapes
+    for c, epi in enumerate(["f16", "f16_gelu", "f32", "f32_resid"], start=28):
+        M = int(rng.choice([1, 127, 128, 129, 257, 300, 513, 2400]))
+        out.append((c, M, int(rng.integers(1, 5)) * 256, int(rng.integers(1, 17)) * 64, epi, 10))
     return out
 
 
