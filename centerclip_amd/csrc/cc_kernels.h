@@ -73,6 +73,9 @@ struct GemmPair {
     int tiles0;          // workgroups [0, tiles0) -> p[0], the rest -> p[1]
     int rider_prio;      // raise the wave priority of p[1]'s workgroups
 };
+// Carriers (p[0]) below this many rows are "small": one round of workgroups (the clustered blocks, 2,400 - 4,800 rows), where the
+// rider's workgroups get the raised priority; the development knobs (CC_TILE_E*, CC_UNPAIR) split their cases at the same line
+#define CC_BIG_CARRIER_ROWS 5000
 
 int cc_gemm_dispatch(GemmArgs g, int epi, int tile, hipStream_t st);
 // slots_out (optional, [2]): for RESID_STATS the number of partial-sum slots per row each problem wrote

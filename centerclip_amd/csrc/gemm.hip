@@ -1247,43 +1247,49 @@ GemmPair gemm_pair(GemmArgs g0, const GemmArgs* g1, int BM, int BN, int* total) 
 #else
         constexpr int rp = 1;
 #endif
-        pr.rider_prio = (rp == 2) || (rp == 1 && g0.M < 5000);
+        pr.rider_prio = (rp == 2) || (rp == 1 && g0.M < CC_BIG_CARRIER_ROWS);
     } else {
         pr.p[1] = g0;
     }
     return pr;
 }
 
-template <int BM, int BN, int WM, int WN, int BK = GEMM_BK>
-int launch_tile(const GemmArgs& g0, const GemmArgs* g1, int epi, hipStream_t st) {
-    int total;
-    const GemmPair pr = gemm_pair(g0, g1, BM, BN, &total);
-    switch (epi) {
-        case EPI_F16: return launch_one<BM, BN, WM, WN, EPI_F16, BK>(pr, total, st);
-        case EPI_F16_GELU: return launch_one<BM, BN, WM, WN, EPI_F16_GELU, BK>(pr, total, st);
-        case EPI_F32_RESID: return launch_one<BM, BN, WM, WN, EPI_F32_RESID, BK>(pr, total, st);
-        case EPI_F32_PATCH: return launch_one<BM, BN, WM, WN, EPI_F32_PATCH, BK>(pr, total, st);
-        case EPI_F32: return launch_one<BM, BN, WM, WN, EPI_F32, BK>(pr, total, st);
-        case EPI_F16_LN: return launch_one<BM, BN, WM, WN, EPI_F16_LN, BK>(pr, total, st);
-        case EPI_F16_GELU_LN: return launch_one<BM, BN, WM, WN, EPI_F16_GELU_LN, BK>(pr, total, st);
-        case EPI_F32_RESID_STATS: return launch_one<BM, BN, WM, WN, EPI_F32_RESID_STATS, BK>(pr, total, st);
-        default: return CC_ERR_INVALID;
-    }
+// The tiles of gemm_f16_kernel, one row per id (0 = auto): 1 - 4 four waves, 5 - 7 and 10 eight; 7's 48-column wave tiles exist
+// for the fp16-output epilogues and the plain fp32 one only; 8 = 64x64 with 128-deep k-steps (K % 128 == 0).
+// (Ids 9 and 11 were the split-K and persistent stream-K forms of round 4: built, bit-checked, measured slower than the tiled
+// kernel - profiles/r04_splitk.txt, r04_persist.txt - and removed in round 5.)
+struct TileRow { int id, BM, BN, WM, WN, BK; bool f16_only; };
+constexpr TileRow kTiles[] = {
+    {1, 128, 128, 2, 2, GEMM_BK, false}, {2, 128, 64, 2, 2, GEMM_BK, false}, {3, 64, 128, 2, 2, GEMM_BK, false},
+    {4, 64, 64, 2, 2, GEMM_BK, false},   {5, 256, 256, 2, 4, GEMM_BK, false}, {6, 256, 128, 4, 2, GEMM_BK, false},
+    {7, 256, 192, 2, 4, GEMM_BK, true},  {8, 64, 64, 2, 2, 128, false},      {10, 128, 256, 2, 4, GEMM_BK, false},
+};
+constexpr const TileRow* tile_row(int id) {
+    for (const TileRow& t : kTiles)
+        if (t.id == id) return &t;
+    return nullptr;
 }
+int tile_slots(const TileRow& t, int N) { return N / t.BN * t.WN; }      // partial-sum slots per row of a RESID_STATS launch
 
-// tiles whose wave tile is 48 columns wide exist for the fp16-output epilogues and the plain fp32 one
-template <int BM, int BN, int WM, int WN>
-int launch_tile_f16(const GemmArgs& g0, const GemmArgs* g1, int epi, hipStream_t st) {
+template <int ID>
+int launch_tile(const GemmArgs& g0, const GemmArgs* g1, int epi, hipStream_t st) {
+    constexpr TileRow t = *tile_row(ID);
     int total;
-    const GemmPair pr = gemm_pair(g0, g1, BM, BN, &total);
+    const GemmPair pr = gemm_pair(g0, g1, t.BM, t.BN, &total);
     switch (epi) {
-        case EPI_F16: return launch_one<BM, BN, WM, WN, EPI_F16>(pr, total, st);
-        case EPI_F16_GELU: return launch_one<BM, BN, WM, WN, EPI_F16_GELU>(pr, total, st);
-        case EPI_F16_LN: return launch_one<BM, BN, WM, WN, EPI_F16_LN>(pr, total, st);
-        case EPI_F16_GELU_LN: return launch_one<BM, BN, WM, WN, EPI_F16_GELU_LN>(pr, total, st);
-        case EPI_F32: return launch_one<BM, BN, WM, WN, EPI_F32>(pr, total, st);      // (the similarity GEMM)
-        default: return CC_ERR_INVALID;
+        case EPI_F16: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16, t.BK>(pr, total, st);
+        case EPI_F16_GELU: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16_GELU, t.BK>(pr, total, st);
+        case EPI_F16_LN: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16_LN, t.BK>(pr, total, st);
+        case EPI_F16_GELU_LN: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16_GELU_LN, t.BK>(pr, total, st);
+        case EPI_F32: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F32, t.BK>(pr, total, st);      // (the similarity GEMM)
     }
+    if constexpr (!t.f16_only)
+        switch (epi) {
+            case EPI_F32_RESID: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F32_RESID, t.BK>(pr, total, st);
+            case EPI_F32_PATCH: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F32_PATCH, t.BK>(pr, total, st);
+            case EPI_F32_RESID_STATS: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F32_RESID_STATS, t.BK>(pr, total, st);
+        }
+    return CC_ERR_INVALID;
 }
 
 }  // namespace
@@ -1295,8 +1301,6 @@ static bool gemm_shape_ok(const GemmArgs& g) {
 static bool epi_is_f16(int epi) {
     return epi == EPI_F16 || epi == EPI_F16_GELU || epi == EPI_F16_LN || epi == EPI_F16_GELU_LN;
 }
-static int tile_bn(int tile) { return (tile == 5 || tile == 10) ? 256 : tile == 7 ? 192 : (tile == 1 || tile == 3 || tile == 6) ? 128 : 64; }
-static int tile_bk(int tile) { return tile == 8 ? 128 : GEMM_BK; }
 
 // Residual epilogue (out_proj / c_proj) and the patch embedding at N % 128 == 0, M >= 4,800: the tile by a two-parameter time
 // model per tile fitted to tools/resid_sweep.py on MI355X (gpurun_out/s2 of round 5 -> profiles/r05_resid_tile_sweep.txt):
@@ -1380,17 +1384,13 @@ static int pick_tile(const GemmArgs& g, int epi) {
     return (g.K % 128 == 0 && g.K >= 768) ? 8 : 4;
 }
 
-// tile: 0 = auto, 1 = 128x128, 2 = 128x64, 3 = 64x128, 4 = 64x64 (4 waves); 5 = 256x256, 6 = 256x128, 7 = 256x192 (8 waves;
-// 7 only for the fp16-output epilogues); 8 = 64x64 with 128-deep k-steps (K % 128 == 0); 10 = 128x256 (8 waves).
-// (Ids 9 and 11 were the split-K and persistent stream-K forms of round 4: built, bit-checked, measured slower than the tiled
-// kernel - profiles/r04_splitk.txt, r04_persist.txt - and removed in round 5.)
 int cc_gemm_dispatch2(GemmArgs g0, const GemmArgs* g1, int epi, int tile, hipStream_t st, int* slots_out) {
     if (!gemm_shape_ok(g0) || (g1 && !gemm_shape_ok(*g1))) return CC_ERR_INVALID;
     if (tile == 0) {
         tile = pick_tile(g0, epi);
 #ifdef CC_DEV_KNOBS
         // tuning aid (development builds only, -DCC_DEV_KNOBS): CC_TILE_E<epi>_<S|B>[_K<k>]=<tile> overrides the choice for
-        // small (M < 5000) / big problems; the environment is scanned once
+        // small (M < CC_BIG_CARRIER_ROWS) / big problems; the environment is scanned once
         static const bool any_override = [] {
             for (char** e = environ; e && *e; ++e)
                 if (!strncmp(*e, "CC_TILE_", 8)) return true;
@@ -1398,39 +1398,38 @@ int cc_gemm_dispatch2(GemmArgs g0, const GemmArgs* g1, int epi, int tile, hipStr
         }();
         if (any_override) {
             char name[32];
-            snprintf(name, sizeof(name), "CC_TILE_E%d_%c", epi, g0.M < 5000 ? 'S' : 'B');
+            snprintf(name, sizeof(name), "CC_TILE_E%d_%c", epi, g0.M < CC_BIG_CARRIER_ROWS ? 'S' : 'B');
             const char* ov = getenv(name);
-            if (ov && atoi(ov) >= 1 && atoi(ov) <= 10 && atoi(ov) != 9) tile = atoi(ov);
-            snprintf(name, sizeof(name), "CC_TILE_E%d_%c_K%d", epi, g0.M < 5000 ? 'S' : 'B', g0.K);   // one shape only
+            if (ov && tile_row(atoi(ov))) tile = atoi(ov);
+            snprintf(name, sizeof(name), "CC_TILE_E%d_%c_K%d", epi, g0.M < CC_BIG_CARRIER_ROWS ? 'S' : 'B', g0.K);   // one shape only
             ov = getenv(name);
-            if (ov && atoi(ov) >= 1 && atoi(ov) <= 10 && atoi(ov) != 9) tile = atoi(ov);
+            if (ov && tile_row(atoi(ov))) tile = atoi(ov);
         }
 #endif
-        if (g1) {                                  // the rider must be divisible by the carrier's BN
-            if (g1->N % tile_bn(tile)) tile = (g1->N % 128 == 0 && (tile == 5 || tile == 7 || tile == 6)) ? 1 : 4;
-            if (g1->K % tile_bk(tile)) tile = 4;
+        if (g1) {      // the rider must be divisible by the carrier's BN: a 256-row tile falls back to 128x128, the others to 64x64
+            if (g1->N % tile_row(tile)->BN) tile = (g1->N % 128 == 0 && tile_row(tile)->BM == 256) ? 1 : 4;
+            if (g1->K % tile_row(tile)->BK) tile = 4;
         }
     }
-    if (tile == 7 && !epi_is_f16(epi) && epi != EPI_F32) return CC_ERR_INVALID;
-    if ((g0.K % tile_bk(tile)) || (g1 && (g1->K % tile_bk(tile)))) return CC_ERR_INVALID;
-    const int bn = tile_bn(tile);
-    if ((g0.N % bn) || (g1 && (g1->N % bn))) return CC_ERR_INVALID;
+    const TileRow* t = tile_row(tile);
+    if (!t || (t->f16_only && !epi_is_f16(epi) && epi != EPI_F32)) return CC_ERR_INVALID;
+    if ((g0.K % t->BK) || (g1 && (g1->K % t->BK))) return CC_ERR_INVALID;
+    if ((g0.N % t->BN) || (g1 && (g1->N % t->BN))) return CC_ERR_INVALID;
     if (slots_out) {
-        const int wn = (tile == 5 || tile == 10) ? 4 : 2;
-        slots_out[0] = g0.N / bn * wn;
-        slots_out[1] = g1 ? g1->N / bn * wn : 0;
+        slots_out[0] = tile_slots(*t, g0.N);
+        slots_out[1] = g1 ? tile_slots(*t, g1->N) : 0;
         if (slots_out[0] > CC_LN_MAX_SLOTS || slots_out[1] > CC_LN_MAX_SLOTS) return CC_ERR_UNSUPPORTED;
     }
     switch (tile) {
-        case 1: return launch_tile<128, 128, 2, 2>(g0, g1, epi, st);
-        case 2: return launch_tile<128, 64, 2, 2>(g0, g1, epi, st);
-        case 3: return launch_tile<64, 128, 2, 2>(g0, g1, epi, st);
-        case 4: return launch_tile<64, 64, 2, 2>(g0, g1, epi, st);
-        case 5: return launch_tile<256, 256, 2, 4>(g0, g1, epi, st);
-        case 6: return launch_tile<256, 128, 4, 2>(g0, g1, epi, st);
-        case 7: return launch_tile_f16<256, 192, 2, 4>(g0, g1, epi, st);
-        case 8: return launch_tile<64, 64, 2, 2, 128>(g0, g1, epi, st);
-        case 10: return launch_tile<128, 256, 2, 4>(g0, g1, epi, st);
+        case 1: return launch_tile<1>(g0, g1, epi, st);
+        case 2: return launch_tile<2>(g0, g1, epi, st);
+        case 3: return launch_tile<3>(g0, g1, epi, st);
+        case 4: return launch_tile<4>(g0, g1, epi, st);
+        case 5: return launch_tile<5>(g0, g1, epi, st);
+        case 6: return launch_tile<6>(g0, g1, epi, st);
+        case 7: return launch_tile<7>(g0, g1, epi, st);
+        case 8: return launch_tile<8>(g0, g1, epi, st);
+        case 10: return launch_tile<10>(g0, g1, epi, st);
         default: return CC_ERR_INVALID;
     }
 }
@@ -1488,7 +1487,7 @@ int cc_gemm_attn_dispatch2(GemmArgs g0, const GemmArgs* g1, hipStream_t st) {
         pr.p[1] = *g1;
         shape(pr.p[1]);
         total += pr.p[1].tiles_m * pr.p[1].tiles_n;
-        pr.rider_prio = g0.M < 5000;
+        pr.rider_prio = g0.M < CC_BIG_CARRIER_ROWS;
     } else {
         pr.p[1] = g0;
     }
@@ -1806,9 +1805,7 @@ int cc_inproj_attention_f16(const void* h_f16, const void* w_ln_f16, const float
 }
 
 /* Host-side query: the tile the dispatcher picks for a stand-alone launch of this shape and epilogue (CC_EPI_* or the
- * internal ids 5 = LN-folded f16, 6 = LN-folded f16 + QuickGELU, 7 = residual + statistics): 1 = 128x128, 2 = 128x64,
- * 3 = 64x128, 4 = 64x64 (4 waves), 5 = 256x256, 6 = 256x128, 7 = 256x192 (8 waves), 8 = 64x64 with 128-deep k-steps;
- * <= 0: unsupported.
+ * internal ids 5 = LN-folded f16, 6 = LN-folded f16 + QuickGELU, 7 = residual + statistics): an id of kTiles; <= 0: unsupported.
  * (bench.py names the kernel instantiation a shape runs on with it.) */
 int cc_linear_tile_for(int32_t M, int32_t N, int32_t K, int32_t epilogue) {
     GemmArgs g{};
@@ -1824,9 +1821,9 @@ int cc_linear_resid_stats_slots(int32_t M, int32_t N, int32_t K, int32_t tile) {
     g.M = M; g.N = N; g.K = K;
     if (!gemm_shape_ok(g)) return CC_ERR_INVALID;
     if (tile == 0) tile = pick_tile(g, EPI_F32_RESID_STATS);
-    if (tile < 1 || tile > 10 || tile == 7 || tile == 9 || (K % tile_bk(tile)) || (N % tile_bn(tile))) return CC_ERR_INVALID;
-    const int slots = N / tile_bn(tile) * ((tile == 5 || tile == 10) ? 4 : 2);
-    return slots > CC_LN_MAX_SLOTS ? CC_ERR_UNSUPPORTED : slots;
+    const TileRow* t = tile_row(tile);
+    if (!t || t->f16_only || (K % t->BK) || (N % t->BN)) return CC_ERR_INVALID;
+    return tile_slots(*t, N) > CC_LN_MAX_SLOTS ? CC_ERR_UNSUPPORTED : tile_slots(*t, N);
 }
 
 /* Residual Linear that also emits what the next folded LayerNorm needs: h (fp32, in place) += a W^T + b;
