@@ -23,6 +23,7 @@ The [Nt, Nv] matrix never exists on one device and never travels.  A sharded loa
 ranks disagreeing on the dataset size, raise instead of returning a silently wrong matrix.
 """
 import contextlib
+import gc
 import time
 
 import numpy as np
@@ -238,6 +239,7 @@ class _GraphedLane:
             bufs = tuple(t.to(device) for t in batch)
             result = tuple(o.clone() for o in self._step(bufs))
             torch.cuda.current_stream(device).synchronize()
+            gc.collect()                  # (no dead cycle's hipGraph may be destroyed inside the capture: GraphedTrainStep.__call__)
             gph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(gph, stream=self.stream):
                 outs = self._step(bufs)

@@ -1,8 +1,11 @@
 """The training loop: ``train_epoch`` (main.py:291-378, launched op by op) and ``GraphedTrainStep``, the same step
 (main.py:300-340 for one batch) captured into a hipGraph and replayed on static input buffers.
 """
+import gc
+
 import torch
 
+from .checkpoint import checkpoint_dict, restore
 from .optim import AdamW, clip_grad_norm_
 from .scaler import DeviceGradScaler, _device_scaler
 
@@ -110,6 +113,25 @@ class GraphedTrainStep:
         self._torch_scaler.load_state_dict(self.scaler.state_dict())
         return self._torch_scaler
 
+    def state_dict(self, epoch=0, best_acc1=0.0):
+        """The checkpoint dictionary (train.checkpoint_dict) of this step's model, optimizer, scaler and global_step, with the
+        last call's step count settled first; epoch and best_acc1 are the caller's and pass through."""
+        return checkpoint_dict(self.model, self.optimizer, epoch, self.global_step, best_acc1=best_acc1, step=self)
+
+    def load_state_dict(self, d, load_from_pretrained=False):
+        """Restore a checkpoint dictionary -> (start_epoch, global_step, best_acc1); the next call is step global_step + 1 of
+        the resumed run.  Before the first call it is the plain restore (train.resume): warm-up, capture and the put-back
+        of the snapshot then run on the restored values.  After the capture the same restore is entirely in place - the
+        graph holds the addresses of the parameters, of the moments and of the scaler's words - and nothing is captured again:
+        a checkpoint that would need a new tensor (another shape, no state for a parameter the graph updates, another value
+        for a frozen parameter) raises before anything is written."""
+        self.sync()                                               # (a pending count belongs to the state about to be replaced)
+        out = restore(d, self.model, self.optimizer, self.scaler, load_from_pretrained, captured=self.graph is not None)
+        if not load_from_pretrained:
+            self.global_step = out[1]
+            self.write_back_scaler()
+        return out
+
     def _schedule(self):
         if self.scheduler is not None:
             self.scheduler(self.optimizer, global_step=self.global_step)
@@ -192,6 +214,10 @@ class GraphedTrainStep:
             if self.scaler is not None:
                 self.scaler.sync()                                # (no host wait may fall into the capture)
             torch.cuda.synchronize()
+            # dead reference cycles can own hipGraphs (a model that ran eval_epoch(graphed=True) holds its lanes and they hold
+            # it); on ROCm a CUDAGraph's destructor synchronises the device, which ends the process when the cycle collector
+            # happens to run it inside a capture - and torch.cuda.graph no longer collects before it begins
+            gc.collect()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph):                    # (the capture pass does not execute)
                 self.loss = self._step()

@@ -93,6 +93,74 @@ class _Optimizer(torch.optim.Optimizer):
             self.state[p]['step'] -= 1
         self._last = []
 
+    _moment_keys = ()                          # the two moment tensors of a parameter's state (set by the subclasses)
+
+    def _pinned(self):
+        """The parameters whose moments a captured step holds by address: their state can only be restored in place."""
+        return ()
+
+    def _check_state_dict(self, state_dict):
+        """Everything load_state_dict needs of a state dict, checked without a write: the group structure, per parameter
+        with state a 'step' and both moments in the parameter's shape, and for the parameters of a captured step (_pinned)
+        state to copy from and one step count per captured class.  Raises ValueError."""
+        who = type(self).__name__
+        saved = state_dict['param_groups']
+        if len(saved) != len(self.param_groups):
+            raise ValueError("%s.load_state_dict: %d parameter groups in the state dict, %d here"
+                             % (who, len(saved), len(self.param_groups)))
+        ids = {}
+        for gi, (group, sg) in enumerate(zip(self.param_groups, saved)):
+            if len(group['params']) != len(sg['params']):
+                raise ValueError("%s.load_state_dict: group %d holds %d parameters in the state dict, %d here"
+                                 % (who, gi, len(sg['params']), len(group['params'])))
+            for p, sid in zip(group['params'], sg['params']):
+                ids[p] = (sid, gi)
+        state = state_dict['state']
+        for p, (sid, gi) in ids.items():
+            st = state.get(sid)
+            if not st:
+                continue
+            for k in ('step',) + self._moment_keys:
+                if k not in st:
+                    raise ValueError("%s.load_state_dict: the state of parameter %r has no %r" % (who, sid, k))
+            for k in self._moment_keys:
+                if not torch.is_tensor(st[k]) or st[k].shape != p.shape:
+                    raise ValueError("%s.load_state_dict: %s of parameter %r is %s, the parameter is %s"
+                                     % (who, k, sid, tuple(getattr(st[k], 'shape', ())), tuple(p.shape)))
+        counts = {}
+        for p in self._pinned():
+            sid, gi = ids[p]
+            if not state.get(sid):
+                raise ValueError("%s.load_state_dict: the captured step updates parameter %r, and the state dict has no state "
+                                 "for it (its moments can only be restored in place)" % (who, sid))
+            counts.setdefault((gi, int(self.state[p]['step'])), set()).add(int(state[sid]['step']))
+        if any(len(c) > 1 for c in counts.values()):
+            raise ValueError("%s.load_state_dict: parameters the captured step counts together have different step counts in "
+                             "the state dict" % who)
+
+    def load_state_dict(self, state_dict):
+        """torch's load_state_dict (group hyper-parameters from the state dict, state cast to each parameter's dtype and
+        device), except that a parameter that already has moments of the same shape, dtype and device keeps those tensors: the
+        loaded values are copied into them.  A captured step and the record tables (_Staged) hold their addresses - moments
+        that torch had swapped for new tensors would be ignored by every replay, silently.  Checked before the first write
+        (_check_state_dict): a state dict that does not fit raises ValueError and changes nothing."""
+        self._check_state_dict(state_dict)
+        kept = {p: st for p, st in self.state.items() if len(st)}
+        super().load_state_dict(state_dict)
+        with torch.no_grad():
+            for p, old in kept.items():
+                new = self.state.get(p)
+                if not new:
+                    continue
+                for k in self._moment_keys:
+                    a, b = old.get(k), new.get(k)
+                    if torch.is_tensor(a) and torch.is_tensor(b) and (a.shape, a.dtype, a.device) == (b.shape, b.dtype, b.device):
+                        new[k] = a.copy_(b)
+        for st in self.state.values():
+            if torch.is_tensor(st.get('step')):
+                st['step'] = int(st['step'].item())
+        self._last = []                        # (no _uncount reaches back across a restore)
+
 
 _ADAMW_ITEM = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('n', '<i8'), ('blk0', '<i4'),
                         ('blocks', '<i4'), ('scal', '<i4'), ('pad', '<i4')])
@@ -196,6 +264,13 @@ class BertAdam(_Optimizer):
                                       weight_decay=weight_decay, max_grad_norm=max_grad_norm), capturable)
         self._lr_dev = {}                      # group index -> its learning rate as a 1-element device tensor (capturable)
         self._partial = {}                     # (b1, b2, e, max_grad_norm) -> the large tensors' fp64 norm partial sums
+
+    _moment_keys = ('next_m', 'next_v')
+
+    def _pinned(self):
+        if not any(s.keep for s in self._staged.values()):        # (no table staged under a capture: nothing captured)
+            return ()
+        return [p for g in self.param_groups for p in g['params'] if p in self.state and len(self.state[p])]
 
     @staticmethod
     def _lr(group, step):
@@ -395,6 +470,11 @@ class AdamW(_Optimizer):
                          capturable)
         self._scal_dev = None                  # the per-(group, step count) scalars of the step: a device float array
         self._cap = None                       # of the captured step: its classes' (group, parameter) and its parameters
+
+    _moment_keys = ('exp_avg', 'exp_avg_sq')
+
+    def _pinned(self):
+        return self._cap['params'] if self._cap is not None else ()
 
     def load_state_dict(self, state_dict):
         """Also takes torch.optim.AdamW's state (a tensor-valued 'step', its extra group keys)."""

@@ -49,7 +49,7 @@ class DeviceGradScaler:
                 raise ValueError("DeviceGradScaler: growth_interval must be a positive integer, got %r" % (growth_interval,))
         self._init_scale, self._growth_factor = float(init_scale), float(growth_factor)
         self._backoff_factor, self._growth_interval = float(backoff_factor), int(growth_interval)
-        self._init_growth_tracker = 0
+        self._init_growth_tracker, self._init_counters = 0, (0, 0)
         self._f = None            # device float32 [8]: scale, 1 / scale, norm, multiplier, found_inf
         self._c = None            # device int32 [4]: growth tracker, steps taken, steps skipped
         self._pin = self._event = self._pending = None
@@ -67,6 +67,7 @@ class DeviceGradScaler:
             self._event = torch.cuda.Event()
             self._set_scale(self._init_scale)
             self._c[0] = self._init_growth_tracker
+            self._c[1], self._c[2] = self._init_counters
         elif self._f.device != device:
             raise RuntimeError("DeviceGradScaler: one device per scaler (%s, then %s)" % (self._f.device, device))
 
@@ -99,7 +100,7 @@ class DeviceGradScaler:
     def counters(self):
         """-> (steps taken, steps skipped) as update() has counted them on the device (reads the device: synchronises)."""
         if self._c is None:
-            return 0, 0
+            return self._init_counters
         c = self._c.tolist()
         return int(c[1]), int(c[2])
 
@@ -111,6 +112,8 @@ class DeviceGradScaler:
                 "growth_interval": self._growth_interval, "_growth_tracker": tracker}
 
     def load_state_dict(self, state_dict):
+        """In place once the device words exist (a captured step holds their addresses).  'counters' - (steps taken, steps
+        skipped), which train.checkpoint_dict adds to torch's keys - continues counters(); without it they stay as they are."""
         if not self._enabled:
             return
         if len(state_dict) == 0:
@@ -120,9 +123,14 @@ class DeviceGradScaler:
         self._growth_factor, self._backoff_factor = float(state_dict["growth_factor"]), float(state_dict["backoff_factor"])
         self._growth_interval = int(state_dict["growth_interval"])
         self._init_growth_tracker = int(state_dict["_growth_tracker"])
+        if "counters" in state_dict:
+            self._init_counters = tuple(int(c) for c in state_dict["counters"])
         if self._f is not None:
             self._set_scale(self._init_scale)
             self._c[0:1].fill_(self._init_growth_tracker)
+            if "counters" in state_dict:
+                self._c[1:2].fill_(self._init_counters[0])
+                self._c[2:3].fill_(self._init_counters[1])
 
     def _snapshot(self):
         return self._f.clone(), self._c.clone()

@@ -7,6 +7,7 @@ Every compute step runs in the HIP library; swap the state dict for a real ViT-B
 dataloaders/* to evaluate a trained model.
 
     python examples/eval_synthetic.py [--clips 64] [--algo kmediods++|spectral|pooling] [--l14 1 [--oracle-check 1]]
+    python examples/eval_synthetic.py --resume DIR/ckpt.pth.tar      (main.py's --resume ... --do_eval 1: evaluate a checkpoint)
 """
 import argparse
 import os
@@ -108,6 +109,8 @@ def main():
                     help="params.py's --camoe_dsl: rank the CAMoE dual softmax S * softmax(S, dim=0) * len(S) instead of S")
     ap.add_argument("--l14", type=int, default=0, help="ViT-L/14 at 224 px instead (257 tokens per frame, width 1024, 24 layers)")
     ap.add_argument("--oracle-check", type=int, default=0, help="--l14: also compare one 2-frame clip's embeddings with the CPU oracle")
+    ap.add_argument("--resume", default=None, help="main.py's --resume with --do_eval 1: a checkpoint (train_synthetic.py --output_dir) "
+                                                   "whose weights are evaluated")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = L14 if a.l14 else bench.CFG2
@@ -122,6 +125,10 @@ def main():
     if a.l14 and a.oracle_check:
         print("ViT-L/14, 2 frames + 1 caption, max|delta| of normalised embeddings vs oracle: visual %.2e text %.2e" % oracle_check(sd, device))
     model = CLIP4Clip.from_state_dict(sd, args).to(device).eval()
+    if a.resume is not None:
+        from centerclip_amd.train import resume
+        resume(a.resume, model, load_from_pretrained=True)  # (the weights alone: nothing here trains)
+        print("evaluating the weights of %s" % a.resume)
     loader = torch.utils.data.DataLoader(SyntheticRetrieval(a.clips), batch_size=a.batch, shuffle=False)
     r1, seconds, info = eval_epoch(model, loader, device, args, log=print, in_flight=a.in_flight)
     print("\n".join(info))

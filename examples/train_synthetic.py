@@ -21,7 +21,14 @@ launchers' --camoe_dsl): same step, the loss chain gains the column softmax and 
 here a train.DeviceGradScaler - loss scaling, inf / NaN check, step skipping and the scale update all on the device - drives
 the eager loop and, inside the graph, the captured step; the taken / skipped counters are printed at the end.
 
+--epochs N runs train_epoch N times over the same loader; --output_dir DIR writes the reference's checkpoint after every epoch
+(main.py:262-272: save_checkpoint(checkpoint_dict(...), is_best, DIR, filename='ckpt.pth.tar'); there is no eval here, so
+is_best is "lowest mean loss so far"), and the captured step's own state_dict() as ckpt.graph.pth.tar.  --resume PATH restores
+one (main.py:185-212) into the eager loop, which continues at the file's epoch and global_step, and then into the captured step
+before its first call.
+
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
+                                       [--epochs 1] [--output_dir DIR] [--resume DIR/ckpt.pth.tar]
                                        [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--l14 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
@@ -36,8 +43,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from centerclip_amd.clip4clip import CLIP4Clip              # noqa: E402
-from centerclip_amd.train import (AdamW, BertAdam, DeviceGradScaler, lr_scheduler, prep_optim_params_groups,   # noqa: E402
-                                  train_epoch)
+from centerclip_amd.train import (AdamW, BertAdam, DeviceGradScaler, checkpoint_dict, lr_scheduler,   # noqa: E402
+                                  prep_optim_params_groups, resume, save_checkpoint, train_epoch)
 from centerclip_amd import dist as ccdist                   # noqa: E402
 import bench                                                # noqa: E402
 from eval_synthetic import SyntheticRetrieval, L14, l14_state_dict, l14_task_config   # noqa: E402
@@ -78,6 +85,9 @@ def build_parser():
                     help="params.py's --linear_patch; 3d: conv2 over (t, h, w) trains (random init), conv1 takes no part")
     ap.add_argument("--camoe_dsl", type=int, default=0,
                     help="params.py's --camoe_dsl: CAMoE's DSL loss - CrossEn on D = n * S * softmax(S, dim=0), both directions")
+    ap.add_argument("--epochs", type=int, default=1, help="passes of train_epoch over the loader (main.py's --epochs)")
+    ap.add_argument("--output_dir", default=None, help="main.py's --output_dir: write ckpt.pth.tar (and ckpt.best.pth.tar) after every epoch")
+    ap.add_argument("--resume", default=None, help="main.py's --resume: a checkpoint to continue from (eager loop and captured step)")
     return ap
 
 
@@ -126,19 +136,40 @@ def main():
     loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False)
     if a.same_batch:
         loader = [next(iter(loader))] * a.steps
-    t = [time.time()]
+    t, dts = [time.time()], []                              # the last time stamp; every step's duration
 
     def log(epoch, step, loss, sim_loss, gs):
         torch.cuda.synchronize()
-        t.append(time.time())
+        dts.append(time.time() - t[0])
+        t[0] += dts[-1]
         if rank == 0:
-            print("step %d  loss %.4f  %.0f ms" % (gs, loss, (t[-1] - t[-2]) * 1e3), flush=True)
+            print("step %d  loss %.4f  %.0f ms" % (gs, loss, dts[-1] * 1e3), flush=True)
     scaler = DeviceGradScaler() if a.precision == "amp" else None          # (main.py:160: GradScaler(), init_scale 2^16)
-    train_epoch(0, targs, model, loader, device, opt, 0, scheduler=sched, buckets=buckets, log=log, scaler=scaler)
+    start_epoch, global_step, best = 0, 0, float("inf")
+    if a.resume is not None:                                # main.py:185-212 (every rank reads the same file)
+        t0 = time.time()
+        start_epoch, global_step, _ = resume(a.resume, model, opt, scaler)
+        torch.cuda.synchronize()
+        if rank == 0:
+            print("resumed %s in %.2f s: continuing from epoch %d, global_step %d" % (a.resume, time.time() - t0, start_epoch, global_step))
+    if a.output_dir is not None and rank == 0:
+        os.makedirs(a.output_dir, exist_ok=True)
+    for epoch in range(start_epoch, a.epochs):
+        t[0] = time.time()                                  # (a resume or a save is not part of the next step's time)
+        tr_loss, global_step = train_epoch(epoch, targs, model, loader, device, opt, global_step, scheduler=sched, buckets=buckets,
+                                           log=log, scaler=scaler)
+        if rank == 0:
+            print("epoch %d/%d finished, train loss %.6f" % (epoch + 1, a.epochs, tr_loss))
+        if a.output_dir is not None and rank == 0:          # main.py:262-272 (rank 0 saves)
+            t0 = time.time()
+            state = checkpoint_dict(model, opt, epoch + 1, global_step, best_acc1=0.0, scaler=scaler)
+            save_checkpoint(state, tr_loss <= best, a.output_dir, filename='ckpt.pth.tar')
+            best = min(best, tr_loss)
+            print("saved %s in %.2f s" % (os.path.join(a.output_dir, 'ckpt.pth.tar'), time.time() - t0))
     if scaler is not None and rank == 0:
         print("eager, DeviceGradScaler: %d steps taken, %d skipped, scale %g" % (scaler.counters() + (scaler.get_scale(),)))
     if rank == 0:
-        steady = (t[-1] - t[2]) / max(len(t) - 3, 1) if len(t) > 3 else float("nan")
+        steady = sum(dts[2:]) / len(dts[2:]) if len(dts) > 2 else float("nan")
         print("steady step %.0f ms = %.1f clips/s per rank (unfused per-op training path, launched op by op)" % (steady * 1e3, a.batch / steady))
     if a.graph and world == 1:
         # the same step (forward, backward, optimizer, clamp) as ONE hipGraph on static input buffers (train.GraphedTrainStep):
@@ -148,6 +179,11 @@ def main():
         gscaler = DeviceGradScaler() if a.precision == "amp" else None
         stepper = GraphedTrainStep(model, gopt, scheduler=gsched, clip_grad_norm=targs.clip_grad_norm, scaler=gscaler)
         batch = next(iter(loader))
+        if a.resume is not None:                            # in place of a first call's fresh start: restored, then captured
+            t0 = time.time()
+            g_epoch, g_step, _ = resume(a.resume, model, step=stepper)
+            torch.cuda.synchronize()
+            print("captured step resumed %s in %.2f s: continuing from epoch %d, global_step %d" % (a.resume, time.time() - t0, g_epoch, g_step))
         gloss = stepper(batch)
         for _ in range(3):
             stepper(batch)
@@ -161,6 +197,10 @@ def main():
         if gscaler is not None:
             stepper.sync()                                  # the last call's step count (settled one call late)
             print("captured, DeviceGradScaler: %d steps taken, %d skipped, scale %g" % (gscaler.counters() + (gscaler.get_scale(),)))
+        if a.output_dir is not None:
+            t0 = time.time()
+            save_checkpoint(stepper.state_dict(epoch=a.epochs), False, a.output_dir, filename='ckpt.graph.pth.tar')
+            print("captured step: state_dict() + save_checkpoint %.2f s (global_step %d)" % (time.time() - t0, stepper.global_step))
     if a.optim_timing and rank == 0:
         optimizer_timing(model, device)
     if world > 1:
