@@ -2,7 +2,8 @@
 import ctypes as c
 
 CC_MAX_LAYERS = 32
-EPI = {"f16": 0, "f16_gelu": 1, "f32_resid": 2, "f32": 4}
+EPI = {"f16": 0, "f16_gelu": 1, "f32_resid": 2, "f32": 4, "f16_gelu_erf": 9}      # CC_EPI_* of cc_linear_f16
+ACT_QUICK_GELU, ACT_GELU = 0, 1                    # CC_ACT_* (cc_vit_model.activation / cc_text_model.activation)
 
 
 class BlockWeights(c.Structure):
@@ -24,7 +25,8 @@ class VitModel(c.Structure):
                 ("cluster_frames", c.c_int32 * CC_MAX_LAYERS), ("cluster_tokens", c.c_int32 * CC_MAX_LAYERS),
                 ("cluster_metric", c.c_int32), ("cluster_norm_p", c.c_float), ("cluster_threshold", c.c_float),
                 ("cluster_iter_limit", c.c_int32), ("cluster_split_size", c.c_int32), ("cluster_pre_norm", c.c_int32),
-                ("cluster_variants", c.c_void_p), ("row_policy", c.c_int32), ("conv2_weight_f16", c.c_void_p)]
+                ("cluster_variants", c.c_void_p), ("row_policy", c.c_int32), ("conv2_weight_f16", c.c_void_p),
+                ("activation", c.c_int32)]
 
 
 class Frames(c.Structure):
@@ -38,7 +40,7 @@ class TextModel(c.Structure):
                 ("vocab_size", c.c_int32), ("embed_dim", c.c_int32),
                 ("token_embedding", c.c_void_p), ("positional_embedding", c.c_void_p),
                 ("ln_final_weight", c.c_void_p), ("ln_final_bias", c.c_void_p), ("text_projection", c.c_void_p),
-                ("blocks", c.POINTER(BlockWeights)), ("row_policy", c.c_int32)]
+                ("blocks", c.POINTER(BlockWeights)), ("row_policy", c.c_int32), ("activation", c.c_int32)]
 
 
 ROWS_ALL_TEXT, ROWS_ALL_LAST_BLOCK = 1, 2          # CC_ROWS_* (include/centerclip_hip.h)
@@ -144,6 +146,10 @@ def declare(lib):
     lib.cc_quick_gelu_f16.restype = c.c_int
     lib.cc_quick_gelu_backward_f16.argtypes = [vp, vp, vp, i64, vp, vp]
     lib.cc_quick_gelu_backward_f16.restype = c.c_int
+    lib.cc_gelu_f16.argtypes = [vp, vp, i64, vp]
+    lib.cc_gelu_f16.restype = c.c_int
+    lib.cc_gelu_backward_f16.argtypes = [vp, vp, vp, i64, vp, vp]
+    lib.cc_gelu_backward_f16.restype = c.c_int
     lib.cc_attention_backward_f16.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, sz, vp]
     lib.cc_attention_backward_workspace_bytes.argtypes = [i32, i32, i32]
     lib.cc_attention_backward_workspace_bytes.restype = sz

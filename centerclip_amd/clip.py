@@ -20,7 +20,8 @@ import os
 from . import _lib as L
 from . import ops
 from . import torch_ops as T
-from ._lib_clip import BlockWeights, TextModel, VitModel, CC_MAX_LAYERS, ROWS_ALL_TEXT, ROWS_ALL_LAST_BLOCK
+from ._lib_clip import (ACT_GELU, ACT_QUICK_GELU, BlockWeights, TextModel, VitModel, CC_MAX_LAYERS, ROWS_ALL_TEXT,
+                        ROWS_ALL_LAST_BLOCK)
 from .cluster import get_cluster_inter
 
 
@@ -98,12 +99,15 @@ class ResidualAttentionBlock(nn.Module):
     (VisualTransformer.encode, CLIP.encode_text / encode_pair) the compute of all blocks runs from one enqueue;
     ``forward`` is the block-level drop-in of clip.py:228-253 on the reference's LND activations, composed from the same
     op-level entry points (folded LayerNorm -> in_proj, attention, out_proj + residual, folded LayerNorm -> c_fc +
-    QuickGELU, c_proj + residual).  ``attn_mask`` follows the reference: None for the visual tower, the (callable)
+    activation, c_proj + residual).  ``quick_gelu``: True = x sigmoid(1.702 x), the OpenAI release's and the reference's
+    activation (clip.py:192-194); False = the exact GELU x Phi(x) (nn.GELU()) of the OpenCLIP / LAION checkpoints.  A
+    construction argument, not state: it is in no state dict.  ``attn_mask`` follows the reference: None for the visual tower, the (callable)
     causal mask builder for the text tower - the kernels take it as a causal flag.
     ``tokencluster_inter`` is decided per block by get_cluster_inter."""
 
-    def __init__(self, d_model, n_head, attn_mask=None, block_id=1, args=None):
+    def __init__(self, d_model, n_head, attn_mask=None, block_id=1, args=None, quick_gelu=True):
         super().__init__()
+        self.quick_gelu = bool(quick_gelu)
         self.attn = _Attn(d_model)
         self.ln_1 = LayerNorm(d_model)
         self.mlp = nn.ModuleDict({"c_fc": nn.Linear(d_model, d_model * 4), "c_proj": nn.Linear(d_model * 4, d_model)})
@@ -153,17 +157,24 @@ class ResidualAttentionBlock(nn.Module):
             # fp16 copy and statistics ln_2 reads
             torch.ops.centerclip.token_shift_rows(h, N, 1, N, Lq, tc.original_frame, tc.shift_fold_div, T.SHIFT_MODES['token_shift'],
                                                   h16, st1, slots1, sh1)
-        u = ops.linear_ln_f16(h16, w["fc_w"], w["fc_c1"], w["fc_c2"], st1, slots1, gelu=True, eps=self.ln_2.eps)
+        u = ops.linear_ln_f16(h16, w["fc_w"], w["fc_c1"], w["fc_c2"], st1, slots1, gelu=True if self.quick_gelu else "erf",
+                              eps=self.ln_2.eps)
         ops.linear_f16(u, w["proj_w"], w["proj_b"], "f32_resid", out=h)
         return (h.view(Lq, N, W).type(x.dtype), video_frame, cluster_loss)
 
 
 class Transformer(nn.Module):
-    def __init__(self, width, layers, heads, attn_mask=None, args=None):
+    def __init__(self, width, layers, heads, attn_mask=None, args=None, quick_gelu=True):
         super().__init__()
         self.width, self.layers, self.heads = width, layers, heads
-        self.resblocks = nn.Sequential(*[ResidualAttentionBlock(width, heads, attn_mask, i + 1, args)
+        self.quick_gelu = bool(quick_gelu)
+        self.resblocks = nn.Sequential(*[ResidualAttentionBlock(width, heads, attn_mask, i + 1, args, quick_gelu)
                                          for i in range(layers)])
+
+    @property
+    def activation(self):
+        """CC_ACT_* of the tower's blocks (cc_vit_model.activation / cc_text_model.activation)."""
+        return ACT_QUICK_GELU if self.quick_gelu else ACT_GELU
 
     def forward(self, x, video_frame=-1, visual=False):
         """x [L, N, W] (LND) through the blocks one by one (clip.py:264-269); visual=True returns the whole tuple."""
@@ -235,7 +246,7 @@ class _Pack:
 
 class VisualTransformer(nn.Module):
     def __init__(self, input_resolution, patch_size, width, layers, heads, output_dim, linear_patch='2d',
-                 video_frames=None, args=None):
+                 video_frames=None, args=None, quick_gelu=True):
         super().__init__()
         assert linear_patch in ['2d', '3d']
         self.input_resolution, self.patch_size, self.output_dim, self.width = input_resolution, patch_size, output_dim, width
@@ -245,7 +256,7 @@ class VisualTransformer(nn.Module):
         self.class_embedding = nn.Parameter(scale * torch.randn(width))
         self.positional_embedding = nn.Parameter(scale * torch.randn((input_resolution // patch_size) ** 2 + 1, width))
         self.ln_pre = LayerNorm(width)
-        self.transformer = Transformer(width, layers, heads, args=args)
+        self.transformer = Transformer(width, layers, heads, args=args, quick_gelu=quick_gelu)
         self.ln_post = LayerNorm(width)
         self.proj = nn.Parameter(scale * torch.randn(width, output_dim))
         self.linear_patch = linear_patch
@@ -293,6 +304,7 @@ class VisualTransformer(nn.Module):
         pk.keep, pk.key = [], sig
         m = VitModel()
         m.row_policy = ROWS_ALL_LAST_BLOCK if self.all_last_block_rows else 0
+        m.activation = self.transformer.activation
         m.layers, m.width, m.heads = self.transformer.layers, self.width, self.heads
         m.patch, m.resolution, m.embed_dim = self.patch_size, self.input_resolution, self.output_dim
         m.conv1_weight_f16 = pk.f16(pack_conv1_weight(self.conv1.weight))
@@ -454,15 +466,18 @@ class VisualTransformer(nn.Module):
 class CLIP(nn.Module):
     def __init__(self, embed_dim, image_resolution, vision_layers, vision_width, vision_patch_size,
                  context_length, vocab_size, transformer_width, transformer_heads, transformer_layers,
-                 linear_patch='2d', video_frames=None, args=None):
+                 linear_patch='2d', video_frames=None, args=None, quick_gelu=True):
+        """quick_gelu (OpenCLIP's config key): the MLP activation of BOTH towers - True QuickGELU (the OpenAI release),
+        False the exact GELU of the OpenCLIP / LAION checkpoints."""
         super().__init__()
         if isinstance(vision_layers, (tuple, list)):
             raise NotImplementedError("ModifiedResNet visual towers are not built (ViT only)")
         self.context_length = context_length
         self.visual = VisualTransformer(image_resolution, vision_patch_size, vision_width, vision_layers,
-                                        vision_width // 64, embed_dim, linear_patch, video_frames, args)
+                                        vision_width // 64, embed_dim, linear_patch, video_frames, args, quick_gelu)
         self.transformer = Transformer(transformer_width, transformer_layers, transformer_heads,
-                                       attn_mask=self.build_attention_mask)
+                                       attn_mask=self.build_attention_mask, quick_gelu=quick_gelu)
+        self.quick_gelu = bool(quick_gelu)
         self.vocab_size = vocab_size
         self.embed_dim = embed_dim
         self.token_embedding = nn.Embedding(vocab_size, transformer_width)
@@ -552,6 +567,7 @@ class CLIP(nn.Module):
         pk.keep, pk.key = [], sig
         m = TextModel()
         m.row_policy = (ROWS_ALL_TEXT if self.all_text_rows else 0) | (ROWS_ALL_LAST_BLOCK if self.all_last_block_rows else 0)
+        m.activation = self.transformer.activation
         m.layers, m.width, m.heads = self.transformer.layers, self.transformer.width, self.transformer.heads
         m.context_length, m.vocab_size, m.embed_dim = self.context_length, self.vocab_size, self.embed_dim
         m.token_embedding, m.positional_embedding = pk.f32(self.token_embedding.weight), pk.f32(self.positional_embedding)
@@ -582,6 +598,7 @@ class CLIP(nn.Module):
             T.release_model(pk.handle)
         pk.keep, pk.key = [], sig
         m = TextModel()
+        m.activation = self.transformer.activation
         m.layers, m.width, m.heads = self.transformer.layers, self.transformer.width, self.transformer.heads
         m.context_length, m.vocab_size, m.embed_dim = self.context_length, self.vocab_size, self.embed_dim
         m.token_embedding, m.positional_embedding = pk.f32(self.token_embedding.weight), pk.f32(self.positional_embedding)
@@ -654,7 +671,19 @@ _PT_NAME = {"ViT-B/32": "ViT-B-32.pt", "ViT-B/16": "ViT-B-16.pt",      # clip.py
 def load_clip_state_dict(pretrained_clip_name="ViT-B/32", pretrained_dir=os.path.expanduser("~/models/pretrained")):
     """The local-file half of modules/clip.py:load_clip_state_dict: <pretrained_dir>/ViT-B-32.pt as a TorchScript
     archive (the OpenAI release format) or a plain state dict.  Nothing is downloaded (no network on the target boxes):
-    a missing file raises."""
+    a missing file raises.  ``pretrained_clip_name`` may also be the path of an existing file (what the reference's branch at
+    clip.py:661 intends) - an OpenCLIP / LAION checkpoint, say: a ``{'state_dict': ...}`` wrapper is unwrapped, a ``module.``
+    prefix stripped, and the entries the towers do not read (``attn_mask``, ``logit_bias``) are dropped.  Such weights want
+    ``build_clip_model(..., quick_gelu=False)``: nothing in the file says which activation they were trained with."""
+    if pretrained_clip_name not in _PT_NAME and os.path.isfile(pretrained_clip_name):
+        try:
+            sd = torch.jit.load(pretrained_clip_name, map_location="cpu").eval().state_dict()
+        except RuntimeError:
+            sd = torch.load(pretrained_clip_name, map_location="cpu")
+        if isinstance(sd, dict) and isinstance(sd.get("state_dict"), dict):
+            sd = sd["state_dict"]
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+        return {k: v for k, v in sd.items() if k not in ("attn_mask", "logit_bias") and not k.endswith(".attn_mask")}
     if pretrained_clip_name not in _PT_NAME:
         raise NotImplementedError("only the ViT checkpoints are supported, got %r" % (pretrained_clip_name,))
     model_path = os.path.join(pretrained_dir, _PT_NAME[pretrained_clip_name])
@@ -667,10 +696,15 @@ def load_clip_state_dict(pretrained_clip_name="ViT-B/32", pretrained_dir=os.path
 
 
 def build_clip_model(state_dict, convert_fp16=True, linear_patch='2d', cut_top_layer=0, load_state_dict=True,
-                     is_eval=True, video_frames=None, args=None):
+                     is_eval=True, video_frames=None, args=None, quick_gelu=True, vision_heads=None, text_heads=None):
     """Infer the architecture from an OpenAI-CLIP style state dict and build the model
     (modules/clip.py:539-635).  Returns (model, config dict).  ``convert_fp16`` is accepted for
-    signature parity: GEMM operands are always fp16 copies, master parameters stay fp32."""
+    signature parity: GEMM operands are always fp16 copies, master parameters stay fp32.
+    ``quick_gelu=False``: the exact GELU of the OpenCLIP / LAION checkpoints (same key names, same geometry; the state dict
+    does not say which activation it was trained with).
+    Heads are 64 wide everywhere (heads = width // 64, as the reference infers them) - a state dict cannot say otherwise.  A
+    caller that knows the checkpoint's head counts passes ``vision_heads`` / ``text_heads``: a checkpoint with another head
+    width (ViT-H/14: 16 heads of 80) is refused with NotImplementedError this way instead of being built as 20 heads of 64."""
     if "visual.proj" not in state_dict:
         raise NotImplementedError("ModifiedResNet checkpoints are not supported (ViT only)")
     vision_width = state_dict["visual.conv1.weight"].shape[0]
@@ -683,6 +717,10 @@ def build_clip_model(state_dict, convert_fp16=True, linear_patch='2d', cut_top_l
     vocab_size = state_dict["token_embedding.weight"].shape[0]
     transformer_width = state_dict["ln_final.weight"].shape[0]
     transformer_heads = transformer_width // 64
+    for name, width, heads in (("vision_heads", vision_width, vision_heads), ("text_heads", transformer_width, text_heads)):
+        if heads is not None and int(heads) * 64 != width:
+            raise NotImplementedError("%s=%r at width %d is a head width of %g: only 64-wide heads are built"
+                                      % (name, heads, width, width / max(int(heads), 1)))
     transformer_layers = len(set(k.split(".")[2] for k in state_dict if k.startswith("transformer.resblocks")))
     config = dict(embed_dim=embed_dim, image_resolution=image_resolution, vision_layers=vision_layers,
                   vision_width=vision_width, vision_patch_size=vision_patch_size, context_length=context_length,
@@ -690,7 +728,7 @@ def build_clip_model(state_dict, convert_fp16=True, linear_patch='2d', cut_top_l
                   transformer_layers=transformer_layers)
     model = CLIP(embed_dim, image_resolution, vision_layers - cut_top_layer, vision_width, vision_patch_size,
                  context_length, vocab_size, transformer_width, transformer_heads, transformer_layers - cut_top_layer,
-                 linear_patch=linear_patch, video_frames=video_frames, args=args)
+                 linear_patch=linear_patch, video_frames=video_frames, args=args, quick_gelu=quick_gelu)
     if load_state_dict:
         sd = {k: v for k, v in state_dict.items() if k not in ("input_resolution", "context_length", "vocab_size")}
         model.load_state_dict(sd, strict=False)

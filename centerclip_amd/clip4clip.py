@@ -49,7 +49,8 @@ class CLIP4Clip(nn.Module):
         self.clip, self.clip_config = build_clip_model(clip_state_dict, convert_fp16=True,
                                                        linear_patch=self.linear_patch, cut_top_layer=0,
                                                        load_state_dict=True, is_eval=False,
-                                                       video_frames=self.video_frames, args=task_config)
+                                                       video_frames=self.video_frames, args=task_config,
+                                                       quick_gelu=bool(getattr(task_config, "quick_gelu", 1)))
         if self.sim_header == "seqTransf":
             if self.pre_visual_pooling:
                 # (the reference would pool first and then index position 512 of the 77-row table)
@@ -59,10 +60,11 @@ class CLIP4Clip(nn.Module):
             if cfg['embed_dim'] != width:
                 raise ValueError("sim_header='seqTransf': the head runs on the visual features, so embed_dim (%d) must equal "
                                  "transformer_width (%d)" % (cfg['embed_dim'], width))
-            # clip4clip.py:178,187-192: an embedding of context_length rows and module_cross.Transformer (fp32 parameters)
+            # clip4clip.py:178,187-192: an embedding of context_length rows and module_cross.Transformer (fp32 parameters);
+            # the head is CLIP4Clip's own transformer: QuickGELU (module_cross.py) whatever activation the towers use
             self.frame_position_embeddings = nn.Embedding(cfg['context_length'], width)
             self.transformerClip = Transformer(width=width, layers=int(getattr(task_config, "cross_num_hidden_layers", 4)),
-                                               heads=cfg['transformer_heads'])
+                                               heads=cfg['transformer_heads'], quick_gelu=True)
             for blk in self.transformerClip.resblocks:    # nn.MultiheadAttention's own initialisation of the packed in_proj
                 nn.init.xavier_uniform_(blk.attn.in_proj_weight)
             self._head_pack = None

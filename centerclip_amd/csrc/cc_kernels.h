@@ -10,7 +10,10 @@ enum { EPI_F16 = 0, EPI_F16_GELU = 1, EPI_F32_RESID = 2, EPI_F32_PATCH = 3, EPI_
        EPI_F16_LN = 5, EPI_F16_GELU_LN = 6, EPI_F32_RESID_STATS = 7,
        // in_proj with the LayerNorm folded AND the attention of its sequences in the epilogue (cc_gemm_attn_dispatch2 only):
        // the q, k, v rows of a tile never leave the CU - C is the attention output [M, W] fp16
-       EPI_ATTN_LN = 8 };
+       EPI_ATTN_LN = 8,
+       // the exact GELU x Phi(x) of the OpenCLIP checkpoints in place of QuickGELU (cc_vit_model::activation = CC_ACT_GELU):
+       // bias + GELU -> fp16, and the LN-folded form; instantiations of their own, tiles of their QuickGELU counterparts
+       EPI_F16_GELU_ERF = 9, EPI_F16_GELU_ERF_LN = 10 };
 #define CC_LN_MAX_SLOTS 32
 
 struct GemmArgs {
@@ -80,7 +83,7 @@ struct GemmPair {
 int cc_gemm_dispatch(GemmArgs g, int epi, int tile, hipStream_t st);
 // slots_out (optional, [2]): for RESID_STATS the number of partial-sum slots per row each problem wrote
 int cc_gemm_dispatch2(GemmArgs g0, const GemmArgs* g1, int epi, int tile, hipStream_t st, int* slots_out = nullptr);
-// The same product for a FEW selected rows (GemmArgs::row_step / row_map; epilogues EPI_F16_GELU_LN, EPI_F32_RESID and
+// The same product for a FEW selected rows (GemmArgs::row_step / row_map; epilogues EPI_F16_GELU_LN, EPI_F16_GELU_ERF_LN, EPI_F32_RESID and
 // EPI_F32_RESID_STATS; N % 32 == 0, K % 32 == 0; with statistics N <= 32 * CC_LN_MAX_SLOTS): latency-bound, so the K
 // range is split over the 8 waves of a workgroup and the grid has one workgroup per 32 output columns.
 // diagnostics (cc_debug_gemm_timing_*): while armed, -> true and a start / stop event pair for this launch

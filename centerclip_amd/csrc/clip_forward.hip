@@ -125,7 +125,11 @@ struct BlockCtx {          // one tower's activations for the current block
     // token_shift (clip.py:246-248): the CLS rows are shifted again between the out_proj residual and ln_2 - mode
     // CC_CLUSTER_TOKEN_SHIFT, segment, fold divisor; mid_shift 0 = none
     int mid_shift, mid_seg, mid_div;
+    int act;               // CC_ACT_*: the activation behind c_fc (the model's)
 };
+// the c_fc epilogue of an activation
+int c_fc_epi(int act) { return act == CC_ACT_GELU ? EPI_F16_GELU_ERF_LN : EPI_F16_GELU_LN; }
+bool act_ok(int act) { return act == CC_ACT_QUICK_GELU || act == CC_ACT_GELU; }
 
 // One set of row statistics of a tower: st0 / sh0 / slots0 (the rows entering in_proj) or st1 / sh1 / slots1 (entering c_fc)
 struct RowStats { float* st; float* sh; int slots; };
@@ -241,9 +245,16 @@ int run_block_pair(const cc_block_weights* w0, BlockCtx* c0, const cc_block_weig
                                      c->slots1, c->a.sh1, st);
         if (rc) return rc;
     }
-    // ---- u = QuickGELU(c_fc(ln_2(x)))   [LayerNorm folded]      reads set 1
+    // ---- u = act(c_fc(ln_2(x)))   [LayerNorm folded]      reads set 1       act: QuickGELU, or the model's exact GELU
+    // (the epilogue is a template argument of the launch: two towers with different activations launch apart)
     build(C_FC, set1, none);
-    rc = tail_launch(EPI_F16_GELU_LN, 4, nullptr);
+    if (c1 && c0->act != c1->act) {
+        rc = launch_pair(g0, nullptr, c0->sel_rows > 0, false, false, c_fc_epi(c0->act), st, nullptr);
+        if (rc) return rc;
+        rc = launch_pair(g1, nullptr, c1->sel_rows > 0, false, false, c_fc_epi(c1->act), st, nullptr);
+    } else {
+        rc = tail_launch(c_fc_epi(c0->act), 4, nullptr);
+    }
     if (rc) return rc;
     // ---- x = x + c_proj(u)   [+ fp16 copy and row statistics for the next block's ln_1]      reads set 1, writes set 0
     build(C_PROJ, set1, set0);
@@ -404,14 +415,14 @@ int encode_towers(const VisualReq* vr, const TextReq* tr, void* ws, size_t ws_by
     cv.slots0 = ct.slots0 = 1;
     if (tr) {
         ct.a = t.a;
-        ct.nseq = tr->Bt; ct.L = tr->Lt; ct.W = tm->width; ct.heads = tm->heads; ct.causal = 1;
+        ct.nseq = tr->Bt; ct.L = tr->Lt; ct.W = tm->width; ct.heads = tm->heads; ct.causal = 1; ct.act = tm->activation;
         if (compact) { ct.m_dev = t.mcount; ct.seq_off = t.seq_off; ct.seq_len = t.seq_len; }
     }
     float* spare = v.h2;           // the side of the visual ping-pong the next cluster step writes
     if (vr) {
         const int g = vm->resolution / vm->patch;
         cv.a = v.a;
-        cv.nseq = vr->B * vr->T; cv.L = g * g + 1; cv.W = vm->width; cv.heads = vm->heads; cv.causal = 0;
+        cv.nseq = vr->B * vr->T; cv.L = g * g + 1; cv.W = vm->width; cv.heads = vm->heads; cv.causal = 0; cv.act = vm->activation;
         rc = patch_embed(*vr, v, st);
         if (rc) return rc;
     }
@@ -439,15 +450,15 @@ int encode_towers(const VisualReq* vr, const TextReq* tr, void* ws, size_t ws_by
         }
         const bool ht = ti < tl;
         // last block, nobody wants the hidden state: everything behind the attention on the CLS / EOT rows only
-        auto few_rows_ok = [](int Wd) {
-            return cc_gemm_rows_ok(Wd, Wd, EPI_F32_RESID_STATS) && cc_gemm_rows_ok(4 * Wd, Wd, EPI_F16_GELU_LN) &&
+        auto few_rows_ok = [](int Wd, int act) {
+            return cc_gemm_rows_ok(Wd, Wd, EPI_F32_RESID_STATS) && cc_gemm_rows_ok(4 * Wd, Wd, c_fc_epi(act)) &&
                    cc_gemm_rows_ok(Wd, 4 * Wd, EPI_F32_RESID_STATS);
         };
-        if (hv && i == vl - 1 && !vr->hidden_out && !(vm->row_policy & CC_ROWS_ALL_LAST_BLOCK) && cv.L > 1 && few_rows_ok(cv.W)) {
+        if (hv && i == vl - 1 && !vr->hidden_out && !(vm->row_policy & CC_ROWS_ALL_LAST_BLOCK) && cv.L > 1 && few_rows_ok(cv.W, cv.act)) {
             cv.sel_rows = cv.nseq;
             cv.sel_step = cv.L;
         }
-        if (ht && ti == tl - 1 && compact && !(tm->row_policy & CC_ROWS_ALL_LAST_BLOCK) && few_rows_ok(tm->width)) {
+        if (ht && ti == tl - 1 && compact && !(tm->row_policy & CC_ROWS_ALL_LAST_BLOCK) && few_rows_ok(tm->width, ct.act)) {
             ct.sel_rows = tr->Bt;
             ct.sel_map = t.eot;
         }
@@ -498,6 +509,7 @@ int cc_vit_encode_frames(const cc_vit_model* m, const cc_frames* frames, int32_t
                          float* hidden_out, int64_t* medoids_out, const int64_t* forced_medoids, void* ws,
                          size_t ws_bytes, void* stream) {
     if (!m || !frames || !frames->data || !features || !m->blocks || B <= 0 || T <= 0) return CC_ERR_INVALID;
+    if (!act_ok(m->activation)) return CC_ERR_INVALID;
     if (!vit_ok(m)) return CC_ERR_UNSUPPORTED;
     const VisualReq vr{m, frames, B, T, features, hidden_out, medoids_out, forced_medoids};
     return encode_towers(&vr, nullptr, ws, ws_bytes, static_cast<hipStream_t>(stream));
@@ -518,6 +530,7 @@ int cc_vit_encode_prefix_frames(const cc_vit_model* m, const cc_frames* frames, 
                                 float* hidden_out, const int64_t* forced_medoids, void* ws, size_t ws_bytes, void* stream) {
     if (!m || !frames || !frames->data || !hidden_out || B <= 0 || T <= 0) return CC_ERR_INVALID;
     if (n_blocks < 0 || n_blocks > m->layers || (n_blocks > 0 && !m->blocks)) return CC_ERR_INVALID;
+    if (!act_ok(m->activation)) return CC_ERR_INVALID;
     if (!vit_ok(m)) return CC_ERR_UNSUPPORTED;
     if (!frames_base_ok(frames, m->patch)) return CC_ERR_INVALID;
     const VisualReq vr{m, frames, B, T, nullptr, hidden_out, nullptr, forced_medoids, n_blocks};
@@ -564,7 +577,7 @@ size_t cc_text_workspace_bytes(const cc_text_model* m, int32_t Bt, int32_t Lt) {
 int cc_text_encode_hidden(const cc_text_model* m, const int64_t* ids, int32_t Bt, int32_t Lt, float* features,
                           float* hidden_out, void* ws, size_t ws_bytes, void* stream) {
     if (!m || !ids || !features || !m->blocks || Bt <= 0 || Lt <= 0) return CC_ERR_INVALID;
-    if (Lt > m->context_length) return CC_ERR_INVALID;
+    if (Lt > m->context_length || !act_ok(m->activation)) return CC_ERR_INVALID;
     if (!text_ok(m, Lt)) return CC_ERR_UNSUPPORTED;
     const TextReq tr{m, ids, Bt, Lt, features, hidden_out};
     return encode_towers(nullptr, &tr, ws, ws_bytes, static_cast<hipStream_t>(stream));
@@ -573,7 +586,7 @@ int cc_text_encode_hidden(const cc_text_model* m, const int64_t* ids, int32_t Bt
 int cc_text_encode_prefix(const cc_text_model* m, const int64_t* ids, int32_t Bt, int32_t Lt, int32_t n_blocks,
                           float* hidden_out, void* ws, size_t ws_bytes, void* stream) {
     if (!m || !ids || !hidden_out || Bt <= 0 || Lt <= 0 || Lt > m->context_length) return CC_ERR_INVALID;
-    if (n_blocks < 0 || n_blocks > m->layers || (n_blocks > 0 && !m->blocks)) return CC_ERR_INVALID;
+    if (n_blocks < 0 || n_blocks > m->layers || (n_blocks > 0 && !m->blocks) || !act_ok(m->activation)) return CC_ERR_INVALID;
     if (!text_ok(m, Lt)) return CC_ERR_UNSUPPORTED;
     const TextReq tr{m, ids, Bt, Lt, nullptr, hidden_out, n_blocks};
     return encode_towers(nullptr, &tr, ws, ws_bytes, static_cast<hipStream_t>(stream));
@@ -603,6 +616,7 @@ int cc_clip_encode_frames(const cc_vit_model* vm, const cc_frames* frames, int32
         !tm->blocks)
         return CC_ERR_INVALID;
     if (B <= 0 || T <= 0 || Bt <= 0 || Lt <= 0 || Lt > tm->context_length) return CC_ERR_INVALID;
+    if (!act_ok(vm->activation) || !act_ok(tm->activation)) return CC_ERR_INVALID;
     if (!vit_ok(vm) || !text_ok(tm, Lt)) return CC_ERR_UNSUPPORTED;
     const VisualReq vr{vm, frames, B, T, visual_features, nullptr, medoids_out, forced_medoids};
     const TextReq tr{tm, ids, Bt, Lt, text_features, nullptr};

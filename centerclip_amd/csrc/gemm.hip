@@ -59,6 +59,15 @@ __device__ __forceinline__ float quick_gelu(float x) {      // x * sigmoid(1.702
     const float e = __builtin_amdgcn_exp2f(-1.702f * 1.4426950408889634f * x);
     return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
+// the exact GELU x Phi(x) (nn.GELU(), the OpenCLIP checkpoints) as x * erfc(-x / sqrt 2) / 2: the textbook x (1 + erf(x / sqrt 2)) / 2
+// cancels in the negative tail (fp32: up to 3 fp16 ulp off at x = -5.42), erfc keeps its relative accuracy there
+__device__ __forceinline__ float gelu_erf(float x) { return x * (0.5f * erfcf(-0.70710678118654752f * x)); }
+// the activation of an epilogue id (EPI_F16_GELU* / EPI_F16_GELU_ERF*)
+template <int EPI>
+__device__ __forceinline__ float epi_act(float x) {
+    if constexpr (EPI == EPI_F16_GELU_ERF || EPI == EPI_F16_GELU_ERF_LN) return gelu_erf(x);
+    else return quick_gelu(x);
+}
 
 // development builds (-DCC_DEV_KNOBS) only: per-workgroup phase timestamps (entry, prologue done, loop done, exit)
 #ifdef CC_DEV_KNOBS
@@ -182,7 +191,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     // folded LayerNorm: thread r < BM reduces the producer's partial sums of tile row r right away (fixed
     // slot order, 8 loads in flight) - the L2 latency hides under the main loop; result parked in 2 registers.
     float row_mu = 0.f, row_rs = 1.f;
-    if ((EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN || ATTN) && tid < BM) {
+    if ((EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN || EPI == EPI_F16_GELU_ERF_LN || ATTN) && tid < BM) {
         const int m = min(row0 + tid, g.M - 1);
         const float2* ps = reinterpret_cast<const float2*>(g.ln_stats) + (int64_t)m * g.ln_slots;
         float sum = 0.f, sq = 0.f;
@@ -232,7 +241,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     // Per-column epilogue operands (bias, LN-fold column sums) are fetched into registers while the last k-step's
     // MFMAs run: issued from inside the epilogue, behind its stores, every fragment would pay its own L2 round trip.
     constexpr bool RESID = (EPI == EPI_F32_RESID || EPI == EPI_F32_RESID_STATS);
-    constexpr bool LNFOLD = (EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN || ATTN);
+    constexpr bool LNFOLD = (EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN || EPI == EPI_F16_GELU_ERF_LN || ATTN);
     float4 biasv[NI], c1v[LNFOLD ? NI : 1];
     auto fetch_epilogue_operands = [&]() {
 #pragma unroll
@@ -573,9 +582,10 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     GEMM_STAMP(2);
     // ---- epilogue: lane holds C[m = .. + l15][n = .. + lg*4 + 0..3]
     constexpr int WTM = BM / WM, WTN = BN / WN;              // wave tile
-    constexpr bool OUT_F16 = (EPI == EPI_F16 || EPI == EPI_F16_GELU || EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN);
-    constexpr bool FOLD_LN = (EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN);
-    constexpr bool GELU = (EPI == EPI_F16_GELU || EPI == EPI_F16_GELU_LN);
+    constexpr bool GELU_ERF = (EPI == EPI_F16_GELU_ERF || EPI == EPI_F16_GELU_ERF_LN);
+    constexpr bool OUT_F16 = (EPI == EPI_F16 || EPI == EPI_F16_GELU || EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN || GELU_ERF);
+    constexpr bool FOLD_LN = (EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN || EPI == EPI_F16_GELU_ERF_LN);
+    constexpr bool GELU = (EPI == EPI_F16_GELU || EPI == EPI_F16_GELU_LN || GELU_ERF);     // (either activation: the c_fc output)
     if constexpr (ATTN) {
         // ---- in_proj + attention.  The tile's q, k, v (fp16, the very values the two-launch form writes to HBM) go to LDS:
         // Q and K row-major [tile row][64 d] (both are the d-contiguous MFMA operands of S^T = K Q^T), V transposed
@@ -1005,7 +1015,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
                     }
                     if (GELU) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = quick_gelu(v[e]);
+                        for (int e = 0; e < 4; ++e) v[e] = epi_act<EPI>(v[e]);
                     }
                     h4 o;
 #pragma unroll
@@ -1281,6 +1291,8 @@ int launch_tile(const GemmArgs& g0, const GemmArgs* g1, int epi, hipStream_t st)
         case EPI_F16_GELU: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16_GELU, t.BK>(pr, total, st);
         case EPI_F16_LN: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16_LN, t.BK>(pr, total, st);
         case EPI_F16_GELU_LN: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16_GELU_LN, t.BK>(pr, total, st);
+        case EPI_F16_GELU_ERF: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16_GELU_ERF, t.BK>(pr, total, st);
+        case EPI_F16_GELU_ERF_LN: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F16_GELU_ERF_LN, t.BK>(pr, total, st);
         case EPI_F32: return launch_one<t.BM, t.BN, t.WM, t.WN, EPI_F32, t.BK>(pr, total, st);      // (the similarity GEMM)
     }
     if constexpr (!t.f16_only)
@@ -1299,7 +1311,8 @@ static bool gemm_shape_ok(const GemmArgs& g) {
 }
 
 static bool epi_is_f16(int epi) {
-    return epi == EPI_F16 || epi == EPI_F16_GELU || epi == EPI_F16_LN || epi == EPI_F16_GELU_LN;
+    return epi == EPI_F16 || epi == EPI_F16_GELU || epi == EPI_F16_LN || epi == EPI_F16_GELU_LN || epi == EPI_F16_GELU_ERF ||
+           epi == EPI_F16_GELU_ERF_LN;
 }
 
 // Residual epilogue (out_proj / c_proj) and the patch embedding at N % 128 == 0, M >= 4,800: the tile by a two-parameter time
@@ -1502,7 +1515,7 @@ int cc_gemm_attn_dispatch2(GemmArgs g0, const GemmArgs* g1, hipStream_t st) {
 // bound by the latency of the k chain, not by MFMA or HBM rate.  So: one workgroup per 32 output columns, its 8 waves
 // split K (each wave keeps 4 k-steps = 24 16-byte loads per lane in flight, fragments loaded straight from global memory
 // in MFMA layout - both operands are K-contiguous), partial tiles summed through LDS, and the epilogues of the main
-// kernel (folded LayerNorm + QuickGELU; residual add with the centred fp16 copy + partial row statistics) applied on
+// kernel (folded LayerNorm + QuickGELU or the exact GELU; residual add with the centred fp16 copy + partial row statistics) applied on
 // the physical rows.
 struct RowsPair {
     GemmArgs p[2];
@@ -1521,7 +1534,7 @@ __global__ __launch_bounds__(64 * ROWS_WAVES) void gemm_rows_kernel(RowsPair pr)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
     __shared__ float red[ROWS_WAVES / 2][ROWS_BM][ROWS_LDR];     // 36 KB
     __shared__ float2 rowst[ROWS_BM];
-    constexpr bool LNFOLD = (EPI == EPI_F16_GELU_LN);
+    constexpr bool LNFOLD = (EPI == EPI_F16_GELU_LN || EPI == EPI_F16_GELU_ERF_LN);
     constexpr bool STATS = (EPI == EPI_F32_RESID_STATS);
     // The kernel is a chain of memory round trips, so every load is issued as early as its address is known: (1) the
     // physical rows, (2) statistics + the first operand fragments + the epilogue operands, (3..) the rest of K.
@@ -1664,10 +1677,10 @@ __global__ __launch_bounds__(64 * ROWS_WAVES) void gemm_rows_kernel(RowsPair pr)
     }
     if (LNFOLD) {
         const float2 st = rowst[r];
-        v.x = quick_gelu(st.y * (v.x - st.x * c1.x) + bb.x);
-        v.y = quick_gelu(st.y * (v.y - st.x * c1.y) + bb.y);
-        v.z = quick_gelu(st.y * (v.z - st.x * c1.z) + bb.z);
-        v.w = quick_gelu(st.y * (v.w - st.x * c1.w) + bb.w);
+        v.x = epi_act<EPI>(st.y * (v.x - st.x * c1.x) + bb.x);
+        v.y = epi_act<EPI>(st.y * (v.y - st.x * c1.y) + bb.y);
+        v.z = epi_act<EPI>(st.y * (v.z - st.x * c1.z) + bb.z);
+        v.w = epi_act<EPI>(st.y * (v.w - st.x * c1.w) + bb.w);
         const h4 o = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
         if (on) *reinterpret_cast<h4*>(reinterpret_cast<_Float16*>(g.C) + pm * g.ldc + n) = o;
         return;
@@ -1695,7 +1708,7 @@ __global__ __launch_bounds__(64 * ROWS_WAVES) void gemm_rows_kernel(RowsPair pr)
 bool cc_gemm_rows_ok(int N, int K, int epi) {
     if (N <= 0 || K <= 0 || (N % ROWS_BN) || (K % 32)) return false;
     if (epi == EPI_F32_RESID_STATS) return N / ROWS_BN <= CC_LN_MAX_SLOTS;
-    return epi == EPI_F16_GELU_LN || epi == EPI_F32_RESID;
+    return epi == EPI_F16_GELU_LN || epi == EPI_F16_GELU_ERF_LN || epi == EPI_F32_RESID;
 }
 
 int cc_gemm_rows_dispatch2(GemmArgs g0, const GemmArgs* g1, int epi, hipStream_t st, int* slots_out) {
@@ -1711,6 +1724,7 @@ int cc_gemm_rows_dispatch2(GemmArgs g0, const GemmArgs* g1, int epi, hipStream_t
     const dim3 grid(total), block(64 * ROWS_WAVES);
     switch (epi) {
         case EPI_F16_GELU_LN: hipLaunchKernelGGL(gemm_rows_kernel<EPI_F16_GELU_LN>, grid, block, 0, st, pr); break;
+        case EPI_F16_GELU_ERF_LN: hipLaunchKernelGGL(gemm_rows_kernel<EPI_F16_GELU_ERF_LN>, grid, block, 0, st, pr); break;
         case EPI_F32_RESID: hipLaunchKernelGGL(gemm_rows_kernel<EPI_F32_RESID>, grid, block, 0, st, pr); break;
         case EPI_F32_RESID_STATS: hipLaunchKernelGGL(gemm_rows_kernel<EPI_F32_RESID_STATS>, grid, block, 0, st, pr); break;
         default: return CC_ERR_UNSUPPORTED;
@@ -1736,7 +1750,7 @@ int cc_linear_unscaled_f16(const void* a_f16, const void* w_f16, float* c, int32
 int cc_linear_f16(const void* a_f16, const void* w_f16, const float* bias, void* c, int32_t M, int32_t N, int32_t K,
                   int32_t ldc, int32_t epilogue, int32_t tile, void* stream) {
     if (!a_f16 || !w_f16 || !c) return CC_ERR_INVALID;
-    if (epilogue == EPI_F32_PATCH) return CC_ERR_INVALID;
+    if (epilogue == EPI_F32_PATCH || epilogue == EPI_F16_GELU_ERF_LN) return CC_ERR_INVALID;      // (operands this entry cannot carry)
     GemmArgs g{};
     g.A = static_cast<const _Float16*>(a_f16);
     g.W = static_cast<const _Float16*>(w_f16);
@@ -1767,6 +1781,7 @@ int cc_linear_ln_f16(const void* h_f16, const void* w_ln_f16, const float* c1, c
                      int32_t slots, float eps, void* out_f16, int32_t M, int32_t N, int32_t K, int32_t gelu,
                      int32_t tile, void* stream) {
     if (!h_f16 || !w_ln_f16 || !c1 || !c2 || !stats || !out_f16 || slots <= 0 || slots > CC_LN_MAX_SLOTS) return CC_ERR_INVALID;
+    if (gelu < 0 || gelu > 2) return CC_ERR_INVALID;           // 0 none, 1 QuickGELU, 2 the exact GELU
     GemmArgs g{};
     g.A = static_cast<const _Float16*>(h_f16);
     g.W = static_cast<const _Float16*>(w_ln_f16);
@@ -1774,7 +1789,8 @@ int cc_linear_ln_f16(const void* h_f16, const void* w_ln_f16, const float* c1, c
     g.C = out_f16;
     g.M = M; g.N = N; g.K = K; g.ldc = N;
     g.ln_stats = stats; g.ln_slots = slots; g.ln_c1 = c1; g.ln_eps = eps;
-    return cc_gemm_dispatch(g, gelu ? EPI_F16_GELU_LN : EPI_F16_LN, tile, static_cast<hipStream_t>(stream));
+    const int epi = gelu == 2 ? EPI_F16_GELU_ERF_LN : (gelu ? EPI_F16_GELU_LN : EPI_F16_LN);
+    return cc_gemm_dispatch(g, epi, tile, static_cast<hipStream_t>(stream));
 }
 
 /* in_proj with the LayerNorm folded + multi-head attention in ONE launch (modules/clip.py:210-214: ln_1 -> nn.MultiheadAttention's
@@ -1805,12 +1821,13 @@ int cc_inproj_attention_f16(const void* h_f16, const void* w_ln_f16, const float
 }
 
 /* Host-side query: the tile the dispatcher picks for a stand-alone launch of this shape and epilogue (CC_EPI_* or the
- * internal ids 5 = LN-folded f16, 6 = LN-folded f16 + QuickGELU, 7 = residual + statistics): an id of kTiles; <= 0: unsupported.
+ * internal ids 5 = LN-folded f16, 6 = LN-folded f16 + QuickGELU, 7 = residual + statistics, 9 / 10 = 1 / 6 with the exact GELU):
+ * an id of kTiles; <= 0: unsupported.
  * (bench.py names the kernel instantiation a shape runs on with it.) */
 int cc_linear_tile_for(int32_t M, int32_t N, int32_t K, int32_t epilogue) {
     GemmArgs g{};
     g.M = M; g.N = N; g.K = K;
-    if (!gemm_shape_ok(g) || epilogue < 0 || epilogue > EPI_F32_RESID_STATS) return CC_ERR_INVALID;
+    if (!gemm_shape_ok(g) || epilogue < 0 || epilogue > EPI_F16_GELU_ERF_LN || epilogue == EPI_ATTN_LN) return CC_ERR_INVALID;
     return pick_tile(g, epilogue);
 }
 
@@ -1876,7 +1893,7 @@ static bool problem_ok(const cc_linear_problem* p, int epi) {
     if (!p->a || !p->w || !p->c || p->M <= 0 || p->N <= 0 || p->K <= 0) return false;
     // (rows are stored in 16-byte pieces; the attention output is [M, K], checked by cc_gemm_attn_applies)
     if (epi != EPI_ATTN_LN && (p->ldc < p->N || (p->ldc % 8))) return false;
-    const bool lnfold = epi == EPI_F16_LN || epi == EPI_F16_GELU_LN || epi == EPI_ATTN_LN;
+    const bool lnfold = epi == EPI_F16_LN || epi == EPI_F16_GELU_LN || epi == EPI_F16_GELU_ERF_LN || epi == EPI_ATTN_LN;
     if (lnfold && (!p->ln_stats || !p->ln_c1 || !p->bias || p->ln_slots <= 0 || p->ln_slots > CC_LN_MAX_SLOTS)) return false;
     if (epi == EPI_F32_RESID_STATS) {
         if (!p->c16 || !p->stats_out) return false;
@@ -1890,7 +1907,8 @@ size_t cc_linear_problem_size(void) { return sizeof(cc_linear_problem); }
 
 int cc_linear_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, int32_t epilogue, int32_t tile,
                        int32_t* slots_out, void* stream) {
-    if (!p0 || epilogue < EPI_F16 || epilogue > EPI_F32_RESID_STATS || (epilogue == EPI_F32_RESID_STATS && !slots_out))
+    if (!p0 || epilogue < EPI_F16 || epilogue > EPI_F16_GELU_ERF_LN || epilogue == EPI_ATTN_LN ||
+        (epilogue == EPI_F32_RESID_STATS && !slots_out))
         return CC_ERR_INVALID;
     for (const cc_linear_problem* p : {p0, p1})
         if (p && (!problem_ok(p, epilogue) || p->row_step || p->row_map)) return CC_ERR_INVALID;

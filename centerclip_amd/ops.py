@@ -23,7 +23,7 @@ def _is(t, dtype, shape=None):
 
 def linear_f16(a, w, bias, epilogue="f16", out=None, tile=0):
     """y = a @ w.T + bias with a fused epilogue; a [M,K] fp16, w [N,K] fp16, bias [N] fp32|None.
-    epilogue: 'f16' | 'f16_gelu' (QuickGELU) | 'f32' | 'f32_resid' (out += ..., out required)."""
+    epilogue: 'f16' | 'f16_gelu' (QuickGELU) | 'f16_gelu_erf' (the exact GELU) | 'f32' | 'f32_resid' (out += ..., out required)."""
     L.require_device(a, w, bias, out)
     _need(a.dim() == 2 and w.dim() == 2 and _is(a, torch.float16) and _is(w, torch.float16, (w.shape[0], a.shape[1])),
           "linear_f16: a [M, K] and w [N, K] contiguous fp16")
@@ -129,14 +129,19 @@ def row_stats(h, centre=True):
 
 
 def linear_ln_f16(h16, w_ln, c1, c2, stats, slots, gelu=False, eps=1e-5, out=None, tile=0):
-    """LayerNorm-folded Linear (stats laid out [M, slots, 2])."""
+    """LayerNorm-folded Linear (stats laid out [M, slots, 2]).  gelu: False / True (QuickGELU) / 'erf' (the exact GELU x Phi(x)
+    of the OpenCLIP checkpoints)."""
     L.require_device(h16, w_ln, c1, c2, stats)
     _need(h16.dim() == 2 and w_ln.dim() == 2 and _is(h16, torch.float16) and _is(w_ln, torch.float16, (w_ln.shape[0], h16.shape[1])),
           "linear_ln_f16: h16 [M, K] and w_ln [N, K] contiguous fp16")
     _need(_is(c1, torch.float32, (w_ln.shape[0],)) and _is(c2, torch.float32, (w_ln.shape[0],)), "linear_ln_f16: c1, c2 [N] fp32")
     _need(1 <= int(slots) <= LN_MAX_SLOTS and stats.dtype == torch.float32 and stats.is_contiguous()
           and stats.numel() >= h16.shape[0] * int(slots) * 2, "linear_ln_f16: stats [M, slots, 2] fp32, 1 <= slots <= %d" % LN_MAX_SLOTS)
-    y = _ops.linear_ln_f16(h16, w_ln, c1, c2, stats, int(slots), bool(gelu), float(eps), tile)
+    _need(isinstance(gelu, (bool, int)) or gelu == "erf", "linear_ln_f16: gelu False, True or 'erf', not %r" % (gelu,))
+    if gelu == "erf":
+        y = _ops.linear_ln_act_f16(h16, w_ln, c1, c2, stats, int(slots), 2, float(eps), tile)
+    else:
+        y = _ops.linear_ln_f16(h16, w_ln, c1, c2, stats, int(slots), bool(gelu), float(eps), tile)
     if out is not None:
         out.copy_(y)
         return out

@@ -243,6 +243,23 @@ def _(h16, w_ln, c1, c2, stats, slots, gelu, eps, tile):
     return h16.new_empty((h16.shape[0], w_ln.shape[0]))
 
 
+@custom_op(NS + "::linear_ln_act_f16", mutates_args=(), device_types="cuda")
+def linear_ln_act_f16(h16: torch.Tensor, w_ln: torch.Tensor, c1: torch.Tensor, c2: torch.Tensor, stats: torch.Tensor,
+                      slots: int, act: int, eps: float, tile: int) -> torch.Tensor:
+    """linear_ln_f16 with the activation by number: 0 none, 1 QuickGELU, 2 the exact GELU (cc_linear_ln_f16's ``gelu``)."""
+    M, K = h16.shape
+    N = w_ln.shape[0]
+    out = _e(M, N, like=h16, dtype=torch.float16)
+    L.check(L.lib().cc_linear_ln_f16(L.ptr(h16), L.ptr(w_ln), L.ptr(c1), L.ptr(c2), L.ptr(stats), int(slots), float(eps),
+                                     L.ptr(out), M, N, K, int(act), tile, _st(h16)), "cc_linear_ln_f16")
+    return out
+
+
+@linear_ln_act_f16.register_fake
+def _(h16, w_ln, c1, c2, stats, slots, act, eps, tile):
+    return h16.new_empty((h16.shape[0], w_ln.shape[0]))
+
+
 @custom_op(NS + "::inproj_attention_f16", mutates_args=(), device_types="cuda")
 def inproj_attention_f16(h16: torch.Tensor, w_ln: torch.Tensor, c1: torch.Tensor, c2: torch.Tensor, stats: torch.Tensor,
                          slots: int, eps: float, nseq: int, L_tok: int, heads: int, causal: bool,
@@ -1327,7 +1344,7 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "pairwise_distance", "pairwise_distance_cross", "token_norms", "vit_encode", "text_encode", "clip_encode_out", "clip_encode",
        "loose_similarity", "video_pool_normalize", "normalize_rows", "scaled_dot_nt", "scaled_dot_nt_out", "rank_counts",
        "rank_counts_cols", "rank_counts_ref", "group_max_rows", "normalize_rows_planes", "video_pool_normalize_planes",
-       "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward")
+       "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16")
 
 
 def logit_multiplier(logit_scale):

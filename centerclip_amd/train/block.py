@@ -2,7 +2,7 @@
 backward, and both inside torch.autograd (the reference gets the backward from autograd, main.py:321).
 
     x [L, N, W] (LND, as the reference's blocks see it)
-    y = x + out_proj(MHA(in_proj(ln_1(x))))          z = y + c_proj(QuickGELU(c_fc(ln_2(y))))
+    y = x + out_proj(MHA(in_proj(ln_1(x))))          z = y + c_proj(act(c_fc(ln_2(y))))      act: QuickGELU | exact GELU
 
 * forward: the op-level HIP entry points of the inference path (LayerNorm -> fp16, cc_linear_f16, cc_attention_f16,
   residual epilogue), keeping x, ln_1(x), qkv, the attention output, y, ln_2(y), the c_fc output before and after QuickGELU.
@@ -241,7 +241,8 @@ def block_forward_train(block, x_lnd, mid_shift=None, key_mask=None, cluster_don
     n2 = ops.layernorm(y, f32(block.ln_2.weight), f32(block.ln_2.bias), eps=block.ln_2.eps, out_f16=True)
     u_pre = ops.linear_f16(n2, wf[0], f32(block.mlp["c_fc"].bias), "f16")
     u = torch.empty_like(u_pre)
-    _check(L.lib().cc_quick_gelu_f16(L.ptr(u_pre), L.ptr(u), u.numel(), _st(u)), "cc_quick_gelu_f16")
+    act = "cc_quick_gelu_f16" if block.quick_gelu else "cc_gelu_f16"              # the block's activation (a construction argument)
+    _check(getattr(L.lib(), act)(L.ptr(u_pre), L.ptr(u), u.numel(), _st(u)), act)
     z = _linear_resid(u, wp[0], f32(block.mlp["c_proj"].bias), y)
     wt = dict(in_proj=wq[1], out_proj=wo[1], c_fc=wf[1], c_proj=wp[1])                  # W^T of the same read, for the dgrads
     saved = dict(x=x, n1=n1, qkv=qkv, att=att, y=y, n2=n2, u_pre=u_pre, u=u, shape=(Lt, N, W), causal=causal, wt=wt,
@@ -270,13 +271,13 @@ def block_backward(block, saved, dz_lnd, need=None, need_dx=True):
     g = {}
     # z = y + c_proj(u)
     du, g["mlp.c_proj.weight"], g["mlp.c_proj.bias"] = _grad_linear(dz, saved["u"], f16t(block.mlp["c_proj"].weight, "c_proj"), need_dw=nw("mlp.c_proj.weight"), need_db=nw("mlp.c_proj.bias"))
-    # u = QuickGELU(u_pre)
+    # u = act(u_pre): QuickGELU, or the exact GELU of a block built with quick_gelu=False
     # (the three gradients this function produces AND multiplies publish their largest magnitude from the producing kernel:
     #  the fp16 cast of each then needs no pass of its own to choose the scale)
     am = torch.zeros(3, 2, device=dz.device, dtype=torch.float32)
     du_pre = torch.empty_like(du)
-    _check(L.lib().cc_quick_gelu_backward_f16(L.ptr(saved["u_pre"]), L.ptr(du), L.ptr(du_pre), du.numel(), L.ptr(am[0]), _st(du)),
-           "cc_quick_gelu_backward_f16")
+    act = "cc_quick_gelu_backward_f16" if block.quick_gelu else "cc_gelu_backward_f16"
+    _check(getattr(L.lib(), act)(L.ptr(saved["u_pre"]), L.ptr(du), L.ptr(du_pre), du.numel(), L.ptr(am[0]), _st(du)), act)
     # u_pre = c_fc(ln_2(y))
     dn2, g["mlp.c_fc.weight"], g["mlp.c_fc.bias"] = _grad_linear(du_pre, saved["n2"], f16t(block.mlp["c_fc"].weight, "c_fc"), amax=am[0], need_dw=nw("mlp.c_fc.weight"), need_db=nw("mlp.c_fc.bias"))
     dy, g["ln_2.weight"], g["ln_2.bias"] = _ln_backward(saved["y"], f32(block.ln_2.weight), dn2, dz, eps=block.ln_2.eps, amax=am[1], need_params=ln2)   # + the residual branch

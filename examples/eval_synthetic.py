@@ -108,6 +108,8 @@ def main():
     ap.add_argument("--camoe_dsl", type=int, default=0,
                     help="params.py's --camoe_dsl: rank the CAMoE dual softmax S * softmax(S, dim=0) * len(S) instead of S")
     ap.add_argument("--l14", type=int, default=0, help="ViT-L/14 at 224 px instead (257 tokens per frame, width 1024, 24 layers)")
+    ap.add_argument("--quick_gelu", type=int, default=1,
+                    help="0: both towers use the exact GELU of the OpenCLIP / LAION checkpoints (OpenCLIP's config key) instead of QuickGELU")
     ap.add_argument("--oracle-check", type=int, default=0, help="--l14: also compare one 2-frame clip's embeddings with the CPU oracle")
     ap.add_argument("--resume", default=None, help="main.py's --resume with --do_eval 1: a checkpoint (train_synthetic.py --output_dir) "
                                                    "whose weights are evaluated")
@@ -118,6 +120,7 @@ def main():
     args.cluster_algo = a.algo
     args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
     args.camoe_dsl = a.camoe_dsl
+    args.quick_gelu = a.quick_gelu
     if a.algo in ("token_shift", "temporal_shift"):
         shift_plan(args)
     vars(args).update(spectral_sigma=2.0, spectral_graph="HeatKernel", spectral_knn_k=1, spectral_spg=0, svd_correct_sign=1)

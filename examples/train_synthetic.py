@@ -29,7 +29,7 @@ before its first call.
 
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
                                        [--epochs 1] [--output_dir DIR] [--resume DIR/ckpt.pth.tar]
-                                       [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--l14 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
+                                       [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--quick_gelu 0] [--l14 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
 import argparse
@@ -85,6 +85,8 @@ def build_parser():
                     help="params.py's --linear_patch; 3d: conv2 over (t, h, w) trains (random init), conv1 takes no part")
     ap.add_argument("--camoe_dsl", type=int, default=0,
                     help="params.py's --camoe_dsl: CAMoE's DSL loss - CrossEn on D = n * S * softmax(S, dim=0), both directions")
+    ap.add_argument("--quick_gelu", type=int, default=1,
+                    help="0: both towers train with the exact GELU of the OpenCLIP / LAION checkpoints instead of QuickGELU")
     ap.add_argument("--epochs", type=int, default=1, help="passes of train_epoch over the loader (main.py's --epochs)")
     ap.add_argument("--output_dir", default=None, help="main.py's --output_dir: write ckpt.pth.tar (and ckpt.best.pth.tar) after every epoch")
     ap.add_argument("--resume", default=None, help="main.py's --resume: a checkpoint to continue from (eager loop and captured step)")
@@ -108,6 +110,7 @@ def main():
     args.sim_header, args.cross_num_hidden_layers = a.sim_header, a.cross_num_hidden_layers
     args.linear_patch = a.linear_patch
     args.camoe_dsl = a.camoe_dsl
+    args.quick_gelu = a.quick_gelu
     if a.algo != "kmediods++":
         args.cluster_algo = a.algo
         shift_plan(args)

@@ -342,6 +342,7 @@ int cc_token_gather_f32(const float* x, int64_t in_tok_stride, int64_t in_frame_
 #define CC_EPI_F16_GELU 1   /* C(fp16) = QuickGELU(A W^T + b)         modules/clip.py:192-194 */
 #define CC_EPI_F32_RESID 2  /* C(fp32) += A W^T + b   (residual add)  modules/clip.py:240,251 */
 #define CC_EPI_F32 4        /* C(fp32) = A W^T + b                                           */
+#define CC_EPI_F16_GELU_ERF 9   /* C(fp16) = GELU(A W^T + b), the exact x Phi(x) of nn.GELU() (OpenCLIP checkpoints) */
 
 /* nn.Linear forward, y = x W^T + b  (c_fc / c_proj / out_proj: modules/clip.py:207-211; the
  * packed in_proj of nn.MultiheadAttention: clip.py:205).  a [M,K] fp16, w [N,K] fp16, bias
@@ -364,7 +365,8 @@ int cc_layernorm_f32(const float* in, int64_t in_stride, const float* gamma, con
  * (replaces ln_1 -> in_proj and ln_2 -> c_fc of modules/clip.py:240,251):
  *   cc_row_stats_f16          h [rows,W] fp32 -> h16 = fp16(h - c), stats [rows][1][2] = (sum, sum of squares) of h16,
  *                             c = the row mean, written to shift_out [rows] (shift_out NULL: c = 0).
- *   cc_linear_ln_f16          out(fp16) = [QuickGELU](LN(h) W^T + b), from h16, the folded weight and the stats
+ *   cc_linear_ln_f16          out(fp16) = [act](LN(h) W^T + b), from h16, the folded weight and the stats; gelu: 0 no
+ *                             activation, 1 QuickGELU, 2 the exact GELU x Phi(x) (anything else: CC_ERR_INVALID)
  *                             (LayerNorm is invariant to the per-row shift c, so the consumer never sees it)
  *   cc_linear_resid_stats_f16 h += a W^T + b (residual), h16 = fp16(h - c), stats [M][*slots_out][2] (one slot per
  *                             tile column x wave column; stats buffers must hold 32 slots per row).  c = the row mean
@@ -392,7 +394,7 @@ int cc_inproj_attention_f16(const void* h_f16, const void* w_ln_f16, const float
                             const int32_t* seq_off, const int32_t* seq_len, const int32_t* m_dev, void* stream);
 /* host-side query: the tile (1 = 128x128, 2 = 128x64, 3 = 64x128, 4 = 64x64, 5 = 256x256, 6 = 256x128, 7 = 256x192, 8 = 64x64 with
  * 128-deep k-steps, 10 = 128x256) the dispatcher picks for this shape / epilogue id (CC_EPI_*; 5, 6 =
- * LN-folded f16 without / with QuickGELU, 7 = residual + statistics); <= 0: unsupported */
+ * LN-folded f16 without / with QuickGELU, 7 = residual + statistics, 9 / 10 = 1 / 6 with the exact GELU); <= 0: unsupported */
 int cc_linear_tile_for(int32_t M, int32_t N, int32_t K, int32_t epilogue);
 /* host-side query: slots per row cc_linear_resid_stats_f16 will write for this shape (tile 0 = auto); <= 0: unsupported */
 int cc_linear_resid_stats_slots(int32_t M, int32_t N, int32_t K, int32_t tile);
@@ -446,15 +448,16 @@ typedef struct cc_linear_problem {
 #define CC_EPI_F16_LN 5           /* C(fp16) = LN(h) W^T + b from the centred copy and its statistics */
 #define CC_EPI_F16_GELU_LN 6      /* ... with QuickGELU */
 #define CC_EPI_F32_RESID_STATS 7  /* C(fp32) += A W^T + b, + fp16 copy + partial row statistics */
+#define CC_EPI_F16_GELU_ERF_LN 10 /* as 6 with the exact GELU x Phi(x) in place of QuickGELU (id 8 is internal) */
 /* sizeof(cc_linear_problem) as the library was built (a binding checks its own layout against it) */
 size_t cc_linear_problem_size(void);
-/* p0 and, if non-NULL, p1 through the tile kernel in one launch; epilogue 0..7, tile as cc_linear_f16 (a forced tile must
+/* p0 and, if non-NULL, p1 through the tile kernel in one launch; epilogue 0..7, 9 or 10, tile as cc_linear_f16 (a forced tile must
  * divide both problems; 0 = the choice for p0, narrowed until it divides p1).  slots_out [2] (required for epilogue 7,
  * else may be NULL): statistics slots per row each problem wrote.  CC_ERR_INVALID - before anything is enqueued - for a
  * NULL operand, an operand its epilogue needs, row_step / row_map, or a tile that does not divide a problem. */
 int cc_linear_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, int32_t epilogue, int32_t tile,
                        int32_t* slots_out, void* stream);
-/* The same product for a FEW selected rows (row_step / row_map), in place on the physical rows: epilogues 6, 2 and 7;
+/* The same product for a FEW selected rows (row_step / row_map), in place on the physical rows: epilogues 6, 10, 2 and 7;
  * N % 32 == 0, K % 32 == 0 and, with statistics, N <= 1024 (N / 32 slots per row) - else CC_ERR_UNSUPPORTED. */
 int cc_linear_rows_pair_f16(const cc_linear_problem* p0, const cc_linear_problem* p1, int32_t epilogue,
                             int32_t* slots_out, void* stream);
@@ -509,6 +512,12 @@ int cc_fold_layernorm_linear_f32(const float* weight, const float* bias, const f
 
 #define CC_MAX_LAYERS 32
 
+/* cc_vit_model.activation / cc_text_model.activation: the MLP activation of the tower's blocks.  0 (a zero-filled struct) is the
+ * reference's model; the OpenCLIP / LAION checkpoints of the same architecture use nn.GELU().  Any other value: CC_ERR_INVALID
+ * before anything is launched.  (The seqTransf head is CLIP4Clip's own transformer: QuickGELU whatever the towers use.) */
+#define CC_ACT_QUICK_GELU 0   /* x sigmoid(1.702 x), modules/clip.py:192-194 */
+#define CC_ACT_GELU       1   /* x Phi(x), evaluated as x erfc(-x / sqrt 2) / 2 in fp32 */
+
 /* cc_vit_model.row_policy / cc_text_model.row_policy: compute rows whose values nothing downstream reads, exactly as the
  * reference does (bench.py and the tests time / compare both forms; results agree bit for bit for the text rows and to the
  * rounding of the fp16 intermediates for the last block). */
@@ -543,6 +552,7 @@ typedef struct cc_vit_model {
      * stride (1, p, p) and zero padding 1 along t - frame t of a clip sees frames t-1, t, t+1 of the SAME clip.
      * conv2_weight_f16 [W, 3*3*p*p] = the Conv3d weight [W, 3(c), 3(t), p, p] flattened; NULL = '2d' (conv1). */
     const void* conv2_weight_f16;
+    int32_t activation;                   /* CC_ACT_*; 0 = QuickGELU */
 } cc_vit_model;
 
 /* Frame input descriptor for the *_frames entry points.  The reference's evaluation
@@ -590,6 +600,7 @@ typedef struct cc_text_model {
     const float* text_projection;         /* [W, embed_dim]    */
     const cc_block_weights* blocks;       /* HOST array [layers] */
     int32_t row_policy;                   /* CC_ROWS_* bits; 0 = shipped policy */
+    int32_t activation;                   /* CC_ACT_*; 0 = QuickGELU */
 } cc_text_model;
 
 size_t cc_text_workspace_bytes(const cc_text_model* m, int32_t Bt, int32_t Lt);
@@ -850,6 +861,8 @@ int cc_group_max_rows_f32(const float* sim, int32_t rows, int32_t cols, int64_t 
  *                               x_stride >= W, x_stride % 4 == 0.
  *   cc_quick_gelu_backward_f16  du_pre = du * d/dx [x sigmoid(1.702 x)] at x = u_pre (fp16, the c_fc output before the
  *                               activation, clip.py:192-194); n % 4 == 0
+ *   cc_gelu_f16 / cc_gelu_backward_f16   the same pair for the exact GELU x Phi(x) (CC_ACT_GELU): Phi(x) = erfc(-x / sqrt 2) / 2,
+ *                               d/dx = Phi(x) + x exp(-x^2 / 2) / sqrt(2 pi)
  *   cc_attention_backward_f16   qkv [nseq*L, 3W] fp16 (as cc_attention_f16), d_out [nseq*L, W] fp32 -> d_qkv [nseq*L, 3W] fp32
  *                               (softmax(q k^T / 8 + mask) v per 64-wide head); fp16 MFMA operands (dO and dS scaled by
  *                               powers of two chosen on the device), fp32 accumulators.  L <= 64: one launch, a workgroup
@@ -872,6 +885,8 @@ int cc_layernorm_backward_f32(const float* x, int64_t x_stride, const float* gam
                               void* ws, size_t ws_bytes, void* stream);
 int cc_quick_gelu_f16(const void* in_f16, void* out_f16, int64_t n, void* stream);     /* QuickGELU on fp16 (training forward) */
 int cc_quick_gelu_backward_f16(const void* u_pre_f16, const float* du, float* du_pre, int64_t n, float* out_amax, void* stream);
+int cc_gelu_f16(const void* in_f16, void* out_f16, int64_t n, void* stream);           /* exact GELU on fp16 (training forward) */
+int cc_gelu_backward_f16(const void* u_pre_f16, const float* du, float* du_pre, int64_t n, float* out_amax, void* stream);
 size_t cc_attention_backward_workspace_bytes(int32_t nseq, int32_t L, int32_t heads);    /* 0 for L <= 64 (ws may be null) */
 int cc_attention_backward_f16(const void* qkv_f16, const float* d_out, float* d_qkv, int32_t nseq, int32_t L,
                               int32_t heads, int32_t W, int32_t causal, float* out_amax, void* ws, size_t ws_bytes,
