@@ -14,6 +14,20 @@
 
 __host__ __device__ static inline size_t cc_align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Hands out consecutive 256-byte aligned pieces of a caller-owned workspace (host only).  With a null base it only counts:
+// `off` is then the size the workspace needs, which is how every *_workspace_bytes query is answered.
+struct Carver {
+    char* base;
+    size_t off;
+    explicit Carver(void* b, size_t start = 0) : base(static_cast<char*>(b)), off(start) {}
+    template <typename T>
+    T* take(size_t count) {
+        T* ptr = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += cc_align_up(count * sizeof(T), 256);
+        return ptr;
+    }
+};
+
 // Opt a kernel into more than the default 64 KB of dynamic LDS; nothing to do at or below it.  Called before every such
 // launch: the attribute is per device, the call is cheap and idempotent - a process-wide "configured" flag would leave every
 // device but the first one at the 64 KB default.

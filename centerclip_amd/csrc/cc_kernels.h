@@ -166,18 +166,36 @@ int cc_launch_head_project2(const HeadArgs& a0, const HeadArgs* a1, hipStream_t 
 int cc_launch_head_project(const float* h, int row_mul, const int* row_idx, const float* gamma, const float* beta,
                            const float* proj, float* out, int R, int W, int E, hipStream_t st);
 
-// cluster.hip: cc_token_gather_f32 / cc_token_cluster_variant_f32 with by-products for the next block's folded ln_1
-// (row_h16 [rows][W] fp16 copy of the dense output rows, row_stats [rows][2] their (sum, sum of squares))
+// cluster.hip: the token ops of a clustered block.  What cc_token_gather_f32 / cc_token_cluster_variant_f32 do, as requests,
+// plus the by-products the next block's folded ln_1 wants from the same launch.
 #define CC_INTERNAL __attribute__((visibility("hidden")))      /* shared between translation units, not exported */
-extern "C" {
-CC_INTERNAL int cc_token_gather_rows(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
-                         int32_t T_new, int32_t n, int32_t W, int32_t K, const int64_t* medoids, float* out,
-                         int64_t out_tok_stride, int64_t out_frame_stride, _Float16* row_h16, float* row_stats,
-                         float* row_shift, void* stream);
-CC_INTERNAL int cc_token_cluster_variant_rows(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
-                                  int32_t T_new, int32_t n, int32_t W, int32_t K, int32_t metric, float norm_p,
-                                  float threshold, int32_t iter_limit, int32_t split_size, int32_t pre_norm,
-                                  const cc_cluster_variant* var, float* out, int64_t out_tok_stride,
-                                  int64_t out_frame_stride, int64_t* medoids, int64_t* assign, int32_t* iters, void* ws,
-                                  size_t ws_bytes, _Float16* row_h16, float* row_stats, float* row_shift, void* stream);
-}
+struct TokenIn { const float* p; int64_t tok, frame; };         // token l of frame f: p + l * tok + f * frame (floats)
+struct TokenOut { float* p; int64_t tok, frame; };
+// B videos of T frames, each frame CLS + n tokens of W floats -> T_new segments per video of CLS + K tokens ('pooling': K = n)
+struct TokenGeom { int B, T, T_new, n, W, K; };
+struct TokenRows {               // what every token op works over
+    TokenIn in;
+    TokenOut out;
+    TokenGeom g;
+    // optional, all three null or the output dense ([segment][1 + K][W]): the fp16 copy of the output rows minus their mean
+    // [rows][W], its (sum, sum of squares) [rows][2] and the means [rows]
+    _Float16* h16;
+    float* stats;
+    float* shift;
+};
+struct TokenGatherReq : TokenRows {
+    const int64_t* medoids;      // [T_new * B, K]
+};
+struct TokenClusterReq : TokenRows {
+    int metric;                  // the k-medoids parameters of cc_token_cluster_variant_f32
+    float norm_p, threshold;
+    int iter_limit, split_size, pre_norm;
+    const cc_cluster_variant* var;
+    int64_t* medoids;            // optional outputs
+    int64_t* assign;
+    int32_t* iters;
+    void* ws;
+    size_t ws_bytes;
+};
+CC_INTERNAL int cc_token_gather_rows(const TokenGatherReq& r, hipStream_t st);
+CC_INTERNAL int cc_token_cluster_variant_rows(const TokenClusterReq& r, hipStream_t st);

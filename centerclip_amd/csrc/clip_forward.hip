@@ -13,18 +13,6 @@
 
 namespace {
 
-struct Carver {
-    char* base;
-    size_t off = 0;
-    explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-    template <typename T>
-    T* take(size_t count) {
-        T* ptr = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += cc_align_up(count * sizeof(T), 256);
-        return ptr;
-    }
-};
-
 struct TowerActs {         // one tower's activations
     float* h;              // residual stream (frame-major)
     _Float16* h16;         // fp16 copy of the residual stream (GEMM A operand; LayerNorm is folded into the GEMM)
@@ -364,18 +352,20 @@ int token_op(const VisualReq& r, const VitWs& v, const ClusterStep& s, const int
         return rc;
     }
     if (s.kind == CK_POOLING && K != tokens) return CC_ERR_INVALID;
-    auto cluster = [&](const cc_cluster_variant* cvar, int64_t* med, _Float16* h16, float* st0, float* sh0) {
-        return cc_token_cluster_variant_rows(cv.a.h, W, (int64_t)(tokens + 1) * W, B, frames, Tn, tokens, W, K, vm->cluster_metric,
-                                             vm->cluster_norm_p, vm->cluster_threshold, vm->cluster_iter_limit,
-                                             vm->cluster_split_size, vm->cluster_pre_norm, cvar, spare, W, (int64_t)(K + 1) * W,
-                                             med, nullptr, nullptr, v.cluster, v.cluster_bytes, h16, st0, sh0, st);
-    };
+    TokenClusterReq rq{};
+    rq.in = TokenIn{cv.a.h, W, (int64_t)(tokens + 1) * W};
+    rq.out = TokenOut{spare, W, (int64_t)(K + 1) * W};
+    rq.g = TokenGeom{B, frames, Tn, tokens, W, K};
+    rq.h16 = cv.a.h16; rq.stats = cv.a.st0; rq.shift = cv.a.sh0;
+    rq.metric = vm->cluster_metric; rq.norm_p = vm->cluster_norm_p; rq.threshold = vm->cluster_threshold;
+    rq.iter_limit = vm->cluster_iter_limit; rq.split_size = vm->cluster_split_size; rq.pre_norm = vm->cluster_pre_norm;
+    rq.var = var; rq.medoids = medoids_out;
+    rq.ws = v.cluster; rq.ws_bytes = v.cluster_bytes;
     if (!forced)
-        rc = cluster(var, medoids_out, cv.a.h16, cv.a.st0, cv.a.sh0);
+        rc = cc_token_cluster_variant_rows(rq, st);
     else if (var->algorithm == CC_CLUSTER_KMEDOIDS && var->aggregation == CC_AGGREGATE_MEDOID && !var->cluster_embed &&
              !var->cls_multiplier)
-        rc = cc_token_gather_rows(cv.a.h, W, (int64_t)(tokens + 1) * W, B, frames, Tn, tokens, W, K, forced, spare, W,
-                                  (int64_t)(K + 1) * W, cv.a.h16, cv.a.st0, cv.a.sh0, st);
+        rc = cc_token_gather_rows(TokenGatherReq{rq, forced}, st);
     else
         rc = CC_ERR_UNSUPPORTED;
     if (rc) return rc;
@@ -385,7 +375,9 @@ int token_op(const VisualReq& r, const VitWs& v, const ClusterStep& s, const int
         if (K != tokens) return CC_ERR_INVALID;                 // cluster.py:229
         cc_cluster_variant pool{};
         pool.algorithm = CC_CLUSTER_POOLING;
-        rc = cluster(&pool, nullptr, nullptr, nullptr, nullptr);
+        rq.var = &pool; rq.medoids = nullptr;
+        rq.h16 = nullptr; rq.stats = nullptr; rq.shift = nullptr;
+        rc = cc_token_cluster_variant_rows(rq, st);
         if (rc) return rc;
     }
     std::swap(cv.a.h, spare);

@@ -600,7 +600,7 @@ __device__ void reduce_row_wave(const GatherDesc& g, int row, int lane, const in
 
 // One-iteration-per-launch form (a k-medoids `threshold` above CC_KMEDOIDS_MAX_THRESHOLD: the reference's chunk-mean stop test,
 // fast_kmeans.py:85-88, couples the problems of a split chunk, so the chunk is stepped in lockstep from the host side - see
-// batch_kmedoids_impl): start from given medoids instead of the KKZ init, pass through untouched once the chunk is done.
+// batch_kmedoids): start from given medoids instead of the KKZ init, pass through untouched once the chunk is done.
 struct SelStep {
     const long long* init;       // [P, K] medoids to start from (null: KKZ init)
     const int* done;             // [chunks] != 0: the chunk has passed the stop test - copy init to the output and leave
@@ -1409,216 +1409,7 @@ __global__ __launch_bounds__(256) void reduce_tokens_kernel(GatherDesc gd) {
     reduce_row_wave<LEFT>(gd, row, threadIdx.x & 63, nullptr);
 }
 
-// ============================================================================ host side
-static GatherDesc gather_desc(const float* x, int64_t in_tok, int64_t in_frame, int B, int T, int T_new, int n, int W, int K,
-                              int mode, const long long* medoids, int med_stride, const long long* assign,
-                              const float* cluster_embed, const float* cls_mult, float* out, int64_t out_tok,
-                              int64_t out_frame, _Float16* h16, float* stats, float* shift) {
-    GatherDesc g{};
-    g.x = x; g.in_tok = in_tok; g.in_frame = in_frame;
-    g.B = B; g.T = T; g.T_new = T_new; g.n = n; g.W = W; g.K = K; g.mode = mode;
-    g.medoids = medoids; g.med_stride = med_stride; g.assign = assign;
-    g.cluster_embed = cluster_embed; g.cls_mult = cls_mult;
-    g.out = out; g.out_tok = out_tok; g.out_frame = out_frame;
-    g.h16 = h16; g.stats = stats; g.shift = shift;
-    return g;
-}
-
-// K3 as a launch of its own (one wave per output row)
-static void launch_reduce_tokens(hipStream_t st, const float* x, int64_t in_tok, int64_t in_frame, int B, int T, int T_new,
-                                 int n, int W, int K, int mode, const long long* medoids, int med_stride,
-                                 const long long* assign, const float* cluster_embed, const float* cls_mult, float* out,
-                                 int64_t out_tok, int64_t out_frame, _Float16* h16, float* stats, float* shift) {
-    const GatherDesc g = gather_desc(x, in_tok, in_frame, B, T, T_new, n, W, K, mode, medoids, med_stride, assign,
-                                     cluster_embed, cls_mult, out, out_tok, out_frame, h16, stats, shift);
-    const int rows = B * T_new * ((mode == 2) ? 1 + n : 1 + K);
-    if (W & 31) hipLaunchKernelGGL(reduce_tokens_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, g);
-    else hipLaunchKernelGGL(reduce_tokens_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, g);
-}
-
 namespace {
-
-struct ClusterWs {
-    int* tilemax;
-    int slots_pp;
-    int* chunkmax;
-    float* sqn;
-    float* nrm;
-    float* inv;
-    float* draw;
-    float* xn;
-    long long* med;
-    long long* asg;
-    long long* med2;     // second medoid buffer + per-chunk stop flags of the stepped (loose threshold) selection
-    int* done;
-    size_t total;
-};
-
-// extra scratch of the spectral selection: L_sym [P,N,N], the eigensolver's global copy (N > 201), Q [P,N,K4], and the
-// k-medoids scratch for P problems of N K4-wide rows (pre-normalised)
-struct SpectralWs {
-    float* lap;
-    float* q;
-    int k4;
-    void* eig;
-    size_t eig_bytes;
-    void* km;
-    size_t km_bytes;
-    size_t total;
-};
-ClusterWs carve(void* ws, int P, int N, int W, int pre_norm, int K_for_med);
-extern "C" size_t cc_spectral_embedding_workspace_bytes(int32_t P, int32_t N);
-SpectralWs carve_spectral(void* ws, int P, int N, int K) {
-    SpectralWs s{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* ptr = ws ? static_cast<char*>(ws) + off : nullptr;
-        off += cc_align_up(bytes, 256);
-        return ptr;
-    };
-    s.k4 = (K + 3) / 4 * 4;
-    s.lap = static_cast<float*>(take((size_t)P * N * N * sizeof(float)));
-    s.q = static_cast<float*>(take((size_t)P * N * s.k4 * sizeof(float)));
-    s.eig_bytes = cc_spectral_embedding_workspace_bytes(P, N);
-    s.eig = take(s.eig_bytes);
-    s.km_bytes = carve(nullptr, P, N, s.k4, 1, N).total;
-    s.km = take(s.km_bytes);
-    s.total = off;
-    return s;
-}
-
-ClusterWs carve(void* ws, int P, int N, int W, int pre_norm, int K_for_med) {
-    ClusterWs c{};
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        void* ptr = ws ? static_cast<char*>(ws) + off : nullptr;
-        off += cc_align_up(bytes, 256);
-        return ptr;
-    };
-    {   // per-(problem, tile, wave) maxima of the distance kernel + the reduced per-chunk values (stand-alone path)
-        const size_t nt = (size_t)(N + GT - 1) / GT;
-        c.slots_pp = (int)(nt * (nt + 1) / 2 * 4);
-        c.tilemax = static_cast<int*>(take((size_t)P * c.slots_pp * 4));
-        c.chunkmax = static_cast<int*>(take((size_t)P * 4));
-    }
-    c.sqn = static_cast<float*>(take((size_t)P * N * 4));
-    c.nrm = static_cast<float*>(take((size_t)P * N * 4));
-    c.inv = static_cast<float*>(take((size_t)P * N * 4));
-    c.draw = static_cast<float*>(take((size_t)P * N * N * 4));
-    c.med = static_cast<long long*>(take((size_t)P * (size_t)K_for_med * 8));
-    c.asg = static_cast<long long*>(take((size_t)P * N * 8));
-    c.med2 = static_cast<long long*>(take((size_t)P * (size_t)K_for_med * 8));
-    c.done = static_cast<int*>(take((size_t)P * 4));
-    c.xn = pre_norm ? static_cast<float*>(take((size_t)P * N * W * 4)) : nullptr;
-    c.total = off;
-    return c;
-}
-
-bool layout_ok(const cc_token_layout* l, int W) {
-    if (!l || l->B <= 0 || l->S <= 0 || l->fd <= 0 || l->n <= 0) return false;
-    if (W <= 0 || (W & 3)) return false;
-    return !((l->stride_b | l->stride_s | l->stride_f | l->stride_i) & 3);
-}
-
-cc_token_layout contiguous_layout(int P, int N, int W) {
-    cc_token_layout l;
-    l.B = P; l.S = 1; l.fd = 1; l.n = N;
-    l.stride_b = (int64_t)N * W; l.stride_s = 0; l.stride_f = 0; l.stride_i = W;
-    return l;
-}
-
-// K0 (+ optional pre-norm copy) and K1: raw distances + chunk max in ws
-int run_distance(const float* x, cc_token_layout lay, int W, int metric, float p, int chunk, int pre_norm,
-                 const ClusterWs& c, hipStream_t st) {
-    const int P = lay.B * lay.S, N = lay.fd * lay.n;
-    const int nb = ((P + 7) / 8) * 8 * ((N + 3) / 4);                  // token_norm_kernel: problem p on XCD p % 8
-    if (pre_norm) {
-        hipLaunchKernelGGL(token_norm_kernel, dim3(nb), dim3(256), 0, st, x, lay, P, N, W, c.sqn, c.nrm, c.inv, c.xn,
-                           (int*)nullptr, 0);
-        x = c.xn;
-        lay = contiguous_layout(P, N, W);
-    }
-    // the Gram kernels produce the row norms themselves (of the pre-normalised copy when pre_norm made one above);
-    // the Minkowski kernels (no Gram) keep the separate norm pass
-    const bool own_norms = (metric == CC_METRIC_COSINE || p == 2.0f);
-    if (!own_norms) {
-        hipLaunchKernelGGL(token_norm_kernel, dim3(nb), dim3(256), 0, st, x, lay, P, N, W, c.sqn, c.nrm, c.inv,
-                           (float*)nullptr, (int*)nullptr, 0);
-        CC_LAUNCH_CHECK();
-    }
-    const int nt = (N + GT - 1) / GT;
-    dim3 grid((unsigned)(((P + 7) / 8) * 8 * (nt * (nt + 1) / 2)));       // 1-D: problem p on XCD p % 8
-    const size_t gram_smem = (size_t)2 * 2 * 2 * GT * GK * sizeof(_Float16) + 2 * GT * sizeof(float);   // 66,048 B
-    if (metric == CC_METRIC_COSINE) {
-        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_COSINE>), gram_smem) != CC_OK) return CC_ERR_HIP;
-        hipLaunchKernelGGL(gram_dist_kernel<CC_METRIC_COSINE>, grid, dim3(256), gram_smem, st, x, lay, N, W, c.sqn, c.nrm,
-                           c.inv, own_norms ? 1 : 0, c.draw, c.tilemax, chunk, nt, P);
-    } else if (p == 2.0f) {
-        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_EUCLIDEAN>), gram_smem) != CC_OK) return CC_ERR_HIP;
-        hipLaunchKernelGGL(gram_dist_kernel<CC_METRIC_EUCLIDEAN>, grid, dim3(256), gram_smem, st, x, lay, N, W, c.sqn,
-                           c.nrm, c.inv, own_norms ? 1 : 0, c.draw, c.tilemax, chunk, nt, P);
-    } else if (p == 1.0f) {
-        hipLaunchKernelGGL(lp_dist_kernel<1>, grid, dim3(256), 0, st, x, lay, N, W, p, c.draw, c.tilemax, chunk, nt, P);
-    } else if (p > 3.0e38f) {
-        hipLaunchKernelGGL(lp_dist_kernel<2>, grid, dim3(256), 0, st, x, lay, N, W, p, c.draw, c.tilemax, chunk, nt, P);
-    } else {
-        hipLaunchKernelGGL(lp_dist_kernel<0>, grid, dim3(256), 0, st, x, lay, N, W, p, c.draw, c.tilemax, chunk, nt, P);
-    }
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-}
-
-// raw squared-L2 distances (spectral affinity): the Gram kernel with its own row norms, no shift
-int run_distance_sq(const float* x, cc_token_layout lay, int W, const ClusterWs& c, hipStream_t st) {
-    const int P = lay.B * lay.S, N = lay.fd * lay.n;
-    const int nt = (N + GT - 1) / GT;
-    dim3 grid((unsigned)(((P + 7) / 8) * 8 * (nt * (nt + 1) / 2)));
-    const size_t gram_smem = (size_t)2 * 2 * 2 * GT * GK * sizeof(_Float16) + 2 * GT * sizeof(float);
-    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(gram_dist_kernel<CC_METRIC_SQL2>), gram_smem) != CC_OK) return CC_ERR_HIP;
-    hipLaunchKernelGGL(gram_dist_kernel<CC_METRIC_SQL2>, grid, dim3(256), gram_smem, st, x, lay, N, W, c.sqn, c.nrm, c.inv,
-                       1, c.draw, c.tilemax, P, nt, P);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-}
-
-int run_select(const float* dist_in, float* dist_rw, const float* norms, const int* chunkmax, int slots_pp, int chunk,
-               int apply_shift, int P, int N, int K, int iter_limit, int id_sort, long long* med, long long* assign,
-               int* iters, hipStream_t st, const GatherDesc* gather = nullptr, const SelStep* step = nullptr) {
-    GatherDesc gd{};
-    if (gather) gd = *gather;
-    SelStep ss{};
-    if (step) ss = *step;
-    const size_t lds_limit = 160 * 1024;
-    const bool in_lds = sel_smem_bytes(N, K, true) <= lds_limit;
-    const size_t smem = sel_smem_bytes(N, K, in_lds);
-    if (smem > lds_limit || K > SEL_THREADS) return CC_ERR_UNSUPPORTED;   // (per-cluster masks K x ceil(N / 64) x 8 bytes in LDS)
-    const int ne = (N + 63) / 64;
-#define SEL_LAUNCH(INLDS, NEV)                                                                                         \
-    do {                                                                                                               \
-        auto kern = kmedoids_select_kernel<INLDS, NEV>;                                                                \
-        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kern), smem) != CC_OK) return CC_ERR_HIP;               \
-        hipLaunchKernelGGL(kern, dim3(P), dim3(SEL_THREADS), smem, st, dist_in, dist_rw, norms, chunkmax, slots_pp, chunk, apply_shift, \
-                           N, K, iter_limit, id_sort, med, assign, iters, gd, ss);                                    \
-    } while (0)
-    if (in_lds) {
-        if (ne <= 1) SEL_LAUNCH(true, 1);
-        else if (ne == 2) SEL_LAUNCH(true, 2);
-        else if (ne == 3) SEL_LAUNCH(true, 3);
-        else SEL_LAUNCH(true, 4);
-    } else {
-        if (ne <= 4) SEL_LAUNCH(false, 4);
-        else if (ne <= 7) SEL_LAUNCH(false, 7);
-        else if (ne <= 10) SEL_LAUNCH(false, 10);
-        else if (ne <= 16) SEL_LAUNCH(false, 16);
-        else if (ne <= 25) SEL_LAUNCH(false, 25);           // N <= 1,600: ViT-B/16, 8 frames per segment (1,568)
-        else if (ne <= 40) SEL_LAUNCH(false, 40);
-        else if (ne <= 64) SEL_LAUNCH(false, 64);
-        else SEL_LAUNCH(false, SEL_MAX_E);
-    }
-#undef SEL_LAUNCH
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-}
 
 // ---- the reference's stop test, literally (fast_kmeans.py:85-88), for thresholds the fixed-point test cannot stand in for.
 // ATen's CPU sum of n fp32 terms along a contiguous dimension (SumKernel.cpp cascade_sum; the same tree as sum_rank above,
@@ -1693,7 +1484,247 @@ __global__ __launch_bounds__(256) void center_shift_kernel(const float* __restri
     }
 }
 
-bool p_supported(int metric, float p) { return metric == CC_METRIC_COSINE || (p > 0.0f); }
+}  // namespace
+
+// ============================================================================ host side
+namespace {
+
+// ---- a token op's geometry and views (TokenIn / TokenOut / TokenGeom / TokenRows: cc_kernels.h)
+// Positive sizes, whole segments, float4 rows; `in` / `out`: the views the op addresses tokens through (null: not checked).
+bool token_geom_ok(const TokenGeom& g, const TokenIn* in = nullptr, const TokenOut* out = nullptr) {
+    if (g.B <= 0 || g.T <= 0 || g.T_new <= 0 || g.n <= 0 || g.W <= 0 || g.K <= 0) return false;
+    if ((g.T % g.T_new) || (g.W & 3)) return false;
+    if (in && (!in->p || ((in->tok | in->frame) & 3))) return false;
+    return !out || (out->p && !((out->tok | out->frame) & 3));
+}
+// ... and the by-products only next to a dense output ([segment][1 + K][W]) and with their statistics
+bool token_rows_ok(const TokenRows& r) {
+    if (!token_geom_ok(r.g, &r.in, &r.out)) return false;
+    return !r.h16 || (r.stats && r.out.tok == r.g.W && r.out.frame == (int64_t)(1 + r.g.K) * r.g.W);
+}
+// the fd * n tokens of every (video, segment) as one problem of the distance / selection kernels; token 0 = in.p
+cc_token_layout segment_layout(const TokenIn& in, const TokenGeom& g) {
+    const int fd = g.T / g.T_new;
+    return cc_token_layout{g.B, g.T_new, fd, g.n, (int64_t)g.T * in.frame, (int64_t)fd * in.frame, in.frame, in.tok};
+}
+cc_token_layout contiguous_layout(int P, int N, int W) { return cc_token_layout{P, 1, 1, N, (int64_t)N * W, 0, 0, W}; }
+bool layout_ok(const cc_token_layout* l, int W) {
+    if (!l || l->B <= 0 || l->S <= 0 || l->fd <= 0 || l->n <= 0) return false;
+    if (W <= 0 || (W & 3)) return false;
+    return !((l->stride_b | l->stride_s | l->stride_f | l->stride_i) & 3);
+}
+
+// ---- K3's descriptor, one constructor per mode; cluster_embed / cls_mult are the variant's (gather_variant)
+GatherDesc gather_rows(const TokenRows& r, int mode) {
+    GatherDesc g{};
+    g.x = r.in.p; g.in_tok = r.in.tok; g.in_frame = r.in.frame;
+    g.B = r.g.B; g.T = r.g.T; g.T_new = r.g.T_new; g.n = r.g.n; g.W = r.g.W; g.K = r.g.K; g.mode = mode;
+    g.out = r.out.p; g.out_tok = r.out.tok; g.out_frame = r.out.frame;
+    g.h16 = r.h16; g.stats = r.stats; g.shift = r.shift;
+    return g;
+}
+GatherDesc gather_medoids(const TokenRows& r, const int64_t* ids, int id_stride) {     // id_stride 0: the same ids for every problem
+    GatherDesc g = gather_rows(r, 0);
+    g.medoids = reinterpret_cast<const long long*>(ids); g.med_stride = id_stride;
+    return g;
+}
+GatherDesc gather_means(const TokenRows& r, const int64_t* assign) {
+    GatherDesc g = gather_rows(r, 1);
+    g.assign = reinterpret_cast<const long long*>(assign);
+    return g;
+}
+GatherDesc gather_pooling(const TokenRows& r) { return gather_rows(r, 2); }             // (r.g.K = r.g.n)
+void gather_variant(GatherDesc& g, const cc_cluster_variant* var) {
+    if (!var) return;
+    g.cluster_embed = var->cluster_embed; g.cls_mult = var->cls_multiplier;
+}
+
+// K3 as a launch of its own (one wave per output row)
+int launch_reduce_tokens(hipStream_t st, const GatherDesc& g) {
+    const int rows = g.B * g.T_new * ((g.mode == 2) ? 1 + g.n : 1 + g.K);
+    if (g.W & 31) hipLaunchKernelGGL(reduce_tokens_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, st, g);
+    else hipLaunchKernelGGL(reduce_tokens_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, st, g);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+struct ClusterWs {
+    int* tilemax;
+    int slots_pp;
+    int* chunkmax;
+    float* sqn;
+    float* nrm;
+    float* inv;
+    float* draw;
+    float* xn;
+    long long* med;
+    long long* asg;
+    long long* med2;     // second medoid buffer + per-chunk stop flags of the stepped (loose threshold) selection
+    int* done;
+    size_t total;
+};
+
+// extra scratch of the spectral selection: L_sym [P,N,N], the eigensolver's global copy (N > 201), Q [P,N,K4], and the
+// k-medoids scratch for P problems of N K4-wide rows (pre-normalised)
+struct SpectralWs {
+    float* lap;
+    float* q;
+    int k4;
+    void* eig;
+    size_t eig_bytes;
+    void* km;
+    size_t km_bytes;
+    size_t total;
+};
+
+ClusterWs carve(void* ws, int P, int N, int W, int pre_norm) {
+    ClusterWs c{};
+    Carver cv(ws);
+    // per-(problem, tile, wave) maxima of the distance kernel + the reduced per-chunk values (stand-alone path)
+    const size_t nt = (size_t)(N + GT - 1) / GT;
+    c.slots_pp = (int)(nt * (nt + 1) / 2 * 4);
+    c.tilemax = cv.take<int>((size_t)P * c.slots_pp);
+    c.chunkmax = cv.take<int>(P);
+    c.sqn = cv.take<float>((size_t)P * N);
+    c.nrm = cv.take<float>((size_t)P * N);
+    c.inv = cv.take<float>((size_t)P * N);
+    c.draw = cv.take<float>((size_t)P * N * N);
+    c.med = cv.take<long long>((size_t)P * N);                   // (up to N medoids per problem)
+    c.asg = cv.take<long long>((size_t)P * N);
+    c.med2 = cv.take<long long>((size_t)P * N);
+    c.done = cv.take<int>(P);
+    c.xn = pre_norm ? cv.take<float>((size_t)P * N * W) : nullptr;
+    c.total = cv.off;
+    return c;
+}
+
+SpectralWs carve_spectral(void* ws, int P, int N, int K) {
+    SpectralWs s{};
+    Carver cv(ws);
+    s.k4 = (K + 3) / 4 * 4;
+    s.lap = cv.take<float>((size_t)P * N * N);
+    s.q = cv.take<float>((size_t)P * N * s.k4);
+    s.eig_bytes = cc_spectral_embedding_workspace_bytes(P, N);
+    s.eig = cv.take<char>(s.eig_bytes);
+    s.km_bytes = carve(nullptr, P, N, s.k4, 1).total;
+    s.km = cv.take<char>(s.km_bytes);
+    s.total = cv.off;
+    return s;
+}
+
+// ---- what the distance / selection kernels support, in the order the entries test it
+bool metric_ok(int metric) { return metric == CC_METRIC_EUCLIDEAN || metric == CC_METRIC_COSINE; }
+bool distance_ok(int metric, float p) { return metric_ok(metric) && (metric == CC_METRIC_COSINE || p > 0.0f); }
+bool selection_ok(int metric, float p, int N) { return distance_ok(metric, p) && N <= SEL_MAX_N; }
+
+// the tokens of P problems of N tokens each
+struct TokenSet {
+    const float* x; cc_token_layout lay; int W;
+    int P() const { return lay.B * lay.S; }
+    int N() const { return lay.fd * lay.n; }
+};
+
+// K0: sqn / inv in c, the row norms in nrm and, with xn, the normalised copy of the tokens
+void launch_token_norms(const TokenSet& t, const ClusterWs& c, float* nrm, float* xn, hipStream_t st) {
+    const int P = t.P(), N = t.N();
+    const dim3 grid(((P + 7) / 8) * 8 * ((N + 3) / 4));                // problem p on XCD p % 8
+    hipLaunchKernelGGL(token_norm_kernel, grid, dim3(256), 0, st, t.x, t.lay, P, N, t.W, c.sqn, nrm, c.inv, xn, (int*)nullptr, 0);
+}
+dim3 tile_grid(int P, int nt) { return dim3((unsigned)(((P + 7) / 8) * 8 * (nt * (nt + 1) / 2))); }   // 1-D: problem p on XCD p % 8
+
+// The Gram kernel with its own row norms: raw distances in c.draw, per-tile maxima in c.tilemax
+template <int METRIC>
+int launch_gram(const TokenSet& t, const ClusterWs& c, int chunk, hipStream_t st) {
+    const int P = t.P(), N = t.N(), nt = (N + GT - 1) / GT;
+    const size_t smem = (size_t)2 * 2 * 2 * GT * GK * sizeof(_Float16) + 2 * GT * sizeof(float);   // 66,048 B
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(gram_dist_kernel<METRIC>), smem) != CC_OK) return CC_ERR_HIP;
+    hipLaunchKernelGGL(gram_dist_kernel<METRIC>, tile_grid(P, nt), dim3(256), smem, st, t.x, t.lay, N, t.W, c.sqn, c.nrm, c.inv, 1,
+                       c.draw, c.tilemax, chunk, nt, P);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+// K0 (+ optional pre-norm copy) and K1: raw distances + chunk max in ws
+int run_distance(TokenSet t, int metric, float p, int chunk, int pre_norm, const ClusterWs& c, hipStream_t st) {
+    const int P = t.P(), N = t.N(), W = t.W;
+    if (pre_norm) {
+        launch_token_norms(t, c, c.nrm, c.xn, st);
+        t = TokenSet{c.xn, contiguous_layout(P, N, W), W};
+    }
+    // the Gram kernels produce the row norms themselves (of the pre-normalised copy when pre_norm made one above);
+    // the Minkowski kernels (no Gram) keep the separate norm pass
+    if (metric == CC_METRIC_COSINE) return launch_gram<CC_METRIC_COSINE>(t, c, chunk, st);
+    if (p == 2.0f) return launch_gram<CC_METRIC_EUCLIDEAN>(t, c, chunk, st);
+    launch_token_norms(t, c, c.nrm, nullptr, st);
+    CC_LAUNCH_CHECK();
+    const int nt = (N + GT - 1) / GT;
+    const auto lp = p == 1.0f ? lp_dist_kernel<1> : p > 3.0e38f ? lp_dist_kernel<2> : lp_dist_kernel<0>;
+    hipLaunchKernelGGL(lp, tile_grid(P, nt), dim3(256), 0, st, t.x, t.lay, N, W, p, c.draw, c.tilemax, chunk, nt, P);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+// raw squared-L2 distances (spectral affinity): the Gram kernel with its own row norms, no shift
+int run_distance_sq(const TokenSet& t, const ClusterWs& c, hipStream_t st) {
+    return launch_gram<CC_METRIC_SQL2>(t, c, t.P(), st);
+}
+
+struct SelectArgs {
+    const float* dist_in; float* dist_rw; const float* norms;    // the distances (dist_rw null: read only) and the row norms
+    const int* chunkmax; int slots_pp, chunk, apply_shift;        // the per-tile maxima the all-negative shift comes from
+    int P, N, K;
+    int iter_limit, id_sort;
+    long long* med; long long* assign; int* iters;                // outputs (assign / iters optional)
+    const GatherDesc* gather;                                     // optional: write the output rows in the kernel's tail
+    const SelStep* step;                                          // optional: one stepped launch of the loose-threshold loop
+};
+// a selection on the distances run_distance left in c, shifted per split chunk; the caller adds limits, outputs, gather, step
+SelectArgs select_from_ws(const ClusterWs& c, int split_size, int P, int N, int K) {
+    SelectArgs a{};
+    a.dist_in = c.draw; a.dist_rw = c.draw; a.norms = c.nrm;
+    a.chunkmax = c.tilemax; a.slots_pp = c.slots_pp; a.chunk = split_size; a.apply_shift = 1;
+    a.P = P; a.N = N; a.K = K;
+    return a;
+}
+
+int run_select(const SelectArgs& a, hipStream_t st) {
+    GatherDesc gd{};
+    if (a.gather) gd = *a.gather;
+    SelStep ss{};
+    if (a.step) ss = *a.step;
+    const int P = a.P, N = a.N, K = a.K;
+    const size_t lds_limit = 160 * 1024;
+    const bool in_lds = sel_smem_bytes(N, K, true) <= lds_limit;
+    const size_t smem = sel_smem_bytes(N, K, in_lds);
+    if (smem > lds_limit || K > SEL_THREADS) return CC_ERR_UNSUPPORTED;   // (per-cluster masks K x ceil(N / 64) x 8 bytes in LDS)
+    const int ne = (N + 63) / 64;
+#define SEL_LAUNCH(INLDS, NEV)                                                                                         \
+    do {                                                                                                               \
+        auto kern = kmedoids_select_kernel<INLDS, NEV>;                                                                \
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kern), smem) != CC_OK) return CC_ERR_HIP;               \
+        hipLaunchKernelGGL(kern, dim3(P), dim3(SEL_THREADS), smem, st, a.dist_in, a.dist_rw, a.norms, a.chunkmax,     \
+                           a.slots_pp, a.chunk, a.apply_shift, N, K, a.iter_limit, a.id_sort, a.med, a.assign, a.iters, \
+                           gd, ss);                                                                                    \
+    } while (0)
+    if (in_lds) {
+        if (ne <= 1) SEL_LAUNCH(true, 1);
+        else if (ne == 2) SEL_LAUNCH(true, 2);
+        else if (ne == 3) SEL_LAUNCH(true, 3);
+        else SEL_LAUNCH(true, 4);
+    } else {
+        if (ne <= 4) SEL_LAUNCH(false, 4);
+        else if (ne <= 7) SEL_LAUNCH(false, 7);
+        else if (ne <= 10) SEL_LAUNCH(false, 10);
+        else if (ne <= 16) SEL_LAUNCH(false, 16);
+        else if (ne <= 25) SEL_LAUNCH(false, 25);           // N <= 1,600: ViT-B/16, 8 frames per segment (1,568)
+        else if (ne <= 40) SEL_LAUNCH(false, 40);
+        else if (ne <= 64) SEL_LAUNCH(false, 64);
+        else SEL_LAUNCH(false, SEL_MAX_E);
+    }
+#undef SEL_LAUNCH
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
 
 }  // namespace
 
@@ -1715,17 +1746,16 @@ size_t cc_spectral_workspace_bytes(int32_t P, int32_t N, int32_t K) {
 
 size_t cc_cluster_workspace_bytes(int32_t P, int32_t N, int32_t W, int32_t pre_norm) {
     if (P <= 0 || N <= 0 || W <= 0) return 0;
-    return carve(nullptr, P, N, W, pre_norm, N).total;
+    return carve(nullptr, P, N, W, pre_norm).total;
 }
 
 int cc_token_norms_f32(const float* x, const cc_token_layout* lay, int32_t W, float* norms, void* ws,
                        size_t ws_bytes, void* stream) {
     if (!x || !norms || !layout_ok(lay, W)) return CC_ERR_INVALID;
     const int P = lay->B * lay->S, N = lay->fd * lay->n;
-    ClusterWs c = carve(ws, P, N, W, 0, N);
+    ClusterWs c = carve(ws, P, N, W, 0);
     if (!ws || ws_bytes < c.total) return CC_ERR_WORKSPACE;
-    hipLaunchKernelGGL(token_norm_kernel, dim3(((P + 7) / 8) * 8 * ((N + 3) / 4)), dim3(256), 0, static_cast<hipStream_t>(stream), x, *lay,
-                       P, N, W, c.sqn, norms, c.inv, (float*)nullptr, (int*)nullptr, 0);
+    launch_token_norms(TokenSet{x, *lay, W}, c, norms, nullptr, static_cast<hipStream_t>(stream));
     CC_LAUNCH_CHECK();
     return CC_OK;
 }
@@ -1734,16 +1764,15 @@ int cc_pairwise_distance_f32(const float* x, const cc_token_layout* lay, int32_t
                              int32_t all_negative, int32_t self_nearest, int32_t chunk, float* dist,
                              float* norms_out, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !dist || !layout_ok(lay, W)) return CC_ERR_INVALID;
-    if (metric != CC_METRIC_EUCLIDEAN && metric != CC_METRIC_COSINE) return CC_ERR_UNSUPPORTED;
-    if (!p_supported(metric, p)) return CC_ERR_UNSUPPORTED;
+    if (!distance_ok(metric, p)) return CC_ERR_UNSUPPORTED;
     const int P = lay->B * lay->S, N = lay->fd * lay->n;
     if (chunk <= 0) chunk = P;
-    ClusterWs c = carve(ws, P, N, W, 0, N);
+    ClusterWs c = carve(ws, P, N, W, 0);
     if (!ws || ws_bytes < c.total) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     c.draw = dist;
     if (norms_out) c.nrm = norms_out;
-    int rc = run_distance(x, *lay, W, metric, p, chunk, 0, c, st);
+    int rc = run_distance(TokenSet{x, *lay, W}, metric, p, chunk, 0, c, st);
     if (rc != CC_OK) return rc;
     if (all_negative || self_nearest) {
         const int64_t total = (int64_t)P * N * N;
@@ -1764,7 +1793,7 @@ int cc_pairwise_distance_cross_f32(const float* x1, const float* x2, int32_t P, 
                                    int32_t metric, float p, int32_t all_negative, int32_t self_nearest, float* dist,
                                    void* ws, size_t ws_bytes, void* stream) {
     if (!x1 || !x2 || !dist || P <= 0 || N1 <= 0 || N2 <= 0 || W <= 0) return CC_ERR_INVALID;
-    if (metric != CC_METRIC_EUCLIDEAN && metric != CC_METRIC_COSINE) return CC_ERR_UNSUPPORTED;
+    if (!metric_ok(metric)) return CC_ERR_UNSUPPORTED;
     if (!(p > 0.f)) return CC_ERR_INVALID;
     if (self_nearest && N2 > N1) return CC_ERR_INVALID;          // the reference indexes dis[..., j, j] for j < N2
     if (all_negative && (!ws || ws_bytes < sizeof(unsigned))) return CC_ERR_WORKSPACE;
@@ -1791,234 +1820,197 @@ int cc_kmedoids_from_dist_f32(const float* dist, const float* norms, int32_t P, 
     (void)ws; (void)ws_bytes;
     if (!dist || !norms || !medoids || P <= 0 || N <= 0 || K <= 0 || K > N || iter_limit < 0) return CC_ERR_INVALID;
     if (N > SEL_MAX_N) return CC_ERR_UNSUPPORTED;
-    return run_select(dist, nullptr, norms, nullptr, 0, 1, 0, P, N, K, iter_limit, id_sort,
-                      reinterpret_cast<long long*>(medoids), reinterpret_cast<long long*>(assign), iters,
-                      static_cast<hipStream_t>(stream));
+    SelectArgs sel{};                                             // distances as given: read only, no shift
+    sel.dist_in = dist; sel.norms = norms; sel.chunk = 1;
+    sel.P = P; sel.N = N; sel.K = K; sel.iter_limit = iter_limit; sel.id_sort = id_sort;
+    sel.med = reinterpret_cast<long long*>(medoids); sel.assign = reinterpret_cast<long long*>(assign); sel.iters = iters;
+    return run_select(sel, static_cast<hipStream_t>(stream));
 }
 
-static int batch_kmedoids_impl(const float* x, const cc_token_layout* lay, int32_t W, int32_t K, int32_t metric,
-                               float norm_p, float threshold, int32_t iter_limit, int32_t id_sort, int32_t split_size,
-                               int32_t pre_norm, int64_t* medoids, int64_t* assign, int32_t* iters, void* ws,
-                               size_t ws_bytes, void* stream, const GatherDesc* gather) {
+}  // extern "C"
+
+namespace {
+
+struct KmedoidsReq {             // cc_batch_kmedoids_f32's arguments
+    const float* x; const cc_token_layout* lay; int W, K, metric;
+    float norm_p, threshold;
+    int iter_limit, id_sort, split_size, pre_norm;
+    int64_t* medoids; int64_t* assign; int32_t* iters;
+    void* ws; size_t ws_bytes;
+};
+
+// gather (optional): the selection launch that leaves the final medoids also writes the output rows
+int batch_kmedoids(const KmedoidsReq& r, hipStream_t st, const GatherDesc* gather) {
     // Stop test: every problem iterates to its fixed point (medoids unchanged), which gives the final state of the
     // reference's chunk-mean test (fast_kmeans.py:85-88) whenever the threshold is below the distance between any two
     // distinct tokens (threshold <= CC_KMEDOIDS_MAX_THRESHOLD: one launch).  A looser threshold stops the reference earlier,
     // and at a point that depends on all problems of the split chunk: that case runs the literal loop - one iteration of
     // every problem per launch, the chunk's center_shift in ATen's own summation order after each, chunks that passed the
     // test passing through untouched (2 * iter_limit + 2 launches; not a hot path: no shipped script sets such a threshold).
-    const bool literal_stop = !(threshold <= CC_KMEDOIDS_MAX_THRESHOLD);
-    if (threshold != threshold) return CC_ERR_INVALID;
-    if (!x || !medoids || !layout_ok(lay, W)) return CC_ERR_INVALID;
-    const int P = lay->B * lay->S, N = lay->fd * lay->n;
+    const bool literal_stop = !(r.threshold <= CC_KMEDOIDS_MAX_THRESHOLD);
+    if (r.threshold != r.threshold) return CC_ERR_INVALID;
+    if (!r.x || !r.medoids || !layout_ok(r.lay, r.W)) return CC_ERR_INVALID;
+    const int P = r.lay->B * r.lay->S, N = r.lay->fd * r.lay->n, W = r.W, K = r.K, iter_limit = r.iter_limit;
     if (K <= 0 || K > N || iter_limit < 0) return CC_ERR_INVALID;
-    if (metric != CC_METRIC_EUCLIDEAN && metric != CC_METRIC_COSINE) return CC_ERR_UNSUPPORTED;
-    if (!p_supported(metric, norm_p)) return CC_ERR_UNSUPPORTED;
-    if (N > SEL_MAX_N) return CC_ERR_UNSUPPORTED;
-    if (split_size <= 0 || split_size > P) split_size = P;
-    ClusterWs c = carve(ws, P, N, W, pre_norm, N);
-    if (!ws || ws_bytes < c.total) return CC_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int rc = run_distance(x, *lay, W, metric, norm_p, split_size, pre_norm, c, st);
+    if (!selection_ok(r.metric, r.norm_p, N)) return CC_ERR_UNSUPPORTED;
+    const int split_size = (r.split_size <= 0 || r.split_size > P) ? P : r.split_size;
+    ClusterWs c = carve(r.ws, P, N, W, r.pre_norm);
+    if (!r.ws || r.ws_bytes < c.total) return CC_ERR_WORKSPACE;
+    int rc = run_distance(TokenSet{r.x, *r.lay, W}, r.metric, r.norm_p, split_size, r.pre_norm, c, st);
     if (rc != CC_OK) return rc;
-    long long* med_out = reinterpret_cast<long long*>(medoids);
-    long long* asg_out = reinterpret_cast<long long*>(assign);
-    if (!literal_stop || iter_limit == 0)
-        return run_select(c.draw, c.draw, c.nrm, c.tilemax, c.slots_pp, split_size, 1, P, N, K, iter_limit, id_sort, med_out,
-                          asg_out, iters, st, gather);
+    long long* med_out = reinterpret_cast<long long*>(r.medoids);
+    long long* asg_out = reinterpret_cast<long long*>(r.assign);
+    SelectArgs sel = select_from_ws(c, split_size, P, N, K);
+    if (!literal_stop || iter_limit == 0) {
+        sel.iter_limit = iter_limit; sel.id_sort = r.id_sort;
+        sel.med = med_out; sel.assign = asg_out; sel.iters = r.iters; sel.gather = gather;
+        return run_select(sel, st);
+    }
     if (split_size > 1024 || W >= 8192 || K >= 8192) return CC_ERR_UNSUPPORTED;      // (center_shift_kernel's per-chunk table / tree depth)
-    const float* xs = pre_norm ? c.xn : x;                         // the tokens the reference's loop sees (fast_kmeans.py:21-22)
-    const cc_token_layout lays = pre_norm ? contiguous_layout(P, N, W) : *lay;
+    // the tokens the reference's loop sees (fast_kmeans.py:21-22)
+    const TokenSet ts = r.pre_norm ? TokenSet{c.xn, contiguous_layout(P, N, W), W} : TokenSet{r.x, *r.lay, W};
     const int chunks = (P + split_size - 1) / split_size;
     if (hipMemsetAsync(c.done, 0, (size_t)chunks * sizeof(int), st) != hipSuccess) return CC_ERR_HIP;
     long long* cur = c.med;                                        // medoids entering a step / leaving it
     long long* nxt = c.med2;
     // KKZ init only (iter_limit 0, no sort): cur = the initial medoids, iters = 0
-    rc = run_select(c.draw, c.draw, c.nrm, c.tilemax, c.slots_pp, split_size, 1, P, N, K, 0, 0, cur, nullptr, iters, st, nullptr);
+    sel.med = cur; sel.iters = r.iters;
+    rc = run_select(sel, st);
     if (rc != CC_OK) return rc;
     float* rows_ws = c.sqn;                                        // [P, N] floats >= [P, K]: free once the distances exist
+    SelStep stp{};                                                 // (outlives every use of sel.step)
+    sel.step = &stp;
     for (int it = 0; it < iter_limit; ++it) {
-        SelStep stp{cur, c.done, 1};
-        rc = run_select(c.draw, c.draw, c.nrm, c.tilemax, c.slots_pp, split_size, 1, P, N, K, 1, 0, nxt, asg_out, iters, st,
-                        nullptr, &stp);
+        stp = SelStep{cur, c.done, 1};
+        sel.iter_limit = 1; sel.med = nxt; sel.assign = asg_out;
+        rc = run_select(sel, st);
         if (rc != CC_OK) return rc;
-        hipLaunchKernelGGL(center_shift_kernel, dim3(chunks), dim3(256), 0, st, xs, lays, W, P, K, split_size, nxt, cur, threshold,
-                           c.done, rows_ws);
+        hipLaunchKernelGGL(center_shift_kernel, dim3(chunks), dim3(256), 0, st, ts.x, ts.lay, W, P, K, split_size, nxt, cur,
+                           r.threshold, c.done, rows_ws);
         CC_LAUNCH_CHECK();
         long long* t = cur; cur = nxt; nxt = t;
     }
-    if (id_sort || gather) {                                       // fast_kmeans.py:90-94 (+ the output rows)
-        SelStep stp{cur, nullptr, 0};
-        return run_select(c.draw, c.draw, c.nrm, c.tilemax, c.slots_pp, split_size, 1, P, N, K, 0, id_sort, med_out,
-                          id_sort ? asg_out : nullptr, nullptr, st, gather, &stp);
+    if (r.id_sort || gather) {                                     // fast_kmeans.py:90-94 (+ the output rows)
+        stp = SelStep{cur, nullptr, 0};
+        sel.iter_limit = 0; sel.id_sort = r.id_sort; sel.gather = gather;
+        sel.med = med_out; sel.assign = r.id_sort ? asg_out : nullptr; sel.iters = nullptr;
+        return run_select(sel, st);
     }
     if (hipMemcpyAsync(med_out, cur, (size_t)P * K * sizeof(long long), hipMemcpyDeviceToDevice, st) != hipSuccess) return CC_ERR_HIP;
     return CC_OK;
 }
 
+}  // namespace
+
+// The token ops as requests (cc_kernels.h): the public entries below plus the by-products the fused forward wants from the same
+// launch - h16 [rows][W] fp16 copy of the output rows and stats [rows][2] their (sum, sum of squares); output then dense.
+int cc_token_gather_rows(const TokenGatherReq& r, hipStream_t st) {
+    if (!r.medoids || !token_rows_ok(r)) return CC_ERR_INVALID;
+    return launch_reduce_tokens(st, gather_medoids(r, r.medoids, r.g.K));
+}
+
+int cc_token_cluster_variant_rows(const TokenClusterReq& rq, hipStream_t st) {
+    const cc_cluster_variant* var = rq.var;
+    if (!var) return CC_ERR_INVALID;
+    TokenRows r = rq;
+    const bool pooling = var->algorithm == CC_CLUSTER_POOLING;  // no selection: every token = mean over the segment's frames
+    if (pooling) r.g.K = r.g.n;
+    if (!token_rows_ok(r)) return CC_ERR_INVALID;
+    const TokenGeom& g = r.g;
+    if (pooling) return launch_reduce_tokens(st, gather_pooling(r));
+    if (var->algorithm == CC_CLUSTER_SPARSE_SAMPLING) {         // fixed ids shared by every problem, then gather + CLS mean
+        if (!var->fixed_ids) return CC_ERR_INVALID;
+        return launch_reduce_tokens(st, gather_medoids(r, var->fixed_ids, 0));
+    }
+    const bool spectral = var->algorithm == CC_CLUSTER_SPECTRAL;
+    if (var->algorithm != CC_CLUSTER_KMEDOIDS && !spectral) return CC_ERR_INVALID;
+    if (var->aggregation != CC_AGGREGATE_MEDOID && var->aggregation != CC_AGGREGATE_MEAN) return CC_ERR_INVALID;
+    const cc_token_layout lay = segment_layout(r.in, g);
+    const float* tokens = r.in.p + r.in.tok;                    // the segment's tokens behind its CLS
+    const int P = lay.B * lay.S, N = lay.fd * lay.n;
+    if (g.K > N) return CC_ERR_INVALID;
+    ClusterWs c = carve(rq.ws, P, N, g.W, rq.pre_norm);
+    if (!rq.ws || rq.ws_bytes < c.total) return CC_ERR_WORKSPACE;
+    int64_t* med = rq.medoids ? rq.medoids : reinterpret_cast<int64_t*>(c.med);
+    const bool mean = var->aggregation == CC_AGGREGATE_MEAN;
+    int64_t* asg = rq.assign ? rq.assign : (mean ? reinterpret_cast<int64_t*>(c.asg) : nullptr);
+    GatherDesc gd = gather_medoids(r, med, g.K);
+    gather_variant(gd, var);
+    KmedoidsReq kq{tokens, &lay, g.W, g.K, rq.metric, rq.norm_p, rq.threshold, rq.iter_limit, 1, rq.split_size, rq.pre_norm,
+                   med, asg, rq.iters, rq.ws, rq.ws_bytes};
+    int rc;
+    if (spectral) {
+        // graph Laplacian of the segment's tokens -> K trailing eigenvectors -> k-medoids on their normalised rows
+        // (spectral.py:42-73; a single chunk unless split_size > 1 and P > split_size, :64-72)
+        SpectralWs sw = carve_spectral(static_cast<char*>(rq.ws) + c.total, P, N, g.K);
+        if (rq.ws_bytes < c.total + sw.total) return CC_ERR_WORKSPACE;
+        if (!metric_ok(rq.metric)) return CC_ERR_INVALID;
+        rc = cc_spectral_graph_laplacian_f32(tokens, &lay, g.W, var->spectral_sigma, var->spectral_graph_mode,
+                                             var->spectral_knn_k, 0, var->spectral_graph, sw.lap, nullptr, nullptr, rq.ws,
+                                             c.total, st);
+        if (rc != CC_OK) return rc;
+        rc = cc_spectral_embedding_f32(sw.lap, P, N, g.K, var->spectral_correct_sign, sw.q, sw.k4, nullptr, nullptr, sw.eig,
+                                       sw.eig_bytes, st);
+        if (rc != CC_OK) return rc;
+        const cc_token_layout ql = contiguous_layout(P, N, sw.k4);
+        kq.x = sw.q; kq.lay = &ql; kq.W = sw.k4;
+        kq.split_size = (rq.split_size > 1 && P > rq.split_size) ? rq.split_size : P;
+        kq.pre_norm = 1;
+        if (!asg) kq.assign = reinterpret_cast<int64_t*>(c.asg);
+        kq.ws = sw.km; kq.ws_bytes = sw.km_bytes;
+        rc = batch_kmedoids(kq, st, nullptr);
+    } else {
+        // the shipped variant: the selection kernel writes the output rows itself (K3 folded into K2's tail)
+        const bool fold = !mean && (g.W & 31) == 0;
+        rc = batch_kmedoids(kq, st, fold ? &gd : nullptr);
+        if (rc == CC_OK && fold) return CC_OK;
+    }
+    if (rc != CC_OK) return rc;
+    gd.assign = reinterpret_cast<const long long*>(asg);         // the launch of its own carries the ids and the assignment:
+    gd.mode = mean ? 1 : 0;                                      // mode 0 reads the one, mode 1 the other
+    return launch_reduce_tokens(st, gd);
+}
+
+extern "C" {
+
 int cc_batch_kmedoids_f32(const float* x, const cc_token_layout* lay, int32_t W, int32_t K, int32_t metric,
                           float norm_p, float threshold, int32_t iter_limit, int32_t id_sort, int32_t split_size,
                           int32_t pre_norm, int64_t* medoids, int64_t* assign, int32_t* iters, void* ws,
                           size_t ws_bytes, void* stream) {
-    return batch_kmedoids_impl(x, lay, W, K, metric, norm_p, threshold, iter_limit, id_sort, split_size, pre_norm, medoids,
-                               assign, iters, ws, ws_bytes, stream, nullptr);
-}
-
-// *_rows: the public entry plus the by-products the fused forward wants from the same launch - row_h16 [rows][W] fp16
-// copy of the output rows and row_stats [rows][2] their (sum, sum of squares); output must be dense ([seg][1+K][W]).
-static bool rows_layout_ok(const _Float16* row_h16, const float* row_stats, int W, int Lout, int64_t out_tok, int64_t out_frame) {
-    return !row_h16 || (row_stats && out_tok == W && out_frame == (int64_t)Lout * W);
-}
-
-int cc_token_gather_rows(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
-                         int32_t T_new, int32_t n, int32_t W, int32_t K, const int64_t* medoids, float* out,
-                         int64_t out_tok_stride, int64_t out_frame_stride, _Float16* row_h16, float* row_stats,
-                         float* row_shift, void* stream) {
-    if (!x || !out || !medoids || B <= 0 || T <= 0 || T_new <= 0 || n <= 0 || W <= 0 || K <= 0) return CC_ERR_INVALID;
-    if (!rows_layout_ok(row_h16, row_stats, W, 1 + K, out_tok_stride, out_frame_stride)) return CC_ERR_INVALID;
-    if ((T % T_new) || (W & 3) || ((in_tok_stride | in_frame_stride | out_tok_stride | out_frame_stride) & 3))
-        return CC_ERR_INVALID;
-    launch_reduce_tokens( static_cast<hipStream_t>(stream), x,
-                       in_tok_stride, in_frame_stride, B, T, T_new, n, W, K, 0, reinterpret_cast<const long long*>(medoids), K,
-                       (const long long*)nullptr, (const float*)nullptr, (const float*)nullptr, out, out_tok_stride,
-                       out_frame_stride, row_h16, row_stats, row_shift);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+    const KmedoidsReq r{x, lay, W, K, metric, norm_p, threshold, iter_limit, id_sort, split_size, pre_norm, medoids, assign,
+                        iters, ws, ws_bytes};
+    return batch_kmedoids(r, static_cast<hipStream_t>(stream), nullptr);
 }
 
 int cc_token_gather_f32(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
                         int32_t T_new, int32_t n, int32_t W, int32_t K, const int64_t* medoids, float* out,
                         int64_t out_tok_stride, int64_t out_frame_stride, void* stream) {
-    return cc_token_gather_rows(x, in_tok_stride, in_frame_stride, B, T, T_new, n, W, K, medoids, out, out_tok_stride,
-                                out_frame_stride, nullptr, nullptr, nullptr, stream);
+    const TokenRows r{{x, in_tok_stride, in_frame_stride}, {out, out_tok_stride, out_frame_stride}, {B, T, T_new, n, W, K}};
+    return cc_token_gather_rows(TokenGatherReq{r, medoids}, static_cast<hipStream_t>(stream));
 }
 
 int cc_token_aggregate_f32(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
                            int32_t T_new, int32_t n, int32_t W, int32_t K, const int64_t* assign,
                            const cc_cluster_variant* var, float* out, int64_t out_tok_stride, int64_t out_frame_stride,
                            void* stream) {
-    if (!x || !out || !assign || B <= 0 || T <= 0 || T_new <= 0 || n <= 0 || W <= 0 || K <= 0) return CC_ERR_INVALID;
-    _Float16* const row_h16 = nullptr;
-    float* const row_stats = nullptr;
-    float* const row_shift = nullptr;
-    if ((T % T_new) || (W & 3) || ((in_tok_stride | in_frame_stride | out_tok_stride | out_frame_stride) & 3))
-        return CC_ERR_INVALID;
-    launch_reduce_tokens( static_cast<hipStream_t>(stream), x,
-                       in_tok_stride, in_frame_stride, B, T, T_new, n, W, K, 1, (const long long*)nullptr, 0,
-                       reinterpret_cast<const long long*>(assign), var ? var->cluster_embed : nullptr,
-                       var ? var->cls_multiplier : nullptr, out, out_tok_stride, out_frame_stride, row_h16, row_stats,
-                       row_shift);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+    const TokenRows r{{x, in_tok_stride, in_frame_stride}, {out, out_tok_stride, out_frame_stride}, {B, T, T_new, n, W, K}};
+    if (!assign || !token_rows_ok(r)) return CC_ERR_INVALID;
+    GatherDesc gd = gather_means(r, assign);
+    gather_variant(gd, var);
+    return launch_reduce_tokens(static_cast<hipStream_t>(stream), gd);
 }
 
 int cc_token_apply_selection_f32(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
                                  int32_t T_new, int32_t n, int32_t W, int32_t K, const cc_cluster_variant* var,
                                  const int64_t* medoids, const int64_t* assign, float* out, int64_t out_tok_stride,
                                  int64_t out_frame_stride, void* stream) {
-    if (!x || !out || B <= 0 || T <= 0 || T_new <= 0 || n <= 0 || W <= 0 || K <= 0) return CC_ERR_INVALID;
-    if ((T % T_new) || (W & 3) || ((in_tok_stride | in_frame_stride | out_tok_stride | out_frame_stride) & 3))
-        return CC_ERR_INVALID;
+    const TokenRows r{{x, in_tok_stride, in_frame_stride}, {out, out_tok_stride, out_frame_stride}, {B, T, T_new, n, W, K}};
+    if (!token_rows_ok(r)) return CC_ERR_INVALID;
     const bool mean = var && var->aggregation == CC_AGGREGATE_MEAN;
     if (mean ? !assign : !medoids) return CC_ERR_INVALID;
-    _Float16* const row_h16 = nullptr;
-    float* const row_stats = nullptr;
-    float* const row_shift = nullptr;
-    launch_reduce_tokens(
-                       static_cast<hipStream_t>(stream), x, in_tok_stride, in_frame_stride, B, T, T_new, n, W, K, mean ? 1 : 0,
-                       mean ? (const long long*)nullptr : reinterpret_cast<const long long*>(medoids), mean ? 0 : K,
-                       mean ? reinterpret_cast<const long long*>(assign) : (const long long*)nullptr,
-                       var ? var->cluster_embed : nullptr, var ? var->cls_multiplier : nullptr, out, out_tok_stride,
-                       out_frame_stride, row_h16, row_stats, row_shift);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-}
-
-int cc_token_cluster_variant_rows(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
-                                  int32_t T_new, int32_t n, int32_t W, int32_t K, int32_t metric, float norm_p,
-                                  float threshold, int32_t iter_limit, int32_t split_size, int32_t pre_norm,
-                                  const cc_cluster_variant* var, float* out, int64_t out_tok_stride,
-                                  int64_t out_frame_stride, int64_t* medoids, int64_t* assign, int32_t* iters, void* ws,
-                                  size_t ws_bytes, _Float16* row_h16, float* row_stats, float* row_shift, void* stream) {
-    if (!x || !out || !var || B <= 0 || T <= 0 || T_new <= 0 || n <= 0 || W <= 0) return CC_ERR_INVALID;
-    if (!rows_layout_ok(row_h16, row_stats, W, 1 + (var->algorithm == CC_CLUSTER_POOLING ? n : K), out_tok_stride,
-                        out_frame_stride))
-        return CC_ERR_INVALID;
-    if (T % T_new) return CC_ERR_INVALID;
-    if ((W & 3) || ((in_tok_stride | in_frame_stride | out_tok_stride | out_frame_stride) & 3)) return CC_ERR_INVALID;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int fd = T / T_new;
-    if (var->algorithm == CC_CLUSTER_POOLING) {                 // no selection: every token = mean over the segment's frames
-        launch_reduce_tokens( st, x, in_tok_stride, in_frame_stride,
-                           B, T, T_new, n, W, n, 2, (const long long*)nullptr, 0, (const long long*)nullptr,
-                           (const float*)nullptr, (const float*)nullptr, out, out_tok_stride, out_frame_stride, row_h16, row_stats,
-                           row_shift);
-        CC_LAUNCH_CHECK();
-        return CC_OK;
-    }
-    if (var->algorithm == CC_CLUSTER_SPARSE_SAMPLING) {         // fixed ids shared by every problem, then gather + CLS mean
-        if (!var->fixed_ids || K <= 0) return CC_ERR_INVALID;
-        launch_reduce_tokens( st, x, in_tok_stride, in_frame_stride,
-                           B, T, T_new, n, W, K, 0, reinterpret_cast<const long long*>(var->fixed_ids), 0,
-                           (const long long*)nullptr, (const float*)nullptr, (const float*)nullptr, out, out_tok_stride,
-                           out_frame_stride, row_h16, row_stats, row_shift);
-        CC_LAUNCH_CHECK();
-        return CC_OK;
-    }
-    const bool spectral = var->algorithm == CC_CLUSTER_SPECTRAL;
-    if ((var->algorithm != CC_CLUSTER_KMEDOIDS && !spectral) || K <= 0) return CC_ERR_INVALID;
-    if (var->aggregation != CC_AGGREGATE_MEDOID && var->aggregation != CC_AGGREGATE_MEAN) return CC_ERR_INVALID;
-    cc_token_layout lay;
-    lay.B = B; lay.S = T_new; lay.fd = fd; lay.n = n;
-    lay.stride_b = (int64_t)T * in_frame_stride;
-    lay.stride_s = (int64_t)fd * in_frame_stride;
-    lay.stride_f = in_frame_stride;
-    lay.stride_i = in_tok_stride;
-    const int P = B * T_new, N = fd * n;
-    if (K > N) return CC_ERR_INVALID;
-    ClusterWs c = carve(ws, P, N, W, pre_norm, N);
-    if (!ws || ws_bytes < c.total) return CC_ERR_WORKSPACE;
-    int64_t* med = medoids ? medoids : reinterpret_cast<int64_t*>(c.med);
-    const bool mean = var->aggregation == CC_AGGREGATE_MEAN;
-    int64_t* asg = assign ? assign : (mean ? reinterpret_cast<int64_t*>(c.asg) : nullptr);
-    int rc;
-    if (spectral) {
-        // graph Laplacian of the segment's tokens -> K trailing eigenvectors -> k-medoids on their normalised rows
-        // (spectral.py:42-73; a single chunk unless split_size > 1 and P > split_size, :64-72)
-        SpectralWs sw = carve_spectral(static_cast<char*>(ws) + c.total, P, N, K);
-        if (ws_bytes < c.total + sw.total) return CC_ERR_WORKSPACE;
-        if (metric != CC_METRIC_EUCLIDEAN && metric != CC_METRIC_COSINE) return CC_ERR_INVALID;
-        rc = cc_spectral_graph_laplacian_f32(x + in_tok_stride, &lay, W, var->spectral_sigma, var->spectral_graph_mode,
-                                             var->spectral_knn_k, 0, var->spectral_graph, sw.lap, nullptr, nullptr, ws,
-                                             c.total, stream);
-        if (rc != CC_OK) return rc;
-        rc = cc_spectral_embedding_f32(sw.lap, P, N, K, var->spectral_correct_sign, sw.q, sw.k4, nullptr, nullptr, sw.eig,
-                                       sw.eig_bytes, stream);
-        if (rc != CC_OK) return rc;
-        cc_token_layout ql;
-        ql.B = P; ql.S = 1; ql.fd = 1; ql.n = N;
-        ql.stride_b = (int64_t)N * sw.k4; ql.stride_s = 0; ql.stride_f = 0; ql.stride_i = sw.k4;
-        int64_t* asg_q = asg ? asg : reinterpret_cast<int64_t*>(c.asg);
-        rc = cc_batch_kmedoids_f32(sw.q, &ql, sw.k4, K, metric, norm_p, threshold, iter_limit, 1,
-                                   (split_size > 1 && P > split_size) ? split_size : P, 1, med, asg_q, iters, sw.km, sw.km_bytes,
-                                   stream);
-    } else {
-        // the shipped variant: the selection kernel writes the output rows itself (K3 folded into K2's tail)
-        const bool fold = !mean && (W & 31) == 0;
-        const GatherDesc gd = gather_desc(x, in_tok_stride, in_frame_stride, B, T, T_new, n, W, K, 0,
-                                          reinterpret_cast<const long long*>(med), K, (const long long*)nullptr,
-                                          var->cluster_embed, var->cls_multiplier, out, out_tok_stride, out_frame_stride,
-                                          row_h16, row_stats, row_shift);
-        rc = batch_kmedoids_impl(x + in_tok_stride, &lay, W, K, metric, norm_p, threshold, iter_limit, 1, split_size,
-                                 pre_norm, med, asg, iters, ws, ws_bytes, stream, fold ? &gd : nullptr);
-        if (rc == CC_OK && fold) return CC_OK;
-    }
-    if (rc != CC_OK) return rc;
-    launch_reduce_tokens( st, x, in_tok_stride, in_frame_stride, B,
-                       T, T_new, n, W, K, mean ? 1 : 0, reinterpret_cast<const long long*>(med), K,
-                       reinterpret_cast<const long long*>(asg), var->cluster_embed, var->cls_multiplier, out,
-                       out_tok_stride, out_frame_stride, row_h16, row_stats, row_shift);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+    GatherDesc gd = mean ? gather_means(r, assign) : gather_medoids(r, medoids, K);
+    gather_variant(gd, var);
+    return launch_reduce_tokens(static_cast<hipStream_t>(stream), gd);
 }
 
 int cc_token_cluster_variant_f32(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
@@ -2027,9 +2019,10 @@ int cc_token_cluster_variant_f32(const float* x, int64_t in_tok_stride, int64_t 
                                  const cc_cluster_variant* var, float* out, int64_t out_tok_stride,
                                  int64_t out_frame_stride, int64_t* medoids, int64_t* assign, int32_t* iters, void* ws,
                                  size_t ws_bytes, void* stream) {
-    return cc_token_cluster_variant_rows(x, in_tok_stride, in_frame_stride, B, T, T_new, n, W, K, metric, norm_p, threshold,
-                                         iter_limit, split_size, pre_norm, var, out, out_tok_stride, out_frame_stride,
-                                         medoids, assign, iters, ws, ws_bytes, nullptr, nullptr, nullptr, stream);
+    const TokenRows r{{x, in_tok_stride, in_frame_stride}, {out, out_tok_stride, out_frame_stride}, {B, T, T_new, n, W, K}};
+    const TokenClusterReq rq{r, metric, norm_p, threshold, iter_limit, split_size, pre_norm, var, medoids, assign, iters, ws,
+                             ws_bytes};
+    return cc_token_cluster_variant_rows(rq, static_cast<hipStream_t>(stream));
 }
 
 int cc_token_cluster_f32(const float* x, int64_t in_tok_stride, int64_t in_frame_stride, int32_t B, int32_t T,
@@ -2163,8 +2156,7 @@ extern "C" int cc_token_cluster_backward_f32(const float* grad_out, int64_t go_t
                                              int64_t gx_frame_stride, float* grad_cluster_embed, float* grad_cls_mult,
                                              void* stream) {
     (void)x_tok_stride;
-    if (!grad_out || !grad_x || !var || B <= 0 || T <= 0 || T_new <= 0 || n <= 0 || W <= 0 || K <= 0) return CC_ERR_INVALID;
-    if ((T % T_new) || (W & 3)) return CC_ERR_INVALID;
+    if (!grad_out || !grad_x || !var || !token_geom_ok(TokenGeom{B, T, T_new, n, W, K})) return CC_ERR_INVALID;
     const int fd = T / T_new, N = fd * n;
     int mode = 0, id_stride = K;
     const long long* ids = reinterpret_cast<const long long*>(medoids);
@@ -2192,12 +2184,12 @@ extern "C" int cc_token_cluster_backward_f32(const float* grad_out, int64_t go_t
     hipLaunchKernelGGL(token_grad_kernel, dim3((rows + 3) / 4), dim3(256), 0, st, grad_out, go_tok_stride, go_frame_stride, B,
                        T, T_new, n, W, K, mode, ids, id_stride, reinterpret_cast<const long long*>(assign),
                        mode == 2 ? nullptr : var->cls_multiplier, grad_x, gx_tok_stride, gx_frame_stride);
-    if (hipGetLastError() != hipSuccess) return CC_ERR_HIP;
+    CC_LAUNCH_CHECK();
     if (grad_cluster_embed || grad_cls_mult) {
         if (mode == 2) return CC_ERR_INVALID;
         hipLaunchKernelGGL(token_param_grad_kernel, dim3((K + T + 3) / 4), dim3(256), 0, st, grad_out, go_tok_stride,
                            go_frame_stride, x, x_frame_stride, B, T, T_new, W, K, grad_cluster_embed, grad_cls_mult);
-        if (hipGetLastError() != hipSuccess) return CC_ERR_HIP;
+        CC_LAUNCH_CHECK();
     }
     return CC_OK;
 }
@@ -2463,7 +2455,7 @@ int cc_spectral_graph_laplacian_f32(const float* x, const cc_token_layout* lay, 
     if (mode != CC_GRAPH_HEAT_KERNEL && mode != CC_GRAPH_KNN) return CC_ERR_UNSUPPORTED;
     if (mode == CC_GRAPH_KNN && (knn_k <= 0 || knn_k > lay->fd * lay->n)) return CC_ERR_INVALID;
     const int P = lay->B * lay->S, N = lay->fd * lay->n;
-    ClusterWs c = carve(ws, P, N, W, 0, N);
+    ClusterWs c = carve(ws, P, N, W, 0);
     if (!ws || ws_bytes < c.total) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     float* wbuf = affinity_out ? affinity_out : c.draw;
@@ -2471,7 +2463,7 @@ int cc_spectral_graph_laplacian_f32(const float* x, const cc_token_layout* lay, 
     ClusterWs g = c;
     g.draw = wbuf;
     g.sqn = c.nrm;                                              // keep the norm scratch apart from `deg`
-    int rc = run_distance_sq(x, *lay, W, g, st);
+    int rc = run_distance_sq(TokenSet{x, *lay, W}, g, st);
     if (rc != CC_OK) return rc;
     const bool knn = mode == CC_GRAPH_KNN;
     hipLaunchKernelGGL(heat_kernel_rows_kernel, dim3((P * N + 3) / 4), dim3(256), 0, st, wbuf, knn ? nullptr : graph, deg, P, N,

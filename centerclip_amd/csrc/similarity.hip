@@ -655,16 +655,12 @@ struct CtrWs {
 
 CtrWs ctr_carve(void* ws, int n, int Tn, int E) {
     CtrWs c{};
-    size_t off = 0;
-    auto take = [&](size_t floats) {
-        float* p = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + off) : nullptr;
-        off += cc_align_up(floats * sizeof(float), 256);
-        return p;
-    };
-    c.that = take((size_t)n * E); c.phat = take((size_t)n * E);
-    c.tn = take(n); c.pn = take(n); c.den = take(n); c.vn = take((size_t)n * Tn);
-    c.S = take((size_t)n * n); c.nce = take(2 * (size_t)n); c.G = take((size_t)n * n); c.dls = take(n);
-    c.total = off;
+    Carver cv(ws);
+    c.that = cv.take<float>((size_t)n * E); c.phat = cv.take<float>((size_t)n * E);
+    c.tn = cv.take<float>(n); c.pn = cv.take<float>(n); c.den = cv.take<float>(n); c.vn = cv.take<float>((size_t)n * Tn);
+    c.S = cv.take<float>((size_t)n * n); c.nce = cv.take<float>(2 * (size_t)n); c.G = cv.take<float>((size_t)n * n);
+    c.dls = cv.take<float>(n);
+    c.total = cv.off;
     return c;
 }
 
@@ -849,14 +845,9 @@ struct DslWs {
 
 DslWs dsl_carve(void* ws, size_t base, int n) {
     DslWs d{};
-    size_t off = base;
-    auto take = [&](size_t floats) {
-        float* p = ws ? reinterpret_cast<float*>(static_cast<char*>(ws) + off) : nullptr;
-        off += cc_align_up(floats * sizeof(float), 256);
-        return p;
-    };
-    d.cm = take(n); d.cs = take(n); d.D = take((size_t)n * n); d.t = take(n);
-    d.total = off;
+    Carver cv(ws, base);
+    d.cm = cv.take<float>(n); d.cs = cv.take<float>(n); d.D = cv.take<float>((size_t)n * n); d.t = cv.take<float>(n);
+    d.total = cv.off;
     return d;
 }
 

@@ -342,6 +342,41 @@ def _cluster_ws(lib, P, N, W, pre_norm, K, algorithm, device):
     return L.workspace(need, device)
 
 
+def _cluster_strides(shape, frame_major):
+    if frame_major:
+        BT, Lt, W = shape
+        return BT, Lt, W, W, Lt * W
+    Lt, BT, W = shape
+    return BT, Lt, W, BT * W, W
+
+
+def _token_cluster(x, frame_major, T, T_new, K, kmedoids, variant, spectral, *, want_medoids, want_assign):
+    """The one cc_token_cluster_variant_f32 call of token_cluster / token_cluster_train -> (out, medoids, assign).
+    kmedoids = (metric, norm_p, threshold, iter_limit, split_size, pre_norm); variant = (algorithm, aggregation,
+    cluster_embed, cls_mult, fixed_ids); spectral = the spectral_* arguments.  The selection outputs only exist for the
+    algorithms that select (0 k-medoids, 3 spectral) and are empty when not wanted."""
+    metric, norm_p, threshold, iter_limit, split_size, pre_norm = kmedoids
+    algorithm = variant[0]
+    BT, Lt, W, tok, frame = _cluster_strides(x.shape, frame_major)
+    B, n = BT // T, Lt - 1
+    oshape = (B * T_new, 1 + K, W) if frame_major else (1 + K, B * T_new, W)
+    out = _e(*oshape, like=x, dtype=torch.float32)
+    _, _, _, o_tok, o_frame = _cluster_strides(oshape, frame_major)
+    kmed = algorithm in (0, 3)
+    N = (T // T_new) * n
+    med = _e(B * T_new if (want_medoids and kmed) else 0, K, like=x, dtype=torch.long)
+    assign = _e(B * T_new if (want_assign and kmed) else 0, N, like=x, dtype=torch.long)
+    var = _variant(*variant, spectral if algorithm == 3 else None)
+    lib = L.lib()
+    ws = _cluster_ws(lib, B * T_new, N, W, pre_norm, K, algorithm, x.device)
+    L.check(lib.cc_token_cluster_variant_f32(L.ptr(x), tok, frame, B, T, T_new, n, W, K, metric, float(norm_p),
+                                             float(threshold), int(iter_limit), int(split_size), int(pre_norm),
+                                             ctypes.byref(var), L.ptr(out), o_tok, o_frame,
+                                             L.ptr(med) if med.numel() else None, L.ptr(assign) if assign.numel() else None,
+                                             None, L.ptr(ws), ws.numel(), _st(x)), "cc_token_cluster_variant_f32")
+    return out, med, assign
+
+
 @custom_op(NS + "::token_cluster", mutates_args=(), device_types="cuda")
 def token_cluster(x: torch.Tensor, frame_major: bool, T: int, T_new: int, K: int, metric: int, norm_p: float,
                   threshold: float, iter_limit: int, split_size: int, pre_norm: bool, algorithm: int, aggregation: int,
@@ -352,31 +387,10 @@ def token_cluster(x: torch.Tensor, frame_major: bool, T: int, T_new: int, K: int
     reference's layout) or [B*T, 1+n, W] (frame_major) -> same layout with T_new segments of 1+K tokens; medoids
     [T_new*B, K] int64 (empty unless want_medoids and algorithm 0 / 3).  algorithm 3 = 'spectral' (the spectral_* arguments:
     sigma, graph mode 0 HeatKernel / 1 KNN, knn_k, sign correction, optional [N,N] uint8 spatial-temporal mask)."""
-    if frame_major:
-        BT, Lt, W = x.shape
-        tok, frame = W, Lt * W
-    else:
-        Lt, BT, W = x.shape
-        tok, frame = BT * W, W
-    B, n = BT // T, Lt - 1
-    if frame_major:
-        out = _e(B * T_new, 1 + K, W, like=x, dtype=torch.float32)
-        o_tok, o_frame = W, (1 + K) * W
-    else:
-        out = _e(1 + K, B * T_new, W, like=x, dtype=torch.float32)
-        o_tok, o_frame = B * T_new * W, W
-    kmed = algorithm in (0, 3)
-    med = _e(B * T_new if (want_medoids and kmed) else 0, K, like=x, dtype=torch.long)
-    var = _variant(algorithm, aggregation, cluster_embed, cls_mult, fixed_ids,
-                   (spectral_sigma, spectral_mode, spectral_knn_k, spectral_sign, spectral_graph) if algorithm == 3 else None)
-    lib = L.lib()
-    N = (T // T_new) * n
-    ws = _cluster_ws(lib, B * T_new, N, W, pre_norm, K, algorithm, x.device)
-    L.check(lib.cc_token_cluster_variant_f32(L.ptr(x), tok, frame, B, T, T_new, n, W, K, metric, float(norm_p),
-                                             float(threshold), int(iter_limit), int(split_size), int(pre_norm),
-                                             ctypes.byref(var), L.ptr(out), o_tok, o_frame,
-                                             L.ptr(med) if med.numel() else None, None, None, L.ptr(ws), ws.numel(),
-                                             _st(x)), "cc_token_cluster_variant_f32")
+    out, med, _ = _token_cluster(x, frame_major, T, T_new, K, (metric, norm_p, threshold, iter_limit, split_size, pre_norm),
+                                 (algorithm, aggregation, cluster_embed, cls_mult, fixed_ids),
+                                 (spectral_sigma, spectral_mode, spectral_knn_k, spectral_sign, spectral_graph),
+                                 want_medoids=want_medoids, want_assign=False)
     return out, med
 
 
@@ -394,14 +408,6 @@ def _(x, frame_major, T, T_new, K, metric, norm_p, threshold, iter_limit, split_
     return out, x.new_empty((rows, K), dtype=torch.long)
 
 
-def _cluster_strides(shape, frame_major):
-    if frame_major:
-        BT, Lt, W = shape
-        return BT, Lt, W, W, Lt * W
-    Lt, BT, W = shape
-    return BT, Lt, W, BT * W, W
-
-
 @custom_op(NS + "::token_cluster_train", mutates_args=(), device_types="cuda")
 def token_cluster_train(x: torch.Tensor, frame_major: bool, T: int, T_new: int, K: int, metric: int, norm_p: float,
                         threshold: float, iter_limit: int, split_size: int, pre_norm: bool, algorithm: int, aggregation: int,
@@ -413,25 +419,10 @@ def token_cluster_train(x: torch.Tensor, frame_major: bool, T: int, T_new: int, 
     empty for 'pooling' / 'sparse_sampling').  Differentiable with respect to x, cluster_embed and cls_mult
     (torch.ops.centerclip.token_cluster_backward); the selection is a constant of the backward pass, as in the reference,
     whose k-medoids runs under no_grad (fast_kmeans.py:13,44)."""
-    BT, Lt, W, tok, frame = _cluster_strides(x.shape, frame_major)
-    B, n = BT // T, Lt - 1
-    oshape = (B * T_new, 1 + K, W) if frame_major else (1 + K, B * T_new, W)
-    out = _e(*oshape, like=x, dtype=torch.float32)
-    _, _, _, o_tok, o_frame = _cluster_strides(oshape, frame_major)
-    kmed = algorithm in (0, 3)
-    N = (T // T_new) * n
-    med = _e(B * T_new if kmed else 0, K, like=x, dtype=torch.long)
-    assign = _e(B * T_new if kmed else 0, N, like=x, dtype=torch.long)
-    var = _variant(algorithm, aggregation, cluster_embed, cls_mult, fixed_ids,
-                   (spectral_sigma, spectral_mode, spectral_knn_k, spectral_sign, spectral_graph) if algorithm == 3 else None)
-    lib = L.lib()
-    ws = _cluster_ws(lib, B * T_new, N, W, pre_norm, K, algorithm, x.device)
-    L.check(lib.cc_token_cluster_variant_f32(L.ptr(x), tok, frame, B, T, T_new, n, W, K, metric, float(norm_p),
-                                             float(threshold), int(iter_limit), int(split_size), int(pre_norm),
-                                             ctypes.byref(var), L.ptr(out), o_tok, o_frame,
-                                             L.ptr(med) if kmed else None, L.ptr(assign) if kmed else None, None,
-                                             L.ptr(ws), ws.numel(), _st(x)), "cc_token_cluster_variant_f32")
-    return out, med, assign
+    return _token_cluster(x, frame_major, T, T_new, K, (metric, norm_p, threshold, iter_limit, split_size, pre_norm),
+                          (algorithm, aggregation, cluster_embed, cls_mult, fixed_ids),
+                          (spectral_sigma, spectral_mode, spectral_knn_k, spectral_sign, spectral_graph),
+                          want_medoids=True, want_assign=True)
 
 
 @token_cluster_train.register_fake
