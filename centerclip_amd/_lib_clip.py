@@ -125,6 +125,14 @@ def declare(lib):
     lib.cc_patch_gather_any_f16.restype = c.c_int
     lib.cc_patch_gather3d_f16.argtypes = [c.POINTER(Frames), i32, i32, i32, i32, vp, vp]
     lib.cc_patch_gather3d_f16.restype = c.c_int
+    lib.cc_resize_plan_bytes.argtypes = [i32, i32, i32, i32]
+    lib.cc_resize_plan_bytes.restype = sz
+    lib.cc_resize_plan_build.argtypes = [i32, i32, i32, i32, vp]
+    lib.cc_resize_plan_build.restype = c.c_int
+    lib.cc_resize_crop_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.cc_resize_crop_workspace_bytes.restype = sz
+    lib.cc_resize_crop_u8.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp, sz, vp]
+    lib.cc_resize_crop_u8.restype = c.c_int
     lib.cc_clip_encode_frames.argtypes = [c.POINTER(VitModel), c.POINTER(Frames), i32, i32, vp, vp, vp,
                                           c.POINTER(TextModel), vp, i32, i32, vp, vp, sz, vp]
     lib.cc_clip_encode_frames.restype = c.c_int

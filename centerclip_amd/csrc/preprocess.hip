@@ -1,0 +1,304 @@
+// Resize + centre crop of decoded uint8 frames on the device, byte for byte what CLIP's loader transform gives
+// (dataloaders/rawvideo_util.py:16-23: Resize(n_px, BICUBIC) -> CenterCrop(n_px); the two operations behind them, ToTensor
+// and Normalize, already run inside the uint8 patch gather).  Resize is Pillow's 8-bit resample: per axis a table of 22-bit
+// integer coefficients computed in double, a horizontal pass rounded to bytes, then a vertical pass on those bytes.
+//
+// Host side (no GPU needed): cc_resize_plan_build fills the plan - geometry + the coefficient tables of the crop window's
+// columns and rows.  THIS TRANSLATION UNIT IS COMPILED WITH -ffp-contract=off (build.py STRICT): the coefficients are IEEE
+// double operations in source order.
+// Device side: two launches of one kernel (horizontal pass into the workspace, vertical pass into dst); a pass whose axis
+// keeps its size is not launched, and with neither the crop is a strided copy.  Only the window is computed: its n_px
+// columns, and of the source rows only those the window's vertical taps read.  Every source sample is loaded as a single byte
+// - a frame base and a row of 3 W bytes carry no alignment.
+#include <math.h>
+
+#include <vector>
+
+#include "cc_common.h"
+
+namespace {
+
+constexpr int kPrecisionBits = 22;
+constexpr int kMaxKsize = 65;                       // taps per output sample the launches take: a shrink factor of 16
+constexpr int32_t kMagic = 0x31504352;              // "RCP1"
+
+struct Geometry {
+    int oh, ow, top, left;                          // resized size, crop offsets in it
+    int row0, row1;                                 // source rows [row0, row1) the window reads
+    int ksize_h, ksize_v;                           // taps per output column / row; 0 = the pass is skipped
+};
+
+// torchvision CenterCrop: int(round((size - n_px) / 2.0)), round half to even
+int crop_offset(int size, int n_px) { return (int)nearbyint((size - n_px) / 2.0); }
+
+struct Axis {
+    int in, out, ksize;
+    double scale, support, ss;
+};
+
+Axis make_axis(int in, int out) {
+    Axis a;
+    a.in = in;
+    a.out = out;
+    a.scale = (double)in / (double)out;
+    const double fs = a.scale < 1.0 ? 1.0 : a.scale;
+    a.support = 2.0 * fs;
+    a.ss = 1.0 / fs;
+    a.ksize = (int)ceil(a.support) * 2 + 1;
+    return a;
+}
+
+double bicubic(double x) {
+    const double a = -0.5;
+    if (x < 0.0) x = -x;
+    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
+    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
+    return 0.0;
+}
+
+// taps of output index xx: first source index, count, and (coef != NULL) the count integer coefficients, zeros behind;
+// w: a.ksize doubles of scratch
+void axis_taps(const Axis& a, int xx, int* first, int* count, int32_t* coef, double* w) {
+    const double center = (xx + 0.5) * a.scale;
+    int xmin = (int)(center - a.support + 0.5);
+    if (xmin < 0) xmin = 0;
+    int xmax = (int)(center + a.support + 0.5);
+    if (xmax > a.in) xmax = a.in;
+    const int n = xmax - xmin;
+    *first = xmin;
+    *count = n;
+    if (!coef) return;
+    double ww = 0.0;
+    for (int x = 0; x < n; ++x) {
+        w[x] = bicubic(((x + xmin) - center + 0.5) * a.ss);
+        ww += w[x];
+    }
+    for (int x = 0; x < a.ksize; ++x) {
+        if (x >= n) {
+            coef[x] = 0;
+            continue;
+        }
+        const double v = ww != 0.0 ? w[x] / ww : w[x];
+        coef[x] = v < 0 ? (int)(-0.5 + v * (double)(1 << kPrecisionBits)) : (int)(0.5 + v * (double)(1 << kPrecisionBits));
+    }
+}
+
+// CC_OK and the geometry, or the status every entry point gives for these sizes.  max_ksize: the taps per output sample the
+// caller takes (the plan builder: any; the launches and their workspace: kMaxKsize).
+int geometry(int H, int W, int n_px, int resize, int max_ksize, Geometry* g) {
+    if (resize != 0 && resize != 1) return CC_ERR_INVALID;
+    if (n_px < 1 || n_px > 1024 || H < 4 || W < 4 || H > 8192 || W > 8192) return CC_ERR_UNSUPPORTED;
+    g->oh = H;
+    g->ow = W;
+    if (resize) {
+        // torchvision Resize(int): true division in double, then truncation; a short side that already is n_px: untouched
+        if (W <= H) {
+            if (W != n_px) {
+                g->ow = n_px;
+                g->oh = (int)((double)n_px * (double)H / (double)W);
+            }
+        } else if (H != n_px) {
+            g->oh = n_px;
+            g->ow = (int)((double)n_px * (double)W / (double)H);
+        }
+    }
+    if (g->oh < n_px || g->ow < n_px) return CC_ERR_UNSUPPORTED;        // (the crop's zero padding is not built)
+    g->top = crop_offset(g->oh, n_px);
+    g->left = crop_offset(g->ow, n_px);
+    g->ksize_h = g->ow != W ? make_axis(W, g->ow).ksize : 0;
+    g->ksize_v = g->oh != H ? make_axis(H, g->oh).ksize : 0;
+    if (g->ksize_h > max_ksize || g->ksize_v > max_ksize) return CC_ERR_UNSUPPORTED;
+    g->row0 = g->top;
+    g->row1 = g->top + n_px;
+    if (g->ksize_v) {
+        const Axis a = make_axis(H, g->oh);
+        g->row0 = H;
+        g->row1 = 0;
+        for (int y = 0; y < n_px; ++y) {
+            int first, count;
+            axis_taps(a, g->top + y, &first, &count, nullptr, nullptr);
+            if (first < g->row0) g->row0 = first;
+            if (first + count > g->row1) g->row1 = first + count;
+        }
+    }
+    return CC_OK;
+}
+
+size_t plan_ints(const Geometry& g, int n_px) { return CC_RESIZE_PLAN_HEADER + (size_t)n_px * (4 + g.ksize_h + g.ksize_v); }
+
+// byte strides of (frame, channel, row, column) of a uint8 image batch
+struct View {
+    int64_t sf, sc, sy, sx;
+};
+
+View view_of(int fmt, int64_t rows, int64_t cols) {
+    if (fmt == CC_FRAMES_U8_CHW) return View{3 * rows * cols, rows * cols, cols, 1};
+    return View{3 * rows * cols, 1, 3 * cols, 3};
+}
+
+// what the host believes the device plan was built for; a kernel handed another plan does nothing (its table entries are
+// source indices - they are only followed when they belong to these sizes)
+struct PlanKey {
+    int32_t H, W, n_px, resize;
+};
+
+__device__ __forceinline__ bool plan_matches(const int32_t* plan, const PlanKey& k) {
+    return plan[0] == kMagic && plan[1] == k.H && plan[2] == k.W && plan[3] == k.n_px && plan[4] == k.resize;
+}
+
+__device__ __forceinline__ uint8_t clip8(int acc) {
+    const int v = acc >> kPrecisionBits;                  // arithmetic shift
+    return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
+constexpr int kTileX = 64, kTileY = 4;
+
+// One pass.  A thread owns output pixel (f, oy, ox) - ox along the lanes, so source, intermediate and output accesses of a wave
+// run along a row - and its three channels.  HORIZONTAL: out(f, c, oy, ox) = sum_k in(f, c, row_base + oy, first[ox] + k) coef[ox][k];
+// vertical: out(f, c, oy, ox) = sum_k in(f, c, first[oy] + k, ox) coef[oy][k] (the coefficients are then uniform over a wave).
+// in_off: byte offset of the origin the row / column indices count from (the vertical pass reads the workspace, whose row 0 is
+// source row row0, or - no horizontal pass - the source itself from column `left`).
+template <bool VERT>
+__global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8_t* __restrict__ in, View iv, int64_t in_off,
+                                                                       int row_base, const int32_t* __restrict__ plan,
+                                                                       PlanKey key, uint8_t* __restrict__ out, View ov,
+                                                                       int out_rows, int tiles_x, int tiles_y) {
+    if (!plan_matches(plan, key)) return;
+    const int n_px = key.n_px;
+    const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
+    const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
+    if (ox >= n_px || oy >= out_rows) return;
+    const int ksize = plan[VERT ? 12 : 11];
+    const int32_t* tab = plan + plan[VERT ? 14 : 13];
+    const int j = VERT ? oy : ox;
+    const int first = tab[j], count = tab[n_px + j];
+    const int32_t* coef = tab + 2 * n_px + (int64_t)j * ksize;
+    const uint8_t* p = in + (in_off + (int64_t)f * iv.sf +
+                             (VERT ? (int64_t)first * iv.sy + (int64_t)ox * iv.sx
+                                   : (int64_t)(row_base + oy) * iv.sy + (int64_t)first * iv.sx));
+    const int64_t step = VERT ? iv.sy : iv.sx;
+    int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
+    for (int k = 0; k < count; ++k, p += step) {
+        const int w = coef[k];
+        a0 += (int)p[0] * w;
+        a1 += (int)p[iv.sc] * w;
+        a2 += (int)p[2 * iv.sc] * w;
+    }
+    uint8_t* q = out + (int64_t)f * ov.sf + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
+    q[0] = clip8(a0);
+    q[ov.sc] = clip8(a1);
+    q[2 * ov.sc] = clip8(a2);
+}
+
+// neither axis is resampled: out(f, c, oy, ox) = in(f, c, top + oy, left + ox)
+__global__ __launch_bounds__(kTileX* kTileY) void crop_u8_kernel(const uint8_t* __restrict__ in, View iv, int top, int left,
+                                                                   uint8_t* __restrict__ out, View ov, int n_px, int tiles_x,
+                                                                   int tiles_y) {
+    const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
+    const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
+    if (ox >= n_px || oy >= n_px) return;
+    const uint8_t* p = in + (int64_t)f * iv.sf + (int64_t)(top + oy) * iv.sy + (int64_t)(left + ox) * iv.sx;
+    uint8_t* q = out + (int64_t)f * ov.sf + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
+    q[0] = p[0];
+    q[ov.sc] = p[iv.sc];
+    q[2 * ov.sc] = p[2 * iv.sc];
+}
+
+bool u8_format(int fmt) { return fmt == CC_FRAMES_U8_CHW || fmt == CC_FRAMES_U8_HWC; }
+
+}  // namespace
+
+extern "C" {
+
+size_t cc_resize_plan_bytes(int32_t H, int32_t W, int32_t n_px, int32_t resize) {
+    Geometry g;
+    if (geometry(H, W, n_px, resize, INT32_MAX, &g) != CC_OK) return 0;
+    return plan_ints(g, n_px) * sizeof(int32_t);
+}
+
+int cc_resize_plan_build(int32_t H, int32_t W, int32_t n_px, int32_t resize, void* host_buf) {
+    if (!host_buf) return CC_ERR_INVALID;
+    Geometry g;
+    const int rc = geometry(H, W, n_px, resize, INT32_MAX, &g);
+    if (rc != CC_OK) return rc;
+    std::vector<double> w((size_t)(g.ksize_h > g.ksize_v ? g.ksize_h : g.ksize_v) + 1);
+    int32_t* plan = static_cast<int32_t*>(host_buf);
+    const int off_h = CC_RESIZE_PLAN_HEADER, off_v = off_h + n_px * (2 + g.ksize_h);
+    const int32_t header[CC_RESIZE_PLAN_HEADER] = {kMagic, H,         W,         n_px,  resize, g.oh,  g.ow,  g.top,
+                                                    g.left, g.row0,    g.row1,    g.ksize_h, g.ksize_v, off_h, off_v,
+                                                    (int32_t)plan_ints(g, n_px)};
+    for (int i = 0; i < CC_RESIZE_PLAN_HEADER; ++i) plan[i] = header[i];
+    for (int pass = 0; pass < 2; ++pass) {
+        const int ksize = pass ? g.ksize_v : g.ksize_h, origin = pass ? g.top : g.left;
+        int32_t* tab = plan + (pass ? off_v : off_h);
+        const Axis a = ksize ? (pass ? make_axis(H, g.oh) : make_axis(W, g.ow)) : Axis{};
+        for (int j = 0; j < n_px; ++j) {
+            if (!ksize) {                           // a skipped pass: the window's own rows / columns, no taps
+                tab[j] = origin + j;
+                tab[n_px + j] = 0;
+                continue;
+            }
+            axis_taps(a, origin + j, &tab[j], &tab[n_px + j], tab + 2 * n_px + (size_t)j * ksize, w.data());
+        }
+    }
+    return CC_OK;
+}
+
+size_t cc_resize_crop_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t n_px, int32_t resize) {
+    Geometry g;
+    if (F <= 0 || geometry(H, W, n_px, resize, kMaxKsize, &g) != CC_OK) return 0;
+    if (!g.ksize_h || !g.ksize_v) return 0;         // at most one pass: it writes dst itself
+    return (size_t)F * 3 * (size_t)(g.row1 - g.row0) * (size_t)n_px;
+}
+
+int cc_resize_crop_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_t W, const void* plan_dev, int32_t n_px,
+                      int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
+    if (!src || !dst || !plan_dev || F <= 0 || !u8_format(fmt) || !u8_format(dst_fmt)) return CC_ERR_INVALID;
+    Geometry g;
+    const int rc = geometry(H, W, n_px, resize, kMaxKsize, &g);
+    if (rc != CC_OK) return rc;
+    const int nrows = g.row1 - g.row0;
+    const int tiles_x = (n_px + kTileX - 1) / kTileX;
+    const int tiles_mid = (nrows + kTileY - 1) / kTileY, tiles_out = (n_px + kTileY - 1) / kTileY;
+    if ((int64_t)F * tiles_x * (tiles_mid > tiles_out ? tiles_mid : tiles_out) > 0x7fffffffLL) return CC_ERR_UNSUPPORTED;
+    const size_t need = cc_resize_crop_workspace_bytes(F, H, W, n_px, resize);
+    if (need && (!ws || ws_bytes < need)) return CC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint8_t* in = static_cast<const uint8_t*>(src);
+    uint8_t* out = static_cast<uint8_t*>(dst);
+    const int32_t* plan = static_cast<const int32_t*>(plan_dev);
+    const View sv = view_of(fmt, H, W), dv = view_of(dst_fmt, n_px, n_px);
+    const PlanKey key{H, W, n_px, resize};
+    const dim3 block(kTileX, kTileY);
+    if (!g.ksize_h && !g.ksize_v) {
+        crop_u8_kernel<<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, g.top, g.left, out, dv, n_px, tiles_x,
+                                                                               tiles_out);
+        CC_LAUNCH_CHECK();
+        return CC_OK;
+    }
+    if (g.ksize_h && !g.ksize_v) {                  // rows keep their size: the horizontal pass writes the window's rows
+        resample_u8_kernel<false><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, 0, g.top, plan, key, out, dv,
+                                                                                          n_px, tiles_x, tiles_out);
+        CC_LAUNCH_CHECK();
+        return CC_OK;
+    }
+    if (!g.ksize_h) {                               // columns keep their size: the vertical pass reads the source from `left`
+        resample_u8_kernel<true><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, (int64_t)g.left * sv.sx, 0,
+                                                                                         plan, key, out, dv, n_px, tiles_x,
+                                                                                         tiles_out);
+        CC_LAUNCH_CHECK();
+        return CC_OK;
+    }
+    // both: the horizontal result of source rows [row0, row1), rounded to bytes, planar [F, 3, nrows, n_px] in the workspace
+    uint8_t* mid = static_cast<uint8_t*>(ws);
+    const View mv = view_of(CC_FRAMES_U8_CHW, nrows, n_px);
+    resample_u8_kernel<false><<<(unsigned)(F * tiles_x * tiles_mid), block, 0, st>>>(in, sv, 0, g.row0, plan, key, mid, mv,
+                                                                                      nrows, tiles_x, tiles_mid);
+    CC_LAUNCH_CHECK();
+    resample_u8_kernel<true><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(mid, mv, -(int64_t)g.row0 * mv.sy, 0, plan,
+                                                                                     key, out, dv, n_px, tiles_x, tiles_out);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+}  // extern "C"

@@ -253,7 +253,7 @@ class _GraphedLane:
 
 
 def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False, backend=HipBackend, in_flight=None,
-               similarity_products=None, graphed=False, camoe_dsl=None):
+               similarity_products=None, graphed=False, camoe_dsl=None, frame_transform=None):
     """main.py:381-499 -> (R1, all_infer_time, info_str).  ``shard=True``: clip-sharded over the ranks of the default
     process group (module docstring) - every rank must call it and every rank returns the same numbers.
     ``in_flight`` (not in the reference; > 1 GPU only; default: 2 on a GPU, 1 on the CPU stand-in): n keeps n batches in flight -
@@ -270,7 +270,11 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
     ``camoe_dsl`` (params.py:278; the reference keeps its use commented out, main.py:526-532): rank D = S * softmax(S, dim=0) * Nt
     instead of S, in both directions.  None = ``args.camoe_dsl`` when ``args`` carries it, else the model's attribute.  Sharded:
     every rank takes the column statistics of its row block, they are combined with an all-reduce MAX and an all-reduce SUM
-    (2 x Nv floats), and each block is rewritten in place - the matrix still never exists on one device."""
+    (2 x Nv floats), and each block is rewritten in place - the matrix still never exists on one device.
+    ``frame_transform`` (not in the reference, whose loader does this per frame on the CPU; GPU only): a
+    ``preprocess.FrameTransform`` - the loader hands over decoded uint8 frames of any size and the resize + centre crop runs on
+    ``video`` right after it reaches the device, on the batch's lane; with ``graphed`` in front of the copy into the lane's
+    device-resident inputs (the graphs see model-resolution frames only).  None: the loop as it always was."""
     log = log or (lambda s: None)
     if in_flight is None:
         in_flight = 2 if (torch.cuda.is_available() and torch.device(device).type == "cuda") else 1
@@ -342,11 +346,15 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
                 if graphs is not None and not multi:
                     lane = graphs.setdefault(bid % in_flight, _GraphedLane(net, core, be, lane_stream if lane_stream is not None
                                                                            else graph_stream))
+                    if frame_transform is not None:
+                        batch = tuple(batch[:3]) + (frame_transform(batch[3].to(device, non_blocking=True)),) + tuple(batch[4:])
                     t_op, v_op = lane(batch, device)
                     cache.add_text(keep_rows(t_op), pos)
                     cache.add_video(keep_rows(v_op), pos)
                     continue
                 input_ids, input_mask, segment_ids, video, video_mask = (t.to(device) for t in batch)
+                if frame_transform is not None:
+                    video = frame_transform(video)
                 if not multi:
                     out = net(input_ids, segment_ids, input_mask, video, video_mask)
                     cache.add_text(keep_rows(be.text_operand(out['sequence_output'].reshape(b if keep.numel() == b else keep.numel(), -1))), pos)

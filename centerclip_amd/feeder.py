@@ -11,13 +11,20 @@ loader: with the decoder's uint8 frames (N3: 1.8 MB per 12-frame clip, the norma
 Ordering: the compute stream waits for the slot's copy event before it reads the slot; the copy stream waits for the
 event the compute stream records when it is done with the slot before it overwrites it.  No host synchronisation.
 PyTorch streams / events / ``Tensor.copy_(non_blocking=True)`` only: plumbing, no kernels of its own.
+
+``frame_transform`` (a ``preprocess.FrameTransform``) takes decoded frames of any size: the loader hands over the raw uint8
+video, the resize + centre crop runs on the copy stream right behind the slot's copy, into a second buffer of the slot, and that
+buffer is yielded in the raw video's place - the consumer sees model-resolution frames at addresses that never change.
+``video_index``: the video's position in the loader's tuple (default: its only 4-D / 6-D uint8 tensor).
 """
 import torch
 
 
 class DeviceFeeder:
-    def __init__(self, device, depth=2):
+    def __init__(self, device, depth=2, frame_transform=None, video_index=None):
         assert depth >= 2, "double buffering needs two slots"
+        self.frame_transform, self.video_index = frame_transform, video_index
+        self.cooked = [None] * depth                                 # per slot: the transform's output buffer, or None
         self.device = torch.device(device)
         self.depth = depth
         self.copy_stream = torch.cuda.Stream(self.device)
@@ -31,6 +38,12 @@ class DeviceFeeder:
         if self.slots[k] is None or any(tuple(d.shape) != tuple(h.shape) or d.dtype != h.dtype
                                         for d, h in zip(self.slots[k], host_batch)):
             self.slots[k] = tuple(torch.empty(h.shape, dtype=h.dtype, device=self.device) for h in host_batch)
+            self.cooked[k] = None
+            if self.frame_transform is not None:
+                vi = self._video_index(host_batch)
+                if not self.frame_transform.passes_through(host_batch[vi].shape):
+                    self.cooked[k] = torch.empty(self.frame_transform.output_shape(host_batch[vi].shape), dtype=torch.uint8,
+                                                 device=self.device)
         with torch.cuda.stream(self.copy_stream):
             if self._used[k]:
                 self.copy_stream.wait_event(self.free[k])
@@ -40,7 +53,24 @@ class DeviceFeeder:
                 self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))
             for d, h in zip(self.slots[k], host_batch):
                 d.copy_(h, non_blocking=True)                        # asynchronous only from pinned memory
+            if self.cooked[k] is not None:
+                self.frame_transform(self.slots[k][self._video_index(host_batch)], out=self.cooked[k])
             self.ready[k].record(self.copy_stream)
+
+    def _video_index(self, batch):
+        if self.video_index is not None:
+            return self.video_index
+        found = [i for i, t in enumerate(batch) if t.dtype == torch.uint8 and t.dim() in (4, 6)]
+        if len(found) != 1:
+            raise ValueError("DeviceFeeder(frame_transform=...): the batch has %d uint8 frame tensors - pass video_index"
+                             % len(found))
+        return found[0]
+
+    def _view(self, k):
+        if self.cooked[k] is None:
+            return self.slots[k]
+        vi = self._video_index(self.slots[k])
+        return self.slots[k][:vi] + (self.cooked[k],) + self.slots[k][vi + 1:]
 
     def __call__(self, host_batches):
         """Iterate over (slot index, device tensors) for an iterable of host batches (tuples of CPU tensors, ideally pinned)."""
@@ -56,7 +86,7 @@ class DeviceFeeder:
             k = filled.pop(0)
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(self.ready[k])
-            yield k, self.slots[k]
+            yield k, (self.slots[k] if self.frame_transform is None else self._view(k))
             self.free[k].record(cur)                                 # everything the consumer enqueued on `cur` so far
             self._used[k] = True
             try:

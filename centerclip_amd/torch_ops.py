@@ -919,6 +919,92 @@ def _(frames, T, resolution, patch):
     return frames.new_empty((frames.shape[0] * g * g, 9 * patch * patch), dtype=torch.float16)
 
 
+def _raw_frames_geometry(shape):
+    """uint8 frames [..., H, W, 3] or [..., 3, H, W] (at least one leading dimension) -> (channels_first, H, W); [.., 3, H, W]
+    wins where both read, as in clip.frames_descriptor."""
+    if len(shape) < 4 or (shape[-3] != 3 and shape[-1] != 3):
+        raise ValueError("uint8 frames must be [..., H, W, 3] or [..., 3, H, W] with a leading frame dimension, got %s"
+                         % (tuple(shape),))
+    if shape[-3] == 3:
+        return True, int(shape[-2]), int(shape[-1])
+    return False, int(shape[-3]), int(shape[-2])
+
+
+_RESIZE_PLANS = {}
+
+
+def resize_plan(H, W, n_px, resize, device):
+    """The device copy of the plan of cc_resize_crop_u8 for (H, W, n_px, resize), built on the host and uploaded ONCE per device.
+    The upload cannot be part of a stream capture: a size that was not seen before the capture is refused there."""
+    device = torch.device(device)
+    key = (int(H), int(W), int(n_px), int(bool(resize)), device.type, device.index if device.index is not None
+           else torch.cuda.current_device())
+    plan = _RESIZE_PLANS.get(key)
+    if plan is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise L.CenterClipHipError("resize_center_crop: no plan for %dx%d -> %d frames yet and the stream is being captured "
+                                       "(the plan is uploaded once, outside any capture: run this size eagerly first)"
+                                       % (H, W, n_px))
+        lib = L.lib()
+        nbytes = lib.cc_resize_plan_bytes(*key[:4])
+        host = torch.empty(max(nbytes // 4, 1), dtype=torch.int32)
+        L.check(lib.cc_resize_plan_build(*key[:4], ctypes.c_void_p(host.data_ptr())), "cc_resize_plan_build")
+        plan = host.to(device)
+        _RESIZE_PLANS[key] = plan
+    return plan
+
+
+def _resize_crop_shape(shape, n_px):
+    chw, _, _ = _raw_frames_geometry(shape)
+    return tuple(shape[:-3]) + ((3, n_px, n_px) if chw else (n_px, n_px, 3))
+
+
+def _resize_crop_into(frames, out, n_px, resize):
+    if frames.dtype != torch.uint8 or out.dtype != torch.uint8:
+        raise ValueError("resize_center_crop takes and gives uint8 frames, got %s -> %s" % (frames.dtype, out.dtype))
+    chw, H, W = _raw_frames_geometry(frames.shape)
+    if tuple(out.shape) != _resize_crop_shape(frames.shape, n_px) or not out.is_contiguous():
+        raise ValueError("resize_center_crop: out must be a contiguous %s, got %s"
+                         % (_resize_crop_shape(frames.shape, n_px), tuple(out.shape)))
+    frames = frames.contiguous()
+    F = math.prod(frames.shape[:-3])
+    if F == 0:
+        return
+    lib = L.lib()
+    plan = resize_plan(H, W, n_px, resize, frames.device)
+    nws = lib.cc_resize_crop_workspace_bytes(F, H, W, int(n_px), int(resize))
+    ws = L.workspace(nws, frames.device) if nws else None
+    fmt = 1 if chw else 2
+    L.check(lib.cc_resize_crop_u8(L.ptr(frames), fmt, F, H, W, L.ptr(plan), int(n_px), int(resize), L.ptr(out), fmt,
+                                  L.ptr(ws), ws.numel() if ws is not None else 0, _st(frames)), "cc_resize_crop_u8")
+
+
+@custom_op(NS + "::resize_center_crop", mutates_args=(), device_types="cuda")
+def resize_center_crop(frames: torch.Tensor, n_px: int, resize: bool) -> torch.Tensor:
+    """The loader transform in front of the encoders (cc_resize_crop_u8): uint8 frames [..., H, W, 3] or [..., 3, H, W] of any
+    size -> uint8 [..., n_px, n_px, 3] / [..., 3, n_px, n_px] (the input's layout), byte for byte Pillow's bicubic
+    Resize(n_px) + CenterCrop(n_px) (dataloaders/rawvideo_util.py:16-23); resize=False: the crop alone."""
+    out = _e(*_resize_crop_shape(frames.shape, n_px), like=frames, dtype=torch.uint8)
+    _resize_crop_into(frames, out, n_px, resize)
+    return out
+
+
+@resize_center_crop.register_fake
+def _(frames, n_px, resize):
+    return frames.new_empty(_resize_crop_shape(frames.shape, n_px), dtype=torch.uint8)
+
+
+@custom_op(NS + "::resize_center_crop_out", mutates_args=("out",), device_types="cuda")
+def resize_center_crop_out(frames: torch.Tensor, n_px: int, resize: bool, out: torch.Tensor) -> None:
+    """resize_center_crop into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay)."""
+    _resize_crop_into(frames, out, n_px, resize)
+
+
+@resize_center_crop_out.register_fake
+def _(frames, n_px, resize, out):
+    return None
+
+
 @custom_op(NS + "::clip_encode_out", mutates_args=("vfeat", "tfeat", "medoids_out"), device_types="cuda")
 def clip_encode_out(frames: torch.Tensor, ids: torch.Tensor, vhandle: int, thandle: int, B: int, T: int,
                     vfeat: torch.Tensor, tfeat: torch.Tensor, medoids_out: Optional[torch.Tensor],
@@ -1335,7 +1421,8 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "pairwise_distance", "pairwise_distance_cross", "token_norms", "vit_encode", "text_encode", "clip_encode_out", "clip_encode",
        "loose_similarity", "video_pool_normalize", "normalize_rows", "scaled_dot_nt", "scaled_dot_nt_out", "rank_counts",
        "rank_counts_cols", "rank_counts_ref", "group_max_rows", "normalize_rows_planes", "video_pool_normalize_planes",
-       "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16")
+       "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
+       "resize_center_crop", "resize_center_crop_out")
 
 
 def logit_multiplier(logit_scale):

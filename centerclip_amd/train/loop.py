@@ -11,7 +11,7 @@ from .scaler import DeviceGradScaler, _device_scaler
 
 
 def train_epoch(epoch, args, model, train_dataloader, device, optimizer, global_step, scheduler=None, buckets=None,
-                log=None, scaler=None):
+                log=None, scaler=None, frame_transform=None):
     """main.py:291-378 for this path: zero_grad -> forward (training branch of CLIP4Clip.forward) -> backward ->
     [gradient average over the ranks, dist.GradientBuckets] -> [clip_grad_norm_] -> optimizer.step -> clamp logit_scale.
     ``model``: a centerclip_amd.clip4clip.CLIP4Clip in training mode.  -> (mean loss, global_step).
@@ -23,7 +23,11 @@ def train_epoch(epoch, args, model, train_dataloader, device, optimizer, global_
     the device, so the factor passes through exactly), gradients are unscaled (and averaged over the ranks) before clipping,
     a step whose gradients hold an inf / NaN is skipped and the scale backed off, as GradScaler.step / update do.
     A ``DeviceGradScaler`` runs the same branch without a host decision (no unscaling pass, no .item() on found_inf); its
-    clipping is its own clip_grad_norm_ over the optimizer's parameters, folded into the step's one multiplier."""
+    clipping is its own clip_grad_norm_ over the optimizer's parameters, folded into the step's one multiplier.
+
+    ``frame_transform`` (not in the reference, whose loader does this per frame on the CPU): a ``preprocess.FrameTransform`` -
+    the loader hands over decoded uint8 frames of any size, resized and centre-cropped on the device right after the copy.
+    None: the loop as it always was."""
     model.train()
     total_loss, nb = 0.0, 0
     for step, batch in enumerate(train_dataloader):
@@ -31,6 +35,8 @@ def train_epoch(epoch, args, model, train_dataloader, device, optimizer, global_
         if scheduler is not None:
             scheduler(optimizer, global_step=global_step)
         input_ids, input_mask, segment_ids, video, video_mask = tuple(t.to(device=device, non_blocking=True) for t in batch)
+        if frame_transform is not None:
+            video = frame_transform(video)
         output = model(input_ids, segment_ids, input_mask, video, video_mask)
         loss = output['loss'].mean()
         if args.gradient_accumulation_steps > 1:

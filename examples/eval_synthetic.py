@@ -8,6 +8,7 @@ dataloaders/* to evaluate a trained model.
 
     python examples/eval_synthetic.py [--clips 64] [--algo kmediods++|spectral|pooling] [--l14 1 [--oracle-check 1]]
     python examples/eval_synthetic.py --resume DIR/ckpt.pth.tar      (main.py's --resume ... --do_eval 1: evaluate a checkpoint)
+    python examples/eval_synthetic.py --raw_frames 240x320           (decoded uint8 frames; resize + centre crop on the device)
 """
 import argparse
 import os
@@ -24,9 +25,14 @@ import bench                                                # noqa: E402  (cfg-2
 class SyntheticRetrieval(torch.utils.data.Dataset):
     """(input_ids, input_mask, segment_ids, video, video_mask) as dataloaders/* yield them (main.py:427)."""
 
-    def __init__(self, n, frames=12, words=32, seed=0):
+    def __init__(self, n, frames=12, words=32, seed=0, raw_frames=None):
+        """raw_frames (H, W): the video as a decoder leaves it - uint8 [n, 1, frames, H, W, 3] of that size, for
+        eval_epoch(frame_transform=...) - instead of the transformed float tensor."""
         g = torch.Generator().manual_seed(seed)
-        self.video = torch.randn(n, 1, frames, 3, 224, 224, generator=g)
+        if raw_frames is None:
+            self.video = torch.randn(n, 1, frames, 3, 224, 224, generator=g)
+        else:
+            self.video = torch.randint(0, 256, (n, 1, frames, raw_frames[0], raw_frames[1], 3), dtype=torch.uint8, generator=g)
         self.ids = torch.randint(1, 49405, (n, words), generator=g)
         self.ids[:, 0] = 49406
         eot = torch.randint(3, words, (n,), generator=g)
@@ -94,6 +100,19 @@ def shift_plan(args):
     return args
 
 
+def transform_ms(transform, video, device, reps=10):
+    """Device time of the frame transform on one batch, from its own events (the first call builds and uploads the plan)."""
+    x = video.to(device)
+    transform(x)
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    start.record()
+    for _ in range(reps):
+        transform(x)
+    stop.record()
+    stop.synchronize()
+    return start.elapsed_time(stop) / reps
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=64)
@@ -113,6 +132,9 @@ def main():
     ap.add_argument("--oracle-check", type=int, default=0, help="--l14: also compare one 2-frame clip's embeddings with the CPU oracle")
     ap.add_argument("--resume", default=None, help="main.py's --resume with --do_eval 1: a checkpoint (train_synthetic.py --output_dir) "
                                                    "whose weights are evaluated")
+    ap.add_argument("--raw_frames", default=None, metavar="HxW",
+                    help="the loader yields decoded uint8 frames of this size; Resize(res, BICUBIC) + CenterCrop(res) of CLIP's "
+                         "transform run on the device (eval_epoch(frame_transform=...))")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = L14 if a.l14 else bench.CFG2
@@ -132,8 +154,16 @@ def main():
         from centerclip_amd.train import resume
         resume(a.resume, model, load_from_pretrained=True)  # (the weights alone: nothing here trains)
         print("evaluating the weights of %s" % a.resume)
-    loader = torch.utils.data.DataLoader(SyntheticRetrieval(a.clips), batch_size=a.batch, shuffle=False)
-    r1, seconds, info = eval_epoch(model, loader, device, args, log=print, in_flight=a.in_flight)
+    raw = tuple(int(v) for v in a.raw_frames.lower().split("x")) if a.raw_frames else None
+    loader = torch.utils.data.DataLoader(SyntheticRetrieval(a.clips, raw_frames=raw), batch_size=a.batch, shuffle=False)
+    transform = None
+    if raw is not None:
+        from centerclip_amd.preprocess import FrameTransform
+        transform = FrameTransform(c["res"])
+        print("frame transform %dx%d -> %d: %.3f ms per batch of %d clips" % (raw[0], raw[1], c["res"], transform_ms(
+            transform, next(iter(loader))[3], device), a.batch))
+    r1, seconds, info = eval_epoch(model, loader, device, args, log=print, in_flight=a.in_flight,
+                                   **({"frame_transform": transform} if transform is not None else {}))
     print("\n".join(info))
     print("R@1 %.1f (random weights: chance level is %.1f); model time %.2f s for %d clips" % (r1, 100.0 / a.clips, seconds, a.clips))
 

@@ -692,6 +692,40 @@ int cc_patch_gather_any_f16(const cc_frames* frames, int32_t F, int32_t resoluti
 int cc_patch_gather3d_f16(const cc_frames* frames, int32_t F, int32_t T, int32_t resolution, int32_t patch, void* out_f16,
                           void* stream);
 
+/* The loader transform in front of the patch gather: decoded uint8 frames of any size H x W -> the n_px x n_px uint8 frames the
+ * uint8 formats of cc_frames take, byte for byte what CLIP's transform (dataloaders/rawvideo_util.py:16-23: Resize(n_px,
+ * BICUBIC) -> CenterCrop(n_px)) produces before ToTensor / Normalize - Pillow's 8-bit bicubic resample (double coefficients
+ * rounded to 22-bit integers; a horizontal pass rounded to bytes, then a vertical pass on those bytes; a pass whose axis
+ * keeps its size is skipped) and torchvision's sizes (the short side becomes n_px, the long side int(n_px * long / short); a
+ * short side that already is n_px leaves the frame as it is; crop offsets round((size - n_px) / 2.0), half to even).
+ * resize = 0 is the crop alone (dataloaders/decode.py:37,46 on videos that preprocess/compress_video.py already shrank).
+ * Range: 1 <= n_px <= 1024, 4 <= H, W <= 8192 and a resized frame no smaller than the crop (torchvision's zero padding is
+ * not built); for cc_resize_crop_u8 and its workspace also at most 65 taps per output sample on either axis (ksize =
+ * 2 ceil(2 in / out) + 1 <= 65: a shrink factor of 16; the plan builder itself takes any) - else CC_ERR_UNSUPPORTED; resize
+ * other than 0 / 1: CC_ERR_INVALID.  DESIGN.md, "Resize and centre crop".
+ *
+ * The plan is a flat int32 table, built on the host without a GPU and uploaded by the caller once per (H, W, n_px, resize):
+ *   [0] magic  [1] H  [2] W  [3] n_px  [4] resize  [5] oh  [6] ow (resized size)  [7] top  [8] left (crop offsets in it)
+ *   [9] row0  [10] row1 (the source rows [row0, row1) the window reads)  [11] ksize_h  [12] ksize_v (taps per output column /
+ *   row; 0 = that pass is skipped)  [13] off_h  [14] off_v (int32 offsets of the two tables)  [15] total int32 count
+ *   table at off_h: first[n_px] (first source column of window column j), count[n_px], coef[n_px][ksize_h] (zeros behind
+ *   count[j]); table at off_v: the same for the window's rows.  A skipped pass: first[j] = left + j (top + j), count[j] = 0.
+ *   One pass over an axis: out = clamp((2^21 + sum_k in[first[j] + k] * coef[j][k]) >> 22, 0, 255) in int32. */
+#define CC_RESIZE_PLAN_HEADER 16
+/* bytes of the plan; 0 for sizes cc_resize_plan_build refuses */
+size_t cc_resize_plan_bytes(int32_t H, int32_t W, int32_t n_px, int32_t resize);
+int cc_resize_plan_build(int32_t H, int32_t W, int32_t n_px, int32_t resize, void* host_buf);
+/* bytes of the horizontal pass' result (F x 3 x (row1 - row0) x n_px); 0 when at most one pass runs or the launch is refused */
+size_t cc_resize_crop_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t n_px, int32_t resize);
+/* src: F frames [H, W, 3] (fmt = CC_FRAMES_U8_HWC) or [3, H, W] (CC_FRAMES_U8_CHW) at ANY byte address; plan_dev: the plan of
+ * (H, W, n_px, resize) in device memory - the host decides the launches from these four arguments and never reads the plan;
+ * the kernels follow its tables only when its header names the same four values, a plan built for anything else leaves dst
+ * unwritten; dst: [F, n_px, n_px, 3] or [F, 3, n_px, n_px] (dst_fmt).  At most two launches, no upload, no synchronisation
+ * (capturable).  CC_ERR_INVALID for a NULL src / dst / plan, F <= 0 or a format other than the two uint8 codes;
+ * CC_ERR_WORKSPACE for a NULL or short workspace where cc_resize_crop_workspace_bytes is not 0; all before any launch. */
+int cc_resize_crop_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_t W, const void* plan_dev, int32_t n_px,
+                      int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream);
+
 /* S2 - the meanP similarity tail, CLIP4Clip._loose_similarity (modules/clip4clip.py:357-366) with
  * _mean_pooling_for_similarity_visual (:305-316):
  *   v_hat = v/|v| per frame; v_bar = sum_t mask*v_hat / max(sum_t mask, 1 if 0); v_bar /= |v_bar|
