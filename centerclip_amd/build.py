@@ -16,7 +16,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # the cluster / similarity paths promise IEEE single operations in source order (no fma contraction); preprocess.hip the same
 # for the double operations of its host-side coefficient tables
 STRICT = {"cluster.hip": ["-ffp-contract=off"], "similarity.hip": ["-ffp-contract=off"], "dsl.hip": ["-ffp-contract=off"],
-          "preprocess.hip": ["-ffp-contract=off"]}
+          "preprocess.hip": ["-ffp-contract=off"], "search.hip": ["-ffp-contract=off"]}
 
 
 def sources():

@@ -1,0 +1,333 @@
+// Exact top-k retrieval over cached similarity operands on gfx950: the k best gallery rows per query row and their scores,
+// without the [Bq, Bg] matrix.  The operands are the split-fp16 planes of similarity.hip; a score is what
+// cc_scaled_dot_planes_products_f32 stores for the same pair, bit for bit: ONE fp32 accumulator per (query, gallery row) fed
+// by v_mfma_f32_16x16x32_f16 over the 32-wide k-slices in ascending order with the gallery fragment as the first operand
+// (gemm.hip: mfma(bf, af, acc) for ks = 0, 1 of every k-step), then sc * acc with sc = mult * 2^-20.
+//
+// Two launches; no workgroup reads what another workgroup of the same launch wrote (the per-XCD L2s are not coherent, the
+// kernel boundary is the hand-over):
+//   1. topk_stream_kernel, grid (gallery slices) x (groups of 16 query rows), 4 waves.  The 16 query rows are staged once
+//      in LDS.  A wave multiplies whole 16-row gallery tiles: its fragments go from global memory straight to registers
+//      (16-byte loads; the two k-slices of a 128-byte line are requested back to back).  Per query row every wave keeps a
+//      descending list of its k best in LDS and, in a register, the row's k-th key.  After a tile the lanes compare their
+//      4 values with that threshold, a wave-wide ballot says whether any survived, and the survivors of all 16 query rows
+//      are inserted side by side, 4 lanes a list (tk_insert_tile).  At the end the four waves' lists are folded into one per
+//      query row and written to the workspace: [Bq][k][slices] keys.
+//   2. topk_merge_kernel, one wave per query row: the slices' lists -> the final k, decoded into scores / ids.
+// A (score, id) pair is ONE 64-bit key whose unsigned order is the result's order (larger score first, equal scores by
+// smaller id; -0 and +0 equal), so ties never need a second look and the lists of any split merge to the same result.
+#include "cc_kernels.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef unsigned long long u64;
+
+namespace {
+
+constexpr int TK_WAVES = 4;            // waves of a streaming workgroup
+constexpr int TK_QROWS = 16;           // query rows of a workgroup (one MFMA tile side)
+constexpr int TK_MAXK = 128;
+constexpr int TK_QPAD = 8;             // halfs behind a staged query row: 16 rows 16 bytes apart mod 256 cover all LDS banks
+constexpr int TK_TARGET_WGS = 512;     // streaming workgroups aimed at: the 256 CUs twice
+constexpr int TK_MIN_TILES = 32;       // 16-row tiles a slice holds at least (8 per wave)
+constexpr int TK_BATCH = 4;            // pairs of k-slices a lane requests at once (8 loads of 16 bytes)
+constexpr int TK_MERGE_BATCH = 8;      // keys per lane the merge requests before it looks at any
+constexpr size_t TK_LDS_LIMIT = 160 * 1024;
+
+// key = [ordered score bits : 32][~id, 31 bits][score was -0 : 1].  The score enters as score + 0.0f (so -0 orders as +0);
+// the last bit only restores the sign of a zero on the way out - ids are unique, it never decides an order.  No finite or
+// infinite score gives the high word 0: key 0 is the empty entry, decoded as (-inf, -1).
+__device__ __forceinline__ u64 tk_key(float score, int id) {
+    const unsigned negzero = __float_as_uint(score) == 0x80000000u ? 1u : 0u;
+    const unsigned low = ((~(unsigned)id & 0x7FFFFFFFu) << 1) | negzero;
+    return ((u64)cc_float_to_ordered_uint(score + 0.0f) << 32) | low;
+}
+__device__ __forceinline__ void tk_decode(u64 key, float& score, int& id) {
+    if (key == 0) { score = -INFINITY; id = -1; return; }
+    const unsigned o = (unsigned)(key >> 32), low = (unsigned)key;
+    unsigned u = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
+    if (low & 1u) u = 0x80000000u;
+    score = __uint_as_float(u);
+    id = (int)(~(low >> 1) & 0x7FFFFFFFu);
+}
+
+// LDS traffic between the lanes of one wave: the hardware runs a wave's LDS instructions in order, the compiler must not
+// move them over this point
+__device__ __forceinline__ void tk_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// max over the 4 lanes l15 + 16 {0, 1, 2, 3} (the lanes that hold one query row's values), in all of them: the row swaps of
+// cc_lane_xor16_pair / cc_lane_xor32_pair on both halves of the key
+__device__ __forceinline__ u64 tk_group_max(u64 x) {
+    {
+        const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)x, (unsigned)x, false, false);
+        const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(x >> 32), (unsigned)(x >> 32), false, false);
+        const u64 a = ((u64)hi[0] << 32) | lo[0], b = ((u64)hi[1] << 32) | lo[1];
+        x = a > b ? a : b;
+    }
+    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)x, (unsigned)x, false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(x >> 32), (unsigned)(x >> 32), false, false);
+    const u64 a = ((u64)hi[0] << 32) | lo[0], b = ((u64)hi[1] << 32) | lo[1];
+    return a > b ? a : b;
+}
+
+// Candidates into the wave's 16 lists at once.  Lane (l15, lg) brings up to 4 keys (0 = none) for `list`, the descending list
+// of query row l15 (k entries), and holds that list's k-th key in `thr`.  A round takes, per list, the largest candidate its 4
+// lanes still hold above the threshold, and those 4 lanes shift it in, 16 entries a step (4 a lane) from the bottom up: a
+// step writes entries [base, base + 15] from the old [base - 1, base + 14], every lane reading before any lane writes, and
+// the entries later steps read lie above - nothing is read after it was overwritten.  `filled` (uniform) bounds the entries
+// any of the wave's lists holds - a round adds at most one - so the steps start at the first empty entry, not at k; they end
+// with the first one in which no list moved an entry (the lists descend: nothing above moves either).  The rounds end when no
+// candidate is above its threshold: at most min(k, 16) of them, where inserting the survivors one at a time took up to
+// 16 x 16 dependent LDS round trips.
+__device__ __forceinline__ void tk_insert_tile(u64 (&key)[4], u64* list, int k, int lg, u64& thr, int& filled) {
+    for (;;) {
+        u64 m = key[0];
+#pragma unroll
+        for (int r = 1; r < 4; ++r) m = key[r] > m ? key[r] : m;
+        m = m > thr ? m : 0;
+        if (!__ballot(m != 0)) break;
+        const u64 gm = tk_group_max(m);                      // 0: nothing for this list in this round
+#pragma unroll
+        for (int r = 0; r < 4; ++r) key[r] = key[r] == gm ? 0 : key[r];      // (ids are unique: one lane, one key)
+        for (int base = min(filled, k - 1) & ~15; base >= 0; base -= 16) {
+            const int i0 = base + 4 * lg;
+            u64 v[5];                                        // old entries i0 - 1 .. i0 + 3; beyond the list: never moved
+#pragma unroll
+            for (int u = 0; u < 5; ++u) {                    // (clamped addresses: five loads in a row, no branch, one wait)
+                const int i = i0 - 1 + u;
+                const u64 raw = list[min(max(i, 0), k - 1)];
+                v[u] = (gm != 0 && i >= 0 && i < k) ? raw : ~0ull;
+            }
+            tk_wave_sync();
+            bool moved = false;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (v[u + 1] < gm) {
+                    list[i0 + u] = v[u] > gm ? gm : v[u];
+                    moved = true;
+                }
+            }
+            tk_wave_sync();
+            if (!__ballot(moved)) break;
+        }
+        filled = min(filled + 1, k);
+        thr = list[k - 1];
+    }
+}
+
+// The wave inserts `key` (uniform) into the descending list of k entries: entries below it move one place down, the last
+// one leaves; a key below the last entry changes nothing.  Every lane reads before any lane writes.  (The merge launch.)
+__device__ __forceinline__ void tk_insert(u64* list, int k, u64 key, int lane) {
+    const bool in0 = lane < k, in1 = lane + 64 < k;
+    const u64 r0 = list[min(lane, k - 1)], q0 = list[min(max(lane - 1, 0), k - 1)];      // (clamped: loads without a branch)
+    const u64 v0 = in0 ? r0 : ~0ull, p0 = (in0 && lane) ? q0 : ~0ull;
+    u64 v1 = ~0ull, p1 = ~0ull;
+    if (k > 64) {
+        const u64 r1 = list[min(lane + 64, k - 1)], q1 = list[min(lane + 63, k - 1)];
+        v1 = in1 ? r1 : ~0ull;
+        p1 = in1 ? q1 : ~0ull;
+    }
+    tk_wave_sync();
+    if (v0 < key) list[lane] = p0 > key ? key : p0;
+    if (v1 < key) list[lane + 64] = p1 > key ? key : p1;
+    tk_wave_sync();
+}
+
+// query / gallery: plane rows `ld` halfs apart, the first K of them multiplied.  ws [Bq][k][slices] keys.
+__global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
+                                                          int Bq, int Bg, int ld, int K, float sc, int k, int slices,
+                                                          u64* __restrict__ ws) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
+    const int QS = K + TK_QPAD;
+    _Float16* qs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][QS]
+    u64* lists = reinterpret_cast<u64*>(tk_smem + (size_t)TK_QROWS * QS * 2);          // [wave][16][k]
+    const int chunks = K >> 3;
+    for (int c = threadIdx.x; c < TK_QROWS * chunks; c += 256) {
+        const int r = c / chunks, cc = c - r * chunks;
+        const int qr = min(q0 + r, Bq - 1);                                           // rows beyond Bq: clamped, results dropped
+        *reinterpret_cast<h8*>(qs + r * QS + cc * 8) = *reinterpret_cast<const h8*>(query + (int64_t)qr * ld + cc * 8);
+    }
+    for (int i = threadIdx.x; i < TK_WAVES * TK_QROWS * k; i += 256) lists[i] = 0;
+    __syncthreads();
+
+    u64* mine = lists + ((size_t)wave * TK_QROWS + l15) * k;                           // this wave's list of query row l15
+    const int tiles = (Bg + 15) >> 4;
+    const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
+    const bool qvalid = q0 + l15 < Bq;
+    const _Float16* qrow = qs + l15 * QS + lg * 8;
+    const int nk2 = K >> 6;                                                            // pairs of k-slices: one 128-byte line per row
+    u64 thr = 0;                                                                       // the k-th key of `mine`
+    int filled = 0;                                                                    // entries any of the wave's lists holds, at most
+    // A batch = TK_BATCH pairs of k-slices of one tile (2 TK_BATCH 16-byte loads a lane).  Two register buffers take turns:
+    // while one batch is multiplied - and, behind a tile's last batch, its survivors are inserted - the next one (the tile's
+    // next, or the first of the wave's next tile) is in flight.  Pairs beyond the row's end are clamped to its last pair
+    // (read again, not multiplied).
+    auto load_batch = [&](h8 (&b)[2 * TK_BATCH], int t, int s0) {
+        const int grow = min(t * 16 + l15, Bg - 1);                                    // rows at Bg or above are never read
+        const _Float16* gp = gallery + (int64_t)grow * ld + lg * 8;
+#pragma unroll
+        for (int u = 0; u < TK_BATCH; ++u) {
+            const int s = min(s0 + u, nk2 - 1);
+            b[2 * u] = *reinterpret_cast<const h8*>(gp + s * 64);
+            b[2 * u + 1] = *reinterpret_cast<const h8*>(gp + s * 64 + 32);
+        }
+    };
+    const int nb = (nk2 + TK_BATCH - 1) / TK_BATCH;                                    // batches of a tile
+    const int my_tiles = t0 + wave < t1 ? (t1 - t0 - wave + TK_WAVES - 1) / TK_WAVES : 0;
+    const int total = my_tiles * nb, t_last = t0 + wave + (my_tiles - 1) * TK_WAVES;
+    int t = t0 + wave, b = 0;                                                          // the batch about to be multiplied
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    auto step = [&](const h8 (&cur)[2 * TK_BATCH], h8 (&nxt)[2 * TK_BATCH]) {
+        // (the request is unconditional - behind the wave's last batch it repeats the last tile's first, a cache hit that
+        // nobody multiplies: under a condition the compiler's wait for `cur` has to cover the path without the request,
+        // and on the other path it then waits for the batch just requested)
+        const bool last = b + 1 == nb;
+        load_batch(nxt, last ? min(t + TK_WAVES, t_last) : t, last ? 0 : (b + 1) * TK_BATCH);
+#pragma unroll
+        for (int u = 0; u < TK_BATCH; ++u) {
+            const int s = b * TK_BATCH + u;
+            if (s < nk2) {
+                const h8 a0 = *reinterpret_cast<const h8*>(qrow + s * 64);
+                const h8 a1 = *reinterpret_cast<const h8*>(qrow + s * 64 + 32);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[2 * u], a0, acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(cur[2 * u + 1], a1, acc, 0, 0, 0);
+            }
+        }
+        if (!last) { ++b; return; }
+        // the lane holds gallery rows t * 16 + 4 lg + r (r = 0..3) of query row l15
+        u64 key[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int id = t * 16 + lg * 4 + r;
+            key[r] = (qvalid && id < Bg) ? tk_key(sc * acc[r], id) : 0;
+        }
+        tk_insert_tile(key, mine, k, lg, thr, filled);
+        acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        t += TK_WAVES;
+        b = 0;
+    };
+    h8 buf0[2 * TK_BATCH], buf1[2 * TK_BATCH];
+    if (total) load_batch(buf0, t, 0);
+    for (int g = 0; g < total; g += 2) {
+        step(buf0, buf1);
+        if (g + 1 < total) step(buf1, buf0);
+    }
+    // the four waves' lists -> wave 0's, as a tree: the other wave's entries are the candidates, 16 a list at a time
+    auto fold = [&](int from) {
+        const u64* other = lists + ((size_t)from * TK_QROWS + l15) * k;
+        u64 th = mine[k - 1];
+        for (int c0 = 0; c0 < k; c0 += 16) {
+            u64 key[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = c0 + lg * 4 + r;
+                key[r] = i < k ? other[i] : 0;
+            }
+            tk_insert_tile(key, mine, k, lg, th, filled);
+        }
+    };
+    __syncthreads();
+    if (wave == 0 || wave == 2) fold(wave + 1);
+    __syncthreads();
+    if (wave == 0) fold(2);
+    __syncthreads();
+    for (int e = threadIdx.x; e < TK_QROWS * k; e += 256) {
+        const int ql = e / k;
+        if (q0 + ql < Bq) ws[((int64_t)(q0 + ql) * k + (e - ql * k)) * slices + slice] = lists[e];     // [query][rank][slice]
+    }
+}
+
+// ws [Bq][k][slices]: rank by rank, the best entry of every slice first.  A rank none of whose entries passes the threshold
+// ends the merge: every list descends, so no deeper entry passes either - for k well below the gallery the result comes from
+// the first few ranks.
+__global__ __launch_bounds__(64) void topk_merge_kernel(const u64* __restrict__ ws, int slices, int k, float* __restrict__ scores,
+                                                        int* __restrict__ ids) {
+    __shared__ u64 list[TK_MAXK];
+    const int q = blockIdx.x, lane = threadIdx.x;
+    for (int i = lane; i < k; i += 64) list[i] = 0;
+    tk_wave_sync();
+    u64 thr = 0;                                                           // list[k - 1]
+    for (int rank = 0; rank < k; ++rank) {
+        const u64* src = ws + ((int64_t)q * k + rank) * slices;
+        bool any = false;
+        for (int i0 = 0; i0 < slices; i0 += 64 * TK_MERGE_BATCH) {
+            u64 c[TK_MERGE_BATCH];
+#pragma unroll
+            for (int u = 0; u < TK_MERGE_BATCH; ++u) {
+                const int i = i0 + u * 64 + lane;
+                c[u] = i < slices ? src[i] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < TK_MERGE_BATCH; ++u) {
+                u64 mask = __ballot(c[u] > thr);
+                any |= mask != 0;
+                while (mask) {                                             // (a survivor of a threshold raised since: no change)
+                    const int from = __builtin_ctzll(mask);
+                    mask &= mask - 1;
+                    const unsigned lo = __builtin_amdgcn_readlane((unsigned)c[u], from);
+                    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(c[u] >> 32), from);
+                    tk_insert(list, k, ((u64)hi << 32) | lo, lane);
+                    thr = list[k - 1];
+                }
+            }
+        }
+        if (!any) break;
+    }
+    for (int i = lane; i < k; i += 64) {
+        float s;
+        int id;
+        tk_decode(list[i], s, id);
+        scores[(int64_t)q * k + i] = s;
+        ids[(int64_t)q * k + i] = id;
+    }
+}
+
+int tk_slices(int Bq, int Bg) {
+    const int groups = (max(Bq, 1) + TK_QROWS - 1) / TK_QROWS, tiles = (max(Bg, 1) + 15) / 16;
+    const int want = (TK_TARGET_WGS + groups - 1) / groups, cap = tiles / TK_MIN_TILES;
+    return max(1, min(want, cap));
+}
+size_t tk_stream_lds(int K, int k) { return (size_t)TK_QROWS * (K + TK_QPAD) * 2 + (size_t)TK_WAVES * TK_QROWS * k * sizeof(u64); }
+
+}  // namespace
+
+extern "C" {
+
+int32_t cc_similarity_topk_slices(int32_t Bq, int32_t Bg, int32_t k) {
+    (void)k;                                    // the split follows the grid alone; k only sizes a list
+    return tk_slices(Bq, Bg);
+}
+
+size_t cc_similarity_topk_workspace_bytes(int32_t Bq, int32_t Bg, int32_t k) {
+    if (Bq <= 0 || Bg <= 0 || k <= 0) return 0;
+    return cc_align_up((size_t)Bq * tk_slices(Bq, Bg) * k * sizeof(u64), 256);
+}
+
+int cc_similarity_topk_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                  float mult, int32_t products, int32_t k, float* scores, int32_t* ids, void* ws,
+                                  size_t ws_bytes, void* stream) {
+    if (!query_planes || !gallery_planes || !scores || !ids || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
+    if (k < 1 || k > TK_MAXK || products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
+    const int K = products * E;
+    const size_t smem = tk_stream_lds(K, k);
+    if (smem > TK_LDS_LIMIT) return CC_ERR_UNSUPPORTED;                   // products * E = 3072 with k = 128 only
+    if ((Bq + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million query rows a call)
+    if (!ws || ws_bytes < cc_similarity_topk_workspace_bytes(Bq, Bg, k)) return CC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int slices = tk_slices(Bq, Bg);
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(topk_stream_kernel), smem) != CC_OK) return CC_ERR_HIP;
+    hipLaunchKernelGGL(topk_stream_kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
+                       static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K,
+                       mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, k, slices, static_cast<u64*>(ws));
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(ws), slices, k, scores, ids);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+}  // extern "C"

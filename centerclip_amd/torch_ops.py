@@ -1168,6 +1168,36 @@ def _(text_planes, video_planes, n_video, mult, products=3):
     return text_planes.new_empty((text_planes.shape[0], n_video), dtype=torch.float32)
 
 
+@custom_op(NS + "::similarity_topk", mutates_args=(), device_types="cuda")
+def similarity_topk(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                    k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The k best of the first n_gallery rows of gallery_planes for every row of query_planes -> (scores [Bq, k] fp32, ids
+    [Bq, k] int64): the first k entries of the stable descending sort of the row scaled_dot_planes gives for the same planes
+    (same bits; equal scores by smaller id; (-inf, -1) beyond n_gallery), without that matrix.  The gallery needs no padding
+    rows.  1 <= k <= 128.  cc_similarity_topk_planes_f32."""
+    Bq, E3 = query_planes.shape
+    if gallery_planes.dim() != 2 or gallery_planes.shape[1] != E3 or gallery_planes.shape[0] < int(n_gallery):
+        raise ValueError("similarity_topk: gallery planes %s do not hold %d rows of %d halfs"
+                         % (tuple(gallery_planes.shape), int(n_gallery), E3))
+    if query_planes.dtype != torch.float16 or gallery_planes.dtype != torch.float16:
+        raise ValueError("similarity_topk: plane rows are fp16")
+    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
+    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
+    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
+    lib = L.lib()
+    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
+    L.check(lib.cc_similarity_topk_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
+                                              float(mult), int(products), int(k), L.ptr(scores), L.ptr(ids), L.ptr(ws),
+                                              ws.numel(), _st(query_planes)), "cc_similarity_topk_planes_f32")
+    return scores, ids.to(torch.int64)
+
+
+@similarity_topk.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, k):
+    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
+            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+
+
 def padded_video_rows(n_video):
     """Rows a video-side plane buffer needs for n_video videos (whole GEMM tiles; the rows behind n_video must be zero)."""
     return int(L.lib().cc_similarity_padded_rows(int(n_video)))
@@ -1422,7 +1452,7 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "loose_similarity", "video_pool_normalize", "normalize_rows", "scaled_dot_nt", "scaled_dot_nt_out", "rank_counts",
        "rank_counts_cols", "rank_counts_ref", "group_max_rows", "normalize_rows_planes", "video_pool_normalize_planes",
        "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
-       "resize_center_crop", "resize_center_crop_out")
+       "resize_center_crop", "resize_center_crop_out", "similarity_topk")
 
 
 def logit_multiplier(logit_scale):

@@ -760,6 +760,29 @@ int cc_scaled_dot_planes_f32(const void* text_planes, const void* video_planes, 
 int cc_scaled_dot_planes_products_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv,
                                       int32_t video_rows, int32_t E, float mult, int32_t products, float* logits,
                                       int32_t ldl, void* stream);
+
+/* Exact top-k search over plane rows (search.hip): for every query row the k best of Bg gallery rows, without the
+ * [Bq, Bg] matrix.  query_planes [Bq, 3E] and gallery_planes [>= Bg, 3E] are plane rows as the two producers above write
+ * them; the first products * E halfs of a query row are multiplied with the first products * E halfs of a gallery row, so
+ * text queries against a video gallery give rows of the matrix S of cc_scaled_dot_planes_products_f32 and video queries
+ * against a text gallery rows of S^T.  Gallery rows at index Bg or above are never read (no tile padding).
+ *   score(q, g) = (mult * 2^-20) * acc, acc ONE fp32 accumulator fed by v_mfma_f32_16x16x32_f16 over the 32-wide k-slices in
+ *   ascending order: the bits cc_scaled_dot_planes_products_f32 stores for the same pair.
+ *   Row q of scores / ids [Bq, k] = the first k entries of the stable descending sort of score(q, 0 .. Bg - 1): larger score
+ *   first, equal scores by smaller id, -0 and +0 equal; entries beyond Bg are (-inf, -1).  Non-finite plane values are
+ *   outside the contract.
+ * Limits: 1 <= k <= 128, products 1..3, E % 64 == 0, E <= 1024, Bq <= 16 * 65535; the one combination the streaming kernel's
+ * LDS cannot hold is products * E == 3072 (E = 1024, products = 3) together with k == 128 - all CC_ERR_UNSUPPORTED.  NULL
+ * operands or Bq, Bg, E <= 0: CC_ERR_INVALID; a NULL or short workspace: CC_ERR_WORKSPACE - every check before anything is
+ * read or launched.  Two launches, no host synchronisation (capturable).  The workspace holds partial lists only -
+ * Bq * cc_similarity_topk_slices * k pairs of 8 bytes; nothing of size Bq * Bg exists.
+ * cc_similarity_topk_slices: the contiguous gallery slices the streaming launch cuts Bg rows into (= partial lists per
+ * query row the merge launch reads); a plan query, no GPU needed, >= 1. */
+int32_t cc_similarity_topk_slices(int32_t Bq, int32_t Bg, int32_t k);
+size_t cc_similarity_topk_workspace_bytes(int32_t Bq, int32_t Bg, int32_t k);
+int cc_similarity_topk_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                  float mult, int32_t products, int32_t k, float* scores, int32_t* ids, void* ws,
+                                  size_t ws_bytes, void* stream);
 int cc_video_pool_normalize_f32(const float* visual, const int64_t* video_mask, int32_t Bv, int32_t Tn,
                                 int32_t E, float* pooled, void* stream);
 int cc_loose_similarity_f32(const float* text, const float* visual, const int64_t* video_mask,
