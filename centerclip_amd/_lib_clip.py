@@ -191,18 +191,12 @@ def declare(lib):
     lib.cc_wgrad_tn_workspace_bytes.argtypes = [i32, i32, i32]
     lib.cc_wgrad_tn_f16.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, i32, vp, vp, sz, vp]
     lib.cc_wgrad_tn_f16.restype = c.c_int
-    lib.cc_bertadam_workspace_bytes.argtypes = []
-    lib.cc_bertadam_workspace_bytes.restype = sz
-    lib.cc_bertadam_multi_f32.argtypes = [vp, i32, f32, f32, f32, f32, vp]
-    lib.cc_bertadam_multi_f32.restype = c.c_int
     lib.cc_bertadam_norm_blocks.argtypes = [i64]
     lib.cc_bertadam_norm_blocks.restype = i32
     lib.cc_bertadam_step_blocks.argtypes = [i64]
     lib.cc_bertadam_step_blocks.restype = i32
-    lib.cc_bertadam_multi_large_f32.argtypes = [vp, i32, i32, i32, f32, f32, f32, f32, vp, sz, vp]
-    lib.cc_bertadam_multi_large_f32.restype = c.c_int
-    lib.cc_bertadam_step_f32.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, sz, vp]
-    lib.cc_bertadam_step_f32.restype = c.c_int
+    lib.cc_bertadam_multi_f32.argtypes = [vp, i32, i32, i32, f32, f32, f32, f32, vp, sz, vp]
+    lib.cc_bertadam_multi_f32.restype = c.c_int
     lib.cc_adamw_blocks.argtypes = [i64]
     lib.cc_adamw_blocks.restype = i32
     lib.cc_adamw_multi_f32.argtypes = [vp, i32, i32, vp, vp, vp]
@@ -221,12 +215,8 @@ def declare(lib):
     lib.cc_adamw_multi_scaled_f32.restype = c.c_int
     lib.cc_grad_scaler_update_f32.argtypes = [vp, vp, vp, f32, f32, i32, vp]
     lib.cc_grad_scaler_update_f32.restype = c.c_int
-    lib.cc_bertadam_step_scaled_f32.argtypes = [vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, vp, vp, sz, vp, vp, vp]
-    lib.cc_bertadam_step_scaled_f32.restype = c.c_int
-    lib.cc_bertadam_multi_scaled_f32.argtypes = [vp, i32, f32, f32, f32, f32, vp, vp, vp]
+    lib.cc_bertadam_multi_scaled_f32.argtypes = [vp, i32, i32, i32, f32, f32, f32, f32, vp, sz, vp, vp, vp]
     lib.cc_bertadam_multi_scaled_f32.restype = c.c_int
-    lib.cc_bertadam_multi_large_scaled_f32.argtypes = [vp, i32, i32, i32, f32, f32, f32, f32, vp, sz, vp, vp, vp]
-    lib.cc_bertadam_multi_large_scaled_f32.restype = c.c_int
     lib.cc_similarity_plane_row_bytes.argtypes = [i32]
     lib.cc_similarity_plane_row_bytes.restype = sz
     lib.cc_similarity_padded_rows.argtypes = [i32]

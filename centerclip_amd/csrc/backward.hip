@@ -853,219 +853,6 @@ inline unsigned grid_for(int64_t n, int per_block) {
 
 }  // namespace
 
-// ---------------------------------------------------------------------------------------------------- BertAdam
-// utils/optimization.py:100-170, one parameter tensor per call: per-tensor gradient clipping (clip_grad_norm_(p, max_grad_norm):
-// g *= max / (||g|| + 1e-6) when that factor is < 1 - the gradient tensor is rescaled in place as the reference does), moments,
-// update = m / (sqrt(v) + e) [+ weight_decay * p], p -= lr_scheduled * update.  Two launches: the sum of squares (a fixed
-// grid, double atomics would make it order dependent: per-block partials reduced in block order by the second kernel), then
-// the elementwise step.  No bias correction - this is the BERT variant.
-constexpr int BA_BLOCKS = 512;
-// SC (the *_scaled_f32 entry points, a step under a device-side loss scale): every gradient is first multiplied by *mult_dev
-// (inv_scale, times the global clip coefficient: cc_grad_scaler_stats_f32) and rounded to fp32 - the value an unscaling pass
-// would have stored - and *found_inf != 0 ends every workgroup before it writes anything (GradScaler.step skipping the step).
-template <bool SC>
-__global__ __launch_bounds__(256) void bertadam_norm_kernel(const float* __restrict__ g, int64_t n, double* __restrict__ partial,
-                                                             const float* __restrict__ mult_dev,
-                                                             const float* __restrict__ found_inf) {
-    if (SC && *found_inf != 0.f) return;
-    const float mult = SC ? *mult_dev : 1.f;
-    double s = 0.0;
-    const int64_t n4 = ((reinterpret_cast<uintptr_t>(g) & 15) == 0) ? (n >> 2) : 0;       // (gradients may be views of a flat bucket)
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
-        float4 v = reinterpret_cast<const float4*>(g)[i];
-        if (SC) { v.x = v.x * mult; v.y = v.y * mult; v.z = v.z * mult; v.w = v.w * mult; }
-        s += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
-    }
-    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const double v = (double)(SC ? g[i] * mult : g[i]);
-        s += v * v;
-    }
-    __shared__ double red[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-template <bool SC>
-__global__ __launch_bounds__(256) void bertadam_step_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                             float* __restrict__ v, int64_t n, const double* __restrict__ partial,
-                                                             int nblocks, float lr, float b1, float b2, float eps, float wd,
-                                                             float max_norm, const float* __restrict__ lr_dev,
-                                                             const float* __restrict__ mult_dev,
-                                                             const float* __restrict__ found_inf) {
-    if (SC && *found_inf != 0.f) return;
-    const float mult = SC ? *mult_dev : 1.f;
-    if (lr_dev) lr = *lr_dev;                                      // (a captured step: the schedule's value arrives through memory)
-    float coef = 1.f;
-    if (max_norm > 0.f) {
-        // the block partials, summed by the first wave in a fixed order (lane l takes l, l + 64, ...; then the wave tree)
-        __shared__ double tot_s;
-        if (threadIdx.x < 64) {
-            double t = 0.0;
-            for (int b = threadIdx.x; b < nblocks; b += 64) t += partial[b];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-            if (threadIdx.x == 0) tot_s = t;
-        }
-        __syncthreads();
-        const float c = max_norm / ((float)sqrt(tot_s) + 1e-6f);
-        coef = c < 1.f ? c : 1.f;
-    }
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        const float gi = (SC ? g[i] * mult : g[i]) * coef;
-        const float mi = m[i] * b1 + (1.f - b1) * gi;
-        const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-        float upd = mi / (sqrtf(vi) + eps);
-        const float pi = p[i];
-        if (wd > 0.f) upd += wd * pi;
-        g[i] = gi; m[i] = mi; v[i] = vi;
-        p[i] = pi - lr * upd;
-    }
-}
-// small tensors (biases, LayerNorm parameters: two thirds of a CLIP model's tensors): norm and step by ONE workgroup
-template <bool SC>
-__device__ __forceinline__ void bertadam_small_body(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int n, float lr, float b1, float b2, float eps, float wd,
-                                                    float max_norm, float mult) {
-    float coef = 1.f;
-    if (max_norm > 0.f) {
-        __shared__ double red[4];
-        double s = 0.0;
-        for (int i = threadIdx.x; i < n; i += 256) { const double x = (double)(SC ? g[i] * mult : g[i]); s += x * x; }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-        __syncthreads();
-        const float c = max_norm / ((float)sqrt((red[0] + red[1]) + (red[2] + red[3])) + 1e-6f);
-        coef = c < 1.f ? c : 1.f;
-    }
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const float gi = (SC ? g[i] * mult : g[i]) * coef;
-        const float mi = m[i] * b1 + (1.f - b1) * gi;
-        const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-        float upd = mi / (sqrtf(vi) + eps);
-        const float pi = p[i];
-        if (wd > 0.f) upd += wd * pi;
-        g[i] = gi; m[i] = mi; v[i] = vi;
-        p[i] = pi - lr * upd;
-    }
-}
-template <bool SC>
-__global__ __launch_bounds__(256) void bertadam_small_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                              float* __restrict__ v, int n, float lr, float b1, float b2, float eps,
-                                                              float wd, float max_norm, const float* __restrict__ lr_dev,
-                                                              const float* __restrict__ mult_dev,
-                                                              const float* __restrict__ found_inf) {
-    if (SC && *found_inf != 0.f) return;
-    if (lr_dev) lr = *lr_dev;
-    bertadam_small_body<SC>(p, g, m, v, n, lr, b1, b2, eps, wd, max_norm, SC ? *mult_dev : 1.f);
-}
-// ... and all of a model's small tensors in one launch: workgroup i takes items[i] (cc_bertadam_item, include/centerclip_hip.h)
-struct BertAdamItem {
-    float* p; float* g; float* m; float* v;
-    const float* lr_dev;
-    int32_t n;
-    float lr, wd;
-    int32_t pad_;
-};
-static_assert(sizeof(BertAdamItem) == 56, "cc_bertadam_item layout");
-// ... and all LARGE tensors in two launches (cc_bertadam_multi_large_f32): the workgroups of every tensor's norm pass, then the
-// workgroups of every tensor's step, each finding its tensor by bisection over the records' first-block numbers.  A tensor's
-// workgroups see the block count and block id cc_bertadam_step_f32 would give them, so its arithmetic and bits are the same.
-struct BertAdamBigItem {
-    float* p; float* g; float* m; float* v;
-    const float* lr_dev;
-    int64_t n;
-    float lr, wd;
-    int32_t norm_blk0, norm_blocks, step_blk0, step_blocks;
-};
-static_assert(sizeof(BertAdamBigItem) == 72, "cc_bertadam_big_item layout");
-template <bool STEP>
-__device__ __forceinline__ int bertadam_find(const BertAdamBigItem* __restrict__ items, int count, int blk) {
-    int lo = 0, hi = count - 1;                                   // last item whose first block <= blk
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((STEP ? items[mid].step_blk0 : items[mid].norm_blk0) <= blk) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-template <bool SC>
-__global__ __launch_bounds__(256) void bertadam_multi_norm_kernel(const BertAdamBigItem* __restrict__ items, int count,
-                                                                   double* __restrict__ partial,
-                                                                   const float* __restrict__ mult_dev,
-                                                                   const float* __restrict__ found_inf) {
-    if (SC && *found_inf != 0.f) return;
-    const float mult = SC ? *mult_dev : 1.f;
-    const int ii = bertadam_find<false>(items, count, blockIdx.x);
-    const float* __restrict__ g = items[ii].g;
-    const int64_t n = items[ii].n;
-    const int64_t bid = (int)blockIdx.x - items[ii].norm_blk0, nblk = items[ii].norm_blocks;
-    double s = 0.0;
-    const int64_t n4 = ((reinterpret_cast<uintptr_t>(g) & 15) == 0) ? (n >> 2) : 0;
-    for (int64_t i = bid * 256 + threadIdx.x; i < n4; i += nblk * 256) {
-        float4 v = reinterpret_cast<const float4*>(g)[i];
-        if (SC) { v.x = v.x * mult; v.y = v.y * mult; v.z = v.z * mult; v.w = v.w * mult; }
-        s += ((double)v.x * v.x + (double)v.y * v.y) + ((double)v.z * v.z + (double)v.w * v.w);
-    }
-    for (int64_t i = (n4 << 2) + bid * 256 + threadIdx.x; i < n; i += nblk * 256) {
-        const double v = (double)(SC ? g[i] * mult : g[i]);
-        s += v * v;
-    }
-    __shared__ double red[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
-}
-template <bool SC>
-__global__ __launch_bounds__(256) void bertadam_multi_step_kernel(const BertAdamBigItem* __restrict__ items, int count,
-                                                                   const double* __restrict__ partial, float b1, float b2, float eps,
-                                                                   float max_norm, const float* __restrict__ mult_dev,
-                                                                   const float* __restrict__ found_inf) {
-    if (SC && *found_inf != 0.f) return;
-    const float mult = SC ? *mult_dev : 1.f;
-    const int ii = bertadam_find<true>(items, count, blockIdx.x);
-    const BertAdamBigItem it = items[ii];
-    const float lr = it.lr_dev ? *it.lr_dev : it.lr;
-    float coef = 1.f;
-    if (max_norm > 0.f) {
-        __shared__ double tot_s;
-        if (threadIdx.x < 64) {
-            double t = 0.0;
-            for (int b = threadIdx.x; b < it.norm_blocks; b += 64) t += partial[it.norm_blk0 + b];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-            if (threadIdx.x == 0) tot_s = t;
-        }
-        __syncthreads();
-        const float c = max_norm / ((float)sqrt(tot_s) + 1e-6f);
-        coef = c < 1.f ? c : 1.f;
-    }
-    float* __restrict__ p = it.p; float* __restrict__ g = it.g; float* __restrict__ m = it.m; float* __restrict__ v = it.v;
-    const int64_t bid = (int)blockIdx.x - it.step_blk0;
-    for (int64_t i = bid * 256 + threadIdx.x; i < it.n; i += (int64_t)it.step_blocks * 256) {
-        const float gi = (SC ? g[i] * mult : g[i]) * coef;
-        const float mi = m[i] * b1 + (1.f - b1) * gi;
-        const float vi = v[i] * b2 + (1.f - b2) * gi * gi;
-        float upd = mi / (sqrtf(vi) + eps);
-        const float pi = p[i];
-        if (it.wd > 0.f) upd += it.wd * pi;
-        g[i] = gi; m[i] = mi; v[i] = vi;
-        p[i] = pi - lr * upd;
-    }
-}
-template <bool SC>
-__global__ __launch_bounds__(256) void bertadam_multi_small_kernel(const BertAdamItem* __restrict__ items, float b1, float b2, float eps,
-                                                                    float max_norm, const float* __restrict__ mult_dev,
-                                                                    const float* __restrict__ found_inf) {
-    if (SC && *found_inf != 0.f) return;
-    const BertAdamItem it = items[blockIdx.x];
-    bertadam_small_body<SC>(it.p, it.g, it.m, it.v, it.n, it.lr_dev ? *it.lr_dev : it.lr, b1, b2, eps, it.wd, max_norm,
-                            SC ? *mult_dev : 1.f);
-}
-
 template <int NK64>
 static int launch_attention_backward_long(const _Float16* qkv, const float* d_out, float* d_qkv, float* stats, int nseq, int L, int heads,
                                           int W, int causal, unsigned* amax, hipStream_t st) {
@@ -1201,114 +988,6 @@ int cc_unscale_f32(float* x, int64_t n, const float* scale_a, const float* scale
                        scale_b);
     CC_LAUNCH_CHECK();
     return CC_OK;
-}
-
-size_t cc_bertadam_workspace_bytes(void) { return BA_BLOCKS * sizeof(double); }
-
-/* One BertAdam step on one parameter tensor (utils/optimization.py:100-170; all tensors fp32, n elements): grad is clipped in
- * place to max_grad_norm (<= 0: no clipping), next_m / next_v updated, param -= lr_scheduled * (m / (sqrt(v) + e) + wd * param).
- * lr_scheduled = lr * schedule(step / t_total, warmup) is the caller's (host arithmetic, centerclip_amd.train.BertAdam);
- * lr_dev != null: read from that device float instead (a step captured into a hipGraph is replayed with new values). */
-extern "C++" {
-template <bool SC>
-static int bertadam_step_launch(float* param, float* grad, float* next_m, float* next_v, int64_t n, float lr_scheduled, float b1,
-                                float b2, float e, float weight_decay, float max_grad_norm, const float* lr_dev, void* ws,
-                                size_t ws_bytes, const float* mult_dev, const float* found_inf_dev, void* stream) {
-    if (!param || !grad || !next_m || !next_v || n <= 0) return CC_ERR_INVALID;
-    if (SC && (!mult_dev || !found_inf_dev)) return CC_ERR_INVALID;
-    if (!ws || ws_bytes < cc_bertadam_workspace_bytes()) return CC_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (n <= 8192) {
-        hipLaunchKernelGGL(bertadam_small_kernel<SC>, dim3(1), dim3(256), 0, st, param, grad, next_m, next_v, (int)n, lr_scheduled, b1,
-                           b2, e, weight_decay, max_grad_norm, lr_dev, mult_dev, found_inf_dev);
-        CC_LAUNCH_CHECK();
-        return CC_OK;
-    }
-    double* partial = static_cast<double*>(ws);
-    const int nb = (int)((n + 1023) / 1024 < BA_BLOCKS ? (n + 1023) / 1024 : BA_BLOCKS);
-    if (max_grad_norm > 0.f)
-        hipLaunchKernelGGL(bertadam_norm_kernel<SC>, dim3(nb), dim3(256), 0, st, grad, n, partial, mult_dev, found_inf_dev);
-    hipLaunchKernelGGL(bertadam_step_kernel<SC>, dim3(grid_for(n, 1024)), dim3(256), 0, st, param, grad, next_m, next_v, n, partial, nb,
-                       lr_scheduled, b1, b2, e, weight_decay, max_grad_norm, lr_dev, mult_dev, found_inf_dev);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-}
-}  // extern "C++"
-
-int cc_bertadam_step_f32(float* param, float* grad, float* next_m, float* next_v, int64_t n, float lr_scheduled, float b1,
-                         float b2, float e, float weight_decay, float max_grad_norm, const float* lr_dev, void* ws, size_t ws_bytes,
-                         void* stream) {
-    return bertadam_step_launch<false>(param, grad, next_m, next_v, n, lr_scheduled, b1, b2, e, weight_decay, max_grad_norm, lr_dev,
-                                       ws, ws_bytes, nullptr, nullptr, stream);
-}
-
-/* The three BertAdam launches under a device-side loss scale (cc_grad_scaler_stats_f32 wrote both words): the gradients are
- * multiplied by *mult_dev as they are loaded - bit for bit the unscaled entry point on gradients that had been multiplied by it
- * first - and *found_inf_dev != 0 makes every launch a no-op: parameters, moments and gradients keep their bits. */
-int cc_bertadam_step_scaled_f32(float* param, float* grad, float* next_m, float* next_v, int64_t n, float lr_scheduled, float b1,
-                                float b2, float e, float weight_decay, float max_grad_norm, const float* lr_dev, void* ws,
-                                size_t ws_bytes, const float* mult_dev, const float* found_inf_dev, void* stream) {
-    return bertadam_step_launch<true>(param, grad, next_m, next_v, n, lr_scheduled, b1, b2, e, weight_decay, max_grad_norm, lr_dev,
-                                      ws, ws_bytes, mult_dev, found_inf_dev, stream);
-}
-
-/* BertAdam steps of `count` small tensors (n <= CC_BERTADAM_MULTI_MAX_N each) in one launch: items_dev = count cc_bertadam_item
- * records in device memory (include/centerclip_hip.h); per tensor the arithmetic - and the bits - of cc_bertadam_step_f32. */
-int cc_bertadam_multi_f32(const void* items_dev, int32_t count, float b1, float b2, float e, float max_grad_norm, void* stream) {
-    if (!items_dev || count <= 0) return CC_ERR_INVALID;
-    const float* none = nullptr;
-    hipLaunchKernelGGL(bertadam_multi_small_kernel<false>, dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const BertAdamItem*>(items_dev), b1, b2, e, max_grad_norm, none, none);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-}
-
-int cc_bertadam_multi_scaled_f32(const void* items_dev, int32_t count, float b1, float b2, float e, float max_grad_norm,
-                                 const float* mult_dev, const float* found_inf_dev, void* stream) {
-    if (!items_dev || !mult_dev || !found_inf_dev || count <= 0) return CC_ERR_INVALID;
-    hipLaunchKernelGGL(bertadam_multi_small_kernel<true>, dim3(count), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const BertAdamItem*>(items_dev), b1, b2, e, max_grad_norm, mult_dev, found_inf_dev);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-}
-
-/* The same for `count` LARGE tensors (any n) in TWO launches: items_dev = count cc_bertadam_big_item records in device memory,
- * ordered, with norm_blk0 / step_blk0 = the running sums of norm_blocks / step_blocks = cc_bertadam_norm_blocks(n) /
- * cc_bertadam_step_blocks(n); ws >= total_norm_blocks doubles.  Per tensor the arithmetic and the bits of cc_bertadam_step_f32. */
-int32_t cc_bertadam_norm_blocks(int64_t n) { return n <= 0 ? 0 : (int32_t)((n + 1023) / 1024 < BA_BLOCKS ? (n + 1023) / 1024 : BA_BLOCKS); }
-int32_t cc_bertadam_step_blocks(int64_t n) { return n <= 0 ? 0 : (int32_t)grid_for(n, 1024); }
-extern "C++" {
-template <bool SC>
-static int bertadam_multi_large_launch(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks,
-                                       float b1, float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes,
-                                       const float* mult_dev, const float* found_inf_dev, void* stream) {
-    if (!items_dev || count <= 0 || total_norm_blocks <= 0 || total_step_blocks <= 0) return CC_ERR_INVALID;
-    if (SC && (!mult_dev || !found_inf_dev)) return CC_ERR_INVALID;
-    if (!ws || ws_bytes < (size_t)total_norm_blocks * sizeof(double)) return CC_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const BertAdamBigItem* items = static_cast<const BertAdamBigItem*>(items_dev);
-    double* partial = static_cast<double*>(ws);
-    if (max_grad_norm > 0.f)
-        hipLaunchKernelGGL(bertadam_multi_norm_kernel<SC>, dim3(total_norm_blocks), dim3(256), 0, st, items, count, partial, mult_dev,
-                           found_inf_dev);
-    hipLaunchKernelGGL(bertadam_multi_step_kernel<SC>, dim3(total_step_blocks), dim3(256), 0, st, items, count, partial, b1, b2, e,
-                       max_grad_norm, mult_dev, found_inf_dev);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
-}
-}  // extern "C++"
-
-int cc_bertadam_multi_large_f32(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks, float b1,
-                                float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes, void* stream) {
-    return bertadam_multi_large_launch<false>(items_dev, count, total_norm_blocks, total_step_blocks, b1, b2, e, max_grad_norm, ws,
-                                              ws_bytes, nullptr, nullptr, stream);
-}
-
-int cc_bertadam_multi_large_scaled_f32(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks,
-                                       float b1, float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes,
-                                       const float* mult_dev, const float* found_inf_dev, void* stream) {
-    return bertadam_multi_large_launch<true>(items_dev, count, total_norm_blocks, total_step_blocks, b1, b2, e, max_grad_norm, ws,
-                                             ws_bytes, mult_dev, found_inf_dev, stream);
 }
 
 /* fp16 operand copies of a matrix for the backward of a Linear: `in` fp32 [rows, cols] (or in_f16, already fp16) ->

@@ -1,6 +1,7 @@
 """The optimizers of main.py:161-175 on the HIP kernels, and what surrounds them:
 
-* ``BertAdam`` (utils/optimization.py:55-170) with its warmup schedules, on cc_bertadam_*_f32;
+* ``BertAdam`` (utils/optimization.py:55-170) with its warmup schedules, on the multi-tensor kernels of csrc/bertadam.hip:
+  one record per tensor (cc_bertadam_item), every tensor of a step in one launch pair;
 * ``AdamW`` and ``clip_grad_norm_`` (torch.optim.AdamW, torch.nn.utils.clip_grad_norm_; main.py:168-175, 316-333) on the
   multi-tensor kernels of csrc/adamw.hip: one record per tensor (cc_adamw_item), every tensor of a step in one launch;
 * ``lr_scheduler`` (utils/lr_scheduler.py) and ``prep_optim_params_groups`` (utils/optimization.py:173-222): host arithmetic.
@@ -15,10 +16,6 @@ import torch
 
 from .. import _lib as L
 from ..torch_ops import _st
-
-
-def _check(rc, what):
-    L.check(rc, what)
 
 
 
@@ -190,11 +187,37 @@ def _grads_table(grads):
     return _adamw_table([(g, g, None, None, 0) for g in grads])
 
 
+_BERTADAM_ITEM = np.dtype([('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('lr_dev', '<u8'), ('n', '<i8'),
+                           ('lr', '<f4'), ('wd', '<f4'), ('norm_blk0', '<i4'), ('norm_blocks', '<i4'), ('step_blk0', '<i4'),
+                           ('step_blocks', '<i4')])
+_bertadam_blocks_cache = {}
+
+
+def _bertadam_table(entries):
+    """entries: (param, grad, next_m, next_v, lr, weight decay), lr a float or a 1-element device tensor (a record's lr or
+    its lr_dev) -> (cc_bertadam_item records as bytes, count, total norm blocks, total step blocks).  Empty tensors get no
+    record."""
+    lib = L.lib()
+    entries = [e for e in entries if e[0].numel() > 0]
+    rec = np.zeros(len(entries), dtype=_BERTADAM_ITEM)
+    nb0 = sb0 = 0
+    for i, (p, g, m, v, lr, wd) in enumerate(entries):
+        n = p.numel()
+        blocks = _bertadam_blocks_cache.get(n)
+        if blocks is None:
+            blocks = _bertadam_blocks_cache[n] = (int(lib.cc_bertadam_norm_blocks(n)), int(lib.cc_bertadam_step_blocks(n)))
+        lr_dev, lr = (lr.data_ptr(), 0.0) if torch.is_tensor(lr) else (0, lr)
+        rec[i] = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), lr_dev, n, lr, wd, nb0, blocks[0], sb0, blocks[1])
+        nb0 += blocks[0]
+        sb0 += blocks[1]
+    return rec.tobytes(), len(entries), nb0, sb0
+
+
 def _norm_partials(table, count, nblk, device, st):
     """cc_grad_norm_partials_f32 over the table's gradients -> the workspace that holds the nblk partial sums."""
     lib = L.lib()
     ws = L.workspace(lib.cc_grad_norm_workspace_bytes(nblk), device)
-    _check(lib.cc_grad_norm_partials_f32(L.ptr(table), count, nblk, L.ptr(ws), ws.numel(), st), "cc_grad_norm_partials_f32")
+    L.check(lib.cc_grad_norm_partials_f32(L.ptr(table), count, nblk, L.ptr(ws), ws.numel(), st), "cc_grad_norm_partials_f32")
     return ws
 
 
@@ -205,9 +228,9 @@ def _clip_launches(table, count, nblk, max_norm, device, coef_only=False):
     out = torch.empty(2, dtype=torch.float32, device=device)
     st = _st(out)
     ws = _norm_partials(table, count, nblk, device, st)
-    _check(lib.cc_grad_clip_coef_f32(L.ptr(ws), nblk, float(max_norm), L.ptr(out), st), "cc_grad_clip_coef_f32")
+    L.check(lib.cc_grad_clip_coef_f32(L.ptr(ws), nblk, float(max_norm), L.ptr(out), st), "cc_grad_clip_coef_f32")
     if not coef_only:
-        _check(lib.cc_grad_scale_f32(L.ptr(table), count, nblk, L.ptr(out[1:]), st), "cc_grad_scale_f32")
+        L.check(lib.cc_grad_scale_f32(L.ptr(table), count, nblk, L.ptr(out[1:]), st), "cc_grad_scale_f32")
     return out
 
 
@@ -242,7 +265,8 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0):
 class BertAdam(_Optimizer):
     """utils/optimization.py:55-170 (the optimizer main.py:161-167 builds): same constructor, same state names
     ('step', 'next_m', 'next_v'), same per-tensor clipping / decoupled weight decay / schedule; the tensor arithmetic of a
-    step is one cc_bertadam_step_f32 call per parameter (no host synchronisation)."""
+    step is one cc_bertadam_multi_f32 call (a norm and a step launch over one record per tensor, csrc/bertadam.hip) per
+    (b1, b2, e, max_grad_norm) class, no host synchronisation."""
 
     def __init__(self, params, lr, warmup=-1, t_total=-1, schedule='warmup_linear', b1=0.9, b2=0.999, e=1e-6,
                  weight_decay=0.01, max_grad_norm=1.0, capturable=False):
@@ -290,54 +314,6 @@ class BertAdam(_Optimizer):
                 lr.append(self._lr(group, state['step']))
         return lr
 
-    _MULTI_MAX_N = 8192                     # CC_BERTADAM_MULTI_MAX_N (include/centerclip_hip.h)
-    _ITEM = [('p', '<u8'), ('g', '<u8'), ('m', '<u8'), ('v', '<u8'), ('lr_dev', '<u8')]
-    _SMALL_ITEM = np.dtype(_ITEM + [('n', '<i4'), ('lr', '<f4'), ('wd', '<f4'), ('pad', '<i4')])                 # cc_bertadam_item
-    _LARGE_ITEM = np.dtype(_ITEM + [('n', '<i8'), ('lr', '<f4'), ('wd', '<f4'), ('nb0', '<i4'), ('nb', '<i4'),   # cc_bertadam_big_item
-                                    ('sb0', '<i4'), ('sb', '<i4')])
-
-    def _multi_small(self, items, hyper, capturing, device, sc):
-        """All small tensors of groups with the same (b1, b2, e, max_grad_norm) in ONE launch (cc_bertadam_multi_f32): the
-        records (cc_bertadam_item: four tensor pointers, the group's device learning rate, n, weight decay) are staged through
-        pinned memory and re-sent only when a pointer changed (_Staged)."""
-        rec = np.zeros(len(items), dtype=self._SMALL_ITEM)
-        for i, (p, grad, m, v, lr_dev, wd) in enumerate(items):
-            rec[i] = (p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), lr_dev.data_ptr(), p.numel(), 0.0, wd, 0)
-        dev = self._table(hyper, rec.tobytes(), device, capturing)
-        b1, b2, e, max_norm = hyper
-        if sc is not None:
-            _check(L.lib().cc_bertadam_multi_scaled_f32(L.ptr(dev), len(items), b1, b2, e, max_norm, L.ptr(sc[0]), L.ptr(sc[1]),
-                                                        _st(dev)), "cc_bertadam_multi_scaled_f32")
-            return
-        _check(L.lib().cc_bertadam_multi_f32(L.ptr(dev), len(items), b1, b2, e, max_norm, _st(dev)), "cc_bertadam_multi_f32")
-
-    def _multi_large(self, items, hyper, capturing, device, sc):
-        """All large tensors of groups with the same (b1, b2, e, max_grad_norm) in TWO launches (cc_bertadam_multi_large_f32:
-        every tensor's norm workgroups, then every tensor's step workgroups) instead of two per tensor - ~100 tensors of a
-        ViT-B/32 CLIP: 204 launches -> 2.  Records (cc_bertadam_big_item) staged like the small tensors'."""
-        lib = L.lib()
-        rec = np.zeros(len(items), dtype=self._LARGE_ITEM)
-        nb0 = sb0 = 0
-        for i, (p, grad, m, v, lr_dev, wd) in enumerate(items):
-            nb, sb = int(lib.cc_bertadam_norm_blocks(p.numel())), int(lib.cc_bertadam_step_blocks(p.numel()))
-            rec[i] = (p.data_ptr(), grad.data_ptr(), m.data_ptr(), v.data_ptr(), lr_dev.data_ptr(), p.numel(), 0.0, wd, nb0, nb, sb0, sb)
-            nb0 += nb
-            sb0 += sb
-        part = self._partial.get(hyper)
-        if part is None or part.numel() < nb0:
-            if capturing:
-                raise RuntimeError("BertAdam: run one eager step with the same parameters before capturing (partial sums)")
-            part = self._partial[hyper] = torch.empty(nb0, dtype=torch.float64, device=device)
-        dev = self._table((hyper, "large"), rec.tobytes(), device, capturing)
-        b1, b2, e, max_norm = hyper
-        if sc is not None:
-            _check(lib.cc_bertadam_multi_large_scaled_f32(L.ptr(dev), len(items), nb0, sb0, b1, b2, e, max_norm, L.ptr(part),
-                                                          part.numel() * 8, L.ptr(sc[0]), L.ptr(sc[1]), _st(dev)),
-                   "cc_bertadam_multi_large_scaled_f32")
-            return
-        _check(lib.cc_bertadam_multi_large_f32(L.ptr(dev), len(items), nb0, sb0, b1, b2, e, max_norm, L.ptr(part),
-                                               part.numel() * 8, _st(dev)), "cc_bertadam_multi_large_f32")
-
     @torch.no_grad()
     def step(self, closure=None):
         loss = closure() if closure is not None else None
@@ -345,11 +321,15 @@ class BertAdam(_Optimizer):
         return loss
 
     def _step(self, sc):
-        """One step over the parameters that have a gradient.  ``sc``: None, or the (multiplier, found_inf) device floats of
-        DeviceGradScaler.step - the *_scaled_f32 launches."""
+        """One step over the parameters that have a gradient: per (b1, b2, e, max_grad_norm) class one record table and one
+        cc_bertadam_multi_f32 call.  ``sc``: None, or the (multiplier, found_inf) device floats of DeviceGradScaler.step -
+        cc_bertadam_multi_scaled_f32.  The learning rate: capturable, the group's device float; otherwise each record holds
+        its parameter's own scheduled value."""
         lib = L.lib()
-        capturing = self.capturable and torch.cuda.is_current_stream_capturing()
-        small, large = {}, {}                                     # (b1, b2, e, max_grad_norm) -> records of the small / large tensors
+        capturing = _capturing()
+        if capturing and not self.capturable:
+            raise RuntimeError("BertAdam: build it with capturable=True to capture its step")
+        classes = {}                                              # (b1, b2, e, max_grad_norm) -> _bertadam_table entries
         if not capturing:
             self._last = []
         for gi, group in enumerate(self.param_groups):
@@ -360,45 +340,45 @@ class BertAdam(_Optimizer):
                 if p.dtype != torch.float32 or not p.is_contiguous():
                     raise RuntimeError("BertAdam (HIP): fp32 contiguous parameters (the master weights)")
                 L.require_device(p)
-                grad = p.grad if (p.grad.dtype == torch.float32 and p.grad.is_contiguous()) else None
-                if grad is None:
+                if p.grad.dtype != torch.float32 or not p.grad.is_contiguous():
                     p.grad = p.grad.float().contiguous()
-                    grad = p.grad
                 state = self.state[p]
                 if len(state) == 0:
                     state['step'] = 0
                     state['next_m'] = torch.zeros_like(p)
                     state['next_v'] = torch.zeros_like(p)
-                ws = L.workspace(lib.cc_bertadam_workspace_bytes(), p.device)
-                lr_dev = None
                 if self.capturable:
-                    lr_dev = self._lr_dev.get(gi)
-                    if lr_dev is None or lr_dev.device != p.device:
-                        lr_dev = self._lr_dev[gi] = torch.zeros(1, device=p.device, dtype=torch.float32)
+                    lr = self._lr_dev.get(gi)
+                    if lr is None or lr.device != p.device:
+                        lr = self._lr_dev[gi] = torch.zeros(1, device=p.device, dtype=torch.float32)
                     if not capturing and not lr_set:
-                        lr_dev.fill_(float(self._lr(group, state['step'])))
+                        lr.fill_(float(self._lr(group, state['step'])))
                         lr_set = True
-                    hyper = (float(group['b1']), float(group['b2']), float(group['e']), float(group['max_grad_norm']))
-                    (small if p.numel() <= self._MULTI_MAX_N else large).setdefault(hyper, []).append(
-                        (p, grad, state['next_m'], state['next_v'], lr_dev, float(group['weight_decay'])))
-                elif sc is not None:
-                    _check(lib.cc_bertadam_step_scaled_f32(L.ptr(p), L.ptr(grad), L.ptr(state['next_m']), L.ptr(state['next_v']),
-                                                           p.numel(), float(self._lr(group, state['step'])), float(group['b1']),
-                                                           float(group['b2']), float(group['e']), float(group['weight_decay']),
-                                                           float(group['max_grad_norm']), L.ptr(lr_dev), L.ptr(ws), ws.numel(),
-                                                           L.ptr(sc[0]), L.ptr(sc[1]), _st(p)), "cc_bertadam_step_scaled_f32")
                 else:
-                    _check(lib.cc_bertadam_step_f32(L.ptr(p), L.ptr(grad), L.ptr(state['next_m']), L.ptr(state['next_v']), p.numel(),
-                                                    float(self._lr(group, state['step'])), float(group['b1']), float(group['b2']),
-                                                    float(group['e']), float(group['weight_decay']), float(group['max_grad_norm']),
-                                                    L.ptr(lr_dev), L.ptr(ws), ws.numel(), _st(p)), "cc_bertadam_step_f32")
+                    lr = float(self._lr(group, state['step']))
+                hyper = (float(group['b1']), float(group['b2']), float(group['e']), float(group['max_grad_norm']))
+                classes.setdefault(hyper, []).append((p, p.grad, state['next_m'], state['next_v'], lr,
+                                                      float(group['weight_decay'])))
                 if not capturing:
                     state['step'] += 1
                     self._last.append(p)
-        for hyper, items in small.items():
-            self._multi_small(items, hyper, capturing, items[0][0].device, sc)
-        for hyper, items in large.items():
-            self._multi_large(items, hyper, capturing, items[0][0].device, sc)
+        for hyper, entries in classes.items():
+            raw, count, nb, sb = _bertadam_table(entries)
+            if count == 0:
+                continue
+            device = entries[0][0].device
+            part = self._partial.get(hyper)
+            if nb and (part is None or part.numel() < nb):
+                if capturing:
+                    raise RuntimeError("BertAdam: run one eager step with the same parameters before capturing (partial sums)")
+                part = self._partial[hyper] = torch.empty(nb, dtype=torch.float64, device=device)
+            table = self._table(hyper, raw, device, capturing)
+            args = (L.ptr(table), count, nb, sb) + hyper + (L.ptr(part), 0 if part is None else part.numel() * 8)
+            if sc is not None:
+                L.check(lib.cc_bertadam_multi_scaled_f32(*args, L.ptr(sc[0]), L.ptr(sc[1]), _st(table)),
+                        "cc_bertadam_multi_scaled_f32")
+            else:
+                L.check(lib.cc_bertadam_multi_f32(*args, _st(table)), "cc_bertadam_multi_f32")
 
     @torch.no_grad()
     def _scaled_step(self, scaler, max_norm):
@@ -475,13 +455,6 @@ class AdamW(_Optimizer):
 
     def _pinned(self):
         return self._cap['params'] if self._cap is not None else ()
-
-    def load_state_dict(self, state_dict):
-        """Also takes torch.optim.AdamW's state (a tensor-valued 'step', its extra group keys)."""
-        super().load_state_dict(state_dict)
-        for st in self.state.values():
-            if torch.is_tensor(st.get('step')):
-                st['step'] = int(st['step'].item())
 
     @staticmethod
     def _scalars(group, t):
@@ -564,7 +537,7 @@ class AdamW(_Optimizer):
         prep = self._prepare()
         if prep is not None:
             dev, table, count, nblk, scal = prep
-            _check(L.lib().cc_adamw_multi_f32(L.ptr(table), count, nblk, L.ptr(scal), None, _st(scal)), "cc_adamw_multi_f32")
+            L.check(L.lib().cc_adamw_multi_f32(L.ptr(table), count, nblk, L.ptr(scal), None, _st(scal)), "cc_adamw_multi_f32")
         return loss
 
     @torch.no_grad()
@@ -578,8 +551,8 @@ class AdamW(_Optimizer):
             return torch.tensor(0.0)
         dev, table, count, nblk, scal = prep
         out = _clip_launches(table, count, nblk, max_norm, dev, coef_only=True)
-        _check(L.lib().cc_adamw_multi_f32(L.ptr(table), count, nblk, L.ptr(scal), L.ptr(out[1:]), _st(scal)),
-               "cc_adamw_multi_f32")
+        L.check(L.lib().cc_adamw_multi_f32(L.ptr(table), count, nblk, L.ptr(scal), L.ptr(out[1:]), _st(scal)),
+                "cc_adamw_multi_f32")
         return out[0]
 
     @torch.no_grad()
@@ -592,8 +565,8 @@ class AdamW(_Optimizer):
             return False
         dev, table, count, nblk, scal = prep
         mult, found = scaler._stats(table, count, nblk, max_norm, dev)
-        _check(L.lib().cc_adamw_multi_scaled_f32(L.ptr(table), count, nblk, L.ptr(scal), L.ptr(mult), L.ptr(found), _st(scal)),
-               "cc_adamw_multi_scaled_f32")
+        L.check(L.lib().cc_adamw_multi_scaled_f32(L.ptr(table), count, nblk, L.ptr(scal), L.ptr(mult), L.ptr(found), _st(scal)),
+                "cc_adamw_multi_scaled_f32")
         return True
 
     def refresh_lr(self):

@@ -6,7 +6,7 @@ import torch
 
 from .. import _lib as L
 from ..torch_ops import _st
-from .optim import AdamW, BertAdam, _capturing, _check, _norm_partials
+from .optim import AdamW, BertAdam, _capturing, _norm_partials
 
 
 class DeviceGradScaler:
@@ -184,8 +184,8 @@ class DeviceGradScaler:
         self._ensure(device)
         st = _st(self._f)
         ws = _norm_partials(table, count, nblk, self._f.device, st)
-        _check(L.lib().cc_grad_scaler_stats_f32(L.ptr(ws), nblk, L.ptr(self._f[1:2]), float(max_norm), L.ptr(self._f[2:5]), st),
-               "cc_grad_scaler_stats_f32")
+        L.check(L.lib().cc_grad_scaler_stats_f32(L.ptr(ws), nblk, L.ptr(self._f[1:2]), float(max_norm), L.ptr(self._f[2:5]), st),
+                "cc_grad_scaler_stats_f32")
         return self._f[3:4], self._f[4:5]
 
     def grad_norm(self):
@@ -250,9 +250,9 @@ class DeviceGradScaler:
         else:
             if not self._stepped:
                 raise RuntimeError("No inf checks were recorded prior to update.")
-            _check(L.lib().cc_grad_scaler_update_f32(L.ptr(self._f[0:2]), L.ptr(self._f[4:5]), L.ptr(self._c), self._growth_factor,
-                                                     self._backoff_factor, self._growth_interval, _st(self._f)),
-                   "cc_grad_scaler_update_f32")
+            L.check(L.lib().cc_grad_scaler_update_f32(L.ptr(self._f[0:2]), L.ptr(self._f[4:5]), L.ptr(self._c),
+                                                      self._growth_factor, self._backoff_factor, self._growth_interval,
+                                                      _st(self._f)), "cc_grad_scaler_update_f32")
         self._stepped = False
         self._unscaled.clear()
         self._max_norm.clear()

@@ -984,58 +984,41 @@ size_t cc_wgrad_tn_workspace_bytes(int32_t M, int32_t N1, int32_t N2);
 int cc_wgrad_tn_f16(const void* dy_f16, const void* x_f16, float* dw, int32_t M, int32_t N1, int32_t N2,
                     const float* scale_dev, const float* col_partial, int32_t col_chunks, float* bias_grad, void* ws,
                     size_t ws_bytes, void* stream);
-/* One BertAdam step on one parameter tensor (utils/optimization.py:100-170: the optimizer main.py:161-167 builds): grad is
- * clipped in place to max_grad_norm (clip_grad_norm_ on the single tensor; <= 0: no clipping), next_m = b1 m + (1-b1) g,
- * next_v = b2 v + (1-b2) g^2, param -= lr_scheduled * (next_m / (sqrt(next_v) + e) + weight_decay * param); no bias correction.
- * lr_scheduled = lr * schedule(step / t_total, warmup) is host arithmetic (centerclip_amd.train.BertAdam).  All tensors fp32. */
-size_t cc_bertadam_workspace_bytes(void);
-/* (lr_dev, may be null: the scheduled learning rate read from a device float instead of lr_scheduled - a training step captured
- * into a hipGraph is replayed with the schedule's new value written there first) */
-int cc_bertadam_step_f32(float* param, float* grad, float* next_m, float* next_v, int64_t n, float lr_scheduled, float b1,
-                         float b2, float e, float weight_decay, float max_grad_norm, const float* lr_dev, void* ws, size_t ws_bytes,
-                         void* stream);
-/* All of a model's small tensors (biases, LayerNorm weights: n <= CC_BERTADAM_MULTI_MAX_N, the size up to which
- * cc_bertadam_step_f32 itself uses one workgroup) in ONE launch: items_dev = `count` records below in device memory, one
- * workgroup each; per tensor the arithmetic and the bits of cc_bertadam_step_f32 (lr_dev != null: the learning rate is read
- * from that device float, otherwise `lr`).  The records hold device pointers: the caller keeps them valid until the launch
- * has run (centerclip_amd.train.BertAdam stages them through pinned memory). */
+/* BertAdam (utils/optimization.py:100-170: the optimizer main.py:161-167 builds), multi-tensor.  csrc/bertadam.hip.
+ * Per tensor: grad is clipped in place to max_grad_norm (clip_grad_norm_ on the single tensor; <= 0: no clipping),
+ * next_m = b1 m + (1-b1) g, next_v = b2 v + (1-b2) g^2, param -= lr * (next_m / (sqrt(next_v) + e) + weight_decay * param); no
+ * bias correction.  lr = lr_scheduled = lr * schedule(step / t_total, warmup) is host arithmetic (centerclip_amd.train.BertAdam):
+ * the record's `lr`, or - lr_dev != null - read from that device float (a training step captured into a hipGraph is replayed
+ * with the schedule's new value written there first).  All tensors fp32.
+ *
+ * One table of `count` records in device memory drives TWO launches for all tensors: every tensor's norm workgroups (fp64
+ * partial sums of squares into ws), then every tensor's step workgroups, each finding its tensor by bisection.  Records are
+ * ordered, norm_blk0 / step_blk0 = the running sums of norm_blocks / step_blocks = cc_bertadam_norm_blocks(n) /
+ * cc_bertadam_step_blocks(n) (host-side queries), total_* their sums, ws >= total_norm_blocks doubles.  A tensor of
+ * n <= CC_BERTADAM_MULTI_MAX_N elements (biases, LayerNorm weights) has norm_blocks == 0 and step_blocks == 1: its one workgroup
+ * forms the sum of squares itself.  The norm launch is skipped when max_grad_norm <= 0 or total_norm_blocks == 0 (ws may then
+ * be null).  A tensor's bits do not depend on what else the table holds.  The records hold device pointers: the caller keeps
+ * them valid until the launches have run (centerclip_amd.train.BertAdam stages them through pinned memory). */
 #define CC_BERTADAM_MULTI_MAX_N 8192
 typedef struct cc_bertadam_item {
-    float* param; float* grad; float* next_m; float* next_v;
-    const float* lr_dev;
-    int32_t n;
-    float lr, weight_decay;
-    int32_t reserved;
-} cc_bertadam_item;                                            /* 56 bytes */
-int cc_bertadam_multi_f32(const void* items_dev, int32_t count, float b1, float b2, float e, float max_grad_norm, void* stream);
-/* ... and of `count` LARGE tensors (any n) in TWO launches - every tensor's norm workgroups, then every tensor's step workgroups,
- * each finding its tensor by bisection: records ordered, norm_blk0 / step_blk0 = running sums of norm_blocks / step_blocks =
- * cc_bertadam_norm_blocks(n) / cc_bertadam_step_blocks(n) (host-side queries), ws >= total_norm_blocks doubles.  Per tensor the
- * arithmetic and the bits of cc_bertadam_step_f32.  (A ViT-B/32 CLIP has ~100 such tensors: 204 launches -> 2.) */
-typedef struct cc_bertadam_big_item {
     float* param; float* grad; float* next_m; float* next_v;
     const float* lr_dev;
     int64_t n;
     float lr, weight_decay;
     int32_t norm_blk0, norm_blocks, step_blk0, step_blocks;
-} cc_bertadam_big_item;                                        /* 72 bytes */
+} cc_bertadam_item;                                            /* 72 bytes */
 int32_t cc_bertadam_norm_blocks(int64_t n);
 int32_t cc_bertadam_step_blocks(int64_t n);
-int cc_bertadam_multi_large_f32(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks,
-                                float b1, float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes, void* stream);
-/* The three forms above under a device-side loss scale (see "Loss scaling on the device" below): the gradients still carry
- * the scale; every gradient is multiplied by *mult_dev as it is loaded (and that value is what is written back), so the
- * result is bit for bit the plain entry point on gradients multiplied by *mult_dev first - for a power-of-two scale, on the
- * gradients divided by it.  *found_inf_dev != 0: the launches write nothing - parameters, moments and gradients keep their
- * bits (GradScaler.step skipping optimizer.step()).  Both words are device floats that cc_grad_scaler_stats_f32 wrote. */
-int cc_bertadam_step_scaled_f32(float* param, float* grad, float* next_m, float* next_v, int64_t n, float lr_scheduled, float b1,
-                                float b2, float e, float weight_decay, float max_grad_norm, const float* lr_dev, void* ws,
-                                size_t ws_bytes, const float* mult_dev, const float* found_inf_dev, void* stream);
-int cc_bertadam_multi_scaled_f32(const void* items_dev, int32_t count, float b1, float b2, float e, float max_grad_norm,
+int cc_bertadam_multi_f32(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks, float b1,
+                          float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes, void* stream);
+/* The same under a device-side loss scale (see "Loss scaling on the device" below): the gradients still carry the scale; every
+ * gradient is multiplied by *mult_dev as it is loaded (and that value is what is written back), so the result is bit for bit
+ * the plain entry point on gradients multiplied by *mult_dev first - for a power-of-two scale, on the gradients divided by it.
+ * *found_inf_dev != 0: the launches write nothing - parameters, moments and gradients keep their bits (GradScaler.step skipping
+ * optimizer.step()).  Both words are device floats that cc_grad_scaler_stats_f32 wrote. */
+int cc_bertadam_multi_scaled_f32(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks,
+                                 float b1, float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes,
                                  const float* mult_dev, const float* found_inf_dev, void* stream);
-int cc_bertadam_multi_large_scaled_f32(const void* items_dev, int32_t count, int32_t total_norm_blocks, int32_t total_step_blocks,
-                                       float b1, float b2, float e, float max_grad_norm, void* ws, size_t ws_bytes,
-                                       const float* mult_dev, const float* found_inf_dev, void* stream);
 
 /* ==========================================================================================
  * AdamW (torch.optim.AdamW, the optimizer main.py:168-175 builds for --optim AdamW) and global gradient clipping

@@ -107,7 +107,8 @@ def test_scaled_step_equals_the_step_on_divided_gradients_and_skips_bit_for_bit(
     """DeviceGradScaler(2^10).step on gradients that carry the scale == optimizer.step() on the gradients divided by it, bit
     for bit (parameters, both moments, the gradients written back), over two steps; then one inf in ONE gradient element: the
     launches write nothing - every parameter and moment of every tensor keeps its bits, and the step is not counted.
-    BertAdam-multi: the small multi-tensor launch + the large two-launch form; BertAdam-single: one launch pair per tensor."""
+    BertAdam-multi / BertAdam-single: the same record table and launch pair; they differ in how the learning rate is delivered
+    (the group's device float / each record's own scheduled value)."""
     from centerclip_amd.train import DeviceGradScaler
     pa, oa = _toy(kind)
     pb, ob = _toy(kind)

@@ -99,10 +99,10 @@ def test_new_entry_points_are_exported_and_declared_for_ctypes():
     from centerclip_amd import _lib as L
     lib = L.lib()
     for name, nargs in (("cc_grad_scaler_stats_f32", 6), ("cc_adamw_multi_scaled_f32", 7), ("cc_grad_scaler_update_f32", 7),
-                        ("cc_bertadam_step_scaled_f32", 17), ("cc_bertadam_multi_scaled_f32", 9),
-                        ("cc_bertadam_multi_large_scaled_f32", 13)):
+                        ("cc_bertadam_multi_scaled_f32", 13)):
         assert len(getattr(lib, name).argtypes) == nargs, name
     # NULL pointers are rejected before anything touches the device
     assert lib.cc_grad_scaler_stats_f32(None, 1, None, 1.0, None, None) == -1
     assert lib.cc_adamw_multi_scaled_f32(None, 1, 1, None, None, None, None) == -1
     assert lib.cc_grad_scaler_update_f32(None, None, None, 2.0, 0.5, 1, None) == -1
+    assert lib.cc_bertadam_multi_f32(None, 1, 0, 1, 0.9, 0.999, 1e-6, 1.0, None, 0, None) == -1

@@ -393,7 +393,7 @@ def _adam_groups(params, clip):
 
 @pytest.mark.parametrize("n", [8192, 8193, 512 * 1024 + 3, 2 ** 22 + 1])
 def test_bertadam_large_tensors_against_float64(n):
-    """cc_bertadam_step_f32 on tensors above and at the one-workgroup size, clipping engaged and not, weight decay 0.2 and 0,
+    """cc_bertadam_multi_f32 on tensors above and at the one-workgroup size, clipping engaged and not, weight decay 0.2 and 0,
     two steps, gradients as views into one flat buffer at offsets that are not multiples of 4 floats (the norm pass's
     scalar branch): parameters and moments against the float64 restatement at rtol 2e-6, atol 2e-7."""
     from oracle.clip_oracle import bertadam_step64
@@ -422,32 +422,48 @@ def test_bertadam_large_tensors_against_float64(n):
                 np.testing.assert_allclose(st['next_v'].cpu().numpy(), ref[j][2].cpu().numpy(), rtol=2e-6, atol=1e-10)
 
 
-@pytest.mark.parametrize("sizes", ["large", "small"])
+@pytest.mark.parametrize("sizes", ["large", "small", "mixed"])
 def test_bertadam_multi_tensor_launches_equal_per_tensor_steps(sizes):
-    """capturable=True (cc_bertadam_multi_large_f32 for 37 tensors of mixed sizes > 8192, which finds its tensor by bisection;
-    cc_bertadam_multi_f32 for 100 tensors of 1..8192 elements) == one cc_bertadam_step_f32 per tensor, bit for bit, over
-    three steps with clipping engaged on some tensors."""
+    """One table of N records (cc_bertadam_multi_f32: 37 tensors of mixed sizes > 8192, each found by bisection; 100 tensors of
+    1..8192 elements, one workgroup each; both kinds in one table, with the one-workgroup records first, last and twice in a
+    row between two large ones) == N tables of one record (one BertAdam per tensor), bit for bit - p, next_v and the
+    written-back gradient - over three steps with clipping engaged on some tensors.  For capturable False and True (the
+    learning rate in the record / read from the group's device float), which also equal each other."""
+    from centerclip_amd.train import BertAdam
     rng = np.random.default_rng(37 if sizes == "large" else 100)
     if sizes == "large":
         ns = [int(v) for v in rng.integers(8193, 400_000, size=37)]
         ns[:3] = [8193, 2 ** 20 + 5, 9600 + 1]
-    else:
+    elif sizes == "small":
         ns = [int(v) for v in rng.integers(1, 8193, size=100)]
         ns[:3] = [1, 8192, 4]
+    else:
+        ns = [4, 8192, 8193, 1, 8192, 9601, 2 ** 20 + 5, 8193, 3]
     g = _gen(len(ns))
     init = [torch.randn(n, device=DEV, generator=g) for n in ns]
-    pa = [torch.nn.Parameter(t.clone()) for t in init]
-    pb = [torch.nn.Parameter(t.clone()) for t in init]
-    oa, ob = _adam_groups(pa, 1.0)(False), _adam_groups(pb, 1.0)(True)
-    for it in range(3):
-        for j, n in enumerate(ns):
-            gr = torch.randn(n, device=DEV, generator=g) * (0.5 if j % 3 else 5.0) / math.sqrt(n)
-            pa[j].grad, pb[j].grad = gr.clone(), gr.clone()
-        oa.step()
-        ob.step()
+    grads = [[torch.randn(n, device=DEV, generator=g) * (0.5 if j % 3 else 5.0) / math.sqrt(n) for j, n in enumerate(ns)]
+             for _ in range(3)]
+    tables = {}
+    for capturable in (False, True):
+        pa = [torch.nn.Parameter(t.clone()) for t in init]
+        pb = [torch.nn.Parameter(t.clone()) for t in init]
+        oa = _adam_groups(pa, 1.0)(capturable)
+        ob = [BertAdam([{'params': [p], 'weight_decay': 0.0 if j % 2 else 0.2}], lr=1e-2, b1=0.9, b2=0.98, e=1e-6,
+                       max_grad_norm=1.0, capturable=capturable) for j, p in enumerate(pb)]
+        for it in range(3):
+            for j in range(len(ns)):
+                pa[j].grad, pb[j].grad = grads[it][j].clone(), grads[it][j].clone()
+            oa.step()
+            for o in ob:
+                o.step()
+            for j in range(len(ns)):
+                assert torch.equal(pa[j], pb[j]), (capturable, it, j, ns[j])
+                assert torch.equal(oa.state[pa[j]]['next_v'], ob[j].state[pb[j]]['next_v']), (capturable, it, j, ns[j])
+                assert torch.equal(pa[j].grad, pb[j].grad), (capturable, it, j, ns[j])
+        tables[capturable] = (pa, [oa.state[p]['next_v'] for p in pa], [p.grad for p in pa])
+    for x, y in zip(tables[False], tables[True]):
         for j in range(len(ns)):
-            assert torch.equal(pa[j], pb[j]), (it, j, ns[j])
-            assert torch.equal(oa.state[pa[j]]['next_v'], ob.state[pb[j]]['next_v']) and torch.equal(pa[j].grad, pb[j].grad)
+            assert torch.equal(x[j], y[j]), (j, ns[j])
 
 
 def test_bertadam_captured_step_keeps_its_tables_through_eager_uploads():

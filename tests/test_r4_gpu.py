@@ -339,7 +339,7 @@ def test_training_step_gradients_against_reference_autograd():
 
 
 def test_bertadam_matches_reference_optimizer():
-    """centerclip_amd.train.BertAdam (cc_bertadam_step_f32) vs three steps of utils/optimization.BertAdam: clipping engaged in
+    """centerclip_amd.train.BertAdam (cc_bertadam_multi_f32) vs three steps of utils/optimization.BertAdam: clipping engaged in
     step 2 (|g| large), weight decay in group 1 only, warmup_linear schedule."""
     from centerclip_amd.train import BertAdam, warmup_linear
     r4 = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "r4_golden.npz"))

@@ -37,6 +37,47 @@ def test_bertadam_arguments_and_lr_bookkeeping():
     assert opt2.get_lr() == [1e-3]
 
 
+def test_bertadam_table_records_and_block_ranges():
+    """_bertadam_table on CPU tensors (pointers and the host-side block queries only): 72-byte cc_bertadam_item records in
+    order, no record for an empty tensor; n <= 8192 is a one-workgroup record (norm_blocks 0, step_blocks 1), above that
+    norm_blocks = min(ceil(n / 1024), 512) and step_blocks = min(ceil(n / 1024), 8192); the blk0 fields are the running sums."""
+    import numpy as np
+    from centerclip_amd.train.optim import _BERTADAM_ITEM, _bertadam_table
+    assert _BERTADAM_ITEM.itemsize == 72
+    ns = [1, 8192, 8193, 8192, 9601, 2 ** 20 + 5, 9_000_000]
+    ts = [torch.empty(n) for n in ns]
+    lr_dev = torch.zeros(1)
+    entries = [(t, t, t, t, lr_dev if i % 2 else 1e-3 * (i + 1), 0.1 * i) for i, t in enumerate(ts)]
+    entries.insert(3, (torch.empty(0),) * 4 + (1e-3, 0.0))
+    raw, count, norm_total, step_total = _bertadam_table(entries)
+    assert count == len(ns) and len(raw) == 72 * len(ns)
+    rec = np.frombuffer(raw, dtype=_BERTADAM_ITEM)
+    nb0 = sb0 = 0
+    for i, (n, t, r) in enumerate(zip(ns, ts, rec)):
+        blocks = -(-n // 1024)
+        nb, sb = (0, 1) if n <= 8192 else (min(blocks, 512), min(blocks, 8192))
+        assert (r['norm_blocks'], r['step_blocks']) == (nb, sb), n
+        assert (r['norm_blk0'], r['step_blk0']) == (nb0, sb0), n
+        assert r['n'] == n and r['p'] == r['g'] == r['m'] == r['v'] == t.data_ptr()
+        assert (r['lr_dev'], r['lr']) == ((lr_dev.data_ptr(), 0.0) if i % 2 else (0, np.float32(1e-3 * (i + 1))))
+        assert r['wd'] == np.float32(0.1 * i)
+        nb0 += nb
+        sb0 += sb
+    assert (norm_total, step_total) == (nb0, sb0) == (9 + 10 + 512 + 512, 3 + 9 + 10 + 1025 + 8192)
+
+
+def test_bertadam_step_under_a_capture_needs_capturable(monkeypatch):
+    """A capturable=False step would bake its learning rates into the graph: it raises, as AdamW's does."""
+    from centerclip_amd.train import optim
+    monkeypatch.setattr(optim, "_capturing", lambda: True)
+    p = torch.nn.Parameter(torch.zeros(3))
+    p.grad = torch.zeros(3)
+    opt = cctrain.BertAdam([p], lr=1e-3)
+    with pytest.raises(RuntimeError, match="capturable=True"):
+        opt.step()
+    assert len(opt.state) == 0                                    # (raised before any state was made)
+
+
 def test_param_groups_follow_the_reference():
     """utils/optimization.py:173-208: CLIP parameters at lr * coef_lr, modules named in new_added_modules at lr, no weight
     decay for biases and LayerNorm parameters."""
