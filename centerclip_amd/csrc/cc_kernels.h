@@ -199,3 +199,12 @@ struct TokenClusterReq : TokenRows {
 };
 CC_INTERNAL int cc_token_gather_rows(const TokenGatherReq& r, hipStream_t st);
 CC_INTERNAL int cc_token_cluster_variant_rows(const TokenClusterReq& r, hipStream_t st);
+
+// camoe_dsl, shared by dsl.hip and search.hip (both built without fma contraction: the operations are IEEE single, in this order)
+// s_a exp(m_a - m): the share of a partial sum under the merged maximum.  s_a == 0 marks the neutral element (-inf, 0) - no
+// row seen - whose exponent would be -inf - -inf.
+__device__ __forceinline__ float cc_dsl_share(float s_a, float m_a, float m) { return s_a == 0.f ? 0.f : s_a * expf(m_a - m); }
+// D = n_total * x * exp(x - m) / s as cc_dsl_apply_f32 stores it
+__device__ __forceinline__ float cc_dsl_value(float nt, float x, float m, float s) { return (nt * x) * (expf(x - m) / s); }
+// [slabs][cols] (m, s) pairs -> m, s [cols]: the pairs under their maximum, the shares added in slab order (dsl.hip)
+CC_INTERNAL int cc_launch_dsl_col_merge(const float* part, int slabs, int cols, float* m, float* s, hipStream_t st);

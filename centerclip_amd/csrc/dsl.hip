@@ -16,10 +16,6 @@ namespace {
 constexpr int DSL_SLAB = 128;        // rows per workgroup: 32 per wave
 constexpr int DSL_APPLY_ROWS = 32;   // rows per workgroup of the rewrite
 
-// s_a exp(m_a - m): the share of a partial sum under the merged maximum.  s_a == 0 marks the neutral element (-inf, 0) - no
-// row seen - whose exponent would be -inf - -inf.
-__device__ __forceinline__ float dsl_share(float s_a, float m_a, float m) { return s_a == 0.f ? 0.f : s_a * expf(m_a - m); }
-
 __global__ __launch_bounds__(256) void dsl_col_partial_kernel(const float* __restrict__ sim, int rows, int cols, int64_t rs,
                                                               float* __restrict__ part) {
     __shared__ float sm[4][64], ss[4][64];
@@ -48,7 +44,7 @@ __global__ __launch_bounds__(256) void dsl_col_partial_kernel(const float* __res
         if (nan) mm = NAN;
         float t = 0.f;
 #pragma unroll
-        for (int w = 0; w < 4; ++w) t += dsl_share(ss[w][lane], sm[w][lane], mm);
+        for (int w = 0; w < 4; ++w) t += cc_dsl_share(ss[w][lane], sm[w][lane], mm);
         float* p = part + ((int64_t)blockIdx.y * cols + c) * 2;
         p[0] = mm;
         p[1] = t;
@@ -71,7 +67,7 @@ __global__ __launch_bounds__(256) void dsl_col_merge_kernel(const float* __restr
     float s = 0.f;
     for (int k = 0; k < slabs; ++k) {
         const float* p = part + ((int64_t)k * cols + c) * 2;
-        s += dsl_share(p[1], p[0], m);
+        s += cc_dsl_share(p[1], p[0], m);
     }
     m_out[c] = m;
     s_out[c] = s;
@@ -80,7 +76,7 @@ __global__ __launch_bounds__(256) void dsl_col_merge_kernel(const float* __restr
 __global__ __launch_bounds__(256) void dsl_rescale_kernel(const float* __restrict__ m_local, const float* __restrict__ m_global,
                                                           float* __restrict__ s, int cols) {
     const int c = blockIdx.x * 256 + threadIdx.x;
-    if (c < cols) s[c] = dsl_share(s[c], m_local[c], m_global[c]);
+    if (c < cols) s[c] = cc_dsl_share(s[c], m_local[c], m_global[c]);
 }
 
 __global__ __launch_bounds__(256) void dsl_apply_kernel(float* __restrict__ sim, int rows, int cols, int64_t rs,
@@ -93,13 +89,20 @@ __global__ __launch_bounds__(256) void dsl_apply_kernel(float* __restrict__ sim,
     for (int r = r0; r < r1; ++r) {
         float* p = sim + (int64_t)r * rs + c;
         const float x = *p;
-        *p = (nt * x) * (expf(x - mc) / sc);
+        *p = cc_dsl_value(nt, x, mc, sc);
     }
 }
 
 inline int dsl_slabs(int rows) { return (rows + DSL_SLAB - 1) / DSL_SLAB; }
 
 }  // namespace
+
+// [slabs][cols] pairs -> m, s [cols] (search.hip's statistics pass ends with the same merge)
+int cc_launch_dsl_col_merge(const float* part, int slabs, int cols, float* m, float* s, hipStream_t st) {
+    hipLaunchKernelGGL(dsl_col_merge_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, part, slabs, cols, m, s);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
 
 extern "C" {
 
@@ -121,9 +124,7 @@ int cc_dsl_col_stats_f32(const float* sim, int32_t rows, int32_t cols, int64_t r
                            part);
         CC_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(dsl_col_merge_kernel, dim3((cols + 255) / 256), dim3(256), 0, st, part, slabs, cols, m, s);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+    return cc_launch_dsl_col_merge(part, slabs, cols, m, s, st);
 }
 
 int cc_dsl_rescale_stats_f32(const float* m_local, const float* m_global, float* s, int32_t cols, void* stream) {

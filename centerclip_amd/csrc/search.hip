@@ -16,6 +16,24 @@
 //   2. topk_merge_kernel, one wave per query row: the slices' lists -> the final k, decoded into scores / ids.
 // A (score, id) pair is ONE 64-bit key whose unsigned order is the result's order (larger score first, equal scores by
 // smaller id; -0 and +0 equal), so ties never need a second look and the lists of any split merge to the same result.
+//
+// camoe_dsl (dual softmax) on the same stream, still without the matrix:
+//   * topk_stream_kernel<true> ranks D = cc_dsl_value(n_total, S, m_x, s_x) - the expression dsl_apply_kernel evaluates, so the
+//     bits cc_dsl_apply_f32 writes over the matrix op's entry - with x the gallery row or the query row.  A compile-time
+//     mode: topk_stream_kernel<false> is the plain kernel.
+//   * dsl_stats_stream_kernel gives the pair (m, s) of every VIDEO row over many text rows: the video rows take the place of
+//     the queries (16 staged in LDS), the text rows are streamed, and a running log-sum-exp pair replaces the lists.
+//     Summation tree of one video row (fixed; no atomics; it depends on Bt alone, never on Bv or on the row's place):
+//       - the text tiles are cut into dsl_stats_slices(Bt) contiguous slices, a workgroup each; wave w takes tiles
+//         t0 + w, t0 + w + 4, ... of its slice, and in a tile the lane group lg holds text rows 16 t + 4 lg + {0, 1, 2, 3};
+//       - lane, per tile: mt = max(m, x0..x3);  s = (((share(s, m, mt) + e0) + e1) + e2) + e3,  e_r = expf(x_r - mt);  m = mt
+//         (share(s, a, b) = s * expf(a - b), 0 for s == 0) - an old term passes 2 (expf) + 1 (mul) + 4 (add) = 7 roundings
+//         per tile of its lane, ceil(ceil(tiles / slices) / 4) tiles at most;
+//       - workgroup: the 16 pairs of a video row (wave-major, then lane group) under their maximum, shares added in that
+//         order: 2 + 1 + 16 roundings;
+//       - second launch (dsl.hip's merge): the slices' pairs under their maximum, added in slice order: 2 + 1 + slices.
+//     The subtractions inside expf telescope: the partial maxima rise from x to m, so together they cost |x - m| U on the
+//     exponent.  Longest chain of roundings: 7 * ceil(ceil(tiles / slices) / 4) + 19 + slices + 3.
 #include "cc_kernels.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -33,6 +51,7 @@ constexpr int TK_MIN_TILES = 32;       // 16-row tiles a slice holds at least (8
 constexpr int TK_BATCH = 4;            // pairs of k-slices a lane requests at once (8 loads of 16 bytes)
 constexpr int TK_MERGE_BATCH = 8;      // keys per lane the merge requests before it looks at any
 constexpr size_t TK_LDS_LIMIT = 160 * 1024;
+constexpr int DSL_MAX_SLICES = 512;    // text slices of the statistics pass at most (the 256 CUs twice for one group of videos)
 
 // key = [ordered score bits : 32][~id, 31 bits][score was -0 : 1].  The score enters as score + 0.0f (so -0 orders as +0);
 // the last bit only restores the sign of a zero on the way out - ids are unique, it never decides an order.  No finite or
@@ -136,37 +155,30 @@ __device__ __forceinline__ void tk_insert(u64* list, int k, u64 key, int lane) {
     tk_wave_sync();
 }
 
-// query / gallery: plane rows `ld` halfs apart, the first K of them multiplied.  ws [Bq][k][slices] keys.
-__global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
-                                                          int Bq, int Bg, int ld, int K, float sc, int k, int slices,
-                                                          u64* __restrict__ ws) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
-    const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
-    const int QS = K + TK_QPAD;
-    _Float16* qs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][QS]
-    u64* lists = reinterpret_cast<u64*>(tk_smem + (size_t)TK_QROWS * QS * 2);          // [wave][16][k]
-    const int chunks = K >> 3;
+// 16 plane rows from `first` on (rows beyond `count`: clamped to the last one, their results are dropped) -> LDS [16][K + TK_QPAD]
+__device__ __forceinline__ void tk_stage_rows(_Float16* qs, const _Float16* __restrict__ rows, int first, int count, int ld, int K) {
+    const int QS = K + TK_QPAD, chunks = K >> 3;
     for (int c = threadIdx.x; c < TK_QROWS * chunks; c += 256) {
         const int r = c / chunks, cc = c - r * chunks;
-        const int qr = min(q0 + r, Bq - 1);                                           // rows beyond Bq: clamped, results dropped
-        *reinterpret_cast<h8*>(qs + r * QS + cc * 8) = *reinterpret_cast<const h8*>(query + (int64_t)qr * ld + cc * 8);
+        const int qr = min(first + r, count - 1);
+        *reinterpret_cast<h8*>(qs + r * QS + cc * 8) = *reinterpret_cast<const h8*>(rows + (int64_t)qr * ld + cc * 8);
     }
-    for (int i = threadIdx.x; i < TK_WAVES * TK_QROWS * k; i += 256) lists[i] = 0;
-    __syncthreads();
+}
 
-    u64* mine = lists + ((size_t)wave * TK_QROWS + l15) * k;                           // this wave's list of query row l15
-    const int tiles = (Bg + 15) >> 4;
-    const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
-    const bool qvalid = q0 + l15 < Bq;
-    const _Float16* qrow = qs + l15 * QS + lg * 8;
+// The stream of one wave: the 16-row tiles t0 + wave, t0 + wave + 4, ... < t1 of `gallery` (Bg rows, `ld` halfs apart, the first
+// K multiplied) against the 16 staged rows (`qrow`: the lane's fragments of staged row l15).  Behind a tile's last k-slice
+// on_tile(t, acc) gets the 16 x 16 products: the lane holds streamed rows t * 16 + 4 lg + r (r = 0..3) of staged row l15, each
+// ONE fp32 accumulator over the k-slices in ascending order, the streamed fragment as the first operand.  before_last(t) runs
+// in front of the request that overlaps tile t's last batch: what it requests arrives before that batch (loads return in
+// order), so on_tile waits for the tile, not for the next one.
+// A batch = TK_BATCH pairs of k-slices of one tile (2 TK_BATCH 16-byte loads a lane).  Two register buffers take turns:
+// while one batch is multiplied - and, behind a tile's last batch, consumed by on_tile - the next one (the tile's next, or the
+// first of the wave's next tile) is in flight.  Pairs beyond the row's end are clamped to its last pair (read again, not
+// multiplied).
+template <class Before, class Tile>
+__device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gallery, int Bg, int ld, int K, const _Float16* qrow,
+                                                int t0, int t1, int wave, int l15, int lg, Before&& before_last, Tile&& on_tile) {
     const int nk2 = K >> 6;                                                            // pairs of k-slices: one 128-byte line per row
-    u64 thr = 0;                                                                       // the k-th key of `mine`
-    int filled = 0;                                                                    // entries any of the wave's lists holds, at most
-    // A batch = TK_BATCH pairs of k-slices of one tile (2 TK_BATCH 16-byte loads a lane).  Two register buffers take turns:
-    // while one batch is multiplied - and, behind a tile's last batch, its survivors are inserted - the next one (the tile's
-    // next, or the first of the wave's next tile) is in flight.  Pairs beyond the row's end are clamped to its last pair
-    // (read again, not multiplied).
     auto load_batch = [&](h8 (&b)[2 * TK_BATCH], int t, int s0) {
         const int grow = min(t * 16 + l15, Bg - 1);                                    // rows at Bg or above are never read
         const _Float16* gp = gallery + (int64_t)grow * ld + lg * 8;
@@ -187,6 +199,7 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
         // nobody multiplies: under a condition the compiler's wait for `cur` has to cover the path without the request,
         // and on the other path it then waits for the batch just requested)
         const bool last = b + 1 == nb;
+        if (last) before_last(t);
         load_batch(nxt, last ? min(t + TK_WAVES, t_last) : t, last ? 0 : (b + 1) * TK_BATCH);
 #pragma unroll
         for (int u = 0; u < TK_BATCH; ++u) {
@@ -199,14 +212,7 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
             }
         }
         if (!last) { ++b; return; }
-        // the lane holds gallery rows t * 16 + 4 lg + r (r = 0..3) of query row l15
-        u64 key[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int id = t * 16 + lg * 4 + r;
-            key[r] = (qvalid && id < Bg) ? tk_key(sc * acc[r], id) : 0;
-        }
-        tk_insert_tile(key, mine, k, lg, thr, filled);
+        on_tile(t, acc);
         acc = f32x4{0.f, 0.f, 0.f, 0.f};
         t += TK_WAVES;
         b = 0;
@@ -217,6 +223,67 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
         step(buf0, buf1);
         if (g + 1 < total) step(buf1, buf0);
     }
+}
+
+// query / gallery: plane rows `ld` halfs apart, the first K of them multiplied.  ws [Bq][k][slices] keys.  DSL: the score is
+// cc_dsl_value(nt, S, m, s) with the pair of the gallery row (on_gallery) or of the query row; without DSL the last four
+// arguments are not read.
+template <bool DSL>
+__global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
+                                                          int Bq, int Bg, int ld, int K, float sc, int k, int slices,
+                                                          u64* __restrict__ ws, const float* __restrict__ stat_m,
+                                                          const float* __restrict__ stat_s, int on_gallery, float nt) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
+    const int QS = K + TK_QPAD;
+    _Float16* qs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][QS]
+    u64* lists = reinterpret_cast<u64*>(tk_smem + (size_t)TK_QROWS * QS * 2);          // [wave][16][k]
+    tk_stage_rows(qs, query, q0, Bq, ld, K);
+    for (int i = threadIdx.x; i < TK_WAVES * TK_QROWS * k; i += 256) lists[i] = 0;
+    __syncthreads();
+
+    u64* mine = lists + ((size_t)wave * TK_QROWS + l15) * k;                           // this wave's list of query row l15
+    const int tiles = (Bg + 15) >> 4;
+    const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
+    const bool qvalid = q0 + l15 < Bq;
+    u64 thr = 0;                                                                       // the k-th key of `mine`
+    int filled = 0;                                                                    // entries any of the wave's lists holds, at most
+    // DSL: the statistics of the lane's 4 gallery rows (requested per tile) or of its query row (once)
+    float dm[4] = {0.f, 0.f, 0.f, 0.f}, ds[4] = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (DSL) {
+        if (!on_gallery) {
+            const int qr = min(q0 + l15, Bq - 1);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { dm[r] = stat_m[qr]; ds[r] = stat_s[qr]; }
+        }
+    }
+    tk_stream_tiles(
+        gallery, Bg, ld, K, qs + l15 * QS + lg * 8, t0, t1, wave, l15, lg,
+        [&](int t) {
+            if constexpr (DSL) {
+                if (on_gallery) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int id = min(t * 16 + lg * 4 + r, Bg - 1);               // statistics at Bg or above are never read
+                        dm[r] = stat_m[id];
+                        ds[r] = stat_s[id];
+                    }
+                }
+            }
+        },
+        [&](int t, const f32x4& acc) {
+            // the lane holds gallery rows t * 16 + 4 lg + r (r = 0..3) of query row l15
+            u64 key[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int id = t * 16 + lg * 4 + r;
+                float x = sc * acc[r];
+                if constexpr (DSL) x = cc_dsl_value(nt, x, dm[r], ds[r]);
+                key[r] = (qvalid && id < Bg) ? tk_key(x, id) : 0;
+            }
+            tk_insert_tile(key, mine, k, lg, thr, filled);
+        });
     // the four waves' lists -> wave 0's, as a tree: the other wave's entries are the candidates, 16 a list at a time
     auto fold = [&](int from) {
         const u64* other = lists + ((size_t)from * TK_QROWS + l15) * k;
@@ -287,11 +354,63 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const u64* __restrict__ 
     }
 }
 
+// The (m, s) pairs of the 16 video rows from blockIdx.y * 16 on over the text tiles of slice blockIdx.x (the tree: the file's
+// head).  part [slices][Bv] pairs.  The split of the text rows uses Bt alone.
+__global__ __launch_bounds__(256) void dsl_stats_stream_kernel(const _Float16* __restrict__ video, const _Float16* __restrict__ text,
+                                                               int Bv, int Bt, int ld, int K, float sc, int slices,
+                                                               float* __restrict__ part) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+    __shared__ float pm[TK_WAVES][4][TK_QROWS], ps[TK_WAVES][4][TK_QROWS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int slice = blockIdx.x, v0 = blockIdx.y * TK_QROWS;
+    _Float16* vs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][K + TK_QPAD]
+    tk_stage_rows(vs, video, v0, Bv, ld, K);
+    __syncthreads();
+    const int tiles = (Bt + 15) >> 4;
+    const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
+    float m = -INFINITY, s = 0.f;                                                      // of video row l15 over the lane's text rows
+    tk_stream_tiles(
+        text, Bt, ld, K, vs + l15 * (K + TK_QPAD) + lg * 8, t0, t1, wave, l15, lg, [](int) {},
+        [&](int t, const f32x4& acc) {
+            float x[4], mt = m;
+            bool in[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                in[r] = t * 16 + lg * 4 + r < Bt;
+                x[r] = sc * acc[r];
+                mt = in[r] ? fmaxf(mt, x[r]) : mt;
+            }
+            float a = cc_dsl_share(s, m, mt);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) a += in[r] ? expf(x[r] - mt) : 0.f;
+            s = a;
+            m = mt;
+        });
+    pm[wave][lg][l15] = m;
+    ps[wave][lg][l15] = s;
+    __syncthreads();
+    if (threadIdx.x < TK_QROWS && v0 + threadIdx.x < Bv) {
+        const int v = threadIdx.x;
+        float mm = -INFINITY;
+#pragma unroll
+        for (int i = 0; i < TK_WAVES * 4; ++i) mm = fmaxf(mm, pm[i >> 2][i & 3][v]);
+        float a = 0.f;
+#pragma unroll
+        for (int i = 0; i < TK_WAVES * 4; ++i) a += cc_dsl_share(ps[i >> 2][i & 3][v], pm[i >> 2][i & 3][v], mm);
+        float* p = part + ((int64_t)slice * Bv + v0 + v) * 2;
+        p[0] = mm;
+        p[1] = a;
+    }
+}
+
 int tk_slices(int Bq, int Bg) {
     const int groups = (max(Bq, 1) + TK_QROWS - 1) / TK_QROWS, tiles = (max(Bg, 1) + 15) / 16;
     const int want = (TK_TARGET_WGS + groups - 1) / groups, cap = tiles / TK_MIN_TILES;
     return max(1, min(want, cap));
 }
+// text slices of the statistics pass: a function of Bt ALONE (a video row's pair must not depend on the rows it shares a call
+// with), at least TK_MIN_TILES tiles a slice
+int dsl_stats_slices(int Bt) { return max(1, min(DSL_MAX_SLICES, (max(Bt, 1) + 15) / 16 / TK_MIN_TILES)); }
 size_t tk_stream_lds(int K, int k) { return (size_t)TK_QROWS * (K + TK_QPAD) * 2 + (size_t)TK_WAVES * TK_QROWS * k * sizeof(u64); }
 
 }  // namespace
@@ -308,10 +427,12 @@ size_t cc_similarity_topk_workspace_bytes(int32_t Bq, int32_t Bg, int32_t k) {
     return cc_align_up((size_t)Bq * tk_slices(Bq, Bg) * k * sizeof(u64), 256);
 }
 
-int cc_similarity_topk_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
-                                  float mult, int32_t products, int32_t k, float* scores, int32_t* ids, void* ws,
-                                  size_t ws_bytes, void* stream) {
+// the checks and the two launches of both top-k entries; dsl: m, s, on_gallery, n_total of the rewrite
+static int tk_launch(bool dsl, const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E, float mult,
+                     int32_t products, int32_t k, const float* m, const float* s, int32_t on_gallery, int32_t n_total,
+                     float* scores, int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
     if (!query_planes || !gallery_planes || !scores || !ids || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
+    if (dsl && (!m || !s || n_total < 0 || (on_gallery != 0 && on_gallery != 1))) return CC_ERR_INVALID;
     if (k < 1 || k > TK_MAXK || products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
     const int K = products * E;
     const size_t smem = tk_stream_lds(K, k);
@@ -320,14 +441,59 @@ int cc_similarity_topk_planes_f32(const void* query_planes, const void* gallery_
     if (!ws || ws_bytes < cc_similarity_topk_workspace_bytes(Bq, Bg, k)) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int slices = tk_slices(Bq, Bg);
-    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(topk_stream_kernel), smem) != CC_OK) return CC_ERR_HIP;
-    hipLaunchKernelGGL(topk_stream_kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
+    const auto kernel = dsl ? topk_stream_kernel<true> : topk_stream_kernel<false>;
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
+    hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
                        static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K,
-                       mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, k, slices, static_cast<u64*>(ws));
+                       mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, k, slices, static_cast<u64*>(ws), m, s,
+                       on_gallery, (float)n_total);
     CC_LAUNCH_CHECK();
     hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(ws), slices, k, scores, ids);
     CC_LAUNCH_CHECK();
     return CC_OK;
+}
+
+int cc_similarity_topk_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                  float mult, int32_t products, int32_t k, float* scores, int32_t* ids, void* ws,
+                                  size_t ws_bytes, void* stream) {
+    return tk_launch(false, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, nullptr, nullptr, 0, 0, scores, ids, ws,
+                     ws_bytes, stream);
+}
+
+int cc_similarity_topk_dsl_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                      float mult, int32_t products, int32_t k, const float* m, const float* s,
+                                      int32_t stats_on_gallery, int32_t n_total, float* scores, int32_t* ids, void* ws,
+                                      size_t ws_bytes, void* stream) {
+    return tk_launch(true, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s, stats_on_gallery, n_total, scores,
+                     ids, ws, ws_bytes, stream);
+}
+
+int32_t cc_dsl_col_stats_planes_slices(int32_t Bt) { return Bt > 0 ? dsl_stats_slices(Bt) : 0; }
+
+size_t cc_dsl_col_stats_planes_workspace_bytes(int32_t Bt, int32_t Bv) {
+    if (Bt <= 0 || Bv <= 0) return 0;
+    return cc_align_up((size_t)dsl_stats_slices(Bt) * Bv * 2 * sizeof(float), 256);
+}
+
+int cc_dsl_col_stats_planes_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv, int32_t E, float mult,
+                                int32_t products, float* m, float* s, void* ws, size_t ws_bytes, void* stream) {
+    if (!video_planes || !m || !s || Bt < 0 || Bv <= 0 || E <= 0 || (Bt > 0 && !text_planes)) return CC_ERR_INVALID;
+    if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
+    const int K = products * E;
+    const size_t smem = (size_t)TK_QROWS * (K + TK_QPAD) * 2;
+    if (smem > TK_LDS_LIMIT) return CC_ERR_UNSUPPORTED;                   // (never with E <= 1024: 96 KB at most)
+    if ((Bv + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million video rows a call)
+    if (Bt > 0 && (!ws || ws_bytes < cc_dsl_col_stats_planes_workspace_bytes(Bt, Bv))) return CC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int slices = Bt > 0 ? dsl_stats_slices(Bt) : 0;
+    if (slices > 0) {
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(dsl_stats_stream_kernel), smem) != CC_OK) return CC_ERR_HIP;
+        hipLaunchKernelGGL(dsl_stats_stream_kernel, dim3(slices, (Bv + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
+                           static_cast<const _Float16*>(video_planes), static_cast<const _Float16*>(text_planes), Bv, Bt, 3 * E, K,
+                           mult * 9.5367431640625e-07f, slices, static_cast<float*>(ws));
+        CC_LAUNCH_CHECK();
+    }
+    return cc_launch_dsl_col_merge(static_cast<const float*>(ws), slices, Bv, m, s, st);      // no slice: (-inf, 0)
 }
 
 }  // extern "C"

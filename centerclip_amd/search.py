@@ -10,6 +10,15 @@ the gallery rows, no [Nq, N] matrix, memory that does not grow with the gallery.
 The rows are what eval_epoch caches (``eval._video_operand`` / ``HipBackend.text_operand``: split-fp16 planes, [n, 3E]), the
 scores are the bits of eval_epoch's matrix for the same pair, and the order is the stable descending sort of its row (equal
 scores by smaller position).  ``similarity`` gives that matrix itself for small galleries and for checking.
+
+``dual_softmax=True`` ranks the CAMoE dual softmax D = S * softmax(S, dim=0) * Nt of ``eval_epoch(camoe_dsl=1)`` instead of S,
+still without the matrix: D[i, j] needs two floats per video j - the maximum and the exp-sum of column j over the captions -
+which ``torch.ops.centerclip.dsl_col_stats_planes`` takes from the operand rows and ``similarity_topk_dsl`` applies.
+
+    gallery = FeatureGallery(model, dual_softmax=True)    # clips in; the captions the softmax runs over are a bank
+    gallery.set_query_bank(all_input_ids)                 # before or after the clips: the same bits
+    gallery.add(video, video_mask)
+    scores, ids = gallery.search(input_ids, k=10)         # rows of eval_epoch's text->video D for captions of the bank
 """
 import torch
 
@@ -24,15 +33,30 @@ class FeatureGallery:
     """``side``: what the gallery holds - "video" (queries are captions) or "text" (queries are clips).  ``capacity``: rows
     to allocate up front; the buffer grows geometrically and keeps its rows bit for bit.  ``products``: the fp16 products per
     multiply-add of a score (``HipBackend.with_products``); None = ``HipBackend.similarity_products``.  The scores are
-    exp(logit_scale) * cosine as in ``eval._similarity_matrix``; a ``camoe_dsl`` model is refused: the dual softmax needs
-    column statistics over all queries and is no per-query ranking."""
+    exp(logit_scale) * cosine as in ``eval._similarity_matrix``; a ``camoe_dsl`` model is refused unless
+    ``dual_softmax=True``: the dual softmax needs column statistics over all queries and is no per-query ranking.
 
-    def __init__(self, model, side="video", capacity=0, products=None):
+    ``dual_softmax=True`` (whatever the model's flag): ``search*`` and ``similarity*`` rank
+    D[t, v] = n_total * S[t, v] * exp(S[t, v] - m_v) / s_v, with (m_v, s_v) the maximum and the exp-sum of S[:, v] over a set
+    of captions, in the fp32 operations of ``dsl_apply_``.
+      * side="video": that set is the bank registered with ``set_query_bank`` / ``set_query_bank_features`` (its operand rows
+        stay on the device; n_total = its size).  The pair of every clip held is computed when the bank is set and of every
+        clip added later when it is added - the same bits either way, whatever the batches.  With the bank equal to the
+        evaluation captions and a query that is one of them, the scores are a row of the matrix ``eval_epoch(camoe_dsl=1)``
+        ranks text->video; for any other query they are the same formula with the bank's statistics, the query not
+        included.  Searching without a bank raises ValueError.  The pairs are taken with the model's logit scale at that
+        moment: set the bank again after changing it.
+      * side="text": no bank (``set_query_bank*`` raises ValueError).  Every search first takes the query clips' pairs over the
+        captions held (n_total = len(self)), then the top-k: two passes over the gallery.  With the gallery holding all
+        evaluation captions this is a row of ``eval_epoch``'s video->text ranking (D^T)."""
+
+    def __init__(self, model, side="video", capacity=0, products=None, dual_softmax=False):
         if side not in SIDES:
             raise ValueError("FeatureGallery: side is 'video' or 'text', not %r" % (side,))
         core = model.module if hasattr(model, 'module') else model
-        if getattr(core, "camoe_dsl", False):
-            raise ValueError("FeatureGallery: camoe_dsl ranks S * softmax(S, dim=0) * Nt, which depends on every query at once")
+        if getattr(core, "camoe_dsl", False) and not dual_softmax:
+            raise ValueError("FeatureGallery: camoe_dsl ranks S * softmax(S, dim=0) * Nt, which depends on every query at once "
+                             "(dual_softmax=True ranks it against a registered set of captions)")
         products = HipBackend.similarity_products if products is None else int(products)
         self.backend = HipBackend.with_products(products)        # (raises for anything but 1, 2, 3)
         self.device = next(core.parameters()).device
@@ -42,12 +66,22 @@ class FeatureGallery:
         self.E = int(core.clip_config['embed_dim'])
         self._rows = torch.zeros((max(int(capacity), 0), 3 * self.E), device=self.device, dtype=torch.float16)
         self._n = 0
+        self.dual_softmax = bool(dual_softmax)
+        if self.dual_softmax:
+            self._bank = None                                    # side="video": operand rows of the captions, [n_bank, 3E]
+            self._m = torch.zeros(self._rows.shape[0], device=self.device)       # per row held (side="video"): max_t S[t, v]
+            self._s = torch.zeros(self._rows.shape[0], device=self.device)       # and sum_t exp(S[t, v] - m_v) over the bank
 
     def __len__(self):
         return self._n
 
     def clear(self):
+        """Empty the rows (a dual-softmax gallery keeps its bank)."""
         self._n = 0
+
+    @property
+    def _dsl(self):
+        return getattr(self, "dual_softmax", False)                # (an instance built without the constructor: plain)
 
     @property
     def rows(self):
@@ -93,9 +127,48 @@ class FeatureGallery:
             grown = torch.zeros((max(n, 2 * self._rows.shape[0]), 3 * self.E), device=self.device, dtype=torch.float16)
             grown[:start] = self._rows[:start]
             self._rows = grown
+            if self._dsl:
+                for name in ("_m", "_s"):
+                    stat = torch.zeros(grown.shape[0], device=self.device)
+                    stat[:start] = getattr(self, name)[:start]
+                    setattr(self, name, stat)
         self._rows[start:n] = rows
         self._n = n
+        if self._dsl:
+            self._take_stats(start, n)
         return torch.arange(start, n)
+
+    # ------------------------------------------------------------------ dual softmax: the bank and the rows' statistics
+    def _take_stats(self, start, stop):
+        """(m, s) of the clips [start, stop) over the bank (side="video" with a bank; otherwise nothing to do)"""
+        if self.side != "video" or self._bank is None or stop <= start:
+            return
+        m, s = torch.ops.centerclip.dsl_col_stats_planes(self._bank, self._rows[start:stop], self._bank.shape[0], stop - start,
+                                                         self._mult(), self.products)
+        self._m[start:stop], self._s[start:stop] = m, s
+
+    def _set_bank(self, encode, source):
+        if not self._dsl or self.side != "video":
+            raise ValueError("FeatureGallery.set_query_bank: only a dual_softmax=True gallery of side 'video' has a bank")
+        self._bank = encode(source).clone()
+        self._take_stats(0, self._n)
+
+    def set_query_bank(self, input_ids):
+        """Register the captions the dual softmax runs over (side="video", dual_softmax=True): encode them as ``search`` does,
+        keep their operand rows and take the statistics of every clip held.  Replacing the bank recomputes them all."""
+        self._set_bank(self._encode_text, input_ids)
+
+    def set_query_bank_features(self, sequence_output):
+        """``set_query_bank`` for captions encoded elsewhere (their sequence_output)."""
+        self._set_bank(self._text_rows, sequence_output)
+
+    def _query_stats(self, q):
+        """side="text": the query clips' (m, s) over the captions held"""
+        return torch.ops.centerclip.dsl_col_stats_planes(self._rows, q, self._n, q.shape[0], self._mult(), self.products)
+
+    def _need_bank(self):
+        if self.side == "video" and self._bank is None:
+            raise ValueError("FeatureGallery: dual_softmax=True needs the captions the softmax runs over: set_query_bank first")
 
     def add(self, *inputs):
         """``add(video, video_mask)`` (``add(input_ids)`` for side="text"): encode a batch as eval_epoch does and append
@@ -116,11 +189,18 @@ class FeatureGallery:
 
     def _search_rows(self, q, k):
         k = int(k)
-        if self._n == 0:                                     # nothing to rank: the fill of a list longer than the gallery
+        if self._dsl:
+            self._need_bank()
+        if self._n == 0:                                    # nothing to rank: the fill of a list longer than the gallery
             if not 1 <= k <= 128:
                 raise ValueError("FeatureGallery: 1 <= k <= 128")
             return (torch.full((q.shape[0], k), float("-inf"), device=self.device),
                     torch.full((q.shape[0], k), -1, device=self.device, dtype=torch.int64))
+        if self._dsl:
+            on_gallery = self.side == "video"
+            m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
+            return torch.ops.centerclip.similarity_topk_dsl(q, self._rows, self._n, self._mult(), self.products, k, m, s,
+                                                            int(on_gallery), self._bank.shape[0] if on_gallery else self._n)
         return torch.ops.centerclip.similarity_topk(q, self._rows, self._n, self._mult(), self.products, k)
 
     def search(self, *inputs, k=10):
@@ -142,11 +222,16 @@ class FeatureGallery:
                              dtype=torch.float16)
         padded[:n_video] = video
         sim = self.backend.dot_operands(text, padded, n_video, self._mult())
+        if self._dsl:                                            # the checking path: the matrix, then the rewrite in place
+            self._need_bank()
+            m, s = (self._m[:n], self._s[:n]) if self.side == "video" else self._query_stats(q)
+            torch.ops.centerclip.dsl_apply_(sim, m.contiguous(), s.contiguous(), self._bank.shape[0] if self.side == "video" else n)
         return sim if self.side == "video" else sim.t().contiguous()
 
     def similarity(self, *inputs):
         """The whole [Nq, len(self)] matrix of the queries ``search`` takes, through the matrix op of eval_epoch (on a zero-
-        padded copy of the video side, as that op requires): for small galleries and for checking ``search``."""
+        padded copy of the video side, as that op requires): for small galleries and for checking ``search``.  With
+        dual_softmax=True: D, by ``dsl_apply_`` on that matrix with the statistics ``search`` uses."""
         return self._matrix(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs))
 
     def similarity_features(self, features, mask=None):
@@ -154,13 +239,22 @@ class FeatureGallery:
 
     # ------------------------------------------------------------------ persistence
     def state_dict(self):
-        return {"rows": self._rows[:self._n].clone(), "count": self._n, "E": self.E, "side": self.side,
-                "products": self.products}
+        state = {"rows": self._rows[:self._n].clone(), "count": self._n, "E": self.E, "side": self.side,
+                 "products": self.products}
+        if self._dsl:                                            # (a plain gallery's keys are what they were)
+            state.update(dual_softmax=True, bank=None if self._bank is None else self._bank.clone(),
+                         m=self._m[:self._n].clone(), s=self._s[:self._n].clone())
+        return state
 
     def load_state_dict(self, state):
         """Replace the contents with a saved gallery's.  E or side that differ from this gallery's: ValueError, nothing
-        written.  The saved ``products`` are taken over, so the loaded gallery answers with the saved one's bits."""
+        written; the same for a plain gallery's state into a dual_softmax=True gallery, or the reverse.  The saved ``products``
+        are taken over - with dual_softmax=True the bank and the statistics too - so the loaded gallery answers with the saved
+        one's bits."""
         rows, count = state["rows"], int(state["count"])
+        if bool(state.get("dual_softmax", False)) != self._dsl:
+            raise ValueError("FeatureGallery.load_state_dict: saved dual_softmax=%s, this gallery dual_softmax=%s"
+                             % (bool(state.get("dual_softmax", False)), self._dsl))
         if int(state["E"]) != self.E or state["side"] != self.side:
             raise ValueError("FeatureGallery.load_state_dict: saved (E=%s, side=%r), this gallery (E=%d, side=%r)"
                              % (state["E"], state["side"], self.E, self.side))
@@ -168,9 +262,20 @@ class FeatureGallery:
             raise ValueError("FeatureGallery.load_state_dict: rows %s %s do not match count %d, E %d"
                              % (tuple(rows.shape), rows.dtype, count, self.E))
         backend = HipBackend.with_products(int(state["products"]))
+        if self._dsl:
+            bank, m, s = state["bank"], state["m"], state["s"]
+            if bank is not None and (bank.dim() != 2 or bank.shape[1] != 3 * self.E or bank.dtype != torch.float16):
+                raise ValueError("FeatureGallery.load_state_dict: bank rows %s %s, E %d" % (tuple(bank.shape), bank.dtype, self.E))
+            if tuple(m.shape) != (count,) or tuple(s.shape) != (count,) or m.dtype != torch.float32 or s.dtype != torch.float32:
+                raise ValueError("FeatureGallery.load_state_dict: statistics %s, %s do not match count %d"
+                                 % (tuple(m.shape), tuple(s.shape), count))
+            self._bank = None                                    # (the saved statistics are taken over, not recomputed)
         self._n = 0
         self._append(rows.to(self.device))
         self.products, self.backend = int(state["products"]), backend
+        if self._dsl:
+            self._bank = None if bank is None else bank.to(self.device).clone()
+            self._m[:count], self._s[:count] = m.to(self.device), s.to(self.device)
 
 
 __all__ = ["FeatureGallery"]

@@ -1198,6 +1198,73 @@ def _(query_planes, gallery_planes, n_gallery, mult, products, k):
             query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
 
 
+def _check_plane_pair(name, a, b, rows_b):
+    E3 = a.shape[1]
+    if b.dim() != 2 or b.shape[1] != E3 or b.shape[0] < int(rows_b):
+        raise ValueError("%s: planes %s do not hold %d rows of %d halfs" % (name, tuple(b.shape), int(rows_b), E3))
+    if a.dtype != torch.float16 or b.dtype != torch.float16:
+        raise ValueError("%s: plane rows are fp16" % name)
+    return E3
+
+
+@custom_op(NS + "::dsl_col_stats_planes", mutates_args=(), device_types="cuda")
+def dsl_col_stats_planes(text_planes: torch.Tensor, video_planes: torch.Tensor, n_text: int, n_video: int, mult: float,
+                         products: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """camoe_dsl without the matrix: (m [n_video], s [n_video]) = dsl_col_stats of the matrix scaled_dot_planes gives for the
+    first n_text text rows and the first n_video video rows (m bit-equal; s in a fixed order that depends on n_text alone, so a
+    video row's pair is the same bits whichever rows share the call).  Neither side needs padding rows.  n_text == 0 gives
+    (-inf, 0).  cc_dsl_col_stats_planes_f32."""
+    E3 = _check_plane_pair("dsl_col_stats_planes", video_planes, text_planes, n_text)
+    if video_planes.dim() != 2 or video_planes.shape[0] < int(n_video):
+        raise ValueError("dsl_col_stats_planes: video planes %s do not hold %d rows" % (tuple(video_planes.shape), int(n_video)))
+    text_planes, video_planes = text_planes.contiguous(), video_planes.contiguous()
+    m = _e(int(n_video), like=video_planes, dtype=torch.float32)
+    s = _e(int(n_video), like=video_planes, dtype=torch.float32)
+    lib = L.lib()
+    ws = L.workspace(lib.cc_dsl_col_stats_planes_workspace_bytes(int(n_text), int(n_video)), video_planes.device)
+    L.check(lib.cc_dsl_col_stats_planes_f32(L.ptr(text_planes), L.ptr(video_planes), int(n_text), int(n_video), E3 // 3,
+                                            float(mult), int(products), L.ptr(m), L.ptr(s), L.ptr(ws), ws.numel(),
+                                            _st(video_planes)), "cc_dsl_col_stats_planes_f32")
+    return m, s
+
+
+@dsl_col_stats_planes.register_fake
+def _(text_planes, video_planes, n_text, n_video, mult, products):
+    return (video_planes.new_empty((n_video,), dtype=torch.float32), video_planes.new_empty((n_video,), dtype=torch.float32))
+
+
+@custom_op(NS + "::similarity_topk_dsl", mutates_args=(), device_types="cuda")
+def similarity_topk_dsl(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                        k: int, m: torch.Tensor, s: torch.Tensor, stats_on_gallery: int,
+                        n_total: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """similarity_topk ranking the dual softmax D = n_total * S * exp(S - m[x]) / s[x] instead of S: x is the gallery row
+    (stats_on_gallery = 1: m, s hold at least n_gallery entries) or the query row (0: m, s [Bq]).  A score has the bits dsl_apply_
+    writes over scaled_dot_planes' entry; order, fill and limits are similarity_topk's.  cc_similarity_topk_dsl_planes_f32."""
+    Bq = query_planes.shape[0]
+    E3 = _check_plane_pair("similarity_topk_dsl", query_planes, gallery_planes, n_gallery)
+    need = int(n_gallery) if stats_on_gallery else Bq
+    if m.dim() != 1 or s.dim() != 1 or m.shape[0] < need or s.shape[0] < need or m.dtype != torch.float32 or s.dtype != torch.float32:
+        raise ValueError("similarity_topk_dsl: m %s, s %s are not fp32 vectors of at least %d entries"
+                         % (tuple(m.shape), tuple(s.shape), need))
+    query_planes, gallery_planes, m, s = query_planes.contiguous(), gallery_planes.contiguous(), m.contiguous(), s.contiguous()
+    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
+    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
+    lib = L.lib()
+    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
+    L.check(lib.cc_similarity_topk_dsl_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
+                                                  float(mult), int(products), int(k), L.ptr(m), L.ptr(s),
+                                                  int(stats_on_gallery), int(n_total), L.ptr(scores), L.ptr(ids),
+                                                  L.ptr(ws), ws.numel(), _st(query_planes)),
+            "cc_similarity_topk_dsl_planes_f32")
+    return scores, ids.to(torch.int64)
+
+
+@similarity_topk_dsl.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, k, m, s, stats_on_gallery, n_total):
+    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
+            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+
+
 def padded_video_rows(n_video):
     """Rows a video-side plane buffer needs for n_video videos (whole GEMM tiles; the rows behind n_video must be zero)."""
     return int(L.lib().cc_similarity_padded_rows(int(n_video)))
@@ -1452,7 +1519,7 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "loose_similarity", "video_pool_normalize", "normalize_rows", "scaled_dot_nt", "scaled_dot_nt_out", "rank_counts",
        "rank_counts_cols", "rank_counts_ref", "group_max_rows", "normalize_rows_planes", "video_pool_normalize_planes",
        "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
-       "resize_center_crop", "resize_center_crop_out", "similarity_topk")
+       "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl")
 
 
 def logit_multiplier(logit_scale):

@@ -9,6 +9,12 @@ device events around every call, the two paths alternating, after a warm-up.
 
     python examples/search_synthetic.py [--clips 40] [--k 5] [--time-rows 200000] [--time-queries 16] [--time-k 10] [--reps 50]
     python examples/search_synthetic.py --clips 0 --time-rows 200000     (the timing alone)
+
+--camoe_dsl 1 does the same under the CAMoE dual softmax (FeatureGallery(dual_softmax=True)): a clip gallery with the captions
+as its bank, a caption gallery asked with clips, and the timing of similarity_topk_dsl against the plain op and of the
+statistics pass (dsl_col_stats_planes) against the matrix op in blocks + dsl_col_stats.
+
+    python examples/search_synthetic.py --camoe_dsl 1 [--time-bank 1000]
 """
 import argparse
 import os
@@ -88,6 +94,80 @@ def time_search(model, device, rows, queries, k, reps, warmup):
           % (read, read / 1e6, queries * rows * 4, L.lib().cc_similarity_topk_workspace_bytes(queries, rows, k)))
 
 
+def report(title, times):
+    print("\n" + title)
+    for name, ms in times.items():
+        print("  %-64s median %9.1f us   min %9.1f   max %9.1f" % (name, 1e3 * statistics.median(ms), 1e3 * min(ms), 1e3 * max(ms)))
+
+
+def time_dsl(model, device, rows, queries, k, bank, reps, warmup):
+    """similarity_topk_dsl against similarity_topk on `queries` x `rows`, and the statistics pass at rows x bank (a clip
+    gallery's add) and queries x rows (a caption gallery's search) against the matrix op + dsl_col_stats"""
+    op = torch.ops.centerclip
+    E = int(model.clip_config['embed_dim'])
+    g = torch.Generator(device=device).manual_seed(1)
+    unit = lambda n, video_side: op.normalize_rows_planes(torch.randn(n, E, device=device, generator=g), video_side)
+    gallery = FeatureGallery(model)
+    products, mult = gallery.products, T.logit_multiplier(model._logit_scale_value())
+    clips, captions = unit(rows, True), unit(rows, False)                     # a clip gallery, a caption gallery
+    text_q, clip_q, bank_rows = unit(queries, False), unit(queries, True), unit(bank, False)
+    m_g, s_g = op.dsl_col_stats_planes(bank_rows, clips, bank, rows, mult, products)
+    m_q, s_q = op.dsl_col_stats_planes(captions, clip_q, rows, queries, mult, products)
+    fns = [("similarity_topk (plain)", lambda: op.similarity_topk(text_q, clips, rows, mult, products, k)),
+           ("similarity_topk_dsl, statistics per gallery row", lambda: op.similarity_topk_dsl(text_q, clips, rows, mult, products, k,
+                                                                                            m_g, s_g, 1, bank)),
+           ("similarity_topk_dsl, statistics per query row", lambda: op.similarity_topk_dsl(clip_q, captions, rows, mult, products,
+                                                                                          k, m_q, s_q, 0, rows))]
+    report("%d queries x %d gallery rows, E = %d, products = %d, k = %d: %d repetitions after %d warm-up rounds, device events"
+           % (queries, rows, E, products, k, reps, warmup), timed(fns, warmup, reps))
+
+    def blocks(text, video, n_video, block):
+        """what a user had before: the matrix op on zero-padded blocks of the video rows, then the column statistics"""
+        ms, ss = [], []
+        for at in range(0, n_video, block):
+            b = min(block, n_video - at)
+            padded = torch.zeros(max(b, T.padded_video_rows(b)), 3 * E, device=device, dtype=torch.float16)
+            padded[:b] = video[at:at + b]
+            mb, sb = op.dsl_col_stats(op.scaled_dot_planes(text, padded, b, mult, products))
+            ms.append(mb)
+            ss.append(sb)
+        return torch.cat(ms), torch.cat(ss)
+    for title, text, video, nt, nv, block in (("a clip gallery's add", bank_rows, clips, bank, rows, 16384),
+                                              ("a caption gallery's search", captions, clip_q, rows, queries, queries)):
+        a, b = op.dsl_col_stats_planes(text, video, nt, nv, mult, products), blocks(text, video, nv, block)
+        assert torch.equal(a[0], b[0]), "the two paths disagree on the maxima"
+        fns = [("dsl_col_stats_planes", lambda: op.dsl_col_stats_planes(text, video, nt, nv, mult, products)),
+               ("scaled_dot_planes on padded blocks of %d + dsl_col_stats" % block, lambda: blocks(text, video, nv, block))]
+        report("statistics of %d video rows over %d text rows (%s): workspace %d bytes, the matrix %d bytes"
+               % (nv, nt, title, L.lib().cc_dsl_col_stats_planes_workspace_bytes(nt, nv), nt * nv * 4), timed(fns, warmup, reps))
+
+
+def dsl_part(model, device, a):
+    """both sides under the dual softmax on encoded synthetic clips: the captions are the bank of the clip gallery"""
+    data = SyntheticRetrieval(a.clips)
+    ids = data.ids.to(device)
+    gallery = FeatureGallery(model, dual_softmax=True)
+    start = 0
+    for b in uneven(a.clips):                                                # (clips before the bank or after it: the same bits)
+        gallery.add(data.video[start:start + b].to(device), data.vmask[start:start + b].to(device))
+        start += b
+    gallery.set_query_bank(ids)
+    scores, found = gallery.search(ids[:a.captions], k=a.k)
+    for i in range(scores.shape[0]):
+        print("caption %d: clips %s  dual-softmax scores %s" % (i, found[i].tolist(), ["%.4f" % s for s in scores[i].tolist()]))
+    D = gallery.similarity(ids)
+    full = torch.topk(D[:a.captions], min(a.k, len(gallery)), dim=1)
+    print("same scores as dsl_apply_ on the matrix: %s" % bool(torch.equal(full.values, scores[:, :full.values.shape[1]])))
+    captions = FeatureGallery(model, side="text", dual_softmax=True)
+    captions.add(ids)
+    video, vmask = data.video[:a.captions].to(device), data.vmask[:a.captions].to(device)
+    scores, found = captions.search(video, vmask, k=a.k)
+    for i in range(scores.shape[0]):
+        print("clip %d: captions %s  dual-softmax scores %s" % (i, found[i].tolist(), ["%.4f" % s for s in scores[i].tolist()]))
+    full = torch.topk(captions.similarity(video, vmask), min(a.k, len(captions)), dim=1)
+    print("same scores as dsl_apply_ on the matrix: %s" % bool(torch.equal(full.values, scores[:, :full.values.shape[1]])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=40, help="clips encoded into the gallery (0: skip the model part)")
@@ -98,10 +178,18 @@ def main():
     ap.add_argument("--time-k", type=int, default=10)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--camoe_dsl", type=int, default=0, help="1: the dual softmax (FeatureGallery(dual_softmax=True))")
+    ap.add_argument("--time-bank", type=int, default=1000, help="--camoe_dsl 1: captions in the bank of the timed clip gallery")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), bench.task_config(c)).to(device).eval()
+    if a.camoe_dsl:
+        if a.clips:
+            dsl_part(model, device, a)
+        if a.time_rows:
+            time_dsl(model, device, a.time_rows, a.time_queries, a.time_k, a.time_bank, a.reps, a.warmup)
+        return
     if a.clips:
         data = SyntheticRetrieval(a.clips)
         gallery = FeatureGallery(model)

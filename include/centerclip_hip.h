@@ -783,6 +783,43 @@ size_t cc_similarity_topk_workspace_bytes(int32_t Bq, int32_t Bg, int32_t k);
 int cc_similarity_topk_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
                                   float mult, int32_t products, int32_t k, float* scores, int32_t* ids, void* ws,
                                   size_t ws_bytes, void* stream);
+/* Top-k search under the CAMoE dual softmax (camoe_dsl), still without a matrix.  D[i, j] = n * S[i, j] * exp(S[i, j] - m_j) / s_j
+ * needs two floats per VIDEO row j: m_j = max_i S[i, j] and s_j = sum_i exp(S[i, j] - m_j) over the text rows i.
+ *
+ * cc_dsl_col_stats_planes_f32: m[Bv], s[Bv] = what cc_dsl_col_stats_f32 gives on the matrix cc_scaled_dot_planes_products_f32
+ * stores for the same planes (texts as rows), computed from the plane rows.  Only the first Bt text rows and the first Bv
+ * video rows are read (no padding, rows behind them may hold anything); Bt == 0 gives (-inf, 0) (text_planes and ws may then
+ * be NULL).  Non-finite plane values are outside the contract.
+ *   Every S(i, j) has the matrix op's bits (one fp32 accumulator, 32-wide k-slices ascending, the operand order of
+ *   gemm_f16_kernel, then sc * acc as described above), so m is BIT-EQUAL to the column maximum of that matrix.
+ *   s: fixed summation tree, no atomics, the same bits on every run.  The text rows are cut into
+ *   cc_dsl_col_stats_planes_slices(Bt) contiguous slices of 16-row tiles - a function of Bt alone - so the pair of a video
+ *   row does not depend on Bv or on the rows that share the call: adding clips in batches equals adding them at once.
+ *   Tree: a lane folds 4 text rows a step into a running pair (online rescale: s <- s * expf(m - m') + sum of 4 expf(x - m'),
+ *   7 roundings a step for an old term, ceil(ceil(tiles / slices) / 4) steps at most, tiles = ceil(Bt / 16)); the 16 pairs
+ *   of a workgroup are merged in a fixed order (19 roundings), the slices' pairs in slice order by a second launch
+ *   (slices + 3).  Longest chain of roundings: 7 * ceil(ceil(tiles / slices) / 4) + 19 + slices + 3 (search.hip).
+ *   Two launches, no host synchronisation (capturable); no workgroup reads what another one of the same launch wrote.
+ *   ws: cc_dsl_col_stats_planes_workspace_bytes(Bt, Bv) = slices * Bv pairs; nothing of size Bt * Bv exists.
+ * Limits: products 1..3, E % 64 == 0, E <= 1024, Bv <= 16 * 65535: CC_ERR_UNSUPPORTED.  NULL operands, Bt < 0, Bv <= 0 or
+ * E <= 0: CC_ERR_INVALID; a NULL or short workspace (Bt > 0): CC_ERR_WORKSPACE - in this order, before anything is launched.
+ *
+ * cc_similarity_topk_dsl_planes_f32: cc_similarity_topk_planes_f32 ranking D instead of S,
+ *   D(q, g) = (n_total * S) * (expf(S - m[x]) / s[x]),  x = g (stats_on_gallery = 1: a gallery of clips, text queries) or
+ *   x = q (stats_on_gallery = 0: a gallery of captions, clip queries; m, s [Bq]),
+ * evaluated with the fp32 operations of cc_dsl_apply_f32: a score has the bits that entry point writes over the matrix op's
+ * entry for the same m, s, n_total.  The order contract is the plain op's (stable descending, equal scores by smaller id,
+ * -0 == +0 with the sign restored, (-inf, -1) beyond Bg; +-inf order as floats; NaN scores are outside the contract).
+ * Rows at or above Bg are never read, their statistics included.  Limits, workspace (cc_similarity_topk_workspace_bytes)
+ * and the two launches are the plain op's; NULL m or s, n_total < 0 or stats_on_gallery other than 0 / 1: CC_ERR_INVALID. */
+int32_t cc_dsl_col_stats_planes_slices(int32_t Bt);
+size_t cc_dsl_col_stats_planes_workspace_bytes(int32_t Bt, int32_t Bv);
+int cc_dsl_col_stats_planes_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv, int32_t E, float mult,
+                                int32_t products, float* m, float* s, void* ws, size_t ws_bytes, void* stream);
+int cc_similarity_topk_dsl_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                      float mult, int32_t products, int32_t k, const float* m, const float* s,
+                                      int32_t stats_on_gallery, int32_t n_total, float* scores, int32_t* ids, void* ws,
+                                      size_t ws_bytes, void* stream);
 int cc_video_pool_normalize_f32(const float* visual, const int64_t* video_mask, int32_t Bv, int32_t Tn,
                                 int32_t E, float* pooled, void* stream);
 int cc_loose_similarity_f32(const float* text, const float* visual, const int64_t* video_mask,
