@@ -34,6 +34,11 @@
 //       - second launch (dsl.hip's merge): the slices' pairs under their maximum, added in slice order: 2 + 1 + slices.
 //     The subtractions inside expf telescope: the partial maxima rise from x to m, so together they cost |x - m| U on the
 //     exponent.  Longest chain of roundings: 7 * ceil(ceil(tiles / slices) / 4) + 19 + slices + 3.
+//
+// Grouped search (the k best GROUPS of adjacent rows, each by its best row) on the same stream: topk_stream_kernel<DSL, true>,
+// a second compile-time mode.  A row's score is computed as before; a wave then takes one contiguous row range between group
+// starts instead of interleaved tiles and hands tk_insert_tile one candidate per finished group (tk_group_tile), so every
+// group lives in one list of one wave and the fold, the workspace and the merge launch are unchanged.
 #include "cc_kernels.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -165,7 +170,7 @@ __device__ __forceinline__ void tk_stage_rows(_Float16* qs, const _Float16* __re
     }
 }
 
-// The stream of one wave: the 16-row tiles t0 + wave, t0 + wave + 4, ... < t1 of `gallery` (Bg rows, `ld` halfs apart, the first
+// The stream of one wave: the 16-row tiles first, first + stride, ... < t1 of `gallery` (Bg rows, `ld` halfs apart, the first
 // K multiplied) against the 16 staged rows (`qrow`: the lane's fragments of staged row l15).  Behind a tile's last k-slice
 // on_tile(t, acc) gets the 16 x 16 products: the lane holds streamed rows t * 16 + 4 lg + r (r = 0..3) of staged row l15, each
 // ONE fp32 accumulator over the k-slices in ascending order, the streamed fragment as the first operand.  before_last(t) runs
@@ -177,7 +182,8 @@ __device__ __forceinline__ void tk_stage_rows(_Float16* qs, const _Float16* __re
 // multiplied).
 template <class Before, class Tile>
 __device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gallery, int Bg, int ld, int K, const _Float16* qrow,
-                                                int t0, int t1, int wave, int l15, int lg, Before&& before_last, Tile&& on_tile) {
+                                                int first, int stride, int t1, int l15, int lg, Before&& before_last,
+                                                Tile&& on_tile) {
     const int nk2 = K >> 6;                                                            // pairs of k-slices: one 128-byte line per row
     auto load_batch = [&](h8 (&b)[2 * TK_BATCH], int t, int s0) {
         const int grow = min(t * 16 + l15, Bg - 1);                                    // rows at Bg or above are never read
@@ -190,9 +196,9 @@ __device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gal
         }
     };
     const int nb = (nk2 + TK_BATCH - 1) / TK_BATCH;                                    // batches of a tile
-    const int my_tiles = t0 + wave < t1 ? (t1 - t0 - wave + TK_WAVES - 1) / TK_WAVES : 0;
-    const int total = my_tiles * nb, t_last = t0 + wave + (my_tiles - 1) * TK_WAVES;
-    int t = t0 + wave, b = 0;                                                          // the batch about to be multiplied
+    const int my_tiles = first < t1 ? (t1 - first + stride - 1) / stride : 0;
+    const int total = my_tiles * nb, t_last = first + (my_tiles - 1) * stride;
+    int t = first, b = 0;                                                              // the batch about to be multiplied
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     auto step = [&](const h8 (&cur)[2 * TK_BATCH], h8 (&nxt)[2 * TK_BATCH]) {
         // (the request is unconditional - behind the wave's last batch it repeats the last tile's first, a cache hit that
@@ -200,7 +206,7 @@ __device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gal
         // and on the other path it then waits for the batch just requested)
         const bool last = b + 1 == nb;
         if (last) before_last(t);
-        load_batch(nxt, last ? min(t + TK_WAVES, t_last) : t, last ? 0 : (b + 1) * TK_BATCH);
+        load_batch(nxt, last ? min(t + stride, t_last) : t, last ? 0 : (b + 1) * TK_BATCH);
 #pragma unroll
         for (int u = 0; u < TK_BATCH; ++u) {
             const int s = b * TK_BATCH + u;
@@ -214,7 +220,7 @@ __device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gal
         if (!last) { ++b; return; }
         on_tile(t, acc);
         acc = f32x4{0.f, 0.f, 0.f, 0.f};
-        t += TK_WAVES;
+        t += stride;
         b = 0;
     };
     h8 buf0[2 * TK_BATCH], buf1[2 * TK_BATCH];
@@ -225,14 +231,63 @@ __device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gal
     }
 }
 
+// Grouped search, one tile of a wave's row range: key[r] (in) is the key of streamed row 4 lg + r of the tile for query row
+// l15, 0 for a row outside the range; head[r] says that the row is the first of its group (the same in all 16 query rows).
+// The rows of a range arrive in ascending order, so a group's rows arrive one after the other: `carry` - the same value in
+// the 4 lanes of a query row - is the best key of the group still open in front of the tile.  A segmented maximum over the
+// 16 rows in row order, started from the carry, replaces the keys: key[r] (out) = the best key of the group that ENDS in
+// front of row 4 lg + r (head[r]; 0 otherwise), at most one candidate a row, and the group open behind row 15 is the new
+// carry.  Keys are unique and 0 is the empty key: the maximum of keys is "best score, smallest id", and max with 0 changes
+// nothing.  Across the 4 lanes: every lane gets the 4 lanes' tails (the open group's best behind the lane's 4 rows, started
+// from nothing) by three row swaps, and a ballot tells which lanes saw a head.
+__device__ __forceinline__ void tk_group_tile(u64 (&key)[4], const bool (&head)[4], int lg, u64& carry) {
+    u64 tail = 0;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tail = (head[r] || key[r] > tail) ? key[r] : tail;
+    const u64 any = __ballot(head[0] || head[1] || head[2] || head[3]);               // bit 16 g: lane group g saw a head
+    u64 tails[4];
+    {
+        const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)tail, (unsigned)tail, false, false);
+        const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(tail >> 32), (unsigned)(tail >> 32), false, false);
+        const unsigned elo = lo[0], olo = lo[1], ehi = hi[0], ohi = hi[1];             // of the even / odd lane group of the pair
+        const auto el = __builtin_amdgcn_permlane32_swap(elo, elo, false, false);
+        const auto eh = __builtin_amdgcn_permlane32_swap(ehi, ehi, false, false);
+        const auto ol = __builtin_amdgcn_permlane32_swap(olo, olo, false, false);
+        const auto oh = __builtin_amdgcn_permlane32_swap(ohi, ohi, false, false);
+        tails[0] = ((u64)eh[0] << 32) | el[0];
+        tails[1] = ((u64)oh[0] << 32) | ol[0];
+        tails[2] = ((u64)eh[1] << 32) | el[1];
+        tails[3] = ((u64)oh[1] << 32) | ol[1];
+    }
+    u64 run = carry, in = carry;                                                       // in: the open group in front of this lane's rows
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        run = ((any >> (16 * g)) & 1) ? tails[g] : (tails[g] > run ? tails[g] : run);
+        if (g < 3) in = lg > g ? run : in;
+    }
+    carry = run;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const u64 x = key[r];
+        key[r] = head[r] ? in : 0;
+        in = (head[r] || x > in) ? x : in;
+    }
+}
+
 // query / gallery: plane rows `ld` halfs apart, the first K of them multiplied.  ws [Bq][k][slices] keys.  DSL: the score is
-// cc_dsl_value(nt, S, m, s) with the pair of the gallery row (on_gallery) or of the query row; without DSL the last four
-// arguments are not read.
-template <bool DSL>
+// cc_dsl_value(nt, S, m, s) with the pair of the gallery row (on_gallery) or of the query row; without DSL those four
+// arguments are not read.  GROUPED: group_head[r] = the first row of r's group (the rows of a group are adjacent); a list
+// then holds the best row of every group, not every row.  Instead of the interleaved tiles of its slice a wave takes ONE
+// contiguous row range whose ends are group starts: the 4 * slices + 1 even shares of the tiles, each planned row b snapped
+// down to group_head[b] (monotone; a range may be empty; a group longer than a share belongs wholly to the range that
+// starts at its head).  Every group lives in one wave, so the fold, the workspace and the merge launch see lists whose
+// groups are disjoint and work unchanged.  Only the snapping indexes with a value of group_head, and clamps it to [0, b].
+template <bool DSL, bool GROUPED>
 __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
                                                           int Bq, int Bg, int ld, int K, float sc, int k, int slices,
                                                           u64* __restrict__ ws, const float* __restrict__ stat_m,
-                                                          const float* __restrict__ stat_s, int on_gallery, float nt) {
+                                                          const float* __restrict__ stat_s, int on_gallery, float nt,
+                                                          const int* __restrict__ group_head) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
     const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
@@ -258,32 +313,64 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
             for (int r = 0; r < 4; ++r) { dm[r] = stat_m[qr]; ds[r] = stat_s[qr]; }
         }
     }
-    tk_stream_tiles(
-        gallery, Bg, ld, K, qs + l15 * QS + lg * 8, t0, t1, wave, l15, lg,
-        [&](int t) {
-            if constexpr (DSL) {
-                if (on_gallery) {
+    // GROUPED: the wave's row range [r0, r1) and the open group's best key (tk_group_tile); the lane's 4 heads come per tile
+    int first = t0 + wave, last = t1, r0 = 0, r1 = Bg;
+    u64 carry = 0;
+    int gh[4] = {0, 0, 0, 0};
+    if constexpr (GROUPED) {
+        auto bound = [&](int j) {
+            if (j <= 0) return 0;
+            if (j >= TK_WAVES * slices) return Bg;
+            const int b = min((int)((int64_t)tiles * j / (TK_WAVES * slices)) * 16, Bg - 1);
+            return min(max(group_head[b], 0), b);                                      // (a malformed head stays inside the rows)
+        };
+        r0 = bound(TK_WAVES * slice + wave);
+        r1 = bound(TK_WAVES * slice + wave + 1);
+        first = r0 >> 4;
+        last = r1 > r0 ? (r1 + 15) >> 4 : first;                                       // the tile at a boundary: both neighbours' work
+    }
+    auto before_last = [&](int t) {
+        if constexpr (DSL) {
+            if (on_gallery) {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int id = min(t * 16 + lg * 4 + r, Bg - 1);               // statistics at Bg or above are never read
-                        dm[r] = stat_m[id];
-                        ds[r] = stat_s[id];
-                    }
+                for (int r = 0; r < 4; ++r) {
+                    const int id = min(t * 16 + lg * 4 + r, Bg - 1);                   // statistics at Bg or above are never read
+                    dm[r] = stat_m[id];
+                    ds[r] = stat_s[id];
                 }
             }
-        },
-        [&](int t, const f32x4& acc) {
-            // the lane holds gallery rows t * 16 + 4 lg + r (r = 0..3) of query row l15
-            u64 key[4];
+        }
+        if constexpr (GROUPED) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int id = t * 16 + lg * 4 + r;
-                float x = sc * acc[r];
-                if constexpr (DSL) x = cc_dsl_value(nt, x, dm[r], ds[r]);
+            for (int r = 0; r < 4; ++r) gh[r] = group_head[min(t * 16 + lg * 4 + r, Bg - 1)];      // nor heads
+        }
+    };
+    auto on_tile = [&](int t, const f32x4& acc) {
+        // the lane holds gallery rows t * 16 + 4 lg + r (r = 0..3) of query row l15
+        u64 key[4];
+        bool head[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int id = t * 16 + lg * 4 + r;
+            float x = sc * acc[r];
+            if constexpr (DSL) x = cc_dsl_value(nt, x, dm[r], ds[r]);
+            if constexpr (GROUPED) {
+                key[r] = (qvalid && id >= r0 && id < r1) ? tk_key(x, id) : 0;
+                head[r] = gh[r] == id;
+            } else {
                 key[r] = (qvalid && id < Bg) ? tk_key(x, id) : 0;
             }
-            tk_insert_tile(key, mine, k, lg, thr, filled);
-        });
+        }
+        if constexpr (GROUPED) tk_group_tile(key, head, lg, carry);
+        tk_insert_tile(key, mine, k, lg, thr, filled);
+    };
+    if constexpr (GROUPED) {
+        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, first, 1, last, l15, lg, before_last, on_tile);
+        u64 key[4] = {lg == 0 ? carry : 0, 0, 0, 0};                                   // the group open at the range's end
+        tk_insert_tile(key, mine, k, lg, thr, filled);
+    } else {
+        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, first, TK_WAVES, last, l15, lg, before_last, on_tile);
+    }
     // the four waves' lists -> wave 0's, as a tree: the other wave's entries are the candidates, 16 a list at a time
     auto fold = [&](int from) {
         const u64* other = lists + ((size_t)from * TK_QROWS + l15) * k;
@@ -370,7 +457,7 @@ __global__ __launch_bounds__(256) void dsl_stats_stream_kernel(const _Float16* _
     const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
     float m = -INFINITY, s = 0.f;                                                      // of video row l15 over the lane's text rows
     tk_stream_tiles(
-        text, Bt, ld, K, vs + l15 * (K + TK_QPAD) + lg * 8, t0, t1, wave, l15, lg, [](int) {},
+        text, Bt, ld, K, vs + l15 * (K + TK_QPAD) + lg * 8, t0 + wave, TK_WAVES, t1, l15, lg, [](int) {},
         [&](int t, const f32x4& acc) {
             float x[4], mt = m;
             bool in[4];
@@ -428,11 +515,12 @@ size_t cc_similarity_topk_workspace_bytes(int32_t Bq, int32_t Bg, int32_t k) {
 }
 
 // the checks and the two launches of both top-k entries; dsl: m, s, on_gallery, n_total of the rewrite
-static int tk_launch(bool dsl, const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E, float mult,
-                     int32_t products, int32_t k, const float* m, const float* s, int32_t on_gallery, int32_t n_total,
-                     float* scores, int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
+static int tk_launch(bool dsl, bool grouped, const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                     float mult, int32_t products, int32_t k, const float* m, const float* s, int32_t on_gallery, int32_t n_total,
+                     const int32_t* group_head, float* scores, int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
     if (!query_planes || !gallery_planes || !scores || !ids || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
     if (dsl && (!m || !s || n_total < 0 || (on_gallery != 0 && on_gallery != 1))) return CC_ERR_INVALID;
+    if (grouped && !group_head) return CC_ERR_INVALID;
     if (k < 1 || k > TK_MAXK || products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
     const int K = products * E;
     const size_t smem = tk_stream_lds(K, k);
@@ -441,12 +529,13 @@ static int tk_launch(bool dsl, const void* query_planes, const void* gallery_pla
     if (!ws || ws_bytes < cc_similarity_topk_workspace_bytes(Bq, Bg, k)) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int slices = tk_slices(Bq, Bg);
-    const auto kernel = dsl ? topk_stream_kernel<true> : topk_stream_kernel<false>;
+    const auto kernel = grouped ? (dsl ? topk_stream_kernel<true, true> : topk_stream_kernel<false, true>)
+                                : (dsl ? topk_stream_kernel<true, false> : topk_stream_kernel<false, false>);
     if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
     hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
                        static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K,
                        mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, k, slices, static_cast<u64*>(ws), m, s,
-                       on_gallery, (float)n_total);
+                       on_gallery, (float)n_total, group_head);
     CC_LAUNCH_CHECK();
     hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(ws), slices, k, scores, ids);
     CC_LAUNCH_CHECK();
@@ -456,16 +545,31 @@ static int tk_launch(bool dsl, const void* query_planes, const void* gallery_pla
 int cc_similarity_topk_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
                                   float mult, int32_t products, int32_t k, float* scores, int32_t* ids, void* ws,
                                   size_t ws_bytes, void* stream) {
-    return tk_launch(false, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, nullptr, nullptr, 0, 0, scores, ids, ws,
-                     ws_bytes, stream);
+    return tk_launch(false, false, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, nullptr, nullptr, 0, 0, nullptr,
+                     scores, ids, ws, ws_bytes, stream);
 }
 
 int cc_similarity_topk_dsl_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
                                       float mult, int32_t products, int32_t k, const float* m, const float* s,
                                       int32_t stats_on_gallery, int32_t n_total, float* scores, int32_t* ids, void* ws,
                                       size_t ws_bytes, void* stream) {
-    return tk_launch(true, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s, stats_on_gallery, n_total, scores,
-                     ids, ws, ws_bytes, stream);
+    return tk_launch(true, false, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s, stats_on_gallery, n_total,
+                     nullptr, scores, ids, ws, ws_bytes, stream);
+}
+
+int cc_similarity_topk_grouped_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                          float mult, int32_t products, int32_t k, const int32_t* group_head, float* scores,
+                                          int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
+    return tk_launch(false, true, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, nullptr, nullptr, 0, 0, group_head,
+                     scores, ids, ws, ws_bytes, stream);
+}
+
+int cc_similarity_topk_grouped_dsl_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg,
+                                              int32_t E, float mult, int32_t products, int32_t k, const float* m, const float* s,
+                                              int32_t stats_on_gallery, int32_t n_total, const int32_t* group_head, float* scores,
+                                              int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
+    return tk_launch(true, true, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s, stats_on_gallery, n_total,
+                     group_head, scores, ids, ws, ws_bytes, stream);
 }
 
 int32_t cc_dsl_col_stats_planes_slices(int32_t Bt) { return Bt > 0 ? dsl_stats_slices(Bt) : 0; }

@@ -19,7 +19,16 @@ which ``torch.ops.centerclip.dsl_col_stats_planes`` takes from the operand rows 
     gallery.set_query_bank(all_input_ids)                 # before or after the clips: the same bits
     gallery.add(video, video_mask)
     scores, ids = gallery.search(input_ids, k=10)         # rows of eval_epoch's text->video D for captions of the bank
+
+``grouped=True`` ranks GROUPS of adjacent rows, each by its best row - the sentences of a video (the multi-sentence sets:
+eval_epoch ranks video->text on the maximum over a video's sentences) or the windows of a long video - with
+``similarity_topk_grouped`` (``_dsl``): still one pass, no matrix, exact.
+
+    gallery = FeatureGallery(model, side="text", grouped=True)
+    gallery.add(input_ids, group=video_index)             # one label for the batch, or one per row; equal neighbours = a group
+    scores, groups, pos = gallery.search_groups(video, video_mask, k=10)    # the 10 best videos, each by its best sentence
 """
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -48,9 +57,19 @@ class FeatureGallery:
         moment: set the bank again after changing it.
       * side="text": no bank (``set_query_bank*`` raises ValueError).  Every search first takes the query clips' pairs over the
         captions held (n_total = len(self)), then the top-k: two passes over the gallery.  With the gallery holding all
-        evaluation captions this is a row of ``eval_epoch``'s video->text ranking (D^T)."""
+        evaluation captions of a set with ONE caption per video this is a row of ``eval_epoch``'s video->text ranking (D^T).
+        On the multi-sentence sets (MSVD, ActivityNet, DiDeMo) eval_epoch ranks the maximum over a video's sentences:
+        that is ``search_groups`` of a ``grouped=True`` gallery whose labels are the videos, not ``search``.
 
-    def __init__(self, model, side="video", capacity=0, products=None, dual_softmax=False):
+    ``grouped=True``: every row carries an int64 label (``add(..., group=)``); adjacent rows with equal labels form a group,
+    which may continue across ``add`` calls but not return after another label.  ``search_groups*`` -> (scores, labels,
+    positions) of the k best groups, each by its best row: of ``search``'s row order the first k rows that are the first of
+    their group to appear (equal scores: the smaller position, between groups and inside one); (-inf, -1, -1) beyond the
+    number of groups.  ``search*`` keep ranking rows.  With dual_softmax=True the statistics are what they are without
+    groups - side="text": over all captions held - so the group maximum of D is what eval_epoch ranks video->text on the
+    multi-sentence sets."""
+
+    def __init__(self, model, side="video", capacity=0, products=None, dual_softmax=False, grouped=False):
         if side not in SIDES:
             raise ValueError("FeatureGallery: side is 'video' or 'text', not %r" % (side,))
         core = model.module if hasattr(model, 'module') else model
@@ -71,17 +90,44 @@ class FeatureGallery:
             self._bank = None                                    # side="video": operand rows of the captions, [n_bank, 3E]
             self._m = torch.zeros(self._rows.shape[0], device=self.device)       # per row held (side="video"): max_t S[t, v]
             self._s = torch.zeros(self._rows.shape[0], device=self.device)       # and sum_t exp(S[t, v] - m_v) over the bank
+        self.grouped = bool(grouped)
+        if self.grouped:
+            self._head = torch.zeros(self._rows.shape[0], device=self.device, dtype=torch.int32)     # first row of the row's group
+            # mirror of the labels, one entry longer than the rows: the last one stays -1, which is what position -1 (the
+            # fill) reads - the gather of a result's labels is one indexing launch
+            self._label_dev = torch.full((self._rows.shape[0] + 1,), -1, device=self.device, dtype=torch.int64)
+            self._reset_groups()
 
     def __len__(self):
         return self._n
 
     def clear(self):
-        """Empty the rows (a dual-softmax gallery keeps its bank)."""
+        """Empty the rows and the groups (a dual-softmax gallery keeps its bank)."""
         self._n = 0
+        if self._grouped:
+            self._reset_groups()
 
     @property
     def _dsl(self):
         return getattr(self, "dual_softmax", False)                # (an instance built without the constructor: plain)
+
+    @property
+    def _grouped(self):
+        return getattr(self, "grouped", False)
+
+    @property
+    def num_groups(self):
+        """Groups held (grouped=True)."""
+        self._need_grouped("num_groups")
+        return self._groups
+
+    @property
+    def labels(self):
+        """The label of every row held, a CPU LongTensor [len(self)] (grouped=True)."""
+        self._need_grouped("labels")
+        if len(self._label_chunks) != 1:
+            self._label_chunks = [torch.cat(self._label_chunks) if self._label_chunks else torch.zeros(0, dtype=torch.int64)]
+        return self._label_chunks[0]
 
     @property
     def rows(self):
@@ -118,22 +164,29 @@ class FeatureGallery:
         return self._text_rows(self._encode(input_ids=input_ids)['sequence_output'])
 
     # ------------------------------------------------------------------ filling
-    def _append(self, rows):
+    def _append(self, rows, group=None):
         if rows.dim() != 2 or rows.shape[1] != 3 * self.E:
             raise ValueError("FeatureGallery: operand rows of width %d, the model's embed_dim gives %d"
                              % (rows.shape[-1], 3 * self.E))
         start, n = self._n, self._n + rows.shape[0]
+        plan = self._plan_groups(group, start, rows.shape[0]) if self._grouped else None     # (raises before anything is written)
         if n > self._rows.shape[0]:
             grown = torch.zeros((max(n, 2 * self._rows.shape[0]), 3 * self.E), device=self.device, dtype=torch.float16)
             grown[:start] = self._rows[:start]
             self._rows = grown
-            if self._dsl:
-                for name in ("_m", "_s"):
-                    stat = torch.zeros(grown.shape[0], device=self.device)
-                    stat[:start] = getattr(self, name)[:start]
-                    setattr(self, name, stat)
+            for name in (("_m", "_s") if self._dsl else ()) + (("_head",) if self._grouped else ()):
+                old = getattr(self, name)
+                new = torch.zeros(grown.shape[0], device=self.device, dtype=old.dtype)
+                new[:start] = old[:start]
+                setattr(self, name, new)
+            if self._grouped:
+                labels = torch.full((grown.shape[0] + 1,), -1, device=self.device, dtype=torch.int64)
+                labels[:start] = self._label_dev[:start]
+                self._label_dev = labels
         self._rows[start:n] = rows
         self._n = n
+        if plan is not None:
+            self._take_groups(plan, start, n)
         if self._dsl:
             self._take_stats(start, n)
         return torch.arange(start, n)
@@ -170,15 +223,88 @@ class FeatureGallery:
         if self.side == "video" and self._bank is None:
             raise ValueError("FeatureGallery: dual_softmax=True needs the captions the softmax runs over: set_query_bank first")
 
-    def add(self, *inputs):
-        """``add(video, video_mask)`` (``add(input_ids)`` for side="text"): encode a batch as eval_epoch does and append
-        its rows -> the positions they got (LongTensor)."""
-        return self._append(self._encode_video(*inputs) if self.side == "video" else self._encode_text(*inputs))
+    # ------------------------------------------------------------------ groups (grouped=True): the labels' bookkeeping, on the host
+    def _need_grouped(self, what):
+        if not self._grouped:
+            raise ValueError("FeatureGallery.%s: only a grouped=True gallery has groups" % what)
 
-    def add_features(self, features, mask=None):
+    def _reset_groups(self):
+        self._label_chunks = []                                  # CPU LongTensors: the label of every row held
+        self._closed = set()                                     # labels of the groups that ended: they must not return
+        self._open = None                                        # (label, first row) of the last group: it may continue
+        self._groups = 0
+
+    def _check_group_arg(self, group, what):
+        """the refusals that need nothing encoded: a grouped gallery wants ``group=``, a plain one refuses it"""
+        if self._grouped and group is None:
+            raise ValueError("FeatureGallery.%s: a grouped=True gallery needs group= (one label, or one per row)" % what)
+        if not self._grouped and group is not None:
+            raise ValueError("FeatureGallery.%s: group= needs a grouped=True gallery" % what)
+        if torch.is_tensor(group) and (group.device.type != "cpu" or group.dtype != torch.int64):
+            raise ValueError("FeatureGallery.%s: group labels are an int, a host sequence or a CPU LongTensor, not a %s %s "
+                             "tensor (reading a device tensor would synchronise)" % (what, group.device, group.dtype))
+
+    def _plan_groups(self, group, start, b):
+        """The labels of the b rows about to get positions start.. -> (labels int64 [b], heads int32 [b], runs): checks only,
+        no state is changed.  A label that returns after another one came in between: ValueError."""
+        self._check_group_arg(group, "add")
+        if isinstance(group, (int, np.integer)):
+            lab = np.full(b, int(group), dtype=np.int64)
+        else:
+            lab = np.ascontiguousarray(group.numpy() if torch.is_tensor(group) else np.asarray(list(group)))
+            if lab.shape != (b,) or (b and lab.dtype.kind not in "iu"):
+                raise ValueError("FeatureGallery: group= holds %s labels of kind %r for %d rows (one int, or one int per row)"
+                                 % (lab.shape, lab.dtype.kind, b))
+            lab = lab.astype(np.int64)
+        if b == 0:
+            return lab, np.zeros(0, dtype=np.int32), []
+        first = np.flatnonzero(np.concatenate(([True], lab[1:] != lab[:-1])))         # where a run of equal labels starts
+        runs = [int(v) for v in lab[first]]
+        continues = self._open is not None and runs[0] == self._open[0]
+        new = runs[1:] if continues else runs
+        back = [v for v in new if v in self._closed or (self._open is not None and v == self._open[0])]
+        if back or len(set(new)) != len(new):
+            raise ValueError("FeatureGallery: group label %s returns after another label came in between (the rows of a group "
+                             "are adjacent)" % (back[0] if back else [v for v in new if new.count(v) > 1][0]))
+        head_of_run = start + first
+        if continues:
+            head_of_run[0] = self._open[1]
+        heads = np.repeat(head_of_run, np.diff(np.concatenate((first, [b])))).astype(np.int32)
+        return lab, heads, (new, int(head_of_run[-1]))
+
+    def _host_to_device(self, array):
+        t = torch.from_numpy(array)
+        if self.device.type != "cuda":
+            return t
+        return t.pin_memory().to(self.device, non_blocking=True)                       # (no synchronisation)
+
+    def _take_groups(self, plan, start, n):
+        lab, heads, runs = plan
+        if n == start:
+            return
+        new, last_head = runs
+        if new:
+            if self._open is not None:
+                self._closed.add(self._open[0])
+            self._closed.update(new[:-1])
+            self._open = (new[-1], last_head)
+            self._groups += len(new)
+        self._label_chunks.append(torch.from_numpy(lab.copy()))
+        self._head[start:n] = self._host_to_device(heads)
+        self._label_dev[start:n] = self._host_to_device(lab)
+
+    def add(self, *inputs, group=None):
+        """``add(video, video_mask)`` (``add(input_ids)`` for side="text"): encode a batch as eval_epoch does and append
+        its rows -> the positions they got (LongTensor).  grouped=True: ``group=`` is the rows' label - an int for the whole
+        batch, or a host sequence / CPU LongTensor with one label per row (never a device tensor: no synchronisation)."""
+        self._check_group_arg(group, "add")
+        return self._append(self._encode_video(*inputs) if self.side == "video" else self._encode_text(*inputs), group)
+
+    def add_features(self, features, mask=None, group=None):
         """The same for features cached elsewhere: ``add_features(visual_output, video_mask)`` ([b, T', E] per-segment
         features with the loader's mask, or [b, E] pooled rows) or, side="text", ``add_features(sequence_output)``."""
-        return self._append(self._video_rows(features, mask) if self.side == "video" else self._text_rows(features))
+        self._check_group_arg(group, "add_features")
+        return self._append(self._video_rows(features, mask) if self.side == "video" else self._text_rows(features), group)
 
     # ------------------------------------------------------------------ asking
     def _mult(self):
@@ -187,7 +313,8 @@ class FeatureGallery:
     def _query_rows(self, features, mask):
         return self._text_rows(features) if self.side == "video" else self._video_rows(features, mask)
 
-    def _search_rows(self, q, k):
+    def _search_rows(self, q, k, groups=False):
+        """the k best rows - groups: the best row of each of the k best groups - of every row of q"""
         k = int(k)
         if self._dsl:
             self._need_bank()
@@ -196,12 +323,30 @@ class FeatureGallery:
                 raise ValueError("FeatureGallery: 1 <= k <= 128")
             return (torch.full((q.shape[0], k), float("-inf"), device=self.device),
                     torch.full((q.shape[0], k), -1, device=self.device, dtype=torch.int64))
+        op, tail = torch.ops.centerclip, ((self._head,) if groups else ())
         if self._dsl:
             on_gallery = self.side == "video"
             m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
-            return torch.ops.centerclip.similarity_topk_dsl(q, self._rows, self._n, self._mult(), self.products, k, m, s,
-                                                            int(on_gallery), self._bank.shape[0] if on_gallery else self._n)
-        return torch.ops.centerclip.similarity_topk(q, self._rows, self._n, self._mult(), self.products, k)
+            return (op.similarity_topk_grouped_dsl if groups else op.similarity_topk_dsl)(
+                q, self._rows, self._n, self._mult(), self.products, k, m, s, int(on_gallery),
+                self._bank.shape[0] if on_gallery else self._n, *tail)
+        return (op.similarity_topk_grouped if groups else op.similarity_topk)(q, self._rows, self._n, self._mult(), self.products,
+                                                                               k, *tail)
+
+    def _search_group_rows(self, q, k):
+        scores, pos = self._search_rows(q, k, groups=True)
+        return scores, self._label_dev[pos], pos                 # (position -1, the fill: the last entry, -1)
+
+    def search_groups(self, *inputs, k=10):
+        """grouped=True: the queries of ``search`` -> (scores [Nq, k] fp32, labels [Nq, k] int64, positions [Nq, k] int64) of
+        the k best groups, best first, each by its best row (``positions``); (-inf, -1, -1) beyond the number of groups."""
+        self._need_grouped("search_groups")
+        return self._search_group_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), k)
+
+    def search_groups_features(self, features, k=10, mask=None):
+        """``search_groups`` for query features computed elsewhere (as ``search_features``)."""
+        self._need_grouped("search_groups_features")
+        return self._search_group_rows(self._query_rows(features, mask), k)
 
     def search(self, *inputs, k=10):
         """``search(input_ids, k=10)`` (``search(video, video_mask, k=10)`` for side="text") -> (scores [Nq, k] fp32, positions
@@ -244,14 +389,20 @@ class FeatureGallery:
         if self._dsl:                                            # (a plain gallery's keys are what they were)
             state.update(dual_softmax=True, bank=None if self._bank is None else self._bank.clone(),
                          m=self._m[:self._n].clone(), s=self._s[:self._n].clone())
+        if self._grouped:                                        # (the same: three keys more, only here)
+            state.update(grouped=True, group_head=self._head[:self._n].clone(), labels=self.labels.clone())
         return state
 
     def load_state_dict(self, state):
         """Replace the contents with a saved gallery's.  E or side that differ from this gallery's: ValueError, nothing
         written; the same for a plain gallery's state into a dual_softmax=True gallery, or the reverse.  The saved ``products``
         are taken over - with dual_softmax=True the bank and the statistics too - so the loaded gallery answers with the saved
-        one's bits."""
+        one's bits.  A grouped=True gallery's state into a plain one, or the reverse: ValueError, nothing written; the groups
+        are rebuilt from the saved labels."""
         rows, count = state["rows"], int(state["count"])
+        if bool(state.get("grouped", False)) != self._grouped:
+            raise ValueError("FeatureGallery.load_state_dict: saved grouped=%s, this gallery grouped=%s"
+                             % (bool(state.get("grouped", False)), self._grouped))
         if bool(state.get("dual_softmax", False)) != self._dsl:
             raise ValueError("FeatureGallery.load_state_dict: saved dual_softmax=%s, this gallery dual_softmax=%s"
                              % (bool(state.get("dual_softmax", False)), self._dsl))
@@ -269,13 +420,30 @@ class FeatureGallery:
             if tuple(m.shape) != (count,) or tuple(s.shape) != (count,) or m.dtype != torch.float32 or s.dtype != torch.float32:
                 raise ValueError("FeatureGallery.load_state_dict: statistics %s, %s do not match count %d"
                                  % (tuple(m.shape), tuple(s.shape), count))
+        labels = None
+        if self._grouped:
+            labels, head = state["labels"], state["group_head"]
+            if (not torch.is_tensor(labels) or tuple(labels.shape) != (count,) or labels.dtype != torch.int64
+                    or tuple(head.shape) != (count,) or head.dtype != torch.int32):
+                raise ValueError("FeatureGallery.load_state_dict: labels / group_head do not match count %d" % count)
+            labels = labels.cpu()
+            kept = (self._label_chunks, self._closed, self._open, self._groups)
+            self._reset_groups()
+            try:
+                self._plan_groups(labels, 0, count)              # (a label that returns: refused before anything is written)
+            except ValueError:
+                self._label_chunks, self._closed, self._open, self._groups = kept
+                raise
+        if self._dsl:
             self._bank = None                                    # (the saved statistics are taken over, not recomputed)
         self._n = 0
-        self._append(rows.to(self.device))
+        self._append(rows.to(self.device), labels)
         self.products, self.backend = int(state["products"]), backend
         if self._dsl:
             self._bank = None if bank is None else bank.to(self.device).clone()
             self._m[:count], self._s[:count] = m.to(self.device), s.to(self.device)
+        if self._grouped:
+            self._head[:count] = head.to(self.device)            # (what the labels give; the saved array is taken over)
 
 
 __all__ = ["FeatureGallery"]

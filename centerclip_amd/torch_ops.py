@@ -1265,6 +1265,82 @@ def _(query_planes, gallery_planes, n_gallery, mult, products, k, m, s, stats_on
             query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
 
 
+def _check_group_head(name, query_planes, gallery_planes, n_gallery, group_head):
+    """the planes and the heads of a grouped search (the fake kernels run it too: every refusal is an op-level ValueError)"""
+    E3 = _check_plane_pair(name, query_planes, gallery_planes, n_gallery)
+    if (group_head.dtype != torch.int32 or group_head.dim() != 1 or not group_head.is_contiguous()
+            or group_head.shape[0] < int(n_gallery)):
+        raise ValueError("%s: group_head %s %s is not a contiguous int32 vector of at least %d entries"
+                         % (name, tuple(group_head.shape), group_head.dtype, int(n_gallery)))
+    if group_head.device != gallery_planes.device or query_planes.device != gallery_planes.device:
+        raise ValueError("%s: group_head on %s, the planes on %s and %s" % (name, group_head.device, query_planes.device,
+                                                                        gallery_planes.device))
+    return E3
+
+
+def _check_dsl_stats(name, m, s, need):
+    if m.dim() != 1 or s.dim() != 1 or m.shape[0] < need or s.shape[0] < need or m.dtype != torch.float32 or s.dtype != torch.float32:
+        raise ValueError("%s: m %s, s %s are not fp32 vectors of at least %d entries" % (name, tuple(m.shape), tuple(s.shape), need))
+
+
+@custom_op(NS + "::similarity_topk_grouped", mutates_args=(), device_types="cuda")
+def similarity_topk_grouped(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                            k: int, group_head: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """similarity_topk over GROUPS of adjacent gallery rows, each by its best row: group_head [>= n_gallery] int32 holds the
+    first row of every row's group.  -> (scores [Bq, k] fp32, ids [Bq, k] int64): of similarity_topk's row order the first k
+    rows that are the first of their group to appear - entry i is the best row of the i-th best group; (-inf, -1) beyond the
+    number of groups.  group_head = arange gives similarity_topk bit for bit.  cc_similarity_topk_grouped_planes_f32."""
+    Bq = query_planes.shape[0]
+    E3 = _check_group_head("similarity_topk_grouped", query_planes, gallery_planes, n_gallery, group_head)
+    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
+    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
+    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
+    lib = L.lib()
+    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
+    L.check(lib.cc_similarity_topk_grouped_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
+                                                      float(mult), int(products), int(k), L.ptr(group_head), L.ptr(scores),
+                                                      L.ptr(ids), L.ptr(ws), ws.numel(), _st(query_planes)),
+            "cc_similarity_topk_grouped_planes_f32")
+    return scores, ids.to(torch.int64)
+
+
+@similarity_topk_grouped.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, k, group_head):
+    _check_group_head("similarity_topk_grouped", query_planes, gallery_planes, n_gallery, group_head)
+    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
+            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+
+
+@custom_op(NS + "::similarity_topk_grouped_dsl", mutates_args=(), device_types="cuda")
+def similarity_topk_grouped_dsl(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float,
+                                products: int, k: int, m: torch.Tensor, s: torch.Tensor, stats_on_gallery: int, n_total: int,
+                                group_head: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """similarity_topk_grouped ranking the dual softmax D of similarity_topk_dsl (same m, s, stats_on_gallery, n_total): a
+    group's score is the largest D of its rows.  cc_similarity_topk_grouped_dsl_planes_f32."""
+    Bq = query_planes.shape[0]
+    E3 = _check_group_head("similarity_topk_grouped_dsl", query_planes, gallery_planes, n_gallery, group_head)
+    _check_dsl_stats("similarity_topk_grouped_dsl", m, s, int(n_gallery) if stats_on_gallery else Bq)
+    query_planes, gallery_planes, m, s = query_planes.contiguous(), gallery_planes.contiguous(), m.contiguous(), s.contiguous()
+    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
+    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
+    lib = L.lib()
+    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
+    L.check(lib.cc_similarity_topk_grouped_dsl_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
+                                                          float(mult), int(products), int(k), L.ptr(m), L.ptr(s),
+                                                          int(stats_on_gallery), int(n_total), L.ptr(group_head), L.ptr(scores),
+                                                          L.ptr(ids), L.ptr(ws), ws.numel(), _st(query_planes)),
+            "cc_similarity_topk_grouped_dsl_planes_f32")
+    return scores, ids.to(torch.int64)
+
+
+@similarity_topk_grouped_dsl.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, k, m, s, stats_on_gallery, n_total, group_head):
+    _check_group_head("similarity_topk_grouped_dsl", query_planes, gallery_planes, n_gallery, group_head)
+    _check_dsl_stats("similarity_topk_grouped_dsl", m, s, int(n_gallery) if stats_on_gallery else query_planes.shape[0])
+    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
+            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+
+
 def padded_video_rows(n_video):
     """Rows a video-side plane buffer needs for n_video videos (whole GEMM tiles; the rows behind n_video must be zero)."""
     return int(L.lib().cc_similarity_padded_rows(int(n_video)))
@@ -1519,7 +1595,8 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "loose_similarity", "video_pool_normalize", "normalize_rows", "scaled_dot_nt", "scaled_dot_nt_out", "rank_counts",
        "rank_counts_cols", "rank_counts_ref", "group_max_rows", "normalize_rows_planes", "video_pool_normalize_planes",
        "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
-       "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl")
+       "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
+       "similarity_topk_grouped", "similarity_topk_grouped_dsl")
 
 
 def logit_multiplier(logit_scale):

@@ -15,6 +15,13 @@ as its bank, a caption gallery asked with clips, and the timing of similarity_to
 statistics pass (dsl_col_stats_planes) against the matrix op in blocks + dsl_col_stats.
 
     python examples/search_synthetic.py --camoe_dsl 1 [--time-bank 1000]
+
+--groups G ranks groups of rows, each by its best row (FeatureGallery(grouped=True): the sentences of a video, the windows of a
+long video): clips added in groups of 1..G rows and asked with search_groups, then the timing of search_groups_features
+against plain search_features on the same gallery and against what there was before - similarity_features, a per-group
+maximum, torch.topk - with groups of 1 row and of 1..G rows.
+
+    python examples/search_synthetic.py --groups 40
 """
 import argparse
 import os
@@ -168,6 +175,69 @@ def dsl_part(model, device, a):
     print("same scores as dsl_apply_ on the matrix: %s" % bool(torch.equal(full.values, scores[:, :full.values.shape[1]])))
 
 
+def group_labels(rows, largest, seed=2):
+    """one label per row: groups of 1..largest adjacent rows (seeded), labelled 0, 1, ... in row order -> CPU LongTensor"""
+    g = torch.Generator().manual_seed(seed)
+    sizes = torch.randint(1, largest + 1, (rows,), generator=g)            # (more than enough groups)
+    return torch.repeat_interleave(torch.arange(rows), sizes)[:rows].contiguous()
+
+
+def time_groups(model, device, rows, queries, k, largest, reps, warmup):
+    """search_groups_features against search_features on the same gallery and against the matrix path a user had before"""
+    E = int(model.clip_config['embed_dim'])
+    g = torch.Generator(device=device).manual_seed(1)
+    feats = torch.randn(rows, E, device=device, generator=g)
+    seq = torch.randn(queries, 1, E, device=device, generator=g)
+    for largest_here in sorted({1, largest}):
+        labels = group_labels(rows, largest_here)
+        gallery = FeatureGallery(model, capacity=rows, grouped=True)
+        start = 0
+        for b in uneven(rows, (rows // 2, rows // 3, rows)):                 # (batches that split groups)
+            gallery.add_features(feats[start:start + b], group=labels[start:start + b])
+            start += b
+        n_groups = gallery.num_groups
+        index = labels.to(device).expand(queries, rows)                      # (labels 0, 1, ...: the column of a group's maximum)
+
+        def matrix_path():
+            sim = gallery.similarity_features(seq)
+            best = torch.full((queries, n_groups), float("-inf"), device=device).scatter_reduce_(1, index, sim, "amax")
+            return torch.topk(best, min(k, n_groups), dim=1)
+
+        fns = [("search_groups_features", lambda: gallery.search_groups_features(seq, k=k)),
+               ("search_features (rows, not groups)", lambda: gallery.search_features(seq, k=k)),
+               ("similarity_features + per-group max (scatter_reduce amax) + topk", matrix_path)]
+        a, b = fns[0][1](), matrix_path()
+        kk = b.values.shape[1]
+        assert torch.equal(a[0][:, :kk], b.values), "the two paths disagree on the scores"
+        report("%d queries x %d gallery rows in %d groups of 1..%d rows, E = %d, products = %d, k = %d: %d repetitions after %d "
+               "warm-up rounds, device events" % (queries, rows, n_groups, largest_here, E, gallery.products, k, reps, warmup),
+               timed(fns, warmup, reps))
+        print("  search workspace %d bytes; the matrix has %d bytes, the per-group maxima %d more"
+              % (L.lib().cc_similarity_topk_workspace_bytes(queries, rows, k), queries * rows * 4, queries * n_groups * 4))
+
+
+def groups_part(model, device, a):
+    """clips in groups of 1..G windows: the k best groups of every caption, each by its best window"""
+    data = SyntheticRetrieval(a.clips)
+    labels = 100 + group_labels(a.clips, a.groups)                           # (labels are any int64, not positions)
+    gallery = FeatureGallery(model, grouped=True)
+    start = 0
+    for b in uneven(a.clips):
+        gallery.add(data.video[start:start + b].to(device), data.vmask[start:start + b].to(device), group=labels[start:start + b])
+        start += b
+    print("%d clips in %d groups" % (len(gallery), gallery.num_groups))
+    ids = data.ids[:a.captions].to(device)
+    scores, groups, pos = gallery.search_groups(ids, k=a.k)
+    for i in range(ids.shape[0]):
+        print("caption %d: groups %s  by their clips %s  scores %s"
+              % (i, groups[i].tolist(), pos[i].tolist(), ["%.4f" % s for s in scores[i].tolist()]))
+    sim = gallery.similarity(ids)
+    on_device = labels.to(device)
+    want = torch.stack([sim[:, on_device == lab].max(dim=1).values for lab in labels.unique().tolist()], 1)
+    full = torch.topk(want, min(a.k, gallery.num_groups), dim=1)
+    print("same scores as the per-group maximum of the matrix: %s" % bool(torch.equal(full.values, scores[:, :full.values.shape[1]])))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=40, help="clips encoded into the gallery (0: skip the model part)")
@@ -180,6 +250,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--camoe_dsl", type=int, default=0, help="1: the dual softmax (FeatureGallery(dual_softmax=True))")
     ap.add_argument("--time-bank", type=int, default=1000, help="--camoe_dsl 1: captions in the bank of the timed clip gallery")
+    ap.add_argument("--groups", type=int, default=0, help="G > 0: grouped search (FeatureGallery(grouped=True)), groups of 1..G rows")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
@@ -189,6 +260,12 @@ def main():
             dsl_part(model, device, a)
         if a.time_rows:
             time_dsl(model, device, a.time_rows, a.time_queries, a.time_k, a.time_bank, a.reps, a.warmup)
+        return
+    if a.groups:
+        if a.clips:
+            groups_part(model, device, a)
+        if a.time_rows:
+            time_groups(model, device, a.time_rows, a.time_queries, a.time_k, a.groups, a.reps, a.warmup)
         return
     if a.clips:
         data = SyntheticRetrieval(a.clips)

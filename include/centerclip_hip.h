@@ -820,6 +820,26 @@ int cc_similarity_topk_dsl_planes_f32(const void* query_planes, const void* gall
                                       float mult, int32_t products, int32_t k, const float* m, const float* s,
                                       int32_t stats_on_gallery, int32_t n_total, float* scores, int32_t* ids, void* ws,
                                       size_t ws_bytes, void* stream);
+/* Grouped top-k search: the k best GROUPS of gallery rows, each by its best row (the sentences of a video, the windows of
+ * a long video), still in one pass without the matrix.  The rows of a group are adjacent; group_head [Bg] int32 names the
+ * first row of every row's group: group_head[r] <= r, group_head[group_head[r]] == group_head[r], non-decreasing.
+ *   Result: of the plain entry's stable descending row order (larger score first, equal scores by smaller id, -0 == +0) the
+ *   first k rows that are the first of their group to appear.  Entry i is the best row of the i-th best group and its
+ *   score; ties between groups go to the group whose best row has the smaller id, ties inside a group to the smallest id;
+ *   fewer than k groups: (-inf, -1).  Scores are the bits of cc_scaled_dot_planes_products_f32 (the _dsl entry: the bits
+ *   cc_dsl_apply_f32 writes over them, as cc_similarity_topk_dsl_planes_f32).  group_head[r] == r for every r gives the plain
+ *   entry's result bit for bit.  Rows and heads at or above Bg are never read.  A malformed group_head gives an unspecified
+ *   ranking and no access outside the Bg rows, the lists or the workspace (every index taken from it is clamped).
+ * Limits, workspace (cc_similarity_topk_workspace_bytes), launches and the order of the early returns are the plain
+ * entries'; a NULL group_head: CC_ERR_INVALID.  A group longer than a wave's share of the rows is streamed by one wave:
+ * exact, unbalanced. */
+int cc_similarity_topk_grouped_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                          float mult, int32_t products, int32_t k, const int32_t* group_head, float* scores,
+                                          int32_t* ids, void* ws, size_t ws_bytes, void* stream);
+int cc_similarity_topk_grouped_dsl_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg,
+                                              int32_t E, float mult, int32_t products, int32_t k, const float* m, const float* s,
+                                              int32_t stats_on_gallery, int32_t n_total, const int32_t* group_head, float* scores,
+                                              int32_t* ids, void* ws, size_t ws_bytes, void* stream);
 int cc_video_pool_normalize_f32(const float* visual, const int64_t* video_mask, int32_t Bv, int32_t Tn,
                                 int32_t E, float* pooled, void* stream);
 int cc_loose_similarity_f32(const float* text, const float* visual, const int64_t* video_mask,
