@@ -39,6 +39,14 @@
 // a second compile-time mode.  A row's score is computed as before; a wave then takes one contiguous row range between group
 // starts instead of interleaved tiles and hands tk_insert_tile one candidate per finished group (tk_group_tile), so every
 // group lives in one list of one wave and the fold, the workspace and the merge launch are unchanged.
+//
+// Masked search (rows taken out of a gallery, a subset of it): topk_stream_kernel<DSL, GROUPED, MASK>, a third compile-time
+// mode.  A bit per gallery row - one mask for all queries, or one per query row - says whether the row may be ranked; a row
+// that may not gets key 0, the empty entry.  With ONE mask a 16-row tile without a selectable row is neither requested nor
+// multiplied: tk_stream_tiles takes its tiles from a rule (TkEvery / TkLive), and dsl_stats_stream_kernel<true> leaves masked
+// text rows out of the statistics the same way.  pack_row_mask_kernel turns byte flags into mask words.
+#include <type_traits>
+
 #include "cc_kernels.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -170,8 +178,54 @@ __device__ __forceinline__ void tk_stage_rows(_Float16* qs, const _Float16* __re
     }
 }
 
-// The stream of one wave: the 16-row tiles first, first + stride, ... < t1 of `gallery` (Bg rows, `ld` halfs apart, the first
-// K multiplied) against the 16 staged rows (`qrow`: the lane's fragments of staged row l15).  Behind a tile's last k-slice
+// Which tiles a wave streams, in which order: the "next tile" rule of tk_stream_tiles.
+// TkEvery: the tiles first, first + stride, ... < t1.  It only names them: tk_stream_tiles keeps the arithmetic it always had
+// for them (count, last tile, t + stride), spelled where it was, so the unmasked kernels compile to the code they were.
+struct TkEvery {
+    int first, stride, t1;
+};
+
+// TkLive: of TkEvery's tiles the LIVE ones under one row mask shared by all staged rows (bit b of word w = row 32 w + b): the
+// 16 bits of tile t are halfword t of the mask, and a tile whose halfword is 0 is neither requested nor multiplied.  The flags
+// of 64 candidate tiles are one load and one ballot (`bits`, wave-uniform; refilled every 64 candidates), so finding the next
+// live tile puts no memory round trip in front of a tile's request.  All lanes of the wave call every member together.
+// count(): how many tiles; start(): the first; request(t), asked once per tile in front of the request that overlaps tile t's
+// last batch: the tile whose first batch that request fetches - behind the wave's last tile a tile already read (a cache hit
+// that nobody multiplies: the request stays unconditional); advance(t), asked once behind request(t): the tile after t.
+struct TkLive {
+    const int* __restrict__ mask;
+    int first, stride, t1, lane, tiles, base, next;
+    u64 bits;                                                                          // bit i: tile base + i * stride is live and not yet taken
+    __device__ __forceinline__ u64 flags(int b) const {
+        const int t = b + lane * stride, tc = max(min(t, t1 - 1), 0);                 // (words behind the last tile are never read)
+        const int w = mask[tc >> 1];
+        return __ballot(t < t1 && ((w >> (16 * (tc & 1))) & 0xFFFF) != 0);
+    }
+    __device__ __forceinline__ TkLive(const int* __restrict__ mask_, int first_, int stride_, int t1_, int lane_)
+        : mask(mask_), first(__builtin_amdgcn_readfirstlane(first_)), stride(stride_), t1(__builtin_amdgcn_readfirstlane(t1_)),
+          lane(lane_), tiles(0), base(first), next(t1), bits(0) {                      // (the ends are the same in all lanes: scalars)
+        for (int b = first; b < t1; b += 64 * stride) tiles += __builtin_popcountll(flags(b));
+        if (first < t1) bits = flags(first);
+    }
+    __device__ __forceinline__ int take() {                                            // the next live tile; t1: none left
+        while (!bits) {
+            base += 64 * stride;
+            if (base >= t1) return t1;
+            bits = flags(base);
+        }
+        const int i = __builtin_ctzll(bits);
+        bits &= bits - 1;
+        return base + i * stride;
+    }
+    __device__ __forceinline__ int count() const { return tiles; }
+    __device__ __forceinline__ int start() { return take(); }
+    __device__ __forceinline__ int request(int t) { return (next = take()) < t1 ? next : t; }
+    __device__ __forceinline__ int advance(int) const { return next; }
+};
+
+// The stream of one wave: the 16-row tiles `rule` names (TkEvery: first, first + stride, ... < t1; TkLive: of those the ones
+// with a selectable row) of `gallery` (Bg rows, `ld` halfs apart, the first K multiplied) against the 16 staged rows
+// (`qrow`: the lane's fragments of staged row l15).  Behind a tile's last k-slice
 // on_tile(t, acc) gets the 16 x 16 products: the lane holds streamed rows t * 16 + 4 lg + r (r = 0..3) of staged row l15, each
 // ONE fp32 accumulator over the k-slices in ascending order, the streamed fragment as the first operand.  before_last(t) runs
 // in front of the request that overlaps tile t's last batch: what it requests arrives before that batch (loads return in
@@ -180,10 +234,9 @@ __device__ __forceinline__ void tk_stage_rows(_Float16* qs, const _Float16* __re
 // while one batch is multiplied - and, behind a tile's last batch, consumed by on_tile - the next one (the tile's next, or the
 // first of the wave's next tile) is in flight.  Pairs beyond the row's end are clamped to its last pair (read again, not
 // multiplied).
-template <class Before, class Tile>
+template <class Rule, class Before, class Tile>
 __device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gallery, int Bg, int ld, int K, const _Float16* qrow,
-                                                int first, int stride, int t1, int l15, int lg, Before&& before_last,
-                                                Tile&& on_tile) {
+                                                Rule&& rule, int l15, int lg, Before&& before_last, Tile&& on_tile) {
     const int nk2 = K >> 6;                                                            // pairs of k-slices: one 128-byte line per row
     auto load_batch = [&](h8 (&b)[2 * TK_BATCH], int t, int s0) {
         const int grow = min(t * 16 + l15, Bg - 1);                                    // rows at Bg or above are never read
@@ -196,17 +249,27 @@ __device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gal
         }
     };
     const int nb = (nk2 + TK_BATCH - 1) / TK_BATCH;                                    // batches of a tile
-    const int my_tiles = first < t1 ? (t1 - first + stride - 1) / stride : 0;
-    const int total = my_tiles * nb, t_last = first + (my_tiles - 1) * stride;
+    constexpr bool every = std::is_same<std::decay_t<Rule>, TkEvery>::value;
+    const int first = rule.first, stride = rule.stride, t1 = rule.t1;
+    const int my_tiles = [&] {
+        if constexpr (every) return first < t1 ? (t1 - first + stride - 1) / stride : 0;
+        else return rule.count();
+    }();
+    const int total = my_tiles * nb, t_last = first + (my_tiles - 1) * stride;         // (t_last: TkEvery's last tile)
     int t = first, b = 0;                                                              // the batch about to be multiplied
+    if constexpr (!every) t = rule.start();
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
     auto step = [&](const h8 (&cur)[2 * TK_BATCH], h8 (&nxt)[2 * TK_BATCH]) {
         // (the request is unconditional - behind the wave's last batch it repeats the last tile's first, a cache hit that
         // nobody multiplies: under a condition the compiler's wait for `cur` has to cover the path without the request,
-        // and on the other path it then waits for the batch just requested)
+        // and on the other path it then waits for the batch just requested.  The rule only says WHICH tile.)
         const bool last = b + 1 == nb;
         if (last) before_last(t);
-        load_batch(nxt, last ? min(t + stride, t_last) : t, last ? 0 : (b + 1) * TK_BATCH);
+        if constexpr (every) {
+            load_batch(nxt, last ? min(t + stride, t_last) : t, last ? 0 : (b + 1) * TK_BATCH);
+        } else {
+            load_batch(nxt, last ? rule.request(t) : t, last ? 0 : (b + 1) * TK_BATCH);
+        }
 #pragma unroll
         for (int u = 0; u < TK_BATCH; ++u) {
             const int s = b * TK_BATCH + u;
@@ -220,7 +283,8 @@ __device__ __forceinline__ void tk_stream_tiles(const _Float16* __restrict__ gal
         if (!last) { ++b; return; }
         on_tile(t, acc);
         acc = f32x4{0.f, 0.f, 0.f, 0.f};
-        t += stride;
+        if constexpr (every) t += stride;
+        else t = rule.advance(t);
         b = 0;
     };
     h8 buf0[2 * TK_BATCH], buf1[2 * TK_BATCH];
@@ -274,6 +338,16 @@ __device__ __forceinline__ void tk_group_tile(u64 (&key)[4], const bool (&head)[
     }
 }
 
+// What a masked stream carries from tile to tile (nothing without a mask): the lane's mask row, the word of it that holds the
+// tile's 16 bits, and - grouped search under one mask - the tile streamed before and the head of the row in front of this one
+template <int MASK>
+struct TkMaskState {
+    const int* row;
+    int word = 0, prev = 0, gap_head = 0;
+};
+template <>
+struct TkMaskState<0> {};
+
 // query / gallery: plane rows `ld` halfs apart, the first K of them multiplied.  ws [Bq][k][slices] keys.  DSL: the score is
 // cc_dsl_value(nt, S, m, s) with the pair of the gallery row (on_gallery) or of the query row; without DSL those four
 // arguments are not read.  GROUPED: group_head[r] = the first row of r's group (the rows of a group are adjacent); a list
@@ -282,12 +356,18 @@ __device__ __forceinline__ void tk_group_tile(u64 (&key)[4], const bool (&head)[
 // down to group_head[b] (monotone; a range may be empty; a group longer than a share belongs wholly to the range that
 // starts at its head).  Every group lives in one wave, so the fold, the workspace and the merge launch see lists whose
 // groups are disjoint and work unchanged.  Only the snapping indexes with a value of group_head, and clamps it to [0, b].
-template <bool DSL, bool GROUPED>
+// MASK: a third compile-time mode - 0 every row may be ranked (row_mask, mask_words are not read), 1 row_mask is ONE mask row
+// for all queries, 2 one per query row, mask_words apart (bit b of word w = row 32 w + b; bits at Bg or above are ignored).
+// A row whose bit is 0 gets key 0, the empty entry: that is the whole ranking rule in every DSL x GROUPED combination, and the
+// fold, the workspace and the merge never know.  Statistics and heads are indexed as without a mask.  MASK == 1 streams the
+// live tiles only (TkLive); MASK == 2 skips nothing.  GROUPED with dead tiles: see on_tile.
+template <bool DSL, bool GROUPED, int MASK>
 __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
                                                           int Bq, int Bg, int ld, int K, float sc, int k, int slices,
                                                           u64* __restrict__ ws, const float* __restrict__ stat_m,
                                                           const float* __restrict__ stat_s, int on_gallery, float nt,
-                                                          const int* __restrict__ group_head) {
+                                                          const int* __restrict__ group_head, const int* __restrict__ row_mask,
+                                                          int mask_words) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
     const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
@@ -329,7 +409,18 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
         first = r0 >> 4;
         last = r1 > r0 ? (r1 + 15) >> 4 : first;                                       // the tile at a boundary: both neighbours' work
     }
+    // MASK: the mask word that holds the tile's 16 bits comes per tile, from the one mask row or from query row l15's (a
+    // query row at Bq or above: clamped, as its statistics).  GROUPED, MASK == 1: the tile streamed before this one, and the
+    // head of the row in front of this one (per tile)
+    TkMaskState<MASK> ms;
+    if constexpr (MASK != 0) {
+        ms.row = row_mask;
+        if constexpr (MASK == 2) ms.row += (int64_t)min(q0 + l15, Bq - 1) * mask_words;
+        ms.prev = first - 1;
+    }
     auto before_last = [&](int t) {
+        if constexpr (MASK != 0) ms.word = ms.row[t >> 1];                             // (t < tiles: inside ceil(Bg / 32) words)
+        if constexpr (GROUPED && MASK == 1) ms.gap_head = group_head[min(max(t * 16 - 1, 0), Bg - 1)];
         if constexpr (DSL) {
             if (on_gallery) {
 #pragma unroll
@@ -360,16 +451,30 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
             } else {
                 key[r] = (qvalid && id < Bg) ? tk_key(x, id) : 0;
             }
+            if constexpr (MASK != 0) key[r] = ((ms.word >> ((t & 1) * 16 + lg * 4 + r)) & 1) ? key[r] : 0;
+        }
+        if constexpr (GROUPED && MASK == 1) {
+            // Dead tiles between the tile streamed before and this one were skipped, heads included.  If a group starts in
+            // them (the head of the row in front of this tile lies behind the tile streamed before), the group open in front
+            // of them ends there, and this tile's rows up to its first head belong to a group whose earlier rows are all
+            // unselectable: both are what a head at the tile's first row says.  (A gap lies inside the wave's range; a group
+            // none of whose rows is selectable only ever holds key 0 and never becomes a candidate.)
+            if (lg == 0 && t > ms.prev + 1 && ms.gap_head >= (ms.prev + 1) * 16) head[0] = true;
+            ms.prev = t;
         }
         if constexpr (GROUPED) tk_group_tile(key, head, lg, carry);
         tk_insert_tile(key, mine, k, lg, thr, filled);
     };
+    constexpr int stride = GROUPED ? 1 : TK_WAVES;
+    if constexpr (MASK == 1) {
+        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, TkLive(row_mask, first, stride, last, lane), l15, lg, before_last,
+                        on_tile);
+    } else {
+        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, TkEvery{first, stride, last}, l15, lg, before_last, on_tile);
+    }
     if constexpr (GROUPED) {
-        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, first, 1, last, l15, lg, before_last, on_tile);
         u64 key[4] = {lg == 0 ? carry : 0, 0, 0, 0};                                   // the group open at the range's end
         tk_insert_tile(key, mine, k, lg, thr, filled);
-    } else {
-        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, first, TK_WAVES, last, l15, lg, before_last, on_tile);
     }
     // the four waves' lists -> wave 0's, as a tree: the other wave's entries are the candidates, 16 a list at a time
     auto fold = [&](int from) {
@@ -442,10 +547,14 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const u64* __restrict__ 
 }
 
 // The (m, s) pairs of the 16 video rows from blockIdx.y * 16 on over the text tiles of slice blockIdx.x (the tree: the file's
-// head).  part [slices][Bv] pairs.  The split of the text rows uses Bt alone.
+// head).  part [slices][Bv] pairs.  The split of the text rows uses Bt alone.  MASKED: text_mask is one mask row over the text
+// rows (topk_stream_kernel's format); a row whose bit is 0 is treated as a row at Bt or above - neither its maximum nor its
+// expf term enters - and a tile without a selectable row is skipped (TkLive), which leaves the lane's pair as it is: the pair
+// of a video row is the unmasked tree with those terms left out, (-inf, 0) without any.
+template <bool MASKED>
 __global__ __launch_bounds__(256) void dsl_stats_stream_kernel(const _Float16* __restrict__ video, const _Float16* __restrict__ text,
                                                                int Bv, int Bt, int ld, int K, float sc, int slices,
-                                                               float* __restrict__ part) {
+                                                               float* __restrict__ part, const int* __restrict__ text_mask) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
     __shared__ float pm[TK_WAVES][4][TK_QROWS], ps[TK_WAVES][4][TK_QROWS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
@@ -456,23 +565,32 @@ __global__ __launch_bounds__(256) void dsl_stats_stream_kernel(const _Float16* _
     const int tiles = (Bt + 15) >> 4;
     const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
     float m = -INFINITY, s = 0.f;                                                      // of video row l15 over the lane's text rows
-    tk_stream_tiles(
-        text, Bt, ld, K, vs + l15 * (K + TK_QPAD) + lg * 8, t0 + wave, TK_WAVES, t1, l15, lg, [](int) {},
-        [&](int t, const f32x4& acc) {
-            float x[4], mt = m;
-            bool in[4];
+    int mw = 0;                                                                        // MASKED: the mask word of the tile's 16 bits
+    auto before_last = [&](int t) {
+        if constexpr (MASKED) mw = text_mask[t >> 1];
+    };
+    auto on_tile = [&](int t, const f32x4& acc) {
+        float x[4], mt = m;
+        bool in[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                in[r] = t * 16 + lg * 4 + r < Bt;
-                x[r] = sc * acc[r];
-                mt = in[r] ? fmaxf(mt, x[r]) : mt;
-            }
-            float a = cc_dsl_share(s, m, mt);
+        for (int r = 0; r < 4; ++r) {
+            const bool sel = MASKED ? ((mw >> ((t & 1) * 16 + lg * 4 + r)) & 1) != 0 : true;
+            in[r] = sel && t * 16 + lg * 4 + r < Bt;
+            x[r] = sc * acc[r];
+            mt = in[r] ? fmaxf(mt, x[r]) : mt;
+        }
+        float a = cc_dsl_share(s, m, mt);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) a += in[r] ? expf(x[r] - mt) : 0.f;
-            s = a;
-            m = mt;
-        });
+        for (int r = 0; r < 4; ++r) a += in[r] ? expf(x[r] - mt) : 0.f;
+        s = a;
+        m = mt;
+    };
+    const _Float16* vrow = vs + l15 * (K + TK_QPAD) + lg * 8;
+    if constexpr (MASKED) {
+        tk_stream_tiles(text, Bt, ld, K, vrow, TkLive(text_mask, t0 + wave, TK_WAVES, t1, lane), l15, lg, before_last, on_tile);
+    } else {
+        tk_stream_tiles(text, Bt, ld, K, vrow, TkEvery{t0 + wave, TK_WAVES, t1}, l15, lg, before_last, on_tile);
+    }
     pm[wave][lg][l15] = m;
     ps[wave][lg][l15] = s;
     __syncthreads();
@@ -490,6 +608,19 @@ __global__ __launch_bounds__(256) void dsl_stats_stream_kernel(const _Float16* _
     }
 }
 
+// flags [R][n] bytes (non-zero = 1) -> out [R][W] mask words: a wave packs 64 flags with one ballot and two of its lanes store
+// the two words (W >= ceil(n / 32); flags at n or above count as 0).  grid: (ceil(32 W / 256), rows, strided over R).
+__global__ __launch_bounds__(256) void pack_row_mask_kernel(const uint8_t* __restrict__ flags, int R, int n, int* __restrict__ out,
+                                                            int W) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;                         // the flag of this lane
+    const int lane = threadIdx.x & 63;
+    for (int r = blockIdx.y; r < R; r += gridDim.y) {
+        const u64 b = __ballot(i < n && flags[(int64_t)r * n + min(i, (int64_t)n - 1)] != 0);
+        const int64_t w = i >> 5;
+        if ((lane & 31) == 0 && w < W) out[(int64_t)r * W + w] = (int)(unsigned)(lane ? b >> 32 : b);
+    }
+}
+
 int tk_slices(int Bq, int Bg) {
     const int groups = (max(Bq, 1) + TK_QROWS - 1) / TK_QROWS, tiles = (max(Bg, 1) + 15) / 16;
     const int want = (TK_TARGET_WGS + groups - 1) / groups, cap = tiles / TK_MIN_TILES;
@@ -499,6 +630,11 @@ int tk_slices(int Bq, int Bg) {
 // with), at least TK_MIN_TILES tiles a slice
 int dsl_stats_slices(int Bt) { return max(1, min(DSL_MAX_SLICES, (max(Bt, 1) + 15) / 16 / TK_MIN_TILES)); }
 size_t tk_stream_lds(int K, int k) { return (size_t)TK_QROWS * (K + TK_QPAD) * 2 + (size_t)TK_WAVES * TK_QROWS * k * sizeof(u64); }
+template <int MASK>
+auto tk_stream_kernel_of(bool dsl, bool grouped) {
+    return grouped ? (dsl ? topk_stream_kernel<true, true, MASK> : topk_stream_kernel<false, true, MASK>)
+                   : (dsl ? topk_stream_kernel<true, false, MASK> : topk_stream_kernel<false, false, MASK>);
+}
 
 }  // namespace
 
@@ -514,13 +650,16 @@ size_t cc_similarity_topk_workspace_bytes(int32_t Bq, int32_t Bg, int32_t k) {
     return cc_align_up((size_t)Bq * tk_slices(Bq, Bg) * k * sizeof(u64), 256);
 }
 
-// the checks and the two launches of both top-k entries; dsl: m, s, on_gallery, n_total of the rewrite
+// the checks and the two launches of all top-k entries; dsl: m, s, on_gallery, n_total of the rewrite; masked: row_mask,
+// mask_rows (1 or Bq), mask_words
 static int tk_launch(bool dsl, bool grouped, const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
                      float mult, int32_t products, int32_t k, const float* m, const float* s, int32_t on_gallery, int32_t n_total,
-                     const int32_t* group_head, float* scores, int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
+                     const int32_t* group_head, float* scores, int32_t* ids, void* ws, size_t ws_bytes, void* stream,
+                     bool masked = false, const int32_t* row_mask = nullptr, int32_t mask_rows = 0, int32_t mask_words = 0) {
     if (!query_planes || !gallery_planes || !scores || !ids || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
     if (dsl && (!m || !s || n_total < 0 || (on_gallery != 0 && on_gallery != 1))) return CC_ERR_INVALID;
     if (grouped && !group_head) return CC_ERR_INVALID;
+    if (masked && (!row_mask || (mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
     if (k < 1 || k > TK_MAXK || products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
     const int K = products * E;
     const size_t smem = tk_stream_lds(K, k);
@@ -529,13 +668,13 @@ static int tk_launch(bool dsl, bool grouped, const void* query_planes, const voi
     if (!ws || ws_bytes < cc_similarity_topk_workspace_bytes(Bq, Bg, k)) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int slices = tk_slices(Bq, Bg);
-    const auto kernel = grouped ? (dsl ? topk_stream_kernel<true, true> : topk_stream_kernel<false, true>)
-                                : (dsl ? topk_stream_kernel<true, false> : topk_stream_kernel<false, false>);
+    const auto kernel = !masked ? tk_stream_kernel_of<0>(dsl, grouped)                 // one shared mask row also when Bq == 1
+                                : mask_rows == 1 ? tk_stream_kernel_of<1>(dsl, grouped) : tk_stream_kernel_of<2>(dsl, grouped);
     if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
     hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
                        static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K,
                        mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, k, slices, static_cast<u64*>(ws), m, s,
-                       on_gallery, (float)n_total, group_head);
+                       on_gallery, (float)n_total, group_head, row_mask, mask_words);
     CC_LAUNCH_CHECK();
     hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(ws), slices, k, scores, ids);
     CC_LAUNCH_CHECK();
@@ -572,6 +711,25 @@ int cc_similarity_topk_grouped_dsl_planes_f32(const void* query_planes, const vo
                      group_head, scores, ids, ws, ws_bytes, stream);
 }
 
+int cc_similarity_topk_masked_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                         float mult, int32_t products, int32_t k, const int32_t* row_mask, int32_t mask_rows,
+                                         int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery,
+                                         int32_t n_total, const int32_t* group_head, float* scores, int32_t* ids, void* ws,
+                                         size_t ws_bytes, void* stream) {
+    const bool dsl = m || s;                                               // (exactly one of them: refused as the _dsl entry does)
+    return tk_launch(dsl, group_head != nullptr, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s,
+                     dsl ? stats_on_gallery : 0, dsl ? n_total : 0, group_head, scores, ids, ws, ws_bytes, stream, true, row_mask,
+                     mask_rows, mask_words);
+}
+
+int cc_pack_row_mask_u8(const uint8_t* flags, int32_t rows, int32_t n, int32_t* out_words, int32_t words_per_row, void* stream) {
+    if (!flags || !out_words || rows <= 0 || n <= 0 || words_per_row < (n - 1) / 32 + 1) return CC_ERR_INVALID;
+    hipLaunchKernelGGL(pack_row_mask_kernel, dim3((words_per_row + 7) / 8, min(rows, 65535)), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), flags, rows, n, out_words, words_per_row);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
 int32_t cc_dsl_col_stats_planes_slices(int32_t Bt) { return Bt > 0 ? dsl_stats_slices(Bt) : 0; }
 
 size_t cc_dsl_col_stats_planes_workspace_bytes(int32_t Bt, int32_t Bv) {
@@ -579,9 +737,12 @@ size_t cc_dsl_col_stats_planes_workspace_bytes(int32_t Bt, int32_t Bv) {
     return cc_align_up((size_t)dsl_stats_slices(Bt) * Bv * 2 * sizeof(float), 256);
 }
 
-int cc_dsl_col_stats_planes_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv, int32_t E, float mult,
-                                int32_t products, float* m, float* s, void* ws, size_t ws_bytes, void* stream) {
+// the checks and the two launches of both statistics entries
+static int dsl_stats_launch(bool masked, const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv, int32_t E,
+                            float mult, int32_t products, const int32_t* text_mask, float* m, float* s, void* ws, size_t ws_bytes,
+                            void* stream) {
     if (!video_planes || !m || !s || Bt < 0 || Bv <= 0 || E <= 0 || (Bt > 0 && !text_planes)) return CC_ERR_INVALID;
+    if (masked && Bt > 0 && !text_mask) return CC_ERR_INVALID;
     if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
     const int K = products * E;
     const size_t smem = (size_t)TK_QROWS * (K + TK_QPAD) * 2;
@@ -591,13 +752,25 @@ int cc_dsl_col_stats_planes_f32(const void* text_planes, const void* video_plane
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int slices = Bt > 0 ? dsl_stats_slices(Bt) : 0;
     if (slices > 0) {
-        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(dsl_stats_stream_kernel), smem) != CC_OK) return CC_ERR_HIP;
-        hipLaunchKernelGGL(dsl_stats_stream_kernel, dim3(slices, (Bv + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
+        const auto kernel = masked ? dsl_stats_stream_kernel<true> : dsl_stats_stream_kernel<false>;
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
+        hipLaunchKernelGGL(kernel, dim3(slices, (Bv + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
                            static_cast<const _Float16*>(video_planes), static_cast<const _Float16*>(text_planes), Bv, Bt, 3 * E, K,
-                           mult * 9.5367431640625e-07f, slices, static_cast<float*>(ws));
+                           mult * 9.5367431640625e-07f, slices, static_cast<float*>(ws), text_mask);
         CC_LAUNCH_CHECK();
     }
     return cc_launch_dsl_col_merge(static_cast<const float*>(ws), slices, Bv, m, s, st);      // no slice: (-inf, 0)
+}
+
+int cc_dsl_col_stats_planes_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv, int32_t E, float mult,
+                                int32_t products, float* m, float* s, void* ws, size_t ws_bytes, void* stream) {
+    return dsl_stats_launch(false, text_planes, video_planes, Bt, Bv, E, mult, products, nullptr, m, s, ws, ws_bytes, stream);
+}
+
+int cc_dsl_col_stats_planes_masked_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv, int32_t E,
+                                       float mult, int32_t products, const int32_t* text_mask, float* m, float* s, void* ws,
+                                       size_t ws_bytes, void* stream) {
+    return dsl_stats_launch(true, text_planes, video_planes, Bt, Bv, E, mult, products, text_mask, m, s, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

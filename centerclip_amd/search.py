@@ -27,6 +27,13 @@ eval_epoch ranks video->text on the maximum over a video's sentences) or the win
     gallery = FeatureGallery(model, side="text", grouped=True)
     gallery.add(input_ids, group=video_index)             # one label for the batch, or one per row; equal neighbours = a group
     scores, groups, pos = gallery.search_groups(video, video_mask, k=10)    # the 10 best videos, each by its best sentence
+
+Rows leave and searches narrow with one bit per row (``similarity_topk_masked``), without re-encoding or a second gallery:
+
+    gallery.remove(pos[:3])                               # no longer ranked; the other rows keep their positions
+    tenant = gallery.row_mask(positions=mine)             # built once on the host ...
+    scores, ids = gallery.search(input_ids, k=10, allow=tenant)             # ... passed to any number of searches
+    new_pos = gallery.compact()                           # drop the holes: the gallery of the surviving rows
 """
 import numpy as np
 import torch
@@ -67,7 +74,16 @@ class FeatureGallery:
     their group to appear (equal scores: the smaller position, between groups and inside one); (-inf, -1, -1) beyond the
     number of groups.  ``search*`` keep ranking rows.  With dual_softmax=True the statistics are what they are without
     groups - side="text": over all captions held - so the group maximum of D is what eval_epoch ranks video->text on the
-    multi-sentence sets."""
+    multi-sentence sets.
+
+    Removing and restricting (``similarity_topk_masked``: a bit per row, still one pass, exact): ``remove(positions)`` /
+    ``remove_groups(labels)`` take rows out - the others keep their positions, ``len(gallery)`` counts the rows held,
+    ``gallery.span`` the positions in use, ``compact()`` closes the holes and returns the map old -> new position.
+    ``search*(..., allow=mask)`` ranks a subset (``row_mask`` builds one on the host).  The ranking sees ``allow & live``; the
+    results are those of a gallery holding only these rows, at their positions here.  dual_softmax=True: side="video" - a
+    clip's statistics never depended on other clips; side="text" - the statistics run over the captions still held
+    (n_total = len(self)), and ``allow`` restricts the ranking, not the softmax.  A gallery that never removes a row and
+    never gets ``allow=`` allocates and launches what it did without any of this."""
 
     def __init__(self, model, side="video", capacity=0, products=None, dual_softmax=False, grouped=False):
         if side not in SIDES:
@@ -90,6 +106,7 @@ class FeatureGallery:
             self._bank = None                                    # side="video": operand rows of the captions, [n_bank, 3E]
             self._m = torch.zeros(self._rows.shape[0], device=self.device)       # per row held (side="video"): max_t S[t, v]
             self._s = torch.zeros(self._rows.shape[0], device=self.device)       # and sum_t exp(S[t, v] - m_v) over the bank
+        self._forget_removals()                                  # (nothing is allocated until the first remove)
         self.grouped = bool(grouped)
         if self.grouped:
             self._head = torch.zeros(self._rows.shape[0], device=self.device, dtype=torch.int32)     # first row of the row's group
@@ -99,11 +116,18 @@ class FeatureGallery:
             self._reset_groups()
 
     def __len__(self):
+        """Rows held: the positions in use minus the removed ones."""
+        return self._n if self._live is None else int(self._live_count)
+
+    @property
+    def span(self):
+        """Positions in use, removed ones included: the next row added gets position ``span``."""
         return self._n
 
     def clear(self):
-        """Empty the rows and the groups (a dual-softmax gallery keeps its bank)."""
+        """Empty the rows and the groups and forget the removals (a dual-softmax gallery keeps its bank)."""
         self._n = 0
+        self._forget_removals()
         if self._grouped:
             self._reset_groups()
 
@@ -116,14 +140,23 @@ class FeatureGallery:
         return getattr(self, "grouped", False)
 
     @property
+    def _live(self):
+        """None until the first ``remove``; then a NumPy bool per position in use, False = removed (the host mirror of
+        the device words ``_live_dev``)"""
+        return getattr(self, "_live_host", None)               # (an instance built without the constructor: nothing removed)
+
+    @property
     def num_groups(self):
-        """Groups held (grouped=True)."""
+        """Groups held (grouped=True); after ``remove``: the groups with a row still held."""
         self._need_grouped("num_groups")
-        return self._groups
+        if self._live is None:
+            return self._groups
+        return int(np.unique(self.labels.numpy()[self._live]).size)      # (a label never returns: one label, one group)
 
     @property
     def labels(self):
-        """The label of every row held, a CPU LongTensor [len(self)] (grouped=True)."""
+        """The label of every position in use, a CPU LongTensor [span] (grouped=True); removed rows keep theirs until
+        ``compact()``."""
         self._need_grouped("labels")
         if len(self._label_chunks) != 1:
             self._label_chunks = [torch.cat(self._label_chunks) if self._label_chunks else torch.zeros(0, dtype=torch.int64)]
@@ -131,7 +164,8 @@ class FeatureGallery:
 
     @property
     def rows(self):
-        """The operand rows held, [len(self), 3E] fp16 (a view of the buffer)."""
+        """The operand rows of the positions in use, [span, 3E] fp16 (a view of the buffer; removed rows included until
+        ``compact()``)."""
         return self._rows[:self._n]
 
     # ------------------------------------------------------------------ operand rows of either side
@@ -185,6 +219,10 @@ class FeatureGallery:
                 self._label_dev = labels
         self._rows[start:n] = rows
         self._n = n
+        if self._live is not None and n > start:                 # rows behind removed ones: new positions, live
+            self._live_host = np.concatenate((self._live, np.ones(n - start, dtype=bool)))
+            self._live_count += n - start
+            self._upload_live(start >> 5, T.mask_words(n))
         if plan is not None:
             self._take_groups(plan, start, n)
         if self._dsl:
@@ -216,7 +254,11 @@ class FeatureGallery:
         self._set_bank(self._text_rows, sequence_output)
 
     def _query_stats(self, q):
-        """side="text": the query clips' (m, s) over the captions held"""
+        """side="text": the query clips' (m, s) over the captions held (after ``remove``: over those still held, whatever a
+        search's ``allow=`` says - it restricts the ranking, not the softmax)"""
+        if self._live is not None:
+            return torch.ops.centerclip.dsl_col_stats_planes_masked(self._rows, q, self._n, q.shape[0], self._mult(),
+                                                                    self.products, self._live_words())
         return torch.ops.centerclip.dsl_col_stats_planes(self._rows, q, self._n, q.shape[0], self._mult(), self.products)
 
     def _need_bank(self):
@@ -306,6 +348,178 @@ class FeatureGallery:
         self._check_group_arg(group, "add_features")
         return self._append(self._video_rows(features, mask) if self.side == "video" else self._text_rows(features), group)
 
+    # ------------------------------------------------------------------ removing rows: the live mask, on the host
+    @staticmethod
+    def _pack_words(flags):
+        """bool [n] -> int32 [ceil(n / 32)], bit b of word w = flag 32 w + b (the ops' mask format)"""
+        flags = np.asarray(flags, dtype=bool)
+        padded = np.zeros(T.mask_words(flags.shape[0]) * 32, dtype=bool)
+        padded[:flags.shape[0]] = flags
+        return np.packbits(padded, bitorder="little").view("<i4").astype(np.int32)
+
+    def _forget_removals(self):
+        self._live_host, self._live_dev, self._live_count = None, None, 0
+
+    def _upload_live(self, w0, w1):
+        """words [w0, w1) of the live mask, computed from the host mirror, to the device buffer (which grows with the rows)"""
+        need = T.mask_words(max(self._rows.shape[0], self._n, 1))
+        dev = getattr(self, "_live_dev", None)
+        if dev is None or dev.shape[0] < need:
+            self._live_dev = torch.zeros(need, device=self.device, dtype=torch.int32)
+            w0, w1 = 0, T.mask_words(self._n)
+        if w1 > w0:
+            self._live_dev[w0:w1] = self._host_to_device(self._pack_words(self._live[32 * w0:32 * w1]))
+
+    def _live_words(self):
+        """the live mask over the positions in use, int32 [ceil(span / 32)] on the device"""
+        return self._live_dev[:T.mask_words(self._n)]
+
+    def _positions(self, positions, what):
+        """int / host sequence / CPU LongTensor -> int64 array of distinct positions inside [0, span): checks only"""
+        if torch.is_tensor(positions):
+            if positions.device.type != "cpu" or positions.dtype != torch.int64:
+                raise ValueError("FeatureGallery.%s: positions are an int, a host sequence or a CPU LongTensor, not a %s %s "
+                                 "tensor (reading a device tensor would synchronise)" % (what, positions.device, positions.dtype))
+            pos = positions.numpy().reshape(-1) if positions.dim() <= 1 else None
+        elif isinstance(positions, (int, np.integer)):
+            pos = np.array([int(positions)])
+        else:
+            pos = np.asarray(list(positions))
+            pos = pos if pos.ndim == 1 and (pos.size == 0 or pos.dtype.kind in "iu") else None
+        if pos is None:
+            raise ValueError("FeatureGallery.%s: positions are one int or a flat sequence of ints" % what)
+        pos = pos.astype(np.int64)
+        if pos.size and (pos.min() < 0 or pos.max() >= self._n):
+            raise ValueError("FeatureGallery.%s: position %d is outside [0, %d)"
+                             % (what, int(pos[(pos < 0) | (pos >= self._n)][0]), self._n))
+        if np.unique(pos).size != pos.size:
+            raise ValueError("FeatureGallery.%s: a position is listed twice" % what)
+        return pos
+
+    def remove(self, positions):
+        """Take rows out: ``search*`` no longer ranks them, ``similarity*`` shows -inf in their columns.  ``positions``: an
+        int, a host sequence or a CPU LongTensor (never a device tensor: no synchronisation).  The other rows keep their
+        positions and rows added later get new ones behind ``span`` - ``compact()`` closes the holes.  A position outside
+        [0, span), already removed or listed twice: ValueError, nothing changed."""
+        pos = self._positions(positions, "remove")
+        live = self._live
+        if live is not None and pos.size and not live[pos].all():
+            raise ValueError("FeatureGallery.remove: position %d is already removed" % int(pos[~live[pos]][0]))
+        if pos.size == 0:
+            return
+        if live is None:
+            self._live_host, self._live_dev, self._live_count = np.ones(self._n, dtype=bool), None, self._n
+        self._live_host[pos] = False
+        self._live_count -= int(pos.size)
+        if getattr(self, "_live_dev", None) is None:
+            self._upload_live(0, T.mask_words(self._n))
+        else:                                                    # one upload: the words from the first to the last changed one
+            self._upload_live(int(pos.min()) >> 5, (int(pos.max()) >> 5) + 1)
+        if self._grouped and self._open is not None and not self._live_host[self._open[1]:].any():
+            self._closed.add(self._open[0])                      # the last group is gone: rows added next start a new one,
+            self._open = None                                    # and its label stays refused like any other held label
+
+    @staticmethod
+    def _label_list(labels, what):
+        """an int, a host sequence or a CPU LongTensor of labels -> int64 array (a device tensor would have to be read)"""
+        if torch.is_tensor(labels):
+            if labels.device.type != "cpu" or labels.dtype != torch.int64:
+                raise ValueError("FeatureGallery.%s: labels are an int, a host sequence or a CPU LongTensor, not a %s %s tensor "
+                                 "(reading a device tensor would synchronise)" % (what, labels.device, labels.dtype))
+            return labels.numpy().reshape(-1).astype(np.int64)
+        if isinstance(labels, (int, np.integer)):
+            return np.array([int(labels)], dtype=np.int64)
+        lab = np.asarray(list(labels))
+        if lab.ndim != 1 or (lab.size and lab.dtype.kind not in "iu"):
+            raise ValueError("FeatureGallery.%s: labels are one int or a flat sequence of ints" % what)
+        return lab.astype(np.int64)
+
+    def remove_groups(self, labels):
+        """grouped=True: ``remove`` all rows still held of the groups with these labels (an int, a host sequence or a CPU
+        LongTensor - never a device tensor).  A label
+        no row held carries: ValueError, nothing changed.  The labels stay refused by ``add`` until ``compact()``."""
+        self._need_grouped("remove_groups")
+        want = np.unique(self._label_list(labels, "remove_groups"))
+        held = self.labels.numpy()
+        hit = np.isin(held, want) & (self._live if self._live is not None else True)
+        missing = np.setdiff1d(want, held[hit])
+        if missing.size:
+            raise ValueError("FeatureGallery.remove_groups: no row held has the label %d" % int(missing[0]))
+        self.remove(np.flatnonzero(hit))
+
+    def row_mask(self, positions=None, groups=None):
+        """A mask for ``allow=``, built on the host: int32 [ceil(span / 32)] on the device with the bits of ``positions`` (as
+        ``remove`` takes them) and of the rows of the groups labelled ``groups`` (grouped=True) set; neither: every position.
+        Build it once per subset - a tenant, a channel - and pass it to any number of searches; it describes the positions in
+        use now (a mask built before rows were added lacks their bits, and after ``compact()`` it is stale)."""
+        flags = np.zeros(self._n, dtype=bool)
+        if positions is None and groups is None:
+            flags[:] = True
+        if positions is not None:
+            flags[self._positions(positions, "row_mask")] = True
+        if groups is not None:
+            self._need_grouped("row_mask")
+            want = self._label_list(groups, "row_mask")
+            held = self.labels.numpy()
+            missing = np.setdiff1d(want, held)
+            if missing.size:
+                raise ValueError("FeatureGallery.row_mask: no row has the label %d" % int(missing[0]))
+            flags |= np.isin(held, want)
+        words = self._pack_words(flags)
+        return self._host_to_device(words) if words.size else torch.zeros(0, device=self.device, dtype=torch.int32)
+
+    def compact(self):
+        """Drop the removed rows, keep the order of the others -> CPU LongTensor [old span]: every row's new position, -1 for
+        the removed ones.  Afterwards the gallery is, bit for bit, the one to which only the surviving rows were added in
+        that order (statistics and labels move with their rows, the groups are rebuilt from the surviving labels, removed
+        labels are free again).  One index_select per buffer with an index computed on the host: no new kernel, no
+        synchronisation.  Nothing removed: nothing happens."""
+        live, old = self._live, self._n
+        if live is None:
+            return torch.arange(old)
+        keep = np.flatnonzero(live)
+        cnt = int(keep.size)
+        new_pos = np.full(old, -1, dtype=np.int64)
+        new_pos[keep] = np.arange(cnt)
+        labels = self.labels[torch.from_numpy(keep)] if self._grouped else None
+        if cnt:
+            index = self._host_to_device(keep)
+            for name in ("_rows",) + (("_m", "_s") if self._dsl else ()):
+                buf = getattr(self, name)
+                buf[:cnt] = buf.index_select(0, index)           # (index_select copies first: no overlap)
+        self._n = cnt
+        self._forget_removals()
+        if self._grouped:
+            self._reset_groups()
+            self._take_groups(self._plan_groups(labels, 0, cnt), 0, cnt)
+        return torch.from_numpy(new_pos)
+
+    def _allow_words(self, allow, nq):
+        """``allow=`` of a search over nq queries -> None, or the mask the ranking sees (``allow & live``): int32 [W] or [nq, W]"""
+        words, live = T.mask_words(self._n), None if self._live is None else self._live_words()
+        if allow is None:
+            return live
+        if not torch.is_tensor(allow) or allow.device != self._rows.device:
+            raise ValueError("FeatureGallery: allow= is a tensor on the gallery's device (an int32 mask [W] or [Nq, W], a bool "
+                             "tensor [span] or [Nq, span], or what row_mask() returns)")
+        if allow.dim() not in (1, 2) or (allow.dim() == 2 and allow.shape[0] != nq):
+            raise ValueError("FeatureGallery: allow= %s is neither one mask nor one per query (%d)" % (tuple(allow.shape), nq))
+        if allow.dtype == torch.bool:
+            if allow.shape[-1] != self._n:
+                raise ValueError("FeatureGallery: a bool allow= has one flag per position in use (%d), not %d"
+                                 % (self._n, allow.shape[-1]))
+            if self._n == 0:
+                return None                                      # (no position in use: nothing to pack, the search gives the fill)
+            packed = torch.ops.centerclip.pack_row_mask(allow)
+            allow = packed[0] if allow.dim() == 1 else packed
+        elif allow.dtype != torch.int32:
+            raise ValueError("FeatureGallery: allow= is int32 mask words or bool flags, not %s" % allow.dtype)
+        if allow.shape[-1] < words:
+            raise ValueError("FeatureGallery: allow= holds %d words, the %d positions in use need %d"
+                             % (allow.shape[-1], self._n, words))
+        allow = allow[..., :words]
+        return (allow if live is None else allow & live).contiguous()
+
     # ------------------------------------------------------------------ asking
     def _mult(self):
         return T.logit_multiplier(self.core._logit_scale_value())
@@ -313,17 +527,27 @@ class FeatureGallery:
     def _query_rows(self, features, mask):
         return self._text_rows(features) if self.side == "video" else self._video_rows(features, mask)
 
-    def _search_rows(self, q, k, groups=False):
-        """the k best rows - groups: the best row of each of the k best groups - of every row of q"""
+    def _search_rows(self, q, k, groups=False, allow=None):
+        """the k best rows - groups: the best row of each of the k best groups - of every row of q; after ``remove`` or with
+        ``allow=``: of the rows both leave selectable"""
         k = int(k)
         if self._dsl:
             self._need_bank()
-        if self._n == 0:                                    # nothing to rank: the fill of a list longer than the gallery
+        mask = self._allow_words(allow, q.shape[0])
+        if len(self) == 0:                                  # nothing to rank: the fill of a list longer than the gallery
             if not 1 <= k <= 128:
                 raise ValueError("FeatureGallery: 1 <= k <= 128")
             return (torch.full((q.shape[0], k), float("-inf"), device=self.device),
                     torch.full((q.shape[0], k), -1, device=self.device, dtype=torch.int64))
         op, tail = torch.ops.centerclip, ((self._head,) if groups else ())
+        if mask is not None:                                # one op for the four rankings (no mask: the ops of before)
+            m = s = None
+            on_gallery, n_total = self.side == "video", 0
+            if self._dsl:
+                m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
+                n_total = self._bank.shape[0] if on_gallery else len(self)
+            return op.similarity_topk_masked(q, self._rows, self._n, self._mult(), self.products, k, mask, m, s, int(on_gallery),
+                                             n_total, self._head if groups else None)
         if self._dsl:
             on_gallery = self.side == "video"
             m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
@@ -333,29 +557,36 @@ class FeatureGallery:
         return (op.similarity_topk_grouped if groups else op.similarity_topk)(q, self._rows, self._n, self._mult(), self.products,
                                                                                k, *tail)
 
-    def _search_group_rows(self, q, k):
-        scores, pos = self._search_rows(q, k, groups=True)
+    def _search_group_rows(self, q, k, allow=None):
+        scores, pos = self._search_rows(q, k, groups=True, allow=allow)
         return scores, self._label_dev[pos], pos                 # (position -1, the fill: the last entry, -1)
 
-    def search_groups(self, *inputs, k=10):
+    def search_groups(self, *inputs, k=10, allow=None):
         """grouped=True: the queries of ``search`` -> (scores [Nq, k] fp32, labels [Nq, k] int64, positions [Nq, k] int64) of
-        the k best groups, best first, each by its best row (``positions``); (-inf, -1, -1) beyond the number of groups."""
+        the k best groups, best first, each by its best row (``positions``); (-inf, -1, -1) beyond the number of groups.
+        After ``remove`` / with ``allow=`` (see ``search``): a group is ranked by its best selectable row, one without any
+        does not appear."""
         self._need_grouped("search_groups")
-        return self._search_group_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), k)
+        return self._search_group_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), k,
+                                       allow)
 
-    def search_groups_features(self, features, k=10, mask=None):
+    def search_groups_features(self, features, k=10, mask=None, allow=None):
         """``search_groups`` for query features computed elsewhere (as ``search_features``)."""
         self._need_grouped("search_groups_features")
-        return self._search_group_rows(self._query_rows(features, mask), k)
+        return self._search_group_rows(self._query_rows(features, mask), k, allow)
 
-    def search(self, *inputs, k=10):
+    def search(self, *inputs, k=10, allow=None):
         """``search(input_ids, k=10)`` (``search(video, video_mask, k=10)`` for side="text") -> (scores [Nq, k] fp32, positions
-        [Nq, k] int64), best first, equal scores by smaller position; (-inf, -1) beyond the gallery's size."""
-        return self._search_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), k)
+        [Nq, k] int64), best first, equal scores by smaller position; (-inf, -1) beyond the gallery's size.  Removed rows are
+        not ranked.  ``allow=``: rank a subset only - an int32 mask [W] or [Nq, W] on the device (bit b of word w = position
+        32 w + b, W >= ceil(span / 32)), a device bool tensor [span] or [Nq, span], or what ``row_mask`` returns; one mask
+        for all queries also skips the tiles of 16 rows it leaves empty.  The fill starts behind the selectable rows."""
+        return self._search_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), k,
+                                 allow=allow)
 
-    def search_features(self, features, k=10, mask=None):
+    def search_features(self, features, k=10, mask=None, allow=None):
         """``search`` for query features computed elsewhere (sequence_output; side="text": visual_output and its mask)."""
-        return self._search_rows(self._query_rows(features, mask), k)
+        return self._search_rows(self._query_rows(features, mask), k, allow=allow)
 
     def _matrix(self, q):
         n = self._n
@@ -370,8 +601,12 @@ class FeatureGallery:
         if self._dsl:                                            # the checking path: the matrix, then the rewrite in place
             self._need_bank()
             m, s = (self._m[:n], self._s[:n]) if self.side == "video" else self._query_stats(q)
-            torch.ops.centerclip.dsl_apply_(sim, m.contiguous(), s.contiguous(), self._bank.shape[0] if self.side == "video" else n)
-        return sim if self.side == "video" else sim.t().contiguous()
+            torch.ops.centerclip.dsl_apply_(sim, m.contiguous(), s.contiguous(),
+                                            self._bank.shape[0] if self.side == "video" else len(self))
+        sim = sim if self.side == "video" else sim.t().contiguous()
+        if self._live is not None:                               # removed rows: -inf in their columns
+            sim.masked_fill_(~self._host_to_device(self._live.copy())[None, :], float("-inf"))
+        return sim
 
     def similarity(self, *inputs):
         """The whole [Nq, len(self)] matrix of the queries ``search`` takes, through the matrix op of eval_epoch (on a zero-
@@ -386,6 +621,8 @@ class FeatureGallery:
     def state_dict(self):
         state = {"rows": self._rows[:self._n].clone(), "count": self._n, "E": self.E, "side": self.side,
                  "products": self.products}
+        if self._live is not None:                               # (one key more, only after a remove: positions still held)
+            state["live"] = torch.from_numpy(self._live.copy())
         if self._dsl:                                            # (a plain gallery's keys are what they were)
             state.update(dual_softmax=True, bank=None if self._bank is None else self._bank.clone(),
                          m=self._m[:self._n].clone(), s=self._s[:self._n].clone())
@@ -412,6 +649,9 @@ class FeatureGallery:
         if rows.dim() != 2 or tuple(rows.shape) != (count, 3 * self.E) or rows.dtype != torch.float16:
             raise ValueError("FeatureGallery.load_state_dict: rows %s %s do not match count %d, E %d"
                              % (tuple(rows.shape), rows.dtype, count, self.E))
+        live = state.get("live")
+        if live is not None and (not torch.is_tensor(live) or live.dtype != torch.bool or tuple(live.shape) != (count,)):
+            raise ValueError("FeatureGallery.load_state_dict: live is a bool tensor of %d entries" % count)
         backend = HipBackend.with_products(int(state["products"]))
         if self._dsl:
             bank, m, s = state["bank"], state["m"], state["s"]
@@ -437,6 +677,7 @@ class FeatureGallery:
         if self._dsl:
             self._bank = None                                    # (the saved statistics are taken over, not recomputed)
         self._n = 0
+        self._forget_removals()
         self._append(rows.to(self.device), labels)
         self.products, self.backend = int(state["products"]), backend
         if self._dsl:
@@ -444,6 +685,8 @@ class FeatureGallery:
             self._m[:count], self._s[:count] = m.to(self.device), s.to(self.device)
         if self._grouped:
             self._head[:count] = head.to(self.device)            # (what the labels give; the saved array is taken over)
+        if live is not None:
+            self.remove(np.flatnonzero(~live.cpu().numpy()))
 
 
 __all__ = ["FeatureGallery"]

@@ -1341,6 +1341,133 @@ def _(query_planes, gallery_planes, n_gallery, mult, products, k, m, s, stats_on
             query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
 
 
+def mask_words(n):
+    """int32 words of a row mask over n rows (bit b of word w = row 32 w + b)"""
+    return (int(n) + 31) // 32
+
+
+def _check_row_mask(name, mask, rows, n, planes, what="row_mask"):
+    """a row mask: int32, contiguous, [W] or - rows given - [rows, W] with W >= ceil(n / 32), on the planes' device"""
+    shapes = "[W]" if rows is None else "[W] or [%d, W]" % rows
+    if (mask.dtype != torch.int32 or not mask.is_contiguous() or mask.dim() not in ((1,) if rows is None else (1, 2))
+            or (mask.dim() == 2 and mask.shape[0] != rows) or mask.shape[-1] < mask_words(n)):
+        raise ValueError("%s: %s %s %s is not a contiguous int32 mask %s of W >= %d words"
+                         % (name, what, tuple(mask.shape), mask.dtype, shapes, mask_words(n)))
+    if mask.device != planes.device:
+        raise ValueError("%s: %s on %s, the planes on %s" % (name, what, mask.device, planes.device))
+
+
+def _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head):
+    name = "similarity_topk_masked"
+    if group_head is not None:
+        E3 = _check_group_head(name, query_planes, gallery_planes, n_gallery, group_head)
+    else:
+        E3 = _check_plane_pair(name, query_planes, gallery_planes, n_gallery)
+    if query_planes.device != gallery_planes.device:
+        raise ValueError("%s: the planes on %s and %s" % (name, query_planes.device, gallery_planes.device))
+    if (m is None) != (s is None):
+        raise ValueError("%s: m and s come together (both for the dual softmax, neither for S)" % name)
+    if m is not None:
+        _check_dsl_stats(name, m, s, int(n_gallery) if stats_on_gallery else query_planes.shape[0])
+    _check_row_mask(name, row_mask, query_planes.shape[0], n_gallery, gallery_planes)
+    return E3
+
+
+@custom_op(NS + "::similarity_topk_masked", mutates_args=(), device_types="cuda")
+def similarity_topk_masked(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                           k: int, row_mask: torch.Tensor, m: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None,
+                           stats_on_gallery: int = 1, n_total: int = 0,
+                           group_head: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """similarity_topk (m, s: similarity_topk_dsl; group_head: the grouped ops) over the gallery rows whose bit is set in
+    row_mask: int32 words, bit b of word w = row 32 w + b; [W] - one mask for all queries, tiles of 16 rows without a set bit
+    are not even read - or [Bq, W], one mask per query row; W >= ceil(n_gallery / 32), bits at or above n_gallery are ignored.
+    The result is the unmasked op's with the other rows left out (same bits, same order, ids of the whole gallery; the fill
+    starts behind the selectable rows or groups - a group is ranked by its best selectable row).
+    cc_similarity_topk_masked_planes_f32."""
+    Bq = query_planes.shape[0]
+    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
+    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
+    if m is not None:
+        m, s = m.contiguous(), s.contiguous()
+    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
+    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
+    lib = L.lib()
+    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
+    L.check(lib.cc_similarity_topk_masked_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
+                                                     float(mult), int(products), int(k), L.ptr(row_mask),
+                                                     1 if row_mask.dim() == 1 else Bq, int(row_mask.shape[-1]), L.ptr(m), L.ptr(s),
+                                                     int(stats_on_gallery), int(n_total), L.ptr(group_head), L.ptr(scores),
+                                                     L.ptr(ids), L.ptr(ws), ws.numel(), _st(query_planes)),
+            "cc_similarity_topk_masked_planes_f32")
+    return scores, ids.to(torch.int64)
+
+
+@similarity_topk_masked.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, k, row_mask, m=None, s=None, stats_on_gallery=1, n_total=0,
+      group_head=None):
+    _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
+    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
+            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+
+
+def _check_masked_stats(text_planes, video_planes, n_text, n_video, text_mask):
+    name = "dsl_col_stats_planes_masked"
+    E3 = _check_plane_pair(name, video_planes, text_planes, n_text)
+    if video_planes.dim() != 2 or video_planes.shape[0] < int(n_video):
+        raise ValueError("%s: video planes %s do not hold %d rows" % (name, tuple(video_planes.shape), int(n_video)))
+    _check_row_mask(name, text_mask, None, n_text, text_planes, "text_mask")
+    return E3
+
+
+@custom_op(NS + "::dsl_col_stats_planes_masked", mutates_args=(), device_types="cuda")
+def dsl_col_stats_planes_masked(text_planes: torch.Tensor, video_planes: torch.Tensor, n_text: int, n_video: int, mult: float,
+                                products: int, text_mask: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """dsl_col_stats_planes over the text rows whose bit is set in text_mask (int32 [W], W >= ceil(n_text / 32), the format of
+    similarity_topk_masked): the same tree with the other rows' terms left out - m bit-equal to the maximum over the set rows,
+    all ones = the unmasked op's bits, no row set = (-inf, 0).  cc_dsl_col_stats_planes_masked_f32."""
+    E3 = _check_masked_stats(text_planes, video_planes, n_text, n_video, text_mask)
+    text_planes, video_planes = text_planes.contiguous(), video_planes.contiguous()
+    m = _e(int(n_video), like=video_planes, dtype=torch.float32)
+    s = _e(int(n_video), like=video_planes, dtype=torch.float32)
+    lib = L.lib()
+    ws = L.workspace(lib.cc_dsl_col_stats_planes_workspace_bytes(int(n_text), int(n_video)), video_planes.device)
+    L.check(lib.cc_dsl_col_stats_planes_masked_f32(L.ptr(text_planes), L.ptr(video_planes), int(n_text), int(n_video), E3 // 3,
+                                                   float(mult), int(products), L.ptr(text_mask), L.ptr(m), L.ptr(s), L.ptr(ws),
+                                                   ws.numel(), _st(video_planes)), "cc_dsl_col_stats_planes_masked_f32")
+    return m, s
+
+
+@dsl_col_stats_planes_masked.register_fake
+def _(text_planes, video_planes, n_text, n_video, mult, products, text_mask):
+    _check_masked_stats(text_planes, video_planes, n_text, n_video, text_mask)
+    return (video_planes.new_empty((n_video,), dtype=torch.float32), video_planes.new_empty((n_video,), dtype=torch.float32))
+
+
+def _check_flags(flags):
+    if flags.dtype not in (torch.bool, torch.uint8) or flags.dim() not in (1, 2) or flags.shape[-1] < 1:
+        raise ValueError("pack_row_mask: flags %s %s are not bool or uint8 [n] or [R, n], n >= 1" % (tuple(flags.shape), flags.dtype))
+
+
+@custom_op(NS + "::pack_row_mask", mutates_args=(), device_types="cuda")
+def pack_row_mask(flags: torch.Tensor) -> torch.Tensor:
+    """bool or uint8 flags [R, n] (or [n]: one row), non-zero = selectable -> the row masks of similarity_topk_masked, int32
+    [R, ceil(n / 32)]: bit b of word w = flag 32 w + b, the bits at or above n zero.  cc_pack_row_mask_u8."""
+    _check_flags(flags)
+    flat = flags.reshape(-1, flags.shape[-1]).contiguous()
+    flat = flat.view(torch.uint8) if flat.dtype == torch.bool else flat
+    R, n = flat.shape
+    out = _e(R, mask_words(n), like=flat, dtype=torch.int32)
+    if R:
+        L.check(L.lib().cc_pack_row_mask_u8(L.ptr(flat), R, n, L.ptr(out), mask_words(n), _st(flat)), "cc_pack_row_mask_u8")
+    return out
+
+
+@pack_row_mask.register_fake
+def _(flags):
+    _check_flags(flags)
+    return flags.new_empty((flags.numel() // flags.shape[-1], mask_words(flags.shape[-1])), dtype=torch.int32)
+
+
 def padded_video_rows(n_video):
     """Rows a video-side plane buffer needs for n_video videos (whole GEMM tiles; the rows behind n_video must be zero)."""
     return int(L.lib().cc_similarity_padded_rows(int(n_video)))
@@ -1596,7 +1723,8 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "rank_counts_cols", "rank_counts_ref", "group_max_rows", "normalize_rows_planes", "video_pool_normalize_planes",
        "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
        "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
-       "similarity_topk_grouped", "similarity_topk_grouped_dsl")
+       "similarity_topk_grouped", "similarity_topk_grouped_dsl", "similarity_topk_masked", "dsl_col_stats_planes_masked",
+       "pack_row_mask")
 
 
 def logit_multiplier(logit_scale):

@@ -22,6 +22,13 @@ against plain search_features on the same gallery and against what there was bef
 maximum, torch.topk - with groups of 1 row and of 1..G rows.
 
     python examples/search_synthetic.py --groups 40
+
+--remove FRACTION / --subset FRACTION take clips out of the gallery (remove, then compact) and search within a subset
+(allow= with a mask from row_mask or a device bool tensor), each checked against masking the matrix + torch.topk; the timing
+is similarity_topk_masked with an all-ones mask, one contiguous 1/16 of the rows, random halves (one mask, one per query) and
+the masked statistics pass against the unmasked ops - and, with --baseline-lib PATH, against another build's unmasked op.
+
+    python examples/search_synthetic.py --remove 0.25 --subset 0.3 [--baseline-lib other/libcenterclip_hip.so]
 """
 import argparse
 import os
@@ -238,6 +245,101 @@ def groups_part(model, device, a):
     print("same scores as the per-group maximum of the matrix: %s" % bool(torch.equal(full.values, scores[:, :full.values.shape[1]])))
 
 
+def masked_part(model, device, a):
+    """take clips out, search within a subset, close the holes - each against the matrix path on the same rows"""
+    data = SyntheticRetrieval(a.clips)
+    gallery = FeatureGallery(model)
+    gallery.add(data.video.to(device), data.vmask.to(device))
+    ids = data.ids[:a.captions].to(device)
+    g = torch.Generator().manual_seed(3)
+    order = torch.randperm(a.clips, generator=g)
+    gone = order[:int(a.remove * a.clips)].sort().values
+    subset = order[:max(1, int(a.subset * a.clips))].sort().values if a.subset else None      # (overlaps the removed ones)
+
+    def check(title, got, sim, selectable):
+        sim = sim.masked_fill(~selectable.to(device)[None, :], float("-inf"))
+        full = torch.topk(sim, min(a.k, int(selectable.sum())), dim=1)
+        print("%s: same scores as masking the matrix + topk: %s" % (title, bool(torch.equal(full.values, got[0][:, :full.values.shape[1]]))))
+    sim = gallery.similarity(ids)
+    live = torch.ones(a.clips, dtype=torch.bool)
+    if gone.numel():
+        gallery.remove(gone)
+        live[gone] = False
+        scores, found = gallery.search(ids, k=a.k)
+        print("removed %d of %d clips: %d held, span %d" % (gone.numel(), a.clips, len(gallery), gallery.span))
+        for i in range(ids.shape[0]):
+            print("caption %d: clips %s  scores %s" % (i, found[i].tolist(), ["%.4f" % s for s in scores[i].tolist()]))
+        check("after remove", (scores, found), sim, live)
+    if subset is not None:
+        mask = gallery.row_mask(positions=subset)                            # built once, passed to any number of searches
+        allowed = torch.zeros(a.clips, dtype=torch.bool)
+        allowed[subset] = True
+        check("allow= a subset of %d" % subset.numel(), gallery.search(ids, k=a.k, allow=mask), sim, allowed & live)
+        check("allow= the same subset as a device bool tensor", gallery.search(ids, k=a.k, allow=allowed.to(device)), sim, allowed & live)
+    new_pos = gallery.compact()
+    fresh = FeatureGallery(model)
+    fresh.add(data.video[live].to(device), data.vmask[live].to(device))
+    same = torch.equal(gallery.rows.view(torch.int16), fresh.rows.view(torch.int16))
+    print("compact(): %d rows, new positions of the first clips %s; the gallery of the survivors bit for bit: %s"
+          % (len(gallery), new_pos[:8].tolist(), same))
+
+
+def time_masked(model, device, rows, queries, k, reps, warmup, baseline_lib):
+    """The masked top-k entry at the shapes DESIGN.md records - all ones, one contiguous 1/16 of the rows, random halves (one
+    mask and one per query) - against the unmasked entry of this build and, with --baseline-lib, of another build of the
+    library (same buffers, same stream); then the masked statistics op against the unmasked one."""
+    import ctypes
+    op = torch.ops.centerclip
+    E = int(model.clip_config['embed_dim'])
+    g = torch.Generator(device=device).manual_seed(1)
+    unit = lambda n, video_side: op.normalize_rows_planes(torch.randn(n, E, device=device, generator=g), video_side)
+    products, mult = FeatureGallery(model).products, T.logit_multiplier(model._logit_scale_value())
+    clips, text_q, captions, clip_q = unit(rows, True), unit(queries, False), unit(rows, False), unit(queries, True)
+    flags = lambda *shape: torch.rand(*shape, device=device, generator=g) < 0.5
+    ones = op.pack_row_mask(torch.ones(rows, dtype=torch.bool, device=device))[0]
+    block = torch.zeros(rows, dtype=torch.bool, device=device)
+    block[rows // 2:rows // 2 + rows // 16] = True
+    sixteenth, half, per_query = op.pack_row_mask(block)[0], op.pack_row_mask(flags(rows))[0], op.pack_row_mask(flags(queries, rows))
+    # the library's entries called directly on buffers allocated once (no allocation, no int64 copy of the ids, a few
+    # microseconds of host work a call): behind the ops' host work a 1/16 search would hide
+    scores = torch.empty(queries, k, device=device)
+    found = torch.empty(queries, k, device=device, dtype=torch.int32)
+    ws = L.workspace(L.lib().cc_similarity_topk_workspace_bytes(queries, rows, k), device)
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+
+    def plain_of(lib):
+        lib.cc_similarity_topk_planes_f32.argtypes = [vp, vp, i32, i32, i32, ctypes.c_float, i32, i32, vp, vp, vp, ctypes.c_size_t, vp]
+        return lambda: L.check(lib.cc_similarity_topk_planes_f32(L.ptr(text_q), L.ptr(clips), queries, rows, E, mult, products, k,
+                                                                 L.ptr(scores), L.ptr(found), L.ptr(ws), ws.numel(),
+                                                                 L.stream_ptr(device)), "cc_similarity_topk_planes_f32")
+
+    def masked(mask):
+        return lambda: L.check(L.lib().cc_similarity_topk_masked_planes_f32(
+            L.ptr(text_q), L.ptr(clips), queries, rows, E, mult, products, k, L.ptr(mask), 1 if mask.dim() == 1 else queries,
+            mask.shape[-1], None, None, 1, 0, None, L.ptr(scores), L.ptr(found), L.ptr(ws), ws.numel(), L.stream_ptr(device)),
+            "cc_similarity_topk_masked_planes_f32")
+    want = op.similarity_topk(text_q, clips, rows, mult, products, k)
+    fns = [("cc_similarity_topk_planes_f32 (this build)", plain_of(L.lib()))]
+    if baseline_lib:
+        fns.append(("cc_similarity_topk_planes_f32 (--baseline-lib)", plain_of(ctypes.CDLL(baseline_lib))))
+    fns += [("cc_similarity_topk_masked_planes_f32, all ones", masked(ones))]
+    for _, fn in fns:                                                        # both builds, and the all-ones mask: the op's result
+        scores.zero_()
+        fn()
+        assert torch.equal(scores, want[0]) and torch.equal(found.long(), want[1]), "the paths disagree"
+    fns += [("... one contiguous 1/16 of the rows", masked(sixteenth)),
+            ("... random p = 0.5 (every tile live)", masked(half)),
+            ("... one mask per query, p = 0.5", masked(per_query))]
+    report("%d queries x %d gallery rows, E = %d, products = %d, k = %d: %d repetitions after %d warm-up rounds, device events"
+           % (queries, rows, E, products, k, reps, warmup), timed(fns, warmup, reps))
+    fns = [("dsl_col_stats_planes", lambda: op.dsl_col_stats_planes(captions, clip_q, rows, queries, mult, products)),
+           ("dsl_col_stats_planes_masked, random p = 0.5", lambda: op.dsl_col_stats_planes_masked(captions, clip_q, rows, queries, mult,
+                                                                                                 products, half)),
+           ("dsl_col_stats_planes_masked, one contiguous 1/16", lambda: op.dsl_col_stats_planes_masked(captions, clip_q, rows, queries,
+                                                                                                      mult, products, sixteenth))]
+    report("statistics of %d video rows over %d text rows" % (queries, rows), timed(fns, warmup, reps))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=40, help="clips encoded into the gallery (0: skip the model part)")
@@ -251,10 +353,19 @@ def main():
     ap.add_argument("--camoe_dsl", type=int, default=0, help="1: the dual softmax (FeatureGallery(dual_softmax=True))")
     ap.add_argument("--time-bank", type=int, default=1000, help="--camoe_dsl 1: captions in the bank of the timed clip gallery")
     ap.add_argument("--groups", type=int, default=0, help="G > 0: grouped search (FeatureGallery(grouped=True)), groups of 1..G rows")
+    ap.add_argument("--remove", type=float, default=0.0, help="FRACTION > 0: remove that share of the clips, search, compact()")
+    ap.add_argument("--subset", type=float, default=0.0, help="FRACTION > 0: search within that share of the clips (allow=)")
+    ap.add_argument("--baseline-lib", default="", help="--remove / --subset: another build of the library to time the unmasked op of")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), bench.task_config(c)).to(device).eval()
+    if a.remove or a.subset:
+        if a.clips:
+            masked_part(model, device, a)
+        if a.time_rows:
+            time_masked(model, device, a.time_rows, a.time_queries, a.time_k, a.reps, a.warmup, a.baseline_lib)
+        return
     if a.camoe_dsl:
         if a.clips:
             dsl_part(model, device, a)

@@ -840,6 +840,44 @@ int cc_similarity_topk_grouped_dsl_planes_f32(const void* query_planes, const vo
                                               int32_t E, float mult, int32_t products, int32_t k, const float* m, const float* s,
                                               int32_t stats_on_gallery, int32_t n_total, const int32_t* group_head, float* scores,
                                               int32_t* ids, void* ws, size_t ws_bytes, void* stream);
+/* Masked search: a bit per gallery row says whether the row may be ranked (rows taken out of a gallery, a tenant's subset,
+ * "everything but the query's own clip").  One mask format for all three entries: int32 words, bit b of word w stands for
+ * row 32 w + b, 1 = selectable; a mask row is mask_words >= ceil(Bg / 32) words, bits at or above Bg are ignored whatever
+ * they hold.
+ *
+ * cc_similarity_topk_masked_planes_f32: the four entries above in one, over the selectable rows only.  row_mask holds ONE
+ * mask row for all queries (mask_rows = 1) or one per query row (mask_rows = Bq, mask_words apart).  m == s == NULL ranks
+ * S, both non-NULL the dual softmax D as cc_similarity_topk_dsl_planes_f32 (stats_on_gallery, n_total as there; ignored
+ * without m, s); group_head == NULL ranks rows, otherwise groups as cc_similarity_topk_grouped_planes_f32.
+ *   Result: the unmasked entry's, of the matrix with the unselectable columns dropped - the same score bits, the same order
+ *   (stable descending, equal scores by smaller id), ids are still row indices of the whole gallery; (-inf, -1) beyond the
+ *   number of selectable rows.  Grouped: a group is ranked by its best SELECTABLE row; a group without one gives no entry.
+ *   Statistics and heads are indexed as in the unmasked entries; an all-ones mask gives their results bit for bit.
+ *   mask_rows = 1: a 16-row tile without a selectable row (an aligned halfword of the mask that is 0) is neither read nor
+ *   multiplied - a search over a clustered subset reads that subset's bytes.  Per-query masks skip nothing.
+ * Limits, workspace (cc_similarity_topk_workspace_bytes / _slices), the two launches and the order of the early returns are
+ * the plain entry's; CC_ERR_INVALID also for a NULL row_mask, mask_rows other than 1 or Bq, mask_words < ceil(Bg / 32), or
+ * exactly one of m / s (and, with both, n_total < 0 or stats_on_gallery other than 0 / 1) - before anything is read.
+ *
+ * cc_dsl_col_stats_planes_masked_f32: cc_dsl_col_stats_planes_f32 over the text rows whose bit is set in text_mask (one mask
+ * row, >= ceil(Bt / 32) words).  The tree is the unmasked one (slices from Bt alone, wave and lane order) with the
+ * unselectable rows' terms left out - neither their maximum nor their expf enters, tiles without a selectable row are not
+ * read: m is bit-equal to the column maximum over the selectable rows, an all-ones mask gives the unmasked entry's bits, no
+ * selectable row gives (-inf, 0).  Workspace, limits and returns are the unmasked entry's; a NULL text_mask with Bt > 0:
+ * CC_ERR_INVALID.
+ *
+ * cc_pack_row_mask_u8: flags [rows][n] bytes (non-zero = selectable) -> out_words [rows][words_per_row] mask words,
+ * words_per_row >= ceil(n / 32); bits at or above n are written as 0.  One launch.  NULL pointers, rows <= 0, n <= 0 or too
+ * few words: CC_ERR_INVALID. */
+int cc_similarity_topk_masked_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                         float mult, int32_t products, int32_t k, const int32_t* row_mask, int32_t mask_rows,
+                                         int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery,
+                                         int32_t n_total, const int32_t* group_head, float* scores, int32_t* ids, void* ws,
+                                         size_t ws_bytes, void* stream);
+int cc_dsl_col_stats_planes_masked_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv, int32_t E,
+                                       float mult, int32_t products, const int32_t* text_mask, float* m, float* s, void* ws,
+                                       size_t ws_bytes, void* stream);
+int cc_pack_row_mask_u8(const uint8_t* flags, int32_t rows, int32_t n, int32_t* out_words, int32_t words_per_row, void* stream);
 int cc_video_pool_normalize_f32(const float* visual, const int64_t* video_mask, int32_t Bv, int32_t Tn,
                                 int32_t E, float* pooled, void* stream);
 int cc_loose_similarity_f32(const float* text, const float* visual, const int64_t* video_mask,
