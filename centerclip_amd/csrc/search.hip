@@ -45,6 +45,13 @@
 // that may not gets key 0, the empty entry.  With ONE mask a 16-row tile without a selectable row is neither requested nor
 // multiplied: tk_stream_tiles takes its tiles from a rule (TkEvery / TkLive), and dsl_stats_stream_kernel<true> leaves masked
 // text rows out of the statistics the same way.  pack_row_mask_kernel turns byte flags into mask words.
+//
+// Rank of a known row or group (where does THIS row stand for THIS query), still without the matrix: three launches.
+// rank_target_kernel computes t_q, the score of every query row's target, with the MFMA sequence of the stream (so the bits are
+// those of every other score); rank_stream_kernel<DSL, GROUPED, MASK> is a new consumer of tk_stream_tiles on the same grid
+// that counts, per query row, the candidates above t_q, equal to it, and equal in front of the target - three integers a lane
+// instead of the lists, so LDS is the staged rows alone; rank_reduce_kernel adds the slices' partial counts.  Integers: any
+// split of the gallery sums to the same result.
 #include <type_traits>
 
 #include "cc_kernels.h"
@@ -546,6 +553,249 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const u64* __restrict__ 
     }
 }
 
+// ---------------------------------------------------------------------------- rank of a known row or group
+// First launch of the rank: t_q, the score of query row q's target, one wave per query row (4 a workgroup).  The wave
+// multiplies the 16-row tiles that cover the target - rows mode: the one tile of row target[q]; GROUPED: the tiles of
+// [head, end), head = group_head[target[q]] and end the next group start, found by walking group_head forward 64 rows a step -
+// with the query row in all 16 columns of the second operand: the k-slices in ascending order, the gallery fragment first, one
+// fp32 accumulator, then sc * acc (and cc_dsl_value) - the instruction sequence of tk_stream_tiles, so t_q has the bits the
+// counting pass computes for the same pair and its `==` finds the target itself.  Rows mode never looks at the target's own
+// mask bit; GROUPED takes the best key (tk_key: best score, smallest row) of the group's selectable rows, as the searches do,
+// and decodes it: -inf without one.  row_mask == nullptr: every row is selectable; mask_step: words between the mask rows of
+// two query rows (0: one mask for all).  A target outside [0, Bg): -inf.
+template <bool DSL, bool GROUPED>
+__global__ __launch_bounds__(256) void rank_target_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
+                                                          int Bq, int Bg, int ld, int K, float sc, const int* __restrict__ target,
+                                                          float* __restrict__ tscore, const float* __restrict__ stat_m,
+                                                          const float* __restrict__ stat_s, int on_gallery, float nt,
+                                                          const int* __restrict__ group_head, const int* __restrict__ row_mask,
+                                                          int mask_step) {
+    const int lane = threadIdx.x & 63, l15 = lane & 15, lg = lane >> 4;
+    const int q = blockIdx.x * TK_WAVES + (threadIdx.x >> 6);
+    if (q >= Bq) return;                                                               // (a whole wave; no barrier below)
+    const int tg = target[q];
+    if (tg < 0 || tg >= Bg) {
+        if (lane == 0) tscore[q] = -INFINITY;
+        return;
+    }
+    int h = tg, e = tg + 1;                                                            // the rows of the target: [h, e)
+    if constexpr (GROUPED) {
+        h = min(max(group_head[tg], 0), tg);                                           // (a malformed head stays inside the rows)
+        for (int base = tg + 1;; base += 64) {
+            const int r = base + lane;
+            const u64 heads = __ballot(r < Bg && group_head[min(r, Bg - 1)] == r);
+            if (heads) { e = base + __builtin_ctzll(heads); break; }
+            if (base + 64 >= Bg) { e = Bg; break; }
+        }
+    }
+    const int nk2 = K >> 6;
+    const _Float16* qp = query + (int64_t)q * ld + lg * 8;
+    const int* mrow = row_mask ? row_mask + (int64_t)q * mask_step : nullptr;
+    float qm = 0.f, qs = 1.f;
+    if constexpr (DSL) {
+        if (!on_gallery) { qm = stat_m[q]; qs = stat_s[q]; }
+    }
+    u64 best = 0;                                                                      // GROUPED: the group's best key so far
+    float xt = 0.f;                                                                    // rows mode: the target's score (one lane group)
+    for (int t = h >> 4; t <= (e - 1) >> 4; ++t) {
+        const _Float16* gp = gallery + (int64_t)min(t * 16 + l15, Bg - 1) * ld + lg * 8;     // rows at Bg or above are never read
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int s0 = 0; s0 < nk2; s0 += TK_BATCH) {                                   // TK_BATCH pairs of k-slices requested at once
+            h8 b[2 * TK_BATCH], a[2 * TK_BATCH];
+#pragma unroll
+            for (int u = 0; u < TK_BATCH; ++u) {
+                const int s = min(s0 + u, nk2 - 1);                                    // (beyond the row's end: read again, not multiplied)
+                b[2 * u] = *reinterpret_cast<const h8*>(gp + s * 64);
+                b[2 * u + 1] = *reinterpret_cast<const h8*>(gp + s * 64 + 32);
+                a[2 * u] = *reinterpret_cast<const h8*>(qp + s * 64);
+                a[2 * u + 1] = *reinterpret_cast<const h8*>(qp + s * 64 + 32);
+            }
+#pragma unroll
+            for (int u = 0; u < TK_BATCH; ++u) {
+                if (s0 + u < nk2) {
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[2 * u], a[2 * u], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(b[2 * u + 1], a[2 * u + 1], acc, 0, 0, 0);
+                }
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int id = t * 16 + lg * 4 + r, idc = min(id, Bg - 1);
+            float x = sc * acc[r];
+            if constexpr (DSL) x = on_gallery ? cc_dsl_value(nt, x, stat_m[idc], stat_s[idc]) : cc_dsl_value(nt, x, qm, qs);
+            if constexpr (GROUPED) {
+                bool sel = id >= h && id < e;
+                if (mrow) sel = sel && ((mrow[idc >> 5] >> (idc & 31)) & 1);
+                const u64 key = sel ? tk_key(x, id) : 0;
+                best = key > best ? key : best;
+            } else {
+                xt = id == tg ? x : xt;
+            }
+        }
+    }
+    if constexpr (GROUPED) {
+        best = tk_group_max(best);                                                     // (all 16 columns hold the same values)
+        int id;
+        tk_decode(best, xt, id);
+        if (lane == 0) tscore[q] = xt;
+    } else {
+        if (l15 == 0 && lg == ((tg & 15) >> 2)) tscore[q] = xt;
+    }
+}
+
+// Second launch: the counts, a new consumer of tk_stream_tiles on topk_stream_kernel's grid (gallery slices x groups of 16
+// query rows, 4 waves, the 16 query rows staged in LDS; the DSL / GROUPED / MASK modes, the wave's tiles or row range, the
+// statistics, heads and mask words per tile are that kernel's, spelled again here so that its instantiations stay the code they
+// were).  In place of the lists every lane keeps three integers for query row l15 against t = tscore[q]: candidates with
+// x > t, with x == t, and with x == t in front of the target (rows mode: a candidate is a selectable row < Bg, in front =
+// its index below target[q]; GROUPED: a candidate is what tk_group_tile hands out - the best key of a finished group, 0 for
+// one without a selectable row - plus the carry at the range's end, in front = its row below the target group's head).  Plain
+// float compares, as rank_counts_kernel: -0 == +0, a NaN is neither greater nor equal.  A query row whose target is outside
+// [0, Bg) counts nothing.  At the end the 4 lanes of a query row and the 4 waves are added: part [Bq][3][slices].
+template <bool DSL, bool GROUPED, int MASK>
+__global__ __launch_bounds__(256) void rank_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
+                                                          int Bq, int Bg, int ld, int K, float sc, int slices,
+                                                          const int* __restrict__ target, const float* __restrict__ tscore,
+                                                          int* __restrict__ part, const float* __restrict__ stat_m,
+                                                          const float* __restrict__ stat_s, int on_gallery, float nt,
+                                                          const int* __restrict__ group_head, const int* __restrict__ row_mask,
+                                                          int mask_words) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
+    __shared__ int pc[TK_WAVES][3][TK_QROWS];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
+    const int QS = K + TK_QPAD;
+    _Float16* qs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][QS]
+    tk_stage_rows(qs, query, q0, Bq, ld, K);
+    __syncthreads();
+
+    const int tiles = (Bg + 15) >> 4;
+    const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
+    const int qr = min(q0 + l15, Bq - 1);
+    const int tg = target[qr];
+    const bool qvalid = q0 + l15 < Bq && tg >= 0 && tg < Bg;
+    const float tq = tscore[qr];
+    int front = tg;                                                                    // a candidate row below it lies in front
+    if constexpr (GROUPED) front = min(max(group_head[min(max(tg, 0), Bg - 1)], 0), tg);
+    int gt = 0, eq = 0, before = 0;
+    float dm[4] = {0.f, 0.f, 0.f, 0.f}, ds[4] = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (DSL) {
+        if (!on_gallery) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { dm[r] = stat_m[qr]; ds[r] = stat_s[qr]; }
+        }
+    }
+    int first = t0 + wave, last = t1, r0 = 0, r1 = Bg;
+    u64 carry = 0;
+    int gh[4] = {0, 0, 0, 0};
+    if constexpr (GROUPED) {
+        auto bound = [&](int j) {
+            if (j <= 0) return 0;
+            if (j >= TK_WAVES * slices) return Bg;
+            const int b = min((int)((int64_t)tiles * j / (TK_WAVES * slices)) * 16, Bg - 1);
+            return min(max(group_head[b], 0), b);
+        };
+        r0 = bound(TK_WAVES * slice + wave);
+        r1 = bound(TK_WAVES * slice + wave + 1);
+        first = r0 >> 4;
+        last = r1 > r0 ? (r1 + 15) >> 4 : first;
+    }
+    TkMaskState<MASK> ms;
+    if constexpr (MASK != 0) {
+        ms.row = row_mask;
+        if constexpr (MASK == 2) ms.row += (int64_t)qr * mask_words;
+        ms.prev = first - 1;
+    }
+    auto before_last = [&](int t) {
+        if constexpr (MASK != 0) ms.word = ms.row[t >> 1];
+        if constexpr (GROUPED && MASK == 1) ms.gap_head = group_head[min(max(t * 16 - 1, 0), Bg - 1)];
+        if constexpr (DSL) {
+            if (on_gallery) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int id = min(t * 16 + lg * 4 + r, Bg - 1);
+                    dm[r] = stat_m[id];
+                    ds[r] = stat_s[id];
+                }
+            }
+        }
+        if constexpr (GROUPED) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gh[r] = group_head[min(t * 16 + lg * 4 + r, Bg - 1)];
+        }
+    };
+    auto count_key = [&](u64 key) {                                                    // GROUPED: one finished group
+        float x;
+        int id;
+        tk_decode(key, x, id);
+        const bool in = key != 0;
+        gt += (in && x > tq) ? 1 : 0;
+        eq += (in && x == tq) ? 1 : 0;
+        before += (in && x == tq && id < front) ? 1 : 0;
+    };
+    auto on_tile = [&](int t, const f32x4& acc) {
+        u64 key[4];
+        bool head[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int id = t * 16 + lg * 4 + r;
+            float x = sc * acc[r];
+            if constexpr (DSL) x = cc_dsl_value(nt, x, dm[r], ds[r]);
+            bool in = qvalid && (GROUPED ? (id >= r0 && id < r1) : id < Bg);
+            if constexpr (MASK != 0) in = in && ((ms.word >> ((t & 1) * 16 + lg * 4 + r)) & 1);
+            if constexpr (GROUPED) {
+                key[r] = in ? tk_key(x, id) : 0;
+                head[r] = gh[r] == id;
+            } else {
+                gt += (in && x > tq) ? 1 : 0;
+                eq += (in && x == tq) ? 1 : 0;
+                before += (in && x == tq && id < front) ? 1 : 0;
+            }
+        }
+        if constexpr (GROUPED) {
+            if constexpr (MASK == 1) {                                                 // dead tiles skipped: topk_stream_kernel's rule
+                if (lg == 0 && t > ms.prev + 1 && ms.gap_head >= (ms.prev + 1) * 16) head[0] = true;
+                ms.prev = t;
+            }
+            tk_group_tile(key, head, lg, carry);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) count_key(key[r]);
+        }
+    };
+    constexpr int stride = GROUPED ? 1 : TK_WAVES;
+    if constexpr (MASK == 1) {
+        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, TkLive(row_mask, first, stride, last, lane), l15, lg, before_last,
+                        on_tile);
+    } else {
+        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, TkEvery{first, stride, last}, l15, lg, before_last, on_tile);
+    }
+    if constexpr (GROUPED) count_key(lg == 0 ? carry : 0);                             // the group open at the range's end
+    int c[3] = {gt, eq, before};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        c[i] += __shfl_xor(c[i], 16, CC_WAVE);
+        c[i] += __shfl_xor(c[i], 32, CC_WAVE);
+        if (lg == 0) pc[wave][i][l15] = c[i];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 * TK_QROWS) {
+        const int i = threadIdx.x >> 4, l = threadIdx.x & 15;
+        if (q0 + l < Bq) part[((int64_t)(q0 + l) * 3 + i) * slices + slice] = pc[0][i][l] + pc[1][i][l] + pc[2][i][l] + pc[3][i][l];
+    }
+}
+
+// Third launch: part [n][slices] -> counts [n] (n = 3 Bq), one wave per count: the lanes take the slices 64 apart, then the
+// wave adds up.  Integers: the order does not matter.
+__global__ __launch_bounds__(256) void rank_reduce_kernel(const int* __restrict__ part, int slices, int n, int* __restrict__ counts) {
+    const int lane = threadIdx.x & 63, i = blockIdx.x * TK_WAVES + (threadIdx.x >> 6);
+    if (i >= n) return;
+    int a = 0;
+    for (int s = lane; s < slices; s += 64) a += part[(int64_t)i * slices + s];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, CC_WAVE);
+    if (lane == 0) counts[i] = a;
+}
+
 // The (m, s) pairs of the 16 video rows from blockIdx.y * 16 on over the text tiles of slice blockIdx.x (the tree: the file's
 // head).  part [slices][Bv] pairs.  The split of the text rows uses Bt alone.  MASKED: text_mask is one mask row over the text
 // rows (topk_stream_kernel's format); a row whose bit is 0 is treated as a row at Bt or above - neither its maximum nor its
@@ -635,6 +885,11 @@ auto tk_stream_kernel_of(bool dsl, bool grouped) {
     return grouped ? (dsl ? topk_stream_kernel<true, true, MASK> : topk_stream_kernel<false, true, MASK>)
                    : (dsl ? topk_stream_kernel<true, false, MASK> : topk_stream_kernel<false, false, MASK>);
 }
+template <int MASK>
+auto rank_stream_kernel_of(bool dsl, bool grouped) {
+    return grouped ? (dsl ? rank_stream_kernel<true, true, MASK> : rank_stream_kernel<false, true, MASK>)
+                   : (dsl ? rank_stream_kernel<true, false, MASK> : rank_stream_kernel<false, false, MASK>);
+}
 
 }  // namespace
 
@@ -720,6 +975,47 @@ int cc_similarity_topk_masked_planes_f32(const void* query_planes, const void* g
     return tk_launch(dsl, group_head != nullptr, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s,
                      dsl ? stats_on_gallery : 0, dsl ? n_total : 0, group_head, scores, ids, ws, ws_bytes, stream, true, row_mask,
                      mask_rows, mask_words);
+}
+
+size_t cc_similarity_rank_workspace_bytes(int32_t Bq, int32_t Bg) {
+    if (Bq <= 0 || Bg <= 0) return 0;
+    return cc_align_up((size_t)tk_slices(Bq, Bg) * Bq * 3 * sizeof(int32_t), 256);
+}
+
+int cc_similarity_rank_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E, float mult,
+                                  int32_t products, const int32_t* target, const int32_t* row_mask, int32_t mask_rows,
+                                  int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery, int32_t n_total,
+                                  const int32_t* group_head, int32_t* counts, float* score, void* ws, size_t ws_bytes, void* stream) {
+    const bool dsl = m || s, grouped = group_head != nullptr, masked = row_mask != nullptr;
+    if (!query_planes || !gallery_planes || !target || !counts || !score || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
+    if (dsl && (!m || !s || n_total < 0 || (stats_on_gallery != 0 && stats_on_gallery != 1))) return CC_ERR_INVALID;
+    if (masked && ((mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
+    if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
+    const int K = products * E;
+    const size_t smem = tk_stream_lds(K, 0);                                // the staged rows: no lists, no (E, products) exclusion
+    if ((Bq + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million query rows a call)
+    if (!ws || ws_bytes < cc_similarity_rank_workspace_bytes(Bq, Bg)) return CC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int slices = tk_slices(Bq, Bg), on_gallery = dsl ? stats_on_gallery : 0;
+    const float sc = mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, nt = dsl ? (float)n_total : 0.f;
+    const _Float16* q = static_cast<const _Float16*>(query_planes);
+    const _Float16* g = static_cast<const _Float16*>(gallery_planes);
+    const auto target_kernel = grouped ? (dsl ? rank_target_kernel<true, true> : rank_target_kernel<false, true>)
+                                       : (dsl ? rank_target_kernel<true, false> : rank_target_kernel<false, false>);
+    hipLaunchKernelGGL(target_kernel, dim3((Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, q, g, Bq, Bg, 3 * E, K, sc, target, score,
+                       m, s, on_gallery, nt, group_head, row_mask, mask_rows == 1 ? 0 : mask_words);
+    CC_LAUNCH_CHECK();
+    const auto kernel = !masked ? rank_stream_kernel_of<0>(dsl, grouped)
+                                : mask_rows == 1 ? rank_stream_kernel_of<1>(dsl, grouped) : rank_stream_kernel_of<2>(dsl, grouped);
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
+    hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st, q, g, Bq, Bg, 3 * E, K, sc, slices,
+                       target, static_cast<const float*>(score), static_cast<int*>(ws), m, s, on_gallery, nt, group_head, row_mask,
+                       mask_words);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_reduce_kernel, dim3((3 * Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, static_cast<const int*>(ws), slices, 3 * Bq,
+                       counts);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
 }
 
 int cc_pack_row_mask_u8(const uint8_t* flags, int32_t rows, int32_t n, int32_t* out_words, int32_t words_per_row, void* stream) {

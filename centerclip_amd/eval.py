@@ -253,7 +253,7 @@ class _GraphedLane:
 
 
 def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False, backend=HipBackend, in_flight=None,
-               similarity_products=None, graphed=False, camoe_dsl=None, frame_transform=None):
+               similarity_products=None, graphed=False, camoe_dsl=None, frame_transform=None, matrix_free=False):
     """main.py:381-499 -> (R1, all_infer_time, info_str).  ``shard=True``: clip-sharded over the ranks of the default
     process group (module docstring) - every rank must call it and every rank returns the same numbers.
     ``in_flight`` (not in the reference; > 1 GPU only; default: 2 on a GPU, 1 on the CPU stand-in): n keeps n batches in flight -
@@ -274,8 +274,15 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
     ``frame_transform`` (not in the reference, whose loader does this per frame on the CPU; GPU only): a
     ``preprocess.FrameTransform`` - the loader hands over decoded uint8 frames of any size and the resize + centre crop runs on
     ``video`` right after it reaches the device, on the batch's lane; with ``graphed`` in front of the copy into the lane's
-    device-resident inputs (the graphs see model-resolution frames only).  None: the loop as it always was."""
+    device-resident inputs (the graphs see model-resolution frames only).  None: the loop as it always was.
+    ``matrix_free`` (not in the reference; GPU only, single process): the metrics come from ``matrix_free_metrics`` - the rank of
+    every ground-truth row counted on a stream over the cached operand rows, no [Nt, Nv] matrix.  Off by default: at evaluation
+    sizes the matrix is small and its path faster.  With ``shard=True`` in a process group of more than one rank: ValueError
+    (ranks across the ranks of a process group are out of scope)."""
     log = log or (lambda s: None)
+    if matrix_free and shard and ccdist.world_size() > 1:
+        raise ValueError("eval_epoch(matrix_free=True) ranks on one process: with shard=True over %d ranks it is out of scope "
+                         "(evaluate on one rank, or leave matrix_free off)" % ccdist.world_size())
     if in_flight is None:
         in_flight = 2 if (torch.cuda.is_available() and torch.device(device).type == "cuda") else 1
     be = backend.with_products(similarity_products) if similarity_products is not None else backend
@@ -377,7 +384,15 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
         n_video = len(last_sentence) if multi else n_text
         # (flag off: the call as it always was - tests replace _sharded_metrics with recorders of that signature)
         dsl_kw = {"dsl": True} if _camoe_dsl(model, args, camoe_dsl) else {}
-        tv_metrics, vt_metrics, shape = _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world, be, **dsl_kw)
+        if matrix_free:
+            text_order = torch.argsort(torch.cat(cache.text_pos)).to(device)             # the rows by their cached positions
+            video_order = torch.argsort(torch.cat(cache.video_pos)).to(device)
+            tv_metrics, vt_metrics = matrix_free_metrics(core, torch.cat(cache.text, 0)[text_order],
+                                                         torch.cat(cache.video, 0)[video_order], last_sentence, bool(dsl_kw), be)
+            shape = (n_text, n_video)
+        else:
+            tv_metrics, vt_metrics, shape = _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world, be,
+                                                             **dsl_kw)
     if multi:
         log("sim matrix size: {} sentences x {} videos ({} groups)".format(shape[0], shape[1], n_video))
     else:
@@ -479,4 +494,42 @@ def _sharded_metrics(core, cache, n_text, n_video, last_sentence, device, world,
     return tv, vt, (n_text, n_video)
 
 
-__all__ = ["eval_epoch", "_run_on_single_gpu", "HipBackend", "np"]
+def matrix_free_metrics(core, text_rows, video_rows, last_sentence=None, dsl=False, backend=HipBackend):
+    """The two metric dicts ``_sharded_metrics`` returns at world == 1, from the operand rows alone (dataset order: text_rows
+    [Nt, 3E], video_rows [Nv, 3E], no padding rows): every ranking is ``torch.ops.centerclip.similarity_rank`` - the rank of the
+    ground-truth row, counted against its own score on a stream over the other side's rows - so neither the [Nt, Nv] matrix nor
+    a second pass over it exists.  -> (tv_metrics, vt_metrics).
+      * one sentence per video: text queries against the video rows with target i; video queries against the text rows with
+        target v.
+      * ``last_sentence`` (the multi-sentence sets): text -> video with target = the sentence's video and the stable position
+        among ties (counts[:, 2]); video -> text against the text rows grouped by video, the target the group's first row.
+      * ``dsl``: D = S * softmax(S, dim=0) * Nt with the columns' (m, s) from ``dsl_col_stats_planes`` - per gallery row text ->
+        video, per query row video -> text.  m has the matrix path's bits; s is summed in that op's own fixed order, so a D
+        may differ from ``dsl_apply_`` on the matrix in its last bits (a rank only where two D are that close).
+    The 16-query stream reads the gallery once per 16 queries: at evaluation sizes the matrix path is faster (DESIGN §7 "Rank
+    without the matrix"), which is why ``eval_epoch(matrix_free=...)`` is off by default."""
+    op = torch.ops.centerclip
+    n_text, n_video = int(text_rows.shape[0]), int(video_rows.shape[0])
+    device = text_rows.device
+    text_rows, video_rows = text_rows.contiguous(), video_rows.contiguous()
+    mult, products = T.logit_multiplier(core._logit_scale_value()), int(backend.similarity_products)
+    m = s = None
+    if dsl:
+        m, s = op.dsl_col_stats_planes(text_rows, video_rows, n_text, n_video, mult, products)
+    sentences = torch.arange(n_text, device=device)
+    videos = torch.arange(n_video, device=device)
+    if last_sentence is None:
+        c_tv, _ = op.similarity_rank(text_rows, video_rows, n_video, mult, products, sentences, None, m, s, 1, n_text)
+        c_vt, _ = op.similarity_rank(video_rows, text_rows, n_text, mult, products, videos, None, m, s, 0, n_text)
+        return metrics_from_counts(c_tv[:, :2]), metrics_from_counts(c_vt[:, :2])
+    bounds = torch.as_tensor(last_sentence, device=device)
+    gt_cols = torch.searchsorted(bounds, sentences)              # sentence at position p describes video #{cut points < p}
+    c_tv, truth = op.similarity_rank(text_rows, video_rows, n_video, mult, products, gt_cols, None, m, s, 1, n_text)
+    tv = multi_sentence_metrics_from_counts(c_tv.cpu().numpy(), np.isfinite(truth.cpu().numpy()))
+    starts = torch.cat([bounds.new_zeros(1), bounds[:-1] + 1])   # the first sentence of every video
+    head = starts[gt_cols.clamp(max=n_video - 1)].to(torch.int32).contiguous()
+    c_vt, _ = op.similarity_rank(video_rows, text_rows, n_text, mult, products, starts, None, m, s, 0, n_text, head)
+    return tv, metrics_from_counts(c_vt[:, :2])
+
+
+__all__ = ["eval_epoch", "_run_on_single_gpu", "HipBackend", "matrix_free_metrics", "np"]

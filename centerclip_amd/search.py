@@ -34,6 +34,12 @@ Rows leave and searches narrow with one bit per row (``similarity_topk_masked``)
     tenant = gallery.row_mask(positions=mine)             # built once on the host ...
     scores, ids = gallery.search(input_ids, k=10, allow=tenant)             # ... passed to any number of searches
     new_pos = gallery.compact()                           # drop the holes: the gallery of the surviving rows
+
+"Where does THIS row stand for THIS query" - the rank R@k, MdR and MnR are made of - comes from the same stream
+(``similarity_rank``): counts against the target's own score instead of a list, so any place, not only the first 128:
+
+    ranks, scores, counts = gallery.rank(input_ids, target=truth)           # 0-based places in search's full ordering
+    ranks, scores, counts = gallery.rank_groups(video, video_mask, target=labels)      # grouped=True: the place of a group
 """
 import numpy as np
 import torch
@@ -83,7 +89,13 @@ class FeatureGallery:
     results are those of a gallery holding only these rows, at their positions here.  dual_softmax=True: side="video" - a
     clip's statistics never depended on other clips; side="text" - the statistics run over the captions still held
     (n_total = len(self)), and ``allow`` restricts the ranking, not the softmax.  A gallery that never removes a row and
-    never gets ``allow=`` allocates and launches what it did without any of this."""
+    never gets ``allow=`` allocates and launches what it did without any of this.
+
+    The rank of a known row or group (``similarity_rank``: three launches, no matrix, no list, exact): ``rank*(..., target=)``
+    -> (ranks, scores, counts) of one target position per query among the rows ``search*`` ranks - removals, ``allow=`` and
+    the dual softmax's statistics act as there; ``rank_groups*`` the same for one target label per query among the groups
+    ``search_groups*`` ranks.  ``counts`` are the (greater, equal, equal in front) triples of ``rank_counts_cols`` on the
+    matrix row, ``ranks = counts[:, 0] + counts[:, 2]``; a target that is not selectable keeps its score and is not counted."""
 
     def __init__(self, model, side="video", capacity=0, products=None, dual_softmax=False, grouped=False):
         if side not in SIDES:
@@ -587,6 +599,99 @@ class FeatureGallery:
     def search_features(self, features, k=10, mask=None, allow=None):
         """``search`` for query features computed elsewhere (sequence_output; side="text": visual_output and its mask)."""
         return self._search_rows(self._query_rows(features, mask), k, allow=allow)
+
+    # ------------------------------------------------------------------ the rank of a known row or group
+    def _targets(self, target, nq, what):
+        """one position per query -> int tensor [nq] on the device.  A host int sequence / CPU LongTensor is checked against
+        [0, span) before anything is launched (the same position may serve several queries); a device integer tensor is
+        passed through unread"""
+        if torch.is_tensor(target) and target.device.type != "cpu":
+            if target.dtype not in (torch.int32, torch.int64) or target.dim() != 1 or target.shape[0] != nq:
+                raise ValueError("FeatureGallery.%s: target %s %s is not one int32 / int64 position per query (%d)"
+                                 % (what, tuple(target.shape), target.dtype, nq))
+            return target
+        if torch.is_tensor(target):
+            pos = target.numpy().reshape(-1) if target.dtype == torch.int64 and target.dim() <= 1 else None
+        elif isinstance(target, (int, np.integer)):
+            pos = np.array([int(target)])
+        else:
+            pos = np.asarray(list(target))
+            pos = pos if pos.ndim == 1 and (pos.size == 0 or pos.dtype.kind in "iu") else None
+        if pos is None:
+            raise ValueError("FeatureGallery.%s: target is a flat host sequence of ints, a CPU LongTensor or a device integer "
+                             "tensor" % what)
+        if pos.size != nq:
+            raise ValueError("FeatureGallery.%s: %d targets for %d queries (one position per query)" % (what, pos.size, nq))
+        pos = pos.astype(np.int64)
+        if pos.size and (pos.min() < 0 or pos.max() >= self._n):
+            raise ValueError("FeatureGallery.%s: target %d is outside [0, %d)"
+                             % (what, int(pos[(pos < 0) | (pos >= self._n)][0]), self._n))
+        return self._host_to_device(pos)
+
+    def _group_targets(self, target, nq):
+        """one group label per query (host values) -> the positions of the groups' heads, through the host label mirror"""
+        want = self._label_list(target, "rank_groups")
+        if want.size != nq:
+            raise ValueError("FeatureGallery.rank_groups: %d target labels for %d queries (one label per query)" % (want.size, nq))
+        held = self.labels.numpy()                               # (removed rows keep their label until compact())
+        first = np.flatnonzero(np.concatenate(([True], held[1:] != held[:-1]))) if held.size else np.zeros(0, dtype=np.int64)
+        head_of = dict(zip(held[first].tolist(), first.tolist()))                      # (a label never returns: one label, one run)
+        missing = [v for v in want.tolist() if v not in head_of]
+        if missing:
+            raise ValueError("FeatureGallery.rank_groups: no row held has the label %d" % missing[0])
+        return np.array([head_of[v] for v in want.tolist()], dtype=np.int64)
+
+    def _rank_rows(self, q, target, groups=False, allow=None):
+        """(ranks int64 [Nq], scores fp32 [Nq], counts int32 [Nq, 3]) of the targets among the rows (groups) ``_search_rows``
+        ranks, with its choices of statistics"""
+        if self._dsl:
+            self._need_bank()
+        mask = self._allow_words(allow, q.shape[0])
+        m = s = None
+        on_gallery, n_total = self.side == "video", 0
+        if self._dsl:
+            m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
+            n_total = self._bank.shape[0] if on_gallery else len(self)
+        counts, scores = torch.ops.centerclip.similarity_rank(q, self._rows, self._n, self._mult(), self.products, target, mask, m, s,
+                                                              int(on_gallery), n_total, self._head if groups else None)
+        return counts[:, 0].to(torch.int64) + counts[:, 2], scores, counts
+
+    def rank(self, *inputs, target, allow=None):
+        """Where a known row stands: the queries of ``search`` and one ``target`` position per query -> (ranks int64 [Nq],
+        scores fp32 [Nq], counts int32 [Nq, 3]), all on the device.  ``ranks[q]`` is the 0-based place of row ``target[q]`` in
+        ``search``'s full ordering for query q (so ``search(k)[1][q, ranks[q]] == target[q]`` whenever ranks[q] < k), for any
+        place, not only the first 128; ``scores[q]`` the pair's score, ``search``'s bits; ``counts[q]`` = (rows with a greater
+        score, with an equal score - the target included -, with an equal score and a smaller position): what R@k, MdR and
+        MnR are made of.  ``target``: a host int sequence or a CPU LongTensor, checked against [0, span) before anything is
+        launched (one position may serve several queries), or a device integer tensor, passed through without a look (a
+        position outside [0, span) then gives counts (0, 0, 0) and score -inf).  Removed rows and ``allow=`` act as in
+        ``search``; a target that is itself removed or not allowed keeps its score and is simply not counted: ranks[q] is then
+        the place it would take among the selectable rows."""
+        target = self._targets(target, inputs[0].shape[0], "rank")           # (refusals come before anything is encoded)
+        return self._rank_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), target,
+                               allow=allow)
+
+    def rank_features(self, features, target, mask=None, allow=None):
+        """``rank`` for query features computed elsewhere (as ``search_features``)."""
+        target = self._targets(target, features.shape[0], "rank_features")
+        return self._rank_rows(self._query_rows(features, mask), target, allow=allow)
+
+    def rank_groups(self, *inputs, target, allow=None):
+        """grouped=True: where a known GROUP stands among the groups ``search_groups`` ranks.  ``target``: one group label per
+        query (an int, a host sequence or a CPU LongTensor - never a device tensor); a label no held row carries: ValueError.
+        -> (ranks, scores, counts) as ``rank``, counted over the groups with a selectable row: scores[q] is the group's best
+        selectable row (-inf without one), counts[q] = (groups with a greater score, with an equal score, with an equal score
+        lying in front of the target's)."""
+        self._need_grouped("rank_groups")
+        target = self._host_to_device(self._group_targets(target, inputs[0].shape[0]))
+        return self._rank_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), target,
+                               groups=True, allow=allow)
+
+    def rank_groups_features(self, features, target, mask=None, allow=None):
+        """``rank_groups`` for query features computed elsewhere."""
+        self._need_grouped("rank_groups_features")
+        target = self._host_to_device(self._group_targets(target, features.shape[0]))
+        return self._rank_rows(self._query_rows(features, mask), target, groups=True, allow=allow)
 
     def _matrix(self, q):
         n = self._n

@@ -1357,8 +1357,9 @@ def _check_row_mask(name, mask, rows, n, planes, what="row_mask"):
         raise ValueError("%s: %s on %s, the planes on %s" % (name, what, mask.device, planes.device))
 
 
-def _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head):
-    name = "similarity_topk_masked"
+def _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head,
+                       name="similarity_topk_masked"):
+    """(similarity_rank runs it under its own name; there the mask is optional)"""
     if group_head is not None:
         E3 = _check_group_head(name, query_planes, gallery_planes, n_gallery, group_head)
     else:
@@ -1369,7 +1370,8 @@ def _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, 
         raise ValueError("%s: m and s come together (both for the dual softmax, neither for S)" % name)
     if m is not None:
         _check_dsl_stats(name, m, s, int(n_gallery) if stats_on_gallery else query_planes.shape[0])
-    _check_row_mask(name, row_mask, query_planes.shape[0], n_gallery, gallery_planes)
+    if row_mask is not None:
+        _check_row_mask(name, row_mask, query_planes.shape[0], n_gallery, gallery_planes)
     return E3
 
 
@@ -1408,6 +1410,62 @@ def _(query_planes, gallery_planes, n_gallery, mult, products, k, row_mask, m=No
     _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
     return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
             query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+
+
+def _check_rank(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head):
+    """similarity_topk_masked's checks (the mask only when there is one) and the targets: one int32 / int64 per query row"""
+    name = "similarity_rank"
+    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head, name)
+    if (target.dtype not in (torch.int32, torch.int64) or target.dim() != 1 or target.shape[0] != query_planes.shape[0]
+            or target.device != query_planes.device):
+        raise ValueError("%s: target %s %s on %s is not one int32 / int64 position per query row (%d) on %s"
+                         % (name, tuple(target.shape), target.dtype, target.device, query_planes.shape[0], query_planes.device))
+    return E3
+
+
+@custom_op(NS + "::similarity_rank", mutates_args=(), device_types="cuda")
+def similarity_rank(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                    target: torch.Tensor, row_mask: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None,
+                    s: Optional[torch.Tensor] = None, stats_on_gallery: int = 1, n_total: int = 0,
+                    group_head: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Where gallery row target[q] stands for query row q, without the matrix and without a list -> (counts [Bq, 3] int32,
+    score [Bq] fp32): score = the target's score (the bits similarity_topk* give the pair; always computed, whatever the
+    target's own mask bit says), counts = (#greater, #equal, #equal with a smaller id) over the rows row_mask leaves selectable
+    (None: all) - what rank_counts_cols gives for the matrix row with gt_cols = target; the 0-based rank in similarity_topk's
+    order is counts[:, 0] + counts[:, 2].  m, s, stats_on_gallery, n_total, group_head as in similarity_topk_masked; with
+    group_head the target is any row of the target group, score the group's best selectable row (-inf without one) and the
+    counts run over the groups with a selectable row.  A target outside [0, n_gallery): (0, 0, 0), -inf.
+    cc_similarity_rank_planes_f32."""
+    Bq = query_planes.shape[0]
+    E3 = _check_rank(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head)
+    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
+    if m is not None:
+        m, s = m.contiguous(), s.contiguous()
+    target = target.to(torch.int32).contiguous()
+    counts = _e(Bq, 3, like=query_planes, dtype=torch.int32)
+    score = _e(Bq, like=query_planes, dtype=torch.float32)
+    if Bq == 0:
+        return counts, score
+    if int(n_gallery) == 0:                                 # no row: every target is outside
+        return counts.zero_(), score.fill_(float("-inf"))
+    lib = L.lib()
+    ws = L.workspace(lib.cc_similarity_rank_workspace_bytes(Bq, int(n_gallery)), query_planes.device)
+    masked = row_mask is not None
+    L.check(lib.cc_similarity_rank_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3, float(mult),
+                                              int(products), L.ptr(target), L.ptr(row_mask),
+                                              (1 if row_mask.dim() == 1 else Bq) if masked else 0,
+                                              int(row_mask.shape[-1]) if masked else 0, L.ptr(m), L.ptr(s), int(stats_on_gallery),
+                                              int(n_total), L.ptr(group_head), L.ptr(counts), L.ptr(score), L.ptr(ws), ws.numel(),
+                                              _st(query_planes)), "cc_similarity_rank_planes_f32")
+    return counts, score
+
+
+@similarity_rank.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, target, row_mask=None, m=None, s=None, stats_on_gallery=1, n_total=0,
+      group_head=None):
+    _check_rank(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head)
+    return (query_planes.new_empty((query_planes.shape[0], 3), dtype=torch.int32),
+            query_planes.new_empty((query_planes.shape[0],), dtype=torch.float32))
 
 
 def _check_masked_stats(text_planes, video_planes, n_text, n_video, text_mask):
@@ -1724,7 +1782,7 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
        "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
        "similarity_topk_grouped", "similarity_topk_grouped_dsl", "similarity_topk_masked", "dsl_col_stats_planes_masked",
-       "pack_row_mask")
+       "pack_row_mask", "similarity_rank")
 
 
 def logit_multiplier(logit_scale):

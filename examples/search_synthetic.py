@@ -29,6 +29,13 @@ is similarity_topk_masked with an all-ones mask, one contiguous 1/16 of the rows
 the masked statistics pass against the unmasked ops - and, with --baseline-lib PATH, against another build's unmasked op.
 
     python examples/search_synthetic.py --remove 0.25 --subset 0.3 [--baseline-lib other/libcenterclip_hip.so]
+
+--rank 1 asks where a known clip stands (FeatureGallery.rank: R@k, MdR, MnR without the matrix): every caption's own clip
+against the matrix + rank_counts_cols, the cross-check with search (its entry at the rank is the target, same score bits), and
+the timing of similarity_rank next to similarity_topk at --time-k and to the matrix op + rank_counts_cols, of its masked,
+grouped and dual-softmax forms next to their top-k counterparts, and of the evaluation-size shape against the matrix path.
+
+    python examples/search_synthetic.py --rank 1
 """
 import argparse
 import os
@@ -340,6 +347,120 @@ def time_masked(model, device, rows, queries, k, reps, warmup, baseline_lib):
     report("statistics of %d video rows over %d text rows" % (queries, rows), timed(fns, warmup, reps))
 
 
+def rank_part(model, device, a):
+    """where every caption's own clip stands: rank against the matrix + rank_counts_cols, and against search's own order"""
+    data = SyntheticRetrieval(a.clips)
+    gallery = FeatureGallery(model)
+    gallery.add(data.video.to(device), data.vmask.to(device))
+    ids = data.ids.to(device)
+    truth = torch.arange(a.clips)                                            # caption i describes clip i
+    ranks, scores, counts = gallery.rank(ids, target=truth)
+    for i in range(min(a.captions, a.clips)):
+        print("caption %d: its clip stands at place %d (score %.4f; %d clips above, %d equal)"
+              % (i, int(ranks[i]), float(scores[i]), int(counts[i, 0]), int(counts[i, 1])))
+    sim = gallery.similarity(ids)
+    want = torch.ops.centerclip.rank_counts_cols(sim, truth.to(device, torch.int32))
+    print("same counts as rank_counts_cols on the matrix: %s; same score bits: %s"
+          % (bool(torch.equal(counts, want)), bool(torch.equal(scores, sim.diagonal().contiguous()))))
+    r = ranks.cpu().numpy()
+    print("R@1 %.1f  R@5 %.1f  R@10 %.1f  MdR %.1f  MnR %.1f  (no matrix)"
+          % tuple([100.0 * float((r < k).mean()) for k in (1, 5, 10)] + [float(statistics.median(r + 1)), float(r.mean() + 1)]))
+    # against the search: for every caption whose rank is below k, search's entry at that rank is the target, same score bits.
+    # Half the targets are taken from search's own result at seeded places, so at least half the captions are checked.
+    k = min(a.k, a.clips)
+    found_scores, found = gallery.search(ids, k=k)
+    g = torch.Generator().manual_seed(4)
+    at = torch.randint(0, k, (a.clips,), generator=g)
+    target = torch.randint(0, a.clips, (a.clips,), generator=g)
+    target[::2] = found.cpu()[torch.arange(a.clips), at][::2]
+    ranks, scores, _ = gallery.rank(ids, target=target)
+    inside = (ranks.cpu() < k).nonzero().flatten()
+    place = ranks.cpu()[inside]
+    assert inside.numel() >= a.clips // 2, "the cross-check with the search ran (nearly) empty"
+    same = torch.equal(found.cpu()[inside, place], target[inside]) and torch.equal(found_scores.cpu()[inside, place], scores.cpu()[inside])
+    print("search(k=%d) holds the target at its rank with the same score for all %d of %d captions ranked below k: %s"
+          % (k, inside.numel(), a.clips, same))
+
+
+def time_rank(model, device, rows, queries, k, largest, bank, reps, warmup):
+    """similarity_rank next to the top-k op at k (untouched: the yardstick) and to the matrix op + rank_counts_cols on a ready
+    padded copy; rank_features next to similarity_features + counts; the masked, grouped and dual-softmax forms next to their
+    top-k counterparts; then the evaluation-size shape (10,000 captions x 1,000 clips, both directions) against the matrix"""
+    op = torch.ops.centerclip
+    E = int(model.clip_config['embed_dim'])
+    g = torch.Generator(device=device).manual_seed(1)
+    gallery = FeatureGallery(model, capacity=rows)
+    for b in uneven(rows, (rows // 2, rows // 3, rows)):
+        gallery.add_features(torch.randn(b, E, device=device, generator=g))
+    seq = torch.randn(queries, 1, E, device=device, generator=g)
+    products, mult = gallery.products, T.logit_multiplier(model._logit_scale_value())
+    q, clips = gallery.backend.text_operand(seq.reshape(queries, -1)), gallery.rows
+    padded = torch.zeros(T.padded_video_rows(rows), 3 * E, device=device, dtype=torch.float16)
+    padded[:rows] = clips
+    target = torch.randint(0, rows, (queries,), device=device, generator=g)
+    target32 = target.to(torch.int32)
+
+    def matrix_op():
+        return op.rank_counts_cols(op.scaled_dot_planes(q, padded, rows, mult, products), target32)
+
+    def matrix_api():
+        return op.rank_counts_cols(gallery.similarity_features(seq), target32)
+
+    fns = [("similarity_rank op", lambda: op.similarity_rank(q, clips, rows, mult, products, target32)),
+           ("similarity_topk op, k = %d (the yardstick)" % k, lambda: op.similarity_topk(q, clips, rows, mult, products, k)),
+           ("scaled_dot_planes op on a padded copy + rank_counts_cols", matrix_op),
+           ("rank_features", lambda: gallery.rank_features(seq, target)),
+           ("similarity_features + rank_counts_cols (pads a copy per call)", matrix_api)]
+    assert torch.equal(fns[0][1]()[0], matrix_op()), "the two paths disagree on the counts"
+    title = "%d queries x %d gallery rows, E = %d, products = %d: %d repetitions after %d warm-up rounds, device events"
+    report(title % (queries, rows, E, products, reps, warmup), timed(fns, warmup, reps))
+    print("  rank workspace %d bytes; the matrix has %d bytes" % (L.lib().cc_similarity_rank_workspace_bytes(queries, rows),
+                                                                   queries * rows * 4))
+    # the forms: one mask (random half), one per query, groups of 1..largest rows, the dual softmax per gallery / query row
+    flags = lambda *shape: torch.rand(*shape, device=device, generator=g) < 0.5
+    half, per_query = op.pack_row_mask(flags(rows))[0], op.pack_row_mask(flags(queries, rows))
+    labels = group_labels(rows, largest)
+    first = torch.cat([torch.ones(1, dtype=torch.bool), labels[1:] != labels[:-1]])
+    head = torch.cummax(torch.where(first, torch.arange(rows), torch.zeros(rows, dtype=torch.long)), 0).values.to(device, torch.int32)
+    unit = lambda n, video_side: op.normalize_rows_planes(torch.randn(n, E, device=device, generator=g), video_side)
+    bank_rows, captions, clip_q = unit(bank, False), unit(rows, False), unit(queries, True)
+    m_g, s_g = op.dsl_col_stats_planes(bank_rows, clips, bank, rows, mult, products)
+    m_q, s_q = op.dsl_col_stats_planes(captions, clip_q, rows, queries, mult, products)
+    pair = lambda name, rank, topk: [("similarity_rank, " + name, rank), ("similarity_topk (k = %d), " % k + name, topk)]
+    fns = (pair("one mask, p = 0.5", lambda: op.similarity_rank(q, clips, rows, mult, products, target32, half),
+                lambda: op.similarity_topk_masked(q, clips, rows, mult, products, k, half))
+           + pair("one mask per query, p = 0.5", lambda: op.similarity_rank(q, clips, rows, mult, products, target32, per_query),
+                  lambda: op.similarity_topk_masked(q, clips, rows, mult, products, k, per_query))
+           + pair("groups of 1..%d rows" % largest, lambda: op.similarity_rank(q, clips, rows, mult, products, target32, group_head=head),
+                  lambda: op.similarity_topk_grouped(q, clips, rows, mult, products, k, head))
+           + pair("dual softmax per gallery row", lambda: op.similarity_rank(q, clips, rows, mult, products, target32, None, m_g, s_g, 1, bank),
+                  lambda: op.similarity_topk_dsl(q, clips, rows, mult, products, k, m_g, s_g, 1, bank))
+           + pair("dual softmax per query row", lambda: op.similarity_rank(clip_q, captions, rows, mult, products, target32, None, m_q, s_q, 0, rows),
+                  lambda: op.similarity_topk_dsl(clip_q, captions, rows, mult, products, k, m_q, s_q, 0, rows)))
+    report("the forms, same shape", timed(fns, warmup, reps))
+    # the evaluation-size shape: the device work of both directions' counts, with and without the matrix
+    nt, nv = 10000, 1000
+    text, video = unit(nt, False), unit(nv, True)
+    vpad = torch.zeros(T.padded_video_rows(nv), 3 * E, device=device, dtype=torch.float16)
+    vpad[:nv] = video
+    gt = torch.randint(0, nv, (nt,), device=device, generator=g)
+    gt32, first_text = gt.to(torch.int32), torch.arange(nv, device=device, dtype=torch.int32) * (nt // nv)
+
+    def with_matrix():
+        sim = op.scaled_dot_planes(text, vpad, nv, mult, products)
+        ref = sim[first_text.long(), torch.arange(nv, device=device)]
+        return op.rank_counts_cols(sim, gt32), op.rank_counts_ref(sim, ref.contiguous(), True)
+
+    def without():
+        return (op.similarity_rank(text, video, nv, mult, products, gt32)[0],
+                op.similarity_rank(video, text, nt, mult, products, first_text)[0])
+    a, b = with_matrix(), without()
+    assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1][:, :2]), "the two paths disagree on the counts"
+    report("evaluation size: %d captions x %d clips, text->video and video->text counts" % (nt, nv),
+           timed([("scaled_dot_planes + rank_counts_cols + rank_counts_ref (the matrix path)", with_matrix),
+                  ("similarity_rank x 2 (no matrix)", without)], warmup, reps))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=40, help="clips encoded into the gallery (0: skip the model part)")
@@ -356,10 +477,17 @@ def main():
     ap.add_argument("--remove", type=float, default=0.0, help="FRACTION > 0: remove that share of the clips, search, compact()")
     ap.add_argument("--subset", type=float, default=0.0, help="FRACTION > 0: search within that share of the clips (allow=)")
     ap.add_argument("--baseline-lib", default="", help="--remove / --subset: another build of the library to time the unmasked op of")
+    ap.add_argument("--rank", type=int, default=0, help="1: the rank of a known clip (FeatureGallery.rank), checked and timed")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), bench.task_config(c)).to(device).eval()
+    if a.rank:
+        if a.clips:
+            rank_part(model, device, a)
+        if a.time_rows:
+            time_rank(model, device, a.time_rows, a.time_queries, a.time_k, a.groups or 40, a.time_bank, a.reps, a.warmup)
+        return
     if a.remove or a.subset:
         if a.clips:
             masked_part(model, device, a)

@@ -878,6 +878,31 @@ int cc_dsl_col_stats_planes_masked_f32(const void* text_planes, const void* vide
                                        float mult, int32_t products, const int32_t* text_mask, float* m, float* s, void* ws,
                                        size_t ws_bytes, void* stream);
 int cc_pack_row_mask_u8(const uint8_t* flags, int32_t rows, int32_t n, int32_t* out_words, int32_t words_per_row, void* stream);
+/* Rank of a known row or group: where target[q] stands for query row q, without the matrix and without a list.  The arguments
+ * are cc_similarity_topk_masked_planes_f32's where they coincide; row_mask == NULL: every row is selectable (mask_rows,
+ * mask_words are then not looked at); m == s == NULL ranks S, both non-NULL the dual softmax D; group_head == NULL ranks rows.
+ * target: int32 [Bq] on the device.  x(q, r) below is the score the top-k entries give the pair, bit for bit.
+ *   Rows: t_q = x(q, target[q]) - always computed from the target row, whose own mask bit is not consulted.  Over the
+ *   selectable rows r < Bg: counts[q] = (#{x > t_q}, #{x == t_q}, #{r < target[q], x == t_q}) and score[q] = t_q: the three
+ *   numbers cc_rank_counts_cols_f32 writes for the matrix row with gt_cols[q] = target[q] (plain float compares: -0 == +0, a
+ *   NaN is neither greater nor equal).  The 0-based rank in the search's full ordering is counts[0] + counts[2].
+ *   Groups: a group's score is the largest x of its selectable rows; target[q] is any row of the target group, t_q that
+ *   group's score (-inf without a selectable row); the counts run over the groups that have a selectable row: greater, equal
+ *   (the target's own included), and equal with the group lying in front of the target's.  Non-finite planes stay outside the
+ *   contract here, as for the grouped searches.
+ *   A target outside [0, Bg): counts (0, 0, 0), score -inf.
+ * counts: int32 [Bq][3]; score: fp32 [Bq].  Three launches on the stream - the targets' scores (one wave per query row, the
+ * MFMA sequence of every other score), the counting pass on the top-k grid, the sum over its slices - no atomics, no host
+ * synchronisation: capturable.  ws: cc_similarity_rank_workspace_bytes(Bq, Bg) bytes (0 for Bq <= 0 or Bg <= 0).
+ * Limits: E % 64 == 0, E <= 1024, products 1..3 (no k, so none of the top-k entries' LDS exclusions).  Returns in this order:
+ * CC_ERR_INVALID (a NULL pointer other than the optional ones, Bq / Bg / E <= 0, exactly one of m / s, with both n_total < 0 or
+ * stats_on_gallery other than 0 / 1, with a mask mask_rows other than 1 or Bq or mask_words < ceil(Bg / 32)),
+ * CC_ERR_UNSUPPORTED, CC_ERR_WORKSPACE - before anything is read. */
+size_t cc_similarity_rank_workspace_bytes(int32_t Bq, int32_t Bg);
+int cc_similarity_rank_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E, float mult,
+                                  int32_t products, const int32_t* target, const int32_t* row_mask, int32_t mask_rows,
+                                  int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery, int32_t n_total,
+                                  const int32_t* group_head, int32_t* counts, float* score, void* ws, size_t ws_bytes, void* stream);
 int cc_video_pool_normalize_f32(const float* visual, const int64_t* video_mask, int32_t Bv, int32_t Tn,
                                 int32_t E, float* pooled, void* stream);
 int cc_loose_similarity_f32(const float* text, const float* visual, const int64_t* video_mask,
