@@ -132,6 +132,11 @@ def _declare(lib):
     lib.cc_similarity_topk_masked_planes_f32.argtypes = [vp, vp, i32, i32, i32, f32, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp,
                                                          vp, vp, vp, sz, vp]
     lib.cc_similarity_topk_masked_planes_f32.restype = c.c_int
+    lib.cc_similarity_topk_deep_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.cc_similarity_topk_deep_workspace_bytes.restype = sz
+    lib.cc_similarity_topk_deep_planes_f32.argtypes = [vp, vp, i32, i32, i32, f32, i32, i32, vp, i32, i32, vp, vp, i32, i32, vp, vp,
+                                                       vp, vp, vp, vp, sz, vp]
+    lib.cc_similarity_topk_deep_planes_f32.restype = c.c_int
     lib.cc_dsl_col_stats_planes_masked_f32.argtypes = [vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, sz, vp]
     lib.cc_dsl_col_stats_planes_masked_f32.restype = c.c_int
     lib.cc_pack_row_mask_u8.argtypes = [vp, i32, i32, vp, i32, vp]

@@ -52,6 +52,15 @@
 // that counts, per query row, the candidates above t_q, equal to it, and equal in front of the target - three integers a lane
 // instead of the lists, so LDS is the staged rows alone; rank_reduce_kernel adds the slices' partial counts.  Integers: any
 // split of the gallery sums to the same result.
+//
+// Deep lists and cursors (more than TK_MAXK entries, or the entries behind a known one), still without the matrix: a list is a
+// chain of PAGES of at most TK_MAXK entries, each the stream above restricted to the keys BELOW a per-query bound - the last
+// key of the page before, or the key of a (score, id) pair the caller holds.  Keys are unique and their unsigned order is the
+// result's order, so "the keys below X" is exact and needs no state.  topk_stream_kernel<DSL, GROUPED, MASK, true>, a fourth
+// compile-time mode: a candidate is kept only if key < bound[q] (bound 0 keeps nothing); GROUPED applies it to the finished
+// group's candidate, never to a row - a group whose best row lies at or above the bound was handed out before and must not
+// return through its second-best row.  topk_merge_kernel writes a page at its column offset of the [Bq, k] result and its last
+// key to bound[q] for the page after it: the pages of a call hand over on the device.
 #include <type_traits>
 
 #include "cc_kernels.h"
@@ -64,7 +73,7 @@ namespace {
 
 constexpr int TK_WAVES = 4;            // waves of a streaming workgroup
 constexpr int TK_QROWS = 16;           // query rows of a workgroup (one MFMA tile side)
-constexpr int TK_MAXK = 128;
+constexpr int TK_MAXK = 128;             // entries of a list (of a page of a deep list) at most
 constexpr int TK_QPAD = 8;             // halfs behind a staged query row: 16 rows 16 bytes apart mod 256 cover all LDS banks
 constexpr int TK_TARGET_WGS = 512;     // streaming workgroups aimed at: the 256 CUs twice
 constexpr int TK_MIN_TILES = 32;       // 16-row tiles a slice holds at least (8 per wave)
@@ -368,13 +377,16 @@ struct TkMaskState<0> {};
 // A row whose bit is 0 gets key 0, the empty entry: that is the whole ranking rule in every DSL x GROUPED combination, and the
 // fold, the workspace and the merge never know.  Statistics and heads are indexed as without a mask.  MASK == 1 streams the
 // live tiles only (TkLive); MASK == 2 skips nothing.  GROUPED with dead tiles: see on_tile.
-template <bool DSL, bool GROUPED, int MASK>
+// BOUND: a fourth compile-time mode - a candidate of query row q is kept only if its key is below bound[q] (0: nothing is
+// kept); without GROUPED a candidate is a row, with it the finished group tk_group_tile hands over (and the carry at the
+// range's end), so the rows of a group are folded before the bound looks at it.  Without BOUND `bound` is not read.
+template <bool DSL, bool GROUPED, int MASK, bool BOUND>
 __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
                                                           int Bq, int Bg, int ld, int K, float sc, int k, int slices,
                                                           u64* __restrict__ ws, const float* __restrict__ stat_m,
                                                           const float* __restrict__ stat_s, int on_gallery, float nt,
                                                           const int* __restrict__ group_head, const int* __restrict__ row_mask,
-                                                          int mask_words) {
+                                                          int mask_words, const u64* __restrict__ bound) {
     extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
     const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
@@ -391,6 +403,8 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
     const bool qvalid = q0 + l15 < Bq;
     u64 thr = 0;                                                                       // the k-th key of `mine`
     int filled = 0;                                                                    // entries any of the wave's lists holds, at most
+    u64 below = 0;                                                                     // BOUND: query row l15's bound
+    if constexpr (BOUND) below = bound[min(q0 + l15, Bq - 1)];
     // DSL: the statistics of the lane's 4 gallery rows (requested per tile) or of its query row (once)
     float dm[4] = {0.f, 0.f, 0.f, 0.f}, ds[4] = {1.f, 1.f, 1.f, 1.f};
     if constexpr (DSL) {
@@ -459,6 +473,7 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
                 key[r] = (qvalid && id < Bg) ? tk_key(x, id) : 0;
             }
             if constexpr (MASK != 0) key[r] = ((ms.word >> ((t & 1) * 16 + lg * 4 + r)) & 1) ? key[r] : 0;
+            if constexpr (BOUND && !GROUPED) key[r] = key[r] < below ? key[r] : 0;
         }
         if constexpr (GROUPED && MASK == 1) {
             // Dead tiles between the tile streamed before and this one were skipped, heads included.  If a group starts in
@@ -470,6 +485,10 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
             ms.prev = t;
         }
         if constexpr (GROUPED) tk_group_tile(key, head, lg, carry);
+        if constexpr (BOUND && GROUPED) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) key[r] = key[r] < below ? key[r] : 0;          // the finished groups, not their rows
+        }
         tk_insert_tile(key, mine, k, lg, thr, filled);
     };
     constexpr int stride = GROUPED ? 1 : TK_WAVES;
@@ -481,6 +500,7 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
     }
     if constexpr (GROUPED) {
         u64 key[4] = {lg == 0 ? carry : 0, 0, 0, 0};                                   // the group open at the range's end
+        if constexpr (BOUND) key[0] = key[0] < below ? key[0] : 0;
         tk_insert_tile(key, mine, k, lg, thr, filled);
     }
     // the four waves' lists -> wave 0's, as a tree: the other wave's entries are the candidates, 16 a list at a time
@@ -510,9 +530,10 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
 
 // ws [Bq][k][slices]: rank by rank, the best entry of every slice first.  A rank none of whose entries passes the threshold
 // ends the merge: every list descends, so no deeper entry passes either - for k well below the gallery the result comes from
-// the first few ranks.
+// the first few ranks.  scores / ids: rows out_ld entries apart (a page of a deep list lands at its column offset of the whole
+// result).  last != nullptr: last[q] = the list's k-th key (0: the list is not full) - the bound of the page behind this one.
 __global__ __launch_bounds__(64) void topk_merge_kernel(const u64* __restrict__ ws, int slices, int k, float* __restrict__ scores,
-                                                        int* __restrict__ ids) {
+                                                        int* __restrict__ ids, int out_ld, u64* __restrict__ last) {
     __shared__ u64 list[TK_MAXK];
     const int q = blockIdx.x, lane = threadIdx.x;
     for (int i = lane; i < k; i += 64) list[i] = 0;
@@ -548,9 +569,18 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const u64* __restrict__ 
         float s;
         int id;
         tk_decode(list[i], s, id);
-        scores[(int64_t)q * k + i] = s;
-        ids[(int64_t)q * k + i] = id;
+        scores[(int64_t)q * out_ld + i] = s;
+        ids[(int64_t)q * out_ld + i] = id;
     }
+    if (last && lane == 0) last[q] = list[k - 1];
+}
+
+// The bound of a search that continues behind a known entry: bound[q] = tk_key(after_scores[q], after_ids[q]), the key that
+// entry has in every list; an id < 0 (the fill: nothing lies behind it) gives 0, which keeps nothing.
+__global__ __launch_bounds__(256) void topk_cursor_kernel(const float* __restrict__ after_scores, const int* __restrict__ after_ids,
+                                                          int Bq, u64* __restrict__ bound) {
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q < Bq) bound[q] = after_ids[q] < 0 ? 0 : tk_key(after_scores[q], after_ids[q]);
 }
 
 // ---------------------------------------------------------------------------- rank of a known row or group
@@ -880,10 +910,23 @@ int tk_slices(int Bq, int Bg) {
 // with), at least TK_MIN_TILES tiles a slice
 int dsl_stats_slices(int Bt) { return max(1, min(DSL_MAX_SLICES, (max(Bt, 1) + 15) / 16 / TK_MIN_TILES)); }
 size_t tk_stream_lds(int K, int k) { return (size_t)TK_QROWS * (K + TK_QPAD) * 2 + (size_t)TK_WAVES * TK_QROWS * k * sizeof(u64); }
-template <int MASK>
+template <int MASK, bool BOUND>
 auto tk_stream_kernel_of(bool dsl, bool grouped) {
-    return grouped ? (dsl ? topk_stream_kernel<true, true, MASK> : topk_stream_kernel<false, true, MASK>)
-                   : (dsl ? topk_stream_kernel<true, false, MASK> : topk_stream_kernel<false, false, MASK>);
+    return grouped ? (dsl ? topk_stream_kernel<true, true, MASK, BOUND> : topk_stream_kernel<false, true, MASK, BOUND>)
+                   : (dsl ? topk_stream_kernel<true, false, MASK, BOUND> : topk_stream_kernel<false, false, MASK, BOUND>);
+}
+// mask_rows: 0 no mask, 1 one mask row (also when Bq == 1), otherwise one per query row
+template <bool BOUND>
+auto tk_stream_kernel_of(bool dsl, bool grouped, int mask_rows) {
+    return mask_rows == 0   ? tk_stream_kernel_of<0, BOUND>(dsl, grouped)
+           : mask_rows == 1 ? tk_stream_kernel_of<1, BOUND>(dsl, grouped)
+                            : tk_stream_kernel_of<2, BOUND>(dsl, grouped);
+}
+// the longest list (page) the stream's LDS holds next to 16 staged rows of K halfs: TK_MAXK, 127 for K = 3072
+int tk_page_len(int K) {
+    int page = TK_MAXK;
+    while (page > 1 && tk_stream_lds(K, page) > TK_LDS_LIMIT) --page;
+    return page;
 }
 template <int MASK>
 auto rank_stream_kernel_of(bool dsl, bool grouped) {
@@ -923,15 +966,15 @@ static int tk_launch(bool dsl, bool grouped, const void* query_planes, const voi
     if (!ws || ws_bytes < cc_similarity_topk_workspace_bytes(Bq, Bg, k)) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int slices = tk_slices(Bq, Bg);
-    const auto kernel = !masked ? tk_stream_kernel_of<0>(dsl, grouped)                 // one shared mask row also when Bq == 1
-                                : mask_rows == 1 ? tk_stream_kernel_of<1>(dsl, grouped) : tk_stream_kernel_of<2>(dsl, grouped);
+    const auto kernel = tk_stream_kernel_of<false>(dsl, grouped, masked ? mask_rows : 0);
     if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
     hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
                        static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K,
                        mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, k, slices, static_cast<u64*>(ws), m, s,
-                       on_gallery, (float)n_total, group_head, row_mask, mask_words);
+                       on_gallery, (float)n_total, group_head, row_mask, mask_words, static_cast<const u64*>(nullptr));
     CC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(ws), slices, k, scores, ids);
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(ws), slices, k, scores, ids, k,
+                       static_cast<u64*>(nullptr));
     CC_LAUNCH_CHECK();
     return CC_OK;
 }
@@ -975,6 +1018,56 @@ int cc_similarity_topk_masked_planes_f32(const void* query_planes, const void* g
     return tk_launch(dsl, group_head != nullptr, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s,
                      dsl ? stats_on_gallery : 0, dsl ? n_total : 0, group_head, scores, ids, ws, ws_bytes, stream, true, row_mask,
                      mask_rows, mask_words);
+}
+
+// one page's workspace (the plain entry's at the page length), then the cursor buffer: u64 [Bq]
+size_t cc_similarity_topk_deep_workspace_bytes(int32_t Bq, int32_t Bg, int32_t E, int32_t products, int32_t k) {
+    if (Bq <= 0 || Bg <= 0 || E <= 0 || k < 1 || k > CC_TOPK_DEEP_MAXK) return 0;
+    if (products < 1 || products > 3 || (E & 63) || E > 1024) return 0;
+    return cc_similarity_topk_workspace_bytes(Bq, Bg, min(k, tk_page_len(products * E)))
+           + cc_align_up((size_t)Bq * sizeof(u64), 256);
+}
+
+int cc_similarity_topk_deep_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                       float mult, int32_t products, int32_t k, const int32_t* row_mask, int32_t mask_rows,
+                                       int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery, int32_t n_total,
+                                       const int32_t* group_head, const float* after_scores, const int32_t* after_ids, float* scores,
+                                       int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
+    const bool dsl = m || s, grouped = group_head != nullptr, masked = row_mask != nullptr;
+    if (!query_planes || !gallery_planes || !scores || !ids || Bq <= 0 || Bg <= 0 || E <= 0 || k < 1) return CC_ERR_INVALID;
+    if (dsl && (!m || !s || n_total < 0 || (stats_on_gallery != 0 && stats_on_gallery != 1))) return CC_ERR_INVALID;
+    if (masked && ((mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
+    if (!after_scores != !after_ids) return CC_ERR_INVALID;
+    if (k > CC_TOPK_DEEP_MAXK || products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
+    if ((Bq + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million query rows a call)
+    if (!ws || ws_bytes < cc_similarity_topk_deep_workspace_bytes(Bq, Bg, E, products, k)) return CC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int K = products * E, page = min(k, tk_page_len(K)), slices = tk_slices(Bq, Bg);
+    const int on_gallery = dsl ? stats_on_gallery : 0;
+    const float sc = mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, nt = dsl ? (float)n_total : 0.f;
+    u64* lists = static_cast<u64*>(ws);
+    u64* cursor = reinterpret_cast<u64*>(static_cast<char*>(ws) + cc_similarity_topk_workspace_bytes(Bq, Bg, page));
+    bool bounded = after_scores != nullptr;
+    if (bounded) {
+        hipLaunchKernelGGL(topk_cursor_kernel, dim3((Bq + 255) / 256), dim3(256), 0, st, after_scores, after_ids, Bq, cursor);
+        CC_LAUNCH_CHECK();
+    }
+    for (int done = 0; done < k; done += page, bounded = true) {                       // (every page behind the first is bounded)
+        const int kp = min(page, k - done);
+        const size_t smem = tk_stream_lds(K, kp);
+        const auto kernel = bounded ? tk_stream_kernel_of<true>(dsl, grouped, masked ? mask_rows : 0)
+                                    : tk_stream_kernel_of<false>(dsl, grouped, masked ? mask_rows : 0);
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
+        hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
+                           static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K,
+                           sc, kp, slices, lists, m, s, on_gallery, nt, group_head, row_mask, mask_words,
+                           static_cast<const u64*>(cursor));
+        CC_LAUNCH_CHECK();
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(lists), slices, kp,
+                           scores + done, ids + done, k, done + kp < k ? cursor : static_cast<u64*>(nullptr));
+        CC_LAUNCH_CHECK();
+    }
+    return CC_OK;
 }
 
 size_t cc_similarity_rank_workspace_bytes(int32_t Bq, int32_t Bg) {

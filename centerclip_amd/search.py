@@ -40,6 +40,12 @@ Rows leave and searches narrow with one bit per row (``similarity_topk_masked``)
 
     ranks, scores, counts = gallery.rank(input_ids, target=truth)           # 0-based places in search's full ordering
     ranks, scores, counts = gallery.rank_groups(video, video_mask, target=labels)      # grouped=True: the place of a group
+
+Lists of up to 4096 entries and "next page" cursors (``similarity_topk_deep``): pages of at most 128, each the same stream
+restricted to what lies behind the page before - exact, no matrix, no state between calls:
+
+    scores, ids = gallery.search(input_ids, k=1000)                         # candidates for a re-ranker
+    more_scores, more_ids = gallery.search(input_ids, k=50, after=(scores[:, -1], ids[:, -1]))     # entries 1000..1049
 """
 import numpy as np
 import torch
@@ -95,7 +101,21 @@ class FeatureGallery:
     -> (ranks, scores, counts) of one target position per query among the rows ``search*`` ranks - removals, ``allow=`` and
     the dual softmax's statistics act as there; ``rank_groups*`` the same for one target label per query among the groups
     ``search_groups*`` ranks.  ``counts`` are the (greater, equal, equal in front) triples of ``rank_counts_cols`` on the
-    matrix row, ``ranks = counts[:, 0] + counts[:, 2]``; a target that is not selectable keeps its score and is not counted."""
+    matrix row, ``ranks = counts[:, 0] + counts[:, 2]``; a target that is not selectable keeps its score and is not counted.
+
+    The contract of a list, for every ``search*`` method and every combination above, 1 <= k <= 4096:
+      * ``search(k=K)`` is the first K entries of the stable descending sort of ``similarity()``'s row: the scores are the
+        matrix op's bits, equal scores are ordered by smaller position, (-inf, -1) fills what lies behind the selectable rows
+        (``search_groups``: of that order the first row of every group).
+      * ``search(k=a)`` followed by ``search(k=b, after=(scores[:, -1], positions[:, -1]))`` of its result is columns
+        [a, a + b) of ``search(k=a + b)``.  A cursor is nothing but that pair: it names a place in the ordering, not a row that
+        must still be held, so it stays right when rows are removed between the two calls (the list continues behind the
+        place the pair had); a cursor equal to the fill gives the fill.  ``compact()`` renumbers positions: cursors do not
+        survive it.
+      * k <= 128 without ``after=`` runs the ops it always ran (one pass).  Otherwise ``similarity_topk_deep``: ceil(k / 128)
+        passes over the gallery (pages of 127 at E = 1024 with three products), the pages handing over on the device;
+        dual_softmax=True, side="text": the queries' statistics are taken once per call, not per page.
+      * A call does not synchronise with the host: ``after=`` takes device tensors and reads none of them."""
 
     def __init__(self, model, side="video", capacity=0, products=None, dual_softmax=False, grouped=False):
         if side not in SIDES:
@@ -539,19 +559,43 @@ class FeatureGallery:
     def _query_rows(self, features, mask):
         return self._text_rows(features) if self.side == "video" else self._video_rows(features, mask)
 
-    def _search_rows(self, q, k, groups=False, allow=None):
+    def _check_list(self, k, after, nq, what):
+        """the refusals of a list's length and cursor, which need nothing encoded: 1 <= k <= 4096; ``after`` is None or a pair
+        (scores fp32 [nq], positions int32 / int64 [nq]) of tensors on the gallery's device, passed through unread"""
+        if not 1 <= int(k) <= T.TOPK_DEEP_MAXK:
+            raise ValueError("FeatureGallery.%s: 1 <= k <= %d, not %d" % (what, T.TOPK_DEEP_MAXK, int(k)))
+        if after is None:
+            return
+        if not isinstance(after, (tuple, list)) or len(after) != 2 or not all(torch.is_tensor(a) for a in after):
+            raise ValueError("FeatureGallery.%s: after= is a pair (scores, positions) of device tensors, typically the last "
+                             "column of an earlier result" % what)
+        scores, pos = after
+        if (scores.dtype != torch.float32 or pos.dtype not in (torch.int32, torch.int64) or tuple(scores.shape) != (nq,)
+                or tuple(pos.shape) != (nq,) or scores.device != self._rows.device or pos.device != self._rows.device):
+            raise ValueError("FeatureGallery.%s: after= holds scores %s %s on %s and positions %s %s on %s, not one fp32 score and "
+                             "one int32 / int64 position per query (%d) on %s (a host value would have to be uploaded: pass the "
+                             "columns of the earlier result)" % (what, tuple(scores.shape), scores.dtype, scores.device,
+                                                                 tuple(pos.shape), pos.dtype, pos.device, nq, self._rows.device))
+
+    def _search_rows(self, q, k, groups=False, allow=None, after=None):
         """the k best rows - groups: the best row of each of the k best groups - of every row of q; after ``remove`` or with
-        ``allow=``: of the rows both leave selectable"""
+        ``allow=``: of the rows both leave selectable; ``after``: of those behind that entry of the ordering"""
         k = int(k)
         if self._dsl:
             self._need_bank()
         mask = self._allow_words(allow, q.shape[0])
         if len(self) == 0:                                  # nothing to rank: the fill of a list longer than the gallery
-            if not 1 <= k <= 128:
-                raise ValueError("FeatureGallery: 1 <= k <= 128")
             return (torch.full((q.shape[0], k), float("-inf"), device=self.device),
                     torch.full((q.shape[0], k), -1, device=self.device, dtype=torch.int64))
         op, tail = torch.ops.centerclip, ((self._head,) if groups else ())
+        if k > 128 or after is not None:                    # a list of pages, or one that starts behind a cursor: one op for all
+            m = s = None
+            on_gallery, n_total = self.side == "video", 0
+            if self._dsl:                                   # (side="text": the queries' pairs once per call, not per page)
+                m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
+                n_total = self._bank.shape[0] if on_gallery else len(self)
+            return op.similarity_topk_deep(q, self._rows, self._n, self._mult(), self.products, k, mask, m, s, int(on_gallery),
+                                           n_total, self._head if groups else None, *(after if after is not None else (None, None)))
         if mask is not None:                                # one op for the four rankings (no mask: the ops of before)
             m = s = None
             on_gallery, n_total = self.side == "video", 0
@@ -569,36 +613,46 @@ class FeatureGallery:
         return (op.similarity_topk_grouped if groups else op.similarity_topk)(q, self._rows, self._n, self._mult(), self.products,
                                                                                k, *tail)
 
-    def _search_group_rows(self, q, k, allow=None):
-        scores, pos = self._search_rows(q, k, groups=True, allow=allow)
+    def _search_group_rows(self, q, k, allow=None, after=None):
+        scores, pos = self._search_rows(q, k, groups=True, allow=allow, after=after)
         return scores, self._label_dev[pos], pos                 # (position -1, the fill: the last entry, -1)
 
-    def search_groups(self, *inputs, k=10, allow=None):
+    def search_groups(self, *inputs, k=10, allow=None, after=None):
         """grouped=True: the queries of ``search`` -> (scores [Nq, k] fp32, labels [Nq, k] int64, positions [Nq, k] int64) of
         the k best groups, best first, each by its best row (``positions``); (-inf, -1, -1) beyond the number of groups.
         After ``remove`` / with ``allow=`` (see ``search``): a group is ranked by its best selectable row, one without any
-        does not appear."""
+        does not appear.  ``after=(scores[:, -1], positions[:, -1])`` of an earlier result: the k groups behind it (see
+        ``search``; the position is the group's best row)."""
         self._need_grouped("search_groups")
+        self._check_list(k, after, inputs[0].shape[0], "search_groups")      # (refusals come before anything is encoded)
         return self._search_group_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), k,
-                                       allow)
+                                       allow, after)
 
-    def search_groups_features(self, features, k=10, mask=None, allow=None):
+    def search_groups_features(self, features, k=10, mask=None, allow=None, after=None):
         """``search_groups`` for query features computed elsewhere (as ``search_features``)."""
         self._need_grouped("search_groups_features")
-        return self._search_group_rows(self._query_rows(features, mask), k, allow)
+        self._check_list(k, after, features.shape[0], "search_groups_features")
+        return self._search_group_rows(self._query_rows(features, mask), k, allow, after)
 
-    def search(self, *inputs, k=10, allow=None):
+    def search(self, *inputs, k=10, allow=None, after=None):
         """``search(input_ids, k=10)`` (``search(video, video_mask, k=10)`` for side="text") -> (scores [Nq, k] fp32, positions
         [Nq, k] int64), best first, equal scores by smaller position; (-inf, -1) beyond the gallery's size.  Removed rows are
         not ranked.  ``allow=``: rank a subset only - an int32 mask [W] or [Nq, W] on the device (bit b of word w = position
         32 w + b, W >= ceil(span / 32)), a device bool tensor [span] or [Nq, span], or what ``row_mask`` returns; one mask
-        for all queries also skips the tiles of 16 rows it leaves empty.  The fill starts behind the selectable rows."""
+        for all queries also skips the tiles of 16 rows it leaves empty.  The fill starts behind the selectable rows.
+        1 <= k <= 4096: beyond 128 the list is built in pages of at most 128, each one more pass over the gallery.
+        ``after=(scores [Nq], positions [Nq])``, device tensors - typically ``(scores[:, -1], positions[:, -1])`` of an earlier
+        result: the k entries that FOLLOW that pair in the full ordering (after the fill (-inf, -1): only fill), whatever
+        happened to the pair's row since - the cursor of a "next page" that needs no state and stays right when rows are
+        removed between two pages (not across ``compact()``, which renumbers).  Nothing here is read on the host."""
+        self._check_list(k, after, inputs[0].shape[0], "search")             # (refusals come before anything is encoded)
         return self._search_rows(self._encode_text(*inputs) if self.side == "video" else self._encode_video(*inputs), k,
-                                 allow=allow)
+                                 allow=allow, after=after)
 
-    def search_features(self, features, k=10, mask=None, allow=None):
+    def search_features(self, features, k=10, mask=None, allow=None, after=None):
         """``search`` for query features computed elsewhere (sequence_output; side="text": visual_output and its mask)."""
-        return self._search_rows(self._query_rows(features, mask), k, allow=allow)
+        self._check_list(k, after, features.shape[0], "search_features")
+        return self._search_rows(self._query_rows(features, mask), k, allow=allow, after=after)
 
     # ------------------------------------------------------------------ the rank of a known row or group
     def _targets(self, target, nq, what):

@@ -1412,6 +1412,79 @@ def _(query_planes, gallery_planes, n_gallery, mult, products, k, row_mask, m=No
             query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
 
 
+TOPK_DEEP_MAXK = 4096          # CC_TOPK_DEEP_MAXK
+
+
+def _check_topk_deep(query_planes, gallery_planes, n_gallery, k, row_mask, m, s, stats_on_gallery, group_head, after_scores,
+                     after_ids):
+    """similarity_topk_masked's checks (the mask only when there is one), k, and the cursor: both tensors or neither, one
+    fp32 score and one int32 / int64 id per query row on the planes' device"""
+    name = "similarity_topk_deep"
+    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head, name)
+    if not 1 <= int(k) <= TOPK_DEEP_MAXK:
+        raise ValueError("%s: 1 <= k <= %d, not %d" % (name, TOPK_DEEP_MAXK, int(k)))
+    if (after_scores is None) != (after_ids is None):
+        raise ValueError("%s: after_scores and after_ids come together" % name)
+    if after_scores is not None:
+        Bq = query_planes.shape[0]
+        if (after_scores.dtype != torch.float32 or after_ids.dtype not in (torch.int32, torch.int64)
+                or tuple(after_scores.shape) != (Bq,) or tuple(after_ids.shape) != (Bq,)
+                or after_scores.device != query_planes.device or after_ids.device != query_planes.device):
+            raise ValueError("%s: after_scores %s %s on %s, after_ids %s %s on %s are not one fp32 score and one int32 / int64 id "
+                             "per query row (%d) on %s" % (name, tuple(after_scores.shape), after_scores.dtype, after_scores.device,
+                                                          tuple(after_ids.shape), after_ids.dtype, after_ids.device, Bq,
+                                                          query_planes.device))
+    return E3
+
+
+@custom_op(NS + "::similarity_topk_deep", mutates_args=(), device_types="cuda")
+def similarity_topk_deep(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                         k: int, row_mask: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None,
+                         s: Optional[torch.Tensor] = None, stats_on_gallery: int = 1, n_total: int = 0,
+                         group_head: Optional[torch.Tensor] = None, after_scores: Optional[torch.Tensor] = None,
+                         after_ids: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """similarity_topk_masked (row_mask optional here) for lists beyond 128 and for cursors: 1 <= k <= 4096 -> (scores [Bq, k]
+    fp32, ids [Bq, k] int64), the first k entries of the same ordering with the same bits.  after_scores [Bq] fp32 and
+    after_ids [Bq] int32 / int64 (both or neither; typically scores[:, -1], ids[:, -1] of an earlier result): the list starts
+    behind that entry of the ordering - k = a, then k = b after its last column, are columns [0, a) and [a, a + b) of k = a + b;
+    an id < 0 (the fill) gives the fill.  Built in pages of at most 128 entries, each one pass over the gallery restricted to
+    the keys below the page before; the pages hand over on the device (no host read).  n_gallery == 0 gives the fill without a
+    launch.  cc_similarity_topk_deep_planes_f32."""
+    Bq = query_planes.shape[0]
+    E3 = _check_topk_deep(query_planes, gallery_planes, n_gallery, k, row_mask, m, s, stats_on_gallery, group_head, after_scores,
+                          after_ids)
+    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
+    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
+    if Bq == 0 or int(n_gallery) == 0:                      # no row: nothing to rank
+        return scores.fill_(float("-inf")), ids.fill_(-1).to(torch.int64)
+    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
+    if m is not None:
+        m, s = m.contiguous(), s.contiguous()
+    if after_scores is not None:
+        after_scores, after_ids = after_scores.contiguous(), after_ids.to(torch.int32).contiguous()
+    lib = L.lib()
+    ws = L.workspace(lib.cc_similarity_topk_deep_workspace_bytes(Bq, int(n_gallery), E3 // 3, int(products), int(k)),
+                     query_planes.device)
+    masked = row_mask is not None
+    L.check(lib.cc_similarity_topk_deep_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
+                                                   float(mult), int(products), int(k), L.ptr(row_mask),
+                                                   (1 if row_mask.dim() == 1 else Bq) if masked else 0,
+                                                   int(row_mask.shape[-1]) if masked else 0, L.ptr(m), L.ptr(s),
+                                                   int(stats_on_gallery), int(n_total), L.ptr(group_head), L.ptr(after_scores),
+                                                   L.ptr(after_ids), L.ptr(scores), L.ptr(ids), L.ptr(ws), ws.numel(),
+                                                   _st(query_planes)), "cc_similarity_topk_deep_planes_f32")
+    return scores, ids.to(torch.int64)
+
+
+@similarity_topk_deep.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, k, row_mask=None, m=None, s=None, stats_on_gallery=1, n_total=0,
+      group_head=None, after_scores=None, after_ids=None):
+    _check_topk_deep(query_planes, gallery_planes, n_gallery, k, row_mask, m, s, stats_on_gallery, group_head, after_scores,
+                     after_ids)
+    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
+            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+
+
 def _check_rank(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head):
     """similarity_topk_masked's checks (the mask only when there is one) and the targets: one int32 / int64 per query row"""
     name = "similarity_rank"
@@ -1782,7 +1855,7 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
        "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
        "similarity_topk_grouped", "similarity_topk_grouped_dsl", "similarity_topk_masked", "dsl_col_stats_planes_masked",
-       "pack_row_mask", "similarity_rank")
+       "pack_row_mask", "similarity_rank", "similarity_topk_deep")
 
 
 def logit_multiplier(logit_scale):

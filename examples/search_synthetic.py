@@ -36,6 +36,13 @@ the timing of similarity_rank next to similarity_topk at --time-k and to the mat
 grouped and dual-softmax forms next to their top-k counterparts, and of the evaluation-size shape against the matrix path.
 
     python examples/search_synthetic.py --rank 1
+
+--deep K asks for lists beyond 128 entries and walks one with a cursor (search*(k=K), after=): on a small gallery with removed
+rows and runs of equal scores the list of K and three calls that continue each other are checked against the matrix + a
+stable sort, rows and groups; the timing is the deep call next to the same gallery's search(k=128) - one page of it - and to
+similarity() + torch.topk(k=K), and, with --baseline-lib PATH, to another build's k = 128 entry.
+
+    python examples/search_synthetic.py --deep 1000 [--baseline-lib other/libcenterclip_hip.so]
 """
 import argparse
 import os
@@ -461,6 +468,93 @@ def time_rank(model, device, rows, queries, k, largest, bank, reps, warmup):
                   ("similarity_rank x 2 (no matrix)", without)], warmup, reps))
 
 
+def deep_part(model, device, k, rows=5000, queries=6):
+    """a list of k entries and a three-step cursor walk over it, against the matrix + a stable sort, rows and groups"""
+    E = int(model.clip_config['embed_dim'])
+    g = torch.Generator(device=device).manual_seed(5)
+    feats = torch.randn(rows, E, device=device, generator=g)
+    feats[1::7] = feats[0]                                                   # (runs of equal scores across the page edges)
+    seq = torch.randn(queries, 1, E, device=device, generator=g)
+    labels = group_labels(rows, 5)
+    gallery = FeatureGallery(model, grouped=True)
+    gallery.add_features(feats, group=labels)
+    gallery.remove(list(range(3, rows, 11)))
+    sim = gallery.similarity_features(seq)                                   # (-inf in the removed columns)
+    held = len(gallery)
+    order = torch.sort(sim, dim=1, descending=True, stable=True)
+    kk = min(k, held)
+    scores, found = gallery.search_features(seq, k=k)
+    same = torch.equal(found[:, :kk], order.indices[:, :kk]) and torch.equal(scores[:, :kk], order.values[:, :kk])
+    print("search_features(k=%d) over %d rows held: the first %d entries of the matrix row's stable sort, same bits: %s; the fill "
+          "behind them: %s" % (k, held, kk, same, bool((found[:, kk:] == -1).all())))
+    steps, walk, after = (k // 3, k // 3, k - 2 * (k // 3)), [], None
+    for step in steps:
+        walk.append(gallery.search_features(seq, k=step, after=after))
+        after = (walk[-1][0][:, -1], walk[-1][1][:, -1])
+    same = torch.equal(torch.cat([w[1] for w in walk], 1), found) and torch.equal(torch.cat([w[0] for w in walk], 1), scores)
+    print("three calls of k = %s, each after= the last column of the one before: the columns of the one call: %s" % (list(steps), same))
+    # groups: the matrix, the per-group maximum, the stable sort - a group by its best row
+    on_device = labels.to(device)
+    best = torch.full((queries, int(labels.max()) + 1), float("-inf"), device=device).scatter_reduce_(
+        1, on_device.expand(queries, rows), sim, "amax")
+    want = torch.sort(best, dim=1, descending=True, stable=True)
+    n_groups = int((want.values[0] > float("-inf")).sum())
+    kg = min(k, n_groups)
+    gs, gl, gp = gallery.search_groups_features(seq, k=k)
+    walk, after = [], None
+    for step in steps:
+        walk.append(gallery.search_groups_features(seq, k=step, after=after))
+        after = (walk[-1][0][:, -1], walk[-1][2][:, -1])
+    same = torch.equal(gs[:, :kg], want.values[:, :kg]) and all(len(set(r[:kg])) == kg for r in gl.tolist())
+    print("search_groups_features(k=%d) over %d groups: the per-group maxima in stable order, no group twice: %s; the cursor walk "
+          "gives its columns: %s" % (k, n_groups, same, torch.equal(torch.cat([w[2] for w in walk], 1), gp)
+                                     and torch.equal(torch.cat([w[0] for w in walk], 1), gs)))
+
+
+def time_deep(model, device, rows, queries, k, reps, warmup, baseline_lib):
+    """the deep call next to the same gallery's search(k=128) - one page, the yardstick; with --baseline-lib another build's
+    k = 128 entry on the same buffers - and to similarity() + torch.topk(k), the only way to such a list before"""
+    import ctypes
+    E = int(model.clip_config['embed_dim'])
+    g = torch.Generator(device=device).manual_seed(1)
+    gallery = FeatureGallery(model, capacity=rows)
+    for b in uneven(rows, (rows // 2, rows // 3, rows)):
+        gallery.add_features(torch.randn(b, E, device=device, generator=g))
+    seq = torch.randn(queries, 1, E, device=device, generator=g)
+    products, mult = gallery.products, T.logit_multiplier(model._logit_scale_value())
+    q = gallery.backend.text_operand(seq.reshape(queries, -1))
+    op, lib = torch.ops.centerclip, L.lib()
+    a, b = gallery.search_features(seq, k=k), torch.topk(gallery.similarity_features(seq), k, dim=1)
+    assert torch.equal(a[0], b.values), "the two paths disagree on the scores"
+    page = gallery.search_features(seq, k=128)
+    assert torch.equal(a[0][:, :128], page[0]) and torch.equal(a[1][:, :128], page[1]), "the first page is not search(k=128)"
+    scores = torch.empty(queries, 128, device=device)
+    found = torch.empty(queries, 128, device=device, dtype=torch.int32)
+    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(queries, rows, 128), device)
+    vp, i32 = ctypes.c_void_p, ctypes.c_int32
+
+    def plain_of(build):
+        build.cc_similarity_topk_planes_f32.argtypes = [vp, vp, i32, i32, i32, ctypes.c_float, i32, i32, vp, vp, vp, ctypes.c_size_t, vp]
+        return lambda: L.check(build.cc_similarity_topk_planes_f32(L.ptr(q), L.ptr(gallery.rows), queries, rows, E, mult, products, 128,
+                                                                   L.ptr(scores), L.ptr(found), L.ptr(ws), ws.numel(),
+                                                                   L.stream_ptr(device)), "cc_similarity_topk_planes_f32")
+    fns = [("search_features(k=%d): %d pages" % (k, -(-k // 128)), lambda: gallery.search_features(seq, k=k)),
+           ("search_features(k=128): one page, the yardstick", lambda: gallery.search_features(seq, k=128)),
+           ("similarity_topk_deep op, k = %d" % k, lambda: op.similarity_topk_deep(q, gallery.rows, rows, mult, products, k)),
+           ("cc_similarity_topk_planes_f32, k = 128 (this build)", plain_of(lib))]
+    if baseline_lib:
+        fns.append(("cc_similarity_topk_planes_f32, k = 128 (--baseline-lib)", plain_of(ctypes.CDLL(baseline_lib))))
+    for _, fn in fns[3:]:
+        scores.zero_()
+        fn()
+        assert torch.equal(scores, page[0]) and torch.equal(found.long(), page[1]), "the builds disagree"
+    fns.append(("similarity_features + torch.topk(k=%d) (the matrix)" % k, lambda: torch.topk(gallery.similarity_features(seq), k, dim=1)))
+    report("%d queries x %d gallery rows, E = %d, products = %d: %d repetitions after %d warm-up rounds, device events"
+           % (queries, rows, E, products, reps, warmup), timed(fns, warmup, reps))
+    print("  deep workspace %d bytes (one page and the cursors, whatever k); the matrix has %d bytes"
+          % (lib.cc_similarity_topk_deep_workspace_bytes(queries, rows, E, products, k), queries * rows * 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=40, help="clips encoded into the gallery (0: skip the model part)")
@@ -478,10 +572,17 @@ def main():
     ap.add_argument("--subset", type=float, default=0.0, help="FRACTION > 0: search within that share of the clips (allow=)")
     ap.add_argument("--baseline-lib", default="", help="--remove / --subset: another build of the library to time the unmasked op of")
     ap.add_argument("--rank", type=int, default=0, help="1: the rank of a known clip (FeatureGallery.rank), checked and timed")
+    ap.add_argument("--deep", type=int, default=0, help="K > 128: a list of K entries and a cursor walk, checked and timed")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), bench.task_config(c)).to(device).eval()
+    if a.deep:
+        if a.clips:
+            deep_part(model, device, a.deep)
+        if a.time_rows:
+            time_deep(model, device, a.time_rows, a.time_queries, a.deep, a.reps, a.warmup, a.baseline_lib)
+        return
     if a.rank:
         if a.clips:
             rank_part(model, device, a)

@@ -878,6 +878,39 @@ int cc_dsl_col_stats_planes_masked_f32(const void* text_planes, const void* vide
                                        float mult, int32_t products, const int32_t* text_mask, float* m, float* s, void* ws,
                                        size_t ws_bytes, void* stream);
 int cc_pack_row_mask_u8(const uint8_t* flags, int32_t rows, int32_t n, int32_t* out_words, int32_t words_per_row, void* stream);
+/* Deep lists and cursors: more than 128 entries, or the entries that follow a known one, still exact and without the matrix.
+ * One entry for the four rankings with cc_similarity_topk_masked_planes_f32's conventions, each part optional: row_mask ==
+ * NULL: every row is selectable (mask_rows, mask_words are then not looked at); m == s == NULL ranks S, both non-NULL the dual
+ * softmax D; group_head == NULL ranks rows, otherwise groups.  1 <= k <= CC_TOPK_DEEP_MAXK.
+ *   Result: scores / ids [Bq][k]: the first k entries of the ordering the other entries cut at 128 (stable descending, equal
+ *   scores by smaller id, the same score bits), (-inf, -1) behind the selectable rows or groups.
+ *   after_scores (fp32 [Bq]) and after_ids (int32 [Bq]), both or neither, on the device: the list of query row q then starts
+ *   BEHIND the entry (after_scores[q], after_ids[q]) of that ordering - typically the last column of an earlier result, so
+ *   two calls with k = a and k = b give the columns [0, a) and [a, a + b) of one call with k = a + b.  The pair need not be
+ *   selectable any more (a row removed since: the list continues behind the place it had); after_ids[q] < 0 (the fill:
+ *   nothing lies behind it) gives the fill.  Grouped: the pair is a group's best row, as the grouped entries return it.
+ *   How: a (score, id) pair is one 64-bit key whose unsigned order is the result's order, so "below key X" is an exact,
+ *   stateless continuation point.  The list is built in pages of P = the longest list the streaming launch's LDS holds for
+ *   (E, products), at most 128 (127 for E = 1024, products = 3): ceil(k / P) pairs of launches, the streaming one keeping only
+ *   the keys below the last key of the page before (below the key of the after_* pair: one small launch in front builds
+ *   it), the merge writing its page at column offset and its last key to a device buffer - no host read between pages, no
+ *   atomics: capturable.  Without after_* the first page is the plain entry's launch.  Groups: the bound is applied to a
+ *   finished group's candidate, not to its rows, so no group returns through its second-best row.  Every page is one pass
+ *   over the gallery.
+ * ws: cc_similarity_topk_deep_workspace_bytes(Bq, Bg, E, products, k) bytes: the plain entry's workspace at min(k, P) plus
+ * 8 Bq bytes for the bounds - it does not grow with the number of pages (0 for arguments the entry refuses).
+ * Returns in this order, before anything is read: CC_ERR_INVALID (a NULL pointer other than the optional ones, Bq / Bg / E
+ * <= 0, k < 1, exactly one of m / s, with both n_total < 0 or stats_on_gallery other than 0 / 1, with a mask mask_rows
+ * other than 1 or Bq or mask_words < ceil(Bg / 32), exactly one of after_scores / after_ids), CC_ERR_UNSUPPORTED (k >
+ * CC_TOPK_DEEP_MAXK, products outside 1..3, E % 64 != 0, E > 1024, Bq > 16 * 65535), CC_ERR_WORKSPACE.  (The cap is a
+ * decision: 32 pages of 128, at most 64 launches a call.) */
+#define CC_TOPK_DEEP_MAXK 4096
+size_t cc_similarity_topk_deep_workspace_bytes(int32_t Bq, int32_t Bg, int32_t E, int32_t products, int32_t k);
+int cc_similarity_topk_deep_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                       float mult, int32_t products, int32_t k, const int32_t* row_mask, int32_t mask_rows,
+                                       int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery, int32_t n_total,
+                                       const int32_t* group_head, const float* after_scores, const int32_t* after_ids, float* scores,
+                                       int32_t* ids, void* ws, size_t ws_bytes, void* stream);
 /* Rank of a known row or group: where target[q] stands for query row q, without the matrix and without a list.  The arguments
  * are cc_similarity_topk_masked_planes_f32's where they coincide; row_mask == NULL: every row is selectable (mask_rows,
  * mask_words are then not looked at); m == s == NULL ranks S, both non-NULL the dual softmax D; group_head == NULL ranks rows.
