@@ -146,6 +146,16 @@ def _declare(lib):
     lib.cc_similarity_rank_planes_f32.argtypes = [vp, vp, i32, i32, i32, f32, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp,
                                                   vp, sz, vp]
     lib.cc_similarity_rank_planes_f32.restype = c.c_int
+    lib.cc_topk_merge_lists_f32.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    lib.cc_topk_merge_lists_f32.restype = c.c_int
+    lib.cc_similarity_target_score_planes_f32.argtypes = [vp, vp, i32, i32, i32, f32, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp,
+                                                          vp]
+    lib.cc_similarity_target_score_planes_f32.restype = c.c_int
+    lib.cc_similarity_count_workspace_bytes.argtypes = [i32, i32]
+    lib.cc_similarity_count_workspace_bytes.restype = sz
+    lib.cc_similarity_count_planes_f32.argtypes = [vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp,
+                                                   sz, vp]
+    lib.cc_similarity_count_planes_f32.restype = c.c_int
     for name in ("cc_token_norms_f32", "cc_pairwise_distance_f32", "cc_kmedoids_from_dist_f32",
                  "cc_batch_kmedoids_f32", "cc_token_cluster_f32", "cc_token_cluster_variant_f32",
                  "cc_token_aggregate_f32"):

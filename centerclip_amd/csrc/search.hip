@@ -61,6 +61,12 @@
 // group's candidate, never to a row - a group whose best row lies at or above the bound was handed out before and must not
 // return through its second-best row.  topk_merge_kernel writes a page at its column offset of the [Bq, k] result and its last
 // key to bound[q] for the page after it: the pages of a call hand over on the device.
+//
+// A gallery split in shards (each shard one buffer, searched and counted on its own; the results are those of the shards'
+// concatenation): topk_merge_lists_kernel merges the shards' lists, ties by smaller shard, then smaller local id - the order the
+// concatenated positions would give; rank_target_kernel behind an entry of its own gives the owner's t_q, and rank_stream_kernel's
+// COUNT mode counts a shard against that score and a `front` position the caller sets (the target's row on its owner, 0 on the
+// shards behind it, 2^31 - 1 on those in front): the counts of the shards add up to the counts of the whole.
 #include <type_traits>
 
 #include "cc_kernels.h"
@@ -682,7 +688,11 @@ __global__ __launch_bounds__(256) void rank_target_kernel(const _Float16* __rest
 // one without a selectable row - plus the carry at the range's end, in front = its row below the target group's head).  Plain
 // float compares, as rank_counts_kernel: -0 == +0, a NaN is neither greater nor equal.  A query row whose target is outside
 // [0, Bg) counts nothing.  At the end the 4 lanes of a query row and the 4 waves are added: part [Bq][3][slices].
-template <bool DSL, bool GROUPED, int MASK>
+// COUNT: a fourth compile-time mode - the bound comes from the caller instead of a target (cc_similarity_count_planes_f32):
+// `tscore` holds the bound's score and `target` the position in front of which an equal candidate counts as "in front", taken as
+// it is (no group_head look-up, no upper limit: a position at Bg or above puts every equal candidate in front; a negative one
+// makes the query row count nothing).  Without COUNT the kernel is the code it was.
+template <bool DSL, bool GROUPED, int MASK, bool COUNT = false>
 __global__ __launch_bounds__(256) void rank_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
                                                           int Bq, int Bg, int ld, int K, float sc, int slices,
                                                           const int* __restrict__ target, const float* __restrict__ tscore,
@@ -703,10 +713,10 @@ __global__ __launch_bounds__(256) void rank_stream_kernel(const _Float16* __rest
     const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
     const int qr = min(q0 + l15, Bq - 1);
     const int tg = target[qr];
-    const bool qvalid = q0 + l15 < Bq && tg >= 0 && tg < Bg;
+    const bool qvalid = q0 + l15 < Bq && tg >= 0 && (COUNT || tg < Bg);
     const float tq = tscore[qr];
     int front = tg;                                                                    // a candidate row below it lies in front
-    if constexpr (GROUPED) front = min(max(group_head[min(max(tg, 0), Bg - 1)], 0), tg);
+    if constexpr (GROUPED && !COUNT) front = min(max(group_head[min(max(tg, 0), Bg - 1)], 0), tg);
     int gt = 0, eq = 0, before = 0;
     float dm[4] = {0.f, 0.f, 0.f, 0.f}, ds[4] = {1.f, 1.f, 1.f, 1.f};
     if constexpr (DSL) {
@@ -826,6 +836,58 @@ __global__ __launch_bounds__(256) void rank_reduce_kernel(const int* __restrict_
     if (lane == 0) counts[i] = a;
 }
 
+// ---------------------------------------------------------------------------- the lists of several shards -> one list
+// S descending lists of k entries per query row (scores / ids [S][Bq][k]; id < 0: a fill, whatever its score) -> the first k of
+// their union.  An entry's place in the union's order is decided by (fills last; tk_key's score part: the ordered bits of
+// score + 0.0f, larger first; smaller shard; smaller local id - a fill: smaller index in its list), a strict total order over
+// all S k entries.  Every list is in that order already (the caller's precondition), so the entries of list t in front of an
+// entry form a prefix of t, a binary search finds its length, and the entry's output slot is its own index plus those
+// lengths over the other lists.  Slots are distinct and cover [0, S k): every slot below k has exactly one writer - no atomics,
+// no initialisation pass, no LDS.  One lane per entry, grid (query rows) x (blocks of 256 entries): one query row already
+// spreads over S k / 256 workgroups; a lane stops as soon as its slot reaches k (slots only grow), which is where most lanes
+// of a deep list end.  The score is written with the bits it came with (the sign of a zero included).
+struct TmEntry {
+    u64 major;                                                                         // 0: a fill; else 2^32 | ordered score bits
+    u64 minor;                                                                         // shard : 32 | local id (a fill: its index)
+};
+__device__ __forceinline__ TmEntry tm_entry(const float* __restrict__ scores, const int* __restrict__ ids, int64_t base, int s, int i) {
+    const int id = ids[base + i];
+    TmEntry e;
+    e.major = id < 0 ? 0 : ((u64)1 << 32) | cc_float_to_ordered_uint(scores[base + i] + 0.0f);
+    e.minor = ((u64)(unsigned)s << 32) | (unsigned)(id < 0 ? i : id);
+    return e;
+}
+__device__ __forceinline__ bool tm_in_front(const TmEntry& a, const TmEntry& b) {
+    return a.major > b.major || (a.major == b.major && a.minor < b.minor);
+}
+
+__global__ __launch_bounds__(256) void topk_merge_lists_kernel(const float* __restrict__ scores, const int* __restrict__ ids, int S, int Bq,
+                                                               int k, float* __restrict__ out_scores, long long* __restrict__ out_ids,
+                                                               int* __restrict__ out_src) {
+    const int q = blockIdx.x, e = blockIdx.y * 256 + threadIdx.x;
+    if (e >= S * k) return;                                                            // (no barrier below)
+    const int s = e / k, i = e - s * k;
+    const TmEntry mine = tm_entry(scores, ids, ((int64_t)s * Bq + q) * k, s, i);
+    int slot = i;
+    for (int t = 0; t < S && slot < k; ++t) {
+        if (t == s) continue;
+        const int64_t base = ((int64_t)t * Bq + q) * k;
+        int lo = 0, hi = k;                                                            // entries [0, lo) of list t lie in front
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;                                            // (< k: inside the list)
+            if (tm_in_front(tm_entry(scores, ids, base, t, mid), mine)) lo = mid + 1;
+            else hi = mid;
+        }
+        slot += lo;
+    }
+    if (slot >= k) return;
+    const int64_t o = (int64_t)q * k + slot, from = ((int64_t)s * Bq + q) * k + i;
+    const int id = ids[from];
+    out_scores[o] = id < 0 ? -INFINITY : scores[from];
+    out_ids[o] = id < 0 ? -1ll : (long long)(((u64)(unsigned)s << 32) | (unsigned)id);
+    out_src[o] = id < 0 ? -1 : e;
+}
+
 // The (m, s) pairs of the 16 video rows from blockIdx.y * 16 on over the text tiles of slice blockIdx.x (the tree: the file's
 // head).  part [slices][Bv] pairs.  The split of the text rows uses Bt alone.  MASKED: text_mask is one mask row over the text
 // rows (topk_stream_kernel's format); a row whose bit is 0 is treated as a row at Bt or above - neither its maximum nor its
@@ -928,10 +990,10 @@ int tk_page_len(int K) {
     while (page > 1 && tk_stream_lds(K, page) > TK_LDS_LIMIT) --page;
     return page;
 }
-template <int MASK>
+template <int MASK, bool COUNT = false>
 auto rank_stream_kernel_of(bool dsl, bool grouped) {
-    return grouped ? (dsl ? rank_stream_kernel<true, true, MASK> : rank_stream_kernel<false, true, MASK>)
-                   : (dsl ? rank_stream_kernel<true, false, MASK> : rank_stream_kernel<false, false, MASK>);
+    return grouped ? (dsl ? rank_stream_kernel<true, true, MASK, COUNT> : rank_stream_kernel<false, true, MASK, COUNT>)
+                   : (dsl ? rank_stream_kernel<true, false, MASK, COUNT> : rank_stream_kernel<false, false, MASK, COUNT>);
 }
 
 }  // namespace
@@ -1107,6 +1169,72 @@ int cc_similarity_rank_planes_f32(const void* query_planes, const void* gallery_
     CC_LAUNCH_CHECK();
     hipLaunchKernelGGL(rank_reduce_kernel, dim3((3 * Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, static_cast<const int*>(ws), slices, 3 * Bq,
                        counts);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+int cc_topk_merge_lists_f32(const float* scores, const int32_t* ids, int32_t S, int32_t Bq, int32_t k, float* out_scores,
+                            int64_t* out_ids, int32_t* out_src, void* stream) {
+    if (!scores || !ids || !out_scores || !out_ids || !out_src || S < 1 || Bq <= 0 || k < 1) return CC_ERR_INVALID;
+    if (S > CC_TOPK_MERGE_MAX_LISTS || k > CC_TOPK_DEEP_MAXK) return CC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(topk_merge_lists_kernel, dim3(Bq, (S * k + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), scores, ids,
+                       S, Bq, k, out_scores, reinterpret_cast<long long*>(out_ids), out_src);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+// the first launch of cc_similarity_rank_planes_f32 on its own: its checks, its kernel, its arguments
+int cc_similarity_target_score_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                          float mult, int32_t products, const int32_t* target, const int32_t* row_mask,
+                                          int32_t mask_rows, int32_t mask_words, const float* m, const float* s,
+                                          int32_t stats_on_gallery, int32_t n_total, const int32_t* group_head, float* score,
+                                          void* stream) {
+    const bool dsl = m || s, grouped = group_head != nullptr, masked = row_mask != nullptr;
+    if (!query_planes || !gallery_planes || !target || !score || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
+    if (dsl && (!m || !s || n_total < 0 || (stats_on_gallery != 0 && stats_on_gallery != 1))) return CC_ERR_INVALID;
+    if (masked && ((mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
+    if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
+    const int on_gallery = dsl ? stats_on_gallery : 0;
+    const float sc = mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, nt = dsl ? (float)n_total : 0.f;
+    const auto target_kernel = grouped ? (dsl ? rank_target_kernel<true, true> : rank_target_kernel<false, true>)
+                                       : (dsl ? rank_target_kernel<true, false> : rank_target_kernel<false, false>);
+    hipLaunchKernelGGL(target_kernel, dim3((Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E,
+                       products * E, sc, target, score, m, s, on_gallery, nt, group_head, row_mask, mask_rows == 1 ? 0 : mask_words);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+size_t cc_similarity_count_workspace_bytes(int32_t Bq, int32_t Bg) { return cc_similarity_rank_workspace_bytes(Bq, Bg); }
+
+// the counting pass and the reduce of cc_similarity_rank_planes_f32 against a bound the caller holds (rank_stream_kernel's
+// COUNT mode)
+int cc_similarity_count_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E, float mult,
+                                   int32_t products, const float* bound_scores, const int32_t* bound_front, const int32_t* row_mask,
+                                   int32_t mask_rows, int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery,
+                                   int32_t n_total, const int32_t* group_head, int32_t* counts, void* ws, size_t ws_bytes,
+                                   void* stream) {
+    const bool dsl = m || s, grouped = group_head != nullptr, masked = row_mask != nullptr;
+    if (!query_planes || !gallery_planes || !bound_scores || !bound_front || !counts || Bq <= 0 || Bg <= 0 || E <= 0)
+        return CC_ERR_INVALID;
+    if (dsl && (!m || !s || n_total < 0 || (stats_on_gallery != 0 && stats_on_gallery != 1))) return CC_ERR_INVALID;
+    if (masked && ((mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
+    if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
+    if ((Bq + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million query rows a call)
+    if (!ws || ws_bytes < cc_similarity_count_workspace_bytes(Bq, Bg)) return CC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int K = products * E, slices = tk_slices(Bq, Bg), on_gallery = dsl ? stats_on_gallery : 0;
+    const size_t smem = tk_stream_lds(K, 0);
+    const float sc = mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, nt = dsl ? (float)n_total : 0.f;
+    const auto kernel = !masked ? rank_stream_kernel_of<0, true>(dsl, grouped)
+                                : mask_rows == 1 ? rank_stream_kernel_of<1, true>(dsl, grouped) : rank_stream_kernel_of<2, true>(dsl, grouped);
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
+    hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
+                       static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K, sc,
+                       slices, bound_front, bound_scores, static_cast<int*>(ws), m, s, on_gallery, nt, group_head, row_mask, mask_words);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_reduce_kernel, dim3((3 * Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, static_cast<const int*>(ws), slices,
+                       3 * Bq, counts);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }

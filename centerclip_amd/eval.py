@@ -278,7 +278,8 @@ def eval_epoch(model, test_dataloader, device, args=None, log=None, shard=False,
     ``matrix_free`` (not in the reference; GPU only, single process): the metrics come from ``matrix_free_metrics`` - the rank of
     every ground-truth row counted on a stream over the cached operand rows, no [Nt, Nv] matrix.  Off by default: at evaluation
     sizes the matrix is small and its path faster.  With ``shard=True`` in a process group of more than one rank: ValueError
-    (ranks across the ranks of a process group are out of scope)."""
+    (here ranks across the ranks of a process group are out of scope; a gallery split over the ranks ranks across them:
+    ``search_sharded.ShardedGallery``)."""
     log = log or (lambda s: None)
     if matrix_free and shard and ccdist.world_size() > 1:
         raise ValueError("eval_epoch(matrix_free=True) ranks on one process: with shard=True over %d ranks it is out of scope "

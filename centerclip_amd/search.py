@@ -687,13 +687,18 @@ class FeatureGallery:
         want = self._label_list(target, "rank_groups")
         if want.size != nq:
             raise ValueError("FeatureGallery.rank_groups: %d target labels for %d queries (one label per query)" % (want.size, nq))
+        heads = self._group_heads(want)
+        if (heads < 0).any():
+            raise ValueError("FeatureGallery.rank_groups: no row held has the label %d" % int(want[heads < 0][0]))
+        return heads
+
+    def _group_heads(self, want):
+        """labels int64 [n] -> the positions of their groups' heads, -1 for a label no row carries (it never raises: a shard
+        of a ShardedGallery is asked for labels another shard holds)"""
         held = self.labels.numpy()                               # (removed rows keep their label until compact())
         first = np.flatnonzero(np.concatenate(([True], held[1:] != held[:-1]))) if held.size else np.zeros(0, dtype=np.int64)
         head_of = dict(zip(held[first].tolist(), first.tolist()))                      # (a label never returns: one label, one run)
-        missing = [v for v in want.tolist() if v not in head_of]
-        if missing:
-            raise ValueError("FeatureGallery.rank_groups: no row held has the label %d" % missing[0])
-        return np.array([head_of[v] for v in want.tolist()], dtype=np.int64)
+        return np.array([head_of.get(v, -1) for v in want.tolist()], dtype=np.int64)
 
     def _rank_rows(self, q, target, groups=False, allow=None):
         """(ranks int64 [Nq], scores fp32 [Nq], counts int32 [Nq, 3]) of the targets among the rows (groups) ``_search_rows``

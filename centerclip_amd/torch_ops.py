@@ -1541,6 +1541,153 @@ def _(query_planes, gallery_planes, n_gallery, mult, products, target, row_mask=
             query_planes.new_empty((query_planes.shape[0],), dtype=torch.float32))
 
 
+TOPK_MERGE_MAX_LISTS = 64      # CC_TOPK_MERGE_MAX_LISTS
+
+
+def _check_topk_merge(scores, ids):
+    name = "similarity_topk_merge"
+    if scores.dim() != 3 or tuple(ids.shape) != tuple(scores.shape) or scores.dtype != torch.float32 or ids.dtype != torch.int32:
+        raise ValueError("%s: scores %s %s and ids %s %s are not fp32 / int32 lists [S, Bq, k]"
+                         % (name, tuple(scores.shape), scores.dtype, tuple(ids.shape), ids.dtype))
+    if scores.device != ids.device:
+        raise ValueError("%s: scores on %s, ids on %s" % (name, scores.device, ids.device))
+    S, _, k = scores.shape
+    if not 1 <= S <= TOPK_MERGE_MAX_LISTS:
+        raise ValueError("%s: 1 <= S <= %d lists, not %d" % (name, TOPK_MERGE_MAX_LISTS, S))
+    if not 1 <= k <= TOPK_DEEP_MAXK:
+        raise ValueError("%s: 1 <= k <= %d, not %d" % (name, TOPK_DEEP_MAXK, k))
+
+
+@custom_op(NS + "::similarity_topk_merge", mutates_args=(), device_types="cuda")
+def similarity_topk_merge(scores: torch.Tensor, ids: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The lists of S shards -> the list of their concatenation.  scores fp32 / ids int32 [S, Bq, k]: per shard what
+    similarity_topk* return for the same queries and the same k (descending, equal scores by smaller id, id -1 = the fill),
+    1 <= S <= 64, 1 <= k <= 4096 -> (scores [Bq, k] fp32, ids [Bq, k] int64 = (shard << 32) | id, src [Bq, k] int32 =
+    shard * k + index of the entry taken): larger score first (-0 == +0, the bits kept), equal scores by smaller shard, then
+    smaller id; the fill (-inf, -1, -1) last.  ``src`` gathers any payload that travels with the entries (labels).  One
+    launch, no host read.  Bq == 0 returns without a launch.  cc_topk_merge_lists_f32."""
+    _check_topk_merge(scores, ids)
+    S, Bq, k = scores.shape
+    out_scores = _e(Bq, k, like=scores, dtype=torch.float32)
+    out_ids = _e(Bq, k, like=scores, dtype=torch.int64)
+    out_src = _e(Bq, k, like=scores, dtype=torch.int32)
+    if Bq == 0:
+        return out_scores, out_ids, out_src
+    scores, ids = scores.contiguous(), ids.contiguous()
+    L.check(L.lib().cc_topk_merge_lists_f32(L.ptr(scores), L.ptr(ids), S, Bq, k, L.ptr(out_scores), L.ptr(out_ids), L.ptr(out_src),
+                                            _st(scores)), "cc_topk_merge_lists_f32")
+    return out_scores, out_ids, out_src
+
+
+@similarity_topk_merge.register_fake
+def _(scores, ids):
+    _check_topk_merge(scores, ids)
+    _, Bq, k = scores.shape
+    return (scores.new_empty((Bq, k), dtype=torch.float32), scores.new_empty((Bq, k), dtype=torch.int64),
+            scores.new_empty((Bq, k), dtype=torch.int32))
+
+
+def _check_per_query(name, what, t, dtypes, planes):
+    if t.dtype not in dtypes or t.dim() != 1 or t.shape[0] != planes.shape[0] or t.device != planes.device:
+        raise ValueError("%s: %s %s %s on %s is not one %s per query row (%d) on %s"
+                         % (name, what, tuple(t.shape), t.dtype, t.device, " / ".join(str(d).replace("torch.", "") for d in dtypes),
+                            planes.shape[0], planes.device))
+
+
+def _check_target_score(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head):
+    name = "similarity_target_score"
+    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head, name)
+    _check_per_query(name, "target", target, (torch.int32, torch.int64), query_planes)
+    return E3
+
+
+@custom_op(NS + "::similarity_target_score", mutates_args=(), device_types="cuda")
+def similarity_target_score(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                            target: torch.Tensor, row_mask: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None,
+                            s: Optional[torch.Tensor] = None, stats_on_gallery: int = 1, n_total: int = 0,
+                            group_head: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """similarity_rank's score alone: [Bq] fp32, the score of gallery row target[q] for query row q (with group_head: of the
+    best selectable row of the target's group, -inf without one), the bits similarity_topk* give the pair; a target outside
+    [0, n_gallery) - a row another shard holds - gives -inf.  Arguments as similarity_rank.  One launch; Bq == 0 or
+    n_gallery == 0: none.  cc_similarity_target_score_planes_f32."""
+    Bq = query_planes.shape[0]
+    E3 = _check_target_score(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head)
+    score = _e(Bq, like=query_planes, dtype=torch.float32)
+    if Bq == 0:
+        return score
+    if int(n_gallery) == 0:                                 # no row: every target is outside
+        return score.fill_(float("-inf"))
+    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
+    if m is not None:
+        m, s = m.contiguous(), s.contiguous()
+    target = target.to(torch.int32).contiguous()
+    masked = row_mask is not None
+    L.check(L.lib().cc_similarity_target_score_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
+                                                          float(mult), int(products), L.ptr(target), L.ptr(row_mask),
+                                                          (1 if row_mask.dim() == 1 else Bq) if masked else 0,
+                                                          int(row_mask.shape[-1]) if masked else 0, L.ptr(m), L.ptr(s),
+                                                          int(stats_on_gallery), int(n_total), L.ptr(group_head), L.ptr(score),
+                                                          _st(query_planes)), "cc_similarity_target_score_planes_f32")
+    return score
+
+
+@similarity_target_score.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, target, row_mask=None, m=None, s=None, stats_on_gallery=1,
+      n_total=0, group_head=None):
+    _check_target_score(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head)
+    return query_planes.new_empty((query_planes.shape[0],), dtype=torch.float32)
+
+
+def _check_count(query_planes, gallery_planes, n_gallery, bound_scores, bound_front, row_mask, m, s, stats_on_gallery, group_head):
+    name = "similarity_count"
+    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head, name)
+    _check_per_query(name, "bound_scores", bound_scores, (torch.float32,), query_planes)
+    _check_per_query(name, "bound_front", bound_front, (torch.int32,), query_planes)
+    return E3
+
+
+@custom_op(NS + "::similarity_count", mutates_args=(), device_types="cuda")
+def similarity_count(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                     bound_scores: torch.Tensor, bound_front: torch.Tensor, row_mask: Optional[torch.Tensor] = None,
+                     m: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None, stats_on_gallery: int = 1,
+                     n_total: int = 0, group_head: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """similarity_rank's counting pass against a bound the caller holds -> counts [Bq, 3] int32: the candidates of query row q
+    (the selectable rows; with group_head the groups that have one, each by its best row) with a score above bound_scores[q],
+    equal to it, and equal to it at a position (the row; the group's best row) below bound_front[q].  bound_scores fp32 [Bq],
+    bound_front int32 [Bq]: negative - the row counts nothing; n_gallery or more (up to 2^31 - 1) - every equal candidate is in
+    front.  Plain float compares: -0 == +0, a NaN bound counts nothing.  The counts of the parts of a gallery split in two
+    add up to those of the whole.  Bq == 0 or n_gallery == 0 (zeros): no launch.  cc_similarity_count_planes_f32."""
+    Bq = query_planes.shape[0]
+    E3 = _check_count(query_planes, gallery_planes, n_gallery, bound_scores, bound_front, row_mask, m, s, stats_on_gallery,
+                      group_head)
+    counts = _e(Bq, 3, like=query_planes, dtype=torch.int32)
+    if Bq == 0:
+        return counts
+    if int(n_gallery) == 0:                                 # no row: nothing to count
+        return counts.zero_()
+    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
+    if m is not None:
+        m, s = m.contiguous(), s.contiguous()
+    bound_scores, bound_front = bound_scores.contiguous(), bound_front.contiguous()
+    lib = L.lib()
+    ws = L.workspace(lib.cc_similarity_count_workspace_bytes(Bq, int(n_gallery)), query_planes.device)
+    masked = row_mask is not None
+    L.check(lib.cc_similarity_count_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3, float(mult),
+                                               int(products), L.ptr(bound_scores), L.ptr(bound_front), L.ptr(row_mask),
+                                               (1 if row_mask.dim() == 1 else Bq) if masked else 0,
+                                               int(row_mask.shape[-1]) if masked else 0, L.ptr(m), L.ptr(s), int(stats_on_gallery),
+                                               int(n_total), L.ptr(group_head), L.ptr(counts), L.ptr(ws), ws.numel(),
+                                               _st(query_planes)), "cc_similarity_count_planes_f32")
+    return counts
+
+
+@similarity_count.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, bound_scores, bound_front, row_mask=None, m=None, s=None,
+      stats_on_gallery=1, n_total=0, group_head=None):
+    _check_count(query_planes, gallery_planes, n_gallery, bound_scores, bound_front, row_mask, m, s, stats_on_gallery, group_head)
+    return query_planes.new_empty((query_planes.shape[0], 3), dtype=torch.int32)
+
+
 def _check_masked_stats(text_planes, video_planes, n_text, n_video, text_mask):
     name = "dsl_col_stats_planes_masked"
     E3 = _check_plane_pair(name, video_planes, text_planes, n_text)
@@ -1855,7 +2002,8 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
        "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
        "similarity_topk_grouped", "similarity_topk_grouped_dsl", "similarity_topk_masked", "dsl_col_stats_planes_masked",
-       "pack_row_mask", "similarity_rank", "similarity_topk_deep")
+       "pack_row_mask", "similarity_rank", "similarity_topk_deep", "similarity_topk_merge", "similarity_target_score",
+       "similarity_count")
 
 
 def logit_multiplier(logit_scale):

@@ -936,6 +936,51 @@ int cc_similarity_rank_planes_f32(const void* query_planes, const void* gallery_
                                   int32_t products, const int32_t* target, const int32_t* row_mask, int32_t mask_rows,
                                   int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery, int32_t n_total,
                                   const int32_t* group_head, int32_t* counts, float* score, void* ws, size_t ws_bytes, void* stream);
+/* A gallery split in shards (centerclip_amd/search_sharded.py; DESIGN.md, "Sharded gallery"): the three pieces that turn the
+ * per-shard results of the entries above into the result of the concatenated gallery.  None reads anything on the host, none
+ * uses atomics: capturable.
+ *
+ * cc_topk_merge_lists_f32: S descending lists per query row -> one.  scores fp32 / ids int32 [S][Bq][k], ids local to their
+ * shard, id < 0 = a fill (its score is not looked at); 1 <= S <= CC_TOPK_MERGE_MAX_LISTS, 1 <= k <= CC_TOPK_DEEP_MAXK.
+ *   out_scores fp32 [Bq][k], out_ids int64 [Bq][k] = ((int64)shard << 32) | id (-1: fill, score -inf), out_src int32 [Bq][k] =
+ *   shard * k + index of the entry taken (-1: fill) - the caller gathers labels or any other payload with it.
+ *   Order: larger score first, compared as the top-k entries' key does (the ordered bits of score + 0.0f: -0 and +0 are
+ *   equal; the score leaves with the bits it came with), equal scores by smaller shard, then smaller id; fills last.
+ *   Precondition, not checked: every input list is in that order (what the top-k entries return).  A violated precondition
+ *   gives an unspecified selection, never an access outside the buffers.
+ *   How: the keys are unique, so an entry's output slot is its own index plus, for each other list, the number of that list's
+ *   entries in front of it - a binary search per list; one lane per entry, ceil(S k / 256) workgroups per query row.
+ *   Returns CC_ERR_INVALID (a NULL pointer, S < 1, Bq <= 0, k < 1), then CC_ERR_UNSUPPORTED (S or k above its cap); there is
+ *   no workspace.
+ *
+ * cc_similarity_target_score_planes_f32: the first launch of cc_similarity_rank_planes_f32 alone - score[q] = t_q of target[q]
+ * (rows; with group_head the best selectable row of the target's group, -inf without one; with m, s the dual softmax, on
+ * either side); a target outside [0, Bg): -inf.  Arguments, limits and the order of the refusals are that entry's, without
+ * counts and workspace (CC_ERR_INVALID, then CC_ERR_UNSUPPORTED).
+ *
+ * cc_similarity_count_planes_f32: its counting pass against a bound the caller holds.  Over the candidates of query row q -
+ * the selectable rows, or with group_head the groups that have one, each by its best row - with score x:
+ *   counts[q] = (#{x > bound_scores[q]}, #{x == bound_scores[q]}, #{x == bound_scores[q], position < bound_front[q]}),
+ * position = the row, or the group's best row.  bound_front[q] < 0: (0, 0, 0); bound_front[q] >= Bg: every equal candidate is
+ * in front.  Plain float compares (-0 == +0; a NaN bound counts nothing).  Integers over a stream that any split of the
+ * gallery partitions: the counts of the parts add up to the counts of the whole - with the bound a target's score from
+ * cc_similarity_target_score_planes_f32 and bound_front its row (its group's head), the sum is cc_similarity_rank_planes_f32's
+ * counts.  Two launches (the rank entry's second and third).  ws: cc_similarity_count_workspace_bytes(Bq, Bg) bytes (0 for
+ * Bq <= 0 or Bg <= 0).  Returns in the rank entry's order: CC_ERR_INVALID, CC_ERR_UNSUPPORTED, CC_ERR_WORKSPACE. */
+#define CC_TOPK_MERGE_MAX_LISTS 64
+int cc_topk_merge_lists_f32(const float* scores, const int32_t* ids, int32_t S, int32_t Bq, int32_t k, float* out_scores,
+                            int64_t* out_ids, int32_t* out_src, void* stream);
+int cc_similarity_target_score_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
+                                          float mult, int32_t products, const int32_t* target, const int32_t* row_mask,
+                                          int32_t mask_rows, int32_t mask_words, const float* m, const float* s,
+                                          int32_t stats_on_gallery, int32_t n_total, const int32_t* group_head, float* score,
+                                          void* stream);
+size_t cc_similarity_count_workspace_bytes(int32_t Bq, int32_t Bg);
+int cc_similarity_count_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E, float mult,
+                                   int32_t products, const float* bound_scores, const int32_t* bound_front, const int32_t* row_mask,
+                                   int32_t mask_rows, int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery,
+                                   int32_t n_total, const int32_t* group_head, int32_t* counts, void* ws, size_t ws_bytes,
+                                   void* stream);
 int cc_video_pool_normalize_f32(const float* visual, const int64_t* video_mask, int32_t Bv, int32_t Tn,
                                 int32_t E, float* pooled, void* stream);
 int cc_loose_similarity_f32(const float* text, const float* visual, const int64_t* video_mask,
