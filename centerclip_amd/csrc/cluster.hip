@@ -65,8 +65,11 @@ __global__ __launch_bounds__(256) void token_norm_kernel(const float* __restrict
 
 // ============================================================================ K1
 // 64x64 tile of the Gram matrix of one problem per 256-thread workgroup (4 waves, 32x32 per wave, 2x2 accumulator
-// fragments).  Only tiles with tj >= ti are launched; the transposed tile is written by the same workgroup
-// (g_ij == g_ji bit for bit: same k order, commutative products).
+// fragments).  Only tiles with tj >= ti are launched; the transposed tile is written by the same workgroup, and inside the
+// 16x16 fragments on the diagonal - the only place where both (i, j) and (j, i) are computed - the element above the diagonal
+// is stored to both places: D is symmetric bit for bit.  (g_ij and g_ji are NOT the same bits there on generic floats: the
+// chain adds hi_i.lo_j before lo_i.hi_j for one and after it for the other, and the cosine epilogue multiplies by iv_i first.
+// The squared-L2 affinity of the spectral path keeps both elements as computed: its epilogue is asymmetric by definition.)
 //
 // Arithmetic: every fp32 token element x is split, while it is staged, into two fp16 values hi = fp16(x) and
 // lo = fp16(x - hi) (x = hi + lo to 22 bits), and x.y is accumulated in fp32 as hi.hi + hi.lo + lo.hi on the fp16
@@ -286,7 +289,7 @@ __global__ __launch_bounds__(256) void gram_dist_kernel(const float* __restrict_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int i = ti * GT + wr * 32 + fm * 16 + g * 4 + r;
-                    if (i < N && j < N) {
+                    if (i < N && j < N && !(METRIC != CC_METRIC_SQL2 && dblock && i > j)) {
                         const float gij = acc[fm][fn][r];
                         const float sqi = own_norms ? lsq[i - ti * GT] : sq[i], sqj = own_norms ? lsq[GT + j - tj * GT] : sq[j];
                         float d;
@@ -302,7 +305,7 @@ __global__ __launch_bounds__(256) void gram_dist_kernel(const float* __restrict_
                         }
                         lmax = fmaxf(lmax, d);
                         Dp[(int64_t)i * N + j] = d;
-                        if (mirror || (dblock && fm == 0 && fn == 1)) Dp[(int64_t)j * N + i] = d;
+                        if (mirror || (dblock && (METRIC != CC_METRIC_SQL2 ? i < j : fm == 0 && fn == 1))) Dp[(int64_t)j * N + i] = d;
                     }
                 }
             }

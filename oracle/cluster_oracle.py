@@ -425,14 +425,266 @@ def exact_zero_diag_distance(X, metric="euclidean", p=2.0, chunk_max=None):
         d = (diff ** p).sum(-1) ** (1.0 / p) if p != 1.0 else diff.sum(-1)
         d = d.astype(np.float32)
     else:
-        nrm = np.sqrt((X.astype(np.float64) ** 2).sum(-1)).astype(np.float32) + np.float32(1e-6)
+        # the kernel's epilogue: 1 - (g * iv_i) * iv_j with iv = 1 / (sqrtf(sq) + 1e-6f), formed for i <= j and mirrored
+        # (until the generic-float tests this branch divided by the norms instead, which no kernel does and no test used)
+        sq = (X.astype(np.float64) ** 2).sum(-1).astype(np.float32)
+        iv = np.float32(1.0) / (np.sqrt(sq, dtype=np.float32) + np.float32(1e-6))
         g = np.einsum("bnw,bmw->bnm", X.astype(np.float64), X.astype(np.float64)).astype(np.float32)
-        d = np.float32(1.0) - g / nrm[:, :, None] / nrm[:, None, :]
+        d = np.float32(1.0) - (g * iv[:, :, None]) * iv[:, None, :]
+        d = np.triu(d) + np.swapaxes(np.triu(d, 1), -1, -2)
     mx = np.float32(d.max() if chunk_max is None else chunk_max)
     d = (d - mx) - np.float32(1.0)
     idx = np.arange(d.shape[-1])
     d[:, idx, idx] -= np.float32(1.0)
     return d.astype(np.float32)
+
+
+# ------------------------------------------------- the distance kernels on generic floats: emulation, float64, bounds
+U32 = 2.0 ** -24          # unit roundoff of fp32 (half an ulp, relative)
+_GT = 64                  # Gram tile (rows, columns and k-slice) of gram_dist_kernel
+_MFMA_K = 32              # products one v_mfma_f32_16x16x32_f16 adds to an accumulator element
+GRAM_DROPS = ("lo", "hi_lo", "lo_hi", "kslice", "mirror")
+
+
+def split_hi_lo(X):
+    """split_store of gram_dist_kernel: hi = fp16(x), lo = fp16(x - hi), both round-to-nearest-even (x - hi is exact in
+    fp32; fp16 subnormals are kept).  -> (hi, lo) as float16."""
+    X = np.asarray(X, dtype=np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        hi = X.astype(np.float16)
+        lo = (X - hi.astype(np.float32)).astype(np.float16)
+    return hi, lo
+
+
+def _bt(a):
+    return np.swapaxes(a, -1, -2)
+
+
+def _kernel_row_sq(X, accumulate):
+    """Sum of squares of every token as gram_dist_kernel's own_norms path forms it.  "f64": float64 sum rounded once.
+    Otherwise literally: thread c of the 16 that stage a row owns elements 4c..4c+3 of every 64-wide k-slice and runs
+    one fmaf chain over them in ascending k; the 16 partial sums meet in a balanced 4-step tree (quad swaps, half mirror,
+    mirror).  (The fmaf is formed as a float64 multiply-add rounded to fp32: x*x is exact in float64.)"""
+    X = np.asarray(X, dtype=np.float32)
+    if accumulate == "f64":
+        return (X.astype(np.float64) ** 2).sum(-1).astype(np.float32)
+    B, N, W = X.shape
+    nk = -(-W // _GT)
+    Xp = np.zeros((B, N, nk * _GT), np.float64)
+    Xp[..., :W] = X
+    v = Xp.reshape(B, N, nk, 16, 4)
+    acc = np.zeros((B, N, 16), np.float32)
+    for kt in range(nk):
+        for e in range(4):
+            acc = (acc.astype(np.float64) + v[:, :, kt, :, e] ** 2).astype(np.float32)
+    while acc.shape[-1] > 1:
+        acc = acc[..., 0::2] + acc[..., 1::2]
+    return acc[..., 0]
+
+
+def _kernel_gram(hi, lo, accumulate, drop):
+    """g = sum_k hi.hi + hi.lo + lo.hi in the kernel's chain order: per 32-wide k block the three planes one after the other.
+    "f64": float64 accumulation, rounded once.  "f32_asc" / "f32_desc": fp32 accumulator, one rounding per product, the 32
+    products of a block in ascending / descending k (two of the orders a matrix-core instruction could use)."""
+    H, L = hi.astype(np.float64), lo.astype(np.float64)
+    W = H.shape[-1]
+    if drop == "lo":
+        L = np.zeros_like(L)
+    if drop == "kslice":                                    # the last 64-wide k-slice never reaches the matrix cores
+        keep = (-(-W // _GT) - 1) * _GT
+        H, L = H[..., :keep], L[..., :keep]
+        W = keep
+    planes = [(H, H)] + ([] if drop == "hi_lo" else [(H, L)]) + ([] if drop == "lo_hi" else [(L, H)])
+    if accumulate == "f64":
+        return sum(np.matmul(a, _bt(b)) for a, b in planes).astype(np.float32)
+    acc = np.zeros(H.shape[:2] + (H.shape[1],), np.float32)
+    for k0 in range(0, W, _MFMA_K):
+        ks = range(k0, min(W, k0 + _MFMA_K))
+        for a, b in planes:
+            for k in (ks if accumulate == "f32_asc" else reversed(ks)):
+                acc = acc + (a[:, :, None, k] * b[:, None, :, k]).astype(np.float32)    # fp16 x fp16: exact in fp32
+    return acc
+
+
+def emulated_gram_distance(X, metric="euclidean", chunk_max=None, drop=None, accumulate="f64", shift=True):
+    """gram_dist_kernel's documented arithmetic (the comment above the kernel and its epilogue) restated in numpy:
+    the fp16 hi / lo split of every element, g = sum(hi.hi + hi.lo + lo.hi) (lo.lo dropped), row norms sum x^2 of the fp32
+    values, then the fp32 epilogue literally - euclidean: sqrtf(max((sq_i + sq_j) - 2 g, 0)) with an exact-zero diagonal;
+    cosine: 1 - (g * iv_i) * iv_j, iv = 1 / (sqrtf(sq) + 1e-6f), evaluated for i <= j and mirrored (the kernel stores D
+    symmetric) - and, with ``shift``, (d - max) - 1 with the maximum of the whole batch handed in (or ``chunk_max``) and
+    another - 1 on the diagonal.  X [B,N,W] -> D [B,N,N] fp32.
+
+    ``accumulate``: "f64" (default) sums in float64 and rounds once: on fp16-exact inputs that IS the kernel's value.
+    "f32_asc" / "f32_desc" accumulate in fp32 with one rounding per product (see _kernel_gram) and form the row norms
+    with the kernel's fmaf chain and lane tree.
+    ``drop`` - deliberately broken variants, for the host test of the error bound only: "lo" (lo plane zero), "hi_lo" /
+    "lo_hi" (that product plane missing), "kslice" (the last 64-wide k-slice ignored), "mirror" (one element below the
+    diagonal per off-diagonal 64 x 64 tile, and one per mirrored 32 x 32 block of a diagonal tile, taken from the fragment
+    row next to the right one)."""
+    assert metric in METRICS and drop in (None,) + GRAM_DROPS
+    f = np.float32
+    X = np.asarray(X, dtype=f)
+    B, N, W = X.shape
+    hi, lo = split_hi_lo(X)
+    g = _kernel_gram(hi, lo, accumulate, drop)
+    sq = _kernel_row_sq(X, accumulate)
+    idx = np.arange(N)
+    with np.errstate(invalid="ignore", over="ignore"):
+        if metric == "euclidean":
+            d2 = (sq[:, :, None] + sq[:, None, :]) - f(2.0) * g
+            d = np.sqrt(np.maximum(d2, f(0.0)), dtype=f)
+            d[:, idx, idx] = f(0.0)
+        else:
+            iv = f(1.0) / (np.sqrt(sq, dtype=f) + f(1e-6))
+            d = f(1.0) - (g * iv[:, :, None]) * iv[:, None, :]
+    d = np.triu(d) + _bt(np.triu(d, 1))
+    if drop == "mirror":
+        for t0 in range(0, N, _GT):
+            if t0 + 32 < N:                                            # block (0, 1) of the diagonal tile
+                d[:, t0 + 32, t0] = d[:, t0 + 1, t0 + 32]
+            for t1 in range(t0 + _GT, N, _GT):
+                d[:, t1, t0] = d[:, t0 + 1, t1]
+    d = d.astype(f)
+    if shift:
+        mx = f(d.max() if chunk_max is None else chunk_max)
+        d = (d - mx) - f(1.0)
+        d[:, idx, idx] -= f(1.0)
+    return d
+
+
+def float64_distance(X, metric="euclidean", p=2.0):
+    """The distance the reference defines (cluster_utils.py:22-30), on the fp32 tokens, in float64 and from differences
+    (no Gram cancellation): |x_i - x_j|_p, or 1 - x_i.x_j / ((|x_i| + 1e-6)(|x_j| + 1e-6)).  X [B,N,W] -> [B,N,N] float64."""
+    X = np.asarray(X, dtype=np.float64)
+    if metric == "cosine":
+        n = np.sqrt((X ** 2).sum(-1)) + 1e-6
+        return 1.0 - np.matmul(X, _bt(X)) / (n[:, :, None] * n[:, None, :])
+    B, N, W = X.shape
+    out = np.empty((B, N, N))
+    for i in range(N):
+        diff = np.abs(X[:, i:i + 1, :] - X)
+        if np.isinf(p):
+            out[:, i] = diff.max(-1)
+        elif p == 2.0:
+            out[:, i] = np.sqrt((diff * diff).sum(-1))
+        elif p == 1.0:
+            out[:, i] = diff.sum(-1)
+        else:
+            out[:, i] = (diff ** p).sum(-1) ** (1.0 / p)
+    return out
+
+
+def gram_error_bound(X, metric="euclidean"):
+    """Bound on |d_kernel - float64_distance| for every pair, before the shift, derived from the kernel's arithmetic
+    (emulated_gram_distance) term by term in float64 - a running-error bound, nothing in it is fitted to an output.
+    u = 2^-24.  X [B,N,W] -> [B,N,N] float64.
+
+    Error of g against sum x_i x_j:
+      * split residual r = x - hi - lo (zero unless lo was rounded, i.e. in fp16's subnormal range):
+        sum |r_i||x_j| + |hi_i + lo_i||r_j|;
+      * the dropped plane, |sum lo_i lo_j| - its value, it is known;
+      * fp32 accumulation.  The accumulator runs through 3 * ceil(W / 32) chained matrix-core instructions, each adding
+        32 products (fp16 x fp16, exact).  How v_mfma_f32_16x16x32_f16 orders and rounds the additions inside one
+        instruction is not documented anywhere we can read and has not been measured, so the worst case is ASSUMED: one
+        fp32 rounding per product, 32 per instruction, in an unknown order.  Every partial sum inside instruction b is at
+        most |S_(b-1)| + A_b in magnitude (S the exact sum of the blocks before it, in the kernel's block order; A_b the
+        sum of the block's |products|), so the instruction adds at most 32 u (|S_(b-1)| + A_b) - the partial sums enter by
+        their running magnitude, not by sum |terms|.  The total is inflated by 1 + 2 n u (n = all additions) for the
+        second-order terms (computed partial sums instead of exact ones).
+    Row norms: 4 ceil(W / 64) chained fmaf per thread and a 4-step lane tree over non-negative terms: (4 ceil(W / 64) + 4) u sq.
+    Epilogue, euclidean: rounding of sq_i + sq_j and of the subtraction, Delta = all of the above on d^2; then
+    |sqrt(a) - sqrt(b)| <= min(Delta / (d + sqrt(max(d^2 - Delta, 0))), sqrt(Delta)) - the first form tends to Delta / (2 d)
+    and the second keeps near-duplicate tokens from dividing by zero (it also covers the clamp at 0) -, plus sqrtf's own
+    rounding.  The diagonal is exact (bound 0).  Cosine: relative error of iv = that of sq / 2 + 4 u (sqrtf, the addition
+    of 1e-6f, a reciprocal allowed one ulp), two multiplications and the final subtraction; first-order terms inflated by
+    1 + 2^-10 (every relative error here is far below 2^-12)."""
+    assert metric in METRICS
+    u = U32
+    X32 = np.asarray(X, dtype=np.float32)
+    X64 = X32.astype(np.float64)
+    B, N, W = X64.shape
+    hi, lo = split_hi_lo(X32)
+    H, L = hi.astype(np.float64), lo.astype(np.float64)
+    XS = H + L
+    R = X64 - XS
+    e_split = np.matmul(np.abs(R), _bt(np.abs(X64))) + np.matmul(np.abs(XS), _bt(np.abs(R)))
+    e_lolo = np.abs(np.matmul(L, _bt(L)))
+    S = np.zeros((B, N, N))
+    e_acc = np.zeros((B, N, N))
+    n_add = 0
+    for k0 in range(0, W, _MFMA_K):
+        sl = slice(k0, min(W, k0 + _MFMA_K))
+        for a, b in ((H, H), (H, L), (L, H)):
+            a_, b_ = a[:, :, sl], b[:, :, sl]
+            e_acc += _MFMA_K * u * (np.abs(S) + np.matmul(np.abs(a_), _bt(np.abs(b_))))
+            S += np.matmul(a_, _bt(b_))
+            n_add += _MFMA_K
+    e_acc *= 1.0 + 2.0 * n_add * u
+    absg = np.matmul(np.abs(X64), _bt(np.abs(X64)))
+    dg = e_split + e_lolo + e_acc + W * 2.0 ** -52 * absg            # (last: the float64 reference's own rounding)
+    sq = (X64 ** 2).sum(-1)
+    e_sq = (4 * -(-W // _GT) + 4) * u * sq * (1.0 + 64 * u)
+    if metric == "euclidean":
+        d64 = float64_distance(X32, "euclidean")
+        ssum = sq[:, :, None] + sq[:, None, :]
+        delta = e_sq[:, :, None] + e_sq[:, None, :] + 2.0 * dg
+        delta = delta + u * (ssum + delta)                            # fl(sq_i + sq_j)
+        delta = delta + u * (d64 ** 2 + delta)                        # fl(. - 2 g)
+        bd = np.minimum(delta / np.maximum(d64 + np.sqrt(np.maximum(d64 ** 2 - delta, 0.0)), 1e-300), np.sqrt(delta))
+        bd = bd + u * (d64 + bd)                                      # sqrtf
+        idx = np.arange(N)
+        bd[:, idx, idx] = 0.0
+        return bd
+    n = np.sqrt(sq)
+    e_iv = 0.5 * e_sq / np.maximum(sq, 1e-300) + 4.0 * u + 1e-13 / np.maximum(n, 1e-300)
+    den = (n[:, :, None] + 1e-6) * (n[:, None, :] + 1e-6)
+    c64 = np.matmul(X64, _bt(X64)) / den
+    bc = dg / den + np.abs(c64) * (e_iv[:, :, None] + e_iv[:, None, :] + 2.0 * u)
+    bc = bc * (1.0 + 2.0 ** -10)
+    return bc + u * (np.abs(1.0 - c64) + bc)
+
+
+POWF_ULPS = 4.0           # allowance for one powf call, in ulps of its result (ROCm's device library documents 1)
+
+
+def minkowski_error_bound(X, p):
+    """Bound on |d_kernel - float64_distance(p)| for lp_dist_kernel, per pair; X [B,N,W] -> [B,N,N] float64.  u = 2^-24.
+    The kernel forms t_k = powf(|x_k - y_k|, p) (p = 1: |x_k - y_k| itself), adds the t_k to an fp32 accumulator one by one
+    in ascending k, and ends with powf(sum, 1 / p).  Terms: the fp32 subtraction (relative u, amplified p times by the
+    power) and POWF_ULPS ulps per powf; the running-error bound u * (sum of the partial sums) for the accumulation,
+    inflated by 1 + 2 W u; the final power: relative (1 / p) of the sum's relative error, |ln sum| / p * u for the rounding
+    of the exponent 1 / p to fp32, and POWF_ULPS ulps.  p = inf has no bound: the kernel's value must be the float64
+    maximum rounded to fp32 (fp32 subtraction is correctly rounded and rounding is monotone).  A zero sum stays zero."""
+    assert p > 0 and not np.isinf(p)
+    u = U32
+    X = np.asarray(X, dtype=np.float32).astype(np.float64)
+    B, N, W = X.shape
+    out = np.empty((B, N, N))
+    pow_rel = 0.0 if p == 1.0 else 2.0 * POWF_ULPS * u
+    for i in range(N):
+        t = np.abs(X[:, i:i + 1, :] - X) ** p
+        cs = np.cumsum(t, axis=-1)
+        s = cs[..., -1]
+        es = s * (p * u + pow_rel) + u * cs.sum(-1) * (1.0 + 2.0 * W * u)
+        if p == 1.0:
+            out[:, i] = es
+            continue
+        pos = s > 0
+        sp = np.where(pos, s, 1.0)
+        rel = (es / sp) / p + np.abs(np.log(sp)) / p * u + pow_rel
+        out[:, i] = np.where(pos, sp ** (1.0 / p) * rel * (1.0 + 2.0 ** -10), 0.0)
+    return out
+
+
+def shifted_distance(d, chunk_max=None):
+    """(d - max) - 1 and the diagonal - 1 more (cluster_utils.py:35-41) in the precision of ``d`` [B,N,N]."""
+    d = np.array(d)
+    one = d.dtype.type(1.0)
+    mx = d.dtype.type(d.max() if chunk_max is None else chunk_max)
+    d = (d - mx) - one
+    idx = np.arange(d.shape[-1])
+    d[:, idx, idx] -= one
+    return d
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,9 @@ so a fixture needs to store just the seed and the reference's outputs.
                         the same D bit for bit (parity level P1).
   dyadic(seed, shape)   sum of four integers in [-32, 32] divided by 64: bell-shaped,
                         every L1 distance over <= 768 dims is exact in fp32 (level P2).
+
+The generic-float recipes further down (generic, offset, wide, near_dup, tiny_lo) are the exception: they draw floats, for
+tests that recompute every expected value from the tokens instead of storing it.
 """
 import numpy as np
 
@@ -406,3 +409,117 @@ def loose_threshold_inputs(tag):
 
 # Round 6: k-medoids above 4,095 tokens per problem.  name: (seed, P, N, W, K, split, iter_limit) - lattice(seed, (P, N, W))
 P1_WIDE_CASES = {"p1w_4500": (181, 2, 4500, 16, 6, 1, 100), "p1w_8191": (182, 1, 8191, 8, 4, 16, 100)}
+
+
+# ---------------------------------------------------------------------------------------------- generic-float token recipes
+# Tokens on which fp32 arithmetic rounds (tests/test_cluster_generic_*.py).  Unlike the lattices above these draw floats
+# from numpy's PCG64 streams (standard_normal / uniform): reproducible for one numpy build, which is all the tests need - they
+# store no outputs, every expected value is recomputed from the tokens.
+def generic(seed, shape):
+    """N(0, 1)."""
+    return np.random.default_rng(seed).standard_normal(shape).astype(np.float32)
+
+
+def offset(seed, shape):
+    """N(0, 1) plus three "massive activation" channels at 100-300 sigma that every token shares (the channel and its level are
+    the same for all tokens, the N(0, 1) part stays on top) - the shape of a trained CLIP residual stream, and the inputs on
+    which |x|^2 + |y|^2 - 2 x.y cancels."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal(shape)
+    ch = rng.choice(shape[-1], size=3, replace=False)
+    x[..., ch] += rng.uniform(100.0, 300.0, size=3) * rng.choice([-1.0, 1.0], size=3)
+    return x.astype(np.float32)
+
+
+def wide(seed, shape):
+    """Element magnitudes log-uniform over 1e-3..1e3, random signs."""
+    rng = np.random.default_rng(seed)
+    return (rng.choice([-1.0, 1.0], size=shape) * 10.0 ** rng.uniform(-3.0, 3.0, size=shape)).astype(np.float32)
+
+
+def near_dup(seed, shape):
+    """N(0, 1) tokens; the last third of every problem are copies of earlier tokens with every element moved by up to 7 units
+    in the last place (its last 2-3 fp32 bits), and the three tokens before them are exact copies."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal(shape).astype(np.float32)
+    N = shape[-2]
+    nd = N // 3
+    flat = x.reshape((-1,) + tuple(shape[-2:]))
+    for prob in flat:
+        src = rng.integers(0, N - nd - 3, size=nd + 3)
+        prob[N - nd - 3:N - nd] = prob[src[:3]]
+        bits = prob[src[3:]].view(np.int32) + rng.integers(-7, 8, size=(nd, shape[-1])).astype(np.int32)
+        prob[N - nd:] = bits.view(np.float32)
+    return x
+
+
+def tiny_lo(seed, shape):
+    """Magnitudes log-uniform over 2^-6..2^-4, random signs: fp16(x) has an ulp of 2^-15..2^-17 there, so the lo part of the
+    Gram kernel's split, |lo| <= ulp / 2, lies wholly in fp16's subnormal range (< 2^-14)."""
+    rng = np.random.default_rng(seed)
+    return (rng.choice([-1.0, 1.0], size=shape) * 2.0 ** rng.uniform(-6.0, -4.0, size=shape)).astype(np.float32)
+
+
+GENERIC_RECIPES = {"generic": generic, "offset": offset, "wide": wide, "near_dup": near_dup, "tiny_lo": tiny_lo}
+
+GRAM_SWEEP_P = 3
+GRAM_SWEEP_N = (63, 64, 65, 130, 196, 257)      # one tile, an exact tile, a ragged second tile, three tiles, ragged 4th / 5th
+GRAM_SWEEP_W = (32, 64, 96, 200, 768)           # half a k-slice, one, 1.5, four with a partial last one, the shipped width
+
+
+def gram_sweep_cases():
+    """(seed, N, W, recipe) of the Gram-kernel distance sweep: 14 seeded draws in which every N, every W and every recipe
+    occurs at least twice, plus the shipped shape on `offset` tokens and a ragged second tile of near-duplicates."""
+    rng = np.random.default_rng(20261020)
+    names = sorted(GENERIC_RECIPES)
+    cols = []
+    for pool in (GRAM_SWEEP_N, GRAM_SWEEP_W, names):
+        idx = np.concatenate([rng.permutation(len(pool)) for _ in range(3)])[:14]
+        cols.append([pool[i] for i in idx])
+    out = [(9100 + c, int(n), int(w), str(r)) for c, (n, w, r) in enumerate(zip(*cols))]
+    out += [(9120, 196, 768, "offset"), (9121, 65, 64, "near_dup")]
+    return out
+
+
+MINKOWSKI_P = (1.0, 3.0, 0.5, float("inf"))
+MINKOWSKI_CASES = [(9200 + 10 * a + b, 3, N, W, r) for a, (N, W) in enumerate(((65, 32), (130, 100), (65, 100), (130, 32)))
+                   for b, r in enumerate(("generic", "wide"))]          # (seed, P, N, W, recipe)
+
+
+def select_d_in_lds(N, K):
+    """Whether the selection kernel keeps the N x N distances of a problem in LDS (cluster.hip sel_smem_bytes, 160 KiB)."""
+    up = lambda v, a: (v + a - 1) // a * a
+    b = up(N * N * 4, 8) + up(K * 8, 128) + up(K * 4, 8) + 4 * up(N * 2, 8) + up(K, 8) + 8
+    return up(b, 16) <= 160 * 1024
+
+
+# The fused op against the oracle selection on the kernel's own distances: name -> problem.  One entry per instantiation
+# <D in LDS, 64-token chunks> of the selection kernel that the dispatch reaches up to N = 1,000 (`sel`).  threshold = 1e-6,
+# iter_limit = 100 throughout; split_size = 2 with P = 5 gives chunks of 2, 2 and 1 problems, each with its own maximum.
+def _bw(seed, N, K, sel, P=5, W=96, recipe="generic", metric="euclidean", norm_p=2.0, pre_norm=False, id_sort=True):
+    return dict(seed=seed, P=P, N=N, W=W, K=K, split=2, sel=sel, recipe=recipe, metric=metric, norm_p=norm_p,
+                pre_norm=pre_norm, id_sort=id_sort)
+
+
+BITWISE_CASES = {
+    "n5": _bw(9301, 5, 2, (True, 1), W=32),
+    "n60": _bw(9302, 60, 9, (True, 1)),
+    "n128": _bw(9303, 128, 16, (True, 2)),
+    "n130": _bw(9304, 130, 49, (True, 3)),
+    "n196_offset": _bw(9310, 196, 49, (True, 4), W=768, recipe="offset"),       # the shipped shape
+    "n202": _bw(9306, 202, 20, (False, 4)),                                    # the first N whose D leaves LDS at K = 20
+    "n256": _bw(9307, 256, 49, (False, 4)),
+    "n392_cos": _bw(9308, 392, 49, (False, 7), W=64, metric="cosine"),
+    "n640": _bw(9309, 640, 49, (False, 10), W=64),
+    "n1000": _bw(9314, 1000, 32, (False, 16), P=2, W=64),
+    "n130_l1": _bw(9311, 130, 12, (True, 3), norm_p=1.0),
+    "n130_prenorm": _bw(9312, 130, 12, (True, 3), pre_norm=True),
+    "n60_nosort": _bw(9313, 60, 9, (True, 1), id_sort=False),
+}
+
+# the module on strided tokens: B, T, T_new, n (N = T / T_new * n = 98), K, W, split
+BITWISE_MODULE_CASE = dict(seed=9320, B=2, T=4, T_new=2, n=49, K=12, W=64, split=16)
+
+
+def bitwise_tokens(cfg):
+    return GENERIC_RECIPES[cfg["recipe"]](cfg["seed"], (cfg["P"], cfg["N"], cfg["W"]))
