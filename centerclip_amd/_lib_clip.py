@@ -133,6 +133,8 @@ def declare(lib):
     lib.cc_resize_crop_workspace_bytes.restype = sz
     lib.cc_resize_crop_u8.argtypes = [vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp, sz, vp]
     lib.cc_resize_crop_u8.restype = c.c_int
+    lib.cc_resized_crop_flip_u8.argtypes = [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp]
+    lib.cc_resized_crop_flip_u8.restype = c.c_int
     lib.cc_clip_encode_frames.argtypes = [c.POINTER(VitModel), c.POINTER(Frames), i32, i32, vp, vp, vp,
                                           c.POINTER(TextModel), vp, i32, i32, vp, vp, sz, vp]
     lib.cc_clip_encode_frames.restype = c.c_int

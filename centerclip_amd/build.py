@@ -14,9 +14,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-pass-failed"] + os.environ.get("CC_EXTRA_FLAGS", "").split()      # e.g. -DCC_DEV_KNOBS for A/B builds
 # the cluster / similarity paths promise IEEE single operations in source order (no fma contraction); preprocess.hip the same
-# for the double operations of its host-side coefficient tables
+# for the double operations of its host-side coefficient tables, augment.hip for the fp32 weights and sums its error bound counts
 STRICT = {"cluster.hip": ["-ffp-contract=off"], "similarity.hip": ["-ffp-contract=off"], "dsl.hip": ["-ffp-contract=off"],
-          "preprocess.hip": ["-ffp-contract=off"], "search.hip": ["-ffp-contract=off"]}
+          "preprocess.hip": ["-ffp-contract=off"], "search.hip": ["-ffp-contract=off"], "augment.hip": ["-ffp-contract=off"]}
 
 
 def sources():

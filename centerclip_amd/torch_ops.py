@@ -1005,6 +1005,67 @@ def _(frames, n_px, resize, out):
     return None
 
 
+def _resized_crop_flip_check(frames, boxes, n_px, frames_per_clip, interp):
+    """The checks the real and the fake kernels share -> (channels_first, H, W, F)."""
+    if frames.dtype != torch.uint8:
+        raise ValueError("resized_crop_flip takes uint8 frames, got %s" % frames.dtype)
+    chw, H, W = _raw_frames_geometry(frames.shape)
+    F = math.prod(frames.shape[:-3])
+    if frames_per_clip < 1 or interp not in (0, 1) or n_px < 1:
+        raise ValueError("resized_crop_flip: frames_per_clip >= 1, n_px >= 1 and interp 0 (bilinear) / 1 (bicubic), got %d, %d, %d"
+                         % (frames_per_clip, n_px, interp))
+    clips = -(-F // frames_per_clip)
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (clips, 5):
+        raise ValueError("resized_crop_flip: boxes must be int32 [%d, 5] rows (top, left, height, width, flip) for %d frames in "
+                         "clips of %d, got %s %s" % (clips, F, frames_per_clip, boxes.dtype, tuple(boxes.shape)))
+    return chw, H, W, F
+
+
+def _resized_crop_flip_into(frames, boxes, out, n_px, frames_per_clip, interp):
+    chw, H, W, F = _resized_crop_flip_check(frames, boxes, n_px, frames_per_clip, interp)
+    L.require_device(frames, boxes, out)
+    if out.dtype != torch.uint8 or tuple(out.shape) != _resize_crop_shape(frames.shape, n_px) or not out.is_contiguous():
+        raise ValueError("resized_crop_flip: out must be a contiguous uint8 %s, got %s %s"
+                         % (_resize_crop_shape(frames.shape, n_px), out.dtype, tuple(out.shape)))
+    if F == 0:
+        return
+    frames, boxes = frames.contiguous(), boxes.contiguous()
+    fmt = 1 if chw else 2
+    L.check(L.lib().cc_resized_crop_flip_u8(L.ptr(frames), fmt, F, H, W, int(frames_per_clip), L.ptr(boxes), int(n_px),
+                                            int(interp), L.ptr(out), fmt, _st(frames)), "cc_resized_crop_flip_u8")
+
+
+@custom_op(NS + "::resized_crop_flip", mutates_args=(), device_types="cuda")
+def resized_crop_flip(frames: torch.Tensor, boxes: torch.Tensor, n_px: int, frames_per_clip: int, interp: int) -> torch.Tensor:
+    """Train-time augmentation (cc_resized_crop_flip_u8): uint8 frames [..., H, W, 3] or [..., 3, H, W] -> uint8
+    [..., n_px, n_px, 3] / [..., 3, n_px, n_px] (the input's layout); the frames count in clips of frames_per_clip and clip i
+    is cropped to boxes[i] = (top, left, height, width, flip) (int32, on the device - the kernel reads it, nothing is copied or
+    read back), resized to n_px x n_px with interp 0 bilinear / 1 bicubic (F.interpolate, align_corners=False, no antialias,
+    rounded to bytes) and mirrored where flip != 0.  A row outside the frame gives zeros for its clip."""
+    out = _e(*_resize_crop_shape(frames.shape, n_px), like=frames, dtype=torch.uint8)
+    _resized_crop_flip_into(frames, boxes, out, n_px, frames_per_clip, interp)
+    return out
+
+
+@resized_crop_flip.register_fake
+def _(frames, boxes, n_px, frames_per_clip, interp):
+    _resized_crop_flip_check(frames, boxes, n_px, frames_per_clip, interp)
+    return frames.new_empty(_resize_crop_shape(frames.shape, n_px), dtype=torch.uint8)
+
+
+@custom_op(NS + "::resized_crop_flip_out", mutates_args=("out",), device_types="cuda")
+def resized_crop_flip_out(frames: torch.Tensor, boxes: torch.Tensor, n_px: int, frames_per_clip: int, interp: int,
+                          out: torch.Tensor) -> None:
+    """resized_crop_flip into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay)."""
+    _resized_crop_flip_into(frames, boxes, out, n_px, frames_per_clip, interp)
+
+
+@resized_crop_flip_out.register_fake
+def _(frames, boxes, n_px, frames_per_clip, interp, out):
+    _resized_crop_flip_check(frames, boxes, n_px, frames_per_clip, interp)
+    return None
+
+
 @custom_op(NS + "::clip_encode_out", mutates_args=("vfeat", "tfeat", "medoids_out"), device_types="cuda")
 def clip_encode_out(frames: torch.Tensor, ids: torch.Tensor, vhandle: int, thandle: int, B: int, T: int,
                     vfeat: torch.Tensor, tfeat: torch.Tensor, medoids_out: Optional[torch.Tensor],
@@ -2003,7 +2064,7 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
        "similarity_topk_grouped", "similarity_topk_grouped_dsl", "similarity_topk_masked", "dsl_col_stats_planes_masked",
        "pack_row_mask", "similarity_rank", "similarity_topk_deep", "similarity_topk_merge", "similarity_target_score",
-       "similarity_count")
+       "similarity_count", "resized_crop_flip", "resized_crop_flip_out")
 
 
 def logit_multiplier(logit_scale):

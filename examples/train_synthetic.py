@@ -27,8 +27,15 @@ is_best is "lowest mean loss so far"), and the captured step's own state_dict() 
 one (main.py:185-212) into the eager loop, which continues at the file's epoch and global_step, and then into the captured step
 before its first call.
 
+--augment multiscale|random_resized [--flip 1] trains the eager loop on the training loader's augmentations
+(dataloaders/decode.py:32-41) done on the device: the loader hands over decoded uint8 frames - --raw_frames H,W as a decoder
+leaves them (default 240,320), or with --uint8 1 the 224 x 224 uint8 frames - and train_epoch(frame_transform=
+preprocess.TrainFrameTransform(...)) crops, resizes and flips each clip with one launch.  The captured step then runs on a batch
+augmented the same way.
+
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
                                        [--epochs 1] [--output_dir DIR] [--resume DIR/ckpt.pth.tar]
+                                       [--augment multiscale|random_resized] [--flip 1] [--raw_frames 240,320]
                                        [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--quick_gelu 0] [--l14 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
@@ -46,6 +53,7 @@ from centerclip_amd.clip4clip import CLIP4Clip              # noqa: E402
 from centerclip_amd.train import (AdamW, BertAdam, DeviceGradScaler, checkpoint_dict, lr_scheduler,   # noqa: E402
                                   prep_optim_params_groups, resume, save_checkpoint, train_epoch)
 from centerclip_amd import dist as ccdist                   # noqa: E402
+from centerclip_amd.preprocess import TrainFrameTransform   # noqa: E402
 import bench                                                # noqa: E402
 from eval_synthetic import SyntheticRetrieval, L14, l14_state_dict, l14_task_config   # noqa: E402
 
@@ -90,6 +98,10 @@ def build_parser():
     ap.add_argument("--epochs", type=int, default=1, help="passes of train_epoch over the loader (main.py's --epochs)")
     ap.add_argument("--output_dir", default=None, help="main.py's --output_dir: write ckpt.pth.tar (and ckpt.best.pth.tar) after every epoch")
     ap.add_argument("--resume", default=None, help="main.py's --resume: a checkpoint to continue from (eager loop and captured step)")
+    ap.add_argument("--augment", choices=["multiscale", "random_resized"], default=None,
+                    help="train-time augmentation on the device (decode.py:32-41): one crop box per clip, resized to 224 px")
+    ap.add_argument("--flip", type=int, default=0, help="with --augment: also one random horizontal flip per clip")
+    ap.add_argument("--raw_frames", default="240,320", help="with --augment (and without --uint8 1): H,W of the decoded uint8 frames")
     return ap
 
 
@@ -136,6 +148,15 @@ def main():
     data = SyntheticRetrieval(a.batch * a.steps, seed=rank)
     if a.uint8:
         data.video = torch.randint(0, 256, data.video.shape, dtype=torch.uint8, generator=torch.Generator().manual_seed(rank))
+    augment = None
+    if a.augment is not None:
+        if not a.uint8:                                     # frames as a decoder leaves them: uint8 [n, 1, T, H, W, 3]
+            H, W = (int(v) for v in a.raw_frames.split(","))
+            data.video = torch.randint(0, 256, data.video.shape[:3] + (H, W, 3), dtype=torch.uint8,
+                                       generator=torch.Generator().manual_seed(rank))
+        augment = TrainFrameTransform(224, crop=a.augment, flip=bool(a.flip), seed=rank)
+    elif a.flip:
+        raise SystemExit("--flip 1 goes with --augment")
     loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False)
     if a.same_batch:
         loader = [next(iter(loader))] * a.steps
@@ -160,7 +181,7 @@ def main():
     for epoch in range(start_epoch, a.epochs):
         t[0] = time.time()                                  # (a resume or a save is not part of the next step's time)
         tr_loss, global_step = train_epoch(epoch, targs, model, loader, device, opt, global_step, scheduler=sched, buckets=buckets,
-                                           log=log, scaler=scaler)
+                                           log=log, scaler=scaler, frame_transform=augment)
         if rank == 0:
             print("epoch %d/%d finished, train loss %.6f" % (epoch + 1, a.epochs, tr_loss))
         if a.output_dir is not None and rank == 0:          # main.py:262-272 (rank 0 saves)
@@ -182,6 +203,8 @@ def main():
         gscaler = DeviceGradScaler() if a.precision == "amp" else None
         stepper = GraphedTrainStep(model, gopt, scheduler=gsched, clip_grad_norm=targs.clip_grad_norm, scaler=gscaler)
         batch = next(iter(loader))
+        if augment is not None:                             # (the captured step takes model-resolution frames)
+            batch = tuple(batch[:3]) + (augment(batch[3].to(device)),) + tuple(batch[4:])
         if a.resume is not None:                            # in place of a first call's fresh start: restored, then captured
             t0 = time.time()
             g_epoch, g_step, _ = resume(a.resume, model, step=stepper)

@@ -726,6 +726,28 @@ size_t cc_resize_crop_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t n
 int cc_resize_crop_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_t W, const void* plan_dev, int32_t n_px,
                       int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream);
 
+/* Train-time augmentation of decoded uint8 frames: per clip one crop box resized to n_px x n_px and one horizontal flip - the
+ * reference's TensorMultiScaleCrop / RandomResizedCrop and TensorRandomHorizontalFlip (dataloaders/decode.py:32-41,
+ * dataloaders/transforms.py:37-134, 168-196) once the box and the flip are drawn; the drawing is the caller's.
+ * src: F frames [H, W, 3] (fmt = CC_FRAMES_U8_HWC) or [3, H, W] (CC_FRAMES_U8_CHW) at ANY byte address; dst: F frames
+ * [n_px, n_px, 3] or [3, n_px, n_px] (dst_fmt).  boxes_dev: int32 [ceil(F / frames_per_clip), 5] in device memory, rows
+ * (top, left, height, width, flip); frame f uses row f / frames_per_clip.  The kernel reads the table, the host never does:
+ * one launch, no workspace, no upload, no synchronisation (capturable; a replay follows the table's contents at that time).
+ * A row that does not lie inside the frame (top < 0, left < 0, height < 1, width < 1, top + height > H or left + width > W) is
+ * not followed: the frames of that clip come out as zeros, no address is formed from the row.
+ * Arithmetic: torch.nn.functional.interpolate(crop, n_px, mode, align_corners=False), no antialias, in fp32 on the bytes.
+ * The source coordinate of output index o of an axis is the exact rational ((2 o + 1) crop - n_px) / (2 n_px) (= (o + 0.5) *
+ * crop / n_px - 0.5): integer floor, fraction t from the remainder.  interp 0, bilinear: the coordinate is clamped below at
+ * 0, weights (1 - t, t), the upper neighbour clamped to the crop's last sample.  interp 1, bicubic: cubic convolution with
+ * A = -0.75 on the four samples floor - 1 .. floor + 2, each index clamped into the crop, the coordinate itself not clamped.
+ * flip != 0: output column ox is what column n_px - 1 - ox would be.  Rows are combined after columns; the result is
+ * clamp(rint(sum), 0, 255), rint half to even.  A box of n_px x n_px is a copy, byte for byte (weights exactly 0 and 1).
+ * CC_ERR_INVALID for a NULL src / dst / table, F <= 0, frames_per_clip <= 0, a format other than the two uint8 codes or an
+ * interp other than 0 / 1; CC_ERR_UNSUPPORTED outside 1 <= n_px <= 1024, 4 <= H, W <= 8192; all before any launch.
+ * DESIGN.md, "Train-time augmentation". */
+int cc_resized_crop_flip_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_t W, int32_t frames_per_clip,
+                            const int32_t* boxes_dev, int32_t n_px, int32_t interp, void* dst, int32_t dst_fmt, void* stream);
+
 /* S2 - the meanP similarity tail, CLIP4Clip._loose_similarity (modules/clip4clip.py:357-366) with
  * _mean_pooling_for_similarity_visual (:305-316):
  *   v_hat = v/|v| per frame; v_bar = sum_t mask*v_hat / max(sum_t mask, 1 if 0); v_bar /= |v_bar|
