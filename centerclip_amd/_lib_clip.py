@@ -227,6 +227,8 @@ def declare(lib):
     lib.cc_normalize_rows_planes_f32.restype = c.c_int
     lib.cc_video_pool_normalize_planes_f32.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     lib.cc_video_pool_normalize_planes_f32.restype = c.c_int
+    lib.cc_video_window_pool_planes_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp]
+    lib.cc_video_window_pool_planes_f32.restype = c.c_int
     lib.cc_scaled_dot_planes_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, i32, vp]
     lib.cc_scaled_dot_planes_f32.restype = c.c_int
     lib.cc_scaled_dot_planes_products_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, i32, vp, i32, vp]

@@ -112,12 +112,14 @@ struct VidAddr {
     int vg;
     int64_t vgs, mgs, mrs, mcs;
 };
-__device__ __forceinline__ void video_pool_wave(const float* __restrict__ visual, const long long* __restrict__ mask,
-                                                const VidAddr& ad, float* __restrict__ pooled, const SplitOut& so, int v,
-                                                int Tn, int E, int lane) {
-    const int grp = v / ad.vg, loc = v - grp * ad.vg;
-    visual += (int64_t)grp * ad.vgs + (int64_t)loc * Tn * E;
-    mask += (int64_t)grp * ad.mgs + (int64_t)loc * ad.mrs;
+// The pooling itself, one wave: segments [0, Tn) at `visual` -> output row `row`.  kMasked: segment t weighs
+// mask[t * mcs]; otherwise every segment weighs 1 and `mask` is not read (the windows of a long video,
+// video_window_pool_kernel) - the same operations in the same order, so a window's row has the bits of
+// video_pool_kernel's on the same segments with a mask of ones.
+template <bool kMasked>
+__device__ __forceinline__ void video_pool_segments(const float* __restrict__ visual, const long long* __restrict__ mask,
+                                                    int64_t mcs, float* __restrict__ pooled, const SplitOut& so,
+                                                    int64_t row, int Tn, int E, int lane) {
     constexpr int MAXE = 16;                      // E <= 1024
     float acc[MAXE];
 #pragma unroll
@@ -134,7 +136,7 @@ __device__ __forceinline__ void video_pool_wave(const float* __restrict__ visual
             s = fmaf(x[q], x[q], s);
         }
         const float nrm = sqrtf(cc_wave_sum_fast(s));
-        const float mk = (float)mask[(int64_t)t * ad.mcs];   // element strides: a strided view is fine
+        const float mk = kMasked ? (float)mask[(int64_t)t * mcs] : 1.f;   // element strides: a strided view is fine
         cnt += mk;
 #pragma unroll
         for (int q = 0; q < MAXE; ++q) acc[q] += (x[q] / nrm) * mk;
@@ -152,10 +154,19 @@ __device__ __forceinline__ void video_pool_wave(const float* __restrict__ visual
         const int e = lane + 64 * q;
         if (e < E) {
             const float pv = acc[q] / nrm;
-            if (pooled) pooled[(int64_t)v * E + e] = pv;
-            if (so.hi) split_put(so, v, e, pv);
+            if (pooled) pooled[row * E + e] = pv;
+            if (so.hi) split_put(so, row, e, pv);
         }
     }
+}
+
+__device__ __forceinline__ void video_pool_wave(const float* __restrict__ visual, const long long* __restrict__ mask,
+                                                const VidAddr& ad, float* __restrict__ pooled, const SplitOut& so, int v,
+                                                int Tn, int E, int lane) {
+    const int grp = v / ad.vg, loc = v - grp * ad.vg;
+    visual += (int64_t)grp * ad.vgs + (int64_t)loc * Tn * E;
+    mask += (int64_t)grp * ad.mgs + (int64_t)loc * ad.mrs;
+    video_pool_segments<true>(visual, mask, ad.mcs, pooled, so, v, Tn, E, lane);
 }
 
 __global__ __launch_bounds__(256) void video_pool_kernel(const float* __restrict__ visual,
@@ -164,6 +175,24 @@ __global__ __launch_bounds__(256) void video_pool_kernel(const float* __restrict
     const int v = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (v >= Bv) return;
     video_pool_wave(visual, mask, ad, pooled, so, v, Tn, E, threadIdx.x & 63);
+}
+
+// Windows of long videos (search.py, FeatureGallery.add_window_features): visual [Bv, S, E] holds the per-segment features of
+// whole videos, windows [nW, 3] int32 = (video, start segment, stop segment); one wave pools the segments [start, stop) of
+// its window into plane row w.  The table lives on the device, so its entries are checked here, per wave (the three
+// values are the same in every lane): an entry outside the tensor reads nothing and writes a zero row.
+__global__ __launch_bounds__(256) void video_window_pool_kernel(const float* __restrict__ visual,
+                                                                const int* __restrict__ windows, SplitOut so, int Bv, int S,
+                                                                int nW, int E) {
+    const int w = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (w >= nW) return;
+    const int v = windows[3 * (int64_t)w], a = windows[3 * (int64_t)w + 1], b = windows[3 * (int64_t)w + 2];
+    if (v < 0 || v >= Bv || a < 0 || b > S || a >= b) {
+        _Float16* p = so.hi + (int64_t)w * (3 * (int64_t)E);
+        for (int e = lane; e < 3 * E; e += 64) p[e] = (_Float16)0.f;
+        return;
+    }
+    video_pool_segments<false>(visual + ((int64_t)v * S + a) * E, nullptr, 0, nullptr, so, w, b - a, E, lane);
 }
 
 // Both producers of the similarity GEMM's operands in ONE launch: workgroups [0, text_blocks) normalise 4 text rows each
@@ -385,6 +414,16 @@ int cc_video_pool_normalize_planes_f32(const float* visual, const int64_t* video
     if (!planes || (E & 63)) return CC_ERR_INVALID;
     const VidAddr ad{Bv > 0 ? Bv : 1, 0, 0, Tn, 1};
     return video_pool_launch(visual, video_mask, ad, Bv, Tn, E, pooled, SplitOut{static_cast<_Float16*>(planes), E, 1}, stream);
+}
+
+int cc_video_window_pool_planes_f32(const float* visual, const int32_t* windows, int32_t Bv, int32_t S, int32_t nW, int32_t E,
+                                    void* planes, void* stream) {
+    if (!visual || !windows || !planes || Bv <= 0 || S <= 0 || nW <= 0 || E <= 0 || (E & 63)) return CC_ERR_INVALID;
+    if (E > 1024) return CC_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(video_window_pool_kernel, dim3((nW + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), visual,
+                       windows, SplitOut{static_cast<_Float16*>(planes), E, 1}, Bv, S, nW, E);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
 }
 
 int cc_scaled_dot_planes_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv,

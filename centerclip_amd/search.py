@@ -46,15 +46,91 @@ restricted to what lies behind the page before - exact, no matrix, no state betw
 
     scores, ids = gallery.search(input_ids, k=1000)                         # candidates for a re-ranker
     more_scores, more_ids = gallery.search(input_ids, k=50, after=(scores[:, -1], ids[:, -1]))     # entries 1000..1049
+
+"Which video, and where in it": a long video is encoded once and every sliding window of it becomes a row
+(``video_window_pool_planes``: the pooling of ``add`` on the window's segments, one launch for all windows), a video one group:
+
+    gallery = FeatureGallery(model, grouped=True)
+    pos, windows = gallery.add_windows(video, lengths, window=[8, 16], group=video_ids)     # video [b, 1, F, ...], F = n * T frames
+    scores, videos, best = gallery.search_groups(input_ids, k=10)
+    frames = gallery.windows(best[0].cpu())                                 # (start_frame, stop_frame) of each best window
 """
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import torch_ops as T
+from .cluster.shift import SHIFT_ALGORITHMS
 from .eval import HipBackend, _video_operand
 
 SIDES = ("video", "text")
+
+
+def _scales(value, frame_duration, what, count=None):
+    """an int, or one int per scale -> list of segment counts; every value a positive multiple of frame_duration"""
+    if isinstance(value, (int, np.integer)):
+        values = [value] * (count or 1)
+    elif isinstance(value, (list, tuple, np.ndarray)):
+        values = list(value)
+    else:
+        raise ValueError("window_table: %s is an int or a sequence of ints, not %r" % (what, value))
+    if not values or (count is not None and len(values) != count):
+        raise ValueError("window_table: %s holds %d values for %s scales" % (what, len(values), count if count is not None else "no"))
+    for v in values:
+        if not isinstance(v, (int, np.integer)) or v <= 0 or v % frame_duration:
+            raise ValueError("window_table: %s %r is not a positive multiple of the %d frames of a segment"
+                             % (what, v, frame_duration))
+    return [int(v) // frame_duration for v in values]
+
+
+def window_table(lengths, frame_duration, window, stride=None, segments=None):
+    """The sliding windows of long videos, in segments: -> np.int64 [nW, 3], columns (video, start_seg, stop_seg).  Pure host
+    work.  ``lengths``: the valid frames of every video (a host sequence or a CPU LongTensor - never a device tensor: reading
+    it would synchronise); video i has n_i = lengths[i] // frame_duration valid segments (a segment is valid when its last
+    frame is - ``get_video_mask_after_cluster`` - so a partial last segment is dropped); none at all, or more than
+    ``segments`` (when given): ValueError.  ``window``: frames per window, an int or one per scale; ``stride``: an int for all
+    scales or one per scale, default half the window rounded down to whole segments (at least one); all positive multiples
+    of ``frame_duration``.  Per video and scale: n_i <= w gives the one window (0, n_i); otherwise the starts 0, s, 2s, ...
+    <= n_i - w, and one more at n_i - w when the last is not there, so every valid segment is covered.  Order: video, scale
+    as given, start; inside a video a (start, stop) pair appears once (the first stays)."""
+    fd = int(frame_duration)
+    if fd <= 0:
+        raise ValueError("window_table: frame_duration %d" % fd)
+    if torch.is_tensor(lengths):
+        if lengths.device.type != "cpu" or lengths.dtype != torch.int64 or lengths.dim() != 1:
+            raise ValueError("window_table: lengths are a host sequence or a flat CPU LongTensor, not a %s %s tensor %s (reading "
+                             "a device tensor would synchronise)" % (lengths.device, lengths.dtype, tuple(lengths.shape)))
+        lens = lengths.numpy()
+    else:
+        lens = np.asarray(list(lengths))
+        if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
+            raise ValueError("window_table: lengths are a flat sequence of ints")
+    ws = _scales(window, fd, "window")
+    if stride is None:
+        ss = [max(w // 2, 1) for w in ws]
+    else:
+        ss = _scales(stride, fd, "stride", len(ws))
+    rows = []
+    for i, length in enumerate(lens.tolist()):
+        n = int(length) // fd
+        if n <= 0:
+            raise ValueError("window_table: video %d has %d frames, not one whole segment of %d" % (i, length, fd))
+        if segments is not None and n > int(segments):
+            raise ValueError("window_table: video %d has %d valid segments, the features hold %d" % (i, n, int(segments)))
+        seen = set()
+        for w, s in zip(ws, ss):
+            if n <= w:
+                spans = [(0, n)]
+            else:
+                starts = list(range(0, n - w + 1, s))
+                if starts[-1] != n - w:
+                    starts.append(n - w)
+                spans = [(a, a + w) for a in starts]
+            for span in spans:
+                if span not in seen:
+                    seen.add(span)
+                    rows.append((i,) + span)
+    return np.array(rows, dtype=np.int64).reshape(-1, 3)
 
 
 class FeatureGallery:
@@ -139,6 +215,7 @@ class FeatureGallery:
             self._m = torch.zeros(self._rows.shape[0], device=self.device)       # per row held (side="video"): max_t S[t, v]
             self._s = torch.zeros(self._rows.shape[0], device=self.device)       # and sum_t exp(S[t, v] - m_v) over the bank
         self._forget_removals()                                  # (nothing is allocated until the first remove)
+        self._win_host = None                                    # (nor until the first window row: _window_records)
         self.grouped = bool(grouped)
         if self.grouped:
             self._head = torch.zeros(self._rows.shape[0], device=self.device, dtype=torch.int32)     # first row of the row's group
@@ -160,6 +237,7 @@ class FeatureGallery:
         """Empty the rows and the groups and forget the removals (a dual-softmax gallery keeps its bank)."""
         self._n = 0
         self._forget_removals()
+        self._win_host = None
         if self._grouped:
             self._reset_groups()
 
@@ -380,6 +458,140 @@ class FeatureGallery:
         self._check_group_arg(group, "add_features")
         return self._append(self._video_rows(features, mask) if self.side == "video" else self._text_rows(features), group)
 
+    # ------------------------------------------------------------------ windows of long videos
+    def _window_records(self):
+        """None until a window row exists; then int64 [span, 2] on the host: the (start_frame, stop_frame) every position
+        stands for, (-1, -1) for the rows of ``add`` / ``add_features`` (padded here: those methods know nothing of it)"""
+        rec = getattr(self, "_win_host", None)                   # (an instance built without the constructor: none)
+        if rec is not None and rec.shape[0] < self._n:
+            rec = self._win_host = np.concatenate((rec, np.full((self._n - rec.shape[0], 2), -1, dtype=np.int64)))
+        return rec
+
+    def _append_windows(self, rows, frames, group=None):
+        """``_append`` for window rows: ``frames`` int64 [n, 2] = the (start_frame, stop_frame) of every row"""
+        pos = self._append(rows, group)                          # (raises before anything is written)
+        if frames.shape[0]:
+            rec = self._window_records()
+            head = rec[:self._n - frames.shape[0]] if rec is not None else np.full((self._n - frames.shape[0], 2), -1, dtype=np.int64)
+            self._win_host = np.concatenate((head, frames.astype(np.int64)))
+        return pos
+
+    def windows(self, positions):
+        """The frames the rows at ``positions`` (as ``remove`` takes them) stand for -> CPU LongTensor [n, 2] of
+        (start_frame, stop_frame) inside their video; (-1, -1) for rows that came from ``add`` / ``add_features``.  Kept on the
+        host like the labels: the records survive ``remove``, move with their rows in ``compact()``, go with ``clear()``."""
+        pos = self._positions(positions, "windows")
+        rec = self._window_records()
+        return torch.from_numpy(rec[pos] if rec is not None else np.full((pos.size, 2), -1, dtype=np.int64))
+
+    def _need_video_side(self, what):
+        if self.side != "video":
+            raise ValueError("FeatureGallery.%s: windows are rows of a side='video' gallery, not side=%r" % (what, self.side))
+
+    def _window_groups(self, group, table, b, what):
+        """``group=`` of a window call - an int, or one label per VIDEO - expanded to the rows of ``table``"""
+        self._check_group_arg(group, what)
+        if group is None or isinstance(group, (int, np.integer)):
+            return group
+        lab = self._label_list(group, what)
+        if lab.shape != (b,):
+            raise ValueError("FeatureGallery.%s: group= holds %d labels for %d videos (one int, or one int per video)"
+                             % (what, lab.size, b))
+        return lab[table[:, 0]]
+
+    def _window_rows(self, visual_output, table):
+        """per-segment features [b, S, E] + the segment table -> the windows' operand rows [nW, 3E]"""
+        visual = visual_output.float().contiguous()
+        if getattr(self.core, "sim_header", "meanP") != "seqTransf":
+            return torch.ops.centerclip.video_window_pool_planes(visual, self._host_to_device(table.astype(np.int32)))
+        # seqTransf: the head is part of a clip's operand and its position rows start at 0 for every clip - the windows of
+        # one length are gathered and go through the head as a batch of clips (the longest first: a window beyond the
+        # position table raises the head's own ValueError before any row exists)
+        rows = torch.empty((table.shape[0], 3 * self.E), device=self.device, dtype=torch.float16)
+        span = table[:, 2] - table[:, 1]
+        for n in sorted(set(span.tolist()), reverse=True):
+            which = np.flatnonzero(span == n)
+            seg = (table[which, 0] * visual.shape[1] + table[which, 1])[:, None] + np.arange(n)[None, :]
+            clips = visual.view(-1, visual.shape[2])[self._host_to_device(seg.reshape(-1))].view(which.size, n, -1)
+            ones = torch.ones((which.size, n), device=self.device, dtype=torch.long)
+            rows[self._host_to_device(which)] = self._video_rows(clips, ones)
+        return rows
+
+    def _add_window_features(self, visual_output, table, group):
+        fd = int(self.core.f_frame_duration)
+        frames = table * np.array([1, fd, fd], dtype=np.int64)
+        with torch.no_grad():
+            rows = self._window_rows(visual_output, table)
+        return self._append_windows(rows, frames[:, 1:], group), torch.from_numpy(frames)
+
+    def add_window_features(self, visual_output, lengths, window, stride=None, group=None):
+        """The sliding windows of long videos from per-segment features encoded ONCE (side="video").  ``visual_output``
+        [b, S, E]: the features of the b videos' segments, before any head; ``lengths``: the valid frames of every video (a
+        host sequence or a CPU LongTensor); ``window`` / ``stride``: frames, as ``window_table`` takes them (a multiple of
+        ``core.f_frame_duration``; several windows = several scales).  Every window becomes one row, the bits of
+        ``add_features(visual_output[v:v+1, a:b], ones)`` for meanP (one launch for all of them:
+        ``video_window_pool_planes``); seqTransf runs the head on every window as on a clip.  ``group=``: an int, or one label
+        per VIDEO - all windows of a video form one group, so ``search_groups`` answers "which video" and the position it
+        returns "where": ``windows(position)``.  -> (positions, windows): the rows' positions and a CPU LongTensor
+        [n_rows, 3] of (video index in this call, start_frame, stop_frame)."""
+        self._need_video_side("add_window_features")
+        L.require_device(visual_output)
+        if visual_output.dim() != 3 or visual_output.shape[2] != self.E:
+            raise ValueError("FeatureGallery.add_window_features: per-segment features [b, S, %d], not %s"
+                             % (self.E, tuple(visual_output.shape)))
+        b, S = visual_output.shape[:2]
+        table = window_table(lengths, int(self.core.f_frame_duration), window, stride, segments=S)
+        if b == 0 or len(lengths) != b:
+            raise ValueError("FeatureGallery.add_window_features: %d lengths for %d videos" % (len(lengths), b))
+        return self._add_window_features(visual_output, table, self._window_groups(group, table, b, "add_window_features"))
+
+    def add_windows(self, video, lengths, window, stride=None, group=None, encode_batch=64):
+        """The same from frames: ``video`` [b, 1, F, ...] as ``add`` takes it, F any positive multiple of the model's clip
+        length T.  The frames are folded to b F / T clips of T frames and encoded as ``add`` encodes clips (at most
+        ``encode_batch`` per call) - every frame once, whatever the windows - and their per-segment features, viewed as
+        [b, F / fd, E], go through ``add_window_features``.  Refused, before anything is encoded: the shift algorithms
+        and linear_patch='3d' (neighbouring frames mix, so a segment's feature is not its own frames' alone), F % T != 0,
+        lengths[i] > F."""
+        self._need_video_side("add_windows")
+        core = self.core
+        if getattr(core, "cluster_algo", None) in SHIFT_ALGORITHMS:
+            raise ValueError("FeatureGallery.add_windows: cluster_algo=%r shifts channels between neighbouring frames, so a "
+                             "segment's feature depends on the clip it was cut into" % core.cluster_algo)
+        if getattr(core, "linear_patch", "2d") == "3d":
+            raise ValueError("FeatureGallery.add_windows: linear_patch='3d' mixes neighbouring frames in the patch embedding, "
+                             "so a segment's feature depends on the clip it was cut into")
+        if getattr(core, "pre_visual_pooling", 0):
+            raise ValueError("FeatureGallery.add_windows: pre_visual_pooling pools the clip inside the model; the windows need "
+                             "the per-segment features")
+        T, fd = int(core.video_frames), int(core.f_frame_duration)
+        if video.dim() < 4 or video.shape[1] != 1:
+            raise ValueError("FeatureGallery.add_windows: video is [b, 1, F, ...], not %s" % (tuple(video.shape),))
+        b, F = int(video.shape[0]), int(video.shape[2])
+        if F <= 0 or F % T:
+            raise ValueError("FeatureGallery.add_windows: %d frames are not a positive multiple of the model's clip length %d"
+                             % (F, T))
+        if int(encode_batch) < 1:
+            raise ValueError("FeatureGallery.add_windows: encode_batch %d" % int(encode_batch))
+        table = window_table(lengths, fd, window, stride)
+        if b == 0 or len(lengths) != b:
+            raise ValueError("FeatureGallery.add_windows: %d lengths for %d videos" % (len(lengths), b))
+        over = np.flatnonzero(np.asarray(lengths.numpy() if torch.is_tensor(lengths) else list(lengths)) > F)
+        if over.size:
+            raise ValueError("FeatureGallery.add_windows: video %d is longer than the %d frames given" % (int(over[0]), F))
+        group = self._window_groups(group, table, b, "add_windows")
+        L.require_device(video)
+        clips = video.reshape((b * (F // T), 1, T) + tuple(video.shape[3:]))
+        ones = torch.ones((min(int(encode_batch), clips.shape[0]), T), device=video.device, dtype=torch.long)
+        parts = []
+        for c0 in range(0, clips.shape[0], int(encode_batch)):
+            part = clips[c0:c0 + int(encode_batch)]
+            parts.append(self._encode(video=part, video_mask=ones[:part.shape[0]])['visual_output'])
+        visual = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+        if visual.dim() != 3 or visual.shape[1] * fd != T:
+            raise ValueError("FeatureGallery.add_windows: the encoder gave features %s for clips of %d frames, not %d segments "
+                             "of %d frames" % (tuple(visual.shape), T, T // fd, fd))
+        return self._add_window_features(visual.reshape(b, F // fd, visual.shape[2]), table, group)
+
     # ------------------------------------------------------------------ removing rows: the live mask, on the host
     @staticmethod
     def _pack_words(flags):
@@ -514,6 +726,8 @@ class FeatureGallery:
         new_pos = np.full(old, -1, dtype=np.int64)
         new_pos[keep] = np.arange(cnt)
         labels = self.labels[torch.from_numpy(keep)] if self._grouped else None
+        if self._window_records() is not None:
+            self._win_host = self._window_records()[keep]
         if cnt:
             index = self._host_to_device(keep)
             for name in ("_rows",) + (("_m", "_s") if self._dsl else ()):
@@ -792,6 +1006,8 @@ class FeatureGallery:
                          m=self._m[:self._n].clone(), s=self._s[:self._n].clone())
         if self._grouped:                                        # (the same: three keys more, only here)
             state.update(grouped=True, group_head=self._head[:self._n].clone(), labels=self.labels.clone())
+        if self._window_records() is not None:                   # (one key more, only once a window row exists)
+            state["windows"] = torch.from_numpy(self._window_records().copy())
         return state
 
     def load_state_dict(self, state):
@@ -816,6 +1032,10 @@ class FeatureGallery:
         live = state.get("live")
         if live is not None and (not torch.is_tensor(live) or live.dtype != torch.bool or tuple(live.shape) != (count,)):
             raise ValueError("FeatureGallery.load_state_dict: live is a bool tensor of %d entries" % count)
+        windows = state.get("windows")
+        if windows is not None and (not torch.is_tensor(windows) or windows.dtype != torch.int64
+                                    or tuple(windows.shape) != (count, 2)):
+            raise ValueError("FeatureGallery.load_state_dict: windows is a LongTensor [%d, 2]" % count)
         backend = HipBackend.with_products(int(state["products"]))
         if self._dsl:
             bank, m, s = state["bank"], state["m"], state["s"]
@@ -843,6 +1063,7 @@ class FeatureGallery:
         self._n = 0
         self._forget_removals()
         self._append(rows.to(self.device), labels)
+        self._win_host = None if windows is None else windows.cpu().numpy().copy()
         self.products, self.backend = int(state["products"]), backend
         if self._dsl:
             self._bank = None if bank is None else bank.to(self.device).clone()

@@ -1210,6 +1210,29 @@ def _(visual, mask):
     return visual.new_empty((visual.shape[0], 3 * visual.shape[2]), dtype=torch.float16)
 
 
+@custom_op(NS + "::video_window_pool_planes", mutates_args=(), device_types="cuda")
+def video_window_pool_planes(visual: torch.Tensor, windows: torch.Tensor) -> torch.Tensor:
+    """The windows of long videos: visual [Bv, S, E] fp32 per-segment features, windows [nW, 3] int32 on the device =
+    (video, start segment, stop segment) -> video-side planes [nW, 3E] fp16, row w = video_pool_normalize_planes of the
+    segments [start, stop) of that video with a mask of ones, bit for bit.  An entry outside the tensor gives a zero row."""
+    Bv, S, E = visual.shape
+    nW = windows.shape[0]
+    if (visual.dtype != torch.float32 or not visual.is_contiguous() or windows.dtype != torch.int32 or windows.dim() != 2
+            or windows.shape[1] != 3 or not windows.is_contiguous() or windows.device != visual.device):
+        raise ValueError("video_window_pool_planes: visual is contiguous fp32 [Bv, S, E] and windows contiguous int32 [nW, 3] "
+                         "on its device, not %s %s and %s %s on %s" % (visual.dtype, tuple(visual.shape), windows.dtype,
+                                                                       tuple(windows.shape), windows.device))
+    planes = _e(nW, 3 * E, like=visual, dtype=torch.float16)
+    L.check(L.lib().cc_video_window_pool_planes_f32(L.ptr(visual), L.ptr(windows), Bv, S, nW, E, L.ptr(planes), _st(visual)),
+            "cc_video_window_pool_planes_f32")
+    return planes
+
+
+@video_window_pool_planes.register_fake
+def _(visual, windows):
+    return visual.new_empty((windows.shape[0], 3 * visual.shape[2]), dtype=torch.float16)
+
+
 @custom_op(NS + "::scaled_dot_planes", mutates_args=(), device_types="cuda")
 def scaled_dot_planes(text_planes: torch.Tensor, video_planes: torch.Tensor, n_video: int, mult: float,
                       products: int = 3) -> torch.Tensor:
@@ -2064,7 +2087,7 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
        "similarity_topk_grouped", "similarity_topk_grouped_dsl", "similarity_topk_masked", "dsl_col_stats_planes_masked",
        "pack_row_mask", "similarity_rank", "similarity_topk_deep", "similarity_topk_merge", "similarity_target_score",
-       "similarity_count", "resized_crop_flip", "resized_crop_flip_out")
+       "similarity_count", "resized_crop_flip", "resized_crop_flip_out", "video_window_pool_planes")
 
 
 def logit_multiplier(logit_scale):

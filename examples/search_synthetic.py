@@ -43,6 +43,14 @@ stable sort, rows and groups; the timing is the deep call next to the same galle
 similarity() + torch.topk(k=K), and, with --baseline-lib PATH, to another build's k = 128 entry.
 
     python examples/search_synthetic.py --deep 1000 [--baseline-lib other/libcenterclip_hip.so]
+
+--windows W1,W2,... (frames, multiples of the model's frames per segment) asks "which video, and where in it": two synthetic
+videos of 10 x T frames go into a grouped gallery with FeatureGallery.add_windows - every frame encoded once, every window of
+every scale one row, a video one group - search_groups names the video and windows() the frames of its best window; then
+add_windows is timed against pushing the frames of every window through the encoder (the windows' frames cut out, laid end
+to end as clips of T frames: the encoder work of adding every window on its own), host clock around a synchronised call.
+
+    python examples/search_synthetic.py --windows 8,16 [--reps 5]
 """
 import argparse
 import os
@@ -555,6 +563,56 @@ def time_deep(model, device, rows, queries, k, reps, warmup, baseline_lib):
           % (lib.cc_similarity_topk_deep_workspace_bytes(queries, rows, E, products, k), queries * rows * 4))
 
 
+def windows_part(model, device, a):
+    """long videos as groups of sliding windows: one encode, every window's row in one launch, the frames it stands for"""
+    import time
+    scales = [int(w) for w in a.windows.split(",")]
+    T_clip, videos = int(model.video_frames), 2
+    F = 10 * T_clip
+    g = torch.Generator().manual_seed(6)
+    video = torch.randn(videos, 1, F, 3, 224, 224, generator=g).to(device)
+    lengths = [F, F - T_clip // 2]                                           # (the second one ends inside its last clip)
+    gallery = FeatureGallery(model, grouped=True)
+    pos, windows = gallery.add_windows(video, lengths, scales, group=[100, 101])
+    print("%d videos of %d frames, windows of %s frames: %d rows in %d groups, every frame encoded once"
+          % (videos, F, scales, len(gallery), gallery.num_groups))
+    ids = SyntheticRetrieval(a.captions).ids.to(device)
+    scores, groups, best = gallery.search_groups(ids, k=1)
+    frames = gallery.windows(best.cpu().reshape(-1))
+    for i in range(ids.shape[0]):
+        print("caption %d: video %d, frames [%d, %d)  score %.4f" % (i, int(groups[i, 0]), int(frames[i, 0]), int(frames[i, 1]),
+                                                                      float(scores[i, 0])))
+    # the encoder work of adding every window on its own: the windows' frames, end to end, as clips of T frames
+    index = torch.cat([v * F + torch.arange(lo, hi) for v, lo, hi in windows.tolist()])
+    index = torch.cat([index, index[:(-index.numel()) % T_clip]])            # (whole clips)
+    flat = video.reshape((videos * F,) + tuple(video.shape[3:]))
+
+    def one_encode():
+        gallery.clear()
+        gallery.add_windows(video, lengths, scales, group=[100, 101])
+
+    def every_window():
+        plain = FeatureGallery(model)
+        clips = flat[index.to(device)].reshape((-1, 1, T_clip) + tuple(flat.shape[1:]))
+        for at in range(0, clips.shape[0], 64):
+            part = clips[at:at + 64]
+            plain.add(part, torch.ones(part.shape[0], 1, T_clip, dtype=torch.long, device=device))
+
+    print("\n%d frames in the videos, %d frames in their %d windows: %d repetitions after one warm-up, host clock, synchronised"
+          % (videos * F, index.numel(), windows.shape[0], a.reps))
+    for name, fn in (("add_windows (one encode, one pooling launch)", one_encode),
+                     ("the frames of every window through the encoder", every_window)):
+        fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.reps):
+            start = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms.append(1e3 * (time.perf_counter() - start))
+        print("  %-52s median %8.1f ms   min %8.1f   max %8.1f" % (name, statistics.median(ms), min(ms), max(ms)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--clips", type=int, default=40, help="clips encoded into the gallery (0: skip the model part)")
@@ -573,10 +631,14 @@ def main():
     ap.add_argument("--baseline-lib", default="", help="--remove / --subset: another build of the library to time the unmasked op of")
     ap.add_argument("--rank", type=int, default=0, help="1: the rank of a known clip (FeatureGallery.rank), checked and timed")
     ap.add_argument("--deep", type=int, default=0, help="K > 128: a list of K entries and a cursor walk, checked and timed")
+    ap.add_argument("--windows", default="", help="W1,W2,...: windows of long videos (FeatureGallery.add_windows), frames per scale")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = bench.CFG2
     model = CLIP4Clip.from_state_dict(bench.random_state_dict(c, seed=0), bench.task_config(c)).to(device).eval()
+    if a.windows:
+        windows_part(model, device, a)
+        return
     if a.deep:
         if a.clips:
             deep_part(model, device, a.deep)

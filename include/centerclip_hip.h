@@ -777,6 +777,13 @@ int cc_normalize_rows_planes_f32(const float* in, float* out, void* planes, int3
                                  void* stream);
 int cc_video_pool_normalize_planes_f32(const float* visual, const int64_t* video_mask, int32_t Bv, int32_t Tn, int32_t E,
                                        float* pooled, void* planes, void* stream);
+/* The windows of long videos: visual [Bv, S, E] fp32 holds the per-segment features of whole videos, windows [nW, 3] int32 ON
+ * THE DEVICE = (video, start segment, stop segment); plane row w (video side) = cc_video_pool_normalize_planes_f32 on the
+ * segments [start, stop) of that video with a mask of ones, bit for bit (one wave per window, the same device code).
+ * E % 64 == 0, E <= 1024 (CC_ERR_UNSUPPORTED beyond).  The table cannot be checked on the host: an entry with video outside
+ * [0, Bv), start < 0, stop > S or start >= stop reads nothing and gives a zero row. */
+int cc_video_window_pool_planes_f32(const float* visual, const int32_t* windows, int32_t Bv, int32_t S, int32_t nW, int32_t E,
+                                    void* planes, void* stream);
 int cc_scaled_dot_planes_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv,
                              int32_t video_rows, int32_t E, float mult, float* logits, int32_t ldl, void* stream);
 int cc_scaled_dot_planes_products_f32(const void* text_planes, const void* video_planes, int32_t Bt, int32_t Bv,
