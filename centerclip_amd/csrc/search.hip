@@ -1,28 +1,73 @@
-// Exact top-k retrieval over cached similarity operands on gfx950: the k best gallery rows per query row and their scores,
-// without the [Bq, Bg] matrix.  The operands are the split-fp16 planes of similarity.hip; a score is what
-// cc_scaled_dot_planes_products_f32 stores for the same pair, bit for bit: ONE fp32 accumulator per (query, gallery row) fed
-// by v_mfma_f32_16x16x32_f16 over the 32-wide k-slices in ascending order with the gallery fragment as the first operand
-// (gemm.hip: mfma(bf, af, acc) for ks = 0, 1 of every k-step), then sc * acc with sc = mult * 2^-20.
+// Exact retrieval over cached similarity operands on gfx950 without the [Bq, Bg] matrix: the k best gallery rows (or groups of
+// rows) per query row, the rank of a known row or group, and the dual-softmax statistics.  The operands are the split-fp16
+// planes of similarity.hip; a score is what cc_scaled_dot_planes_products_f32 stores for the same pair, bit for bit: ONE fp32
+// accumulator per (query, gallery row) fed by v_mfma_f32_16x16x32_f16 over the 32-wide k-slices in ascending order with the
+// gallery fragment as the first operand (gemm.hip: mfma(bf, af, acc) for ks = 0, 1 of every k-step), then sc * acc with
+// sc = mult * 2^-20.
 //
-// Two launches; no workgroup reads what another workgroup of the same launch wrote (the per-XCD L2s are not coherent, the
-// kernel boundary is the hand-over):
-//   1. topk_stream_kernel, grid (gallery slices) x (groups of 16 query rows), 4 waves.  The 16 query rows are staged once
-//      in LDS.  A wave multiplies whole 16-row gallery tiles: its fragments go from global memory straight to registers
-//      (16-byte loads; the two k-slices of a 128-byte line are requested back to back).  Per query row every wave keeps a
-//      descending list of its k best in LDS and, in a register, the row's k-th key.  After a tile the lanes compare their
-//      4 values with that threshold, a wave-wide ballot says whether any survived, and the survivors of all 16 query rows
-//      are inserted side by side, 4 lanes a list (tk_insert_tile).  At the end the four waves' lists are folded into one per
-//      query row and written to the workspace: [Bq][k][slices] keys.
-//   2. topk_merge_kernel, one wave per query row: the slices' lists -> the final k, decoded into scores / ids.
-// A (score, id) pair is ONE 64-bit key whose unsigned order is the result's order (larger score first, equal scores by
-// smaller id; -0 and +0 equal), so ties never need a second look and the lists of any split merge to the same result.
+// The structure, from the inside out:
 //
-// camoe_dsl (dual softmax) on the same stream, still without the matrix:
-//   * topk_stream_kernel<true> ranks D = cc_dsl_value(n_total, S, m_x, s_x) - the expression dsl_apply_kernel evaluates, so the
-//     bits cc_dsl_apply_f32 writes over the matrix op's entry - with x the gallery row or the query row.  A compile-time
-//     mode: topk_stream_kernel<false> is the plain kernel.
-//   * dsl_stats_stream_kernel gives the pair (m, s) of every VIDEO row over many text rows: the video rows take the place of
-//     the queries (16 staged in LDS), the text rows are streamed, and a running log-sum-exp pair replaces the lists.
+// THE STREAM (tk_stream_tiles).  Grid (gallery slices) x (groups of 16 query rows), 4 waves; the 16 query rows are staged once
+// in LDS (tk_stage_rows).  A wave multiplies whole 16-row gallery tiles: its fragments go from global memory straight to
+// registers (16-byte loads; the two k-slices of a 128-byte line are requested back to back), two register buffers taking
+// turns.  Which tiles a wave takes comes from a rule: TkEvery (all of them) or TkLive (under ONE row mask, the tiles with a
+// selectable row: a dead tile is neither requested nor multiplied).  The request that overlaps a tile's last batch is
+// unconditional - the rule only says WHICH tile - for the reason tk_stream_tiles gives.
+//
+// THE PRODUCER OF CANDIDATES (tk_candidates<DSL, GROUPED, MASK>), written once for every search and count.  It owns the split
+// of a slice's tiles over the waves, the query row's statistics and the per-tile loads (gallery statistics, heads, mask word -
+// all requested in before_last, in front of the load that overlaps the tile's last batch), the score, the selectable
+// predicate, and in grouped mode the folding of rows into groups:
+//   * the score is sc * acc; DSL: D = cc_dsl_value(n_total, S, m_x, s_x) - the expression dsl_apply_kernel evaluates, so the
+//     bits cc_dsl_apply_f32 writes over the matrix op's entry - with x the gallery row or the query row;
+//   * MASK: a bit per gallery row - one mask for all queries (1), or one per query row (2) - says whether the row may be
+//     ranked; a row that may not is no candidate.  That is the whole rule in every DSL x GROUPED combination;
+//   * rows mode hands the consumer, per tile, the lane's 4 scores, their row ids and whether each is selectable;
+//   * GROUPED (the k best GROUPS of adjacent rows, each by its best row): a wave takes one contiguous row range between group
+//     starts instead of interleaved tiles, and the consumer gets one candidate key per finished group (tk_group_tile) and, once,
+//     the group open at the range's end - so every group lives in one wave.
+// Two consumers:
+//   * the LISTS (topk_stream_kernel).  Per query row every wave keeps a descending list of its k best in LDS and, in a
+//     register, the row's k-th key.  After a tile the lanes compare their 4 keys with that threshold, a wave-wide ballot says
+//     whether any survived, and the survivors of all 16 query rows are inserted side by side, 4 lanes a list (tk_insert_tile).
+//     At the end the four waves' lists are folded into one per query row and written to the workspace: [Bq][k][slices] keys.
+//     BOUND is this consumer's: a candidate is kept only if key < bound[q].
+//   * the COUNTS (rank_stream_kernel).  Three integers a lane against a score t_q - candidates above it, equal to it, equal in
+//     front - so LDS is the staged rows alone; plain float compares on the score the producer hands over.  COUNT (the bound
+//     comes from the caller, not from a target) is this consumer's.
+//
+// THE KEY.  A (score, id) pair is ONE 64-bit key whose unsigned order is the result's order (larger score first, equal scores
+// by smaller id; -0 and +0 equal), so ties never need a second look and the lists of any split merge to the same result.  Key
+// 0 is the empty entry.
+//
+// THE MERGES.  No workgroup reads what another workgroup of the same launch wrote (the per-XCD L2s are not coherent, the kernel
+// boundary is the hand-over), so every result takes a second launch:
+//   * topk_merge_kernel, one wave per query row: the slices' lists -> the final k, decoded into scores / ids;
+//   * rank_reduce_kernel adds the slices' partial counts.  Integers: any split of the gallery sums to the same result;
+//   * topk_merge_lists_kernel merges the lists of a gallery split in shards (each shard one buffer, searched and counted on
+//     its own; the results are those of the shards' concatenation), ties by smaller shard, then smaller local id - the order
+//     the concatenated positions would give.
+//
+// Deep lists and cursors (more than TK_MAXK entries, or the entries behind a known one): a list is a chain of PAGES of at most
+// TK_MAXK entries, each the list stream restricted to the keys BELOW a per-query bound - the last key of the page before, or
+// the key of a (score, id) pair the caller holds.  Keys are unique and their unsigned order is the result's order, so "the
+// keys below X" is exact and needs no state.  Bound 0 keeps nothing.  GROUPED applies the bound to the finished group's
+// candidate, never to a row - a group whose best row lies at or above the bound was handed out before and must not return
+// through its second-best row.  topk_merge_kernel writes a page at its column offset of the [Bq, k] result and its last key to
+// bound[q] for the page after it: the pages of a call hand over on the device.  A list of at most TK_MAXK entries without a
+// cursor is one page.
+//
+// The rank of a known row or group (where does THIS row stand for THIS query): three launches.  rank_target_kernel computes
+// t_q, the score of every query row's target, with the MFMA sequence of the stream (so the bits are those of every other
+// score); the count stream counts against it; rank_reduce_kernel adds up.  For a gallery split in shards rank_target_kernel
+// behind an entry of its own gives the owner's t_q, and the COUNT mode counts a shard against that score and a `front`
+// position the caller sets (the target's row on its owner, 0 on the shards behind it, 2^31 - 1 on those in front): the counts
+// of the shards add up to the counts of the whole.
+//
+// The dual-softmax statistics (dsl_stats_stream_kernel): the pair (m, s) of every VIDEO row over many text rows on the same
+// stream - the video rows take the place of the queries (16 staged in LDS), the text rows are streamed, and a running
+// log-sum-exp pair is the consumer; with a mask, masked text rows are left out the way the producer leaves rows out (TkLive,
+// the tile's mask word).
 //     Summation tree of one video row (fixed; no atomics; it depends on Bt alone, never on Bv or on the row's place):
 //       - the text tiles are cut into dsl_stats_slices(Bt) contiguous slices, a workgroup each; wave w takes tiles
 //         t0 + w, t0 + w + 4, ... of its slice, and in a tile the lane group lg holds text rows 16 t + 4 lg + {0, 1, 2, 3};
@@ -35,38 +80,7 @@
 //     The subtractions inside expf telescope: the partial maxima rise from x to m, so together they cost |x - m| U on the
 //     exponent.  Longest chain of roundings: 7 * ceil(ceil(tiles / slices) / 4) + 19 + slices + 3.
 //
-// Grouped search (the k best GROUPS of adjacent rows, each by its best row) on the same stream: topk_stream_kernel<DSL, true>,
-// a second compile-time mode.  A row's score is computed as before; a wave then takes one contiguous row range between group
-// starts instead of interleaved tiles and hands tk_insert_tile one candidate per finished group (tk_group_tile), so every
-// group lives in one list of one wave and the fold, the workspace and the merge launch are unchanged.
-//
-// Masked search (rows taken out of a gallery, a subset of it): topk_stream_kernel<DSL, GROUPED, MASK>, a third compile-time
-// mode.  A bit per gallery row - one mask for all queries, or one per query row - says whether the row may be ranked; a row
-// that may not gets key 0, the empty entry.  With ONE mask a 16-row tile without a selectable row is neither requested nor
-// multiplied: tk_stream_tiles takes its tiles from a rule (TkEvery / TkLive), and dsl_stats_stream_kernel<true> leaves masked
-// text rows out of the statistics the same way.  pack_row_mask_kernel turns byte flags into mask words.
-//
-// Rank of a known row or group (where does THIS row stand for THIS query), still without the matrix: three launches.
-// rank_target_kernel computes t_q, the score of every query row's target, with the MFMA sequence of the stream (so the bits are
-// those of every other score); rank_stream_kernel<DSL, GROUPED, MASK> is a new consumer of tk_stream_tiles on the same grid
-// that counts, per query row, the candidates above t_q, equal to it, and equal in front of the target - three integers a lane
-// instead of the lists, so LDS is the staged rows alone; rank_reduce_kernel adds the slices' partial counts.  Integers: any
-// split of the gallery sums to the same result.
-//
-// Deep lists and cursors (more than TK_MAXK entries, or the entries behind a known one), still without the matrix: a list is a
-// chain of PAGES of at most TK_MAXK entries, each the stream above restricted to the keys BELOW a per-query bound - the last
-// key of the page before, or the key of a (score, id) pair the caller holds.  Keys are unique and their unsigned order is the
-// result's order, so "the keys below X" is exact and needs no state.  topk_stream_kernel<DSL, GROUPED, MASK, true>, a fourth
-// compile-time mode: a candidate is kept only if key < bound[q] (bound 0 keeps nothing); GROUPED applies it to the finished
-// group's candidate, never to a row - a group whose best row lies at or above the bound was handed out before and must not
-// return through its second-best row.  topk_merge_kernel writes a page at its column offset of the [Bq, k] result and its last
-// key to bound[q] for the page after it: the pages of a call hand over on the device.
-//
-// A gallery split in shards (each shard one buffer, searched and counted on its own; the results are those of the shards'
-// concatenation): topk_merge_lists_kernel merges the shards' lists, ties by smaller shard, then smaller local id - the order the
-// concatenated positions would give; rank_target_kernel behind an entry of its own gives the owner's t_q, and rank_stream_kernel's
-// COUNT mode counts a shard against that score and a `front` position the caller sets (the target's row on its owner, 0 on the
-// shards behind it, 2^31 - 1 on those in front): the counts of the shards add up to the counts of the whole.
+// pack_row_mask_kernel turns byte flags into mask words.
 #include <type_traits>
 
 #include "cc_kernels.h"
@@ -201,8 +215,8 @@ __device__ __forceinline__ void tk_stage_rows(_Float16* qs, const _Float16* __re
 }
 
 // Which tiles a wave streams, in which order: the "next tile" rule of tk_stream_tiles.
-// TkEvery: the tiles first, first + stride, ... < t1.  It only names them: tk_stream_tiles keeps the arithmetic it always had
-// for them (count, last tile, t + stride), spelled where it was, so the unmasked kernels compile to the code they were.
+// TkEvery: the tiles first, first + stride, ... < t1.  It only names them: tk_stream_tiles does their arithmetic (count, last
+// tile, t + stride) in place, with no state to carry.
 struct TkEvery {
     int first, stride, t1;
 };
@@ -360,32 +374,162 @@ __device__ __forceinline__ void tk_group_tile(u64 (&key)[4], const bool (&head)[
     }
 }
 
-// What a masked stream carries from tile to tile (nothing without a mask): the lane's mask row, the word of it that holds the
-// tile's 16 bits, and - grouped search under one mask - the tile streamed before and the head of the row in front of this one
-template <int MASK>
-struct TkMaskState {
-    const int* row;
-    int word = 0, prev = 0, gap_head = 0;
-};
-template <>
-struct TkMaskState<0> {};
+// The contiguous share of the 16-row tiles of `rows` rows that slice `slice` of `slices` takes: [t0, t1).  -> all tiles.
+__device__ __forceinline__ int tk_slice_tiles(int rows, int slice, int slices, int& t0, int& t1) {
+    const int tiles = (rows + 15) >> 4;
+    t0 = (int)((int64_t)tiles * slice / slices);
+    t1 = (int)((int64_t)tiles * (slice + 1) / slices);
+    return tiles;
+}
 
-// query / gallery: plane rows `ld` halfs apart, the first K of them multiplied.  ws [Bq][k][slices] keys.  DSL: the score is
-// cc_dsl_value(nt, S, m, s) with the pair of the gallery row (on_gallery) or of the query row; without DSL those four
-// arguments are not read.  GROUPED: group_head[r] = the first row of r's group (the rows of a group are adjacent); a list
-// then holds the best row of every group, not every row.  Instead of the interleaved tiles of its slice a wave takes ONE
-// contiguous row range whose ends are group starts: the 4 * slices + 1 even shares of the tiles, each planned row b snapped
-// down to group_head[b] (monotone; a range may be empty; a group longer than a share belongs wholly to the range that
-// starts at its head).  Every group lives in one wave, so the fold, the workspace and the merge launch see lists whose
-// groups are disjoint and work unchanged.  Only the snapping indexes with a value of group_head, and clamps it to [0, b].
-// MASK: a third compile-time mode - 0 every row may be ranked (row_mask, mask_words are not read), 1 row_mask is ONE mask row
-// for all queries, 2 one per query row, mask_words apart (bit b of word w = row 32 w + b; bits at Bg or above are ignored).
-// A row whose bit is 0 gets key 0, the empty entry: that is the whole ranking rule in every DSL x GROUPED combination, and the
-// fold, the workspace and the merge never know.  Statistics and heads are indexed as without a mask.  MASK == 1 streams the
-// live tiles only (TkLive); MASK == 2 skips nothing.  GROUPED with dead tiles: see on_tile.
-// BOUND: a fourth compile-time mode - a candidate of query row q is kept only if its key is below bound[q] (0: nothing is
-// kept); without GROUPED a candidate is a row, with it the finished group tk_group_tile hands over (and the carry at the
-// range's end), so the rows of a group are folded before the bound looks at it.  Without BOUND `bound` is not read.
+// The bit of row 4 lg + r of tile t in `word`, the mask word that holds the tile's 16 bits (word t >> 1 of the mask row).
+__device__ __forceinline__ bool tk_mask_bit(int word, int t, int lg, int r) { return (word >> ((t & 1) * 16 + lg * 4 + r)) & 1; }
+
+// tk_stream_tiles over the tiles first, first + stride, ... < t1 - LIVE: of those the live ones under the one mask row `mask`
+template <bool LIVE, class Before, class Tile>
+__device__ __forceinline__ void tk_stream_rule(const _Float16* __restrict__ gallery, int Bg, int ld, int K, const _Float16* qrow,
+                                               const int* __restrict__ mask, int first, int stride, int t1, Before&& before_last,
+                                               Tile&& on_tile) {
+    const int lane = threadIdx.x & 63, l15 = lane & 15, lg = lane >> 4;
+    if constexpr (LIVE) tk_stream_tiles(gallery, Bg, ld, K, qrow, TkLive(mask, first, stride, t1, lane), l15, lg, before_last, on_tile);
+    else tk_stream_tiles(gallery, Bg, ld, K, qrow, TkEvery{first, stride, t1}, l15, lg, before_last, on_tile);
+}
+
+// What the producer of candidates reads: the gallery side of a search or count kernel's arguments and the block's slice.
+// gallery: plane rows `ld` halfs apart, the first K of them multiplied.  DSL: the score is cc_dsl_value(nt, S, m, s) with the
+// pair of the gallery row (on_gallery) or of the query row; without DSL those four are not read.  GROUPED: group_head[r] = the
+// first row of r's group (the rows of a group are adjacent).  MASK: 0 every row may be ranked (row_mask, mask_words are not
+// read), 1 row_mask is ONE mask row for all queries, 2 one per query row, mask_words apart (bit b of word w = row 32 w + b;
+// bits at Bg or above are ignored).
+struct TkSource {
+    const _Float16* __restrict__ gallery;
+    int Bg, ld, K;
+    float sc;
+    int slice, slices;
+    const float* __restrict__ stat_m;
+    const float* __restrict__ stat_s;
+    int on_gallery;
+    float nt;
+    const int* __restrict__ group_head;
+    const int* __restrict__ row_mask;
+    int mask_words;
+};
+
+// The candidates of one wave for the 16 rows staged in `qs` ([16][K + TK_QPAD]); the lane works for staged row l15, query row
+// `qr` (clamped into [0, Bq): its statistics and its mask row), and `qvalid` says whether that row has candidates at all.
+// Rows mode: the wave streams the tiles t0 + wave, t0 + wave + 4, ... of its slice and on_rows(x, id, in) gets, per tile, the
+// lane's 4 scores x[r] of gallery rows id[r] and in[r]: the row is a candidate (qvalid, below Bg, its mask bit set).
+// GROUPED: instead of the interleaved tiles a wave takes ONE contiguous row range whose ends are group starts: the
+// 4 * slices + 1 even shares of the tiles, each planned row b snapped down to group_head[b] (monotone; a range may be empty; a
+// group longer than a share belongs wholly to the range that starts at its head).  A row outside the range or not selectable
+// gets key 0, the empty key; on_groups(key) gets what tk_group_tile hands out - at most one candidate a row, the best key of
+// the group that ends in front of it - and once, behind the range, the group still open in key[0] of lane group 0.  Every
+// group lives in one wave.  Only the snapping indexes with a value of group_head, and clamps it to [0, b].
+// Statistics and heads are indexed as without a mask.  MASK == 1 streams the live tiles only (TkLive); MASK == 2 skips nothing.
+template <bool DSL, bool GROUPED, int MASK, class Rows, class Groups>
+__device__ __forceinline__ void tk_candidates(const TkSource& a, const _Float16* qs, int qr, bool qvalid, Rows&& on_rows,
+                                              Groups&& on_groups) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
+    const int Bg = a.Bg;
+    int t0, t1;
+    const int tiles = tk_slice_tiles(Bg, a.slice, a.slices, t0, t1);
+    // DSL: the statistics of the lane's 4 gallery rows (requested per tile) or of its query row (once)
+    float dm[4] = {0.f, 0.f, 0.f, 0.f}, ds[4] = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (DSL) {
+        if (!a.on_gallery) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { dm[r] = a.stat_m[qr]; ds[r] = a.stat_s[qr]; }
+        }
+    }
+    // GROUPED: the wave's row range [r0, r1) and the open group's best key (tk_group_tile); the lane's 4 heads come per tile
+    int first = t0 + wave, last = t1, r0 = 0, r1 = Bg;
+    u64 carry = 0;
+    int gh[4] = {0, 0, 0, 0};
+    if constexpr (GROUPED) {
+        auto bound = [&](int j) {
+            if (j <= 0) return 0;
+            if (j >= TK_WAVES * a.slices) return Bg;
+            const int b = min((int)((int64_t)tiles * j / (TK_WAVES * a.slices)) * 16, Bg - 1);
+            return min(max(a.group_head[b], 0), b);                                    // (a malformed head stays inside the rows)
+        };
+        r0 = bound(TK_WAVES * a.slice + wave);
+        r1 = bound(TK_WAVES * a.slice + wave + 1);
+        first = r0 >> 4;
+        last = r1 > r0 ? (r1 + 15) >> 4 : first;                                       // the tile at a boundary: both neighbours' work
+    }
+    // MASK: the mask word that holds the tile's 16 bits comes per tile, from the one mask row or from query row qr's.
+    // GROUPED, MASK == 1: the tile streamed before this one, and the head of the row in front of this one (per tile)
+    const int* mrow = a.row_mask;
+    if constexpr (MASK == 2) mrow += (int64_t)qr * a.mask_words;
+    int word = 0, prev = first - 1, gap_head = 0;
+    auto before_last = [&](int t) {
+        if constexpr (MASK != 0) word = mrow[t >> 1];                                  // (t < tiles: inside ceil(Bg / 32) words)
+        if constexpr (GROUPED && MASK == 1) gap_head = a.group_head[min(max(t * 16 - 1, 0), Bg - 1)];
+        if constexpr (DSL) {
+            if (a.on_gallery) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int id = min(t * 16 + lg * 4 + r, Bg - 1);                   // statistics at Bg or above are never read
+                    dm[r] = a.stat_m[id];
+                    ds[r] = a.stat_s[id];
+                }
+            }
+        }
+        if constexpr (GROUPED) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gh[r] = a.group_head[min(t * 16 + lg * 4 + r, Bg - 1)];    // nor heads
+        }
+    };
+    auto on_tile = [&](int t, const f32x4& acc) {
+        // the lane holds gallery rows t * 16 + 4 lg + r (r = 0..3) of staged row l15
+        float x[4];
+        int id[4];
+        bool in[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            id[r] = t * 16 + lg * 4 + r;
+            x[r] = a.sc * acc[r];
+            if constexpr (DSL) x[r] = cc_dsl_value(a.nt, x[r], dm[r], ds[r]);
+            in[r] = qvalid && (GROUPED ? (id[r] >= r0 && id[r] < r1) : id[r] < Bg);
+            if constexpr (MASK != 0) in[r] = in[r] && tk_mask_bit(word, t, lg, r);
+        }
+        if constexpr (GROUPED) {
+            u64 key[4];
+            bool head[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                key[r] = in[r] ? tk_key(x[r], id[r]) : 0;
+                head[r] = gh[r] == id[r];
+            }
+            if constexpr (MASK == 1) {
+                // Dead tiles between the tile streamed before and this one were skipped, heads included.  If a group starts in
+                // them (the head of the row in front of this tile lies behind the tile streamed before), the group open in front
+                // of them ends there, and this tile's rows up to its first head belong to a group whose earlier rows are all
+                // unselectable: both are what a head at the tile's first row says.  (A gap lies inside the wave's range; a group
+                // none of whose rows is selectable only ever holds key 0 and never becomes a candidate.)
+                if (lg == 0 && t > prev + 1 && gap_head >= (prev + 1) * 16) head[0] = true;
+                prev = t;
+            }
+            tk_group_tile(key, head, lg, carry);
+            on_groups(key);
+        } else {
+            on_rows(x, id, in);
+        }
+    };
+    tk_stream_rule<MASK == 1>(a.gallery, Bg, a.ld, a.K, qs + l15 * (a.K + TK_QPAD) + lg * 8, a.row_mask, first,
+                              GROUPED ? 1 : TK_WAVES, last, before_last, on_tile);
+    if constexpr (GROUPED) {
+        u64 key[4] = {lg == 0 ? carry : 0, 0, 0, 0};                                   // the group open at the range's end
+        on_groups(key);
+    }
+}
+
+// The lists: stage the query rows, clear the lists, insert what the producer hands over, fold, write.  query: plane rows as
+// the gallery's.  ws [Bq][k][slices] keys.  The fold, the workspace and the merge launch never know the mode: a row that may
+// not be ranked is no candidate, and with GROUPED the lists hold groups that are disjoint between the waves.
+// BOUND: a candidate of query row q is kept only if its key is below bound[q] (0: nothing is kept); without GROUPED a
+// candidate is a row, with it the finished group the producer hands over (and the one open at the range's end), so the rows
+// of a group are folded before the bound looks at it.  Without BOUND `bound` is not read.
 template <bool DSL, bool GROUPED, int MASK, bool BOUND>
 __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
                                                           int Bq, int Bg, int ld, int K, float sc, int k, int slices,
@@ -396,119 +540,36 @@ __global__ __launch_bounds__(256) void topk_stream_kernel(const _Float16* __rest
     extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
     const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
-    const int QS = K + TK_QPAD;
-    _Float16* qs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][QS]
-    u64* lists = reinterpret_cast<u64*>(tk_smem + (size_t)TK_QROWS * QS * 2);          // [wave][16][k]
+    _Float16* qs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][K + TK_QPAD]
+    u64* lists = reinterpret_cast<u64*>(tk_smem + (size_t)TK_QROWS * (K + TK_QPAD) * 2);     // [wave][16][k]
     tk_stage_rows(qs, query, q0, Bq, ld, K);
     for (int i = threadIdx.x; i < TK_WAVES * TK_QROWS * k; i += 256) lists[i] = 0;
     __syncthreads();
 
     u64* mine = lists + ((size_t)wave * TK_QROWS + l15) * k;                           // this wave's list of query row l15
-    const int tiles = (Bg + 15) >> 4;
-    const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
-    const bool qvalid = q0 + l15 < Bq;
+    const int qr = min(q0 + l15, Bq - 1);
     u64 thr = 0;                                                                       // the k-th key of `mine`
     int filled = 0;                                                                    // entries any of the wave's lists holds, at most
     u64 below = 0;                                                                     // BOUND: query row l15's bound
-    if constexpr (BOUND) below = bound[min(q0 + l15, Bq - 1)];
-    // DSL: the statistics of the lane's 4 gallery rows (requested per tile) or of its query row (once)
-    float dm[4] = {0.f, 0.f, 0.f, 0.f}, ds[4] = {1.f, 1.f, 1.f, 1.f};
-    if constexpr (DSL) {
-        if (!on_gallery) {
-            const int qr = min(q0 + l15, Bq - 1);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { dm[r] = stat_m[qr]; ds[r] = stat_s[qr]; }
-        }
-    }
-    // GROUPED: the wave's row range [r0, r1) and the open group's best key (tk_group_tile); the lane's 4 heads come per tile
-    int first = t0 + wave, last = t1, r0 = 0, r1 = Bg;
-    u64 carry = 0;
-    int gh[4] = {0, 0, 0, 0};
-    if constexpr (GROUPED) {
-        auto bound = [&](int j) {
-            if (j <= 0) return 0;
-            if (j >= TK_WAVES * slices) return Bg;
-            const int b = min((int)((int64_t)tiles * j / (TK_WAVES * slices)) * 16, Bg - 1);
-            return min(max(group_head[b], 0), b);                                      // (a malformed head stays inside the rows)
-        };
-        r0 = bound(TK_WAVES * slice + wave);
-        r1 = bound(TK_WAVES * slice + wave + 1);
-        first = r0 >> 4;
-        last = r1 > r0 ? (r1 + 15) >> 4 : first;                                       // the tile at a boundary: both neighbours' work
-    }
-    // MASK: the mask word that holds the tile's 16 bits comes per tile, from the one mask row or from query row l15's (a
-    // query row at Bq or above: clamped, as its statistics).  GROUPED, MASK == 1: the tile streamed before this one, and the
-    // head of the row in front of this one (per tile)
-    TkMaskState<MASK> ms;
-    if constexpr (MASK != 0) {
-        ms.row = row_mask;
-        if constexpr (MASK == 2) ms.row += (int64_t)min(q0 + l15, Bq - 1) * mask_words;
-        ms.prev = first - 1;
-    }
-    auto before_last = [&](int t) {
-        if constexpr (MASK != 0) ms.word = ms.row[t >> 1];                             // (t < tiles: inside ceil(Bg / 32) words)
-        if constexpr (GROUPED && MASK == 1) ms.gap_head = group_head[min(max(t * 16 - 1, 0), Bg - 1)];
-        if constexpr (DSL) {
-            if (on_gallery) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int id = min(t * 16 + lg * 4 + r, Bg - 1);                   // statistics at Bg or above are never read
-                    dm[r] = stat_m[id];
-                    ds[r] = stat_s[id];
-                }
-            }
-        }
-        if constexpr (GROUPED) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) gh[r] = group_head[min(t * 16 + lg * 4 + r, Bg - 1)];      // nor heads
-        }
+    if constexpr (BOUND) below = bound[qr];
+    auto keep = [&](u64 key) {                                                         // a candidate that passes the bound, or 0
+        if constexpr (BOUND) return key < below ? key : 0;
+        else return key;
     };
-    auto on_tile = [&](int t, const f32x4& acc) {
-        // the lane holds gallery rows t * 16 + 4 lg + r (r = 0..3) of query row l15
-        u64 key[4];
-        bool head[4];
+    const TkSource src{gallery, Bg, ld, K, sc, slice, slices, stat_m, stat_s, on_gallery, nt, group_head, row_mask, mask_words};
+    tk_candidates<DSL, GROUPED, MASK>(
+        src, qs, qr, q0 + l15 < Bq,
+        [&](const float (&x)[4], const int (&id)[4], const bool (&in)[4]) {
+            u64 key[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int id = t * 16 + lg * 4 + r;
-            float x = sc * acc[r];
-            if constexpr (DSL) x = cc_dsl_value(nt, x, dm[r], ds[r]);
-            if constexpr (GROUPED) {
-                key[r] = (qvalid && id >= r0 && id < r1) ? tk_key(x, id) : 0;
-                head[r] = gh[r] == id;
-            } else {
-                key[r] = (qvalid && id < Bg) ? tk_key(x, id) : 0;
-            }
-            if constexpr (MASK != 0) key[r] = ((ms.word >> ((t & 1) * 16 + lg * 4 + r)) & 1) ? key[r] : 0;
-            if constexpr (BOUND && !GROUPED) key[r] = key[r] < below ? key[r] : 0;
-        }
-        if constexpr (GROUPED && MASK == 1) {
-            // Dead tiles between the tile streamed before and this one were skipped, heads included.  If a group starts in
-            // them (the head of the row in front of this tile lies behind the tile streamed before), the group open in front
-            // of them ends there, and this tile's rows up to its first head belong to a group whose earlier rows are all
-            // unselectable: both are what a head at the tile's first row says.  (A gap lies inside the wave's range; a group
-            // none of whose rows is selectable only ever holds key 0 and never becomes a candidate.)
-            if (lg == 0 && t > ms.prev + 1 && ms.gap_head >= (ms.prev + 1) * 16) head[0] = true;
-            ms.prev = t;
-        }
-        if constexpr (GROUPED) tk_group_tile(key, head, lg, carry);
-        if constexpr (BOUND && GROUPED) {
+            for (int r = 0; r < 4; ++r) key[r] = keep(in[r] ? tk_key(x[r], id[r]) : 0);
+            tk_insert_tile(key, mine, k, lg, thr, filled);
+        },
+        [&](u64 (&key)[4]) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) key[r] = key[r] < below ? key[r] : 0;          // the finished groups, not their rows
-        }
-        tk_insert_tile(key, mine, k, lg, thr, filled);
-    };
-    constexpr int stride = GROUPED ? 1 : TK_WAVES;
-    if constexpr (MASK == 1) {
-        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, TkLive(row_mask, first, stride, last, lane), l15, lg, before_last,
-                        on_tile);
-    } else {
-        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, TkEvery{first, stride, last}, l15, lg, before_last, on_tile);
-    }
-    if constexpr (GROUPED) {
-        u64 key[4] = {lg == 0 ? carry : 0, 0, 0, 0};                                   // the group open at the range's end
-        if constexpr (BOUND) key[0] = key[0] < below ? key[0] : 0;
-        tk_insert_tile(key, mine, k, lg, thr, filled);
-    }
+            for (int r = 0; r < 4; ++r) key[r] = keep(key[r]);                         // the finished groups, not their rows
+            tk_insert_tile(key, mine, k, lg, thr, filled);
+        });
     // the four waves' lists -> wave 0's, as a tree: the other wave's entries are the candidates, 16 a list at a time
     auto fold = [&](int from) {
         const u64* other = lists + ((size_t)from * TK_QROWS + l15) * k;
@@ -679,20 +740,18 @@ __global__ __launch_bounds__(256) void rank_target_kernel(const _Float16* __rest
     }
 }
 
-// Second launch: the counts, a new consumer of tk_stream_tiles on topk_stream_kernel's grid (gallery slices x groups of 16
-// query rows, 4 waves, the 16 query rows staged in LDS; the DSL / GROUPED / MASK modes, the wave's tiles or row range, the
-// statistics, heads and mask words per tile are that kernel's, spelled again here so that its instantiations stay the code they
-// were).  In place of the lists every lane keeps three integers for query row l15 against t = tscore[q]: candidates with
-// x > t, with x == t, and with x == t in front of the target (rows mode: a candidate is a selectable row < Bg, in front =
-// its index below target[q]; GROUPED: a candidate is what tk_group_tile hands out - the best key of a finished group, 0 for
-// one without a selectable row - plus the carry at the range's end, in front = its row below the target group's head).  Plain
-// float compares, as rank_counts_kernel: -0 == +0, a NaN is neither greater nor equal.  A query row whose target is outside
-// [0, Bg) counts nothing.  At the end the 4 lanes of a query row and the 4 waves are added: part [Bq][3][slices].
-// COUNT: a fourth compile-time mode - the bound comes from the caller instead of a target (cc_similarity_count_planes_f32):
-// `tscore` holds the bound's score and `target` the position in front of which an equal candidate counts as "in front", taken as
-// it is (no group_head look-up, no upper limit: a position at Bg or above puts every equal candidate in front; a negative one
-// makes the query row count nothing).  Without COUNT the kernel is the code it was.
-template <bool DSL, bool GROUPED, int MASK, bool COUNT = false>
+// Second launch: the counts, on topk_stream_kernel's grid: stage the query rows, count what the producer hands over, reduce,
+// write.  Every lane keeps three integers for query row l15 against t = tscore[q]: candidates with x > t, with x == t, and with
+// x == t in front of the target (rows mode: a candidate is a selectable row < Bg, in front = its index below target[q];
+// GROUPED: a candidate is a key the producer hands over - the best key of a finished group, 0 for one without a selectable
+// row - in front = its row below the target group's head).  Plain float compares, as rank_counts_kernel: -0 == +0, a NaN is
+// neither greater nor equal; in rows mode the score never passes through a key.  A query row whose target is outside [0, Bg)
+// counts nothing.  At the end the 4 lanes of a query row and the 4 waves are added: part [Bq][3][slices].
+// COUNT: the bound comes from the caller instead of a target (cc_similarity_count_planes_f32): `tscore` holds the bound's score
+// and `target` the position in front of which an equal candidate counts as "in front", taken as it is (no group_head look-up,
+// no upper limit: a position at Bg or above puts every equal candidate in front; a negative one makes the query row count
+// nothing).
+template <bool DSL, bool GROUPED, int MASK, bool COUNT>
 __global__ __launch_bounds__(256) void rank_stream_kernel(const _Float16* __restrict__ query, const _Float16* __restrict__ gallery,
                                                           int Bq, int Bg, int ld, int K, float sc, int slices,
                                                           const int* __restrict__ target, const float* __restrict__ tscore,
@@ -704,13 +763,10 @@ __global__ __launch_bounds__(256) void rank_stream_kernel(const _Float16* __rest
     __shared__ int pc[TK_WAVES][3][TK_QROWS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, l15 = lane & 15, lg = lane >> 4;
     const int slice = blockIdx.x, q0 = blockIdx.y * TK_QROWS;
-    const int QS = K + TK_QPAD;
-    _Float16* qs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][QS]
+    _Float16* qs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][K + TK_QPAD]
     tk_stage_rows(qs, query, q0, Bq, ld, K);
     __syncthreads();
 
-    const int tiles = (Bg + 15) >> 4;
-    const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
     const int qr = min(q0 + l15, Bq - 1);
     const int tg = target[qr];
     const bool qvalid = q0 + l15 < Bq && tg >= 0 && (COUNT || tg < Bg);
@@ -718,98 +774,27 @@ __global__ __launch_bounds__(256) void rank_stream_kernel(const _Float16* __rest
     int front = tg;                                                                    // a candidate row below it lies in front
     if constexpr (GROUPED && !COUNT) front = min(max(group_head[min(max(tg, 0), Bg - 1)], 0), tg);
     int gt = 0, eq = 0, before = 0;
-    float dm[4] = {0.f, 0.f, 0.f, 0.f}, ds[4] = {1.f, 1.f, 1.f, 1.f};
-    if constexpr (DSL) {
-        if (!on_gallery) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) { dm[r] = stat_m[qr]; ds[r] = stat_s[qr]; }
-        }
-    }
-    int first = t0 + wave, last = t1, r0 = 0, r1 = Bg;
-    u64 carry = 0;
-    int gh[4] = {0, 0, 0, 0};
-    if constexpr (GROUPED) {
-        auto bound = [&](int j) {
-            if (j <= 0) return 0;
-            if (j >= TK_WAVES * slices) return Bg;
-            const int b = min((int)((int64_t)tiles * j / (TK_WAVES * slices)) * 16, Bg - 1);
-            return min(max(group_head[b], 0), b);
-        };
-        r0 = bound(TK_WAVES * slice + wave);
-        r1 = bound(TK_WAVES * slice + wave + 1);
-        first = r0 >> 4;
-        last = r1 > r0 ? (r1 + 15) >> 4 : first;
-    }
-    TkMaskState<MASK> ms;
-    if constexpr (MASK != 0) {
-        ms.row = row_mask;
-        if constexpr (MASK == 2) ms.row += (int64_t)qr * mask_words;
-        ms.prev = first - 1;
-    }
-    auto before_last = [&](int t) {
-        if constexpr (MASK != 0) ms.word = ms.row[t >> 1];
-        if constexpr (GROUPED && MASK == 1) ms.gap_head = group_head[min(max(t * 16 - 1, 0), Bg - 1)];
-        if constexpr (DSL) {
-            if (on_gallery) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int id = min(t * 16 + lg * 4 + r, Bg - 1);
-                    dm[r] = stat_m[id];
-                    ds[r] = stat_s[id];
-                }
-            }
-        }
-        if constexpr (GROUPED) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) gh[r] = group_head[min(t * 16 + lg * 4 + r, Bg - 1)];
-        }
-    };
-    auto count_key = [&](u64 key) {                                                    // GROUPED: one finished group
-        float x;
-        int id;
-        tk_decode(key, x, id);
-        const bool in = key != 0;
+    auto count = [&](bool in, float x, int id) {
         gt += (in && x > tq) ? 1 : 0;
         eq += (in && x == tq) ? 1 : 0;
         before += (in && x == tq && id < front) ? 1 : 0;
     };
-    auto on_tile = [&](int t, const f32x4& acc) {
-        u64 key[4];
-        bool head[4];
+    const TkSource src{gallery, Bg, ld, K, sc, slice, slices, stat_m, stat_s, on_gallery, nt, group_head, row_mask, mask_words};
+    tk_candidates<DSL, GROUPED, MASK>(
+        src, qs, qr, qvalid,
+        [&](const float (&x)[4], const int (&id)[4], const bool (&in)[4]) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int id = t * 16 + lg * 4 + r;
-            float x = sc * acc[r];
-            if constexpr (DSL) x = cc_dsl_value(nt, x, dm[r], ds[r]);
-            bool in = qvalid && (GROUPED ? (id >= r0 && id < r1) : id < Bg);
-            if constexpr (MASK != 0) in = in && ((ms.word >> ((t & 1) * 16 + lg * 4 + r)) & 1);
-            if constexpr (GROUPED) {
-                key[r] = in ? tk_key(x, id) : 0;
-                head[r] = gh[r] == id;
-            } else {
-                gt += (in && x > tq) ? 1 : 0;
-                eq += (in && x == tq) ? 1 : 0;
-                before += (in && x == tq && id < front) ? 1 : 0;
-            }
-        }
-        if constexpr (GROUPED) {
-            if constexpr (MASK == 1) {                                                 // dead tiles skipped: topk_stream_kernel's rule
-                if (lg == 0 && t > ms.prev + 1 && ms.gap_head >= (ms.prev + 1) * 16) head[0] = true;
-                ms.prev = t;
-            }
-            tk_group_tile(key, head, lg, carry);
+            for (int r = 0; r < 4; ++r) count(in[r], x[r], id[r]);
+        },
+        [&](u64 (&key)[4]) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) count_key(key[r]);
-        }
-    };
-    constexpr int stride = GROUPED ? 1 : TK_WAVES;
-    if constexpr (MASK == 1) {
-        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, TkLive(row_mask, first, stride, last, lane), l15, lg, before_last,
-                        on_tile);
-    } else {
-        tk_stream_tiles(gallery, Bg, ld, K, qs + l15 * QS + lg * 8, TkEvery{first, stride, last}, l15, lg, before_last, on_tile);
-    }
-    if constexpr (GROUPED) count_key(lg == 0 ? carry : 0);                             // the group open at the range's end
+            for (int r = 0; r < 4; ++r) {
+                float x;
+                int id;
+                tk_decode(key[r], x, id);
+                count(key[r] != 0, x, id);
+            }
+        });
     int c[3] = {gt, eq, before};
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -904,8 +889,8 @@ __global__ __launch_bounds__(256) void dsl_stats_stream_kernel(const _Float16* _
     _Float16* vs = reinterpret_cast<_Float16*>(tk_smem);                               // [16][K + TK_QPAD]
     tk_stage_rows(vs, video, v0, Bv, ld, K);
     __syncthreads();
-    const int tiles = (Bt + 15) >> 4;
-    const int t0 = (int)((int64_t)tiles * slice / slices), t1 = (int)((int64_t)tiles * (slice + 1) / slices);
+    int t0, t1;
+    tk_slice_tiles(Bt, slice, slices, t0, t1);
     float m = -INFINITY, s = 0.f;                                                      // of video row l15 over the lane's text rows
     int mw = 0;                                                                        // MASKED: the mask word of the tile's 16 bits
     auto before_last = [&](int t) {
@@ -916,7 +901,7 @@ __global__ __launch_bounds__(256) void dsl_stats_stream_kernel(const _Float16* _
         bool in[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const bool sel = MASKED ? ((mw >> ((t & 1) * 16 + lg * 4 + r)) & 1) != 0 : true;
+            const bool sel = MASKED ? tk_mask_bit(mw, t, lg, r) : true;
             in[r] = sel && t * 16 + lg * 4 + r < Bt;
             x[r] = sc * acc[r];
             mt = in[r] ? fmaxf(mt, x[r]) : mt;
@@ -927,12 +912,8 @@ __global__ __launch_bounds__(256) void dsl_stats_stream_kernel(const _Float16* _
         s = a;
         m = mt;
     };
-    const _Float16* vrow = vs + l15 * (K + TK_QPAD) + lg * 8;
-    if constexpr (MASKED) {
-        tk_stream_tiles(text, Bt, ld, K, vrow, TkLive(text_mask, t0 + wave, TK_WAVES, t1, lane), l15, lg, before_last, on_tile);
-    } else {
-        tk_stream_tiles(text, Bt, ld, K, vrow, TkEvery{t0 + wave, TK_WAVES, t1}, l15, lg, before_last, on_tile);
-    }
+    tk_stream_rule<MASKED>(text, Bt, ld, K, vs + l15 * (K + TK_QPAD) + lg * 8, text_mask, t0 + wave, TK_WAVES, t1, before_last,
+                           on_tile);
     pm[wave][lg][l15] = m;
     ps[wave][lg][l15] = s;
     __syncthreads();
@@ -972,28 +953,139 @@ int tk_slices(int Bq, int Bg) {
 // with), at least TK_MIN_TILES tiles a slice
 int dsl_stats_slices(int Bt) { return max(1, min(DSL_MAX_SLICES, (max(Bt, 1) + 15) / 16 / TK_MIN_TILES)); }
 size_t tk_stream_lds(int K, int k) { return (size_t)TK_QROWS * (K + TK_QPAD) * 2 + (size_t)TK_WAVES * TK_QROWS * k * sizeof(u64); }
-template <int MASK, bool BOUND>
-auto tk_stream_kernel_of(bool dsl, bool grouped) {
-    return grouped ? (dsl ? topk_stream_kernel<true, true, MASK, BOUND> : topk_stream_kernel<false, true, MASK, BOUND>)
-                   : (dsl ? topk_stream_kernel<true, false, MASK, BOUND> : topk_stream_kernel<false, false, MASK, BOUND>);
-}
-// mask_rows: 0 no mask, 1 one mask row (also when Bq == 1), otherwise one per query row
-template <bool BOUND>
-auto tk_stream_kernel_of(bool dsl, bool grouped, int mask_rows) {
-    return mask_rows == 0   ? tk_stream_kernel_of<0, BOUND>(dsl, grouped)
-           : mask_rows == 1 ? tk_stream_kernel_of<1, BOUND>(dsl, grouped)
-                            : tk_stream_kernel_of<2, BOUND>(dsl, grouped);
-}
 // the longest list (page) the stream's LDS holds next to 16 staged rows of K halfs: TK_MAXK, 127 for K = 3072
 int tk_page_len(int K) {
     int page = TK_MAXK;
     while (page > 1 && tk_stream_lds(K, page) > TK_LDS_LIMIT) --page;
     return page;
 }
-template <int MASK, bool COUNT = false>
+// sc of a score: mult * 2^-20, as the matrix GEMM's epilogue
+float tk_scale(float mult) { return mult * 9.5367431640625e-07f; }
+int tk_row_groups(int Bq) { return (Bq + TK_QROWS - 1) / TK_QROWS; }
+
+// A search request: what every list, rank and count entry is asked over.  dsl / grouped / masked say which of the optional
+// parts the ENTRY asks for (the plain entries by their name, the others by the pointers they got), so a part that is asked
+// for and missing is refused.  Without dsl, on_gallery and n_total are 0 whatever the caller passed.
+struct TkRequest {
+    const _Float16* query;
+    const _Float16* gallery;
+    int Bq, Bg, E;
+    float mult;
+    int products;
+    bool dsl;
+    const float* m;
+    const float* s;
+    int on_gallery, n_total;
+    bool grouped;
+    const int* group_head;
+    bool masked;
+    const int* row_mask;
+    int mask_rows, mask_words;
+    int K() const { return products * E; }
+    int mask_mode() const { return !masked ? 0 : mask_rows == 1 ? 1 : 2; }            // one mask row also when Bq == 1
+    dim3 grid() const { return dim3(tk_slices(Bq, Bg), tk_row_groups(Bq)); }
+};
+TkRequest tk_request(const void* query, const void* gallery, int Bq, int Bg, int E, float mult, int products, bool dsl, const float* m,
+                     const float* s, int on_gallery, int n_total, bool grouped, const int* group_head, bool masked,
+                     const int* row_mask, int mask_rows, int mask_words) {
+    return TkRequest{static_cast<const _Float16*>(query), static_cast<const _Float16*>(gallery), Bq, Bg, E, mult, products, dsl, m, s,
+                     dsl ? on_gallery : 0, dsl ? n_total : 0, grouped, group_head, masked, row_mask, mask_rows, mask_words};
+}
+// m, s, group_head and row_mask all optional, each part asked for by its pointer (the deep, rank, target-score and count
+// entries; exactly one of m, s: refused as a dsl request)
+TkRequest tk_request(const void* query, const void* gallery, int Bq, int Bg, int E, float mult, int products, const int* row_mask,
+                     int mask_rows, int mask_words, const float* m, const float* s, int on_gallery, int n_total,
+                     const int* group_head) {
+    return tk_request(query, gallery, Bq, Bg, E, mult, products, m || s, m, s, on_gallery, n_total, group_head != nullptr, group_head,
+                      row_mask != nullptr, row_mask, mask_rows, mask_words);
+}
+
+// The refusals all entries share.  Every entry refuses what is invalid before what is unsupported, and the workspace last:
+// an entry passes its own invalid / unsupported conditions (missing outputs, k, the cursor pair) and checks its workspace
+// behind this.  stream_grid: the entry launches on the stream's grid (grid.y: a million query rows a call).
+int tk_check(const TkRequest& r, bool own_invalid, bool own_unsupported, bool stream_grid = true) {
+    if (!r.query || !r.gallery || r.Bq <= 0 || r.Bg <= 0 || r.E <= 0 || own_invalid) return CC_ERR_INVALID;
+    if (r.dsl && (!r.m || !r.s || r.n_total < 0 || (r.on_gallery != 0 && r.on_gallery != 1))) return CC_ERR_INVALID;
+    if (r.grouped && !r.group_head) return CC_ERR_INVALID;
+    if (r.masked && (!r.row_mask || (r.mask_rows != 1 && r.mask_rows != r.Bq) || r.mask_words < (r.Bg - 1) / 32 + 1))
+        return CC_ERR_INVALID;
+    if (own_unsupported || r.products < 1 || r.products > 3 || (r.E & 63) || r.E > 1024) return CC_ERR_UNSUPPORTED;
+    if (stream_grid && tk_row_groups(r.Bq) > 65535) return CC_ERR_UNSUPPORTED;
+    return CC_OK;
+}
+
+template <int MASK, bool BOUND>
+auto tk_stream_kernel_of(bool dsl, bool grouped) {
+    return grouped ? (dsl ? topk_stream_kernel<true, true, MASK, BOUND> : topk_stream_kernel<false, true, MASK, BOUND>)
+                   : (dsl ? topk_stream_kernel<true, false, MASK, BOUND> : topk_stream_kernel<false, false, MASK, BOUND>);
+}
+template <bool BOUND>
+auto tk_stream_kernel_of(const TkRequest& r) {
+    return r.mask_mode() == 0   ? tk_stream_kernel_of<0, BOUND>(r.dsl, r.grouped)
+           : r.mask_mode() == 1 ? tk_stream_kernel_of<1, BOUND>(r.dsl, r.grouped)
+                                : tk_stream_kernel_of<2, BOUND>(r.dsl, r.grouped);
+}
+template <int MASK, bool COUNT>
 auto rank_stream_kernel_of(bool dsl, bool grouped) {
     return grouped ? (dsl ? rank_stream_kernel<true, true, MASK, COUNT> : rank_stream_kernel<false, true, MASK, COUNT>)
                    : (dsl ? rank_stream_kernel<true, false, MASK, COUNT> : rank_stream_kernel<false, false, MASK, COUNT>);
+}
+template <bool COUNT>
+auto rank_stream_kernel_of(const TkRequest& r) {
+    return r.mask_mode() == 0   ? rank_stream_kernel_of<0, COUNT>(r.dsl, r.grouped)
+           : r.mask_mode() == 1 ? rank_stream_kernel_of<1, COUNT>(r.dsl, r.grouped)
+                                : rank_stream_kernel_of<2, COUNT>(r.dsl, r.grouped);
+}
+
+// The pages of a list of k entries, `page` entries each (the last one what is left): per page the list stream and the merge,
+// which writes the page at its column offset of scores / ids [Bq, k] and - if a page follows - its last key to `cursor`.
+// bounded: the first page already lies below `cursor`; every page behind the first does.  One page, not bounded, no cursor
+// buffer: the two launches of a plain list.
+int tk_launch_pages(const TkRequest& r, int k, int page, bool bounded, u64* lists, u64* cursor, float* scores, int32_t* ids,
+                    hipStream_t st) {
+    const int K = r.K(), slices = tk_slices(r.Bq, r.Bg);
+    for (int done = 0; done < k; done += page, bounded = true) {
+        const int kp = min(page, k - done);
+        const size_t smem = tk_stream_lds(K, kp);
+        const auto kernel = bounded ? tk_stream_kernel_of<true>(r) : tk_stream_kernel_of<false>(r);
+        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
+        hipLaunchKernelGGL(kernel, r.grid(), dim3(256), smem, st, r.query, r.gallery, r.Bq, r.Bg, 3 * r.E, K, tk_scale(r.mult), kp,
+                           slices, lists, r.m, r.s, r.on_gallery, (float)r.n_total, r.group_head, r.row_mask, r.mask_words,
+                           static_cast<const u64*>(cursor));
+        CC_LAUNCH_CHECK();
+        hipLaunchKernelGGL(topk_merge_kernel, dim3(r.Bq), dim3(64), 0, st, static_cast<const u64*>(lists), slices, kp, scores + done,
+                           ids + done, k, done + kp < k ? cursor : static_cast<u64*>(nullptr));
+        CC_LAUNCH_CHECK();
+    }
+    return CC_OK;
+}
+
+// t_q of every query row's target -> score (rank_target_kernel)
+int tk_launch_target(const TkRequest& r, const int32_t* target, float* score, hipStream_t st) {
+    const auto kernel = r.grouped ? (r.dsl ? rank_target_kernel<true, true> : rank_target_kernel<false, true>)
+                                  : (r.dsl ? rank_target_kernel<true, false> : rank_target_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((r.Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, r.query, r.gallery, r.Bq, r.Bg, 3 * r.E, r.K(),
+                       tk_scale(r.mult), target, score, r.m, r.s, r.on_gallery, (float)r.n_total, r.group_head, r.row_mask,
+                       r.mask_rows == 1 ? 0 : r.mask_words);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+// the count stream against tscore and target (bound: the caller's bound and front position, rank_stream_kernel's COUNT mode),
+// then the reduce: part [Bq][3][slices] -> counts [Bq][3]
+int tk_launch_count(const TkRequest& r, bool bound, const int32_t* target, const float* tscore, int* part, int32_t* counts,
+                    hipStream_t st) {
+    const int K = r.K(), slices = tk_slices(r.Bq, r.Bg);
+    const size_t smem = tk_stream_lds(K, 0);                                // the staged rows: no lists, no (E, products) exclusion
+    const auto kernel = bound ? rank_stream_kernel_of<true>(r) : rank_stream_kernel_of<false>(r);
+    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
+    hipLaunchKernelGGL(kernel, r.grid(), dim3(256), smem, st, r.query, r.gallery, r.Bq, r.Bg, 3 * r.E, K, tk_scale(r.mult), slices, target,
+                       tscore, part, r.m, r.s, r.on_gallery, (float)r.n_total, r.group_head, r.row_mask, r.mask_words);
+    CC_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rank_reduce_kernel, dim3((3 * r.Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, static_cast<const int*>(part),
+                       slices, 3 * r.Bq, counts);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
 }
 
 }  // namespace
@@ -1010,65 +1102,42 @@ size_t cc_similarity_topk_workspace_bytes(int32_t Bq, int32_t Bg, int32_t k) {
     return cc_align_up((size_t)Bq * tk_slices(Bq, Bg) * k * sizeof(u64), 256);
 }
 
-// the checks and the two launches of all top-k entries; dsl: m, s, on_gallery, n_total of the rewrite; masked: row_mask,
-// mask_rows (1 or Bq), mask_words
-static int tk_launch(bool dsl, bool grouped, const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
-                     float mult, int32_t products, int32_t k, const float* m, const float* s, int32_t on_gallery, int32_t n_total,
-                     const int32_t* group_head, float* scores, int32_t* ids, void* ws, size_t ws_bytes, void* stream,
-                     bool masked = false, const int32_t* row_mask = nullptr, int32_t mask_rows = 0, int32_t mask_words = 0) {
-    if (!query_planes || !gallery_planes || !scores || !ids || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
-    if (dsl && (!m || !s || n_total < 0 || (on_gallery != 0 && on_gallery != 1))) return CC_ERR_INVALID;
-    if (grouped && !group_head) return CC_ERR_INVALID;
-    if (masked && (!row_mask || (mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
-    if (k < 1 || k > TK_MAXK || products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
-    const int K = products * E;
-    const size_t smem = tk_stream_lds(K, k);
-    if (smem > TK_LDS_LIMIT) return CC_ERR_UNSUPPORTED;                   // products * E = 3072 with k = 128 only
-    if ((Bq + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million query rows a call)
-    if (!ws || ws_bytes < cc_similarity_topk_workspace_bytes(Bq, Bg, k)) return CC_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int slices = tk_slices(Bq, Bg);
-    const auto kernel = tk_stream_kernel_of<false>(dsl, grouped, masked ? mask_rows : 0);
-    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
-    hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
-                       static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K,
-                       mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, k, slices, static_cast<u64*>(ws), m, s,
-                       on_gallery, (float)n_total, group_head, row_mask, mask_words, static_cast<const u64*>(nullptr));
-    CC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(ws), slices, k, scores, ids, k,
-                       static_cast<u64*>(nullptr));
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+// the plain / dsl / grouped / masked entries: a list of at most TK_MAXK entries that the stream's LDS holds, as one page
+static int tk_launch(const TkRequest& r, int32_t k, float* scores, int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
+    if (const int rc = tk_check(r, !scores || !ids, k < 1 || k > TK_MAXK)) return rc;
+    if (tk_stream_lds(r.K(), k) > TK_LDS_LIMIT) return CC_ERR_UNSUPPORTED;  // products * E = 3072 with k = 128 only
+    if (!ws || ws_bytes < cc_similarity_topk_workspace_bytes(r.Bq, r.Bg, k)) return CC_ERR_WORKSPACE;
+    return tk_launch_pages(r, k, k, false, static_cast<u64*>(ws), nullptr, scores, ids, static_cast<hipStream_t>(stream));
 }
 
 int cc_similarity_topk_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
                                   float mult, int32_t products, int32_t k, float* scores, int32_t* ids, void* ws,
                                   size_t ws_bytes, void* stream) {
-    return tk_launch(false, false, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, nullptr, nullptr, 0, 0, nullptr,
-                     scores, ids, ws, ws_bytes, stream);
+    return tk_launch(tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, false, nullptr, nullptr, 0, 0, false, nullptr,
+                                false, nullptr, 0, 0), k, scores, ids, ws, ws_bytes, stream);
 }
 
 int cc_similarity_topk_dsl_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
                                       float mult, int32_t products, int32_t k, const float* m, const float* s,
                                       int32_t stats_on_gallery, int32_t n_total, float* scores, int32_t* ids, void* ws,
                                       size_t ws_bytes, void* stream) {
-    return tk_launch(true, false, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s, stats_on_gallery, n_total,
-                     nullptr, scores, ids, ws, ws_bytes, stream);
+    return tk_launch(tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, true, m, s, stats_on_gallery, n_total, false,
+                                nullptr, false, nullptr, 0, 0), k, scores, ids, ws, ws_bytes, stream);
 }
 
 int cc_similarity_topk_grouped_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
                                           float mult, int32_t products, int32_t k, const int32_t* group_head, float* scores,
                                           int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
-    return tk_launch(false, true, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, nullptr, nullptr, 0, 0, group_head,
-                     scores, ids, ws, ws_bytes, stream);
+    return tk_launch(tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, false, nullptr, nullptr, 0, 0, true, group_head,
+                                false, nullptr, 0, 0), k, scores, ids, ws, ws_bytes, stream);
 }
 
 int cc_similarity_topk_grouped_dsl_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg,
                                               int32_t E, float mult, int32_t products, int32_t k, const float* m, const float* s,
                                               int32_t stats_on_gallery, int32_t n_total, const int32_t* group_head, float* scores,
                                               int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
-    return tk_launch(true, true, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s, stats_on_gallery, n_total,
-                     group_head, scores, ids, ws, ws_bytes, stream);
+    return tk_launch(tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, true, m, s, stats_on_gallery, n_total, true,
+                                group_head, false, nullptr, 0, 0), k, scores, ids, ws, ws_bytes, stream);
 }
 
 int cc_similarity_topk_masked_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
@@ -1076,10 +1145,9 @@ int cc_similarity_topk_masked_planes_f32(const void* query_planes, const void* g
                                          int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery,
                                          int32_t n_total, const int32_t* group_head, float* scores, int32_t* ids, void* ws,
                                          size_t ws_bytes, void* stream) {
-    const bool dsl = m || s;                                               // (exactly one of them: refused as the _dsl entry does)
-    return tk_launch(dsl, group_head != nullptr, query_planes, gallery_planes, Bq, Bg, E, mult, products, k, m, s,
-                     dsl ? stats_on_gallery : 0, dsl ? n_total : 0, group_head, scores, ids, ws, ws_bytes, stream, true, row_mask,
-                     mask_rows, mask_words);
+    return tk_launch(tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, m || s, m, s, stats_on_gallery, n_total,
+                                group_head != nullptr, group_head, true, row_mask, mask_rows, mask_words),      // (a mask it must have)
+                     k, scores, ids, ws, ws_bytes, stream);
 }
 
 // one page's workspace (the plain entry's at the page length), then the cursor buffer: u64 [Bq]
@@ -1095,41 +1163,18 @@ int cc_similarity_topk_deep_planes_f32(const void* query_planes, const void* gal
                                        int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery, int32_t n_total,
                                        const int32_t* group_head, const float* after_scores, const int32_t* after_ids, float* scores,
                                        int32_t* ids, void* ws, size_t ws_bytes, void* stream) {
-    const bool dsl = m || s, grouped = group_head != nullptr, masked = row_mask != nullptr;
-    if (!query_planes || !gallery_planes || !scores || !ids || Bq <= 0 || Bg <= 0 || E <= 0 || k < 1) return CC_ERR_INVALID;
-    if (dsl && (!m || !s || n_total < 0 || (stats_on_gallery != 0 && stats_on_gallery != 1))) return CC_ERR_INVALID;
-    if (masked && ((mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
-    if (!after_scores != !after_ids) return CC_ERR_INVALID;
-    if (k > CC_TOPK_DEEP_MAXK || products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
-    if ((Bq + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million query rows a call)
+    const TkRequest r = tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, row_mask, mask_rows, mask_words, m, s,
+                                   stats_on_gallery, n_total, group_head);
+    if (const int rc = tk_check(r, !scores || !ids || k < 1 || !after_scores != !after_ids, k > CC_TOPK_DEEP_MAXK)) return rc;
     if (!ws || ws_bytes < cc_similarity_topk_deep_workspace_bytes(Bq, Bg, E, products, k)) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int K = products * E, page = min(k, tk_page_len(K)), slices = tk_slices(Bq, Bg);
-    const int on_gallery = dsl ? stats_on_gallery : 0;
-    const float sc = mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, nt = dsl ? (float)n_total : 0.f;
-    u64* lists = static_cast<u64*>(ws);
+    const int page = min(k, tk_page_len(r.K()));
     u64* cursor = reinterpret_cast<u64*>(static_cast<char*>(ws) + cc_similarity_topk_workspace_bytes(Bq, Bg, page));
-    bool bounded = after_scores != nullptr;
-    if (bounded) {
+    if (after_scores) {
         hipLaunchKernelGGL(topk_cursor_kernel, dim3((Bq + 255) / 256), dim3(256), 0, st, after_scores, after_ids, Bq, cursor);
         CC_LAUNCH_CHECK();
     }
-    for (int done = 0; done < k; done += page, bounded = true) {                       // (every page behind the first is bounded)
-        const int kp = min(page, k - done);
-        const size_t smem = tk_stream_lds(K, kp);
-        const auto kernel = bounded ? tk_stream_kernel_of<true>(dsl, grouped, masked ? mask_rows : 0)
-                                    : tk_stream_kernel_of<false>(dsl, grouped, masked ? mask_rows : 0);
-        if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
-        hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
-                           static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K,
-                           sc, kp, slices, lists, m, s, on_gallery, nt, group_head, row_mask, mask_words,
-                           static_cast<const u64*>(cursor));
-        CC_LAUNCH_CHECK();
-        hipLaunchKernelGGL(topk_merge_kernel, dim3(Bq), dim3(64), 0, st, static_cast<const u64*>(lists), slices, kp,
-                           scores + done, ids + done, k, done + kp < k ? cursor : static_cast<u64*>(nullptr));
-        CC_LAUNCH_CHECK();
-    }
-    return CC_OK;
+    return tk_launch_pages(r, k, page, after_scores != nullptr, static_cast<u64*>(ws), cursor, scores, ids, st);
 }
 
 size_t cc_similarity_rank_workspace_bytes(int32_t Bq, int32_t Bg) {
@@ -1141,36 +1186,13 @@ int cc_similarity_rank_planes_f32(const void* query_planes, const void* gallery_
                                   int32_t products, const int32_t* target, const int32_t* row_mask, int32_t mask_rows,
                                   int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery, int32_t n_total,
                                   const int32_t* group_head, int32_t* counts, float* score, void* ws, size_t ws_bytes, void* stream) {
-    const bool dsl = m || s, grouped = group_head != nullptr, masked = row_mask != nullptr;
-    if (!query_planes || !gallery_planes || !target || !counts || !score || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
-    if (dsl && (!m || !s || n_total < 0 || (stats_on_gallery != 0 && stats_on_gallery != 1))) return CC_ERR_INVALID;
-    if (masked && ((mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
-    if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
-    const int K = products * E;
-    const size_t smem = tk_stream_lds(K, 0);                                // the staged rows: no lists, no (E, products) exclusion
-    if ((Bq + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million query rows a call)
+    const TkRequest r = tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, row_mask, mask_rows, mask_words, m, s,
+                                   stats_on_gallery, n_total, group_head);
+    if (const int rc = tk_check(r, !target || !counts || !score, false)) return rc;
     if (!ws || ws_bytes < cc_similarity_rank_workspace_bytes(Bq, Bg)) return CC_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const int slices = tk_slices(Bq, Bg), on_gallery = dsl ? stats_on_gallery : 0;
-    const float sc = mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, nt = dsl ? (float)n_total : 0.f;
-    const _Float16* q = static_cast<const _Float16*>(query_planes);
-    const _Float16* g = static_cast<const _Float16*>(gallery_planes);
-    const auto target_kernel = grouped ? (dsl ? rank_target_kernel<true, true> : rank_target_kernel<false, true>)
-                                       : (dsl ? rank_target_kernel<true, false> : rank_target_kernel<false, false>);
-    hipLaunchKernelGGL(target_kernel, dim3((Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, q, g, Bq, Bg, 3 * E, K, sc, target, score,
-                       m, s, on_gallery, nt, group_head, row_mask, mask_rows == 1 ? 0 : mask_words);
-    CC_LAUNCH_CHECK();
-    const auto kernel = !masked ? rank_stream_kernel_of<0>(dsl, grouped)
-                                : mask_rows == 1 ? rank_stream_kernel_of<1>(dsl, grouped) : rank_stream_kernel_of<2>(dsl, grouped);
-    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
-    hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st, q, g, Bq, Bg, 3 * E, K, sc, slices,
-                       target, static_cast<const float*>(score), static_cast<int*>(ws), m, s, on_gallery, nt, group_head, row_mask,
-                       mask_words);
-    CC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_reduce_kernel, dim3((3 * Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, static_cast<const int*>(ws), slices, 3 * Bq,
-                       counts);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+    if (const int rc = tk_launch_target(r, target, score, st)) return rc;
+    return tk_launch_count(r, false, target, score, static_cast<int*>(ws), counts, st);
 }
 
 int cc_topk_merge_lists_f32(const float* scores, const int32_t* ids, int32_t S, int32_t Bq, int32_t k, float* out_scores,
@@ -1183,60 +1205,31 @@ int cc_topk_merge_lists_f32(const float* scores, const int32_t* ids, int32_t S, 
     return CC_OK;
 }
 
-// the first launch of cc_similarity_rank_planes_f32 on its own: its checks, its kernel, its arguments
+// the first launch of cc_similarity_rank_planes_f32 on its own: its checks but the grid's and the workspace's
 int cc_similarity_target_score_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E,
                                           float mult, int32_t products, const int32_t* target, const int32_t* row_mask,
                                           int32_t mask_rows, int32_t mask_words, const float* m, const float* s,
                                           int32_t stats_on_gallery, int32_t n_total, const int32_t* group_head, float* score,
                                           void* stream) {
-    const bool dsl = m || s, grouped = group_head != nullptr, masked = row_mask != nullptr;
-    if (!query_planes || !gallery_planes || !target || !score || Bq <= 0 || Bg <= 0 || E <= 0) return CC_ERR_INVALID;
-    if (dsl && (!m || !s || n_total < 0 || (stats_on_gallery != 0 && stats_on_gallery != 1))) return CC_ERR_INVALID;
-    if (masked && ((mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
-    if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
-    const int on_gallery = dsl ? stats_on_gallery : 0;
-    const float sc = mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, nt = dsl ? (float)n_total : 0.f;
-    const auto target_kernel = grouped ? (dsl ? rank_target_kernel<true, true> : rank_target_kernel<false, true>)
-                                       : (dsl ? rank_target_kernel<true, false> : rank_target_kernel<false, false>);
-    hipLaunchKernelGGL(target_kernel, dim3((Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E,
-                       products * E, sc, target, score, m, s, on_gallery, nt, group_head, row_mask, mask_rows == 1 ? 0 : mask_words);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+    const TkRequest r = tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, row_mask, mask_rows, mask_words, m, s,
+                                   stats_on_gallery, n_total, group_head);
+    if (const int rc = tk_check(r, !target || !score, false, false)) return rc;
+    return tk_launch_target(r, target, score, static_cast<hipStream_t>(stream));
 }
 
 size_t cc_similarity_count_workspace_bytes(int32_t Bq, int32_t Bg) { return cc_similarity_rank_workspace_bytes(Bq, Bg); }
 
-// the counting pass and the reduce of cc_similarity_rank_planes_f32 against a bound the caller holds (rank_stream_kernel's
-// COUNT mode)
+// the counting pass and the reduce of cc_similarity_rank_planes_f32 against a bound the caller holds
 int cc_similarity_count_planes_f32(const void* query_planes, const void* gallery_planes, int32_t Bq, int32_t Bg, int32_t E, float mult,
                                    int32_t products, const float* bound_scores, const int32_t* bound_front, const int32_t* row_mask,
                                    int32_t mask_rows, int32_t mask_words, const float* m, const float* s, int32_t stats_on_gallery,
                                    int32_t n_total, const int32_t* group_head, int32_t* counts, void* ws, size_t ws_bytes,
                                    void* stream) {
-    const bool dsl = m || s, grouped = group_head != nullptr, masked = row_mask != nullptr;
-    if (!query_planes || !gallery_planes || !bound_scores || !bound_front || !counts || Bq <= 0 || Bg <= 0 || E <= 0)
-        return CC_ERR_INVALID;
-    if (dsl && (!m || !s || n_total < 0 || (stats_on_gallery != 0 && stats_on_gallery != 1))) return CC_ERR_INVALID;
-    if (masked && ((mask_rows != 1 && mask_rows != Bq) || mask_words < (Bg - 1) / 32 + 1)) return CC_ERR_INVALID;
-    if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
-    if ((Bq + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million query rows a call)
+    const TkRequest r = tk_request(query_planes, gallery_planes, Bq, Bg, E, mult, products, row_mask, mask_rows, mask_words, m, s,
+                                   stats_on_gallery, n_total, group_head);
+    if (const int rc = tk_check(r, !bound_scores || !bound_front || !counts, false)) return rc;
     if (!ws || ws_bytes < cc_similarity_count_workspace_bytes(Bq, Bg)) return CC_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int K = products * E, slices = tk_slices(Bq, Bg), on_gallery = dsl ? stats_on_gallery : 0;
-    const size_t smem = tk_stream_lds(K, 0);
-    const float sc = mult * 9.5367431640625e-07f /* 2^-20, as the matrix GEMM's epilogue */, nt = dsl ? (float)n_total : 0.f;
-    const auto kernel = !masked ? rank_stream_kernel_of<0, true>(dsl, grouped)
-                                : mask_rows == 1 ? rank_stream_kernel_of<1, true>(dsl, grouped) : rank_stream_kernel_of<2, true>(dsl, grouped);
-    if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
-    hipLaunchKernelGGL(kernel, dim3(slices, (Bq + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
-                       static_cast<const _Float16*>(query_planes), static_cast<const _Float16*>(gallery_planes), Bq, Bg, 3 * E, K, sc,
-                       slices, bound_front, bound_scores, static_cast<int*>(ws), m, s, on_gallery, nt, group_head, row_mask, mask_words);
-    CC_LAUNCH_CHECK();
-    hipLaunchKernelGGL(rank_reduce_kernel, dim3((3 * Bq + TK_WAVES - 1) / TK_WAVES), dim3(256), 0, st, static_cast<const int*>(ws), slices,
-                       3 * Bq, counts);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+    return tk_launch_count(r, true, bound_front, bound_scores, static_cast<int*>(ws), counts, static_cast<hipStream_t>(stream));
 }
 
 int cc_pack_row_mask_u8(const uint8_t* flags, int32_t rows, int32_t n, int32_t* out_words, int32_t words_per_row, void* stream) {
@@ -1262,7 +1255,7 @@ static int dsl_stats_launch(bool masked, const void* text_planes, const void* vi
     if (masked && Bt > 0 && !text_mask) return CC_ERR_INVALID;
     if (products < 1 || products > 3 || (E & 63) || E > 1024) return CC_ERR_UNSUPPORTED;
     const int K = products * E;
-    const size_t smem = (size_t)TK_QROWS * (K + TK_QPAD) * 2;
+    const size_t smem = tk_stream_lds(K, 0);
     if (smem > TK_LDS_LIMIT) return CC_ERR_UNSUPPORTED;                   // (never with E <= 1024: 96 KB at most)
     if ((Bv + TK_QROWS - 1) / TK_QROWS > 65535) return CC_ERR_UNSUPPORTED;  // (grid.y: a million video rows a call)
     if (Bt > 0 && (!ws || ws_bytes < cc_dsl_col_stats_planes_workspace_bytes(Bt, Bv))) return CC_ERR_WORKSPACE;
@@ -1273,7 +1266,7 @@ static int dsl_stats_launch(bool masked, const void* text_planes, const void* vi
         if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kernel), smem) != CC_OK) return CC_ERR_HIP;
         hipLaunchKernelGGL(kernel, dim3(slices, (Bv + TK_QROWS - 1) / TK_QROWS), dim3(256), smem, st,
                            static_cast<const _Float16*>(video_planes), static_cast<const _Float16*>(text_planes), Bv, Bt, 3 * E, K,
-                           mult * 9.5367431640625e-07f, slices, static_cast<float*>(ws), text_mask);
+                           tk_scale(mult), slices, static_cast<float*>(ws), text_mask);
         CC_LAUNCH_CHECK();
     }
     return cc_launch_dsl_col_merge(static_cast<const float*>(ws), slices, Bv, m, s, st);      // no slice: (-inf, 0)

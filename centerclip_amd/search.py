@@ -42,7 +42,8 @@ Rows leave and searches narrow with one bit per row (``similarity_topk_masked``)
     ranks, scores, counts = gallery.rank_groups(video, video_mask, target=labels)      # grouped=True: the place of a group
 
 Lists of up to 4096 entries and "next page" cursors (``similarity_topk_deep``): pages of at most 128, each the same stream
-restricted to what lies behind the page before - exact, no matrix, no state between calls:
+restricted to what lies behind the page before - exact, no matrix, no state between calls.  The gallery asks this one op
+for every list; up to 128 entries without a cursor it is one page, the launches of the ops named above:
 
     scores, ids = gallery.search(input_ids, k=1000)                         # candidates for a re-ranker
     more_scores, more_ids = gallery.search(input_ids, k=50, after=(scores[:, -1], ids[:, -1]))     # entries 1000..1049
@@ -188,9 +189,10 @@ class FeatureGallery:
         must still be held, so it stays right when rows are removed between the two calls (the list continues behind the
         place the pair had); a cursor equal to the fill gives the fill.  ``compact()`` renumbers positions: cursors do not
         survive it.
-      * k <= 128 without ``after=`` runs the ops it always ran (one pass).  Otherwise ``similarity_topk_deep``: ceil(k / 128)
-        passes over the gallery (pages of 127 at E = 1024 with three products), the pages handing over on the device;
-        dual_softmax=True, side="text": the queries' statistics are taken once per call, not per page.
+      * Every list is ``similarity_topk_deep``: ceil(k / 128) passes over the gallery (pages of 127 at E = 1024 with three
+        products, so k = 128 there takes two), the pages handing over on the device - k <= 128 without ``after=`` is one pass,
+        the launches of the specialised ops; dual_softmax=True, side="text": the queries' statistics are taken once per
+        call, not per page.
       * A call does not synchronise with the host: ``after=`` takes device tensors and reads none of them."""
 
     def __init__(self, model, side="video", capacity=0, products=None, dual_softmax=False, grouped=False):
@@ -791,6 +793,17 @@ class FeatureGallery:
                              "columns of the earlier result)" % (what, tuple(scores.shape), scores.dtype, scores.device,
                                                                  tuple(pos.shape), pos.dtype, pos.device, nq, self._rows.device))
 
+    def _softmax_args(self, q):
+        """(m, s, stats_on_gallery, n_total) of every ranking of the queries q: the dual softmax's statistics - side="video":
+        the gallery rows' pairs over the bank; side="text": the queries' pairs over the captions held, taken once per call -
+        or (None, None, ., 0) for the plain score"""
+        on_gallery = int(self.side == "video")
+        if not self._dsl:
+            return None, None, on_gallery, 0
+        if on_gallery:
+            return self._m, self._s, 1, self._bank.shape[0]
+        return self._query_stats(q) + (0, len(self))
+
     def _search_rows(self, q, k, groups=False, allow=None, after=None):
         """the k best rows - groups: the best row of each of the k best groups - of every row of q; after ``remove`` or with
         ``allow=``: of the rows both leave selectable; ``after``: of those behind that entry of the ordering"""
@@ -801,31 +814,9 @@ class FeatureGallery:
         if len(self) == 0:                                  # nothing to rank: the fill of a list longer than the gallery
             return (torch.full((q.shape[0], k), float("-inf"), device=self.device),
                     torch.full((q.shape[0], k), -1, device=self.device, dtype=torch.int64))
-        op, tail = torch.ops.centerclip, ((self._head,) if groups else ())
-        if k > 128 or after is not None:                    # a list of pages, or one that starts behind a cursor: one op for all
-            m = s = None
-            on_gallery, n_total = self.side == "video", 0
-            if self._dsl:                                   # (side="text": the queries' pairs once per call, not per page)
-                m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
-                n_total = self._bank.shape[0] if on_gallery else len(self)
-            return op.similarity_topk_deep(q, self._rows, self._n, self._mult(), self.products, k, mask, m, s, int(on_gallery),
-                                           n_total, self._head if groups else None, *(after if after is not None else (None, None)))
-        if mask is not None:                                # one op for the four rankings (no mask: the ops of before)
-            m = s = None
-            on_gallery, n_total = self.side == "video", 0
-            if self._dsl:
-                m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
-                n_total = self._bank.shape[0] if on_gallery else len(self)
-            return op.similarity_topk_masked(q, self._rows, self._n, self._mult(), self.products, k, mask, m, s, int(on_gallery),
-                                             n_total, self._head if groups else None)
-        if self._dsl:
-            on_gallery = self.side == "video"
-            m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
-            return (op.similarity_topk_grouped_dsl if groups else op.similarity_topk_dsl)(
-                q, self._rows, self._n, self._mult(), self.products, k, m, s, int(on_gallery),
-                self._bank.shape[0] if on_gallery else self._n, *tail)
-        return (op.similarity_topk_grouped if groups else op.similarity_topk)(q, self._rows, self._n, self._mult(), self.products,
-                                                                               k, *tail)
+        return torch.ops.centerclip.similarity_topk_deep(q, self._rows, self._n, self._mult(), self.products, k, mask,
+                                                         *self._softmax_args(q), self._head if groups else None,
+                                                         *(after if after is not None else (None, None)))
 
     def _search_group_rows(self, q, k, allow=None, after=None):
         scores, pos = self._search_rows(q, k, groups=True, allow=allow, after=after)
@@ -920,13 +911,8 @@ class FeatureGallery:
         if self._dsl:
             self._need_bank()
         mask = self._allow_words(allow, q.shape[0])
-        m = s = None
-        on_gallery, n_total = self.side == "video", 0
-        if self._dsl:
-            m, s = (self._m, self._s) if on_gallery else self._query_stats(q)
-            n_total = self._bank.shape[0] if on_gallery else len(self)
-        counts, scores = torch.ops.centerclip.similarity_rank(q, self._rows, self._n, self._mult(), self.products, target, mask, m, s,
-                                                              int(on_gallery), n_total, self._head if groups else None)
+        counts, scores = torch.ops.centerclip.similarity_rank(q, self._rows, self._n, self._mult(), self.products, target, mask,
+                                                              *self._softmax_args(q), self._head if groups else None)
         return counts[:, 0].to(torch.int64) + counts[:, 2], scores, counts
 
     def rank(self, *inputs, target, allow=None):

@@ -403,9 +403,8 @@ class ShardedGallery:
             if g._dsl:
                 g._need_bank()
             qr = q.to(g.device)
-            m, s, n_total = (g._m, g._s, g._bank.shape[0]) if g._dsl else (None, None, 0)
             args = (qr, g._rows, g._n, g._mult(), g.products)
-            tail = (g._allow_words(mask, qr.shape[0]), m, s, 1, n_total, g._head if groups else None)
+            tail = (g._allow_words(mask, qr.shape[0]), *g._softmax_args(qr), g._head if groups else None)
             calls.append((r, args, tail, tg))
             score = op.similarity_target_score(*args, tg, *tail)
             owns = (tg >= 0) & (tg < g._n)

@@ -1259,27 +1259,12 @@ def similarity_topk(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_
     [Bq, k] int64): the first k entries of the stable descending sort of the row scaled_dot_planes gives for the same planes
     (same bits; equal scores by smaller id; (-inf, -1) beyond n_gallery), without that matrix.  The gallery needs no padding
     rows.  1 <= k <= 128.  cc_similarity_topk_planes_f32."""
-    Bq, E3 = query_planes.shape
-    if gallery_planes.dim() != 2 or gallery_planes.shape[1] != E3 or gallery_planes.shape[0] < int(n_gallery):
-        raise ValueError("similarity_topk: gallery planes %s do not hold %d rows of %d halfs"
-                         % (tuple(gallery_planes.shape), int(n_gallery), E3))
-    if query_planes.dtype != torch.float16 or gallery_planes.dtype != torch.float16:
-        raise ValueError("similarity_topk: plane rows are fp16")
-    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
-    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
-    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
-    lib = L.lib()
-    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
-    L.check(lib.cc_similarity_topk_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
-                                              float(mult), int(products), int(k), L.ptr(scores), L.ptr(ids), L.ptr(ws),
-                                              ws.numel(), _st(query_planes)), "cc_similarity_topk_planes_f32")
-    return scores, ids.to(torch.int64)
+    return _topk("similarity_topk", query_planes, gallery_planes, n_gallery, mult, products, k)
 
 
 @similarity_topk.register_fake
 def _(query_planes, gallery_planes, n_gallery, mult, products, k):
-    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
-            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+    return _topk_fake("similarity_topk", query_planes, gallery_planes, n_gallery, k)
 
 
 def _check_plane_pair(name, a, b, rows_b):
@@ -1324,29 +1309,13 @@ def similarity_topk_dsl(query_planes: torch.Tensor, gallery_planes: torch.Tensor
     """similarity_topk ranking the dual softmax D = n_total * S * exp(S - m[x]) / s[x] instead of S: x is the gallery row
     (stats_on_gallery = 1: m, s hold at least n_gallery entries) or the query row (0: m, s [Bq]).  A score has the bits dsl_apply_
     writes over scaled_dot_planes' entry; order, fill and limits are similarity_topk's.  cc_similarity_topk_dsl_planes_f32."""
-    Bq = query_planes.shape[0]
-    E3 = _check_plane_pair("similarity_topk_dsl", query_planes, gallery_planes, n_gallery)
-    need = int(n_gallery) if stats_on_gallery else Bq
-    if m.dim() != 1 or s.dim() != 1 or m.shape[0] < need or s.shape[0] < need or m.dtype != torch.float32 or s.dtype != torch.float32:
-        raise ValueError("similarity_topk_dsl: m %s, s %s are not fp32 vectors of at least %d entries"
-                         % (tuple(m.shape), tuple(s.shape), need))
-    query_planes, gallery_planes, m, s = query_planes.contiguous(), gallery_planes.contiguous(), m.contiguous(), s.contiguous()
-    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
-    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
-    lib = L.lib()
-    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
-    L.check(lib.cc_similarity_topk_dsl_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
-                                                  float(mult), int(products), int(k), L.ptr(m), L.ptr(s),
-                                                  int(stats_on_gallery), int(n_total), L.ptr(scores), L.ptr(ids),
-                                                  L.ptr(ws), ws.numel(), _st(query_planes)),
-            "cc_similarity_topk_dsl_planes_f32")
-    return scores, ids.to(torch.int64)
+    return _topk("similarity_topk_dsl", query_planes, gallery_planes, n_gallery, mult, products, k, m=m, s=s,
+                 stats_on_gallery=stats_on_gallery, n_total=n_total)
 
 
 @similarity_topk_dsl.register_fake
 def _(query_planes, gallery_planes, n_gallery, mult, products, k, m, s, stats_on_gallery, n_total):
-    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
-            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+    return _topk_fake("similarity_topk_dsl", query_planes, gallery_planes, n_gallery, k, m=m, s=s, stats_on_gallery=stats_on_gallery)
 
 
 def _check_group_head(name, query_planes, gallery_planes, n_gallery, group_head):
@@ -1374,25 +1343,12 @@ def similarity_topk_grouped(query_planes: torch.Tensor, gallery_planes: torch.Te
     first row of every row's group.  -> (scores [Bq, k] fp32, ids [Bq, k] int64): of similarity_topk's row order the first k
     rows that are the first of their group to appear - entry i is the best row of the i-th best group; (-inf, -1) beyond the
     number of groups.  group_head = arange gives similarity_topk bit for bit.  cc_similarity_topk_grouped_planes_f32."""
-    Bq = query_planes.shape[0]
-    E3 = _check_group_head("similarity_topk_grouped", query_planes, gallery_planes, n_gallery, group_head)
-    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
-    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
-    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
-    lib = L.lib()
-    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
-    L.check(lib.cc_similarity_topk_grouped_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
-                                                      float(mult), int(products), int(k), L.ptr(group_head), L.ptr(scores),
-                                                      L.ptr(ids), L.ptr(ws), ws.numel(), _st(query_planes)),
-            "cc_similarity_topk_grouped_planes_f32")
-    return scores, ids.to(torch.int64)
+    return _topk("similarity_topk_grouped", query_planes, gallery_planes, n_gallery, mult, products, k, group_head=group_head)
 
 
 @similarity_topk_grouped.register_fake
 def _(query_planes, gallery_planes, n_gallery, mult, products, k, group_head):
-    _check_group_head("similarity_topk_grouped", query_planes, gallery_planes, n_gallery, group_head)
-    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
-            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+    return _topk_fake("similarity_topk_grouped", query_planes, gallery_planes, n_gallery, k, group_head=group_head)
 
 
 @custom_op(NS + "::similarity_topk_grouped_dsl", mutates_args=(), device_types="cuda")
@@ -1401,28 +1357,14 @@ def similarity_topk_grouped_dsl(query_planes: torch.Tensor, gallery_planes: torc
                                 group_head: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """similarity_topk_grouped ranking the dual softmax D of similarity_topk_dsl (same m, s, stats_on_gallery, n_total): a
     group's score is the largest D of its rows.  cc_similarity_topk_grouped_dsl_planes_f32."""
-    Bq = query_planes.shape[0]
-    E3 = _check_group_head("similarity_topk_grouped_dsl", query_planes, gallery_planes, n_gallery, group_head)
-    _check_dsl_stats("similarity_topk_grouped_dsl", m, s, int(n_gallery) if stats_on_gallery else Bq)
-    query_planes, gallery_planes, m, s = query_planes.contiguous(), gallery_planes.contiguous(), m.contiguous(), s.contiguous()
-    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
-    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
-    lib = L.lib()
-    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
-    L.check(lib.cc_similarity_topk_grouped_dsl_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
-                                                          float(mult), int(products), int(k), L.ptr(m), L.ptr(s),
-                                                          int(stats_on_gallery), int(n_total), L.ptr(group_head), L.ptr(scores),
-                                                          L.ptr(ids), L.ptr(ws), ws.numel(), _st(query_planes)),
-            "cc_similarity_topk_grouped_dsl_planes_f32")
-    return scores, ids.to(torch.int64)
+    return _topk("similarity_topk_grouped_dsl", query_planes, gallery_planes, n_gallery, mult, products, k, m=m, s=s,
+                 stats_on_gallery=stats_on_gallery, n_total=n_total, group_head=group_head)
 
 
 @similarity_topk_grouped_dsl.register_fake
 def _(query_planes, gallery_planes, n_gallery, mult, products, k, m, s, stats_on_gallery, n_total, group_head):
-    _check_group_head("similarity_topk_grouped_dsl", query_planes, gallery_planes, n_gallery, group_head)
-    _check_dsl_stats("similarity_topk_grouped_dsl", m, s, int(n_gallery) if stats_on_gallery else query_planes.shape[0])
-    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
-            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+    return _topk_fake("similarity_topk_grouped_dsl", query_planes, gallery_planes, n_gallery, k, m=m, s=s,
+                      stats_on_gallery=stats_on_gallery, group_head=group_head)
 
 
 def mask_words(n):
@@ -1441,9 +1383,9 @@ def _check_row_mask(name, mask, rows, n, planes, what="row_mask"):
         raise ValueError("%s: %s on %s, the planes on %s" % (name, what, mask.device, planes.device))
 
 
-def _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head,
-                       name="similarity_topk_masked"):
-    """(similarity_rank runs it under its own name; there the mask is optional)"""
+def _check_search(name, query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head):
+    """the planes and the optional parts of a search request - row mask, dual-softmax statistics, group heads - for every
+    top-k, rank, target-score and count op (the fake kernels run it too: every refusal is an op-level ValueError)"""
     if group_head is not None:
         E3 = _check_group_head(name, query_planes, gallery_planes, n_gallery, group_head)
     else:
@@ -1459,52 +1401,31 @@ def _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, 
     return E3
 
 
-@custom_op(NS + "::similarity_topk_masked", mutates_args=(), device_types="cuda")
-def similarity_topk_masked(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
-                           k: int, row_mask: torch.Tensor, m: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None,
-                           stats_on_gallery: int = 1, n_total: int = 0,
-                           group_head: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """similarity_topk (m, s: similarity_topk_dsl; group_head: the grouped ops) over the gallery rows whose bit is set in
-    row_mask: int32 words, bit b of word w = row 32 w + b; [W] - one mask for all queries, tiles of 16 rows without a set bit
-    are not even read - or [Bq, W], one mask per query row; W >= ceil(n_gallery / 32), bits at or above n_gallery are ignored.
-    The result is the unmasked op's with the other rows left out (same bits, same order, ids of the whole gallery; the fill
-    starts behind the selectable rows or groups - a group is ranked by its best selectable row).
-    cc_similarity_topk_masked_planes_f32."""
-    Bq = query_planes.shape[0]
-    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
-    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
-    if m is not None:
-        m, s = m.contiguous(), s.contiguous()
-    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
-    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
-    lib = L.lib()
-    ws = L.workspace(lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k)), query_planes.device)
-    L.check(lib.cc_similarity_topk_masked_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
-                                                     float(mult), int(products), int(k), L.ptr(row_mask),
-                                                     1 if row_mask.dim() == 1 else Bq, int(row_mask.shape[-1]), L.ptr(m), L.ptr(s),
-                                                     int(stats_on_gallery), int(n_total), L.ptr(group_head), L.ptr(scores),
-                                                     L.ptr(ids), L.ptr(ws), ws.numel(), _st(query_planes)),
-            "cc_similarity_topk_masked_planes_f32")
-    return scores, ids.to(torch.int64)
-
-
-@similarity_topk_masked.register_fake
-def _(query_planes, gallery_planes, n_gallery, mult, products, k, row_mask, m=None, s=None, stats_on_gallery=1, n_total=0,
-      group_head=None):
-    _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
-    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
-            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
-
-
 TOPK_DEEP_MAXK = 4096          # CC_TOPK_DEEP_MAXK
+# the optional parts the C entry of every top-k op takes, in its argument order, between k and the outputs
+_TOPK_PARTS = {"similarity_topk": (), "similarity_topk_dsl": ("stats",), "similarity_topk_grouped": ("heads",),
+               "similarity_topk_grouped_dsl": ("stats", "heads"), "similarity_topk_masked": ("mask", "stats", "heads"),
+               "similarity_topk_deep": ("mask", "stats", "heads", "cursor")}
 
 
-def _check_topk_deep(query_planes, gallery_planes, n_gallery, k, row_mask, m, s, stats_on_gallery, group_head, after_scores,
-                     after_ids):
-    """similarity_topk_masked's checks (the mask only when there is one), k, and the cursor: both tensors or neither, one
-    fp32 score and one int32 / int64 id per query row on the planes' device"""
-    name = "similarity_topk_deep"
-    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head, name)
+def _mask_args(row_mask, Bq):
+    """an optional row mask -> the (pointer, mask_rows, mask_words) of the C entries"""
+    if row_mask is None:
+        return L.ptr(None), 0, 0
+    return L.ptr(row_mask), 1 if row_mask.dim() == 1 else Bq, int(row_mask.shape[-1])
+
+
+def _contiguous_stats(m, s):
+    return (m, s) if m is None else (m.contiguous(), s.contiguous())
+
+
+def _check_topk(name, query_planes, gallery_planes, n_gallery, k, row_mask=None, m=None, s=None, stats_on_gallery=1,
+                group_head=None, after_scores=None, after_ids=None):
+    """_check_search and, for similarity_topk_deep, k and the cursor: both tensors or neither, one fp32 score and one int32 /
+    int64 id per query row on the planes' device"""
+    E3 = _check_search(name, query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
+    if name != "similarity_topk_deep":
+        return E3
     if not 1 <= int(k) <= TOPK_DEEP_MAXK:
         raise ValueError("%s: 1 <= k <= %d, not %d" % (name, TOPK_DEEP_MAXK, int(k)))
     if (after_scores is None) != (after_ids is None):
@@ -1521,6 +1442,63 @@ def _check_topk_deep(query_planes, gallery_planes, n_gallery, k, row_mask, m, s,
     return E3
 
 
+def _topk(name, query_planes, gallery_planes, n_gallery, mult, products, k, row_mask=None, m=None, s=None, stats_on_gallery=1,
+          n_total=0, group_head=None, after_scores=None, after_ids=None):
+    """The body of the six top-k ops: check, allocate scores / ids, size the workspace, call the C entry cc_<name>_planes_f32
+    with the parts _TOPK_PARTS names, ids to int64."""
+    Bq, deep = query_planes.shape[0], name == "similarity_topk_deep"
+    E3 = _check_topk(name, query_planes, gallery_planes, n_gallery, k, row_mask, m, s, stats_on_gallery, group_head, after_scores,
+                     after_ids)
+    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
+    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
+    if deep and (Bq == 0 or int(n_gallery) == 0):           # no row: nothing to rank
+        return scores.fill_(float("-inf")), ids.fill_(-1).to(torch.int64)
+    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
+    m, s = _contiguous_stats(m, s)
+    if after_scores is not None:
+        after_scores, after_ids = after_scores.contiguous(), after_ids.to(torch.int32).contiguous()
+    parts = {"mask": _mask_args(row_mask, Bq), "stats": (L.ptr(m), L.ptr(s), int(stats_on_gallery), int(n_total)),
+             "heads": (L.ptr(group_head),), "cursor": (L.ptr(after_scores), L.ptr(after_ids))}
+    lib, entry = L.lib(), "cc_%s_planes_f32" % name
+    if deep:
+        nbytes = lib.cc_similarity_topk_deep_workspace_bytes(Bq, int(n_gallery), E3 // 3, int(products), int(k))
+    else:
+        nbytes = lib.cc_similarity_topk_workspace_bytes(Bq, int(n_gallery), int(k))
+    ws = L.workspace(nbytes, query_planes.device)
+    L.check(getattr(lib, entry)(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3, float(mult), int(products),
+                                int(k), *(a for part in _TOPK_PARTS[name] for a in parts[part]), L.ptr(scores), L.ptr(ids),
+                                L.ptr(ws), ws.numel(), _st(query_planes)), entry)
+    return scores, ids.to(torch.int64)
+
+
+def _topk_fake(name, query_planes, gallery_planes, n_gallery, k, **parts):
+    _check_topk(name, query_planes, gallery_planes, n_gallery, k, **parts)
+    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
+            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+
+
+@custom_op(NS + "::similarity_topk_masked", mutates_args=(), device_types="cuda")
+def similarity_topk_masked(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
+                           k: int, row_mask: torch.Tensor, m: Optional[torch.Tensor] = None, s: Optional[torch.Tensor] = None,
+                           stats_on_gallery: int = 1, n_total: int = 0,
+                           group_head: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """similarity_topk (m, s: similarity_topk_dsl; group_head: the grouped ops) over the gallery rows whose bit is set in
+    row_mask: int32 words, bit b of word w = row 32 w + b; [W] - one mask for all queries, tiles of 16 rows without a set bit
+    are not even read - or [Bq, W], one mask per query row; W >= ceil(n_gallery / 32), bits at or above n_gallery are ignored.
+    The result is the unmasked op's with the other rows left out (same bits, same order, ids of the whole gallery; the fill
+    starts behind the selectable rows or groups - a group is ranked by its best selectable row).
+    cc_similarity_topk_masked_planes_f32."""
+    return _topk("similarity_topk_masked", query_planes, gallery_planes, n_gallery, mult, products, k, row_mask, m, s, stats_on_gallery,
+                 n_total, group_head)
+
+
+@similarity_topk_masked.register_fake
+def _(query_planes, gallery_planes, n_gallery, mult, products, k, row_mask, m=None, s=None, stats_on_gallery=1, n_total=0,
+      group_head=None):
+    return _topk_fake("similarity_topk_masked", query_planes, gallery_planes, n_gallery, k, row_mask=row_mask, m=m, s=s,
+                      stats_on_gallery=stats_on_gallery, group_head=group_head)
+
+
 @custom_op(NS + "::similarity_topk_deep", mutates_args=(), device_types="cuda")
 def similarity_topk_deep(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_gallery: int, mult: float, products: int,
                          k: int, row_mask: Optional[torch.Tensor] = None, m: Optional[torch.Tensor] = None,
@@ -1534,45 +1512,21 @@ def similarity_topk_deep(query_planes: torch.Tensor, gallery_planes: torch.Tenso
     an id < 0 (the fill) gives the fill.  Built in pages of at most 128 entries, each one pass over the gallery restricted to
     the keys below the page before; the pages hand over on the device (no host read).  n_gallery == 0 gives the fill without a
     launch.  cc_similarity_topk_deep_planes_f32."""
-    Bq = query_planes.shape[0]
-    E3 = _check_topk_deep(query_planes, gallery_planes, n_gallery, k, row_mask, m, s, stats_on_gallery, group_head, after_scores,
-                          after_ids)
-    scores = _e(Bq, int(k), like=query_planes, dtype=torch.float32)
-    ids = _e(Bq, int(k), like=query_planes, dtype=torch.int32)
-    if Bq == 0 or int(n_gallery) == 0:                      # no row: nothing to rank
-        return scores.fill_(float("-inf")), ids.fill_(-1).to(torch.int64)
-    query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
-    if m is not None:
-        m, s = m.contiguous(), s.contiguous()
-    if after_scores is not None:
-        after_scores, after_ids = after_scores.contiguous(), after_ids.to(torch.int32).contiguous()
-    lib = L.lib()
-    ws = L.workspace(lib.cc_similarity_topk_deep_workspace_bytes(Bq, int(n_gallery), E3 // 3, int(products), int(k)),
-                     query_planes.device)
-    masked = row_mask is not None
-    L.check(lib.cc_similarity_topk_deep_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
-                                                   float(mult), int(products), int(k), L.ptr(row_mask),
-                                                   (1 if row_mask.dim() == 1 else Bq) if masked else 0,
-                                                   int(row_mask.shape[-1]) if masked else 0, L.ptr(m), L.ptr(s),
-                                                   int(stats_on_gallery), int(n_total), L.ptr(group_head), L.ptr(after_scores),
-                                                   L.ptr(after_ids), L.ptr(scores), L.ptr(ids), L.ptr(ws), ws.numel(),
-                                                   _st(query_planes)), "cc_similarity_topk_deep_planes_f32")
-    return scores, ids.to(torch.int64)
+    return _topk("similarity_topk_deep", query_planes, gallery_planes, n_gallery, mult, products, k, row_mask, m, s, stats_on_gallery,
+                 n_total, group_head, after_scores, after_ids)
 
 
 @similarity_topk_deep.register_fake
 def _(query_planes, gallery_planes, n_gallery, mult, products, k, row_mask=None, m=None, s=None, stats_on_gallery=1, n_total=0,
       group_head=None, after_scores=None, after_ids=None):
-    _check_topk_deep(query_planes, gallery_planes, n_gallery, k, row_mask, m, s, stats_on_gallery, group_head, after_scores,
-                     after_ids)
-    return (query_planes.new_empty((query_planes.shape[0], k), dtype=torch.float32),
-            query_planes.new_empty((query_planes.shape[0], k), dtype=torch.int64))
+    return _topk_fake("similarity_topk_deep", query_planes, gallery_planes, n_gallery, k, row_mask=row_mask, m=m, s=s,
+                      stats_on_gallery=stats_on_gallery, group_head=group_head, after_scores=after_scores, after_ids=after_ids)
 
 
 def _check_rank(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head):
-    """similarity_topk_masked's checks (the mask only when there is one) and the targets: one int32 / int64 per query row"""
+    """_check_search and the targets: one int32 / int64 per query row"""
     name = "similarity_rank"
-    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head, name)
+    E3 = _check_search(name, query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
     if (target.dtype not in (torch.int32, torch.int64) or target.dim() != 1 or target.shape[0] != query_planes.shape[0]
             or target.device != query_planes.device):
         raise ValueError("%s: target %s %s on %s is not one int32 / int64 position per query row (%d) on %s"
@@ -1596,8 +1550,7 @@ def similarity_rank(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_
     Bq = query_planes.shape[0]
     E3 = _check_rank(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head)
     query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
-    if m is not None:
-        m, s = m.contiguous(), s.contiguous()
+    m, s = _contiguous_stats(m, s)
     target = target.to(torch.int32).contiguous()
     counts = _e(Bq, 3, like=query_planes, dtype=torch.int32)
     score = _e(Bq, like=query_planes, dtype=torch.float32)
@@ -1607,11 +1560,9 @@ def similarity_rank(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n_
         return counts.zero_(), score.fill_(float("-inf"))
     lib = L.lib()
     ws = L.workspace(lib.cc_similarity_rank_workspace_bytes(Bq, int(n_gallery)), query_planes.device)
-    masked = row_mask is not None
     L.check(lib.cc_similarity_rank_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3, float(mult),
-                                              int(products), L.ptr(target), L.ptr(row_mask),
-                                              (1 if row_mask.dim() == 1 else Bq) if masked else 0,
-                                              int(row_mask.shape[-1]) if masked else 0, L.ptr(m), L.ptr(s), int(stats_on_gallery),
+                                              int(products), L.ptr(target), *_mask_args(row_mask, Bq), L.ptr(m), L.ptr(s),
+                                              int(stats_on_gallery),
                                               int(n_total), L.ptr(group_head), L.ptr(counts), L.ptr(score), L.ptr(ws), ws.numel(),
                                               _st(query_planes)), "cc_similarity_rank_planes_f32")
     return counts, score
@@ -1680,7 +1631,7 @@ def _check_per_query(name, what, t, dtypes, planes):
 
 def _check_target_score(query_planes, gallery_planes, n_gallery, target, row_mask, m, s, stats_on_gallery, group_head):
     name = "similarity_target_score"
-    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head, name)
+    E3 = _check_search(name, query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
     _check_per_query(name, "target", target, (torch.int32, torch.int64), query_planes)
     return E3
 
@@ -1702,14 +1653,11 @@ def similarity_target_score(query_planes: torch.Tensor, gallery_planes: torch.Te
     if int(n_gallery) == 0:                                 # no row: every target is outside
         return score.fill_(float("-inf"))
     query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
-    if m is not None:
-        m, s = m.contiguous(), s.contiguous()
+    m, s = _contiguous_stats(m, s)
     target = target.to(torch.int32).contiguous()
-    masked = row_mask is not None
     L.check(L.lib().cc_similarity_target_score_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3,
-                                                          float(mult), int(products), L.ptr(target), L.ptr(row_mask),
-                                                          (1 if row_mask.dim() == 1 else Bq) if masked else 0,
-                                                          int(row_mask.shape[-1]) if masked else 0, L.ptr(m), L.ptr(s),
+                                                          float(mult), int(products), L.ptr(target),
+                                                          *_mask_args(row_mask, Bq), L.ptr(m), L.ptr(s),
                                                           int(stats_on_gallery), int(n_total), L.ptr(group_head), L.ptr(score),
                                                           _st(query_planes)), "cc_similarity_target_score_planes_f32")
     return score
@@ -1724,7 +1672,7 @@ def _(query_planes, gallery_planes, n_gallery, mult, products, target, row_mask=
 
 def _check_count(query_planes, gallery_planes, n_gallery, bound_scores, bound_front, row_mask, m, s, stats_on_gallery, group_head):
     name = "similarity_count"
-    E3 = _check_masked_topk(query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head, name)
+    E3 = _check_search(name, query_planes, gallery_planes, n_gallery, row_mask, m, s, stats_on_gallery, group_head)
     _check_per_query(name, "bound_scores", bound_scores, (torch.float32,), query_planes)
     _check_per_query(name, "bound_front", bound_front, (torch.int32,), query_planes)
     return E3
@@ -1750,16 +1698,13 @@ def similarity_count(query_planes: torch.Tensor, gallery_planes: torch.Tensor, n
     if int(n_gallery) == 0:                                 # no row: nothing to count
         return counts.zero_()
     query_planes, gallery_planes = query_planes.contiguous(), gallery_planes.contiguous()
-    if m is not None:
-        m, s = m.contiguous(), s.contiguous()
+    m, s = _contiguous_stats(m, s)
     bound_scores, bound_front = bound_scores.contiguous(), bound_front.contiguous()
     lib = L.lib()
     ws = L.workspace(lib.cc_similarity_count_workspace_bytes(Bq, int(n_gallery)), query_planes.device)
-    masked = row_mask is not None
     L.check(lib.cc_similarity_count_planes_f32(L.ptr(query_planes), L.ptr(gallery_planes), Bq, int(n_gallery), E3 // 3, float(mult),
-                                               int(products), L.ptr(bound_scores), L.ptr(bound_front), L.ptr(row_mask),
-                                               (1 if row_mask.dim() == 1 else Bq) if masked else 0,
-                                               int(row_mask.shape[-1]) if masked else 0, L.ptr(m), L.ptr(s), int(stats_on_gallery),
+                                               int(products), L.ptr(bound_scores), L.ptr(bound_front),
+                                               *_mask_args(row_mask, Bq), L.ptr(m), L.ptr(s), int(stats_on_gallery),
                                                int(n_total), L.ptr(group_head), L.ptr(counts), L.ptr(ws), ws.numel(),
                                                _st(query_planes)), "cc_similarity_count_planes_f32")
     return counts

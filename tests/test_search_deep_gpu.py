@@ -154,6 +154,63 @@ def test_the_first_128_columns_are_the_plain_ops():
         assert torch.equal(deep[1][:, :128], plain[1]) and _bits(deep[0][:, :128].contiguous(), plain[0])
 
 
+def _mode_case(n):
+    """-> (head int32 [n + BEHIND], one mask bool [n], per-query masks bool [5, n]) with a group boundary inside a tile and
+    one group that has an all-dead tile between two live ones under the one mask"""
+    if n == 40:
+        sizes, dead = (3, 34, 3), (16, 32)                                 # the middle group: tiles 0 and 2 live, tile 1 dead
+    else:
+        sizes, dead = (7,) * 85 + (1000,) + (5,) * 500 + (4,), (640, 704)  # the group of 1000 rows [595, 1595): tiles 40..43 dead
+    assert sum(sizes) == n
+    starts = np.concatenate(([0], np.cumsum(sizes)[:-1]))
+    head = np.concatenate([np.repeat(starts, sizes), np.arange(n, n + BEHIND)]).astype(np.int32)
+    rng = np.random.default_rng(n)
+    one = rng.random(n) < 0.75
+    one[dead[0]:dead[1]] = False
+    one[[dead[0] - 2, dead[1] + 2]] = True
+    assert (starts % 16 != 0).any() and dead[0] % 16 == 0 and dead[1] % 16 == 0
+    assert head[dead[0] - 2] == head[dead[1] + 2]                           # one group on both sides of the dead tiles
+    return head, one, rng.random((5, n)) < 0.5
+
+
+@pytest.mark.parametrize("n", [4099, 40])
+def test_without_a_cursor_the_deep_op_is_the_specialised_op_of_every_mode(n):
+    """k <= 128: one page, the launches of the specialised op - scores as int32 bits, ids equal.  n = 4099: 8 slices and a
+    ragged last tile; n = 40: one slice and the fill beyond 40.  Bq = 5: a partial group of 16 query rows."""
+    Bq, products = 5, 2
+    assert L.lib().cc_similarity_topk_slices(Bq, n, 128) == (8 if n == 4099 else 1)
+    g = torch.Generator().manual_seed(150 + n)
+    rows_q, rows_g = torch.randn(Bq, 64, generator=g), torch.randn(n + BEHIND, 64, generator=g)
+    q, gal = _planes(rows_q, False), _planes(rows_g, True)                 # text queries, a clip gallery
+    q0, gal0 = _planes(rows_q, True), _planes(rows_g, False)               # clip queries, a caption gallery
+    on_gallery = op.dsl_col_stats_planes(q, gal, Bq, n, MULT, products) + (1, Bq)
+    on_query = op.dsl_col_stats_planes(gal0, q0, n, Bq, MULT, products) + (0, n)
+    head, one, per_query = _mode_case(n)
+    hd, one_w, per_query_w = _dev(head), _mask(one, n), _mask(per_query, n)
+    for k in (17, 128):
+        pairs = {
+            "plain": (_deep(q, gal, n, products, k), op.similarity_topk(q, gal, n, MULT, products, k)),
+            "dual softmax, gallery side": (_deep(q, gal, n, products, k, stats=on_gallery),
+                                           op.similarity_topk_dsl(q, gal, n, MULT, products, k, *on_gallery)),
+            "dual softmax, query side": (_deep(q0, gal0, n, products, k, stats=on_query),
+                                         op.similarity_topk_dsl(q0, gal0, n, MULT, products, k, *on_query)),
+            "grouped": (_deep(q, gal, n, products, k, head=head), op.similarity_topk_grouped(q, gal, n, MULT, products, k, hd)),
+            "grouped + dual softmax": (_deep(q, gal, n, products, k, head=head, stats=on_gallery),
+                                       op.similarity_topk_grouped_dsl(q, gal, n, MULT, products, k, *on_gallery, hd)),
+            "one mask": (_deep(q, gal, n, products, k, mask=one_w), op.similarity_topk_masked(q, gal, n, MULT, products, k, one_w)),
+            "per-query masks": (_deep(q, gal, n, products, k, mask=per_query_w),
+                                op.similarity_topk_masked(q, gal, n, MULT, products, k, per_query_w)),
+            "masked + grouped": (_deep(q, gal, n, products, k, mask=one_w, head=head),
+                                 op.similarity_topk_masked(q, gal, n, MULT, products, k, one_w, group_head=hd)),
+        }
+        for mode, (deep, special) in pairs.items():
+            assert bool((special[1][:, 0] >= 0).all()), mode                   # (a list, not the fill)
+            assert torch.equal(deep[1], special[1]) and _bits(deep[0], special[0]), (mode, k)
+        if n == 40 and k == 128:                                               # the fill begins behind the 40 rows
+            ids = pairs["plain"][1][1]
+            assert bool((ids[:, :40] >= 0).all()) and bool((ids[:, 40:] == -1).all())
+
+
 # ------------------------------------------------------------------------------------------------ 3. ties across page edges
 def test_identical_gallery_rows_come_in_id_order():
     g = torch.Generator().manual_seed(11)
