@@ -67,6 +67,35 @@ from .eval import HipBackend, _video_operand
 SIDES = ("video", "text")
 
 
+def _host_ints(value, what, name):
+    """The one reading of a host integer argument: an int, a flat host sequence of ints or a CPU LongTensor (0-D or 1-D) ->
+    int64 array [n].  Anything else is the one ValueError - a device tensor above all: it would have to be read, and reading
+    synchronises.  ``what``: the method, for the message ("FeatureGallery.rank_groups"); ``name``: what the values are
+    called ("labels")."""
+    arr = None
+    if torch.is_tensor(value):
+        if value.device.type == "cpu" and value.dtype == torch.int64 and value.dim() <= 1:
+            arr = value.numpy().reshape(-1)
+    elif isinstance(value, (int, np.integer)):
+        arr = np.array([int(value)])
+    else:
+        try:
+            arr = np.asarray(list(value))
+        except (TypeError, ValueError):                          # (not iterable; a ragged nest)
+            pass
+    if arr is None or arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+        got = "a %s %s tensor %s" % (value.device, value.dtype, tuple(value.shape)) if torch.is_tensor(value) else "%.60r" % (value,)
+        raise ValueError("%s: %s are an int, a flat host sequence of ints or a CPU LongTensor, not %s (reading a device "
+                         "tensor would synchronise)" % (what, name, got))
+    return arr.astype(np.int64)
+
+
+def _exactly(arr, n, what, name, per):
+    if arr.size != n:
+        raise ValueError("%s: %d %s, not one per %s (%d)" % (what, arr.size, name, per, n))
+    return arr
+
+
 def _scales(value, frame_duration, what, count=None):
     """an int, or one int per scale -> list of segment counts; every value a positive multiple of frame_duration"""
     if isinstance(value, (int, np.integer)):
@@ -97,15 +126,7 @@ def window_table(lengths, frame_duration, window, stride=None, segments=None):
     fd = int(frame_duration)
     if fd <= 0:
         raise ValueError("window_table: frame_duration %d" % fd)
-    if torch.is_tensor(lengths):
-        if lengths.device.type != "cpu" or lengths.dtype != torch.int64 or lengths.dim() != 1:
-            raise ValueError("window_table: lengths are a host sequence or a flat CPU LongTensor, not a %s %s tensor %s (reading "
-                             "a device tensor would synchronise)" % (lengths.device, lengths.dtype, tuple(lengths.shape)))
-        lens = lengths.numpy()
-    else:
-        lens = np.asarray(list(lengths))
-        if lens.ndim != 1 or (lens.size and lens.dtype.kind not in "iu"):
-            raise ValueError("window_table: lengths are a flat sequence of ints")
+    lens = _host_ints(lengths, "window_table", "lengths")
     ws = _scales(window, fd, "window")
     if stride is None:
         ss = [max(w // 2, 1) for w in ws]
@@ -495,11 +516,8 @@ class FeatureGallery:
         self._check_group_arg(group, what)
         if group is None or isinstance(group, (int, np.integer)):
             return group
-        lab = self._label_list(group, what)
-        if lab.shape != (b,):
-            raise ValueError("FeatureGallery.%s: group= holds %d labels for %d videos (one int, or one int per video)"
-                             % (what, lab.size, b))
-        return lab[table[:, 0]]
+        what = "FeatureGallery." + what
+        return _exactly(_host_ints(group, what, "group= labels"), b, what, "group= labels", "video")[table[:, 0]]
 
     def _window_rows(self, visual_output, table):
         """per-segment features [b, S, E] + the segment table -> the windows' operand rows [nW, 3E]"""
@@ -542,9 +560,10 @@ class FeatureGallery:
             raise ValueError("FeatureGallery.add_window_features: per-segment features [b, S, %d], not %s"
                              % (self.E, tuple(visual_output.shape)))
         b, S = visual_output.shape[:2]
-        table = window_table(lengths, int(self.core.f_frame_duration), window, stride, segments=S)
-        if b == 0 or len(lengths) != b:
-            raise ValueError("FeatureGallery.add_window_features: %d lengths for %d videos" % (len(lengths), b))
+        lens = _host_ints(lengths, "FeatureGallery.add_window_features", "lengths")
+        table = window_table(lens, int(self.core.f_frame_duration), window, stride, segments=S)
+        if b == 0 or lens.size != b:
+            raise ValueError("FeatureGallery.add_window_features: %d lengths for %d videos" % (lens.size, b))
         return self._add_window_features(visual_output, table, self._window_groups(group, table, b, "add_window_features"))
 
     def add_windows(self, video, lengths, window, stride=None, group=None, encode_batch=64):
@@ -574,10 +593,11 @@ class FeatureGallery:
                              % (F, T))
         if int(encode_batch) < 1:
             raise ValueError("FeatureGallery.add_windows: encode_batch %d" % int(encode_batch))
-        table = window_table(lengths, fd, window, stride)
-        if b == 0 or len(lengths) != b:
-            raise ValueError("FeatureGallery.add_windows: %d lengths for %d videos" % (len(lengths), b))
-        over = np.flatnonzero(np.asarray(lengths.numpy() if torch.is_tensor(lengths) else list(lengths)) > F)
+        lens = _host_ints(lengths, "FeatureGallery.add_windows", "lengths")
+        table = window_table(lens, fd, window, stride)
+        if b == 0 or lens.size != b:
+            raise ValueError("FeatureGallery.add_windows: %d lengths for %d videos" % (lens.size, b))
+        over = np.flatnonzero(lens > F)
         if over.size:
             raise ValueError("FeatureGallery.add_windows: video %d is longer than the %d frames given" % (int(over[0]), F))
         group = self._window_groups(group, table, b, "add_windows")
@@ -869,29 +889,16 @@ class FeatureGallery:
                 raise ValueError("FeatureGallery.%s: target %s %s is not one int32 / int64 position per query (%d)"
                                  % (what, tuple(target.shape), target.dtype, nq))
             return target
-        if torch.is_tensor(target):
-            pos = target.numpy().reshape(-1) if target.dtype == torch.int64 and target.dim() <= 1 else None
-        elif isinstance(target, (int, np.integer)):
-            pos = np.array([int(target)])
-        else:
-            pos = np.asarray(list(target))
-            pos = pos if pos.ndim == 1 and (pos.size == 0 or pos.dtype.kind in "iu") else None
-        if pos is None:
-            raise ValueError("FeatureGallery.%s: target is a flat host sequence of ints, a CPU LongTensor or a device integer "
-                             "tensor" % what)
-        if pos.size != nq:
-            raise ValueError("FeatureGallery.%s: %d targets for %d queries (one position per query)" % (what, pos.size, nq))
-        pos = pos.astype(np.int64)
+        what = "FeatureGallery." + what
+        pos = _exactly(_host_ints(target, what, "targets"), nq, what, "targets", "query")
         if pos.size and (pos.min() < 0 or pos.max() >= self._n):
-            raise ValueError("FeatureGallery.%s: target %d is outside [0, %d)"
-                             % (what, int(pos[(pos < 0) | (pos >= self._n)][0]), self._n))
+            raise ValueError("%s: target %d is outside [0, %d)" % (what, int(pos[(pos < 0) | (pos >= self._n)][0]), self._n))
         return self._host_to_device(pos)
 
     def _group_targets(self, target, nq):
         """one group label per query (host values) -> the positions of the groups' heads, through the host label mirror"""
-        want = self._label_list(target, "rank_groups")
-        if want.size != nq:
-            raise ValueError("FeatureGallery.rank_groups: %d target labels for %d queries (one label per query)" % (want.size, nq))
+        want = _exactly(_host_ints(target, "FeatureGallery.rank_groups", "labels"), nq, "FeatureGallery.rank_groups",
+                        "target labels", "query")
         heads = self._group_heads(want)
         if (heads < 0).any():
             raise ValueError("FeatureGallery.rank_groups: no row held has the label %d" % int(want[heads < 0][0]))

@@ -36,24 +36,9 @@ import torch.distributed as tdist
 
 from . import dist as ccdist
 from . import torch_ops as T
-from .search import FeatureGallery
+from .search import FeatureGallery, _exactly, _host_ints
 
 FRONT_ALL = 2 ** 31 - 1                                          # a position no shard holds: every equal entry lies in front of it
-
-
-def _host_ints(values, what):
-    """an int, a flat host sequence of ints or a CPU LongTensor -> int64 array (a device tensor would have to be read)"""
-    if torch.is_tensor(values):
-        if values.device.type != "cpu" or values.dtype != torch.int64 or values.dim() > 1:
-            raise ValueError("ShardedGallery.%s: an int, a flat host sequence of ints or a CPU LongTensor, not a %s %s tensor %s"
-                             % (what, values.device, values.dtype, tuple(values.shape)))
-        return values.numpy().reshape(-1).astype(np.int64)
-    if isinstance(values, (int, np.integer)):
-        return np.array([int(values)], dtype=np.int64)
-    arr = np.asarray(list(values))
-    if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
-        raise ValueError("ShardedGallery.%s: one int or a flat sequence of ints" % what)
-    return arr.astype(np.int64)
 
 
 class ShardedGallery:
@@ -132,7 +117,7 @@ class ShardedGallery:
     def _route(self, ids, what):
         """host global ids -> {shard index: int64 local positions} for the shards of this process; a shard index outside
         [0, S): ValueError (on every rank alike)"""
-        ids = _host_ints(ids, what)
+        ids = _host_ints(ids, "ShardedGallery." + what, "ids")
         shard, local = self.split(ids)
         if ids.size and ((ids < 0).any() or (shard >= self.S).any()):
             raise ValueError("ShardedGallery.%s: id %d names no shard of %d" % (what, int(ids[(ids < 0) | (shard >= self.S)][0]), self.S))
@@ -193,7 +178,7 @@ class ShardedGallery:
     def _route_labels(self, labels, what, live_only):
         """labels -> {shard index: the ones that shard holds}; in-process a label nobody holds: ValueError"""
         self._need_grouped(what)
-        want = np.unique(_host_ints(labels, what))
+        want = np.unique(_host_ints(labels, "ShardedGallery." + what, "labels"))
         routed = {r: np.intersect1d(want, self._held(g, live_only)) for r, g in self._mine()}
         if not self.distributed:
             missing = np.setdiff1d(want, np.concatenate(list(routed.values())) if routed else want)
@@ -324,18 +309,16 @@ class ShardedGallery:
                 raise ValueError("ShardedGallery.%s: target %s %s is not one int64 global id per query (%d)"
                                  % (what, tuple(target.shape), target.dtype, nq))
             return target.to(self.device)
-        ids = _host_ints(target, what)
-        if ids.size != nq:
-            raise ValueError("ShardedGallery.%s: %d targets for %d queries (one global id per query)" % (what, ids.size, nq))
+        what = "ShardedGallery." + what
+        ids = _exactly(_host_ints(target, what, "targets"), nq, what, "target global ids", "query")
         return self.shards[0]._host_to_device(ids)
 
     def _label_targets(self, target, nq, what):
         """one label per query (host ints) -> per shard of this process the local heads, int32 on the shard's device, -1 where
         the shard does not hold the label"""
         self._need_grouped(what)
-        want = _host_ints(target, what)
-        if want.size != nq:
-            raise ValueError("ShardedGallery.%s: %d target labels for %d queries (one label per query)" % (what, want.size, nq))
+        want = _exactly(_host_ints(target, "ShardedGallery." + what, "labels"), nq, "ShardedGallery." + what, "target labels",
+                        "query")
         return [g._host_to_device(g._group_heads(want).astype(np.int32)) for g in self.shards]
 
     # ------------------------------------------------------------------ asking

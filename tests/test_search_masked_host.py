@@ -381,3 +381,88 @@ def test_allow_is_checked_on_the_host(model):
     assert gal._allow_words(None, 2).tolist() == pack_bits(gal._live).tolist()
     got = gal._allow_words(torch.from_numpy(np.stack([pack_bits(np.arange(70) < 40), pack_bits(np.arange(70) >= 40)])), 2)
     assert got.tolist() == pack_bits(np.stack([(np.arange(70) < 40), (np.arange(70) >= 40)]) & gal._live).tolist()
+
+
+# ------------------------------------------------------------------------------------------------ host integer arguments
+ACCEPTED = (lambda: 1, lambda: np.int64(1), lambda: [1], lambda: (1,), lambda: torch.tensor([1]), lambda: torch.tensor(1),
+            lambda: [])                                                       # int, NumPy int, list, tuple, 1-D, 0-D; empty
+REFUSED = (lambda: [1.5], lambda: [[1, 2]], lambda: "ab", lambda: torch.tensor([1], dtype=torch.int32),
+           lambda: torch.zeros(1, 1, dtype=torch.long), lambda: torch.zeros(1, dtype=torch.long, device="meta"))
+
+
+def _count(value):
+    """the queries (videos) an entry is asked about: one per value of an accepted form, one for a refused form"""
+    return int(value.numel()) if torch.is_tensor(value) else len(value) if isinstance(value, (list, tuple)) else 1
+
+
+def _lists(value):
+    if isinstance(value, (list, tuple)):
+        return [_lists(v) for v in value]
+    return value.tolist() if hasattr(value, "tolist") else value
+
+
+def _entries():
+    """The entries that read host ints through ``search._host_ints`` -> (name, read, one, none, public): ``read(g, sg, v)``
+    gives what the entry made of ``v`` as nested lists - through the method that does the reading where the public one goes
+    on to the encoder, which refuses CPU tensors; ``one`` / ``none``: that for the value 1 / for no value; ``public``: the
+    public call of the same entry, which must refuse what ``read`` refuses before anything is encoded.  Not here, because
+    they keep their own reading: ``remove`` / ``row_mask(positions=)`` / ``windows`` (``_positions``), ``remove_groups`` /
+    ``row_mask(groups=)`` (``_label_list``) and the labels of ``add*(group=)`` (``_plan_groups``)."""
+    from centerclip_amd.search import window_table
+    ids = lambda v: torch.zeros(_count(v), 16, dtype=torch.long)
+    table = lambda v: window_table([4] * _count(v), 1, 4)                    # one window per video
+    clips = lambda g, v: torch.zeros(_count(v), 1, int(g.core.video_frames), 3, 8, 8)
+    sizes = lambda sg: [len(g) for g in sg.shards]
+    return (("rank(target=)", lambda g, sg, v: g._targets(v, _count(v), "rank"), [1], [],
+             lambda g, sg, v: g.rank(ids(v), target=v)),
+            ("rank_groups(target=)", lambda g, sg, v: g._group_targets(v, _count(v)), [3], [],
+             lambda g, sg, v: g.rank_groups(ids(v), target=v)),
+            ("add_windows(group=)", lambda g, sg, v: np.atleast_1d(g._window_groups(v, table(v), _count(v), "add_windows")), [1], [],
+             lambda g, sg, v: g.add_windows(clips(g, v), [clips(g, v).shape[2]] * _count(v), clips(g, v).shape[2], group=v)),
+            ("window_table(lengths=)", lambda g, sg, v: window_table(v, 1, 1), [[0, 0, 1]], [], None),
+            ("ShardedGallery.remove", lambda g, sg, v: (sg.remove(v), sizes(sg))[1], [3, 4], [4, 4], None),
+            ("ShardedGallery.row_mask(positions=)", lambda g, sg, v: sg.row_mask(positions=v), [[2], [0]], [[0], [0]], None),
+            ("ShardedGallery.remove_groups", lambda g, sg, v: (sg.remove_groups(v), sizes(sg))[1], [3, 4], [4, 4], None),
+            ("ShardedGallery.row_mask(groups=)", lambda g, sg, v: sg.row_mask(groups=v), [[8], [0]], [[0], [0]], None),
+            ("ShardedGallery.rank(target=)", lambda g, sg, v: sg._row_targets(v, _count(v), "rank"), [1], [],
+             lambda g, sg, v: sg.rank(ids(v), target=v)),
+            ("ShardedGallery.rank_groups(target=)", lambda g, sg, v: sg._label_targets(v, _count(v), "rank_groups"), [[3], [-1]],
+             [[], []], lambda g, sg, v: sg.rank_groups(ids(v), target=v)))
+
+
+def _snapshot(*galleries):
+    return [(len(g), g.span, {k: v.clone() if torch.is_tensor(v) else v for k, v in g.state_dict().items()}) for g in galleries]
+
+
+def _same_snapshot(a, b):
+    for (la, sa, da), (lb, sb, db) in zip(a, b):
+        assert (la, sa, set(da)) == (lb, sb, set(db))
+        assert all(torch.equal(da[k], db[k]) if torch.is_tensor(da[k]) else da[k] == db[k] for k in da)
+
+
+@pytest.mark.parametrize("name,read,one,none,public", _entries(), ids=[e[0] for e in _entries()])
+def test_every_host_int_argument_reads_the_same_forms(model, name, read, one, none, public):
+    """One parser: every form of the value 1 that ``remove`` accepts is read as that 1 by each of these entries, the empty
+    list as no value, and what ``remove`` refuses they refuse - by ``read`` and by the public call alike, nothing changed.
+    ``rank(target=)`` has a second form, a device integer tensor passed through unread, so there the device LongTensor is no
+    host form at all (tests/test_search_rank_host.py and test_search_sharded_host.py hold the refusals of that form)."""
+    from centerclip_amd.search_sharded import ShardedGallery
+
+    def galleries():                                 # g and shard 0: labels 0 0 0 1 - the value 1 is a position and a label
+        made = [_bare(model, grouped=True) for _ in range(3)]
+        for g, first in zip(made, (0, 0, 20)):
+            g._append(_rows(4), [first, first, first, first + 1])
+        return made[0], ShardedGallery(shards=made[1:])
+    for form in ACCEPTED:
+        g, sg = galleries()
+        assert _lists(read(g, sg, form())) == (one if _count(form()) else none), form()
+        if public is not None and (_count(form()) or "windows" not in name):       # (no video at all: add_windows refuses that first)
+            with pytest.raises(L.CenterClipHipError):                        # every host check passed: CPU tensors are refused next
+                public(*galleries(), form())
+    g, sg = galleries()
+    before = _snapshot(g, *sg.shards)
+    for form in REFUSED[:-1] if name.endswith("rank(target=)") else REFUSED:  # (the last one is the device tensor)
+        for call in (read, public) if public is not None else (read,):
+            with pytest.raises(ValueError, match="CPU LongTensor"):
+                call(g, sg, form())
+    _same_snapshot(before, _snapshot(g, *sg.shards))
