@@ -135,6 +135,14 @@ def declare(lib):
     lib.cc_resize_crop_u8.restype = c.c_int
     lib.cc_resized_crop_flip_u8.argtypes = [vp, i32, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp]
     lib.cc_resized_crop_flip_u8.restype = c.c_int
+    lib.cc_resize_crop_status.argtypes = [i32, i32, i32, i32]
+    lib.cc_resize_crop_status.restype = c.c_int
+    lib.cc_collate_resize_crop_workspace_bytes.argtypes = [vp, i32, i32, i32, i32]
+    lib.cc_collate_resize_crop_workspace_bytes.restype = sz
+    lib.cc_collate_resize_crop_u8.argtypes = [vp, sz, i32, vp, i32, vp, i32, vp, sz, i32, i32, vp, i32, vp, sz, vp]
+    lib.cc_collate_resize_crop_u8.restype = c.c_int
+    lib.cc_collate_crop_flip_u8.argtypes = [vp, sz, i32, vp, i32, vp, i32, i32, vp, i32, vp]
+    lib.cc_collate_crop_flip_u8.restype = c.c_int
     lib.cc_clip_encode_frames.argtypes = [c.POINTER(VitModel), c.POINTER(Frames), i32, i32, vp, vp, vp,
                                           c.POINTER(TextModel), vp, i32, i32, vp, vp, sz, vp]
     lib.cc_clip_encode_frames.restype = c.c_int

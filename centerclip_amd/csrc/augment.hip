@@ -9,6 +9,8 @@
 // along the lanes.  The box table stays on the device - the host never reads it, so the call is capturable and a replay
 // follows whatever the table holds by then; a row that does not lie inside the frame is never turned into an address.
 //
+// A ragged batch (cc_collate_crop_flip_u8): the same thread's work per output pixel, the box in a table row per output frame.
+//
 // Coordinates are exact: the source coordinate (o + 0.5) crop / n_px - 0.5 is the rational ((2 o + 1) crop - n_px) / (2 n_px);
 // its floor is an integer division and its fraction the remainder over 2 n_px, one correctly rounded fp32 division of two
 // small integers.  THIS TRANSLATION UNIT IS COMPILED WITH -ffp-contract=off (build.py STRICT): the weights and the sums are
@@ -23,7 +25,7 @@ struct View {
     int64_t sf, sc, sy, sx;
 };
 
-View view_of(int fmt, int64_t rows, int64_t cols) {
+__host__ __device__ inline View view_of(int fmt, int64_t rows, int64_t cols) {
     if (fmt == CC_FRAMES_U8_CHW) return View{3 * rows * cols, rows * cols, cols, 1};
     return View{3 * rows * cols, 1, 3 * cols, 3};
 }
@@ -74,19 +76,15 @@ __device__ __forceinline__ uint8_t to_byte(float v) {
     return (uint8_t)(r < 0.0f ? 0.0f : (r > 255.0f ? 255.0f : r));
 }
 
+// The work of the thread that owns output pixel (oy, ox) of one frame, the one statement of the arithmetic: the per-size
+// kernel below and the ragged-batch kernel behind it both call it.  in / out: the frame's first byte; the box is followed only
+// when it lies inside the H x W frame, else the pixel is zero.
 template <int TAPS>
-__global__ __launch_bounds__(kTileX* kTileY) void resized_crop_flip_u8_kernel(const uint8_t* __restrict__ in, View iv, int H,
-                                                                                int W, int frames_per_clip,
-                                                                                const int32_t* __restrict__ boxes,
-                                                                                uint8_t* __restrict__ out, View ov, int n_px,
-                                                                                int tiles_x, int tiles_y) {
-    const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
-    const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
-    if (ox >= n_px || oy >= n_px) return;
-    uint8_t* q = out + (int64_t)f * ov.sf + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
-    const int32_t* box = boxes + (int64_t)(f / frames_per_clip) * kBoxInts;
-    const int top = box[0], left = box[1], bh = box[2], bw = box[3], flip = box[4];
-    // the row is followed only when the box lies inside the frame (H - bh, W - bw cannot overflow: bh, bw >= 1)
+__device__ __forceinline__ void crop_flip_pixel(const uint8_t* __restrict__ base, const View& iv, int H, int W, int top, int left,
+                                                int bh, int bw, int flip, int n_px, int oy, int ox, uint8_t* __restrict__ out,
+                                                const View& ov) {
+    uint8_t* q = out + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
+    // (H - bh, W - bw cannot overflow: bh, bw >= 1)
     if (top < 0 || left < 0 || bh < 1 || bw < 1 || top > H - bh || left > W - bw) {
         q[0] = 0;
         q[ov.sc] = 0;
@@ -97,7 +95,6 @@ __global__ __launch_bounds__(kTileX* kTileY) void resized_crop_flip_u8_kernel(co
     float wx[TAPS], wy[TAPS];
     axis_taps<TAPS>(flip ? n_px - 1 - ox : ox, bw, n_px, ix, wx);
     axis_taps<TAPS>(oy, bh, n_px, iy, wy);
-    const uint8_t* base = in + (int64_t)f * iv.sf;
     float v0 = 0.0f, v1 = 0.0f, v2 = 0.0f;
 #pragma unroll
     for (int r = 0; r < TAPS; ++r) {
@@ -117,6 +114,56 @@ __global__ __launch_bounds__(kTileX* kTileY) void resized_crop_flip_u8_kernel(co
     q[0] = to_byte(v0);
     q[ov.sc] = to_byte(v1);
     q[2 * ov.sc] = to_byte(v2);
+}
+
+template <int TAPS>
+__global__ __launch_bounds__(kTileX* kTileY) void resized_crop_flip_u8_kernel(const uint8_t* __restrict__ in, View iv, int H,
+                                                                                int W, int frames_per_clip,
+                                                                                const int32_t* __restrict__ boxes,
+                                                                                uint8_t* __restrict__ out, View ov, int n_px,
+                                                                                int tiles_x, int tiles_y) {
+    const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
+    const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
+    if (ox >= n_px || oy >= n_px) return;
+    const int32_t* box = boxes + (int64_t)(f / frames_per_clip) * kBoxInts;
+    crop_flip_pixel<TAPS>(in + (int64_t)f * iv.sf, iv, H, W, box[0], box[1], box[2], box[3], box[4], n_px, oy, ox,
+                          out + (int64_t)f * ov.sf, ov);
+}
+
+// A ragged batch (cc_collate_crop_flip_u8 in the header): one table row per OUTPUT frame, blockIdx.z over output frames, folded
+// where there are more frames than planes.  Every workgroup reads its frame's row first - the same address in every lane.  The
+// host never reads the table: a row whose frame does not lie inside the packed buffer, or whose kind is not 1, gives a zero
+// frame, and crop_flip_pixel does the same for a box outside the frame.
+__global__ __launch_bounds__(kTileX* kTileY) void collate_crop_flip_u8_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
+                                                                                int fmt, const int64_t* __restrict__ rows,
+                                                                                int n_out, uint8_t* __restrict__ dst,
+                                                                                int dst_fmt, int n_px) {
+    const int ox = blockIdx.x * kTileX + threadIdx.x, oy = blockIdx.y * kTileY + threadIdx.y;
+    if (ox >= n_px || oy >= n_px) return;
+    const View ov = view_of(dst_fmt, n_px, n_px);
+    for (int f = blockIdx.z; f < n_out; f += gridDim.z) {
+        const int64_t* row = rows + (int64_t)f * CC_COLLATE_BOX_ROW;
+        const int64_t kind = row[0], off = row[1], H = row[2], W = row[3], interp = row[9];
+        uint8_t* out = dst + (int64_t)f * ov.sf;
+        const bool ok = kind == 1 && H >= 4 && W >= 4 && H <= 8192 && W <= 8192 && off >= 0 && off <= src_bytes &&
+                        3 * H * W <= src_bytes - off && (interp == 0 || interp == 1);
+        if (!ok) {
+            uint8_t* q = out + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
+            q[0] = 0;
+            q[ov.sc] = 0;
+            q[2 * ov.sc] = 0;
+            continue;
+        }
+        // a box value that is no int32 becomes -1, which crop_flip_pixel refuses (a zero frame) like any box outside the frame
+        const auto i32 = [](int64_t v) { return v < INT32_MIN || v > INT32_MAX ? -1 : (int)v; };
+        const int top = i32(row[4]), left = i32(row[5]), bh = i32(row[6]), bw = i32(row[7]);
+        const View iv = view_of(fmt, H, W);
+        const uint8_t* base = src + off;
+        if (interp == 1)
+            crop_flip_pixel<4>(base, iv, (int)H, (int)W, top, left, bh, bw, row[8] != 0, n_px, oy, ox, out, ov);
+        else
+            crop_flip_pixel<2>(base, iv, (int)H, (int)W, top, left, bh, bw, row[8] != 0, n_px, oy, ox, out, ov);
+    }
 }
 
 }  // namespace
@@ -143,6 +190,28 @@ int cc_resized_crop_flip_u8(const void* src, int32_t fmt, int32_t F, int32_t H, 
     else
         resized_crop_flip_u8_kernel<4><<<grid, block, 0, st>>>(in, sv, H, W, frames_per_clip, boxes_dev, out, dv, n_px, tiles_x,
                                                                 tiles_y);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+int cc_collate_crop_flip_u8(const void* src, size_t src_bytes, int32_t fmt, const int64_t* clips_host, int32_t n_clips,
+                            const int64_t* rows_dev, int32_t n_out, int32_t n_px, void* dst, int32_t dst_fmt, void* stream) {
+    if (!src || !dst || !rows_dev || !clips_host || n_out <= 0 || n_clips <= 0 || !u8_format(fmt) || !u8_format(dst_fmt))
+        return CC_ERR_INVALID;
+    for (int i = 0; i < n_clips; ++i) {
+        const int64_t off = clips_host[4 * i], t = clips_host[4 * i + 1], H = clips_host[4 * i + 2], W = clips_host[4 * i + 3];
+        if (off < 0 || t < 1 || H < 1 || W < 1 || H > 8192 || W > 8192 || t > (int64_t)1 << 31) return CC_ERR_INVALID;
+        if ((uint64_t)off > src_bytes || (uint64_t)(t * H * W * 3) > src_bytes - (uint64_t)off) return CC_ERR_INVALID;
+        if (H < 4 || W < 4) return CC_ERR_UNSUPPORTED;
+    }
+    if (n_px < 1 || n_px > 1024) return CC_ERR_UNSUPPORTED;
+    const int tiles_x = (n_px + kTileX - 1) / kTileX, tiles_y = (n_px + kTileY - 1) / kTileY;
+    int64_t planes = 0x7fffffffLL / ((int64_t)tiles_x * tiles_y * kTileX * kTileY);
+    if (planes > CC_COLLATE_MAX_PLANES) planes = CC_COLLATE_MAX_PLANES;
+    if (planes > n_out) planes = n_out;
+    collate_crop_flip_u8_kernel<<<dim3(tiles_x, tiles_y, (unsigned)planes), dim3(kTileX, kTileY), 0,
+                                  static_cast<hipStream_t>(stream)>>>(static_cast<const uint8_t*>(src), (int64_t)src_bytes, fmt,
+                                                                      rows_dev, n_out, static_cast<uint8_t*>(dst), dst_fmt, n_px);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }

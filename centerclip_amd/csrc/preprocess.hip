@@ -10,6 +10,8 @@
 // keeps its size is not launched, and with neither the crop is a strided copy.  Only the window is computed: its n_px
 // columns, and of the source rows only those the window's vertical taps read.  Every source sample is loaded as a single byte
 // - a frame base and a row of 3 W bytes carry no alignment.
+// A ragged batch (clips of mixed sizes and lengths packed back to back, cc_collate_resize_crop_u8): the same two passes as at
+// most two launches for the whole batch, one table row per output frame; the per-pixel arithmetic is the same device function.
 #include <math.h>
 
 #include <vector>
@@ -19,7 +21,7 @@
 namespace {
 
 constexpr int kPrecisionBits = 22;
-constexpr int kMaxKsize = 65;                       // taps per output sample the launches take: a shrink factor of 16
+constexpr int kMaxKsize = CC_RESIZE_MAX_TAPS;                     // taps per output sample the launches take: a shrink factor of 16
 constexpr int32_t kMagic = 0x31504352;              // "RCP1"
 
 struct Geometry {
@@ -131,7 +133,7 @@ struct View {
     int64_t sf, sc, sy, sx;
 };
 
-View view_of(int fmt, int64_t rows, int64_t cols) {
+__host__ __device__ inline View view_of(int fmt, int64_t rows, int64_t cols) {
     if (fmt == CC_FRAMES_U8_CHW) return View{3 * rows * cols, rows * cols, cols, 1};
     return View{3 * rows * cols, 1, 3 * cols, 3};
 }
@@ -158,16 +160,12 @@ constexpr int kTileX = 64, kTileY = 4;
 // vertical: out(f, c, oy, ox) = sum_k in(f, c, first[oy] + k, ox) coef[oy][k] (the coefficients are then uniform over a wave).
 // in_off: byte offset of the origin the row / column indices count from (the vertical pass reads the workspace, whose row 0 is
 // source row row0, or - no horizontal pass - the source itself from column `left`).
+// resample_pixel is that thread's work, the one statement of the arithmetic: the per-size kernel below and the ragged-batch
+// kernel behind it both call it.
 template <bool VERT>
-__global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8_t* __restrict__ in, View iv, int64_t in_off,
-                                                                       int row_base, const int32_t* __restrict__ plan,
-                                                                       PlanKey key, uint8_t* __restrict__ out, View ov,
-                                                                       int out_rows, int tiles_x, int tiles_y) {
-    if (!plan_matches(plan, key)) return;
-    const int n_px = key.n_px;
-    const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
-    const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
-    if (ox >= n_px || oy >= out_rows) return;
+__device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ in, const View& iv, int64_t in_off, int row_base,
+                                               const int32_t* __restrict__ plan, int n_px, int f, int oy, int ox,
+                                               uint8_t* __restrict__ out, const View& ov) {
     const int ksize = plan[VERT ? 12 : 11];
     const int32_t* tab = plan + plan[VERT ? 14 : 13];
     const int j = VERT ? oy : ox;
@@ -191,17 +189,147 @@ __global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8
 }
 
 // neither axis is resampled: out(f, c, oy, ox) = in(f, c, top + oy, left + ox)
+__device__ __forceinline__ void crop_pixel(const uint8_t* __restrict__ in, const View& iv, int top, int left, int f, int oy,
+                                           int ox, uint8_t* __restrict__ out, const View& ov) {
+    const uint8_t* p = in + (int64_t)f * iv.sf + (int64_t)(top + oy) * iv.sy + (int64_t)(left + ox) * iv.sx;
+    uint8_t* q = out + (int64_t)f * ov.sf + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
+    q[0] = p[0];
+    q[ov.sc] = p[iv.sc];
+    q[2 * ov.sc] = p[2 * iv.sc];
+}
+
+template <bool VERT>
+__global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8_t* __restrict__ in, View iv, int64_t in_off,
+                                                                       int row_base, const int32_t* __restrict__ plan,
+                                                                       PlanKey key, uint8_t* __restrict__ out, View ov,
+                                                                       int out_rows, int tiles_x, int tiles_y) {
+    if (!plan_matches(plan, key)) return;
+    const int n_px = key.n_px;
+    const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
+    const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
+    if (ox >= n_px || oy >= out_rows) return;
+    resample_pixel<VERT>(in, iv, in_off, row_base, plan, n_px, f, oy, ox, out, ov);
+}
+
 __global__ __launch_bounds__(kTileX* kTileY) void crop_u8_kernel(const uint8_t* __restrict__ in, View iv, int top, int left,
                                                                    uint8_t* __restrict__ out, View ov, int n_px, int tiles_x,
                                                                    int tiles_y) {
     const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
     const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
     if (ox >= n_px || oy >= n_px) return;
-    const uint8_t* p = in + (int64_t)f * iv.sf + (int64_t)(top + oy) * iv.sy + (int64_t)(left + ox) * iv.sx;
-    uint8_t* q = out + (int64_t)f * ov.sf + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
-    q[0] = p[0];
-    q[ov.sc] = p[iv.sc];
-    q[2 * ov.sc] = p[2 * iv.sc];
+    crop_pixel(in, iv, top, left, f, oy, ox, out, ov);
+}
+
+// ---- a ragged batch: clips of mixed sizes and lengths packed back to back, one table row per OUTPUT frame ----------------
+// (cc_collate_resize_crop_u8 in the header).  blockIdx.z runs over output frames, folded where there are more frames than
+// planes; every workgroup reads its frame's row first - the same address in every lane, so plain loads.  The grid covers the
+// largest frame of the call; a tile beyond its own frame's extent exits.  The host never reads the table, so nothing in a row
+// becomes an address before it is checked against the sizes the host passed: a row that fails comes out as a zero frame.
+struct CollateArgs {
+    const uint8_t* src;
+    int64_t src_bytes;
+    const int64_t* rows;
+    const int32_t* plans;
+    int64_t plans_ints;
+    uint8_t* ws;
+    int64_t ws_bytes;
+    uint8_t* dst;
+    int32_t n_out, n_px, resize, fmt, dst_fmt;
+};
+
+struct CollateFrame {
+    const uint8_t* src;                             // the frame's first byte
+    const int32_t* plan;
+    uint8_t* mid;                                   // both passes: the horizontal result [3, nrows, n_px]
+    int H, W, top, left, row0, nrows, ksize_h, ksize_v;
+};
+
+// -> whether output frame f is a transform whose row holds up; false: a zero frame
+__device__ __forceinline__ bool collate_frame(const CollateArgs& a, int f, CollateFrame* c) {
+    const int64_t* row = a.rows + (int64_t)f * CC_COLLATE_ROW;
+    const int64_t kind = row[0], off = row[1], H = row[2], W = row[3], plan_off = row[4], ws_off = row[5];
+    if (kind != 1 || H < 4 || W < 4 || H > 8192 || W > 8192) return false;
+    if (off < 0 || off > a.src_bytes || 3 * H * W > a.src_bytes - off) return false;
+    if (plan_off < 0 || plan_off > a.plans_ints - CC_RESIZE_PLAN_HEADER) return false;
+    const int32_t* plan = a.plans + plan_off;
+    if (!plan_matches(plan, PlanKey{(int32_t)H, (int32_t)W, a.n_px, a.resize})) return false;
+    if (plan[15] < CC_RESIZE_PLAN_HEADER || plan[15] > a.plans_ints - plan_off) return false;
+    c->src = a.src + off;
+    c->plan = plan;
+    c->H = (int)H;
+    c->W = (int)W;
+    c->top = plan[7];
+    c->left = plan[8];
+    c->row0 = plan[9];
+    c->nrows = plan[10] - plan[9];
+    c->ksize_h = plan[11];
+    c->ksize_v = plan[12];
+    c->mid = nullptr;
+    if (c->ksize_h && c->ksize_v) {
+        const int64_t need = (int64_t)3 * c->nrows * a.n_px;
+        if (!a.ws || c->nrows < 1 || ws_off < 0 || ws_off > a.ws_bytes || need > a.ws_bytes - ws_off) return false;
+        c->mid = a.ws + ws_off;
+    }
+    return true;
+}
+
+// FINAL = false: the horizontal pass of the frames that run both passes, into the workspace; nothing else is touched.
+// FINAL = true: every output frame is written - zeros, the crop alone, the one pass its size needs, or the vertical pass over
+// the workspace.
+template <bool FINAL>
+__global__ __launch_bounds__(kTileX* kTileY) void collate_resample_u8_kernel(CollateArgs a) {
+    const int ox = blockIdx.x * kTileX + threadIdx.x, oy = blockIdx.y * kTileY + threadIdx.y;
+    if (ox >= a.n_px) return;
+    const View dv = view_of(a.dst_fmt, a.n_px, a.n_px);
+    for (int f = blockIdx.z; f < a.n_out; f += gridDim.z) {
+        CollateFrame c;
+        const bool ok = collate_frame(a, f, &c);
+        if (!FINAL) {
+            if (!ok || !c.mid || oy >= c.nrows) continue;
+            resample_pixel<false>(c.src, view_of(a.fmt, c.H, c.W), 0, c.row0, c.plan, a.n_px, 0, oy, ox, c.mid,
+                                  view_of(CC_FRAMES_U8_CHW, c.nrows, a.n_px));
+            continue;
+        }
+        if (oy >= a.n_px) return;
+        uint8_t* out = a.dst + (int64_t)f * dv.sf;
+        if (!ok) {
+            uint8_t* q = out + (int64_t)oy * dv.sy + (int64_t)ox * dv.sx;
+            q[0] = 0;
+            q[dv.sc] = 0;
+            q[2 * dv.sc] = 0;
+            continue;
+        }
+        const View sv = view_of(a.fmt, c.H, c.W);
+        if (c.mid) {
+            const View mv = view_of(CC_FRAMES_U8_CHW, c.nrows, a.n_px);
+            resample_pixel<true>(c.mid, mv, -(int64_t)c.row0 * mv.sy, 0, c.plan, a.n_px, 0, oy, ox, out, dv);
+        } else if (c.ksize_h) {
+            resample_pixel<false>(c.src, sv, 0, c.top, c.plan, a.n_px, 0, oy, ox, out, dv);
+        } else if (c.ksize_v) {
+            resample_pixel<true>(c.src, sv, (int64_t)c.left * sv.sx, 0, c.plan, a.n_px, 0, oy, ox, out, dv);
+        } else {
+            crop_pixel(c.src, sv, c.top, c.left, 0, oy, ox, out, dv);
+        }
+    }
+}
+
+// planes of blockIdx.z a launch of tiles_x x tiles_y workgroups per plane uses for n_out frames (the rest is folded)
+int collate_planes(int n_out, int tiles_x, int tiles_y) {
+    int64_t z = 0x7fffffffLL / ((int64_t)tiles_x * tiles_y * kTileX * kTileY);
+    if (z > CC_COLLATE_MAX_PLANES) z = CC_COLLATE_MAX_PLANES;
+    if (z > n_out) z = n_out;
+    return z < 1 ? 1 : (int)z;
+}
+
+// the host's checks of a clip table [n_clips, 4] rows (byte offset, frames, H, W) against the packed buffer's size
+int collate_check_clips(const int64_t* clips, int n_clips, size_t src_bytes) {
+    if (!clips || n_clips <= 0) return CC_ERR_INVALID;
+    for (int i = 0; i < n_clips; ++i) {
+        const int64_t off = clips[4 * i], t = clips[4 * i + 1], H = clips[4 * i + 2], W = clips[4 * i + 3];
+        if (off < 0 || t < 1 || H < 1 || W < 1 || H > 8192 || W > 8192 || t > (int64_t)1 << 31) return CC_ERR_INVALID;
+        if ((uint64_t)off > src_bytes || (uint64_t)(t * H * W * 3) > src_bytes - (uint64_t)off) return CC_ERR_INVALID;
+    }
+    return CC_OK;
 }
 
 bool u8_format(int fmt) { return fmt == CC_FRAMES_U8_CHW || fmt == CC_FRAMES_U8_HWC; }
@@ -297,6 +425,65 @@ int cc_resize_crop_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_
     CC_LAUNCH_CHECK();
     resample_u8_kernel<true><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(mid, mv, -(int64_t)g.row0 * mv.sy, 0, plan,
                                                                                      key, out, dv, n_px, tiles_x, tiles_out);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+int cc_resize_crop_status(int32_t H, int32_t W, int32_t n_px, int32_t resize) {
+    Geometry g;
+    return geometry(H, W, n_px, resize, kMaxKsize, &g);
+}
+
+size_t cc_collate_resize_crop_workspace_bytes(const int64_t* clips_host, int32_t n_clips, int32_t n_out, int32_t n_px,
+                                              int32_t resize) {
+    if (!clips_host || n_clips <= 0 || n_out <= 0) return 0;
+    size_t frame = 0;
+    for (int i = 0; i < n_clips; ++i) {
+        const size_t one = cc_resize_crop_workspace_bytes(1, (int32_t)clips_host[4 * i + 2], (int32_t)clips_host[4 * i + 3], n_px, resize);
+        if (one > frame) frame = one;
+    }
+    return frame * (size_t)n_out;
+}
+
+int cc_collate_resize_crop_u8(const void* src, size_t src_bytes, int32_t fmt, const int64_t* clips_host, int32_t n_clips,
+                              const int64_t* rows_dev, int32_t n_out, const int32_t* plans_dev, size_t plans_ints, int32_t n_px,
+                              int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
+    if (!src || !dst || !rows_dev || !plans_dev || n_out <= 0 || !u8_format(fmt) || !u8_format(dst_fmt) ||
+        plans_ints < CC_RESIZE_PLAN_HEADER)
+        return CC_ERR_INVALID;
+    int rc = collate_check_clips(clips_host, n_clips, src_bytes);
+    if (rc != CC_OK) return rc;
+    int max_mid = 0;                                // rows of the largest horizontal result; 0: no clip runs both passes
+    for (int i = 0; i < n_clips; ++i) {
+        Geometry g;
+        rc = geometry((int)clips_host[4 * i + 2], (int)clips_host[4 * i + 3], n_px, resize, kMaxKsize, &g);
+        if (rc != CC_OK) return rc;
+        if (g.ksize_h && g.ksize_v && g.row1 - g.row0 > max_mid) max_mid = g.row1 - g.row0;
+    }
+    if (max_mid && (!ws || ws_bytes < (size_t)3 * max_mid * n_px)) return CC_ERR_WORKSPACE;
+    CollateArgs a;
+    a.src = static_cast<const uint8_t*>(src);
+    a.src_bytes = (int64_t)src_bytes;
+    a.rows = rows_dev;
+    a.plans = plans_dev;
+    a.plans_ints = (int64_t)plans_ints;
+    a.ws = static_cast<uint8_t*>(ws);
+    a.ws_bytes = ws ? (int64_t)ws_bytes : 0;
+    a.dst = static_cast<uint8_t*>(dst);
+    a.n_out = n_out;
+    a.n_px = n_px;
+    a.resize = resize;
+    a.fmt = fmt;
+    a.dst_fmt = dst_fmt;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 block(kTileX, kTileY);
+    const int tiles_x = (n_px + kTileX - 1) / kTileX, tiles_out = (n_px + kTileY - 1) / kTileY;
+    if (max_mid) {
+        const int tiles_mid = (max_mid + kTileY - 1) / kTileY;
+        collate_resample_u8_kernel<false><<<dim3(tiles_x, tiles_mid, collate_planes(n_out, tiles_x, tiles_mid)), block, 0, st>>>(a);
+        CC_LAUNCH_CHECK();
+    }
+    collate_resample_u8_kernel<true><<<dim3(tiles_x, tiles_out, collate_planes(n_out, tiles_x, tiles_out)), block, 0, st>>>(a);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }

@@ -16,8 +16,23 @@ PyTorch streams / events / ``Tensor.copy_(non_blocking=True)`` only: plumbing, n
 video, the resize + centre crop runs on the copy stream right behind the slot's copy, into a second buffer of the slot, and that
 buffer is yielded in the raw video's place - the consumer sees model-resolution frames at addresses that never change.
 ``video_index``: the video's position in the loader's tuple (default: its only 4-D / 6-D uint8 tensor).
+
+A ragged batch (``preprocess.PackedClips`` in the video's place, ``frame_transform=preprocess.ClipCollate(...)``): the slot's
+raw buffer is a byte buffer that grows geometrically and never shrinks - batches differ in their total bytes - filled by one
+copy; the collate runs on the copy stream into the slot's fixed [B, 1, T, ...] cooked buffer, whose address never changes: that
+is the address consumers and captured graphs see.  A batch of another B (or layout) gets new buffers, as a tensor batch of
+another shape does.
 """
 import torch
+
+from .preprocess import PackedClips
+
+
+def _fits(d, h):
+    """whether slot entry d can take host entry h as it is"""
+    if isinstance(h, PackedClips):
+        return isinstance(d, PackedClips) and len(d) == len(h) and d.chw == h.chw
+    return isinstance(d, torch.Tensor) and tuple(d.shape) == tuple(h.shape) and d.dtype == h.dtype
 
 
 class DeviceFeeder:
@@ -29,21 +44,26 @@ class DeviceFeeder:
         self.depth = depth
         self.copy_stream = torch.cuda.Stream(self.device)
         self.slots = [None] * depth
+        self.raw = [None] * depth                                    # per slot: the byte buffer of a PackedClips entry
         self.ready = [torch.cuda.Event() for _ in range(depth)]      # slot filled
         self.free = [torch.cuda.Event() for _ in range(depth)]       # slot no longer read by the compute stream
         self._used = [False] * depth
 
     def _fill(self, k, host_batch):
         host_batch = tuple(host_batch)
-        if self.slots[k] is None or any(tuple(d.shape) != tuple(h.shape) or d.dtype != h.dtype
-                                        for d, h in zip(self.slots[k], host_batch)):
-            self.slots[k] = tuple(torch.empty(h.shape, dtype=h.dtype, device=self.device) for h in host_batch)
+        if self.slots[k] is None or len(self.slots[k]) != len(host_batch) or not all(map(_fits, self.slots[k], host_batch)):
+            # (a PackedClips entry: the table only - its bytes are pointed at the slot's byte buffer below, per batch)
+            self.slots[k] = tuple(PackedClips(None, h.table, h.chw) if isinstance(h, PackedClips)
+                                  else torch.empty(h.shape, dtype=h.dtype, device=self.device) for h in host_batch)
             self.cooked[k] = None
             if self.frame_transform is not None:
-                vi = self._video_index(host_batch)
-                if not self.frame_transform.passes_through(host_batch[vi].shape):
-                    self.cooked[k] = torch.empty(self.frame_transform.output_shape(host_batch[vi].shape), dtype=torch.uint8,
-                                                 device=self.device)
+                video = host_batch[self._video_index(host_batch)]
+                packed = isinstance(video, PackedClips)
+                if not self.frame_transform.passes_through(video if packed else video.shape):
+                    self.cooked[k] = torch.empty(self.frame_transform.output_shape(video if packed else video.shape),
+                                                 dtype=torch.uint8, device=self.device)
+            if any(isinstance(h, PackedClips) for h in host_batch) and self.cooked[k] is None:
+                raise ValueError("DeviceFeeder: a PackedClips batch needs frame_transform=preprocess.ClipCollate(...)")
         with torch.cuda.stream(self.copy_stream):
             if self._used[k]:
                 self.copy_stream.wait_event(self.free[k])
@@ -52,7 +72,16 @@ class DeviceFeeder:
                 # stream's last kernels on it still queued: the first copy into it waits for what is enqueued there
                 self.copy_stream.wait_stream(torch.cuda.current_stream(self.device))
             for d, h in zip(self.slots[k], host_batch):
-                d.copy_(h, non_blocking=True)                        # asynchronous only from pinned memory
+                if isinstance(h, PackedClips):
+                    # the byte buffer is allocated and only ever used on the copy stream (the consumer sees the cooked buffer)
+                    n = h.data.numel()
+                    if self.raw[k] is None or self.raw[k].numel() < n:
+                        self.raw[k] = torch.empty(max(n, 2 * self.raw[k].numel() if self.raw[k] is not None else 0),
+                                                  dtype=torch.uint8, device=self.device)
+                    d.data, d.table = self.raw[k][:n], h.table
+                    d.data.copy_(h.data, non_blocking=True)
+                else:
+                    d.copy_(h, non_blocking=True)                    # asynchronous only from pinned memory
             if self.cooked[k] is not None:
                 self.frame_transform(self.slots[k][self._video_index(host_batch)], out=self.cooked[k])
             self.ready[k].record(self.copy_stream)
@@ -60,7 +89,7 @@ class DeviceFeeder:
     def _video_index(self, batch):
         if self.video_index is not None:
             return self.video_index
-        found = [i for i, t in enumerate(batch) if t.dtype == torch.uint8 and t.dim() in (4, 6)]
+        found = [i for i, t in enumerate(batch) if isinstance(t, PackedClips) or (t.dtype == torch.uint8 and t.dim() in (4, 6))]
         if len(found) != 1:
             raise ValueError("DeviceFeeder(frame_transform=...): the batch has %d uint8 frame tensors - pass video_index"
                              % len(found))

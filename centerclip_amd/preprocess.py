@@ -11,10 +11,19 @@ dataset code lives here.  HIP only: a CPU tensor raises, as everywhere in the pa
 
 ``TrainFrameTransform`` is the training loader's counterpart (dataloaders/decode.py:32-41): a multi-scale or random-resized
 crop and a horizontal flip per clip, the boxes drawn on the host, one launch on the clip's uint8 frames.
+
+Both take one uniform tensor.  What a decoder produces is ragged - clips of mixed H x W and mixed lengths - and goes through
+``pack_clips`` (one byte buffer + a host table, usable as a DataLoader ``collate_fn``) and ``ClipCollate`` (either transform
+on every clip of the batch, zero padding included, in at most two launches):
+
+    packed = pack_clips([clip_0, clip_1, ...])                           # uint8 [t_i, H_i, W_i, 3] each, t_i <= T
+    video = ClipCollate(224, max_frames=12)(packed.to(device))           # uint8 [B, 1, T, 224, 224, 3]
+    out = model(ids, seg, mask, video, packed.video_mask(12))
 """
 import math
 import random
 
+import numpy as np
 import torch
 
 from . import _lib as L
@@ -210,4 +219,255 @@ class TrainFrameTransform:
         return self.apply(frames, self.sample(self._clips(frames.shape)[0], H, W), out=out)
 
 
-__all__ = ["resize_center_crop", "FrameTransform", "TrainFrameTransform"]
+
+# ------------------------------------------------------------------------------------------ ragged clip batches
+class PackedClips:
+    """A ragged batch of decoded clips: ``data`` - the clips' bytes back to back in one 1-D uint8 tensor, no alignment padding
+    (odd sizes give odd offsets; the kernels read single bytes) - and ``table`` - HOST int64 [B, 4] rows (byte offset, frames
+    t, H, W).  ``chw``: every clip is [t, 3, H, W] instead of [t, H, W, 3].  Built by ``pack_clips``."""
+
+    def __init__(self, data, table, chw):
+        self.data, self.table, self.chw = data, table, bool(chw)
+
+    def __len__(self):
+        return int(self.table.shape[0])
+
+    @property
+    def device(self):
+        return self.data.device
+
+    @property
+    def is_cuda(self):
+        return self.data.is_cuda
+
+    def to(self, device=None, non_blocking=False, **_):
+        """ONE host-to-device copy of the bytes (asynchronous from the pinned buffer with non_blocking=True); the table stays
+        on the host."""
+        return PackedClips(self.data.to(device=device, non_blocking=non_blocking), self.table, self.chw)
+
+    def pin_memory(self):
+        return self if self.data.is_pinned() else PackedClips(self.data.pin_memory(), self.table, self.chw)
+
+    def clip(self, b):
+        """Clip b as a view of the bytes: [t, H, W, 3] or [t, 3, H, W]."""
+        off, t, H, W = (int(v) for v in self.table[b])
+        return self.data[off:off + t * H * W * 3].view((t, 3, H, W) if self.chw else (t, H, W, 3))
+
+    def __getitem__(self, rows):
+        """The clips ``rows`` (an index tensor or list) as a new PackedClips - a copy of their bytes (eval_epoch uses it for a
+        DistributedSampler's padded tail only)."""
+        return pack_clips([self.clip(int(b)) for b in torch.as_tensor(rows).reshape(-1).tolist()], "chw" if self.chw else "hwc")
+
+    def video_mask(self, T, lengths=None):
+        """-> int64 [B, T], ones in the first min(t_b, T) slots of clip b - or in the first lengths[b] slots, e.g. the
+        reference's min(num_frames, T) for a clip sampled down to T frames (sampling.py).  Host work only."""
+        n = self.table[:, 1].clamp(max=int(T)) if lengths is None else torch.as_tensor(lengths, dtype=torch.int64).reshape(-1)
+        if n.numel() != len(self) or bool((n < 0).any()) or bool((n > int(T)).any()):
+            raise ValueError("video_mask: lengths must be %d values in [0, %d], got %s" % (len(self), T, n.tolist()))
+        return (torch.arange(int(T)).unsqueeze(0) < n.unsqueeze(1)).to(torch.int64)
+
+
+def pack_clips(clips, layout=None):
+    """A list of B uint8 arrays / tensors [t_i, H_i, W_i, 3] or [t_i, 3, H_i, W_i] (t_i >= 1; one layout per batch: "hwc",
+    "chw" or None = what the shapes say) -> ``PackedClips``.  Host clips are copied once into one pinned buffer (plain host
+    memory where no device is present and inside a DataLoader worker process), so ``.to(device)`` is one asynchronous copy;
+    usable as, or inside, a DataLoader ``collate_fn``.  Device tensors are accepted too and packed with ONE ``torch.cat`` of their flat views: a device-to-device
+    copy of every byte (and the non-contiguous ones once more) - decode into host memory where that matters."""
+    clips = [torch.from_numpy(np.ascontiguousarray(c)) if isinstance(c, np.ndarray) else c for c in clips]
+    if not clips:
+        raise ValueError("pack_clips: no clips")
+    if layout not in (None, "hwc", "chw"):
+        raise ValueError("pack_clips: layout must be 'hwc', 'chw' or None, got %r" % (layout,))
+    for i, c in enumerate(clips):
+        if not isinstance(c, torch.Tensor) or c.dtype != torch.uint8 or c.dim() != 4:
+            raise ValueError("pack_clips: clip %d is not a 4-D uint8 array or tensor" % i)
+    # the one layout every clip reads as; [t, 3, H, W] wins where both do, as everywhere in the package
+    reads = {"chw": all(c.shape[1] == 3 for c in clips), "hwc": all(c.shape[3] == 3 for c in clips)}
+    if not reads["chw" if layout is None and reads["chw"] else (layout or "hwc")]:
+        raise ValueError("pack_clips: one layout per batch - the clips %s are not all %s"
+                         % ([tuple(c.shape) for c in clips], {"chw": "[t, 3, H, W]", "hwc": "[t, H, W, 3]",
+                                                              None: "[t, H, W, 3] nor all [t, 3, H, W]"}[layout]))
+    chw = reads["chw"] if layout is None else layout == "chw"
+    rows, off = [], 0
+    for i, c in enumerate(clips):
+        t, H, W = (int(c.shape[0]), int(c.shape[2]), int(c.shape[3])) if chw else (int(c.shape[0]), int(c.shape[1]), int(c.shape[2]))
+        if t < 1 or H < 1 or W < 1:
+            raise ValueError("pack_clips: clip %d is empty: %s" % (i, tuple(c.shape)))
+        rows.append((off, t, H, W))
+        off += t * H * W * 3
+    table = torch.tensor(rows, dtype=torch.int64)
+    if any(c.is_cuda for c in clips):
+        if not all(c.is_cuda for c in clips):
+            raise ValueError("pack_clips: host and device clips in one batch")
+        return PackedClips(torch.cat([c.contiguous().view(-1) for c in clips]), table, chw)
+    # (a DataLoader worker process must not touch the device: it packs into plain memory, and DataLoader(pin_memory=True)
+    #  pins the batch through PackedClips.pin_memory in the main process)
+    pin = torch.cuda.is_available() and torch.utils.data.get_worker_info() is None
+    data = torch.empty(off, dtype=torch.uint8, pin_memory=pin)
+    for (o, t, H, W), c in zip(rows, clips):
+        data[o:o + t * H * W * 3].view(c.shape).copy_(c)
+    return PackedClips(data, table, chw)
+
+
+class ClipCollate:
+    """A ``PackedClips`` on the device -> the loaders' uniform video, uint8 [B, 1, T, n_px, n_px, 3] ([B, 1, T, 3, n_px, n_px]
+    for a channels-first batch), T = max_frames: per clip the evaluation transform (``train=None``: Resize(n_px, BICUBIC) +
+    CenterCrop(n_px), the crop alone with resize=False - byte for byte ``resize_center_crop`` of that clip) or the training
+    transform (``train=TrainFrameTransform(...)``: one box and one flip per clip, drawn by that object for the clips in batch
+    order, each with exactly the calls of ``train.sample(1, H_b, W_b)``, applied to all T slots - byte for byte
+    ``resized_crop_flip`` of that clip), in at most two launches whatever the batch holds (torch.ops.centerclip.collate_clips /
+    collate_clips_crop_flip).  A ``frame_transform`` for eval_epoch, train_epoch and DeviceFeeder.
+
+    ``index``: host ints [B, T]; slot s of clip b is frame index[b, s] of that clip, -1 a zero frame; repeats and any order
+    are allowed.  Default: frame s for s < t_b and zero frames behind (the CV2 loaders' padding); a clip longer than T must be
+    sampled by the caller (sampling.py).  Zero frames are written by the launch: a reused ``out`` never shows a stale frame.
+
+    Everything is checked on the host before anything is launched - ValueError for an index outside [-1, t_b), a clip longer
+    than T without an index, a size the per-clip op refuses (a frame smaller than the crop, more than 65 taps per axis; the
+    error names the clip).  The resize plans are built once per (H, W) and kept on the host; a call's tables (frame rows + the
+    plans of its sizes) go to the device in ONE small copy from pinned memory - which cannot be captured: inside a stream
+    capture the call raises CenterClipHipError.  No host synchronisation anywhere."""
+
+    def __init__(self, n_px=224, max_frames=12, resize=True, train=None):
+        self.n_px, self.max_frames, self.resize, self.train = int(n_px), int(max_frames), bool(resize), train
+        if train is not None and train.n_px != self.n_px:
+            raise ValueError("ClipCollate(n_px=%d) with a TrainFrameTransform(n_px=%d)" % (self.n_px, train.n_px))
+        self._plans = {}                                         # (H, W) -> the host plan, int32
+
+    def passes_through(self, packed):
+        return False
+
+    def output_shape(self, packed):
+        n = self.n_px
+        return (len(packed), 1, self.max_frames) + ((3, n, n) if packed.chw else (n, n, 3))
+
+    def plan(self, H, W, clip=None):
+        """The host plan (cc_resize_plan_build) of a frame size, built once; ValueError for a size resize_center_crop refuses."""
+        key = (int(H), int(W))
+        if key not in self._plans:
+            lib = L.lib()
+            if lib.cc_resize_crop_status(key[0], key[1], self.n_px, int(self.resize)) != L.CC_OK:
+                raise ValueError("ClipCollate: %s %d x %d frames are outside what resize_center_crop(n_px=%d, resize=%s) takes (a "
+                                 "frame smaller than the crop, or more than 65 taps per axis)"
+                                 % ("clip %d:" % clip if clip is not None else "", key[0], key[1], self.n_px, self.resize))
+            host = np.empty(lib.cc_resize_plan_bytes(key[0], key[1], self.n_px, int(self.resize)) // 4, dtype=np.int32)
+            L.check(lib.cc_resize_plan_build(key[0], key[1], self.n_px, int(self.resize), host.ctypes.data), "cc_resize_plan_build")
+            self._plans[key] = host
+        return self._plans[key]
+
+    def index(self, packed, index=None):
+        """The validated frame index, int64 [B, T] NumPy (the default where index is None)."""
+        B, T, t = len(packed), self.max_frames, packed.table[:, 1].numpy()
+        if index is None:
+            if (t > T).any():
+                raise ValueError("ClipCollate: clip %d has %d frames for %d slots - sample it (sampling.uniform_sampling) and pass "
+                                 "the index, or pack the sampled frames only" % (int((t > T).argmax()), int(t.max()), T))
+            s = np.arange(T, dtype=np.int64)[None, :]
+            return np.where(s < t[:, None], s, -1)
+        index = np.asarray(index.cpu() if isinstance(index, torch.Tensor) else index)
+        if index.shape != (B, T) or index.dtype.kind not in "iu":
+            raise ValueError("ClipCollate: index must be integers [%d, %d], got %s %s" % (B, T, index.dtype, index.shape))
+        index = index.astype(np.int64)
+        bad = (index < -1) | (index >= t[:, None])
+        if bad.any():
+            b, s = (int(v[0]) for v in np.nonzero(bad))
+            raise ValueError("ClipCollate: index[%d, %d] = %d, clip %d has frames 0 .. %d (-1: a zero frame)"
+                             % (b, s, index[b, s], b, t[b] - 1))
+        return index
+
+    def _rows(self, packed, index, width):
+        """The first four columns of the frame table: kind, byte offset of the source frame, H, W."""
+        tab = packed.table.numpy()
+        rows = np.zeros((index.shape[0], index.shape[1], width), dtype=np.int64)
+        frame = tab[:, 2] * tab[:, 3] * 3
+        rows[:, :, 0] = index >= 0
+        rows[:, :, 1] = tab[:, :1] + np.maximum(index, 0) * frame[:, None]
+        rows[:, :, 2] = tab[:, 2:3]
+        rows[:, :, 3] = tab[:, 3:4]
+        return rows
+
+    def _upload(self, host, device):
+        if torch.cuda.is_current_stream_capturing():
+            raise L.CenterClipHipError("ClipCollate: a call's tables are uploaded, which cannot be part of a stream capture")
+        return torch.from_numpy(host).pin_memory().to(device, non_blocking=True)
+
+    def _check(self, packed, out):
+        if not isinstance(packed, PackedClips):
+            raise ValueError("ClipCollate takes a PackedClips (pack_clips), got %s" % type(packed).__name__)
+        L.require_device(packed.data)
+        if out is not None and tuple(out.shape) != self.output_shape(packed):
+            raise ValueError("ClipCollate: out must be %s, got %s" % (self.output_shape(packed), tuple(out.shape)))
+
+    def _eval(self, packed, index, out):
+        self._check(packed, out)
+        index = self.index(packed, index)
+        tab = packed.table.numpy()
+        offsets, parts, at = {}, [], 0                           # the call's plans one behind the other: (H, W) -> int32 offset
+        for b, (H, W) in enumerate(zip(tab[:, 2].tolist(), tab[:, 3].tolist())):
+            if (H, W) not in offsets:
+                plan = self.plan(H, W, clip=b)
+                offsets[(H, W)] = at
+                parts.append(plan)
+                at += plan.size
+        B, S = index.shape
+        rows = self._rows(packed, index, T.COLLATE_ROW)
+        rows[:, :, 4] = np.array([offsets[(H, W)] for H, W in zip(tab[:, 2].tolist(), tab[:, 3].tolist())], dtype=np.int64)[:, None]
+        clips = tab.reshape(-1).tolist()
+        nws = L.lib().cc_collate_resize_crop_workspace_bytes(T._clips_host(clips), B, B * S, self.n_px, int(self.resize))
+        rows[:, :, 5] = np.arange(B * S, dtype=np.int64).reshape(B, S) * (nws // (B * S))
+        head = rows.reshape(-1)
+        host = np.zeros(head.size + (at + 1) // 2, dtype=np.int64)
+        host[:head.size] = head
+        host[head.size:].view(np.int32)[:at] = np.concatenate(parts)
+        dev = self._upload(host, packed.device)
+        rows_dev, plans_dev = dev[:head.size].view(B * S, T.COLLATE_ROW), dev[head.size:].view(torch.int32)
+        if out is None:
+            return torch.ops.centerclip.collate_clips(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
+                                                      packed.chw).view(self.output_shape(packed))
+        torch.ops.centerclip.collate_clips_out(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize, packed.chw, out)
+        return out
+
+    def sample(self, packed):
+        """-> int32 [B, 5] on the host, rows (top, left, height, width, flip): for the clips in batch order, each the draws of
+        ``train.sample(1, H_b, W_b)``."""
+        if self.train is None:
+            raise ValueError("ClipCollate.sample: no TrainFrameTransform was given (train=None is the evaluation transform)")
+        return torch.cat([self.train.sample(1, int(H), int(W)) for _, _, H, W in packed.table.tolist()], 0)
+
+    def apply(self, packed, boxes, index=None, out=None):
+        """The training transform on given boxes (host ints [B, 5] as ``sample`` gives them): deterministic."""
+        if self.train is None:
+            raise ValueError("ClipCollate.apply: no TrainFrameTransform was given (train=None is the evaluation transform)")
+        self._check(packed, out)
+        index = self.index(packed, index)
+        B, S = index.shape
+        tab = packed.table.numpy()
+        boxes = np.asarray(boxes.cpu() if isinstance(boxes, torch.Tensor) else boxes).astype(np.int64)
+        if boxes.shape != (B, 5):
+            raise ValueError("ClipCollate.apply: boxes must be [%d, 5] rows (top, left, height, width, flip), got %s" % (B, boxes.shape))
+        top, left, h, w = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+        bad = (top < 0) | (left < 0) | (h < 1) | (w < 1) | (top + h > tab[:, 2]) | (left + w > tab[:, 3]) | (tab[:, 2] < 4) | (tab[:, 3] < 4)
+        if bad.any():
+            b = int(bad.argmax())
+            raise ValueError("ClipCollate.apply: clip %d: the box (top %d, left %d, %d x %d) does not lie inside its %d x %d frame "
+                             "(at least 4 x 4)" % (b, top[b], left[b], h[b], w[b], tab[b, 2], tab[b, 3]))
+        rows = self._rows(packed, index, T.COLLATE_BOX_ROW)
+        rows[:, :, 4:9] = boxes[:, None, :]
+        rows[:, :, 9] = self.train.interp
+        dev = self._upload(rows.reshape(-1), packed.device).view(B * S, T.COLLATE_BOX_ROW)
+        clips = tab.reshape(-1).tolist()
+        if out is None:
+            return torch.ops.centerclip.collate_clips_crop_flip(packed.data, dev, clips, self.n_px,
+                                                                packed.chw).view(self.output_shape(packed))
+        torch.ops.centerclip.collate_clips_crop_flip_out(packed.data, dev, clips, self.n_px, packed.chw, out)
+        return out
+
+    def __call__(self, packed, index=None, out=None):
+        if self.train is None:
+            return self._eval(packed, index, out)
+        if not isinstance(packed, PackedClips):
+            raise ValueError("ClipCollate takes a PackedClips (pack_clips), got %s" % type(packed).__name__)
+        return self.apply(packed, self.sample(packed), index=index, out=out)
+
+
+__all__ = ["resize_center_crop", "FrameTransform", "TrainFrameTransform", "PackedClips", "pack_clips", "ClipCollate"]

@@ -1066,6 +1066,124 @@ def _(frames, boxes, n_px, frames_per_clip, interp, out):
     return None
 
 
+COLLATE_ROW, COLLATE_BOX_ROW, COLLATE_MAX_PLANES = 6, 10, 4096      # CC_COLLATE_ROW / _BOX_ROW / _MAX_PLANES of the header
+
+
+def _collate_shape(n_out, n_px, chw):
+    return (n_out, 3, n_px, n_px) if chw else (n_out, n_px, n_px, 3)
+
+
+def _collate_check(name, src, rows, clips, n_px, chw, row_ints, out=None):
+    """The checks the real and the fake kernels of the ragged-batch ops share -> n_out."""
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError("%s: the packed clips are one 1-D uint8 buffer, got %s %s" % (name, src.dtype, tuple(src.shape)))
+    if rows.dtype != torch.int64 or rows.dim() != 2 or rows.shape[1] != row_ints or rows.shape[0] < 1:
+        raise ValueError("%s: the frame table is int64 [n_out >= 1, %d], got %s %s" % (name, row_ints, rows.dtype, tuple(rows.shape)))
+    if len(clips) == 0 or len(clips) % 4:
+        raise ValueError("%s: the clip table is B >= 1 rows of (byte offset, frames, H, W), got %d values" % (name, len(clips)))
+    if n_px < 1:
+        raise ValueError("%s: n_px >= 1, got %d" % (name, n_px))
+    n_out = int(rows.shape[0])
+    if out is not None and (out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() < 3
+                            or tuple(out.shape[-3:]) != _collate_shape(n_out, n_px, chw)[1:]
+                            or out.numel() != n_out * 3 * n_px * n_px):
+        raise ValueError("%s: out must be contiguous uint8 frames [..., %s] with %d frames in all, got %s %s"
+                         % (name, ", ".join(map(str, _collate_shape(n_out, n_px, chw)[1:])), n_out, out.dtype, tuple(out.shape)))
+    return n_out
+
+
+def _clips_host(clips):
+    return (ctypes.c_int64 * len(clips))(*clips)
+
+
+def _collate_into(src, rows, plans, clips, n_px, resize, chw, out):
+    n_out = _collate_check("collate_clips", src, rows, clips, n_px, chw, COLLATE_ROW, out)
+    if plans.dtype != torch.int32 or plans.dim() != 1:
+        raise ValueError("collate_clips: the plans are one 1-D int32 buffer, got %s %s" % (plans.dtype, tuple(plans.shape)))
+    L.require_device(src, rows, plans, out)
+    src, rows, plans = src.contiguous(), rows.contiguous(), plans.contiguous()
+    lib, table, fmt = L.lib(), _clips_host(clips), 1 if chw else 2
+    nws = lib.cc_collate_resize_crop_workspace_bytes(table, len(clips) // 4, n_out, int(n_px), int(resize))
+    ws = L.workspace(nws, src.device) if nws else None
+    L.check(lib.cc_collate_resize_crop_u8(L.ptr(src), src.numel(), fmt, table, len(clips) // 4, L.ptr(rows), n_out, L.ptr(plans),
+                                          plans.numel(), int(n_px), int(resize), L.ptr(out), fmt, L.ptr(ws), nws, _st(src)),
+            "cc_collate_resize_crop_u8")
+
+
+@custom_op(NS + "::collate_clips", mutates_args=(), device_types="cuda")
+def collate_clips(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
+                  chw: bool) -> torch.Tensor:
+    """A ragged batch of decoded clips -> uniform frames (cc_collate_resize_crop_u8, at most two launches whatever the batch
+    holds).  src: the packed uint8 bytes; clips: the HOST table, flat rows (byte offset, frames, H, W) - what is checked before
+    any launch; rows: int64 [n_out, 6] on the device, per output frame (kind 0 zero / 1 transform, byte offset, H, W, int32 offset
+    of the size's plan in ``plans``, byte offset of the frame's horizontal result in the workspace = i * the per-frame share of
+    cc_collate_resize_crop_workspace_bytes).  -> uint8 [n_out, n_px, n_px, 3] ([n_out, 3, n_px, n_px] with chw), each frame byte
+    for byte resize_center_crop of its source frame, zero frames zero.  preprocess.ClipCollate builds the tables."""
+    out = _e(*_collate_shape(_collate_check("collate_clips", src, rows, clips, n_px, chw, COLLATE_ROW), n_px, chw), like=src,
+             dtype=torch.uint8)
+    _collate_into(src, rows, plans, clips, n_px, resize, chw, out)
+    return out
+
+
+@collate_clips.register_fake
+def _(src, rows, plans, clips, n_px, resize, chw):
+    n_out = _collate_check("collate_clips", src, rows, clips, n_px, chw, COLLATE_ROW)
+    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::collate_clips_out", mutates_args=("out",), device_types="cuda")
+def collate_clips_out(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
+                      chw: bool, out: torch.Tensor) -> None:
+    """collate_clips into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay); every
+    frame of it is written, the zero frames included."""
+    _collate_into(src, rows, plans, clips, n_px, resize, chw, out)
+
+
+@collate_clips_out.register_fake
+def _(src, rows, plans, clips, n_px, resize, chw, out):
+    _collate_check("collate_clips", src, rows, clips, n_px, chw, COLLATE_ROW, out)
+    return None
+
+
+def _collate_crop_flip_into(src, rows, clips, n_px, chw, out):
+    n_out = _collate_check("collate_clips_crop_flip", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
+    L.require_device(src, rows, out)
+    src, rows = src.contiguous(), rows.contiguous()
+    fmt = 1 if chw else 2
+    L.check(L.lib().cc_collate_crop_flip_u8(L.ptr(src), src.numel(), fmt, _clips_host(clips), len(clips) // 4, L.ptr(rows), n_out,
+                                            int(n_px), L.ptr(out), fmt, _st(src)), "cc_collate_crop_flip_u8")
+
+
+@custom_op(NS + "::collate_clips_crop_flip", mutates_args=(), device_types="cuda")
+def collate_clips_crop_flip(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, chw: bool) -> torch.Tensor:
+    """The training form of collate_clips (cc_collate_crop_flip_u8, one launch): rows int64 [n_out, 10] on the device, per output
+    frame (kind, byte offset, H, W, top, left, height, width, flip, interp 0 bilinear / 1 bicubic); each frame byte for byte
+    resized_crop_flip of its source frame with that box, zero frames zero."""
+    out = _e(*_collate_shape(_collate_check("collate_clips_crop_flip", src, rows, clips, n_px, chw, COLLATE_BOX_ROW), n_px, chw),
+             like=src, dtype=torch.uint8)
+    _collate_crop_flip_into(src, rows, clips, n_px, chw, out)
+    return out
+
+
+@collate_clips_crop_flip.register_fake
+def _(src, rows, clips, n_px, chw):
+    n_out = _collate_check("collate_clips_crop_flip", src, rows, clips, n_px, chw, COLLATE_BOX_ROW)
+    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::collate_clips_crop_flip_out", mutates_args=("out",), device_types="cuda")
+def collate_clips_crop_flip_out(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, chw: bool,
+                                out: torch.Tensor) -> None:
+    """collate_clips_crop_flip into a buffer of the caller's; every frame of it is written."""
+    _collate_crop_flip_into(src, rows, clips, n_px, chw, out)
+
+
+@collate_clips_crop_flip_out.register_fake
+def _(src, rows, clips, n_px, chw, out):
+    _collate_check("collate_clips_crop_flip", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
+    return None
+
+
 @custom_op(NS + "::clip_encode_out", mutates_args=("vfeat", "tfeat", "medoids_out"), device_types="cuda")
 def clip_encode_out(frames: torch.Tensor, ids: torch.Tensor, vhandle: int, thandle: int, B: int, T: int,
                     vfeat: torch.Tensor, tfeat: torch.Tensor, medoids_out: Optional[torch.Tensor],

@@ -9,6 +9,7 @@ dataloaders/* to evaluate a trained model.
     python examples/eval_synthetic.py [--clips 64] [--algo kmediods++|spectral|pooling] [--l14 1 [--oracle-check 1]]
     python examples/eval_synthetic.py --resume DIR/ckpt.pth.tar      (main.py's --resume ... --do_eval 1: evaluate a checkpoint)
     python examples/eval_synthetic.py --raw_frames 240x320           (decoded uint8 frames; resize + centre crop on the device)
+    python examples/eval_synthetic.py --ragged 1                     (clips of mixed sizes and lengths, collated on the device)
 """
 import argparse
 import os
@@ -47,6 +48,30 @@ class SyntheticRetrieval(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         return self.ids[i], self.mask[i], torch.zeros_like(self.ids[i]), self.video[i], self.vmask[i]
+
+
+class RaggedRetrieval(torch.utils.data.Dataset):
+    """The same items with the video as a decoder leaves it: uint8 [t, H, W, 3], H x W and t <= frames differing from clip to
+    clip (the short side is not 224 for every clip, so some are resized and some only cropped).  ``collate`` packs a batch
+    (preprocess.pack_clips) and builds its video mask from the clips' lengths."""
+    SIZES = ((224, 298), (224, 398), (398, 224), (240, 320))
+
+    def __init__(self, n, frames=12, seed=0):
+        self.text, self.frames = SyntheticRetrieval(n, frames=1, seed=seed, raw_frames=(4, 4)), frames
+        g = torch.Generator().manual_seed(seed + 1)
+        self.video = [torch.randint(0, 256, (frames - (i % 3) * 2,) + self.SIZES[i % len(self.SIZES)] + (3,), dtype=torch.uint8,
+                                    generator=g) for i in range(n)]
+
+    def __len__(self):
+        return len(self.video)
+
+    def __getitem__(self, i):
+        return self.text.ids[i], self.text.mask[i], torch.zeros_like(self.text.ids[i]), self.video[i]
+
+    def collate(self, items):
+        from centerclip_amd.preprocess import pack_clips
+        packed = pack_clips([it[3] for it in items])
+        return tuple(torch.stack([it[k] for it in items]) for k in range(3)) + (packed, packed.video_mask(self.frames).unsqueeze(1))
 
 
 # ViT-L/14 at 224 px (OpenAI's ViT-L-14.pt geometry: width 1024, 24 layers, patch 14 -> 257 tokens per frame, embedding 768,
@@ -135,6 +160,9 @@ def main():
     ap.add_argument("--raw_frames", default=None, metavar="HxW",
                     help="the loader yields decoded uint8 frames of this size; Resize(res, BICUBIC) + CenterCrop(res) of CLIP's "
                          "transform run on the device (eval_epoch(frame_transform=...))")
+    ap.add_argument("--ragged", type=int, default=0,
+                    help="1: the loader yields PackedClips - decoded clips of mixed H x W and lengths - and preprocess.ClipCollate "
+                         "resizes, crops and zero-pads them into the uniform batch on the device, at most two launches per batch")
     a = ap.parse_args()
     device = torch.device("cuda:0")
     c = L14 if a.l14 else bench.CFG2
@@ -162,6 +190,17 @@ def main():
         transform = FrameTransform(c["res"])
         print("frame transform %dx%d -> %d: %.3f ms per batch of %d clips" % (raw[0], raw[1], c["res"], transform_ms(
             transform, next(iter(loader))[3], device), a.batch))
+    if a.ragged:
+        from centerclip_amd.preprocess import ClipCollate
+        from centerclip_amd.search import FeatureGallery
+        data = RaggedRetrieval(a.clips, frames=c["T"])
+        loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False, collate_fn=data.collate)
+        transform = ClipCollate(c["res"], max_frames=c["T"])
+        packed, vmask = next(iter(loader))[3:]
+        print("ragged batch: %d clips, %d bytes, lengths %s" % (len(packed), packed.data.numel(), packed.table[:, 1].tolist()))
+        # a FeatureGallery takes the collated tensor as it is
+        pos = FeatureGallery(model).add(transform(packed.to(device)), vmask.to(device))
+        print("FeatureGallery.add(collate(packed), mask): %d clips added" % len(pos))
     r1, seconds, info = eval_epoch(model, loader, device, args, log=print, in_flight=a.in_flight,
                                    **({"frame_transform": transform} if transform is not None else {}))
     print("\n".join(info))

@@ -102,6 +102,9 @@ def build_parser():
                     help="train-time augmentation on the device (decode.py:32-41): one crop box per clip, resized to 224 px")
     ap.add_argument("--flip", type=int, default=0, help="with --augment: also one random horizontal flip per clip")
     ap.add_argument("--raw_frames", default="240,320", help="with --augment (and without --uint8 1): H,W of the decoded uint8 frames")
+    ap.add_argument("--ragged", type=int, default=0,
+                    help="1: the loader yields PackedClips - decoded clips of mixed H x W and lengths - collated on the device by "
+                         "preprocess.ClipCollate: the evaluation transform, or with --augment one box and one flip per clip")
     return ap
 
 
@@ -158,6 +161,12 @@ def main():
     elif a.flip:
         raise SystemExit("--flip 1 goes with --augment")
     loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False)
+    if a.ragged:
+        from centerclip_amd.preprocess import ClipCollate
+        from eval_synthetic import RaggedRetrieval
+        data = RaggedRetrieval(a.batch * a.steps, frames=c["T"], seed=rank)
+        loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False, collate_fn=data.collate)
+        augment = ClipCollate(c["res"], max_frames=c["T"], train=augment)
     if a.same_batch:
         loader = [next(iter(loader))] * a.steps
     t, dts = [time.time()], []                              # the last time stamp; every step's duration

@@ -748,6 +748,51 @@ int cc_resize_crop_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_
 int cc_resized_crop_flip_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_t W, int32_t frames_per_clip,
                             const int32_t* boxes_dev, int32_t n_px, int32_t interp, void* dst, int32_t dst_fmt, void* stream);
 
+/* Ragged clip batches: what a decoder produces - clips of mixed H x W and mixed lengths, packed back to back in ONE byte
+ * buffer with no alignment padding - collated into the uniform [n_out, n_px, n_px, 3] / [n_out, 3, n_px, n_px] frames the
+ * encoders take.  cc_collate_resize_crop_u8 is cc_resize_crop_u8 per frame and cc_collate_crop_flip_u8 is
+ * cc_resized_crop_flip_u8 per frame: the kernels call the same device functions, so each output frame is byte for byte what the
+ * per-size entry point gives for its source frame.  DESIGN.md, "Ragged clip batches".
+ *
+ * LAUNCH BOUND: one call of cc_collate_resize_crop_u8 is at most TWO launches (the horizontal pass of the frames that run both
+ * passes, then one launch that writes every output frame) and one call of cc_collate_crop_flip_u8 is ONE launch - at most
+ * three for either, whatever the number of clips, of output frames and of distinct sizes.  The third grid dimension runs over
+ * output frames, at most CC_COLLATE_MAX_PLANES of them at a time (fewer where the grid would pass 2^31 threads); more frames
+ * than planes are folded onto the planes, none is refused.  The grid covers the largest frame of the call.
+ *
+ * src: the packed bytes, src_bytes of them; every frame is [H, W, 3] (fmt = CC_FRAMES_U8_HWC) or [3, H, W]
+ * (CC_FRAMES_U8_CHW), at ANY byte address.  clips_host: HOST int64 [n_clips, 4] rows (byte offset, frames t, H, W) - what
+ * the entry point checks before any launch: CC_ERR_INVALID unless 0 <= offset, t >= 1 and offset + t * H * W * 3 <= src_bytes for
+ * every clip, and the status cc_resize_crop_status (resp. cc_resized_crop_flip_u8) gives for a size it refuses.
+ * rows_dev: DEVICE int64 table, one row per OUTPUT frame; the host never reads it, the kernels read a frame's row before
+ * anything else and follow it only when it holds up against src_bytes (and plans_ints, ws_bytes): a row that does not comes out
+ * as a zero frame, no address is formed from it.  Zero frames are written by the last launch, so dst is fully defined.
+ *   cc_collate_resize_crop_u8, CC_COLLATE_ROW = 6 values: [0] kind (0 = a zero frame, 1 = transform)  [1] byte offset of the
+ *     source frame in src  [2] H  [3] W  [4] int32 offset of the frame's plan (cc_resize_plan_build of (H, W, n_px, resize)) in
+ *     plans_dev  [5] byte offset in ws of the frame's horizontal result (3 x (row1 - row0) x n_px bytes; read only where both
+ *     passes run; frames must not share it)
+ *   cc_collate_crop_flip_u8, CC_COLLATE_BOX_ROW = 10 values: [0] kind  [1] byte offset  [2] H  [3] W  [4] top  [5] left
+ *     [6] height  [7] width  [8] flip  [9] interp (0 bilinear, 1 bicubic)
+ * plans_dev: the plans of the call's sizes one behind the other, plans_ints int32 values in all.
+ * cc_collate_resize_crop_workspace_bytes: n_out x the largest horizontal result among the clips' sizes (0 where no size runs
+ * both passes) - frame i may then use offset i * (bytes / n_out).
+ * CC_ERR_INVALID for a NULL src / dst / table / plans / clips_host, n_out <= 0, n_clips <= 0 or a format other than the two uint8
+ * codes; CC_ERR_WORKSPACE for a workspace that cannot hold one horizontal result of the call's largest size; all before any
+ * launch.  No upload, no synchronisation (capturable once the tables are on the device). */
+#define CC_RESIZE_MAX_TAPS 65
+#define CC_COLLATE_ROW 6
+#define CC_COLLATE_BOX_ROW 10
+#define CC_COLLATE_MAX_PLANES 4096
+/* the status cc_resize_crop_u8 gives for frames of this size (CC_OK, CC_ERR_UNSUPPORTED, CC_ERR_INVALID); no GPU needed */
+int cc_resize_crop_status(int32_t H, int32_t W, int32_t n_px, int32_t resize);
+size_t cc_collate_resize_crop_workspace_bytes(const int64_t* clips_host, int32_t n_clips, int32_t n_out, int32_t n_px,
+                                              int32_t resize);
+int cc_collate_resize_crop_u8(const void* src, size_t src_bytes, int32_t fmt, const int64_t* clips_host, int32_t n_clips,
+                              const int64_t* rows_dev, int32_t n_out, const int32_t* plans_dev, size_t plans_ints, int32_t n_px,
+                              int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream);
+int cc_collate_crop_flip_u8(const void* src, size_t src_bytes, int32_t fmt, const int64_t* clips_host, int32_t n_clips,
+                            const int64_t* rows_dev, int32_t n_out, int32_t n_px, void* dst, int32_t dst_fmt, void* stream);
+
 /* S2 - the meanP similarity tail, CLIP4Clip._loose_similarity (modules/clip4clip.py:357-366) with
  * _mean_pooling_for_similarity_visual (:305-316):
  *   v_hat = v/|v| per frame; v_bar = sum_t mask*v_hat / max(sum_t mask, 1 if 0); v_bar /= |v_bar|
