@@ -574,8 +574,10 @@ __global__ void group_max_fill_kernel(float* __restrict__ out, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = -INFINITY;
 }
-__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {      // (finite or -inf values; initial -inf)
-    if (v >= 0.f) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
+// By the SIGN BIT of v, not by v >= 0.f: -0.0 (bits 0x80000000 = INT_MIN) would lose the signed maximum to the -inf fill and
+// to every negative value; as the smallest unsigned pattern with the sign bit set it wins the unsigned minimum over them.
+__device__ __forceinline__ void atomic_max_f32(float* addr, float v) {      // (no NaN; initial -inf)
+    if (__float_as_int(v) >= 0) atomicMax(reinterpret_cast<int*>(addr), __float_as_int(v));
     else atomicMin(reinterpret_cast<unsigned*>(addr), __float_as_uint(v));
 }
 constexpr int GMAX_ROWS = 64;       // rows per chunk

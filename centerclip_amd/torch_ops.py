@@ -1945,9 +1945,26 @@ def _(sim, transpose, diag_offset):
     return sim.new_empty((sim.shape[1] if transpose else sim.shape[0], 2), dtype=torch.int32)
 
 
+def _check_sim_f32(name, sim):
+    """The retrieval-tail kernels take bare pointers and walk fp32 [rows, cols] matrices: anything else is refused here, from
+    the tensor's metadata alone."""
+    if sim.dim() != 2 or sim.dtype != torch.float32:
+        raise ValueError("%s: sim %s %s is not a 2-D fp32 matrix" % (name, tuple(sim.shape), sim.dtype))
+
+
+def _check_per_row(name, what, t, dtype, rows, sim):
+    if t.dtype != dtype or t.dim() != 1 or t.numel() != int(rows) or not t.is_contiguous() or t.device != sim.device:
+        raise ValueError("%s: %s %s %s on %s is not one contiguous %s per row (%d) on %s"
+                         % (name, what, tuple(t.shape), t.dtype, t.device, dtype, int(rows), sim.device))
+
+
 @custom_op(NS + "::rank_counts_cols", mutates_args=(), device_types="cuda")
 def rank_counts_cols(sim: torch.Tensor, gt_cols: torch.Tensor) -> torch.Tensor:
     """utils/metrics.py:38-65: sim [R, C] contiguous, gt_cols [R] int32 -> (#greater, #equal, #equal before) per row."""
+    _check_sim_f32("rank_counts_cols", sim)
+    if not sim.is_contiguous():
+        raise ValueError("rank_counts_cols: sim %s with strides %s is not contiguous" % (tuple(sim.shape), tuple(sim.stride())))
+    _check_per_row("rank_counts_cols", "gt_cols", gt_cols, torch.int32, sim.shape[0], sim)
     R, C = sim.shape
     counts = _e(R, 3, like=sim, dtype=torch.int32)
     L.check(L.lib().cc_rank_counts_cols_f32(L.ptr(sim), R, C, C, 1, L.ptr(gt_cols), L.ptr(counts), _st(sim)),
@@ -2093,7 +2110,9 @@ def _(sim, m, s, n_total):
 def rank_counts_ref(sim: torch.Tensor, ref_vals: torch.Tensor, transpose: bool) -> torch.Tensor:
     """(#greater, #equal) than ref_vals[i] per row of sim (per COLUMN with transpose=True, through the strides): the
     partial video->text counts of a row block of the similarity matrix (clip-sharded eval)."""
+    _check_sim_f32("rank_counts_ref", sim)
     rows, cols = (sim.shape[1], sim.shape[0]) if transpose else sim.shape
+    _check_per_row("rank_counts_ref", "ref_vals", ref_vals, torch.float32, rows, sim)
     rs, cs = (sim.stride(1), sim.stride(0)) if transpose else (sim.stride(0), sim.stride(1))
     counts = _e(rows, 2, like=sim, dtype=torch.int32)
     L.check(L.lib().cc_rank_counts_ref_f32(L.ptr(sim), rows, cols, rs, cs, L.ptr(ref_vals), L.ptr(counts), _st(sim)),
@@ -2109,7 +2128,14 @@ def _(sim, ref_vals, transpose):
 @custom_op(NS + "::group_max_rows", mutates_args=(), device_types="cuda")
 def group_max_rows(sim: torch.Tensor, group: torch.Tensor, n_groups: int) -> torch.Tensor:
     """[n_groups, cols] maxima of sim's rows per group id (int32 [rows]), NaN ignored, -inf for groups without a row:
-    tensor_video_to_text_sim (utils/metrics.py:68-76)."""
+    tensor_video_to_text_sim (utils/metrics.py:68-76).  sim [rows, cols] fp32 with unit column stride (any row stride)."""
+    _check_sim_f32("group_max_rows", sim)
+    if sim.stride(1) != 1:
+        raise ValueError("group_max_rows: sim %s with strides %s does not have a unit column stride"
+                         % (tuple(sim.shape), tuple(sim.stride())))
+    _check_per_row("group_max_rows", "group", group, torch.int32, sim.shape[0], sim)
+    if int(n_groups) <= 0:
+        raise ValueError("group_max_rows: n_groups >= 1, not %d" % int(n_groups))
     rows, cols = sim.shape
     out = _e(int(n_groups), cols, like=sim, dtype=torch.float32)
     L.check(L.lib().cc_group_max_rows_f32(L.ptr(sim) if rows else None, rows, cols, sim.stride(0) if rows else cols,
@@ -2125,7 +2151,11 @@ def _(sim, group, n_groups):
 
 @custom_op(NS + "::contrastive_loss", mutates_args=(), device_types="cuda")
 def contrastive_loss(sim: torch.Tensor) -> torch.Tensor:
-    """CrossEn(sim), CrossEn(sim.T) and their mean (modules/losses.py:8-18, clip4clip.py:250-253) -> [3] fp32."""
+    """CrossEn(sim), CrossEn(sim.T) and their mean (modules/losses.py:8-18, clip4clip.py:250-253) -> [3] fp32.
+    sim [n, n] fp32, any strides."""
+    _check_sim_f32("contrastive_loss", sim)
+    if sim.shape[0] != sim.shape[1]:
+        raise ValueError("contrastive_loss: sim %s is not square" % (tuple(sim.shape),))
     n = sim.shape[0]
     out = _e(3, like=sim, dtype=torch.float32)
     ws = L.workspace(2 * n * 4, sim.device)
