@@ -32,6 +32,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // rather than the Infinity Cache needs (a launch inside the step reads what the launch before it has just written: c_proj
 // 55 us with its A operand left in the MALL by the previous launch of a loop, 65-75 us with it cold, tools/cold_operands.py).
 #define GEMM_NST(BM, BN, WAVES, BK) (((WAVES) == 8 && (BK) == 64 && 3 * ((BM) + (BN)) * (BK) * 2 <= 160 * 1024) ? 3 : 2)
+// The folded-LayerNorm epilogues (not the attention form) keep each tile row's (mean, rstd) in LDS behind the stage buffers from
+// the prologue on: BM x 8 bytes more per workgroup instead of two registers carried across the whole loop, which the 256x256
+// tile does not have (they were spilled to private memory and reloaded at the head of the epilogue).
+#define GEMM_LN_PARK(EPI) ((EPI) == EPI_F16_LN || (EPI) == EPI_F16_GELU_LN || (EPI) == EPI_F16_GELU_ERF_LN)
 
 // EPI_ATTN_LN epilogue LDS map (bytes): row statistics [256] x 8 | Q [256][72] | K [256][72] | V^T [64][328] (5 slots of 64
 // keys or 8 of 32) | P strips 8 x [16][72] | sequence table [16] | V^T column of every tile row [256]
@@ -95,6 +99,52 @@ extern "C" void cc_debug_set_attn_dump(_Float16* dev_buf) {
 }
 #endif
 
+// The wave's index inside its workgroup, as a scalar: threadIdx.x >> 6 is uniform over a wave but the compiler cannot know
+// that, and everything derived from a divergent index (the wave's tile position, its LDS-DMA destinations, the buffer
+// resource of the residual prefetch) then costs v_readfirstlane / waterfall loops where it has to be uniform.
+#define CC_WAVE_ID() __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+
+// Row statistics of a consumer: the producer's nslots <= 2 NP partial (sum, sum of squares) pairs of one row.  Every lane
+// reads another row, so a load instruction touches 64 cache lines whatever its width and the reduction is bound by the number
+// of load instructions, not by their latency (measured: all CC_LN_MAX_SLOTS 8-byte loads in flight at once was SLOWER than
+// batches of eight, profiles/gemm_prologue.txt).  So: two slots per 16-byte load, all of them issued before the first add,
+// an odd last slot by an 8-byte load of its own.  The adds run left to right in slot order; loads behind the row's last pair
+// read that pair again and add nothing - the sums are those of a serial loop bit for bit.
+typedef f32x4 f32x4_a8 __attribute__((aligned(8)));           // (a row of an odd slot count starts 8 bytes off)
+template <int NP, bool SQ>
+__device__ __forceinline__ void reduce_row_pairs(const float2* ps, int nslots, float& sum, float& sq) {
+    const int npairs = nslots >> 1;
+    f32x4 t4[NP];
+    float2 last = make_float2(0.f, 0.f);
+    if (npairs) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) t4[p] = *reinterpret_cast<const f32x4_a8*>(ps + 2 * min(p, npairs - 1));
+    } else {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) t4[p] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (nslots & 1) last = ps[nslots - 1];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        const bool on = p < npairs;
+        sum += on ? t4[p][0] : 0.f;
+        if (SQ) sq += on ? t4[p][1] : 0.f;
+        sum += on ? t4[p][2] : 0.f;
+        if (SQ) sq += on ? t4[p][3] : 0.f;
+    }
+    sum += last.x;
+    if (SQ) sq += last.y;
+}
+// (one arm per eight slots: a launch never issues more than three loads per row that it does not need)
+template <bool SQ>
+__device__ __forceinline__ void reduce_row_stats(const float2* ps, int nslots, float& sum, float& sq) {
+    static_assert(CC_LN_MAX_SLOTS == 32, "four arms");
+    if (nslots <= 8) reduce_row_pairs<4, SQ>(ps, nslots, sum, sq);
+    else if (nslots <= 16) reduce_row_pairs<8, SQ>(ps, nslots, sum, sq);
+    else if (nslots <= 24) reduce_row_pairs<12, SQ>(ps, nslots, sum, sq);
+    else reduce_row_pairs<16, SQ>(ps, nslots, sum, sq);
+}
+
 template <int CTRL>
 __device__ __forceinline__ float dpp_f32(float x) {          // lane exchange inside a 16-lane DPP row (bit pattern)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
@@ -148,32 +198,43 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     const int row0 = ATTN ? (g.att_seq_off ? g.att_seq_off[att_s0] : att_s0 * g.att_L) : tm * BM, col0 = tn * BN;
     if (row0 >= g.M) return;                                 // (only with m_dev: the grid was sized for the upper bound)
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63, wave = CC_WAVE_ID();
     const int wr = wave / WN, wc = wave % WN;
 
     // ---- staging addresses: LDS chunk idx -> (row r, chunk position cp); source chunk = cp ^ (r & (CH - 1))
     constexpr int A_LOADS = BMS * CH / THREADS, B_LOADS = BN * CH / THREADS;
-    const _Float16* asrc[A_LOADS];
-    const _Float16* bsrc[B_LOADS];
+    // A lane's source is a wave-uniform 64-bit base (the tile's first row / the weight rows of the tile) plus a 32-bit byte
+    // offset inside the tile's panel: what has to live in VGPRs from the prologue on is one register per piece instead of a
+    // 64-bit pointer, which is what the 8-wave residual tiles were short of (7 VGPRs spilled around the loop before).
+    const int lda = g.lda ? g.lda : g.K, ldw = g.ldw ? g.ldw : g.K;
+    const _Float16* abase = g.A + (int64_t)row0 * lda;
+    const _Float16* bbase = g.W + (int64_t)(ATTN ? tn * 64 : col0) * ldw;
+    unsigned aoff[A_LOADS], boff[B_LOADS];
 #pragma unroll
     for (int q = 0; q < A_LOADS; ++q) {
         const int idx = (q * NWAVES + wave) * 64 + lane, r = idx / CH, c = (idx % CH) ^ (r & (CH - 1));
-        asrc[q] = g.A + (int64_t)min(row0 + r, g.M - 1) * (g.lda ? g.lda : g.K) + c * 8;
+        aoff[q] = (unsigned)((min(row0 + r, g.M - 1) - row0) * lda + c * 8) * 2u;
     }
 #pragma unroll
     for (int q = 0; q < B_LOADS; ++q) {
         const int idx = (q * NWAVES + wave) * 64 + lane, r = idx / CH, c = (idx % CH) ^ (r & (CH - 1));
         // (ATTN: wave column wc multiplies the d-slice [16 wc, 16 wc + 16) of q, of k and of v: LDS row 48 wc + 16 sec + dd)
-        const int wrow = ATTN ? ((r % 48) >> 4) * (g.N / 3) + tn * 64 + (r / 48) * 16 + (r & 15) : col0 + r;
-        bsrc[q] = g.W + (int64_t)wrow * (g.ldw ? g.ldw : g.K) + c * 8;
+        const int wrow = ATTN ? ((r % 48) >> 4) * (g.N / 3) + (r / 48) * 16 + (r & 15) : r;
+        boff[q] = (unsigned)(wrow * ldw + c * 8) * 2u;
     }
+    auto a_src = [&](int q, int kt) {
+        return reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(abase + kt * BK) + aoff[q]);
+    };
+    auto b_src = [&](int q, int kt) {
+        return reinterpret_cast<const _Float16*>(reinterpret_cast<const char*>(bbase + kt * BK) + boff[q]);
+    };
     auto stage = [&](int buf, int kt) {
         _Float16* la = reinterpret_cast<_Float16*>(smem + buf * (A_BYTES + B_BYTES));
         _Float16* lb = reinterpret_cast<_Float16*>(smem + buf * (A_BYTES + B_BYTES) + A_BYTES);
 #pragma unroll
-        for (int q = 0; q < A_LOADS; ++q) glds16(asrc[q] + kt * BK, la + (q * NWAVES + wave) * 512);
+        for (int q = 0; q < A_LOADS; ++q) glds16(a_src(q, kt), la + (q * NWAVES + wave) * 512);
 #pragma unroll
-        for (int q = 0; q < B_LOADS; ++q) glds16(bsrc[q] + kt * BK, lb + (q * NWAVES + wave) * 512);
+        for (int q = 0; q < B_LOADS; ++q) glds16(b_src(q, kt), lb + (q * NWAVES + wave) * 512);
     };
 
     f32x4 acc[MI][NI];
@@ -188,23 +249,19 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     const bool rider_first = second && pr.rider_prio;
     if (rider_first) __builtin_amdgcn_s_setprio(2);
     stage(0, 0);
-    // folded LayerNorm: thread r < BM reduces the producer's partial sums of tile row r right away (fixed
-    // slot order, 8 loads in flight) - the L2 latency hides under the main loop; result parked in 2 registers.
+    // folded LayerNorm: thread r < BM reduces the producer's partial sums of tile row r right away (fixed slot order, every
+    // load in flight at once: reduce_row_stats).  The barrier below waits for them - the latency is exposed, one round trip
+    // next to the one of stage 0; result parked behind the stage buffers (GEMM_LN_PARK; the attention form: in 2 registers).
     float row_mu = 0.f, row_rs = 1.f;
     if ((EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN || EPI == EPI_F16_GELU_ERF_LN || ATTN) && tid < BM) {
         const int m = min(row0 + tid, g.M - 1);
         const float2* ps = reinterpret_cast<const float2*>(g.ln_stats) + (int64_t)m * g.ln_slots;
         float sum = 0.f, sq = 0.f;
-        for (int q0 = 0; q0 < g.ln_slots; q0 += 8) {
-            float2 t2[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t2[u] = (q0 + u < g.ln_slots) ? ps[q0 + u] : make_float2(0.f, 0.f);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) { sum += t2[u].x; sq += t2[u].y; }
-        }
+        reduce_row_stats<true>(ps, g.ln_slots, sum, sq);
         row_mu = sum / (float)g.K;
         const float var = fmaxf(sq / (float)g.K - row_mu * row_mu, 0.f);
         row_rs = 1.0f / sqrtf(var + g.ln_eps);
+        if (GEMM_LN_PARK(EPI)) reinterpret_cast<float2*>(smem + NST * (A_BYTES + B_BYTES))[tid] = make_float2(row_mu, row_rs);
     }
     // ATTN: thread r also finds where tile row r lands in the V^T tile (sequence slot * slot width + token), -1 = no sequence
     int att_vcol = -1;
@@ -225,25 +282,25 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     if (EPI == EPI_F32_RESID_STATS && g.shift_stats && tid < BM) {
         const int m = min(row0 + tid, g.M - 1);
         const float2* ps = reinterpret_cast<const float2*>(g.shift_stats) + (int64_t)m * g.shift_slots;
-        float sum = 0.f;
-        for (int q0 = 0; q0 < g.shift_slots; q0 += 8) {
-            float2 t2[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t2[u] = (q0 + u < g.shift_slots) ? ps[q0 + u] : make_float2(0.f, 0.f);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) sum += t2[u].x;
-        }
+        float sum = 0.f, unused = 0.f;
+        reduce_row_stats<false>(ps, g.shift_slots, sum, unused);
         row_mu = (g.shift_in ? g.shift_in[m] : 0.f) + sum / (float)g.N;
     }
     __syncthreads();
     GEMM_STAMP(1);
-    const int l15 = lane & 15, lg = lane >> 4;
+    int l15 = lane & 15, lg = lane >> 4;                      // (formed again behind the loop, see fresh_lane)
     // Per-column epilogue operands (bias, LN-fold column sums) are fetched into registers while the last k-step's
     // MFMAs run: issued from inside the epilogue, behind its stores, every fragment would pay its own L2 round trip.
     constexpr bool RESID = (EPI == EPI_F32_RESID || EPI == EPI_F32_RESID_STATS);
     constexpr bool LNFOLD = (EPI == EPI_F16_LN || EPI == EPI_F16_GELU_LN || EPI == EPI_F16_GELU_ERF_LN || ATTN);
     float4 biasv[NI], c1v[LNFOLD ? NI : 1];
+    // The loop's LDS addresses have l15 and lg folded in; what comes behind it (the operand fetch under the last k-step, the
+    // epilogue) needs the bare values again.  Formed afresh from the lane counter - an expression the compiler cannot merge
+    // with the first one - they are a few VALU operations there instead of registers held across the whole loop, which the
+    // 256x256 tile spilled to private memory.
+    auto fresh_lane = [&]() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); };
     auto fetch_epilogue_operands = [&]() {
+        const int l15 = fresh_lane() & 15, lg = fresh_lane() >> 4;
 #pragma unroll
         for (int j = 0; j < NI; ++j) {
             if (ATTN && j == 2) {                       // the V fragment is accumulated transposed: one column (d) per lane
@@ -303,8 +360,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     };
     auto stage_piece = [&](int buf, int kt, int q) {        // q-th of the A_LOADS + B_LOADS pieces of a stage
         unsigned char* base = smem + buf * (A_BYTES + B_BYTES);
-        if (q < A_LOADS) glds16(asrc[q] + kt * BK, reinterpret_cast<_Float16*>(base) + (q * NWAVES + wave) * 512);
-        else glds16(bsrc[q - A_LOADS] + kt * BK,
+        if (q < A_LOADS) glds16(a_src(q, kt), reinterpret_cast<_Float16*>(base) + (q * NWAVES + wave) * 512);
+        else glds16(b_src(q - A_LOADS, kt),
                     reinterpret_cast<_Float16*>(base + A_BYTES) + ((q - A_LOADS) * NWAVES + wave) * 512);
     };
     auto mma_row = [&](int i, const h8 (&af)[MI], const h8 (&bf)[NI]) {
@@ -580,6 +637,8 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
     }
 
     GEMM_STAMP(2);
+    l15 = fresh_lane() & 15;
+    lg = fresh_lane() >> 4;
     // ---- epilogue: lane holds C[m = .. + l15][n = .. + lg*4 + 0..3]
     constexpr int WTM = BM / WM, WTN = BN / WN;              // wave tile
     constexpr bool GELU_ERF = (EPI == EPI_F16_GELU_ERF || EPI == EPI_F16_GELU_ERF_LN);
@@ -978,13 +1037,13 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_f16_kernel(GemmPair pr) {
         // fp16 outputs go through LDS (the staging buffers are free now) so that a wave stores whole
         // 128-byte row segments (8 lanes x 16 B) instead of 16 rows x 32 B per instruction.
         constexpr int LDO = WTN + 8;                          // halfs per staged row (144-byte rows for WTN = 64)
-        constexpr int STATS_BYTES = FOLD_LN ? BM * 8 : 0;     // (mu, rstd) per tile row, at the start of smem
+        constexpr int STATS_BYTES = FOLD_LN ? BM * 8 : 0;     // (mu, rstd) per tile row, at the start of smem when not parked
         constexpr int RH_MAX = (NST * (A_BYTES + B_BYTES) - STATS_BYTES) / (NWAVES * LDO * 2);
         constexpr int RH = (RH_MAX >= WTM) ? WTM : (RH_MAX >= 64 ? 64 : (RH_MAX >= 32 ? 32 : 16));
         static_assert(WTM % RH == 0 && RH % 16 == 0, "epilogue staging geometry");
-        float2* rowst = reinterpret_cast<float2*>(smem);
-        if (FOLD_LN) {
-            static_assert(BM <= THREADS, "one thread per tile row");
+        static_assert(BM <= THREADS, "one thread per tile row");
+        float2* rowst = reinterpret_cast<float2*>(smem + (GEMM_LN_PARK(EPI) ? NST * (A_BYTES + B_BYTES) : 0));
+        if (FOLD_LN && !GEMM_LN_PARK(EPI)) {                  // (parked: written in the prologue, barriers passed since)
             if (tid < BM) rowst[tid] = make_float2(row_mu, row_rs);
             __syncthreads();
         }
@@ -1218,7 +1277,7 @@ namespace {
 template <int BM, int BN, int WM, int WN, int EPI, int BK = GEMM_BK>
 int launch_one(const GemmPair& pr, int total, hipStream_t st) {
     constexpr int BMS = (BM + 63) / 64 * 64;
-    constexpr size_t smem_loop = (size_t)GEMM_NST(BMS, BN, WM * WN, BK) * (size_t)(BMS + BN) * BK * 2;
+    constexpr size_t smem_loop = (size_t)GEMM_NST(BMS, BN, WM * WN, BK) * (size_t)(BMS + BN) * BK * 2 + (GEMM_LN_PARK(EPI) ? BM * 8 : 0);
     constexpr size_t smem = (EPI == EPI_ATTN_LN && smem_loop < ATTN_SMEM) ? (size_t)ATTN_SMEM : smem_loop;
     auto kern = gemm_f16_kernel<BM, BN, WM, WN, EPI, BK>;
     if (cc_allow_dynamic_lds(reinterpret_cast<const void*>(kern), smem) != CC_OK) return CC_ERR_HIP;
@@ -1531,7 +1590,7 @@ __global__ __launch_bounds__(64 * ROWS_WAVES) void gemm_rows_kernel(RowsPair pr)
     const int bid = second ? blockIdx.x - pr.blocks0 : blockIdx.x;
     const int ncb = g.N / ROWS_BN;
     const int cb = bid % ncb, row0 = (bid / ncb) * ROWS_BM, col0 = cb * ROWS_BN;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
+    const int tid = threadIdx.x, wave = CC_WAVE_ID(), lane = tid & 63, l15 = lane & 15, lg = lane >> 4;
     __shared__ float red[ROWS_WAVES / 2][ROWS_BM][ROWS_LDR];     // 36 KB
     __shared__ float2 rowst[ROWS_BM];
     constexpr bool LNFOLD = (EPI == EPI_F16_GELU_LN || EPI == EPI_F16_GELU_ERF_LN);
