@@ -26,6 +26,15 @@ class TokenLayout(ctypes.Structure):
                 ("stride_f", ctypes.c_int64), ("stride_i", ctypes.c_int64)]
 
 
+class Yuv420Layout(ctypes.Structure):
+    """struct cc_yuv420_layout: byte offsets of an 8-bit 4:2:0 source - Y(y, x) at y * y_pitch + x, Cb(cy, cx) at u_offset +
+    cy * c_pitch + cx * c_step, Cr the same from v_offset, frame f at f * frame_stride; matrix 0 BT.601 / 1 BT.709, range 0 limited /
+    1 full."""
+    _fields_ = [("frame_stride", ctypes.c_int64), ("y_pitch", ctypes.c_int64), ("u_offset", ctypes.c_int64),
+                ("v_offset", ctypes.c_int64), ("c_pitch", ctypes.c_int64), ("c_step", ctypes.c_int32),
+                ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
+
+
 _lib = None
 
 

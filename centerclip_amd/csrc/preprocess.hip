@@ -12,13 +12,24 @@
 // - a frame base and a row of 3 W bytes carry no alignment.
 // A ragged batch (clips of mixed sizes and lengths packed back to back, cc_collate_resize_crop_u8): the same two passes as at
 // most two launches for the whole batch, one table row per output frame; the per-pixel arithmetic is the same device function.
+// YUV 4:2:0 sources (the cc_*_yuv420_u8 entries): the same kernels with the other pixel source of cc_pixels.h - the first pass
+// that touches the source converts each tap in its fetch; cc_yuv420_to_rgb_u8 is the crop kernel with the whole frame as window.
 #include <math.h>
 
 #include <vector>
 
 #include "cc_common.h"
+#include "cc_pixels.h"
 
 namespace {
+
+using cc_px::PixelSource;
+using cc_px::View;
+using cc_px::fetch_pixel;
+using cc_px::rgb_source;
+using cc_px::u8_format;
+using cc_px::view_of;
+using cc_px::YuvCoef;
 
 constexpr int kPrecisionBits = 22;
 constexpr int kMaxKsize = CC_RESIZE_MAX_TAPS;                     // taps per output sample the launches take: a shrink factor of 16
@@ -128,16 +139,6 @@ int geometry(int H, int W, int n_px, int resize, int max_ksize, Geometry* g) {
 
 size_t plan_ints(const Geometry& g, int n_px) { return CC_RESIZE_PLAN_HEADER + (size_t)n_px * (4 + g.ksize_h + g.ksize_v); }
 
-// byte strides of (frame, channel, row, column) of a uint8 image batch
-struct View {
-    int64_t sf, sc, sy, sx;
-};
-
-__host__ __device__ inline View view_of(int fmt, int64_t rows, int64_t cols) {
-    if (fmt == CC_FRAMES_U8_CHW) return View{3 * rows * cols, rows * cols, cols, 1};
-    return View{3 * rows * cols, 1, 3 * cols, 3};
-}
-
 // what the host believes the device plan was built for; a kernel handed another plan does nothing (its table entries are
 // source indices - they are only followed when they belong to these sizes)
 struct PlanKey {
@@ -157,13 +158,13 @@ constexpr int kTileX = 64, kTileY = 4;
 
 // One pass.  A thread owns output pixel (f, oy, ox) - ox along the lanes, so source, intermediate and output accesses of a wave
 // run along a row - and its three channels.  HORIZONTAL: out(f, c, oy, ox) = sum_k in(f, c, row_base + oy, first[ox] + k) coef[ox][k];
-// vertical: out(f, c, oy, ox) = sum_k in(f, c, first[oy] + k, ox) coef[oy][k] (the coefficients are then uniform over a wave).
-// in_off: byte offset of the origin the row / column indices count from (the vertical pass reads the workspace, whose row 0 is
-// source row row0, or - no horizontal pass - the source itself from column `left`).
+// vertical: out(f, c, oy, ox) = sum_k in(f, c, row_base + first[oy] + k, col_base + ox) coef[oy][k] (the coefficients are then
+// uniform over a wave).  row_base / col_base: the origin the row / column indices count from (the vertical pass reads the
+// workspace, whose row 0 is source row row0: row_base = -row0 - or, no horizontal pass, the source itself from column `left`).
 // resample_pixel is that thread's work, the one statement of the arithmetic: the per-size kernel below and the ragged-batch
-// kernel behind it both call it.
-template <bool VERT>
-__device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ in, const View& iv, int64_t in_off, int row_base,
+// kernel behind it both call it.  YUV: the source is 4:2:0 planes, every tap converted by the fetch (cc_pixels.h).
+template <bool VERT, bool YUV>
+__device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ in, const PixelSource& iv, int row_base, int col_base,
                                                const int32_t* __restrict__ plan, int n_px, int f, int oy, int ox,
                                                uint8_t* __restrict__ out, const View& ov) {
     const int ksize = plan[VERT ? 12 : 11];
@@ -171,16 +172,20 @@ __device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ in, c
     const int j = VERT ? oy : ox;
     const int first = tab[j], count = tab[n_px + j];
     const int32_t* coef = tab + 2 * n_px + (int64_t)j * ksize;
-    const uint8_t* p = in + (in_off + (int64_t)f * iv.sf +
-                             (VERT ? (int64_t)first * iv.sy + (int64_t)ox * iv.sx
-                                   : (int64_t)(row_base + oy) * iv.sy + (int64_t)first * iv.sx));
-    const int64_t step = VERT ? iv.sy : iv.sx;
+    const uint8_t* frame = in + (int64_t)f * iv.sf;
+    int y = row_base + (VERT ? first : oy), x = col_base + (VERT ? ox : first);
     int a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
-    for (int k = 0; k < count; ++k, p += step) {
+    for (int k = 0; k < count; ++k) {
         const int w = coef[k];
-        a0 += (int)p[0] * w;
-        a1 += (int)p[iv.sc] * w;
-        a2 += (int)p[2 * iv.sc] * w;
+        int c0, c1, c2;
+        fetch_pixel<YUV>(frame, iv, y, x, c0, c1, c2);
+        a0 += c0 * w;
+        a1 += c1 * w;
+        a2 += c2 * w;
+        if (VERT)
+            ++y;
+        else
+            ++x;
     }
     uint8_t* q = out + (int64_t)f * ov.sf + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
     q[0] = clip8(a0);
@@ -189,18 +194,20 @@ __device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ in, c
 }
 
 // neither axis is resampled: out(f, c, oy, ox) = in(f, c, top + oy, left + ox)
-__device__ __forceinline__ void crop_pixel(const uint8_t* __restrict__ in, const View& iv, int top, int left, int f, int oy,
+template <bool YUV>
+__device__ __forceinline__ void crop_pixel(const uint8_t* __restrict__ in, const PixelSource& iv, int top, int left, int f, int oy,
                                            int ox, uint8_t* __restrict__ out, const View& ov) {
-    const uint8_t* p = in + (int64_t)f * iv.sf + (int64_t)(top + oy) * iv.sy + (int64_t)(left + ox) * iv.sx;
+    int c0, c1, c2;
+    fetch_pixel<YUV>(in + (int64_t)f * iv.sf, iv, top + oy, left + ox, c0, c1, c2);
     uint8_t* q = out + (int64_t)f * ov.sf + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
-    q[0] = p[0];
-    q[ov.sc] = p[iv.sc];
-    q[2 * ov.sc] = p[2 * iv.sc];
+    q[0] = (uint8_t)c0;
+    q[ov.sc] = (uint8_t)c1;
+    q[2 * ov.sc] = (uint8_t)c2;
 }
 
-template <bool VERT>
-__global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8_t* __restrict__ in, View iv, int64_t in_off,
-                                                                       int row_base, const int32_t* __restrict__ plan,
+template <bool VERT, bool YUV>
+__global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8_t* __restrict__ in, PixelSource iv, int row_base,
+                                                                       int col_base, const int32_t* __restrict__ plan,
                                                                        PlanKey key, uint8_t* __restrict__ out, View ov,
                                                                        int out_rows, int tiles_x, int tiles_y) {
     if (!plan_matches(plan, key)) return;
@@ -208,16 +215,18 @@ __global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8
     const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
     const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
     if (ox >= n_px || oy >= out_rows) return;
-    resample_pixel<VERT>(in, iv, in_off, row_base, plan, n_px, f, oy, ox, out, ov);
+    resample_pixel<VERT, YUV>(in, iv, row_base, col_base, plan, n_px, f, oy, ox, out, ov);
 }
 
-__global__ __launch_bounds__(kTileX* kTileY) void crop_u8_kernel(const uint8_t* __restrict__ in, View iv, int top, int left,
-                                                                   uint8_t* __restrict__ out, View ov, int n_px, int tiles_x,
-                                                                   int tiles_y) {
+// the crop alone (n_px x n_px at (top, left)) and, with the whole frame as the window, the stand-alone conversion
+template <bool YUV>
+__global__ __launch_bounds__(kTileX* kTileY) void crop_u8_kernel(const uint8_t* __restrict__ in, PixelSource iv, int top, int left,
+                                                                   uint8_t* __restrict__ out, View ov, int rows, int cols,
+                                                                   int tiles_x, int tiles_y) {
     const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
     const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
-    if (ox >= n_px || oy >= n_px) return;
-    crop_pixel(in, iv, top, left, f, oy, ox, out, ov);
+    if (ox >= cols || oy >= rows) return;
+    crop_pixel<YUV>(in, iv, top, left, f, oy, ox, out, ov);
 }
 
 // ---- a ragged batch: clips of mixed sizes and lengths packed back to back, one table row per OUTPUT frame ----------------
@@ -234,7 +243,8 @@ struct CollateArgs {
     uint8_t* ws;
     int64_t ws_bytes;
     uint8_t* dst;
-    int32_t n_out, n_px, resize, fmt, dst_fmt;
+    int32_t n_out, n_px, resize, fmt, dst_fmt;      // fmt: the RGB format code, or (YUV) CC_YUV420_I420 / _NV12
+    YuvCoef k;                                      // YUV only
 };
 
 struct CollateFrame {
@@ -245,11 +255,12 @@ struct CollateFrame {
 };
 
 // -> whether output frame f is a transform whose row holds up; false: a zero frame
+template <bool YUV>
 __device__ __forceinline__ bool collate_frame(const CollateArgs& a, int f, CollateFrame* c) {
     const int64_t* row = a.rows + (int64_t)f * CC_COLLATE_ROW;
     const int64_t kind = row[0], off = row[1], H = row[2], W = row[3], plan_off = row[4], ws_off = row[5];
     if (kind != 1 || H < 4 || W < 4 || H > 8192 || W > 8192) return false;
-    if (off < 0 || off > a.src_bytes || 3 * H * W > a.src_bytes - off) return false;
+    if (off < 0 || off > a.src_bytes || (YUV ? cc_px::yuv420_frame_bytes(H, W) : 3 * H * W) > a.src_bytes - off) return false;
     if (plan_off < 0 || plan_off > a.plans_ints - CC_RESIZE_PLAN_HEADER) return false;
     const int32_t* plan = a.plans + plan_off;
     if (!plan_matches(plan, PlanKey{(int32_t)H, (int32_t)W, a.n_px, a.resize})) return false;
@@ -276,18 +287,21 @@ __device__ __forceinline__ bool collate_frame(const CollateArgs& a, int f, Colla
 // FINAL = false: the horizontal pass of the frames that run both passes, into the workspace; nothing else is touched.
 // FINAL = true: every output frame is written - zeros, the crop alone, the one pass its size needs, or the vertical pass over
 // the workspace.
-template <bool FINAL>
+template <bool FINAL, bool YUV>
 __global__ __launch_bounds__(kTileX* kTileY) void collate_resample_u8_kernel(CollateArgs a) {
     const int ox = blockIdx.x * kTileX + threadIdx.x, oy = blockIdx.y * kTileY + threadIdx.y;
     if (ox >= a.n_px) return;
     const View dv = view_of(a.dst_fmt, a.n_px, a.n_px);
     for (int f = blockIdx.z; f < a.n_out; f += gridDim.z) {
         CollateFrame c;
-        const bool ok = collate_frame(a, f, &c);
+        const bool ok = collate_frame<YUV>(a, f, &c);
+        // (a frame that fails its checks has no sizes to build a source from)
+        const PixelSource sv = !ok ? PixelSource{}
+                                   : (YUV ? cc_px::yuv420_tight_source(a.fmt, c.H, c.W, a.k) : rgb_source(a.fmt, c.H, c.W));
         if (!FINAL) {
             if (!ok || !c.mid || oy >= c.nrows) continue;
-            resample_pixel<false>(c.src, view_of(a.fmt, c.H, c.W), 0, c.row0, c.plan, a.n_px, 0, oy, ox, c.mid,
-                                  view_of(CC_FRAMES_U8_CHW, c.nrows, a.n_px));
+            resample_pixel<false, YUV>(c.src, sv, c.row0, 0, c.plan, a.n_px, 0, oy, ox, c.mid,
+                                       view_of(CC_FRAMES_U8_CHW, c.nrows, a.n_px));
             continue;
         }
         if (oy >= a.n_px) return;
@@ -299,16 +313,15 @@ __global__ __launch_bounds__(kTileX* kTileY) void collate_resample_u8_kernel(Col
             q[2 * dv.sc] = 0;
             continue;
         }
-        const View sv = view_of(a.fmt, c.H, c.W);
         if (c.mid) {
-            const View mv = view_of(CC_FRAMES_U8_CHW, c.nrows, a.n_px);
-            resample_pixel<true>(c.mid, mv, -(int64_t)c.row0 * mv.sy, 0, c.plan, a.n_px, 0, oy, ox, out, dv);
+            resample_pixel<true, false>(c.mid, rgb_source(CC_FRAMES_U8_CHW, c.nrows, a.n_px), -c.row0, 0, c.plan, a.n_px, 0, oy, ox,
+                                        out, dv);
         } else if (c.ksize_h) {
-            resample_pixel<false>(c.src, sv, 0, c.top, c.plan, a.n_px, 0, oy, ox, out, dv);
+            resample_pixel<false, YUV>(c.src, sv, c.top, 0, c.plan, a.n_px, 0, oy, ox, out, dv);
         } else if (c.ksize_v) {
-            resample_pixel<true>(c.src, sv, (int64_t)c.left * sv.sx, 0, c.plan, a.n_px, 0, oy, ox, out, dv);
+            resample_pixel<true, YUV>(c.src, sv, 0, c.left, c.plan, a.n_px, 0, oy, ox, out, dv);
         } else {
-            crop_pixel(c.src, sv, c.top, c.left, 0, oy, ox, out, dv);
+            crop_pixel<YUV>(c.src, sv, c.top, c.left, 0, oy, ox, out, dv);
         }
     }
 }
@@ -322,17 +335,67 @@ int collate_planes(int n_out, int tiles_x, int tiles_y) {
 }
 
 // the host's checks of a clip table [n_clips, 4] rows (byte offset, frames, H, W) against the packed buffer's size
-int collate_check_clips(const int64_t* clips, int n_clips, size_t src_bytes) {
+int collate_check_clips(const int64_t* clips, int n_clips, size_t src_bytes, bool yuv) {
     if (!clips || n_clips <= 0) return CC_ERR_INVALID;
     for (int i = 0; i < n_clips; ++i) {
         const int64_t off = clips[4 * i], t = clips[4 * i + 1], H = clips[4 * i + 2], W = clips[4 * i + 3];
         if (off < 0 || t < 1 || H < 1 || W < 1 || H > 8192 || W > 8192 || t > (int64_t)1 << 31) return CC_ERR_INVALID;
-        if ((uint64_t)off > src_bytes || (uint64_t)(t * H * W * 3) > src_bytes - (uint64_t)off) return CC_ERR_INVALID;
+        const int64_t frame = yuv ? cc_px::yuv420_frame_bytes(H, W) : H * W * 3;
+        if ((uint64_t)off > src_bytes || (uint64_t)(t * frame) > src_bytes - (uint64_t)off) return CC_ERR_INVALID;
     }
     return CC_OK;
 }
 
-bool u8_format(int fmt) { return fmt == CC_FRAMES_U8_CHW || fmt == CC_FRAMES_U8_HWC; }
+// the launches of cc_resize_crop_u8 / cc_resize_crop_yuv420_u8 once the source is known to be sound
+template <bool YUV>
+int resize_crop_launch(const void* src, const PixelSource& sv, int32_t F, int32_t H, int32_t W, const void* plan_dev, int32_t n_px,
+                       int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
+    Geometry g;
+    const int rc = geometry(H, W, n_px, resize, kMaxKsize, &g);
+    if (rc != CC_OK) return rc;
+    const int nrows = g.row1 - g.row0;
+    const int tiles_x = (n_px + kTileX - 1) / kTileX;
+    const int tiles_mid = (nrows + kTileY - 1) / kTileY, tiles_out = (n_px + kTileY - 1) / kTileY;
+    if ((int64_t)F * tiles_x * (tiles_mid > tiles_out ? tiles_mid : tiles_out) > 0x7fffffffLL) return CC_ERR_UNSUPPORTED;
+    size_t need = 0;                                // (cc_resize_crop_workspace_bytes)
+    if (g.ksize_h && g.ksize_v) need = (size_t)F * 3 * (size_t)nrows * (size_t)n_px;
+    if (need && (!ws || ws_bytes < need)) return CC_ERR_WORKSPACE;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint8_t* in = static_cast<const uint8_t*>(src);
+    uint8_t* out = static_cast<uint8_t*>(dst);
+    const int32_t* plan = static_cast<const int32_t*>(plan_dev);
+    const View dv = view_of(dst_fmt, n_px, n_px);
+    const PlanKey key{H, W, n_px, resize};
+    const dim3 block(kTileX, kTileY);
+    if (!g.ksize_h && !g.ksize_v) {
+        crop_u8_kernel<YUV><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, g.top, g.left, out, dv, n_px, n_px,
+                                                                                    tiles_x, tiles_out);
+        CC_LAUNCH_CHECK();
+        return CC_OK;
+    }
+    if (g.ksize_h && !g.ksize_v) {                  // rows keep their size: the horizontal pass writes the window's rows
+        resample_u8_kernel<false, YUV><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, g.top, 0, plan, key, out,
+                                                                                               dv, n_px, tiles_x, tiles_out);
+        CC_LAUNCH_CHECK();
+        return CC_OK;
+    }
+    if (!g.ksize_h) {                               // columns keep their size: the vertical pass reads the source from `left`
+        resample_u8_kernel<true, YUV><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, 0, g.left, plan, key, out,
+                                                                                              dv, n_px, tiles_x, tiles_out);
+        CC_LAUNCH_CHECK();
+        return CC_OK;
+    }
+    // both: the horizontal result of source rows [row0, row1), rounded to bytes, planar [F, 3, nrows, n_px] in the workspace
+    uint8_t* mid = static_cast<uint8_t*>(ws);
+    const View mv = view_of(CC_FRAMES_U8_CHW, nrows, n_px);
+    resample_u8_kernel<false, YUV><<<(unsigned)(F * tiles_x * tiles_mid), block, 0, st>>>(in, sv, g.row0, 0, plan, key, mid, mv,
+                                                                                           nrows, tiles_x, tiles_mid);
+    CC_LAUNCH_CHECK();
+    resample_u8_kernel<true, false><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(
+        mid, rgb_source(CC_FRAMES_U8_CHW, nrows, n_px), -g.row0, 0, plan, key, out, dv, n_px, tiles_x, tiles_out);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
 
 }  // namespace
 
@@ -382,49 +445,55 @@ size_t cc_resize_crop_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t n
 int cc_resize_crop_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_t W, const void* plan_dev, int32_t n_px,
                       int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
     if (!src || !dst || !plan_dev || F <= 0 || !u8_format(fmt) || !u8_format(dst_fmt)) return CC_ERR_INVALID;
-    Geometry g;
-    const int rc = geometry(H, W, n_px, resize, kMaxKsize, &g);
+    return resize_crop_launch<false>(src, rgb_source(fmt, H, W), F, H, W, plan_dev, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
+}
+
+int cc_resize_crop_yuv420_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H, int32_t W,
+                             const void* plan_dev, int32_t n_px, int32_t resize, void* dst, int32_t dst_fmt, void* ws,
+                             size_t ws_bytes, void* stream) {
+    if (!src || !dst || !plan_dev || !layout || F <= 0 || !u8_format(dst_fmt)) return CC_ERR_INVALID;
+    PixelSource sv;
+    const int rc = cc_px::yuv420_source(layout, src_bytes, F, H, W, &sv);
     if (rc != CC_OK) return rc;
-    const int nrows = g.row1 - g.row0;
-    const int tiles_x = (n_px + kTileX - 1) / kTileX;
-    const int tiles_mid = (nrows + kTileY - 1) / kTileY, tiles_out = (n_px + kTileY - 1) / kTileY;
-    if ((int64_t)F * tiles_x * (tiles_mid > tiles_out ? tiles_mid : tiles_out) > 0x7fffffffLL) return CC_ERR_UNSUPPORTED;
-    const size_t need = cc_resize_crop_workspace_bytes(F, H, W, n_px, resize);
-    if (need && (!ws || ws_bytes < need)) return CC_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const uint8_t* in = static_cast<const uint8_t*>(src);
-    uint8_t* out = static_cast<uint8_t*>(dst);
-    const int32_t* plan = static_cast<const int32_t*>(plan_dev);
-    const View sv = view_of(fmt, H, W), dv = view_of(dst_fmt, n_px, n_px);
-    const PlanKey key{H, W, n_px, resize};
-    const dim3 block(kTileX, kTileY);
-    if (!g.ksize_h && !g.ksize_v) {
-        crop_u8_kernel<<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, g.top, g.left, out, dv, n_px, tiles_x,
-                                                                               tiles_out);
-        CC_LAUNCH_CHECK();
-        return CC_OK;
-    }
-    if (g.ksize_h && !g.ksize_v) {                  // rows keep their size: the horizontal pass writes the window's rows
-        resample_u8_kernel<false><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, 0, g.top, plan, key, out, dv,
-                                                                                          n_px, tiles_x, tiles_out);
-        CC_LAUNCH_CHECK();
-        return CC_OK;
-    }
-    if (!g.ksize_h) {                               // columns keep their size: the vertical pass reads the source from `left`
-        resample_u8_kernel<true><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, (int64_t)g.left * sv.sx, 0,
-                                                                                         plan, key, out, dv, n_px, tiles_x,
-                                                                                         tiles_out);
-        CC_LAUNCH_CHECK();
-        return CC_OK;
-    }
-    // both: the horizontal result of source rows [row0, row1), rounded to bytes, planar [F, 3, nrows, n_px] in the workspace
-    uint8_t* mid = static_cast<uint8_t*>(ws);
-    const View mv = view_of(CC_FRAMES_U8_CHW, nrows, n_px);
-    resample_u8_kernel<false><<<(unsigned)(F * tiles_x * tiles_mid), block, 0, st>>>(in, sv, 0, g.row0, plan, key, mid, mv,
-                                                                                      nrows, tiles_x, tiles_mid);
-    CC_LAUNCH_CHECK();
-    resample_u8_kernel<true><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(mid, mv, -(int64_t)g.row0 * mv.sy, 0, plan,
-                                                                                     key, out, dv, n_px, tiles_x, tiles_out);
+    return resize_crop_launch<true>(src, sv, F, H, W, plan_dev, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
+}
+
+int cc_yuv_coefficients(int32_t matrix, int32_t range, int32_t* out5) {
+    YuvCoef k;
+    if (!out5 || !cc_px::yuv_coefficients(matrix, range, &k)) return CC_ERR_INVALID;
+    const int32_t v[5] = {k.cy, k.crv, k.cgu, k.cgv, k.cbu};
+    for (int i = 0; i < 5; ++i) out5[i] = v[i];
+    return CC_OK;
+}
+
+size_t cc_yuv420_layout_tight(int32_t kind, int32_t H, int32_t W, int32_t matrix, int32_t range, cc_yuv420_layout* out) {
+    YuvCoef k;
+    if (!out || (kind != CC_YUV420_I420 && kind != CC_YUV420_NV12) || !cc_px::yuv_coefficients(matrix, range, &k) || H < 1 ||
+        W < 1 || H > 8192 || W > 8192)
+        return 0;
+    const PixelSource s = cc_px::yuv420_tight_source(kind, H, W, k);
+    out->frame_stride = s.sf;
+    out->y_pitch = s.sy;
+    out->u_offset = s.u_off;
+    out->v_offset = s.v_off;
+    out->c_pitch = s.c_pitch;
+    out->c_step = s.c_step;
+    out->matrix = matrix;
+    out->range = range;
+    return (size_t)s.sf;
+}
+
+int cc_yuv420_to_rgb_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H, int32_t W,
+                        void* dst, int32_t dst_fmt, void* stream) {
+    if (!src || !dst || !layout || F <= 0 || !u8_format(dst_fmt)) return CC_ERR_INVALID;
+    PixelSource sv;
+    const int rc = cc_px::yuv420_source(layout, src_bytes, F, H, W, &sv);
+    if (rc != CC_OK) return rc;
+    const int tiles_x = (W + kTileX - 1) / kTileX, tiles_y = (H + kTileY - 1) / kTileY;
+    if ((int64_t)F * tiles_x * tiles_y > 0x7fffffffLL) return CC_ERR_UNSUPPORTED;
+    // the crop kernel with the whole frame as its window
+    crop_u8_kernel<true><<<(unsigned)(F * tiles_x * tiles_y), dim3(kTileX, kTileY), 0, static_cast<hipStream_t>(stream)>>>(
+        static_cast<const uint8_t*>(src), sv, 0, 0, static_cast<uint8_t*>(dst), view_of(dst_fmt, H, W), H, W, tiles_x, tiles_y);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }
@@ -445,13 +514,16 @@ size_t cc_collate_resize_crop_workspace_bytes(const int64_t* clips_host, int32_t
     return frame * (size_t)n_out;
 }
 
-int cc_collate_resize_crop_u8(const void* src, size_t src_bytes, int32_t fmt, const int64_t* clips_host, int32_t n_clips,
-                              const int64_t* rows_dev, int32_t n_out, const int32_t* plans_dev, size_t plans_ints, int32_t n_px,
-                              int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
-    if (!src || !dst || !rows_dev || !plans_dev || n_out <= 0 || !u8_format(fmt) || !u8_format(dst_fmt) ||
-        plans_ints < CC_RESIZE_PLAN_HEADER)
-        return CC_ERR_INVALID;
-    int rc = collate_check_clips(clips_host, n_clips, src_bytes);
+}  // extern "C"
+
+namespace {
+
+// the checks and launches of cc_collate_resize_crop_u8 / _yuv420_u8; fmt: the RGB format code or the tight 4:2:0 kind
+template <bool YUV>
+int collate_launch(const void* src, size_t src_bytes, int32_t fmt, const YuvCoef& k, const int64_t* clips_host, int32_t n_clips,
+                   const int64_t* rows_dev, int32_t n_out, const int32_t* plans_dev, size_t plans_ints, int32_t n_px,
+                   int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
+    int rc = collate_check_clips(clips_host, n_clips, src_bytes, YUV);
     if (rc != CC_OK) return rc;
     int max_mid = 0;                                // rows of the largest horizontal result; 0: no clip runs both passes
     for (int i = 0; i < n_clips; ++i) {
@@ -475,17 +547,44 @@ int cc_collate_resize_crop_u8(const void* src, size_t src_bytes, int32_t fmt, co
     a.resize = resize;
     a.fmt = fmt;
     a.dst_fmt = dst_fmt;
+    a.k = k;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 block(kTileX, kTileY);
     const int tiles_x = (n_px + kTileX - 1) / kTileX, tiles_out = (n_px + kTileY - 1) / kTileY;
     if (max_mid) {
         const int tiles_mid = (max_mid + kTileY - 1) / kTileY;
-        collate_resample_u8_kernel<false><<<dim3(tiles_x, tiles_mid, collate_planes(n_out, tiles_x, tiles_mid)), block, 0, st>>>(a);
+        collate_resample_u8_kernel<false, YUV><<<dim3(tiles_x, tiles_mid, collate_planes(n_out, tiles_x, tiles_mid)), block, 0, st>>>(a);
         CC_LAUNCH_CHECK();
     }
-    collate_resample_u8_kernel<true><<<dim3(tiles_x, tiles_out, collate_planes(n_out, tiles_x, tiles_out)), block, 0, st>>>(a);
+    collate_resample_u8_kernel<true, YUV><<<dim3(tiles_x, tiles_out, collate_planes(n_out, tiles_x, tiles_out)), block, 0, st>>>(a);
     CC_LAUNCH_CHECK();
     return CC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int cc_collate_resize_crop_u8(const void* src, size_t src_bytes, int32_t fmt, const int64_t* clips_host, int32_t n_clips,
+                              const int64_t* rows_dev, int32_t n_out, const int32_t* plans_dev, size_t plans_ints, int32_t n_px,
+                              int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
+    if (!src || !dst || !rows_dev || !plans_dev || n_out <= 0 || !u8_format(fmt) || !u8_format(dst_fmt) ||
+        plans_ints < CC_RESIZE_PLAN_HEADER)
+        return CC_ERR_INVALID;
+    return collate_launch<false>(src, src_bytes, fmt, YuvCoef{}, clips_host, n_clips, rows_dev, n_out, plans_dev, plans_ints, n_px,
+                                 resize, dst, dst_fmt, ws, ws_bytes, stream);
+}
+
+int cc_collate_resize_crop_yuv420_u8(const void* src, size_t src_bytes, int32_t kind, int32_t matrix, int32_t range,
+                                     const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out,
+                                     const int32_t* plans_dev, size_t plans_ints, int32_t n_px, int32_t resize, void* dst,
+                                     int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
+    YuvCoef k;
+    if (!src || !dst || !rows_dev || !plans_dev || n_out <= 0 || (kind != CC_YUV420_I420 && kind != CC_YUV420_NV12) ||
+        !cc_px::yuv_coefficients(matrix, range, &k) || !u8_format(dst_fmt) || plans_ints < CC_RESIZE_PLAN_HEADER)
+        return CC_ERR_INVALID;
+    return collate_launch<true>(src, src_bytes, kind, k, clips_host, n_clips, rows_dev, n_out, plans_dev, plans_ints, n_px, resize,
+                                dst, dst_fmt, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -89,7 +89,8 @@ class DeviceFeeder:
     def _video_index(self, batch):
         if self.video_index is not None:
             return self.video_index
-        found = [i for i, t in enumerate(batch) if isinstance(t, PackedClips) or (t.dtype == torch.uint8 and t.dim() in (4, 6))]
+        dims = getattr(self.frame_transform, "frame_dims", (4, 6))          # (a YUV transform's frames are [..., 3H/2, W])
+        found = [i for i, t in enumerate(batch) if isinstance(t, PackedClips) or (t.dtype == torch.uint8 and t.dim() in dims)]
         if len(found) != 1:
             raise ValueError("DeviceFeeder(frame_transform=...): the batch has %d uint8 frame tensors - pass video_index"
                              % len(found))

@@ -19,7 +19,13 @@ on every clip of the batch, zero padding included, in at most two launches):
     packed = pack_clips([clip_0, clip_1, ...])                           # uint8 [t_i, H_i, W_i, 3] each, t_i <= T
     video = ClipCollate(224, max_frames=12)(packed.to(device))           # uint8 [B, 1, T, 224, 224, 3]
     out = model(ids, seg, mask, video, packed.video_mask(12))
+
+All of the above start from RGB bytes.  Decoders produce 8-bit YUV 4:2:0; the ``Yuv*`` counterparts at the end of this file take
+the planes as decoded ([..., 3H/2, W], PyAV's ``to_ndarray()`` of yuv420p / nv12) and convert inside the first resampling pass:
+
+    video = YuvFrameTransform(224, layout="nv12", matrix="bt709")(video_yuv)     # uint8 [B, 1, T, 3H/2, W] -> [B, 1, T, 224, 224, 3]
 """
+import ctypes
 import math
 import random
 
@@ -375,11 +381,16 @@ class ClipCollate:
                              % (b, s, index[b, s], b, t[b] - 1))
         return index
 
+    @staticmethod
+    def _frame_bytes(tab):
+        """Bytes of one frame of every clip of the host table."""
+        return tab[:, 2] * tab[:, 3] * 3
+
     def _rows(self, packed, index, width):
         """The first four columns of the frame table: kind, byte offset of the source frame, H, W."""
         tab = packed.table.numpy()
         rows = np.zeros((index.shape[0], index.shape[1], width), dtype=np.int64)
-        frame = tab[:, 2] * tab[:, 3] * 3
+        frame = self._frame_bytes(tab)
         rows[:, :, 0] = index >= 0
         rows[:, :, 1] = tab[:, :1] + np.maximum(index, 0) * frame[:, None]
         rows[:, :, 2] = tab[:, 2:3]
@@ -421,6 +432,9 @@ class ClipCollate:
         host[head.size:].view(np.int32)[:at] = np.concatenate(parts)
         dev = self._upload(host, packed.device)
         rows_dev, plans_dev = dev[:head.size].view(B * S, T.COLLATE_ROW), dev[head.size:].view(torch.int32)
+        return self._eval_op(packed, rows_dev, plans_dev, clips, out)
+
+    def _eval_op(self, packed, rows_dev, plans_dev, clips, out):
         if out is None:
             return torch.ops.centerclip.collate_clips(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
                                                       packed.chw).view(self.output_shape(packed))
@@ -455,11 +469,13 @@ class ClipCollate:
         rows[:, :, 4:9] = boxes[:, None, :]
         rows[:, :, 9] = self.train.interp
         dev = self._upload(rows.reshape(-1), packed.device).view(B * S, T.COLLATE_BOX_ROW)
-        clips = tab.reshape(-1).tolist()
+        return self._train_op(packed, dev, tab.reshape(-1).tolist(), out)
+
+    def _train_op(self, packed, rows_dev, clips, out):
         if out is None:
-            return torch.ops.centerclip.collate_clips_crop_flip(packed.data, dev, clips, self.n_px,
+            return torch.ops.centerclip.collate_clips_crop_flip(packed.data, rows_dev, clips, self.n_px,
                                                                 packed.chw).view(self.output_shape(packed))
-        torch.ops.centerclip.collate_clips_crop_flip_out(packed.data, dev, clips, self.n_px, packed.chw, out)
+        torch.ops.centerclip.collate_clips_crop_flip_out(packed.data, rows_dev, clips, self.n_px, packed.chw, out)
         return out
 
     def __call__(self, packed, index=None, out=None):
@@ -470,4 +486,205 @@ class ClipCollate:
         return self.apply(packed, self.sample(packed), index=index, out=out)
 
 
-__all__ = ["resize_center_crop", "FrameTransform", "TrainFrameTransform", "PackedClips", "pack_clips", "ClipCollate"]
+# ------------------------------------------------------------------------------------------ YUV 4:2:0 sources
+# What decoders produce before any colour conversion ("YUV 4:2:0 sources").  At this level frames are uint8
+# [..., 3H/2, W] with H and W even and the layout tight - exactly PyAV's ``frame.to_ndarray()`` of a ``yuv420p`` ("i420": H rows
+# of Y, then the U plane and the V plane, each H/2 x W/2, as H/4 + H/4 rows) or ``nv12`` (H rows of Y, then H/2 rows of
+# interleaved UV) frame; a pitched or odd-sized surface goes through the ops (torch_ops.yuv420_*) with an explicit layout.
+def yuv_coefficients(matrix="bt601", full_range=False):
+    """-> (CY, CRV, CGU, CGV, CBU), the 16-bit fixed-point coefficients of the conversion (cc_yuv_coefficients)."""
+    if matrix not in T.YUV_MATRICES:
+        raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+    out = (ctypes.c_int32 * 5)()
+    L.check(L.lib().cc_yuv_coefficients(T.YUV_MATRICES[matrix], int(bool(full_range)), out), "cc_yuv_coefficients")
+    return tuple(int(v) for v in out)
+
+
+def _yuv_geometry(shape):
+    """[..., 3H/2, W] with at least one leading dimension -> (leading dimensions, H, W)."""
+    if len(shape) < 3 or shape[-2] % 3 or shape[-1] % 2 or shape[-2] < 3 or shape[-1] < 2:
+        raise ValueError("4:2:0 frames must be [..., 3H/2, W] with H and W even and a leading frame dimension (a decoder's "
+                         "to_ndarray() of yuv420p / nv12), got %s" % (tuple(shape),))
+    return tuple(shape[:-2]), int(shape[-2]) // 3 * 2, int(shape[-1])
+
+
+class _YuvSource:
+    """What the YUV transforms share: the colour description, the checks, the tight layout of a frame size."""
+
+    def _init_yuv(self, layout, matrix, full_range):
+        if layout not in T.YUV_KINDS or matrix not in T.YUV_MATRICES:
+            raise ValueError("layout must be 'i420' or 'nv12' and matrix 'bt601' or 'bt709', got %r, %r" % (layout, matrix))
+        self.layout, self.matrix, self.full_range = layout, matrix, bool(full_range)
+
+    def _source(self, frames):
+        """-> (leading dimensions, F, H, W, the eight layout integers) of device frames [..., 3H/2, W]"""
+        L.require_device(frames)
+        if frames.dtype != torch.uint8:
+            raise ValueError("the frame transform takes the decoder's uint8 planes, got %s" % frames.dtype)
+        lead, H, W = _yuv_geometry(frames.shape)
+        return lead, math.prod(lead), H, W, T.yuv420_tight_layout(self.layout, H, W, self.matrix, self.full_range)
+
+    def output_shape(self, shape):
+        lead, _, _ = _yuv_geometry(shape)
+        return lead + (self.n_px, self.n_px, 3)
+
+
+def yuv420_to_rgb(frames, layout="i420", matrix="bt601", full_range=False):
+    """uint8 [..., 3H/2, W] 4:2:0 frames -> uint8 [..., H, W, 3] RGB (torch.ops.centerclip.yuv420_to_rgb): the fixed integer
+    conversion of the header, chroma replicated.  The fused transforms below never store this image; it is the stand-alone form
+    and what they are defined against."""
+    src = _YuvSource()
+    src._init_yuv(layout, matrix, full_range)
+    lead, F, H, W, lay = src._source(frames)
+    return torch.ops.centerclip.yuv420_to_rgb(frames, F, H, W, lay, False).view(lead + (H, W, 3))
+
+
+class YuvFrameTransform(_YuvSource):
+    """``FrameTransform`` on 4:2:0 frames as decoded: uint8 [..., 3H/2, W] -> uint8 [..., n_px, n_px, 3], bit for bit
+    ``FrameTransform(n_px, resize)(yuv420_to_rgb(frames, ...))`` with the conversion inside the first resampling pass - half the
+    bytes cross PCIe and are read, and no ``to_rgb()`` runs on a CPU core.  The same protocol (eval_epoch, train_epoch,
+    DeviceFeeder); nothing passes through: a frame of the model's size is still converted."""
+    frame_dims = (3, 5)                              # what DeviceFeeder recognises as this transform's video: [F, ..] / [B, 1, T, ..]
+
+    def __init__(self, n_px=224, resize=True, layout="i420", matrix="bt601", full_range=False):
+        self.n_px, self.resize = int(n_px), bool(resize)
+        self._init_yuv(layout, matrix, full_range)
+
+    def passes_through(self, shape):
+        return False
+
+    def __call__(self, frames, out=None):
+        lead, F, H, W, lay = self._source(frames)
+        T.resize_plan(H, W, self.n_px, self.resize, frames.device)
+        if out is None:
+            return torch.ops.centerclip.resize_center_crop_yuv420(frames, F, H, W, lay, self.n_px, self.resize,
+                                                                  False).view(lead + (self.n_px, self.n_px, 3))
+        torch.ops.centerclip.resize_center_crop_yuv420_out(frames, F, H, W, lay, self.n_px, self.resize, False, out)
+        return out
+
+
+class YuvTrainFrameTransform(_YuvSource, TrainFrameTransform):
+    """``TrainFrameTransform`` on 4:2:0 frames as decoded: the same boxes from the same draws (``sample`` is that class's), applied
+    by one launch that converts its taps - bit for bit ``TrainFrameTransform.apply(yuv420_to_rgb(frames, ...), boxes)``."""
+    frame_dims = (3, 5)
+
+    def __init__(self, n_px=224, layout="i420", matrix="bt601", full_range=False, **train):
+        TrainFrameTransform.__init__(self, n_px, **train)
+        self._init_yuv(layout, matrix, full_range)
+
+    def apply(self, frames, boxes, out=None, frames_per_clip=None):
+        lead, F, H, W, lay = self._source(frames)
+        fpc = self._clips(lead + (H, W, 3))[1] if frames_per_clip is None else int(frames_per_clip)
+        if not boxes.is_cuda:
+            if torch.cuda.is_current_stream_capturing():
+                raise L.CenterClipHipError("YuvTrainFrameTransform.apply: a host box table cannot be uploaded while the stream is "
+                                           "being captured - pass a device tensor and refill it between replays")
+            boxes = boxes.to(device=frames.device, dtype=torch.int32)
+        if out is None:
+            return torch.ops.centerclip.resized_crop_flip_yuv420(frames, F, H, W, lay, boxes, self.n_px, fpc, self.interp,
+                                                                 False).view(lead + (self.n_px, self.n_px, 3))
+        torch.ops.centerclip.resized_crop_flip_yuv420_out(frames, F, H, W, lay, boxes, self.n_px, fpc, self.interp, False, out)
+        return out
+
+    def __call__(self, frames, out=None):
+        lead, _, H, W, _ = self._source(frames)
+        return self.apply(frames, self.sample(self._clips(lead + (H, W, 3))[0], H, W), out=out)
+
+
+class PackedYuvClips(PackedClips):
+    """``PackedClips`` of tight 4:2:0 clips: ``table`` rows (byte offset, frames t, H, W) with a frame of 3 H W / 2 bytes;
+    ``layout`` "i420" / "nv12".  Built by ``pack_yuv_clips``."""
+
+    def __init__(self, data, table, layout):
+        PackedClips.__init__(self, data, table, False)
+        self.layout = layout
+
+    def to(self, device=None, non_blocking=False, **_):
+        return PackedYuvClips(self.data.to(device=device, non_blocking=non_blocking), self.table, self.layout)
+
+    def pin_memory(self):
+        return self if self.data.is_pinned() else PackedYuvClips(self.data.pin_memory(), self.table, self.layout)
+
+    def clip(self, b):
+        """Clip b as a view of the bytes: [t, 3H/2, W]."""
+        off, t, H, W = (int(v) for v in self.table[b])
+        return self.data[off:off + t * H * W * 3 // 2].view(t, H * 3 // 2, W)
+
+    def __getitem__(self, rows):
+        return pack_yuv_clips([self.clip(int(b)) for b in torch.as_tensor(rows).reshape(-1).tolist()], self.layout)
+
+
+def pack_yuv_clips(clips, layout="i420"):
+    """``pack_clips`` for 4:2:0 clips: a list of B uint8 arrays / tensors [t_i, 3H_i/2, W_i] (H_i, W_i even), all "i420" or all
+    "nv12" -> ``PackedYuvClips`` (a ``PackedClips``: one pinned byte buffer + the host table), for ``YuvClipCollate``."""
+    if layout not in T.YUV_KINDS:
+        raise ValueError("pack_yuv_clips: layout must be 'i420' or 'nv12', got %r" % (layout,))
+    clips = [torch.from_numpy(np.ascontiguousarray(c)) if isinstance(c, np.ndarray) else c for c in clips]
+    if not clips:
+        raise ValueError("pack_yuv_clips: no clips")
+    rows, off = [], 0
+    for i, c in enumerate(clips):
+        if not isinstance(c, torch.Tensor) or c.dtype != torch.uint8 or c.dim() != 3 or c.shape[0] < 1:
+            raise ValueError("pack_yuv_clips: clip %d is not a uint8 array or tensor [t >= 1, 3H/2, W]" % i)
+        _, H, W = _yuv_geometry(c.shape)
+        rows.append((off, int(c.shape[0]), H, W))
+        off += c.numel()
+    table = torch.tensor(rows, dtype=torch.int64)
+    if any(c.is_cuda for c in clips):
+        if not all(c.is_cuda for c in clips):
+            raise ValueError("pack_yuv_clips: host and device clips in one batch")
+        return PackedYuvClips(torch.cat([c.contiguous().view(-1) for c in clips]), table, layout)
+    pin = torch.cuda.is_available() and torch.utils.data.get_worker_info() is None
+    data = torch.empty(off, dtype=torch.uint8, pin_memory=pin)
+    for (o, _, _, _), c in zip(rows, clips):
+        data[o:o + c.numel()].view(c.shape).copy_(c)
+    return PackedYuvClips(data, table, layout)
+
+
+class YuvClipCollate(_YuvSource, ClipCollate):
+    """``ClipCollate`` on a ``PackedYuvClips``: the same tables, checks and launch bound, every clip's taps converted on the way
+    in - each output frame bit for bit ``YuvFrameTransform`` / ``YuvTrainFrameTransform.apply`` of its clip.  ``train``: a
+    ``TrainFrameTransform`` (or its Yuv subclass - only its box drawing and interpolation are used).  -> uint8
+    [B, 1, T, n_px, n_px, 3]."""
+
+    def __init__(self, n_px=224, max_frames=12, resize=True, train=None, layout="i420", matrix="bt601", full_range=False):
+        ClipCollate.__init__(self, n_px, max_frames, resize, train)
+        self._init_yuv(layout, matrix, full_range)
+
+    def output_shape(self, packed):
+        return ClipCollate.output_shape(self, packed)
+
+    @staticmethod
+    def _frame_bytes(tab):
+        return tab[:, 2] * tab[:, 3] * 3 // 2
+
+    def _check(self, packed, out):
+        ClipCollate._check(self, packed, out)
+        if getattr(packed, "layout", self.layout) != self.layout:
+            raise ValueError("YuvClipCollate(layout=%r) on clips packed as %r" % (self.layout, packed.layout))
+        tab = packed.table.numpy()
+        if ((tab[:, 2] | tab[:, 3]) & 1).any():
+            raise ValueError("YuvClipCollate: packed 4:2:0 clips have even H and W, got %s" % tab[:, 2:].tolist())
+
+    def _kind(self):
+        return T.YUV_KINDS[self.layout], T.YUV_MATRICES[self.matrix], self.full_range
+
+    def _eval_op(self, packed, rows_dev, plans_dev, clips, out):
+        if out is None:
+            return torch.ops.centerclip.collate_clips_yuv420(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
+                                                             *self._kind(), False).view(self.output_shape(packed))
+        torch.ops.centerclip.collate_clips_yuv420_out(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
+                                                      *self._kind(), False, out)
+        return out
+
+    def _train_op(self, packed, rows_dev, clips, out):
+        if out is None:
+            return torch.ops.centerclip.collate_clips_crop_flip_yuv420(packed.data, rows_dev, clips, self.n_px, *self._kind(),
+                                                                       False).view(self.output_shape(packed))
+        torch.ops.centerclip.collate_clips_crop_flip_yuv420_out(packed.data, rows_dev, clips, self.n_px, *self._kind(), False, out)
+        return out
+
+
+__all__ = ["resize_center_crop", "FrameTransform", "TrainFrameTransform", "PackedClips", "pack_clips", "ClipCollate",
+           "yuv_coefficients", "yuv420_to_rgb", "YuvFrameTransform", "YuvTrainFrameTransform", "PackedYuvClips", "pack_yuv_clips",
+           "YuvClipCollate"]

@@ -1184,6 +1184,262 @@ def _(src, rows, clips, n_px, chw, out):
     return None
 
 
+# ---- YUV 4:2:0 sources (include/centerclip_hip.h, "YUV 4:2:0 sources").  The ops take the source as ANY contiguous uint8 tensor -
+# its bytes are what the layout's offsets count in - with the geometry spelled out: F frames of H x W and ``layout``, the eight
+# integers of cc_yuv420_layout (frame_stride, y_pitch, u_offset, v_offset, c_pitch, c_step, matrix, range).  preprocess.py
+# builds the tight layouts of a decoder's [..., 3H/2, W] arrays; a pitched or odd-sized surface is described by hand.
+YUV_KINDS = {"i420": 0, "nv12": 1}                  # CC_YUV420_I420 / CC_YUV420_NV12
+YUV_MATRICES = {"bt601": 0, "bt709": 1}             # CC_YUV_BT601 / CC_YUV_BT709
+
+
+def yuv420_tight_layout(kind, H, W, matrix, full_range):
+    """-> the eight integers of cc_yuv420_layout_tight for tight ``kind`` ("i420" / "nv12") frames of H x W one behind the
+    other; [0] is the bytes of a frame, H W + 2 ceil(H / 2) ceil(W / 2)."""
+    lay = L.Yuv420Layout()
+    if kind not in YUV_KINDS or matrix not in YUV_MATRICES:
+        raise ValueError("a 4:2:0 layout is 'i420' or 'nv12' and a matrix 'bt601' or 'bt709', got %r, %r" % (kind, matrix))
+    if not L.lib().cc_yuv420_layout_tight(YUV_KINDS[kind], int(H), int(W), YUV_MATRICES[matrix], int(bool(full_range)),
+                                          ctypes.byref(lay)):
+        raise ValueError("no tight %s layout for %s x %s frames (1 .. 8192)" % (kind, H, W))
+    return [getattr(lay, name) for name, _ in L.Yuv420Layout._fields_]
+
+
+def _yuv_source(name, src, F, H, W, layout):
+    """The checks the real and the fake kernels of the YUV ops share."""
+    if src.dtype != torch.uint8:
+        raise ValueError("%s takes the decoder's uint8 planes, got %s" % (name, src.dtype))
+    if len(layout) != 8:
+        raise ValueError("%s: layout is the eight integers of cc_yuv420_layout (frame_stride, y_pitch, u_offset, v_offset, c_pitch, "
+                         "c_step, matrix, range), got %d values" % (name, len(layout)))
+    if F < 0 or H < 1 or W < 1:
+        raise ValueError("%s: F >= 0 frames of H, W >= 1, got %d x %d x %d" % (name, F, H, W))
+
+
+def _yuv_layout(layout):
+    return L.Yuv420Layout(*(int(v) for v in layout))
+
+
+def _yuv_shape(F, n_rows, n_cols, chw):
+    return (F, 3, n_rows, n_cols) if chw else (F, n_rows, n_cols, 3)
+
+
+def _yuv_out_check(name, out, shape):
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() < 3 or tuple(out.shape[-3:]) != shape[1:] \
+            or out.numel() != math.prod(shape):
+        raise ValueError("%s: out must be contiguous uint8 frames [..., %s] with %d frames in all, got %s %s"
+                         % (name, ", ".join(map(str, shape[1:])), shape[0], out.dtype, tuple(out.shape)))
+
+
+@custom_op(NS + "::yuv420_to_rgb", mutates_args=(), device_types="cuda")
+def yuv420_to_rgb(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], chw: bool) -> torch.Tensor:
+    """The conversion alone (cc_yuv420_to_rgb_u8, one launch): F frames of H x W 8-bit 4:2:0 in ``src`` as ``layout`` describes
+    -> uint8 [F, H, W, 3] ([F, 3, H, W] with chw), the fixed integer conversion of the header, chroma replicated."""
+    _yuv_source("yuv420_to_rgb", src, F, H, W, layout)
+    L.require_device(src)
+    out = _e(*_yuv_shape(F, H, W, chw), like=src, dtype=torch.uint8)
+    if F:
+        src = src.contiguous()
+        L.check(L.lib().cc_yuv420_to_rgb_u8(L.ptr(src), src.numel(), ctypes.byref(_yuv_layout(layout)), F, H, W, L.ptr(out),
+                                            1 if chw else 2, _st(src)), "cc_yuv420_to_rgb_u8")
+    return out
+
+
+@yuv420_to_rgb.register_fake
+def _(src, F, H, W, layout, chw):
+    _yuv_source("yuv420_to_rgb", src, F, H, W, layout)
+    return src.new_empty(_yuv_shape(F, H, W, chw), dtype=torch.uint8)
+
+
+def _resize_crop_yuv420_into(src, F, H, W, layout, n_px, resize, chw, out):
+    _yuv_source("resize_center_crop_yuv420", src, F, H, W, layout)
+    _yuv_out_check("resize_center_crop_yuv420", out, _yuv_shape(F, n_px, n_px, chw))
+    L.require_device(src, out)
+    if F == 0:
+        return
+    src = src.contiguous()
+    lib = L.lib()
+    plan = resize_plan(H, W, n_px, resize, src.device)
+    nws = lib.cc_resize_crop_workspace_bytes(F, H, W, int(n_px), int(resize))
+    ws = L.workspace(nws, src.device) if nws else None
+    L.check(lib.cc_resize_crop_yuv420_u8(L.ptr(src), src.numel(), ctypes.byref(_yuv_layout(layout)), F, H, W, L.ptr(plan), int(n_px),
+                                         int(resize), L.ptr(out), 1 if chw else 2, L.ptr(ws),
+                                         ws.numel() if ws is not None else 0, _st(src)), "cc_resize_crop_yuv420_u8")
+
+
+@custom_op(NS + "::resize_center_crop_yuv420", mutates_args=(), device_types="cuda")
+def resize_center_crop_yuv420(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], n_px: int, resize: bool,
+                              chw: bool) -> torch.Tensor:
+    """resize_center_crop on a 4:2:0 source (cc_resize_crop_yuv420_u8): -> uint8 [F, n_px, n_px, 3] ([F, 3, n_px, n_px] with chw),
+    bit for bit resize_center_crop(yuv420_to_rgb(src)); the first pass converts its taps, no RGB frame of H x W is stored."""
+    out = _e(*_yuv_shape(F, n_px, n_px, chw), like=src, dtype=torch.uint8)
+    _resize_crop_yuv420_into(src, F, H, W, layout, n_px, resize, chw, out)
+    return out
+
+
+@resize_center_crop_yuv420.register_fake
+def _(src, F, H, W, layout, n_px, resize, chw):
+    _yuv_source("resize_center_crop_yuv420", src, F, H, W, layout)
+    return src.new_empty(_yuv_shape(F, n_px, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::resize_center_crop_yuv420_out", mutates_args=("out",), device_types="cuda")
+def resize_center_crop_yuv420_out(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], n_px: int, resize: bool,
+                                  chw: bool, out: torch.Tensor) -> None:
+    """resize_center_crop_yuv420 into a buffer of the caller's."""
+    _resize_crop_yuv420_into(src, F, H, W, layout, n_px, resize, chw, out)
+
+
+@resize_center_crop_yuv420_out.register_fake
+def _(src, F, H, W, layout, n_px, resize, chw, out):
+    return None
+
+
+def _crop_flip_yuv420_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp):
+    _yuv_source("resized_crop_flip_yuv420", src, F, H, W, layout)
+    if frames_per_clip < 1 or interp not in (0, 1) or n_px < 1:
+        raise ValueError("resized_crop_flip_yuv420: frames_per_clip >= 1, n_px >= 1 and interp 0 (bilinear) / 1 (bicubic), got "
+                         "%d, %d, %d" % (frames_per_clip, n_px, interp))
+    clips = -(-F // frames_per_clip)
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (clips, 5):
+        raise ValueError("resized_crop_flip_yuv420: boxes must be int32 [%d, 5] rows (top, left, height, width, flip) for %d frames "
+                         "in clips of %d, got %s %s" % (clips, F, frames_per_clip, boxes.dtype, tuple(boxes.shape)))
+
+
+def _crop_flip_yuv420_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out):
+    _crop_flip_yuv420_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
+    _yuv_out_check("resized_crop_flip_yuv420", out, _yuv_shape(F, n_px, n_px, chw))
+    L.require_device(src, boxes, out)
+    if F == 0:
+        return
+    src, boxes = src.contiguous(), boxes.contiguous()
+    L.check(L.lib().cc_resized_crop_flip_yuv420_u8(L.ptr(src), src.numel(), ctypes.byref(_yuv_layout(layout)), F, H, W,
+                                                   int(frames_per_clip), L.ptr(boxes), int(n_px), int(interp), L.ptr(out),
+                                                   1 if chw else 2, _st(src)), "cc_resized_crop_flip_yuv420_u8")
+
+
+@custom_op(NS + "::resized_crop_flip_yuv420", mutates_args=(), device_types="cuda")
+def resized_crop_flip_yuv420(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], boxes: torch.Tensor, n_px: int,
+                             frames_per_clip: int, interp: int, chw: bool) -> torch.Tensor:
+    """resized_crop_flip on a 4:2:0 source (cc_resized_crop_flip_yuv420_u8, one launch): bit for bit
+    resized_crop_flip(yuv420_to_rgb(src), boxes, ...)."""
+    out = _e(*_yuv_shape(F, n_px, n_px, chw), like=src, dtype=torch.uint8)
+    _crop_flip_yuv420_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out)
+    return out
+
+
+@resized_crop_flip_yuv420.register_fake
+def _(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw):
+    _crop_flip_yuv420_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
+    return src.new_empty(_yuv_shape(F, n_px, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::resized_crop_flip_yuv420_out", mutates_args=("out",), device_types="cuda")
+def resized_crop_flip_yuv420_out(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], boxes: torch.Tensor, n_px: int,
+                                 frames_per_clip: int, interp: int, chw: bool, out: torch.Tensor) -> None:
+    """resized_crop_flip_yuv420 into a buffer of the caller's."""
+    _crop_flip_yuv420_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out)
+
+
+@resized_crop_flip_yuv420_out.register_fake
+def _(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out):
+    _crop_flip_yuv420_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
+    return None
+
+
+def _collate_yuv420_check(name, kind, matrix):
+    if kind not in (0, 1) or matrix not in (0, 1):
+        raise ValueError("%s: kind 0 (tight I420) / 1 (tight NV12) and matrix 0 (BT.601) / 1 (BT.709), got %d, %d" % (name, kind, matrix))
+
+
+def _collate_yuv420_into(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw, out):
+    _collate_yuv420_check("collate_clips_yuv420", kind, matrix)
+    n_out = _collate_check("collate_clips_yuv420", src, rows, clips, n_px, chw, COLLATE_ROW, out)
+    if plans.dtype != torch.int32 or plans.dim() != 1:
+        raise ValueError("collate_clips_yuv420: the plans are one 1-D int32 buffer, got %s %s" % (plans.dtype, tuple(plans.shape)))
+    L.require_device(src, rows, plans, out)
+    src, rows, plans = src.contiguous(), rows.contiguous(), plans.contiguous()
+    lib, table = L.lib(), _clips_host(clips)
+    nws = lib.cc_collate_resize_crop_workspace_bytes(table, len(clips) // 4, n_out, int(n_px), int(resize))
+    ws = L.workspace(nws, src.device) if nws else None
+    L.check(lib.cc_collate_resize_crop_yuv420_u8(L.ptr(src), src.numel(), int(kind), int(matrix), int(full_range), table,
+                                                 len(clips) // 4, L.ptr(rows), n_out, L.ptr(plans), plans.numel(), int(n_px),
+                                                 int(resize), L.ptr(out), 1 if chw else 2, L.ptr(ws), nws, _st(src)),
+            "cc_collate_resize_crop_yuv420_u8")
+
+
+@custom_op(NS + "::collate_clips_yuv420", mutates_args=(), device_types="cuda")
+def collate_clips_yuv420(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
+                         kind: int, matrix: int, full_range: bool, chw: bool) -> torch.Tensor:
+    """collate_clips on packed tight 4:2:0 frames (cc_collate_resize_crop_yuv420_u8): the same tables, byte offsets counting
+    frames of H W + 2 ceil(H / 2) ceil(W / 2) bytes; kind 0 I420 / 1 NV12; chw: the OUTPUT's layout."""
+    out = _e(*_collate_shape(_collate_check("collate_clips_yuv420", src, rows, clips, n_px, chw, COLLATE_ROW), n_px, chw), like=src,
+             dtype=torch.uint8)
+    _collate_yuv420_into(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw, out)
+    return out
+
+
+@collate_clips_yuv420.register_fake
+def _(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw):
+    _collate_yuv420_check("collate_clips_yuv420", kind, matrix)
+    n_out = _collate_check("collate_clips_yuv420", src, rows, clips, n_px, chw, COLLATE_ROW)
+    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::collate_clips_yuv420_out", mutates_args=("out",), device_types="cuda")
+def collate_clips_yuv420_out(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
+                             kind: int, matrix: int, full_range: bool, chw: bool, out: torch.Tensor) -> None:
+    """collate_clips_yuv420 into a buffer of the caller's; every frame of it is written."""
+    _collate_yuv420_into(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw, out)
+
+
+@collate_clips_yuv420_out.register_fake
+def _(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw, out):
+    _collate_yuv420_check("collate_clips_yuv420", kind, matrix)
+    _collate_check("collate_clips_yuv420", src, rows, clips, n_px, chw, COLLATE_ROW, out)
+    return None
+
+
+def _collate_crop_flip_yuv420_into(src, rows, clips, n_px, kind, matrix, full_range, chw, out):
+    _collate_yuv420_check("collate_clips_crop_flip_yuv420", kind, matrix)
+    n_out = _collate_check("collate_clips_crop_flip_yuv420", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
+    L.require_device(src, rows, out)
+    src, rows = src.contiguous(), rows.contiguous()
+    L.check(L.lib().cc_collate_crop_flip_yuv420_u8(L.ptr(src), src.numel(), int(kind), int(matrix), int(full_range),
+                                                   _clips_host(clips), len(clips) // 4, L.ptr(rows), n_out, int(n_px), L.ptr(out),
+                                                   1 if chw else 2, _st(src)), "cc_collate_crop_flip_yuv420_u8")
+
+
+@custom_op(NS + "::collate_clips_crop_flip_yuv420", mutates_args=(), device_types="cuda")
+def collate_clips_crop_flip_yuv420(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, kind: int, matrix: int,
+                                   full_range: bool, chw: bool) -> torch.Tensor:
+    """collate_clips_crop_flip on packed tight 4:2:0 frames (cc_collate_crop_flip_yuv420_u8, one launch)."""
+    out = _e(*_collate_shape(_collate_check("collate_clips_crop_flip_yuv420", src, rows, clips, n_px, chw, COLLATE_BOX_ROW), n_px,
+                             chw), like=src, dtype=torch.uint8)
+    _collate_crop_flip_yuv420_into(src, rows, clips, n_px, kind, matrix, full_range, chw, out)
+    return out
+
+
+@collate_clips_crop_flip_yuv420.register_fake
+def _(src, rows, clips, n_px, kind, matrix, full_range, chw):
+    _collate_yuv420_check("collate_clips_crop_flip_yuv420", kind, matrix)
+    n_out = _collate_check("collate_clips_crop_flip_yuv420", src, rows, clips, n_px, chw, COLLATE_BOX_ROW)
+    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::collate_clips_crop_flip_yuv420_out", mutates_args=("out",), device_types="cuda")
+def collate_clips_crop_flip_yuv420_out(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, kind: int, matrix: int,
+                                       full_range: bool, chw: bool, out: torch.Tensor) -> None:
+    """collate_clips_crop_flip_yuv420 into a buffer of the caller's; every frame of it is written."""
+    _collate_crop_flip_yuv420_into(src, rows, clips, n_px, kind, matrix, full_range, chw, out)
+
+
+@collate_clips_crop_flip_yuv420_out.register_fake
+def _(src, rows, clips, n_px, kind, matrix, full_range, chw, out):
+    _collate_yuv420_check("collate_clips_crop_flip_yuv420", kind, matrix)
+    _collate_check("collate_clips_crop_flip_yuv420", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
+    return None
+
+
 @custom_op(NS + "::clip_encode_out", mutates_args=("vfeat", "tfeat", "medoids_out"), device_types="cuda")
 def clip_encode_out(frames: torch.Tensor, ids: torch.Tensor, vhandle: int, thandle: int, B: int, T: int,
                     vfeat: torch.Tensor, tfeat: torch.Tensor, medoids_out: Optional[torch.Tensor],
@@ -2180,7 +2436,10 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
        "similarity_topk_grouped", "similarity_topk_grouped_dsl", "similarity_topk_masked", "dsl_col_stats_planes_masked",
        "pack_row_mask", "similarity_rank", "similarity_topk_deep", "similarity_topk_merge", "similarity_target_score",
-       "similarity_count", "resized_crop_flip", "resized_crop_flip_out", "video_window_pool_planes")
+       "similarity_count", "resized_crop_flip", "resized_crop_flip_out", "video_window_pool_planes",
+       "yuv420_to_rgb", "resize_center_crop_yuv420", "resize_center_crop_yuv420_out", "resized_crop_flip_yuv420",
+       "resized_crop_flip_yuv420_out", "collate_clips_yuv420", "collate_clips_yuv420_out", "collate_clips_crop_flip_yuv420",
+       "collate_clips_crop_flip_yuv420_out")
 
 
 def logit_multiplier(logit_scale):

@@ -10,6 +10,7 @@ dataloaders/* to evaluate a trained model.
     python examples/eval_synthetic.py --resume DIR/ckpt.pth.tar      (main.py's --resume ... --do_eval 1: evaluate a checkpoint)
     python examples/eval_synthetic.py --raw_frames 240x320           (decoded uint8 frames; resize + centre crop on the device)
     python examples/eval_synthetic.py --ragged 1                     (clips of mixed sizes and lengths, collated on the device)
+    python examples/eval_synthetic.py --raw_frames 240x320 --yuv nv12  (4:2:0 frames as a decoder leaves them; also with --ragged 1)
 """
 import argparse
 import os
@@ -26,12 +27,15 @@ import bench                                                # noqa: E402  (cfg-2
 class SyntheticRetrieval(torch.utils.data.Dataset):
     """(input_ids, input_mask, segment_ids, video, video_mask) as dataloaders/* yield them (main.py:427)."""
 
-    def __init__(self, n, frames=12, words=32, seed=0, raw_frames=None):
+    def __init__(self, n, frames=12, words=32, seed=0, raw_frames=None, yuv=None):
         """raw_frames (H, W): the video as a decoder leaves it - uint8 [n, 1, frames, H, W, 3] of that size, for
-        eval_epoch(frame_transform=...) - instead of the transformed float tensor."""
+        eval_epoch(frame_transform=...) - instead of the transformed float tensor; with yuv ("i420" / "nv12") before any
+        colour conversion: uint8 [n, 1, frames, 3H/2, W], the tight 4:2:0 planes."""
         g = torch.Generator().manual_seed(seed)
         if raw_frames is None:
             self.video = torch.randn(n, 1, frames, 3, 224, 224, generator=g)
+        elif yuv:
+            self.video = torch.randint(0, 256, (n, 1, frames, raw_frames[0] * 3 // 2, raw_frames[1]), dtype=torch.uint8, generator=g)
         else:
             self.video = torch.randint(0, 256, (n, 1, frames, raw_frames[0], raw_frames[1], 3), dtype=torch.uint8, generator=g)
         self.ids = torch.randint(1, 49405, (n, words), generator=g)
@@ -56,10 +60,12 @@ class RaggedRetrieval(torch.utils.data.Dataset):
     (preprocess.pack_clips) and builds its video mask from the clips' lengths."""
     SIZES = ((224, 298), (224, 398), (398, 224), (240, 320))
 
-    def __init__(self, n, frames=12, seed=0):
-        self.text, self.frames = SyntheticRetrieval(n, frames=1, seed=seed, raw_frames=(4, 4)), frames
+    def __init__(self, n, frames=12, seed=0, yuv=None):
+        """yuv ("i420" / "nv12"): the clips before any colour conversion, uint8 [t, 3H/2, W]"""
+        self.text, self.frames, self.yuv = SyntheticRetrieval(n, frames=1, seed=seed, raw_frames=(4, 4)), frames, yuv
         g = torch.Generator().manual_seed(seed + 1)
-        self.video = [torch.randint(0, 256, (frames - (i % 3) * 2,) + self.SIZES[i % len(self.SIZES)] + (3,), dtype=torch.uint8,
+        shape = lambda H, W: (H * 3 // 2, W) if yuv else (H, W, 3)
+        self.video = [torch.randint(0, 256, (frames - (i % 3) * 2,) + shape(*self.SIZES[i % len(self.SIZES)]), dtype=torch.uint8,
                                     generator=g) for i in range(n)]
 
     def __len__(self):
@@ -69,8 +75,8 @@ class RaggedRetrieval(torch.utils.data.Dataset):
         return self.text.ids[i], self.text.mask[i], torch.zeros_like(self.text.ids[i]), self.video[i]
 
     def collate(self, items):
-        from centerclip_amd.preprocess import pack_clips
-        packed = pack_clips([it[3] for it in items])
+        from centerclip_amd.preprocess import pack_clips, pack_yuv_clips
+        packed = pack_yuv_clips([it[3] for it in items], self.yuv) if self.yuv else pack_clips([it[3] for it in items])
         return tuple(torch.stack([it[k] for it in items]) for k in range(3)) + (packed, packed.video_mask(self.frames).unsqueeze(1))
 
 
@@ -163,7 +169,12 @@ def main():
     ap.add_argument("--ragged", type=int, default=0,
                     help="1: the loader yields PackedClips - decoded clips of mixed H x W and lengths - and preprocess.ClipCollate "
                          "resizes, crops and zero-pads them into the uniform batch on the device, at most two launches per batch")
+    ap.add_argument("--yuv", default=None, choices=["i420", "nv12"],
+                    help="with --raw_frames or --ragged: the frames are 8-bit YUV 4:2:0 as a decoder leaves them (PyAV's "
+                         "to_ndarray() of yuv420p / nv12, [..., 3H/2, W]); the conversion to RGB runs inside the device transform")
     a = ap.parse_args()
+    if a.yuv and not (a.raw_frames or a.ragged):
+        ap.error("--yuv describes decoded frames: give --raw_frames HxW or --ragged 1")
     device = torch.device("cuda:0")
     c = L14 if a.l14 else bench.CFG2
     args = l14_task_config(c) if a.l14 else bench.task_config(c)     # cfg 2: 12 frames -> 3 segments at block 7, K = 49
@@ -183,19 +194,20 @@ def main():
         resume(a.resume, model, load_from_pretrained=True)  # (the weights alone: nothing here trains)
         print("evaluating the weights of %s" % a.resume)
     raw = tuple(int(v) for v in a.raw_frames.lower().split("x")) if a.raw_frames else None
-    loader = torch.utils.data.DataLoader(SyntheticRetrieval(a.clips, raw_frames=raw), batch_size=a.batch, shuffle=False)
+    loader = torch.utils.data.DataLoader(SyntheticRetrieval(a.clips, raw_frames=raw, yuv=a.yuv), batch_size=a.batch, shuffle=False)
     transform = None
     if raw is not None:
-        from centerclip_amd.preprocess import FrameTransform
-        transform = FrameTransform(c["res"])
+        from centerclip_amd.preprocess import FrameTransform, YuvFrameTransform
+        transform = YuvFrameTransform(c["res"], layout=a.yuv) if a.yuv else FrameTransform(c["res"])
         print("frame transform %dx%d -> %d: %.3f ms per batch of %d clips" % (raw[0], raw[1], c["res"], transform_ms(
             transform, next(iter(loader))[3], device), a.batch))
     if a.ragged:
-        from centerclip_amd.preprocess import ClipCollate
+        from centerclip_amd.preprocess import ClipCollate, YuvClipCollate
         from centerclip_amd.search import FeatureGallery
-        data = RaggedRetrieval(a.clips, frames=c["T"])
+        data = RaggedRetrieval(a.clips, frames=c["T"], yuv=a.yuv)
         loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False, collate_fn=data.collate)
-        transform = ClipCollate(c["res"], max_frames=c["T"])
+        transform = (YuvClipCollate(c["res"], max_frames=c["T"], layout=a.yuv) if a.yuv
+                     else ClipCollate(c["res"], max_frames=c["T"]))
         packed, vmask = next(iter(loader))[3:]
         print("ragged batch: %d clips, %d bytes, lengths %s" % (len(packed), packed.data.numel(), packed.table[:, 1].tolist()))
         # a FeatureGallery takes the collated tensor as it is

@@ -35,7 +35,7 @@ augmented the same way.
 
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
                                        [--epochs 1] [--output_dir DIR] [--resume DIR/ckpt.pth.tar]
-                                       [--augment multiscale|random_resized] [--flip 1] [--raw_frames 240,320]
+                                       [--augment multiscale|random_resized] [--flip 1] [--raw_frames 240,320] [--yuv i420|nv12]
                                        [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--quick_gelu 0] [--l14 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
@@ -53,7 +53,7 @@ from centerclip_amd.clip4clip import CLIP4Clip              # noqa: E402
 from centerclip_amd.train import (AdamW, BertAdam, DeviceGradScaler, checkpoint_dict, lr_scheduler,   # noqa: E402
                                   prep_optim_params_groups, resume, save_checkpoint, train_epoch)
 from centerclip_amd import dist as ccdist                   # noqa: E402
-from centerclip_amd.preprocess import TrainFrameTransform   # noqa: E402
+from centerclip_amd.preprocess import TrainFrameTransform, YuvTrainFrameTransform   # noqa: E402
 import bench                                                # noqa: E402
 from eval_synthetic import SyntheticRetrieval, L14, l14_state_dict, l14_task_config   # noqa: E402
 
@@ -105,11 +105,16 @@ def build_parser():
     ap.add_argument("--ragged", type=int, default=0,
                     help="1: the loader yields PackedClips - decoded clips of mixed H x W and lengths - collated on the device by "
                          "preprocess.ClipCollate: the evaluation transform, or with --augment one box and one flip per clip")
+    ap.add_argument("--yuv", default=None, choices=["i420", "nv12"],
+                    help="with --augment or --ragged: the decoded frames are 8-bit YUV 4:2:0 ([..., 3H/2, W], PyAV's to_ndarray() of "
+                         "yuv420p / nv12); the conversion to RGB runs inside the device transform")
     return ap
 
 
 def main():
     a = build_parser().parse_args()
+    if a.yuv and (a.uint8 or not (a.augment or a.ragged)):
+        raise SystemExit("--yuv describes decoded frames: it goes with --augment or --ragged 1, without --uint8 1")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("LOCAL_RANK", "0"))
     device = torch.device("cuda", rank)
@@ -155,18 +160,21 @@ def main():
     if a.augment is not None:
         if not a.uint8:                                     # frames as a decoder leaves them: uint8 [n, 1, T, H, W, 3]
             H, W = (int(v) for v in a.raw_frames.split(","))
-            data.video = torch.randint(0, 256, data.video.shape[:3] + (H, W, 3), dtype=torch.uint8,
+            data.video = torch.randint(0, 256, data.video.shape[:3] + ((H * 3 // 2, W) if a.yuv else (H, W, 3)), dtype=torch.uint8,
                                        generator=torch.Generator().manual_seed(rank))
         augment = TrainFrameTransform(224, crop=a.augment, flip=bool(a.flip), seed=rank)
+        if a.yuv:
+            augment = YuvTrainFrameTransform(224, layout=a.yuv, crop=a.augment, flip=bool(a.flip), seed=rank)
     elif a.flip:
         raise SystemExit("--flip 1 goes with --augment")
     loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False)
     if a.ragged:
-        from centerclip_amd.preprocess import ClipCollate
+        from centerclip_amd.preprocess import ClipCollate, YuvClipCollate
         from eval_synthetic import RaggedRetrieval
-        data = RaggedRetrieval(a.batch * a.steps, frames=c["T"], seed=rank)
+        data = RaggedRetrieval(a.batch * a.steps, frames=c["T"], seed=rank, yuv=a.yuv)
         loader = torch.utils.data.DataLoader(data, batch_size=a.batch, shuffle=False, collate_fn=data.collate)
-        augment = ClipCollate(c["res"], max_frames=c["T"], train=augment)
+        augment = (YuvClipCollate(c["res"], max_frames=c["T"], train=augment, layout=a.yuv) if a.yuv
+                   else ClipCollate(c["res"], max_frames=c["T"], train=augment))
     if a.same_batch:
         loader = [next(iter(loader))] * a.steps
     t, dts = [time.time()], []                              # the last time stamp; every step's duration

@@ -793,6 +793,79 @@ int cc_collate_resize_crop_u8(const void* src, size_t src_bytes, int32_t fmt, co
 int cc_collate_crop_flip_u8(const void* src, size_t src_bytes, int32_t fmt, const int64_t* clips_host, int32_t n_clips,
                             const int64_t* rows_dev, int32_t n_out, int32_t n_px, void* dst, int32_t dst_fmt, void* stream);
 
+/* YUV 4:2:0 sources: what decoders produce (a software decoder's yuv420p, a hardware decoder's pitched NV12 surfaces) taken
+ * by the frame preprocessing directly - the conversion to RGB happens in the fetch of the first pass that touches the source,
+ * no RGB image of the source size is ever in memory.  DESIGN.md, "YUV 4:2:0 sources".
+ *
+ * THE CONVERSION, a fixed integer definition.  8-bit Y, Cb, Cr.  matrix: CC_YUV_BT601 (Kr = 0.299, Kb = 0.114) or CC_YUV_BT709
+ * (Kr = 0.2126, Kb = 0.0722), Kg = 1 - Kr - Kb.  range: CC_YUV_LIMITED (oy = 16, sy = 255/219, sc = 255/224) or CC_YUV_FULL
+ * (oy = 0, sy = sc = 1).  Five real coefficients cY = sy, cRV = 2 (1 - Kr) sc, cGU = 2 Kb (1 - Kb) / Kg sc,
+ * cGV = 2 Kr (1 - Kr) / Kg sc, cBU = 2 (1 - Kb) sc, each C = round(c 2^16) computed on the host in double
+ * (cc_yuv_coefficients).  Per pixel in int32, >> an arithmetic shift:
+ *   y = Y - oy, u = Cb - 128, v = Cr - 128
+ *   R = clamp((CY y + CRV v         + 32768) >> 16, 0, 255)
+ *   G = clamp((CY y - CGU u - CGV v + 32768) >> 16, 0, 255)
+ *   B = clamp((CY y + CBU u         + 32768) >> 16, 0, 255)
+ *                  CY     CRV    CGU    CGV    CBU
+ *   601 limited  76309 104597  25675  53279 132201        (the constants of swscale's ITU601 table; swscale's BYTES are not
+ *   601 full     65536  91881  22553  46802 116130         claimed - its converters differ among themselves)
+ *   709 limited  76309 117489  13975  34925 138438
+ *   709 full     65536 103206  12276  30679 121609
+ * Every channel is within 1 LSB of clamp(floor(real + 0.5)) of the real formula; the accumulator stays below 2^31.
+ * Chroma is REPLICATED: luma (y, x) uses chroma sample (y >> 1, x >> 1), chroma planes are ceil(H / 2) x ceil(W / 2); no
+ * chroma interpolation, no siting.
+ *
+ * cc_yuv420_layout describes every 8-bit 4:2:0 arrangement, in bytes from the source's first byte: frame f starts at
+ * f * frame_stride; in a frame Y(y, x) is at y * y_pitch + x, Cb(cy, cx) at u_offset + cy * c_pitch + cx * c_step and Cr the same
+ * from v_offset.  Tight I420: c_step 1, V behind U; YV12: the offsets swapped; NV12: c_step 2, v_offset = u_offset + 1; NV21:
+ * the reverse; a pitched decoder surface: its pitches.  cc_yuv420_layout_tight fills it for tight CC_YUV420_I420 /
+ * CC_YUV420_NV12 frames one behind the other and returns the bytes of one frame, H W + 2 ceil(H / 2) ceil(W / 2) (0, and
+ * nothing written, for another kind, a matrix / range outside {0, 1} or H, W outside 1 .. 8192).
+ *
+ * Every entry point takes src_bytes and checks, before any launch, that every address the descriptor can form for (F, H, W)
+ * lies inside [0, src_bytes): a descriptor that fails, a negative field, a pitch shorter than its row, a c_step outside
+ * {1, 2}, a matrix or range outside {0, 1}: CC_ERR_INVALID.  Sources may start at ANY byte address, H and W may be odd;
+ * 4 <= H, W <= 8192, else CC_ERR_UNSUPPORTED (as the RGB entries).  Not taken (the check refuses what can be told): 4:2:2,
+ * 4:4:4, 10-bit (P010), interlaced chroma siting, chroma interpolation, BT.2020, alpha.
+ *
+ *   cc_yuv420_to_rgb_u8             the conversion alone -> [F, H, W, 3] / [F, 3, H, W] (dst_fmt); one launch.
+ *   cc_resize_crop_yuv420_u8        cc_resize_crop_u8 with this source: the same plan, the same workspace
+ *                                   (cc_resize_crop_workspace_bytes), the same status rules, at most two launches, capturable.
+ *   cc_resized_crop_flip_yuv420_u8  cc_resized_crop_flip_u8 with this source: one launch, the same box rules.
+ *   cc_collate_resize_crop_yuv420_u8 / cc_collate_crop_flip_yuv420_u8   the ragged forms: the packed buffer holds TIGHT frames
+ *                                   of one kind (CC_YUV420_I420 or CC_YUV420_NV12; another kind: CC_ERR_INVALID), a frame of H x W
+ *                                   is H W + 2 ceil(H / 2) ceil(W / 2) bytes and the clip table's and the rows' byte offsets count
+ *                                   in those; the same row tables, launch bound and zero-frame rule as the RGB entries.
+ * CONTRACT of the four fused entries: dst is bit for bit what the RGB entry gives on cc_yuv420_to_rgb_u8's output. */
+#define CC_YUV_BT601 0
+#define CC_YUV_BT709 1
+#define CC_YUV_LIMITED 0
+#define CC_YUV_FULL 1
+#define CC_YUV420_I420 0
+#define CC_YUV420_NV12 1
+typedef struct cc_yuv420_layout {
+    int64_t frame_stride, y_pitch, u_offset, v_offset, c_pitch;
+    int32_t c_step, matrix, range;
+} cc_yuv420_layout;
+/* out5: (CY, CRV, CGU, CGV, CBU); CC_ERR_INVALID for a matrix / range outside {0, 1}; no GPU needed */
+int cc_yuv_coefficients(int32_t matrix, int32_t range, int32_t* out5);
+size_t cc_yuv420_layout_tight(int32_t kind, int32_t H, int32_t W, int32_t matrix, int32_t range, cc_yuv420_layout* out);
+int cc_yuv420_to_rgb_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H, int32_t W,
+                        void* dst, int32_t dst_fmt, void* stream);
+int cc_resize_crop_yuv420_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H, int32_t W,
+                             const void* plan_dev, int32_t n_px, int32_t resize, void* dst, int32_t dst_fmt, void* ws,
+                             size_t ws_bytes, void* stream);
+int cc_resized_crop_flip_yuv420_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H,
+                                   int32_t W, int32_t frames_per_clip, const int32_t* boxes_dev, int32_t n_px, int32_t interp,
+                                   void* dst, int32_t dst_fmt, void* stream);
+int cc_collate_resize_crop_yuv420_u8(const void* src, size_t src_bytes, int32_t kind, int32_t matrix, int32_t range,
+                                     const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out,
+                                     const int32_t* plans_dev, size_t plans_ints, int32_t n_px, int32_t resize, void* dst,
+                                     int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream);
+int cc_collate_crop_flip_yuv420_u8(const void* src, size_t src_bytes, int32_t kind, int32_t matrix, int32_t range,
+                                   const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out,
+                                   int32_t n_px, void* dst, int32_t dst_fmt, void* stream);
+
 /* S2 - the meanP similarity tail, CLIP4Clip._loose_similarity (modules/clip4clip.py:357-366) with
  * _mean_pooling_for_similarity_visual (:305-316):
  *   v_hat = v/|v| per frame; v_bar = sum_t mask*v_hat / max(sum_t mask, 1 if 0); v_bar /= |v_bar|
