@@ -35,6 +35,16 @@ class Yuv420Layout(ctypes.Structure):
                 ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
 
 
+class YuvLayout(ctypes.Structure):
+    """struct cc_yuv_layout: the general descriptor - the five byte positions of cc_yuv420_layout, then c_step (bytes between two
+    samples of one chroma plane in a row), sub_x / sub_y (log2 of the chroma subsampling, 0 or 1), depth (8, 10, 12, 16), shift
+    (a sample is word >> shift), matrix, range."""
+    _fields_ = [("frame_stride", ctypes.c_int64), ("y_pitch", ctypes.c_int64), ("u_offset", ctypes.c_int64),
+                ("v_offset", ctypes.c_int64), ("c_pitch", ctypes.c_int64), ("c_step", ctypes.c_int32),
+                ("sub_x", ctypes.c_int32), ("sub_y", ctypes.c_int32), ("depth", ctypes.c_int32), ("shift", ctypes.c_int32),
+                ("matrix", ctypes.c_int32), ("range", ctypes.c_int32)]
+
+
 _lib = None
 
 

@@ -159,6 +159,22 @@ def declare(lib):
     lib.cc_collate_resize_crop_yuv420_u8.restype = c.c_int
     lib.cc_collate_crop_flip_yuv420_u8.argtypes = [vp, sz, i32, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp]
     lib.cc_collate_crop_flip_yuv420_u8.restype = c.c_int
+    from ._lib import YuvLayout
+    glay = c.POINTER(YuvLayout)
+    lib.cc_yuv_coefficients_depth.argtypes = [i32, i32, i32, vp]
+    lib.cc_yuv_coefficients_depth.restype = c.c_int
+    lib.cc_yuv_layout_tight.argtypes = [i32, i32, i32, i32, i32, glay]
+    lib.cc_yuv_layout_tight.restype = sz
+    lib.cc_yuv_to_rgb_u8.argtypes = [vp, sz, glay, i32, i32, i32, vp, i32, vp]
+    lib.cc_yuv_to_rgb_u8.restype = c.c_int
+    lib.cc_resize_crop_yuv_u8.argtypes = [vp, sz, glay, i32, i32, i32, vp, i32, i32, vp, i32, vp, sz, vp]
+    lib.cc_resize_crop_yuv_u8.restype = c.c_int
+    lib.cc_resized_crop_flip_yuv_u8.argtypes = [vp, sz, glay, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp]
+    lib.cc_resized_crop_flip_yuv_u8.restype = c.c_int
+    lib.cc_collate_resize_crop_yuv_u8.argtypes = [vp, sz, i32, i32, i32, vp, i32, vp, i32, vp, sz, i32, i32, vp, i32, vp, sz, vp]
+    lib.cc_collate_resize_crop_yuv_u8.restype = c.c_int
+    lib.cc_collate_crop_flip_yuv_u8.argtypes = [vp, sz, i32, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp]
+    lib.cc_collate_crop_flip_yuv_u8.restype = c.c_int
     lib.cc_clip_encode_frames.argtypes = [c.POINTER(VitModel), c.POINTER(Frames), i32, i32, vp, vp, vp,
                                           c.POINTER(TextModel), vp, i32, i32, vp, vp, sz, vp]
     lib.cc_clip_encode_frames.restype = c.c_int

@@ -28,6 +28,8 @@ using cc_px::rgb_source;
 using cc_px::u8_format;
 using cc_px::view_of;
 using cc_px::YuvCoef;
+using cc_px::YuvFormat;
+using cc_px::kRgb;
 
 constexpr int kTileX = 64, kTileY = 4;
 constexpr int kBoxInts = 5;                         // (top, left, height, width, flip)
@@ -75,9 +77,9 @@ __device__ __forceinline__ uint8_t to_byte(float v) {
 
 // The work of the thread that owns output pixel (oy, ox) of one frame, the one statement of the arithmetic: the per-size
 // kernel below and the ragged-batch kernel behind it both call it.  in / out: the frame's first byte; the box is followed only
-// when it lies inside the H x W frame, else the pixel is zero.  YUV: a 4:2:0 source, every tap converted by the fetch
+// when it lies inside the H x W frame, else the pixel is zero.  SRC: what the fetch reads and converts
 // (cc_pixels.h).
-template <int TAPS, bool YUV>
+template <int TAPS, int SRC>
 __device__ __forceinline__ void crop_flip_pixel(const uint8_t* __restrict__ base, const PixelSource& iv, int H, int W, int top, int left,
                                                 int bh, int bw, int flip, int n_px, int oy, int ox, uint8_t* __restrict__ out,
                                                 const View& ov) {
@@ -100,7 +102,7 @@ __device__ __forceinline__ void crop_flip_pixel(const uint8_t* __restrict__ base
 #pragma unroll
         for (int k = 0; k < TAPS; ++k) {
             int c0, c1, c2;
-            fetch_pixel<YUV>(base, iv, top + iy[r], left + ix[k], c0, c1, c2);
+            fetch_pixel<SRC>(base, iv, top + iy[r], left + ix[k], c0, c1, c2);
             h0 += wx[k] * (float)c0;
             h1 += wx[k] * (float)c1;
             h2 += wx[k] * (float)c2;
@@ -114,7 +116,7 @@ __device__ __forceinline__ void crop_flip_pixel(const uint8_t* __restrict__ base
     q[2 * ov.sc] = to_byte(v2);
 }
 
-template <int TAPS, bool YUV>
+template <int TAPS, int SRC>
 __global__ __launch_bounds__(kTileX* kTileY) void resized_crop_flip_u8_kernel(const uint8_t* __restrict__ in, PixelSource iv, int H,
                                                                                 int W, int frames_per_clip,
                                                                                 const int32_t* __restrict__ boxes,
@@ -124,7 +126,7 @@ __global__ __launch_bounds__(kTileX* kTileY) void resized_crop_flip_u8_kernel(co
     const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
     if (ox >= n_px || oy >= n_px) return;
     const int32_t* box = boxes + (int64_t)(f / frames_per_clip) * kBoxInts;
-    crop_flip_pixel<TAPS, YUV>(in + (int64_t)f * iv.sf, iv, H, W, box[0], box[1], box[2], box[3], box[4], n_px, oy, ox,
+    crop_flip_pixel<TAPS, SRC>(in + (int64_t)f * iv.sf, iv, H, W, box[0], box[1], box[2], box[3], box[4], n_px, oy, ox,
                           out + (int64_t)f * ov.sf, ov);
 }
 
@@ -132,10 +134,11 @@ __global__ __launch_bounds__(kTileX* kTileY) void resized_crop_flip_u8_kernel(co
 // where there are more frames than planes.  Every workgroup reads its frame's row first - the same address in every lane.  The
 // host never reads the table: a row whose frame does not lie inside the packed buffer, or whose kind is not 1, gives a zero
 // frame, and crop_flip_pixel does the same for a box outside the frame.
-// fmt: the RGB format code, or (YUV) the tight 4:2:0 kind with k its conversion.
-template <bool YUV>
+// fmt: the RGB format code, or (a YUV source) yf: the tight format with k its conversion.
+template <int SRC>
 __global__ __launch_bounds__(kTileX* kTileY) void collate_crop_flip_u8_kernel(const uint8_t* __restrict__ src, int64_t src_bytes,
-                                                                                int fmt, YuvCoef k, const int64_t* __restrict__ rows,
+                                                                                int fmt, YuvFormat yf, YuvCoef k,
+                                                                                const int64_t* __restrict__ rows,
                                                                                 int n_out, uint8_t* __restrict__ dst,
                                                                                 int dst_fmt, int n_px) {
     const int ox = blockIdx.x * kTileX + threadIdx.x, oy = blockIdx.y * kTileY + threadIdx.y;
@@ -146,7 +149,8 @@ __global__ __launch_bounds__(kTileX* kTileY) void collate_crop_flip_u8_kernel(co
         const int64_t kind = row[0], off = row[1], H = row[2], W = row[3], interp = row[9];
         uint8_t* out = dst + (int64_t)f * ov.sf;
         const bool ok = kind == 1 && H >= 4 && W >= 4 && H <= 8192 && W <= 8192 && off >= 0 && off <= src_bytes &&
-                        (YUV ? cc_px::yuv420_frame_bytes(H, W) : 3 * H * W) <= src_bytes - off && (interp == 0 || interp == 1);
+                        cc_px::packed_frame_bytes<SRC>(yf, H, W) <= src_bytes - off && (interp == 0 || interp == 1) &&
+                        !(cc_px::src_wide(SRC) && (off & 1));
         if (!ok) {
             uint8_t* q = out + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
             q[0] = 0;
@@ -157,17 +161,17 @@ __global__ __launch_bounds__(kTileX* kTileY) void collate_crop_flip_u8_kernel(co
         // a box value that is no int32 becomes -1, which crop_flip_pixel refuses (a zero frame) like any box outside the frame
         const auto i32 = [](int64_t v) { return v < INT32_MIN || v > INT32_MAX ? -1 : (int)v; };
         const int top = i32(row[4]), left = i32(row[5]), bh = i32(row[6]), bw = i32(row[7]);
-        const PixelSource iv = YUV ? cc_px::yuv420_tight_source(fmt, H, W, k) : rgb_source(fmt, H, W);
+        const PixelSource iv = SRC != kRgb ? cc_px::yuv_tight_source(yf, H, W, k) : rgb_source(fmt, H, W);
         const uint8_t* base = src + off;
         if (interp == 1)
-            crop_flip_pixel<4, YUV>(base, iv, (int)H, (int)W, top, left, bh, bw, row[8] != 0, n_px, oy, ox, out, ov);
+            crop_flip_pixel<4, SRC>(base, iv, (int)H, (int)W, top, left, bh, bw, row[8] != 0, n_px, oy, ox, out, ov);
         else
-            crop_flip_pixel<2, YUV>(base, iv, (int)H, (int)W, top, left, bh, bw, row[8] != 0, n_px, oy, ox, out, ov);
+            crop_flip_pixel<2, SRC>(base, iv, (int)H, (int)W, top, left, bh, bw, row[8] != 0, n_px, oy, ox, out, ov);
     }
 }
 
-// the launch of cc_resized_crop_flip_u8 / _yuv420_u8 once the source is known to be sound
-template <bool YUV>
+// the launch of cc_resized_crop_flip_u8 / _yuv_u8 once the source is known to be sound
+template <int SRC>
 int crop_flip_launch(const void* src, const PixelSource& sv, int32_t F, int32_t H, int32_t W, int32_t frames_per_clip,
                      const int32_t* boxes_dev, int32_t n_px, int32_t interp, void* dst, int32_t dst_fmt, void* stream) {
     if (n_px < 1 || n_px > 1024 || H < 4 || W < 4 || H > 8192 || W > 8192) return CC_ERR_UNSUPPORTED;
@@ -180,24 +184,26 @@ int crop_flip_launch(const void* src, const PixelSource& sv, int32_t F, int32_t 
     const dim3 block(kTileX, kTileY);
     const unsigned grid = (unsigned)(F * tiles_x * tiles_y);
     if (interp == 0)
-        resized_crop_flip_u8_kernel<2, YUV><<<grid, block, 0, st>>>(in, sv, H, W, frames_per_clip, boxes_dev, out, dv, n_px,
+        resized_crop_flip_u8_kernel<2, SRC><<<grid, block, 0, st>>>(in, sv, H, W, frames_per_clip, boxes_dev, out, dv, n_px,
                                                                      tiles_x, tiles_y);
     else
-        resized_crop_flip_u8_kernel<4, YUV><<<grid, block, 0, st>>>(in, sv, H, W, frames_per_clip, boxes_dev, out, dv, n_px,
+        resized_crop_flip_u8_kernel<4, SRC><<<grid, block, 0, st>>>(in, sv, H, W, frames_per_clip, boxes_dev, out, dv, n_px,
                                                                      tiles_x, tiles_y);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }
 
-// the checks and the launch of cc_collate_crop_flip_u8 / _yuv420_u8; fmt: the RGB format code or the tight 4:2:0 kind
-template <bool YUV>
-int collate_crop_flip_launch(const void* src, size_t src_bytes, int32_t fmt, const YuvCoef& k, const int64_t* clips_host,
+// the checks and the launch of cc_collate_crop_flip_u8 / _yuv_u8; fmt: the RGB format code, or yf: the tight YUV format
+template <int SRC>
+int collate_crop_flip_launch(const void* src, size_t src_bytes, int32_t fmt, const YuvFormat& yf, const YuvCoef& k,
+                             const int64_t* clips_host,
                              int32_t n_clips, const int64_t* rows_dev, int32_t n_out, int32_t n_px, void* dst, int32_t dst_fmt,
                              void* stream) {
     for (int i = 0; i < n_clips; ++i) {
         const int64_t off = clips_host[4 * i], t = clips_host[4 * i + 1], H = clips_host[4 * i + 2], W = clips_host[4 * i + 3];
         if (off < 0 || t < 1 || H < 1 || W < 1 || H > 8192 || W > 8192 || t > (int64_t)1 << 31) return CC_ERR_INVALID;
-        const int64_t frame = YUV ? cc_px::yuv420_frame_bytes(H, W) : H * W * 3;
+        if (cc_px::src_wide(SRC) && (off & 1)) return CC_ERR_INVALID;
+        const int64_t frame = cc_px::packed_frame_bytes<SRC>(yf, H, W);
         if ((uint64_t)off > src_bytes || (uint64_t)(t * frame) > src_bytes - (uint64_t)off) return CC_ERR_INVALID;
         if (H < 4 || W < 4) return CC_ERR_UNSUPPORTED;
     }
@@ -206,9 +212,9 @@ int collate_crop_flip_launch(const void* src, size_t src_bytes, int32_t fmt, con
     int64_t planes = 0x7fffffffLL / ((int64_t)tiles_x * tiles_y * kTileX * kTileY);
     if (planes > CC_COLLATE_MAX_PLANES) planes = CC_COLLATE_MAX_PLANES;
     if (planes > n_out) planes = n_out;
-    collate_crop_flip_u8_kernel<YUV><<<dim3(tiles_x, tiles_y, (unsigned)planes), dim3(kTileX, kTileY), 0,
+    collate_crop_flip_u8_kernel<SRC><<<dim3(tiles_x, tiles_y, (unsigned)planes), dim3(kTileX, kTileY), 0,
                                        static_cast<hipStream_t>(stream)>>>(static_cast<const uint8_t*>(src), (int64_t)src_bytes,
-                                                                           fmt, k, rows_dev, n_out, static_cast<uint8_t*>(dst),
+                                                                           fmt, yf, k, rows_dev, n_out, static_cast<uint8_t*>(dst),
                                                                            dst_fmt, n_px);
     CC_LAUNCH_CHECK();
     return CC_OK;
@@ -223,38 +229,62 @@ int cc_resized_crop_flip_u8(const void* src, int32_t fmt, int32_t F, int32_t H, 
     if (!src || !dst || !boxes_dev || F <= 0 || frames_per_clip <= 0 || !u8_format(fmt) || !u8_format(dst_fmt) ||
         (interp != 0 && interp != 1))
         return CC_ERR_INVALID;
-    return crop_flip_launch<false>(src, rgb_source(fmt, H, W), F, H, W, frames_per_clip, boxes_dev, n_px, interp, dst, dst_fmt,
+    return crop_flip_launch<kRgb>(src, rgb_source(fmt, H, W), F, H, W, frames_per_clip, boxes_dev, n_px, interp, dst, dst_fmt,
                                    stream);
+}
+
+int cc_resized_crop_flip_yuv_u8(const void* src, size_t src_bytes, const cc_yuv_layout* layout, int32_t F, int32_t H, int32_t W,
+                                int32_t frames_per_clip, const int32_t* boxes_dev, int32_t n_px, int32_t interp, void* dst,
+                                int32_t dst_fmt, void* stream) {
+    if (!src || !dst || !boxes_dev || !layout || F <= 0 || frames_per_clip <= 0 || !u8_format(dst_fmt) ||
+        (interp != 0 && interp != 1))
+        return CC_ERR_INVALID;
+    PixelSource sv;
+    const int rc = cc_px::yuv_source(src, layout, src_bytes, F, H, W, &sv);
+    if (rc != CC_OK) return rc;
+    return cc_px::dispatch_yuv(layout->depth, layout->sub_x, layout->sub_y, [&](auto s) {
+        return crop_flip_launch<decltype(s)::value>(src, sv, F, H, W, frames_per_clip, boxes_dev, n_px, interp, dst, dst_fmt, stream);
+    });
 }
 
 int cc_resized_crop_flip_yuv420_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H,
                                    int32_t W, int32_t frames_per_clip, const int32_t* boxes_dev, int32_t n_px, int32_t interp,
                                    void* dst, int32_t dst_fmt, void* stream) {
-    if (!src || !dst || !boxes_dev || !layout || F <= 0 || frames_per_clip <= 0 || !u8_format(dst_fmt) ||
-        (interp != 0 && interp != 1))
-        return CC_ERR_INVALID;
-    PixelSource sv;
-    const int rc = cc_px::yuv420_source(layout, src_bytes, F, H, W, &sv);
-    if (rc != CC_OK) return rc;
-    return crop_flip_launch<true>(src, sv, F, H, W, frames_per_clip, boxes_dev, n_px, interp, dst, dst_fmt, stream);
+    if (!layout) return CC_ERR_INVALID;
+    const cc_yuv_layout lay = cc_px::yuv420_layout(*layout);
+    return cc_resized_crop_flip_yuv_u8(src, src_bytes, &lay, F, H, W, frames_per_clip, boxes_dev, n_px, interp, dst, dst_fmt,
+                                       stream);
 }
 
 int cc_collate_crop_flip_u8(const void* src, size_t src_bytes, int32_t fmt, const int64_t* clips_host, int32_t n_clips,
                             const int64_t* rows_dev, int32_t n_out, int32_t n_px, void* dst, int32_t dst_fmt, void* stream) {
     if (!src || !dst || !rows_dev || !clips_host || n_out <= 0 || n_clips <= 0 || !u8_format(fmt) || !u8_format(dst_fmt))
         return CC_ERR_INVALID;
-    return collate_crop_flip_launch<false>(src, src_bytes, fmt, YuvCoef{}, clips_host, n_clips, rows_dev, n_out, n_px, dst, dst_fmt,
+    return collate_crop_flip_launch<kRgb>(src, src_bytes, fmt, YuvFormat{}, YuvCoef{}, clips_host, n_clips, rows_dev, n_out, n_px, dst, dst_fmt,
                                            stream);
+}
+
+int cc_collate_crop_flip_yuv_u8(const void* src, size_t src_bytes, int32_t format, int32_t matrix, int32_t range,
+                                const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out, int32_t n_px,
+                                void* dst, int32_t dst_fmt, void* stream) {
+    YuvCoef k;
+    YuvFormat yf;
+    if (!src || !dst || !rows_dev || !clips_host || n_out <= 0 || n_clips <= 0 || !u8_format(dst_fmt) ||
+        !cc_px::yuv_format(format, &yf) || !cc_px::yuv_coefficients(matrix, range, yf.depth, &k))
+        return CC_ERR_INVALID;
+    if (yf.depth > 8 && ((uintptr_t)src & 1)) return CC_ERR_INVALID;
+    return cc_px::dispatch_yuv(yf.depth, yf.sub_x, yf.sub_y, [&](auto s) {
+        return collate_crop_flip_launch<decltype(s)::value>(src, src_bytes, 0, yf, k, clips_host, n_clips, rows_dev, n_out, n_px, dst,
+                                                            dst_fmt, stream);
+    });
 }
 
 int cc_collate_crop_flip_yuv420_u8(const void* src, size_t src_bytes, int32_t kind, int32_t matrix, int32_t range,
                                    const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out,
                                    int32_t n_px, void* dst, int32_t dst_fmt, void* stream) {
-    YuvCoef k;
-    if (!src || !dst || !rows_dev || !clips_host || n_out <= 0 || n_clips <= 0 || !u8_format(dst_fmt) ||
-        (kind != CC_YUV420_I420 && kind != CC_YUV420_NV12) || !cc_px::yuv_coefficients(matrix, range, &k))
-        return CC_ERR_INVALID;
-    return collate_crop_flip_launch<true>(src, src_bytes, kind, k, clips_host, n_clips, rows_dev, n_out, n_px, dst, dst_fmt, stream);
+    if (kind != CC_YUV420_I420 && kind != CC_YUV420_NV12) return CC_ERR_INVALID;
+    return cc_collate_crop_flip_yuv_u8(src, src_bytes, kind, matrix, range, clips_host, n_clips, rows_dev, n_out, n_px, dst,
+                                       dst_fmt, stream);
 }
 
 }  // extern "C"

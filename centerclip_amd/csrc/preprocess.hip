@@ -12,8 +12,9 @@
 // - a frame base and a row of 3 W bytes carry no alignment.
 // A ragged batch (clips of mixed sizes and lengths packed back to back, cc_collate_resize_crop_u8): the same two passes as at
 // most two launches for the whole batch, one table row per output frame; the per-pixel arithmetic is the same device function.
-// YUV 4:2:0 sources (the cc_*_yuv420_u8 entries): the same kernels with the other pixel source of cc_pixels.h - the first pass
-// that touches the source converts each tap in its fetch; cc_yuv420_to_rgb_u8 is the crop kernel with the whole frame as window.
+// YUV sources (the cc_*_yuv_u8 entries, and cc_*_yuv420_u8 as their 8-bit 4:2:0 case): the same kernels with the other pixel
+// sources of cc_pixels.h (SRC = a yuv_src code) - the first pass that touches the source converts each tap in its fetch;
+// cc_yuv_to_rgb_u8 is the crop kernel with the whole frame as window.
 #include <math.h>
 
 #include <vector>
@@ -30,6 +31,8 @@ using cc_px::rgb_source;
 using cc_px::u8_format;
 using cc_px::view_of;
 using cc_px::YuvCoef;
+using cc_px::YuvFormat;
+using cc_px::kRgb;
 
 constexpr int kPrecisionBits = 22;
 constexpr int kMaxKsize = CC_RESIZE_MAX_TAPS;                     // taps per output sample the launches take: a shrink factor of 16
@@ -162,8 +165,8 @@ constexpr int kTileX = 64, kTileY = 4;
 // uniform over a wave).  row_base / col_base: the origin the row / column indices count from (the vertical pass reads the
 // workspace, whose row 0 is source row row0: row_base = -row0 - or, no horizontal pass, the source itself from column `left`).
 // resample_pixel is that thread's work, the one statement of the arithmetic: the per-size kernel below and the ragged-batch
-// kernel behind it both call it.  YUV: the source is 4:2:0 planes, every tap converted by the fetch (cc_pixels.h).
-template <bool VERT, bool YUV>
+// kernel behind it both call it.  SRC: what the fetch reads and converts (cc_pixels.h).
+template <bool VERT, int SRC>
 __device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ in, const PixelSource& iv, int row_base, int col_base,
                                                const int32_t* __restrict__ plan, int n_px, int f, int oy, int ox,
                                                uint8_t* __restrict__ out, const View& ov) {
@@ -178,7 +181,7 @@ __device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ in, c
     for (int k = 0; k < count; ++k) {
         const int w = coef[k];
         int c0, c1, c2;
-        fetch_pixel<YUV>(frame, iv, y, x, c0, c1, c2);
+        fetch_pixel<SRC>(frame, iv, y, x, c0, c1, c2);
         a0 += c0 * w;
         a1 += c1 * w;
         a2 += c2 * w;
@@ -194,18 +197,18 @@ __device__ __forceinline__ void resample_pixel(const uint8_t* __restrict__ in, c
 }
 
 // neither axis is resampled: out(f, c, oy, ox) = in(f, c, top + oy, left + ox)
-template <bool YUV>
+template <int SRC>
 __device__ __forceinline__ void crop_pixel(const uint8_t* __restrict__ in, const PixelSource& iv, int top, int left, int f, int oy,
                                            int ox, uint8_t* __restrict__ out, const View& ov) {
     int c0, c1, c2;
-    fetch_pixel<YUV>(in + (int64_t)f * iv.sf, iv, top + oy, left + ox, c0, c1, c2);
+    fetch_pixel<SRC>(in + (int64_t)f * iv.sf, iv, top + oy, left + ox, c0, c1, c2);
     uint8_t* q = out + (int64_t)f * ov.sf + (int64_t)oy * ov.sy + (int64_t)ox * ov.sx;
     q[0] = (uint8_t)c0;
     q[ov.sc] = (uint8_t)c1;
     q[2 * ov.sc] = (uint8_t)c2;
 }
 
-template <bool VERT, bool YUV>
+template <bool VERT, int SRC>
 __global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8_t* __restrict__ in, PixelSource iv, int row_base,
                                                                        int col_base, const int32_t* __restrict__ plan,
                                                                        PlanKey key, uint8_t* __restrict__ out, View ov,
@@ -215,18 +218,18 @@ __global__ __launch_bounds__(kTileX* kTileY) void resample_u8_kernel(const uint8
     const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
     const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
     if (ox >= n_px || oy >= out_rows) return;
-    resample_pixel<VERT, YUV>(in, iv, row_base, col_base, plan, n_px, f, oy, ox, out, ov);
+    resample_pixel<VERT, SRC>(in, iv, row_base, col_base, plan, n_px, f, oy, ox, out, ov);
 }
 
 // the crop alone (n_px x n_px at (top, left)) and, with the whole frame as the window, the stand-alone conversion
-template <bool YUV>
+template <int SRC>
 __global__ __launch_bounds__(kTileX* kTileY) void crop_u8_kernel(const uint8_t* __restrict__ in, PixelSource iv, int top, int left,
                                                                    uint8_t* __restrict__ out, View ov, int rows, int cols,
                                                                    int tiles_x, int tiles_y) {
     const int bx = blockIdx.x % tiles_x, by = (blockIdx.x / tiles_x) % tiles_y, f = blockIdx.x / (tiles_x * tiles_y);
     const int ox = bx * kTileX + threadIdx.x, oy = by * kTileY + threadIdx.y;
     if (ox >= cols || oy >= rows) return;
-    crop_pixel<YUV>(in, iv, top, left, f, oy, ox, out, ov);
+    crop_pixel<SRC>(in, iv, top, left, f, oy, ox, out, ov);
 }
 
 // ---- a ragged batch: clips of mixed sizes and lengths packed back to back, one table row per OUTPUT frame ----------------
@@ -243,8 +246,9 @@ struct CollateArgs {
     uint8_t* ws;
     int64_t ws_bytes;
     uint8_t* dst;
-    int32_t n_out, n_px, resize, fmt, dst_fmt;      // fmt: the RGB format code, or (YUV) CC_YUV420_I420 / _NV12
-    YuvCoef k;                                      // YUV only
+    int32_t n_out, n_px, resize, fmt, dst_fmt;      // fmt: the RGB format code (SRC = kRgb only)
+    YuvFormat yf;                                   // a YUV source: the packed frames' format and its conversion
+    YuvCoef k;
 };
 
 struct CollateFrame {
@@ -255,12 +259,13 @@ struct CollateFrame {
 };
 
 // -> whether output frame f is a transform whose row holds up; false: a zero frame
-template <bool YUV>
+template <int SRC>
 __device__ __forceinline__ bool collate_frame(const CollateArgs& a, int f, CollateFrame* c) {
     const int64_t* row = a.rows + (int64_t)f * CC_COLLATE_ROW;
     const int64_t kind = row[0], off = row[1], H = row[2], W = row[3], plan_off = row[4], ws_off = row[5];
     if (kind != 1 || H < 4 || W < 4 || H > 8192 || W > 8192) return false;
-    if (off < 0 || off > a.src_bytes || (YUV ? cc_px::yuv420_frame_bytes(H, W) : 3 * H * W) > a.src_bytes - off) return false;
+    if (off < 0 || off > a.src_bytes || cc_px::packed_frame_bytes<SRC>(a.yf, H, W) > a.src_bytes - off) return false;
+    if (cc_px::src_wide(SRC) && (off & 1)) return false;
     if (plan_off < 0 || plan_off > a.plans_ints - CC_RESIZE_PLAN_HEADER) return false;
     const int32_t* plan = a.plans + plan_off;
     if (!plan_matches(plan, PlanKey{(int32_t)H, (int32_t)W, a.n_px, a.resize})) return false;
@@ -287,20 +292,20 @@ __device__ __forceinline__ bool collate_frame(const CollateArgs& a, int f, Colla
 // FINAL = false: the horizontal pass of the frames that run both passes, into the workspace; nothing else is touched.
 // FINAL = true: every output frame is written - zeros, the crop alone, the one pass its size needs, or the vertical pass over
 // the workspace.
-template <bool FINAL, bool YUV>
+template <bool FINAL, int SRC>
 __global__ __launch_bounds__(kTileX* kTileY) void collate_resample_u8_kernel(CollateArgs a) {
     const int ox = blockIdx.x * kTileX + threadIdx.x, oy = blockIdx.y * kTileY + threadIdx.y;
     if (ox >= a.n_px) return;
     const View dv = view_of(a.dst_fmt, a.n_px, a.n_px);
     for (int f = blockIdx.z; f < a.n_out; f += gridDim.z) {
         CollateFrame c;
-        const bool ok = collate_frame<YUV>(a, f, &c);
+        const bool ok = collate_frame<SRC>(a, f, &c);
         // (a frame that fails its checks has no sizes to build a source from)
         const PixelSource sv = !ok ? PixelSource{}
-                                   : (YUV ? cc_px::yuv420_tight_source(a.fmt, c.H, c.W, a.k) : rgb_source(a.fmt, c.H, c.W));
+                                   : (SRC != kRgb ? cc_px::yuv_tight_source(a.yf, c.H, c.W, a.k) : rgb_source(a.fmt, c.H, c.W));
         if (!FINAL) {
             if (!ok || !c.mid || oy >= c.nrows) continue;
-            resample_pixel<false, YUV>(c.src, sv, c.row0, 0, c.plan, a.n_px, 0, oy, ox, c.mid,
+            resample_pixel<false, SRC>(c.src, sv, c.row0, 0, c.plan, a.n_px, 0, oy, ox, c.mid,
                                        view_of(CC_FRAMES_U8_CHW, c.nrows, a.n_px));
             continue;
         }
@@ -314,14 +319,14 @@ __global__ __launch_bounds__(kTileX* kTileY) void collate_resample_u8_kernel(Col
             continue;
         }
         if (c.mid) {
-            resample_pixel<true, false>(c.mid, rgb_source(CC_FRAMES_U8_CHW, c.nrows, a.n_px), -c.row0, 0, c.plan, a.n_px, 0, oy, ox,
+            resample_pixel<true, kRgb>(c.mid, rgb_source(CC_FRAMES_U8_CHW, c.nrows, a.n_px), -c.row0, 0, c.plan, a.n_px, 0, oy, ox,
                                         out, dv);
         } else if (c.ksize_h) {
-            resample_pixel<false, YUV>(c.src, sv, c.top, 0, c.plan, a.n_px, 0, oy, ox, out, dv);
+            resample_pixel<false, SRC>(c.src, sv, c.top, 0, c.plan, a.n_px, 0, oy, ox, out, dv);
         } else if (c.ksize_v) {
-            resample_pixel<true, YUV>(c.src, sv, 0, c.left, c.plan, a.n_px, 0, oy, ox, out, dv);
+            resample_pixel<true, SRC>(c.src, sv, 0, c.left, c.plan, a.n_px, 0, oy, ox, out, dv);
         } else {
-            crop_pixel<YUV>(c.src, sv, c.top, c.left, 0, oy, ox, out, dv);
+            crop_pixel<SRC>(c.src, sv, c.top, c.left, 0, oy, ox, out, dv);
         }
     }
 }
@@ -335,19 +340,21 @@ int collate_planes(int n_out, int tiles_x, int tiles_y) {
 }
 
 // the host's checks of a clip table [n_clips, 4] rows (byte offset, frames, H, W) against the packed buffer's size
-int collate_check_clips(const int64_t* clips, int n_clips, size_t src_bytes, bool yuv) {
+template <int SRC>
+int collate_check_clips(const int64_t* clips, int n_clips, size_t src_bytes, const YuvFormat& yf) {
     if (!clips || n_clips <= 0) return CC_ERR_INVALID;
     for (int i = 0; i < n_clips; ++i) {
         const int64_t off = clips[4 * i], t = clips[4 * i + 1], H = clips[4 * i + 2], W = clips[4 * i + 3];
         if (off < 0 || t < 1 || H < 1 || W < 1 || H > 8192 || W > 8192 || t > (int64_t)1 << 31) return CC_ERR_INVALID;
-        const int64_t frame = yuv ? cc_px::yuv420_frame_bytes(H, W) : H * W * 3;
+        if (cc_px::src_wide(SRC) && (off & 1)) return CC_ERR_INVALID;
+        const int64_t frame = cc_px::packed_frame_bytes<SRC>(yf, H, W);
         if ((uint64_t)off > src_bytes || (uint64_t)(t * frame) > src_bytes - (uint64_t)off) return CC_ERR_INVALID;
     }
     return CC_OK;
 }
 
-// the launches of cc_resize_crop_u8 / cc_resize_crop_yuv420_u8 once the source is known to be sound
-template <bool YUV>
+// the launches of cc_resize_crop_u8 / cc_resize_crop_yuv_u8 once the source is known to be sound
+template <int SRC>
 int resize_crop_launch(const void* src, const PixelSource& sv, int32_t F, int32_t H, int32_t W, const void* plan_dev, int32_t n_px,
                        int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
     Geometry g;
@@ -368,19 +375,19 @@ int resize_crop_launch(const void* src, const PixelSource& sv, int32_t F, int32_
     const PlanKey key{H, W, n_px, resize};
     const dim3 block(kTileX, kTileY);
     if (!g.ksize_h && !g.ksize_v) {
-        crop_u8_kernel<YUV><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, g.top, g.left, out, dv, n_px, n_px,
+        crop_u8_kernel<SRC><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, g.top, g.left, out, dv, n_px, n_px,
                                                                                     tiles_x, tiles_out);
         CC_LAUNCH_CHECK();
         return CC_OK;
     }
     if (g.ksize_h && !g.ksize_v) {                  // rows keep their size: the horizontal pass writes the window's rows
-        resample_u8_kernel<false, YUV><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, g.top, 0, plan, key, out,
+        resample_u8_kernel<false, SRC><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, g.top, 0, plan, key, out,
                                                                                                dv, n_px, tiles_x, tiles_out);
         CC_LAUNCH_CHECK();
         return CC_OK;
     }
     if (!g.ksize_h) {                               // columns keep their size: the vertical pass reads the source from `left`
-        resample_u8_kernel<true, YUV><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, 0, g.left, plan, key, out,
+        resample_u8_kernel<true, SRC><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(in, sv, 0, g.left, plan, key, out,
                                                                                               dv, n_px, tiles_x, tiles_out);
         CC_LAUNCH_CHECK();
         return CC_OK;
@@ -388,11 +395,23 @@ int resize_crop_launch(const void* src, const PixelSource& sv, int32_t F, int32_
     // both: the horizontal result of source rows [row0, row1), rounded to bytes, planar [F, 3, nrows, n_px] in the workspace
     uint8_t* mid = static_cast<uint8_t*>(ws);
     const View mv = view_of(CC_FRAMES_U8_CHW, nrows, n_px);
-    resample_u8_kernel<false, YUV><<<(unsigned)(F * tiles_x * tiles_mid), block, 0, st>>>(in, sv, g.row0, 0, plan, key, mid, mv,
+    resample_u8_kernel<false, SRC><<<(unsigned)(F * tiles_x * tiles_mid), block, 0, st>>>(in, sv, g.row0, 0, plan, key, mid, mv,
                                                                                            nrows, tiles_x, tiles_mid);
     CC_LAUNCH_CHECK();
-    resample_u8_kernel<true, false><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(
+    resample_u8_kernel<true, kRgb><<<(unsigned)(F * tiles_x * tiles_out), block, 0, st>>>(
         mid, rgb_source(CC_FRAMES_U8_CHW, nrows, n_px), -g.row0, 0, plan, key, out, dv, n_px, tiles_x, tiles_out);
+    CC_LAUNCH_CHECK();
+    return CC_OK;
+}
+
+// the launch of cc_yuv_to_rgb_u8: the crop kernel with the whole frame as its window
+template <int SRC>
+int to_rgb_launch(const void* src, const PixelSource& sv, int32_t F, int32_t H, int32_t W, void* dst, int32_t dst_fmt,
+                         void* stream) {
+    const int tiles_x = (W + kTileX - 1) / kTileX, tiles_y = (H + kTileY - 1) / kTileY;
+    if ((int64_t)F * tiles_x * tiles_y > 0x7fffffffLL) return CC_ERR_UNSUPPORTED;
+    crop_u8_kernel<SRC><<<(unsigned)(F * tiles_x * tiles_y), dim3(kTileX, kTileY), 0, static_cast<hipStream_t>(stream)>>>(
+        static_cast<const uint8_t*>(src), sv, 0, 0, static_cast<uint8_t*>(dst), view_of(dst_fmt, H, W), H, W, tiles_x, tiles_y);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }
@@ -445,57 +464,93 @@ size_t cc_resize_crop_workspace_bytes(int32_t F, int32_t H, int32_t W, int32_t n
 int cc_resize_crop_u8(const void* src, int32_t fmt, int32_t F, int32_t H, int32_t W, const void* plan_dev, int32_t n_px,
                       int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
     if (!src || !dst || !plan_dev || F <= 0 || !u8_format(fmt) || !u8_format(dst_fmt)) return CC_ERR_INVALID;
-    return resize_crop_launch<false>(src, rgb_source(fmt, H, W), F, H, W, plan_dev, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
+    return resize_crop_launch<kRgb>(src, rgb_source(fmt, H, W), F, H, W, plan_dev, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
+}
+
+int cc_resize_crop_yuv_u8(const void* src, size_t src_bytes, const cc_yuv_layout* layout, int32_t F, int32_t H, int32_t W,
+                          const void* plan_dev, int32_t n_px, int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes,
+                          void* stream) {
+    if (!src || !dst || !plan_dev || !layout || F <= 0 || !u8_format(dst_fmt)) return CC_ERR_INVALID;
+    PixelSource sv;
+    const int rc = cc_px::yuv_source(src, layout, src_bytes, F, H, W, &sv);
+    if (rc != CC_OK) return rc;
+    return cc_px::dispatch_yuv(layout->depth, layout->sub_x, layout->sub_y, [&](auto s) {
+        return resize_crop_launch<decltype(s)::value>(src, sv, F, H, W, plan_dev, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
+    });
 }
 
 int cc_resize_crop_yuv420_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H, int32_t W,
                              const void* plan_dev, int32_t n_px, int32_t resize, void* dst, int32_t dst_fmt, void* ws,
                              size_t ws_bytes, void* stream) {
-    if (!src || !dst || !plan_dev || !layout || F <= 0 || !u8_format(dst_fmt)) return CC_ERR_INVALID;
-    PixelSource sv;
-    const int rc = cc_px::yuv420_source(layout, src_bytes, F, H, W, &sv);
-    if (rc != CC_OK) return rc;
-    return resize_crop_launch<true>(src, sv, F, H, W, plan_dev, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
+    if (!layout) return CC_ERR_INVALID;
+    const cc_yuv_layout lay = cc_px::yuv420_layout(*layout);
+    return cc_resize_crop_yuv_u8(src, src_bytes, &lay, F, H, W, plan_dev, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
 }
 
-int cc_yuv_coefficients(int32_t matrix, int32_t range, int32_t* out5) {
+int cc_yuv_coefficients_depth(int32_t matrix, int32_t range, int32_t depth, int32_t* out5) {
     YuvCoef k;
-    if (!out5 || !cc_px::yuv_coefficients(matrix, range, &k)) return CC_ERR_INVALID;
+    if (!out5 || !cc_px::yuv_coefficients(matrix, range, depth, &k)) return CC_ERR_INVALID;
     const int32_t v[5] = {k.cy, k.crv, k.cgu, k.cgv, k.cbu};
     for (int i = 0; i < 5; ++i) out5[i] = v[i];
     return CC_OK;
 }
 
-size_t cc_yuv420_layout_tight(int32_t kind, int32_t H, int32_t W, int32_t matrix, int32_t range, cc_yuv420_layout* out) {
+int cc_yuv_coefficients(int32_t matrix, int32_t range, int32_t* out5) { return cc_yuv_coefficients_depth(matrix, range, 8, out5); }
+
+size_t cc_yuv_layout_tight(int32_t format, int32_t H, int32_t W, int32_t matrix, int32_t range, cc_yuv_layout* out) {
     YuvCoef k;
-    if (!out || (kind != CC_YUV420_I420 && kind != CC_YUV420_NV12) || !cc_px::yuv_coefficients(matrix, range, &k) || H < 1 ||
-        W < 1 || H > 8192 || W > 8192)
+    YuvFormat f;
+    if (!out || !cc_px::yuv_format(format, &f) || !cc_px::yuv_coefficients(matrix, range, f.depth, &k) || H < 1 || W < 1 ||
+        H > 8192 || W > 8192)
         return 0;
-    const PixelSource s = cc_px::yuv420_tight_source(kind, H, W, k);
+    const PixelSource s = cc_px::yuv_tight_source(f, H, W, k);
     out->frame_stride = s.sf;
     out->y_pitch = s.sy;
     out->u_offset = s.u_off;
     out->v_offset = s.v_off;
     out->c_pitch = s.c_pitch;
     out->c_step = s.c_step;
+    out->sub_x = f.sub_x;
+    out->sub_y = f.sub_y;
+    out->depth = f.depth;
+    out->shift = f.shift;
     out->matrix = matrix;
     out->range = range;
     return (size_t)s.sf;
 }
 
-int cc_yuv420_to_rgb_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H, int32_t W,
-                        void* dst, int32_t dst_fmt, void* stream) {
+size_t cc_yuv420_layout_tight(int32_t kind, int32_t H, int32_t W, int32_t matrix, int32_t range, cc_yuv420_layout* out) {
+    cc_yuv_layout g;
+    if (!out || (kind != CC_YUV420_I420 && kind != CC_YUV420_NV12)) return 0;
+    const size_t n = cc_yuv_layout_tight(kind, H, W, matrix, range, &g);       // (CC_YUV_I420 / _NV12 are the two kinds)
+    if (!n) return 0;
+    out->frame_stride = g.frame_stride;
+    out->y_pitch = g.y_pitch;
+    out->u_offset = g.u_offset;
+    out->v_offset = g.v_offset;
+    out->c_pitch = g.c_pitch;
+    out->c_step = g.c_step;
+    out->matrix = matrix;
+    out->range = range;
+    return n;
+}
+
+int cc_yuv_to_rgb_u8(const void* src, size_t src_bytes, const cc_yuv_layout* layout, int32_t F, int32_t H, int32_t W, void* dst,
+                     int32_t dst_fmt, void* stream) {
     if (!src || !dst || !layout || F <= 0 || !u8_format(dst_fmt)) return CC_ERR_INVALID;
     PixelSource sv;
-    const int rc = cc_px::yuv420_source(layout, src_bytes, F, H, W, &sv);
+    const int rc = cc_px::yuv_source(src, layout, src_bytes, F, H, W, &sv);
     if (rc != CC_OK) return rc;
-    const int tiles_x = (W + kTileX - 1) / kTileX, tiles_y = (H + kTileY - 1) / kTileY;
-    if ((int64_t)F * tiles_x * tiles_y > 0x7fffffffLL) return CC_ERR_UNSUPPORTED;
-    // the crop kernel with the whole frame as its window
-    crop_u8_kernel<true><<<(unsigned)(F * tiles_x * tiles_y), dim3(kTileX, kTileY), 0, static_cast<hipStream_t>(stream)>>>(
-        static_cast<const uint8_t*>(src), sv, 0, 0, static_cast<uint8_t*>(dst), view_of(dst_fmt, H, W), H, W, tiles_x, tiles_y);
-    CC_LAUNCH_CHECK();
-    return CC_OK;
+    return cc_px::dispatch_yuv(layout->depth, layout->sub_x, layout->sub_y, [&](auto s) {
+        return to_rgb_launch<decltype(s)::value>(src, sv, F, H, W, dst, dst_fmt, stream);
+    });
+}
+
+int cc_yuv420_to_rgb_u8(const void* src, size_t src_bytes, const cc_yuv420_layout* layout, int32_t F, int32_t H, int32_t W,
+                        void* dst, int32_t dst_fmt, void* stream) {
+    if (!layout) return CC_ERR_INVALID;
+    const cc_yuv_layout lay = cc_px::yuv420_layout(*layout);
+    return cc_yuv_to_rgb_u8(src, src_bytes, &lay, F, H, W, dst, dst_fmt, stream);
 }
 
 int cc_resize_crop_status(int32_t H, int32_t W, int32_t n_px, int32_t resize) {
@@ -518,12 +573,12 @@ size_t cc_collate_resize_crop_workspace_bytes(const int64_t* clips_host, int32_t
 
 namespace {
 
-// the checks and launches of cc_collate_resize_crop_u8 / _yuv420_u8; fmt: the RGB format code or the tight 4:2:0 kind
-template <bool YUV>
-int collate_launch(const void* src, size_t src_bytes, int32_t fmt, const YuvCoef& k, const int64_t* clips_host, int32_t n_clips,
+// the checks and launches of cc_collate_resize_crop_u8 / _yuv_u8; fmt: the RGB format code, or yf: the tight YUV format
+template <int SRC>
+int collate_launch(const void* src, size_t src_bytes, int32_t fmt, const YuvFormat& yf, const YuvCoef& k, const int64_t* clips_host, int32_t n_clips,
                    const int64_t* rows_dev, int32_t n_out, const int32_t* plans_dev, size_t plans_ints, int32_t n_px,
                    int32_t resize, void* dst, int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
-    int rc = collate_check_clips(clips_host, n_clips, src_bytes, YUV);
+    int rc = collate_check_clips<SRC>(clips_host, n_clips, src_bytes, yf);
     if (rc != CC_OK) return rc;
     int max_mid = 0;                                // rows of the largest horizontal result; 0: no clip runs both passes
     for (int i = 0; i < n_clips; ++i) {
@@ -547,16 +602,17 @@ int collate_launch(const void* src, size_t src_bytes, int32_t fmt, const YuvCoef
     a.resize = resize;
     a.fmt = fmt;
     a.dst_fmt = dst_fmt;
+    a.yf = yf;
     a.k = k;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const dim3 block(kTileX, kTileY);
     const int tiles_x = (n_px + kTileX - 1) / kTileX, tiles_out = (n_px + kTileY - 1) / kTileY;
     if (max_mid) {
         const int tiles_mid = (max_mid + kTileY - 1) / kTileY;
-        collate_resample_u8_kernel<false, YUV><<<dim3(tiles_x, tiles_mid, collate_planes(n_out, tiles_x, tiles_mid)), block, 0, st>>>(a);
+        collate_resample_u8_kernel<false, SRC><<<dim3(tiles_x, tiles_mid, collate_planes(n_out, tiles_x, tiles_mid)), block, 0, st>>>(a);
         CC_LAUNCH_CHECK();
     }
-    collate_resample_u8_kernel<true, YUV><<<dim3(tiles_x, tiles_out, collate_planes(n_out, tiles_x, tiles_out)), block, 0, st>>>(a);
+    collate_resample_u8_kernel<true, SRC><<<dim3(tiles_x, tiles_out, collate_planes(n_out, tiles_x, tiles_out)), block, 0, st>>>(a);
     CC_LAUNCH_CHECK();
     return CC_OK;
 }
@@ -571,20 +627,33 @@ int cc_collate_resize_crop_u8(const void* src, size_t src_bytes, int32_t fmt, co
     if (!src || !dst || !rows_dev || !plans_dev || n_out <= 0 || !u8_format(fmt) || !u8_format(dst_fmt) ||
         plans_ints < CC_RESIZE_PLAN_HEADER)
         return CC_ERR_INVALID;
-    return collate_launch<false>(src, src_bytes, fmt, YuvCoef{}, clips_host, n_clips, rows_dev, n_out, plans_dev, plans_ints, n_px,
+    return collate_launch<kRgb>(src, src_bytes, fmt, YuvFormat{}, YuvCoef{}, clips_host, n_clips, rows_dev, n_out, plans_dev, plans_ints, n_px,
                                  resize, dst, dst_fmt, ws, ws_bytes, stream);
+}
+
+int cc_collate_resize_crop_yuv_u8(const void* src, size_t src_bytes, int32_t format, int32_t matrix, int32_t range,
+                                  const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out,
+                                  const int32_t* plans_dev, size_t plans_ints, int32_t n_px, int32_t resize, void* dst,
+                                  int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
+    YuvCoef k;
+    YuvFormat yf;
+    if (!src || !dst || !rows_dev || !plans_dev || n_out <= 0 || !cc_px::yuv_format(format, &yf) ||
+        !cc_px::yuv_coefficients(matrix, range, yf.depth, &k) || !u8_format(dst_fmt) || plans_ints < CC_RESIZE_PLAN_HEADER)
+        return CC_ERR_INVALID;
+    if (yf.depth > 8 && ((uintptr_t)src & 1)) return CC_ERR_INVALID;
+    return cc_px::dispatch_yuv(yf.depth, yf.sub_x, yf.sub_y, [&](auto s) {
+        return collate_launch<decltype(s)::value>(src, src_bytes, 0, yf, k, clips_host, n_clips, rows_dev, n_out, plans_dev,
+                                                  plans_ints, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
+    });
 }
 
 int cc_collate_resize_crop_yuv420_u8(const void* src, size_t src_bytes, int32_t kind, int32_t matrix, int32_t range,
                                      const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out,
                                      const int32_t* plans_dev, size_t plans_ints, int32_t n_px, int32_t resize, void* dst,
                                      int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream) {
-    YuvCoef k;
-    if (!src || !dst || !rows_dev || !plans_dev || n_out <= 0 || (kind != CC_YUV420_I420 && kind != CC_YUV420_NV12) ||
-        !cc_px::yuv_coefficients(matrix, range, &k) || !u8_format(dst_fmt) || plans_ints < CC_RESIZE_PLAN_HEADER)
-        return CC_ERR_INVALID;
-    return collate_launch<true>(src, src_bytes, kind, k, clips_host, n_clips, rows_dev, n_out, plans_dev, plans_ints, n_px, resize,
-                                dst, dst_fmt, ws, ws_bytes, stream);
+    if (kind != CC_YUV420_I420 && kind != CC_YUV420_NV12) return CC_ERR_INVALID;
+    return cc_collate_resize_crop_yuv_u8(src, src_bytes, kind, matrix, range, clips_host, n_clips, rows_dev, n_out, plans_dev,
+                                         plans_ints, n_px, resize, dst, dst_fmt, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -90,9 +90,10 @@ class DeviceFeeder:
         if self.video_index is not None:
             return self.video_index
         dims = getattr(self.frame_transform, "frame_dims", (4, 6))          # (a YUV transform's frames are [..., 3H/2, W])
-        found = [i for i, t in enumerate(batch) if isinstance(t, PackedClips) or (t.dtype == torch.uint8 and t.dim() in dims)]
+        dtypes = getattr(self.frame_transform, "frame_dtypes", (torch.uint8,))  # (16-bit YUV layouts: uint16 / int16 words)
+        found = [i for i, t in enumerate(batch) if isinstance(t, PackedClips) or (t.dtype in dtypes and t.dim() in dims)]
         if len(found) != 1:
-            raise ValueError("DeviceFeeder(frame_transform=...): the batch has %d uint8 frame tensors - pass video_index"
+            raise ValueError("DeviceFeeder(frame_transform=...): the batch has %d frame tensors of the transform's dtype - pass video_index"
                              % len(found))
         return found[0]
 

@@ -20,8 +20,9 @@ on every clip of the batch, zero padding included, in at most two launches):
     video = ClipCollate(224, max_frames=12)(packed.to(device))           # uint8 [B, 1, T, 224, 224, 3]
     out = model(ids, seg, mask, video, packed.video_mask(12))
 
-All of the above start from RGB bytes.  Decoders produce 8-bit YUV 4:2:0; the ``Yuv*`` counterparts at the end of this file take
-the planes as decoded ([..., 3H/2, W], PyAV's ``to_ndarray()`` of yuv420p / nv12) and convert inside the first resampling pass:
+All of the above start from RGB bytes.  Decoders produce YUV; the ``Yuv*`` counterparts at the end of this file take the planes
+as decoded ([..., 3H/2, W], PyAV's ``to_ndarray()`` of yuv420p / nv12; 4:2:2, 4:4:4 and the 10-, 12- and 16-bit layouts - "p010",
+"i420p10", ... as uint16 - the same way) and convert inside the first resampling pass:
 
     video = YuvFrameTransform(224, layout="nv12", matrix="bt709")(video_yuv)     # uint8 [B, 1, T, 3H/2, W] -> [B, 1, T, 224, 224, 3]
 """
@@ -486,64 +487,88 @@ class ClipCollate:
         return self.apply(packed, self.sample(packed), index=index, out=out)
 
 
-# ------------------------------------------------------------------------------------------ YUV 4:2:0 sources
-# What decoders produce before any colour conversion ("YUV 4:2:0 sources").  At this level frames are uint8
-# [..., 3H/2, W] with H and W even and the layout tight - exactly PyAV's ``frame.to_ndarray()`` of a ``yuv420p`` ("i420": H rows
-# of Y, then the U plane and the V plane, each H/2 x W/2, as H/4 + H/4 rows) or ``nv12`` (H rows of Y, then H/2 rows of
-# interleaved UV) frame; a pitched or odd-sized surface goes through the ops (torch_ops.yuv420_*) with an explicit layout.
-def yuv_coefficients(matrix="bt601", full_range=False):
-    """-> (CY, CRV, CGU, CGV, CBU), the 16-bit fixed-point coefficients of the conversion (cc_yuv_coefficients)."""
+# ------------------------------------------------------------------------------------------ YUV sources
+# What decoders produce before any colour conversion ("YUV sources").  At this level frames are [..., rows, W] arrays
+# with the layout tight - exactly PyAV's ``frame.to_ndarray()``: H rows of Y, then the chroma bytes as further rows of W samples,
+# rows = 3H/2 for 4:2:0 ("i420": the U plane and the V plane, each H/2 x W/2; "nv12": H/2 rows of interleaved UV), 2H for 4:2:2
+# and 3H for 4:4:4; uint8 for the 8-bit layouts, uint16 (or int16 with the same bits) for the 10-, 12- and 16-bit ones; H and W
+# even where the axis is subsampled.  torch_ops.YUV_FORMATS is the one table of what a layout name means.  A pitched or
+# odd-sized surface goes through the ops (torch_ops.yuv_*) with an explicit layout.
+def yuv_coefficients(matrix="bt601", full_range=False, depth=8):
+    """-> (CY, CRV, CGU, CGV, CBU), the fixed-point coefficients of the conversion (cc_yuv_coefficients_depth): 16 fraction bits
+    at depth 8, 20 at depth 10 / 12 / 16."""
     if matrix not in T.YUV_MATRICES:
         raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
     out = (ctypes.c_int32 * 5)()
-    L.check(L.lib().cc_yuv_coefficients(T.YUV_MATRICES[matrix], int(bool(full_range)), out), "cc_yuv_coefficients")
+    L.check(L.lib().cc_yuv_coefficients_depth(T.YUV_MATRICES[matrix], int(bool(full_range)), int(depth), out),
+            "cc_yuv_coefficients_depth")
     return tuple(int(v) for v in out)
 
 
-def _yuv_geometry(shape):
-    """[..., 3H/2, W] with at least one leading dimension -> (leading dimensions, H, W)."""
-    if len(shape) < 3 or shape[-2] % 3 or shape[-1] % 2 or shape[-2] < 3 or shape[-1] < 2:
-        raise ValueError("4:2:0 frames must be [..., 3H/2, W] with H and W even and a leading frame dimension (a decoder's "
-                         "to_ndarray() of yuv420p / nv12), got %s" % (tuple(shape),))
-    return tuple(shape[:-2]), int(shape[-2]) // 3 * 2, int(shape[-1])
+def _yuv_geometry(shape, layout="i420"):
+    """[..., rows, W] with at least one leading dimension -> (leading dimensions, H, W); rows = H (2^s + 2) / 2^s with s the
+    number of subsampled axes: 3H/2, 2H or 3H."""
+    _, sub_x, sub_y, _, _, _ = T.YUV_FORMATS[layout]
+    den = 1 << (sub_x + sub_y)
+    num = den + 2
+    name = {4: "3H/2", 2: "2H", 1: "3H"}[den]
+    H = int(shape[-2]) * den // num if len(shape) >= 3 else 0
+    if len(shape) < 3 or int(shape[-2]) * den % num or H < 1 or shape[-1] < 1 or (sub_y and H % 2) or (sub_x and shape[-1] % 2):
+        raise ValueError("%s frames must be [..., %s, W] with a leading frame dimension and H / W even where chroma is subsampled (a "
+                         "decoder's to_ndarray()), got %s" % (layout, name, tuple(shape)))
+    return tuple(shape[:-2]), H, int(shape[-1])
 
 
 class _YuvSource:
     """What the YUV transforms share: the colour description, the checks, the tight layout of a frame size."""
 
     def _init_yuv(self, layout, matrix, full_range):
-        if layout not in T.YUV_KINDS or matrix not in T.YUV_MATRICES:
-            raise ValueError("layout must be 'i420' or 'nv12' and matrix 'bt601' or 'bt709', got %r, %r" % (layout, matrix))
+        if layout not in T.YUV_FORMATS or matrix not in T.YUV_MATRICES:
+            raise ValueError("layout must be one of %s and matrix 'bt601' or 'bt709', got %r, %r"
+                             % (", ".join(sorted(T.YUV_FORMATS)), layout, matrix))
         self.layout, self.matrix, self.full_range = layout, matrix, bool(full_range)
 
+    @property
+    def frame_dtypes(self):
+        """The dtypes of this layout's frames (what DeviceFeeder recognises as the video of a batch)."""
+        return (torch.uint8,) if T.YUV_FORMATS[self.layout][3] == 8 else (torch.uint16, torch.int16)
+
     def _source(self, frames):
-        """-> (leading dimensions, F, H, W, the eight layout integers) of device frames [..., 3H/2, W]"""
+        """-> (leading dimensions, F, H, W, the twelve layout integers) of device frames [..., rows, W]"""
         L.require_device(frames)
-        if frames.dtype != torch.uint8:
-            raise ValueError("the frame transform takes the decoder's uint8 planes, got %s" % frames.dtype)
-        lead, H, W = _yuv_geometry(frames.shape)
-        return lead, math.prod(lead), H, W, T.yuv420_tight_layout(self.layout, H, W, self.matrix, self.full_range)
+        if frames.dtype not in self.frame_dtypes:
+            raise ValueError("the %s frame transform takes the decoder's %s planes, got %s"
+                             % (self.layout, " / ".join(str(d).replace("torch.", "") for d in self.frame_dtypes), frames.dtype))
+        lead, H, W = _yuv_geometry(frames.shape, self.layout)
+        return lead, math.prod(lead), H, W, T.yuv_tight_layout(self.layout, H, W, self.matrix, self.full_range)
 
     def output_shape(self, shape):
-        lead, _, _ = _yuv_geometry(shape)
+        lead, _, _ = _yuv_geometry(shape, self.layout)
         return lead + (self.n_px, self.n_px, 3)
 
 
-def yuv420_to_rgb(frames, layout="i420", matrix="bt601", full_range=False):
-    """uint8 [..., 3H/2, W] 4:2:0 frames -> uint8 [..., H, W, 3] RGB (torch.ops.centerclip.yuv420_to_rgb): the fixed integer
-    conversion of the header, chroma replicated.  The fused transforms below never store this image; it is the stand-alone form
-    and what they are defined against."""
+def yuv_to_rgb(frames, layout="i420", matrix="bt601", full_range=False):
+    """[..., rows, W] frames of a named layout -> uint8 [..., H, W, 3] RGB (torch.ops.centerclip.yuv_to_rgb): the fixed integer
+    conversion of the header for the layout's depth, chroma replicated.  The fused transforms below never store this image; it is
+    the stand-alone form and what they are defined against."""
     src = _YuvSource()
     src._init_yuv(layout, matrix, full_range)
     lead, F, H, W, lay = src._source(frames)
-    return torch.ops.centerclip.yuv420_to_rgb(frames, F, H, W, lay, False).view(lead + (H, W, 3))
+    return torch.ops.centerclip.yuv_to_rgb(frames, F, H, W, lay, False).view(lead + (H, W, 3))
+
+
+def yuv420_to_rgb(frames, layout="i420", matrix="bt601", full_range=False):
+    """``yuv_to_rgb`` for the two 8-bit 4:2:0 layouts: uint8 [..., 3H/2, W] -> uint8 [..., H, W, 3]."""
+    if layout not in T.YUV_KINDS:
+        raise ValueError("layout must be 'i420' or 'nv12', got %r" % (layout,))
+    return yuv_to_rgb(frames, layout, matrix, full_range)
 
 
 class YuvFrameTransform(_YuvSource):
-    """``FrameTransform`` on 4:2:0 frames as decoded: uint8 [..., 3H/2, W] -> uint8 [..., n_px, n_px, 3], bit for bit
-    ``FrameTransform(n_px, resize)(yuv420_to_rgb(frames, ...))`` with the conversion inside the first resampling pass - half the
-    bytes cross PCIe and are read, and no ``to_rgb()`` runs on a CPU core.  The same protocol (eval_epoch, train_epoch,
-    DeviceFeeder); nothing passes through: a frame of the model's size is still converted."""
+    """``FrameTransform`` on YUV frames as decoded: [..., rows, W] -> uint8 [..., n_px, n_px, 3], bit for bit
+    ``FrameTransform(n_px, resize)(yuv_to_rgb(frames, ...))`` with the conversion inside the first resampling pass - half the
+    bytes (4:2:0, 8-bit) cross PCIe and are read, and no ``to_rgb()`` runs on a CPU core.  The same protocol (eval_epoch,
+    train_epoch, DeviceFeeder); nothing passes through: a frame of the model's size is still converted."""
     frame_dims = (3, 5)                              # what DeviceFeeder recognises as this transform's video: [F, ..] / [B, 1, T, ..]
 
     def __init__(self, n_px=224, resize=True, layout="i420", matrix="bt601", full_range=False):
@@ -557,15 +582,15 @@ class YuvFrameTransform(_YuvSource):
         lead, F, H, W, lay = self._source(frames)
         T.resize_plan(H, W, self.n_px, self.resize, frames.device)
         if out is None:
-            return torch.ops.centerclip.resize_center_crop_yuv420(frames, F, H, W, lay, self.n_px, self.resize,
-                                                                  False).view(lead + (self.n_px, self.n_px, 3))
-        torch.ops.centerclip.resize_center_crop_yuv420_out(frames, F, H, W, lay, self.n_px, self.resize, False, out)
+            return torch.ops.centerclip.resize_center_crop_yuv(frames, F, H, W, lay, self.n_px, self.resize,
+                                                               False).view(lead + (self.n_px, self.n_px, 3))
+        torch.ops.centerclip.resize_center_crop_yuv_out(frames, F, H, W, lay, self.n_px, self.resize, False, out)
         return out
 
 
 class YuvTrainFrameTransform(_YuvSource, TrainFrameTransform):
-    """``TrainFrameTransform`` on 4:2:0 frames as decoded: the same boxes from the same draws (``sample`` is that class's), applied
-    by one launch that converts its taps - bit for bit ``TrainFrameTransform.apply(yuv420_to_rgb(frames, ...), boxes)``."""
+    """``TrainFrameTransform`` on YUV frames as decoded: the same boxes from the same draws (``sample`` is that class's), applied
+    by one launch that converts its taps - bit for bit ``TrainFrameTransform.apply(yuv_to_rgb(frames, ...), boxes)``."""
     frame_dims = (3, 5)
 
     def __init__(self, n_px=224, layout="i420", matrix="bt601", full_range=False, **train):
@@ -581,9 +606,9 @@ class YuvTrainFrameTransform(_YuvSource, TrainFrameTransform):
                                            "being captured - pass a device tensor and refill it between replays")
             boxes = boxes.to(device=frames.device, dtype=torch.int32)
         if out is None:
-            return torch.ops.centerclip.resized_crop_flip_yuv420(frames, F, H, W, lay, boxes, self.n_px, fpc, self.interp,
-                                                                 False).view(lead + (self.n_px, self.n_px, 3))
-        torch.ops.centerclip.resized_crop_flip_yuv420_out(frames, F, H, W, lay, boxes, self.n_px, fpc, self.interp, False, out)
+            return torch.ops.centerclip.resized_crop_flip_yuv(frames, F, H, W, lay, boxes, self.n_px, fpc, self.interp,
+                                                              False).view(lead + (self.n_px, self.n_px, 3))
+        torch.ops.centerclip.resized_crop_flip_yuv_out(frames, F, H, W, lay, boxes, self.n_px, fpc, self.interp, False, out)
         return out
 
     def __call__(self, frames, out=None):
@@ -591,9 +616,15 @@ class YuvTrainFrameTransform(_YuvSource, TrainFrameTransform):
         return self.apply(frames, self.sample(self._clips(lead + (H, W, 3))[0], H, W), out=out)
 
 
+def _yuv_frame_bytes(layout, H, W):
+    """Bytes of one tight frame of a named layout; H, W: ints or integer arrays."""
+    _, sub_x, sub_y, depth, _, _ = T.YUV_FORMATS[layout]
+    return (H * W + 2 * ((H + sub_y) >> sub_y) * ((W + sub_x) >> sub_x)) * (1 if depth == 8 else 2)
+
+
 class PackedYuvClips(PackedClips):
-    """``PackedClips`` of tight 4:2:0 clips: ``table`` rows (byte offset, frames t, H, W) with a frame of 3 H W / 2 bytes;
-    ``layout`` "i420" / "nv12".  Built by ``pack_yuv_clips``."""
+    """``PackedClips`` of tight YUV clips of one named layout: ``data`` the bytes (uint8, whatever the sample size), ``table`` rows
+    (byte offset, frames t, H, W).  Built by ``pack_yuv_clips``."""
 
     def __init__(self, data, table, layout):
         PackedClips.__init__(self, data, table, False)
@@ -606,38 +637,46 @@ class PackedYuvClips(PackedClips):
         return self if self.data.is_pinned() else PackedYuvClips(self.data.pin_memory(), self.table, self.layout)
 
     def clip(self, b):
-        """Clip b as a view of the bytes: [t, 3H/2, W]."""
+        """Clip b as a view of the bytes: [t, rows, W], uint8 or (16-bit samples) uint16."""
         off, t, H, W = (int(v) for v in self.table[b])
-        return self.data[off:off + t * H * W * 3 // 2].view(t, H * 3 // 2, W)
+        n = t * _yuv_frame_bytes(self.layout, H, W)
+        flat = self.data[off:off + n]
+        if T.YUV_FORMATS[self.layout][3] > 8:
+            flat = flat.view(torch.uint16)
+        return flat.view(t, -1, W)
 
     def __getitem__(self, rows):
         return pack_yuv_clips([self.clip(int(b)) for b in torch.as_tensor(rows).reshape(-1).tolist()], self.layout)
 
 
 def pack_yuv_clips(clips, layout="i420"):
-    """``pack_clips`` for 4:2:0 clips: a list of B uint8 arrays / tensors [t_i, 3H_i/2, W_i] (H_i, W_i even), all "i420" or all
-    "nv12" -> ``PackedYuvClips`` (a ``PackedClips``: one pinned byte buffer + the host table), for ``YuvClipCollate``."""
-    if layout not in T.YUV_KINDS:
-        raise ValueError("pack_yuv_clips: layout must be 'i420' or 'nv12', got %r" % (layout,))
+    """``pack_clips`` for YUV clips: a list of B arrays / tensors [t_i, rows_i, W_i] of one named layout (uint8, or uint16 / int16
+    for the 10-, 12- and 16-bit layouts) -> ``PackedYuvClips`` (a ``PackedClips``: one pinned byte buffer + the host table), for
+    ``YuvClipCollate``."""
+    if layout not in T.YUV_FORMATS:
+        raise ValueError("pack_yuv_clips: layout must be one of %s, got %r" % (", ".join(sorted(T.YUV_FORMATS)), layout))
+    dtypes = (torch.uint8,) if T.YUV_FORMATS[layout][3] == 8 else (torch.uint16, torch.int16)
     clips = [torch.from_numpy(np.ascontiguousarray(c)) if isinstance(c, np.ndarray) else c for c in clips]
     if not clips:
         raise ValueError("pack_yuv_clips: no clips")
     rows, off = [], 0
     for i, c in enumerate(clips):
-        if not isinstance(c, torch.Tensor) or c.dtype != torch.uint8 or c.dim() != 3 or c.shape[0] < 1:
-            raise ValueError("pack_yuv_clips: clip %d is not a uint8 array or tensor [t >= 1, 3H/2, W]" % i)
-        _, H, W = _yuv_geometry(c.shape)
+        if not isinstance(c, torch.Tensor) or c.dtype not in dtypes or c.dim() != 3 or c.shape[0] < 1:
+            raise ValueError("pack_yuv_clips: clip %d is not a %s array or tensor [t >= 1, rows, W] of layout %s"
+                             % (i, " / ".join(str(d).replace("torch.", "") for d in dtypes), layout))
+        _, H, W = _yuv_geometry(c.shape, layout)
         rows.append((off, int(c.shape[0]), H, W))
-        off += c.numel()
+        off += c.numel() * c.element_size()
     table = torch.tensor(rows, dtype=torch.int64)
+    flat = [c.contiguous().view(torch.uint8).reshape(-1) for c in clips]                 # the clips' bytes
     if any(c.is_cuda for c in clips):
         if not all(c.is_cuda for c in clips):
             raise ValueError("pack_yuv_clips: host and device clips in one batch")
-        return PackedYuvClips(torch.cat([c.contiguous().view(-1) for c in clips]), table, layout)
+        return PackedYuvClips(torch.cat(flat), table, layout)
     pin = torch.cuda.is_available() and torch.utils.data.get_worker_info() is None
     data = torch.empty(off, dtype=torch.uint8, pin_memory=pin)
-    for (o, _, _, _), c in zip(rows, clips):
-        data[o:o + c.numel()].view(c.shape).copy_(c)
+    for (o, _, _, _), c in zip(rows, flat):
+        data[o:o + c.numel()].copy_(c)
     return PackedYuvClips(data, table, layout)
 
 
@@ -654,37 +693,38 @@ class YuvClipCollate(_YuvSource, ClipCollate):
     def output_shape(self, packed):
         return ClipCollate.output_shape(self, packed)
 
-    @staticmethod
-    def _frame_bytes(tab):
-        return tab[:, 2] * tab[:, 3] * 3 // 2
+    def _frame_bytes(self, tab):
+        return _yuv_frame_bytes(self.layout, tab[:, 2], tab[:, 3])
 
     def _check(self, packed, out):
         ClipCollate._check(self, packed, out)
         if getattr(packed, "layout", self.layout) != self.layout:
             raise ValueError("YuvClipCollate(layout=%r) on clips packed as %r" % (self.layout, packed.layout))
         tab = packed.table.numpy()
-        if ((tab[:, 2] | tab[:, 3]) & 1).any():
-            raise ValueError("YuvClipCollate: packed 4:2:0 clips have even H and W, got %s" % tab[:, 2:].tolist())
+        _, sub_x, sub_y, _, _, _ = T.YUV_FORMATS[self.layout]
+        if (((tab[:, 2] & sub_y) | (tab[:, 3] & sub_x)) & 1).any():
+            raise ValueError("YuvClipCollate: packed %s clips have even H / W where chroma is subsampled, got %s"
+                             % (self.layout, tab[:, 2:].tolist()))
 
     def _kind(self):
-        return T.YUV_KINDS[self.layout], T.YUV_MATRICES[self.matrix], self.full_range
+        return T.YUV_FORMATS[self.layout][0], T.YUV_MATRICES[self.matrix], self.full_range
 
     def _eval_op(self, packed, rows_dev, plans_dev, clips, out):
         if out is None:
-            return torch.ops.centerclip.collate_clips_yuv420(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
-                                                             *self._kind(), False).view(self.output_shape(packed))
-        torch.ops.centerclip.collate_clips_yuv420_out(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
-                                                      *self._kind(), False, out)
+            return torch.ops.centerclip.collate_clips_yuv(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
+                                                          *self._kind(), False).view(self.output_shape(packed))
+        torch.ops.centerclip.collate_clips_yuv_out(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize, *self._kind(),
+                                                   False, out)
         return out
 
     def _train_op(self, packed, rows_dev, clips, out):
         if out is None:
-            return torch.ops.centerclip.collate_clips_crop_flip_yuv420(packed.data, rows_dev, clips, self.n_px, *self._kind(),
-                                                                       False).view(self.output_shape(packed))
-        torch.ops.centerclip.collate_clips_crop_flip_yuv420_out(packed.data, rows_dev, clips, self.n_px, *self._kind(), False, out)
+            return torch.ops.centerclip.collate_clips_crop_flip_yuv(packed.data, rows_dev, clips, self.n_px, *self._kind(),
+                                                                    False).view(self.output_shape(packed))
+        torch.ops.centerclip.collate_clips_crop_flip_yuv_out(packed.data, rows_dev, clips, self.n_px, *self._kind(), False, out)
         return out
 
 
 __all__ = ["resize_center_crop", "FrameTransform", "TrainFrameTransform", "PackedClips", "pack_clips", "ClipCollate",
-           "yuv_coefficients", "yuv420_to_rgb", "YuvFrameTransform", "YuvTrainFrameTransform", "PackedYuvClips", "pack_yuv_clips",
-           "YuvClipCollate"]
+           "yuv_coefficients", "yuv_to_rgb", "yuv420_to_rgb", "YuvFrameTransform", "YuvTrainFrameTransform", "PackedYuvClips",
+           "pack_yuv_clips", "YuvClipCollate"]

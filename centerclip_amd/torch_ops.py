@@ -1440,6 +1440,263 @@ def _(src, rows, clips, n_px, kind, matrix, full_range, chw, out):
     return None
 
 
+# ---- YUV sources in general (include/centerclip_hip.h, "YUV sources in general"): 4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar,
+# samples of 8 bits or of 10 / 12 / 16 bits in 16-bit words.  The ops mirror the *_yuv420 ones with ``layout`` the twelve integers
+# of cc_yuv_layout (frame_stride, y_pitch, u_offset, v_offset, c_pitch, c_step, sub_x, sub_y, depth, shift, matrix, range), all
+# positions in BYTES; ``src`` is any contiguous uint8 tensor or, for 16-bit samples, a uint16 / int16 tensor with the same bits.
+# YUV_FORMATS is THE table of what a name means; nothing else branches on names.
+YUV_FORMATS = {                                     # name: (CC_YUV_* code, sub_x, sub_y, depth, shift, interleaved)
+    "i420": (0, 1, 1, 8, 0, False), "nv12": (1, 1, 1, 8, 0, True), "i422": (2, 1, 0, 8, 0, False), "i444": (3, 0, 0, 8, 0, False),
+    "i420p10": (4, 1, 1, 10, 0, False), "i422p10": (5, 1, 0, 10, 0, False), "i444p10": (6, 0, 0, 10, 0, False),
+    "p010": (7, 1, 1, 10, 6, True), "i420p12": (8, 1, 1, 12, 0, False), "p012": (9, 1, 1, 12, 4, True),
+    "p016": (10, 1, 1, 16, 0, True), "i444p16": (11, 0, 0, 16, 0, False)}
+_YUV_WORDS = (torch.uint16, torch.int16)
+
+
+def yuv_tight_layout(name, H, W, matrix, full_range):
+    """-> the twelve integers of cc_yuv_layout_tight for tight frames of the named format, H x W, one behind the other; [0] is
+    the bytes of a frame."""
+    lay = L.YuvLayout()
+    if name not in YUV_FORMATS or matrix not in YUV_MATRICES:
+        raise ValueError("a YUV layout is one of %s and a matrix 'bt601' or 'bt709', got %r, %r" % (sorted(YUV_FORMATS), name, matrix))
+    if not L.lib().cc_yuv_layout_tight(YUV_FORMATS[name][0], int(H), int(W), YUV_MATRICES[matrix], int(bool(full_range)),
+                                       ctypes.byref(lay)):
+        raise ValueError("no tight %s layout for %s x %s frames (1 .. 8192)" % (name, H, W))
+    return [getattr(lay, field) for field, _ in L.YuvLayout._fields_]
+
+
+def _yuv_general_source(name, src, F, H, W, layout):
+    """The checks the real and the fake kernels of the general YUV ops share."""
+    if len(layout) != 12:
+        raise ValueError("%s: layout is the twelve integers of cc_yuv_layout (frame_stride, y_pitch, u_offset, v_offset, c_pitch, "
+                         "c_step, sub_x, sub_y, depth, shift, matrix, range), got %d values" % (name, len(layout)))
+    if src.dtype != torch.uint8 and not (src.dtype in _YUV_WORDS and layout[8] > 8):
+        raise ValueError("%s takes the decoder's planes as uint8 bytes or, for samples of more than 8 bits, uint16 / int16 words, "
+                         "got %s at depth %d" % (name, src.dtype, layout[8]))
+    if F < 0 or H < 1 or W < 1:
+        raise ValueError("%s: F >= 0 frames of H, W >= 1, got %d x %d x %d" % (name, F, H, W))
+
+
+def _yuv_general_layout(layout):
+    return L.YuvLayout(*(int(v) for v in layout))
+
+
+def _nbytes(t):
+    return t.numel() * t.element_size()
+
+
+@custom_op(NS + "::yuv_to_rgb", mutates_args=(), device_types="cuda")
+def yuv_to_rgb(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], chw: bool) -> torch.Tensor:
+    """The conversion alone (cc_yuv_to_rgb_u8, one launch): F frames of H x W in ``src`` as ``layout`` describes -> uint8
+    [F, H, W, 3] ([F, 3, H, W] with chw), the fixed integer conversion of the header for the layout's depth, chroma replicated."""
+    _yuv_general_source("yuv_to_rgb", src, F, H, W, layout)
+    L.require_device(src)
+    out = _e(*_yuv_shape(F, H, W, chw), like=src, dtype=torch.uint8)
+    if F:
+        src = src.contiguous()
+        L.check(L.lib().cc_yuv_to_rgb_u8(L.ptr(src), _nbytes(src), ctypes.byref(_yuv_general_layout(layout)), F, H, W, L.ptr(out),
+                                         1 if chw else 2, _st(src)), "cc_yuv_to_rgb_u8")
+    return out
+
+
+@yuv_to_rgb.register_fake
+def _(src, F, H, W, layout, chw):
+    _yuv_general_source("yuv_to_rgb", src, F, H, W, layout)
+    return src.new_empty(_yuv_shape(F, H, W, chw), dtype=torch.uint8)
+
+
+def _resize_crop_yuv_into(src, F, H, W, layout, n_px, resize, chw, out):
+    _yuv_general_source("resize_center_crop_yuv", src, F, H, W, layout)
+    _yuv_out_check("resize_center_crop_yuv", out, _yuv_shape(F, n_px, n_px, chw))
+    L.require_device(src, out)
+    if F == 0:
+        return
+    src = src.contiguous()
+    lib = L.lib()
+    plan = resize_plan(H, W, n_px, resize, src.device)
+    nws = lib.cc_resize_crop_workspace_bytes(F, H, W, int(n_px), int(resize))
+    ws = L.workspace(nws, src.device) if nws else None
+    L.check(lib.cc_resize_crop_yuv_u8(L.ptr(src), _nbytes(src), ctypes.byref(_yuv_general_layout(layout)), F, H, W, L.ptr(plan),
+                                      int(n_px), int(resize), L.ptr(out), 1 if chw else 2, L.ptr(ws),
+                                      ws.numel() if ws is not None else 0, _st(src)), "cc_resize_crop_yuv_u8")
+
+
+@custom_op(NS + "::resize_center_crop_yuv", mutates_args=(), device_types="cuda")
+def resize_center_crop_yuv(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], n_px: int, resize: bool,
+                           chw: bool) -> torch.Tensor:
+    """resize_center_crop on a YUV source (cc_resize_crop_yuv_u8): -> uint8 [F, n_px, n_px, 3] ([F, 3, n_px, n_px] with chw), bit
+    for bit resize_center_crop(yuv_to_rgb(src)); the first pass converts its taps, no RGB frame of H x W is stored."""
+    out = _e(*_yuv_shape(F, n_px, n_px, chw), like=src, dtype=torch.uint8)
+    _resize_crop_yuv_into(src, F, H, W, layout, n_px, resize, chw, out)
+    return out
+
+
+@resize_center_crop_yuv.register_fake
+def _(src, F, H, W, layout, n_px, resize, chw):
+    _yuv_general_source("resize_center_crop_yuv", src, F, H, W, layout)
+    return src.new_empty(_yuv_shape(F, n_px, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::resize_center_crop_yuv_out", mutates_args=("out",), device_types="cuda")
+def resize_center_crop_yuv_out(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], n_px: int, resize: bool, chw: bool,
+                               out: torch.Tensor) -> None:
+    """resize_center_crop_yuv into a buffer of the caller's."""
+    _resize_crop_yuv_into(src, F, H, W, layout, n_px, resize, chw, out)
+
+
+@resize_center_crop_yuv_out.register_fake
+def _(src, F, H, W, layout, n_px, resize, chw, out):
+    _yuv_general_source("resize_center_crop_yuv", src, F, H, W, layout)
+    return None
+
+
+def _crop_flip_yuv_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp):
+    _yuv_general_source("resized_crop_flip_yuv", src, F, H, W, layout)
+    if frames_per_clip < 1 or interp not in (0, 1) or n_px < 1:
+        raise ValueError("resized_crop_flip_yuv: frames_per_clip >= 1, n_px >= 1 and interp 0 (bilinear) / 1 (bicubic), got "
+                         "%d, %d, %d" % (frames_per_clip, n_px, interp))
+    clips = -(-F // frames_per_clip)
+    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (clips, 5):
+        raise ValueError("resized_crop_flip_yuv: boxes must be int32 [%d, 5] rows (top, left, height, width, flip) for %d frames "
+                         "in clips of %d, got %s %s" % (clips, F, frames_per_clip, boxes.dtype, tuple(boxes.shape)))
+
+
+def _crop_flip_yuv_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out):
+    _crop_flip_yuv_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
+    _yuv_out_check("resized_crop_flip_yuv", out, _yuv_shape(F, n_px, n_px, chw))
+    L.require_device(src, boxes, out)
+    if F == 0:
+        return
+    src, boxes = src.contiguous(), boxes.contiguous()
+    L.check(L.lib().cc_resized_crop_flip_yuv_u8(L.ptr(src), _nbytes(src), ctypes.byref(_yuv_general_layout(layout)), F, H, W,
+                                                int(frames_per_clip), L.ptr(boxes), int(n_px), int(interp), L.ptr(out),
+                                                1 if chw else 2, _st(src)), "cc_resized_crop_flip_yuv_u8")
+
+
+@custom_op(NS + "::resized_crop_flip_yuv", mutates_args=(), device_types="cuda")
+def resized_crop_flip_yuv(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], boxes: torch.Tensor, n_px: int,
+                          frames_per_clip: int, interp: int, chw: bool) -> torch.Tensor:
+    """resized_crop_flip on a YUV source (cc_resized_crop_flip_yuv_u8, one launch): bit for bit
+    resized_crop_flip(yuv_to_rgb(src), boxes, ...)."""
+    out = _e(*_yuv_shape(F, n_px, n_px, chw), like=src, dtype=torch.uint8)
+    _crop_flip_yuv_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out)
+    return out
+
+
+@resized_crop_flip_yuv.register_fake
+def _(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw):
+    _crop_flip_yuv_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
+    return src.new_empty(_yuv_shape(F, n_px, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::resized_crop_flip_yuv_out", mutates_args=("out",), device_types="cuda")
+def resized_crop_flip_yuv_out(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], boxes: torch.Tensor, n_px: int,
+                              frames_per_clip: int, interp: int, chw: bool, out: torch.Tensor) -> None:
+    """resized_crop_flip_yuv into a buffer of the caller's."""
+    _crop_flip_yuv_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out)
+
+
+@resized_crop_flip_yuv_out.register_fake
+def _(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out):
+    _crop_flip_yuv_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
+    return None
+
+
+def _collate_yuv_check(name, fmt, matrix):
+    if not 0 <= fmt < len(YUV_FORMATS) or matrix not in (0, 1):
+        raise ValueError("%s: format 0 .. %d (the CC_YUV_* codes of YUV_FORMATS) and matrix 0 (BT.601) / 1 (BT.709), got %d, %d"
+                         % (name, len(YUV_FORMATS) - 1, fmt, matrix))
+
+
+def _collate_yuv_into(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw, out):
+    _collate_yuv_check("collate_clips_yuv", fmt, matrix)
+    n_out = _collate_check("collate_clips_yuv", src, rows, clips, n_px, chw, COLLATE_ROW, out)
+    if plans.dtype != torch.int32 or plans.dim() != 1:
+        raise ValueError("collate_clips_yuv: the plans are one 1-D int32 buffer, got %s %s" % (plans.dtype, tuple(plans.shape)))
+    L.require_device(src, rows, plans, out)
+    src, rows, plans = src.contiguous(), rows.contiguous(), plans.contiguous()
+    lib, table = L.lib(), _clips_host(clips)
+    nws = lib.cc_collate_resize_crop_workspace_bytes(table, len(clips) // 4, n_out, int(n_px), int(resize))
+    ws = L.workspace(nws, src.device) if nws else None
+    L.check(lib.cc_collate_resize_crop_yuv_u8(L.ptr(src), src.numel(), int(fmt), int(matrix), int(full_range), table,
+                                              len(clips) // 4, L.ptr(rows), n_out, L.ptr(plans), plans.numel(), int(n_px),
+                                              int(resize), L.ptr(out), 1 if chw else 2, L.ptr(ws), nws, _st(src)),
+            "cc_collate_resize_crop_yuv_u8")
+
+
+@custom_op(NS + "::collate_clips_yuv", mutates_args=(), device_types="cuda")
+def collate_clips_yuv(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
+                      fmt: int, matrix: int, full_range: bool, chw: bool) -> torch.Tensor:
+    """collate_clips on packed tight YUV frames of one named format (cc_collate_resize_crop_yuv_u8): the same tables, byte
+    offsets counting tight frames of that format (even for 16-bit samples); fmt: the CC_YUV_* code; chw: the OUTPUT's layout."""
+    out = _e(*_collate_shape(_collate_check("collate_clips_yuv", src, rows, clips, n_px, chw, COLLATE_ROW), n_px, chw), like=src,
+             dtype=torch.uint8)
+    _collate_yuv_into(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw, out)
+    return out
+
+
+@collate_clips_yuv.register_fake
+def _(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw):
+    _collate_yuv_check("collate_clips_yuv", fmt, matrix)
+    n_out = _collate_check("collate_clips_yuv", src, rows, clips, n_px, chw, COLLATE_ROW)
+    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::collate_clips_yuv_out", mutates_args=("out",), device_types="cuda")
+def collate_clips_yuv_out(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
+                          fmt: int, matrix: int, full_range: bool, chw: bool, out: torch.Tensor) -> None:
+    """collate_clips_yuv into a buffer of the caller's; every frame of it is written."""
+    _collate_yuv_into(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw, out)
+
+
+@collate_clips_yuv_out.register_fake
+def _(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw, out):
+    _collate_yuv_check("collate_clips_yuv", fmt, matrix)
+    _collate_check("collate_clips_yuv", src, rows, clips, n_px, chw, COLLATE_ROW, out)
+    return None
+
+
+def _collate_crop_flip_yuv_into(src, rows, clips, n_px, fmt, matrix, full_range, chw, out):
+    _collate_yuv_check("collate_clips_crop_flip_yuv", fmt, matrix)
+    n_out = _collate_check("collate_clips_crop_flip_yuv", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
+    L.require_device(src, rows, out)
+    src, rows = src.contiguous(), rows.contiguous()
+    L.check(L.lib().cc_collate_crop_flip_yuv_u8(L.ptr(src), src.numel(), int(fmt), int(matrix), int(full_range), _clips_host(clips),
+                                                len(clips) // 4, L.ptr(rows), n_out, int(n_px), L.ptr(out), 1 if chw else 2,
+                                                _st(src)), "cc_collate_crop_flip_yuv_u8")
+
+
+@custom_op(NS + "::collate_clips_crop_flip_yuv", mutates_args=(), device_types="cuda")
+def collate_clips_crop_flip_yuv(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, fmt: int, matrix: int,
+                                full_range: bool, chw: bool) -> torch.Tensor:
+    """collate_clips_crop_flip on packed tight YUV frames of one named format (cc_collate_crop_flip_yuv_u8, one launch)."""
+    out = _e(*_collate_shape(_collate_check("collate_clips_crop_flip_yuv", src, rows, clips, n_px, chw, COLLATE_BOX_ROW), n_px, chw),
+             like=src, dtype=torch.uint8)
+    _collate_crop_flip_yuv_into(src, rows, clips, n_px, fmt, matrix, full_range, chw, out)
+    return out
+
+
+@collate_clips_crop_flip_yuv.register_fake
+def _(src, rows, clips, n_px, fmt, matrix, full_range, chw):
+    _collate_yuv_check("collate_clips_crop_flip_yuv", fmt, matrix)
+    n_out = _collate_check("collate_clips_crop_flip_yuv", src, rows, clips, n_px, chw, COLLATE_BOX_ROW)
+    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
+
+
+@custom_op(NS + "::collate_clips_crop_flip_yuv_out", mutates_args=("out",), device_types="cuda")
+def collate_clips_crop_flip_yuv_out(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, fmt: int, matrix: int,
+                                    full_range: bool, chw: bool, out: torch.Tensor) -> None:
+    """collate_clips_crop_flip_yuv into a buffer of the caller's; every frame of it is written."""
+    _collate_crop_flip_yuv_into(src, rows, clips, n_px, fmt, matrix, full_range, chw, out)
+
+
+@collate_clips_crop_flip_yuv_out.register_fake
+def _(src, rows, clips, n_px, fmt, matrix, full_range, chw, out):
+    _collate_yuv_check("collate_clips_crop_flip_yuv", fmt, matrix)
+    _collate_check("collate_clips_crop_flip_yuv", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
+    return None
+
+
 @custom_op(NS + "::clip_encode_out", mutates_args=("vfeat", "tfeat", "medoids_out"), device_types="cuda")
 def clip_encode_out(frames: torch.Tensor, ids: torch.Tensor, vhandle: int, thandle: int, B: int, T: int,
                     vfeat: torch.Tensor, tfeat: torch.Tensor, medoids_out: Optional[torch.Tensor],
@@ -2439,7 +2696,9 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "similarity_count", "resized_crop_flip", "resized_crop_flip_out", "video_window_pool_planes",
        "yuv420_to_rgb", "resize_center_crop_yuv420", "resize_center_crop_yuv420_out", "resized_crop_flip_yuv420",
        "resized_crop_flip_yuv420_out", "collate_clips_yuv420", "collate_clips_yuv420_out", "collate_clips_crop_flip_yuv420",
-       "collate_clips_crop_flip_yuv420_out")
+       "collate_clips_crop_flip_yuv420_out", "yuv_to_rgb", "resize_center_crop_yuv", "resize_center_crop_yuv_out",
+       "resized_crop_flip_yuv", "resized_crop_flip_yuv_out", "collate_clips_yuv", "collate_clips_yuv_out",
+       "collate_clips_crop_flip_yuv", "collate_clips_crop_flip_yuv_out")
 
 
 def logit_multiplier(logit_scale):

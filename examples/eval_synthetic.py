@@ -10,7 +10,7 @@ dataloaders/* to evaluate a trained model.
     python examples/eval_synthetic.py --resume DIR/ckpt.pth.tar      (main.py's --resume ... --do_eval 1: evaluate a checkpoint)
     python examples/eval_synthetic.py --raw_frames 240x320           (decoded uint8 frames; resize + centre crop on the device)
     python examples/eval_synthetic.py --ragged 1                     (clips of mixed sizes and lengths, collated on the device)
-    python examples/eval_synthetic.py --raw_frames 240x320 --yuv nv12  (4:2:0 frames as a decoder leaves them; also with --ragged 1)
+    python examples/eval_synthetic.py --raw_frames 240x320 --yuv nv12  (YUV frames as a decoder leaves them, also p010, i444, ...; also with --ragged 1)
 """
 import argparse
 import os
@@ -24,18 +24,34 @@ from centerclip_amd.eval import eval_epoch                  # noqa: E402
 import bench                                                # noqa: E402  (cfg-2 task config, random ViT-B/32 state dict)
 
 
+def yuv_frames(layout, lead, H, W, generator):
+    """Random frames of a named YUV layout as a decoder leaves them: [*lead, rows, W] with rows = 3H/2, 2H or 3H; uint8, or
+    uint16 words (the sample above the layout's shift) for the 10-, 12- and 16-bit layouts."""
+    from centerclip_amd.torch_ops import YUV_FORMATS
+    _, sub_x, sub_y, depth, shift, _ = YUV_FORMATS[layout]
+    den = 1 << (sub_x + sub_y)
+    shape = tuple(lead) + (H * (den + 2) // den, W)
+    if depth == 8:
+        return torch.randint(0, 256, shape, dtype=torch.uint8, generator=generator)
+    words = torch.randint(0, 1 << depth, shape, dtype=torch.int32, generator=generator) << shift
+    return torch.from_numpy(words.numpy().astype("uint16"))
+
+
+YUV_LAYOUTS = ["i420", "nv12", "i422", "i444", "i420p10", "i422p10", "i444p10", "p010", "i420p12", "p012", "p016", "i444p16"]
+
+
 class SyntheticRetrieval(torch.utils.data.Dataset):
     """(input_ids, input_mask, segment_ids, video, video_mask) as dataloaders/* yield them (main.py:427)."""
 
     def __init__(self, n, frames=12, words=32, seed=0, raw_frames=None, yuv=None):
         """raw_frames (H, W): the video as a decoder leaves it - uint8 [n, 1, frames, H, W, 3] of that size, for
-        eval_epoch(frame_transform=...) - instead of the transformed float tensor; with yuv ("i420" / "nv12") before any
-        colour conversion: uint8 [n, 1, frames, 3H/2, W], the tight 4:2:0 planes."""
+        eval_epoch(frame_transform=...) - instead of the transformed float tensor; with yuv (a layout name, "i420" .. "i444p16")
+        before any colour conversion: [n, 1, frames, rows, W], the tight planes (uint8, or uint16 above 8 bits)."""
         g = torch.Generator().manual_seed(seed)
         if raw_frames is None:
             self.video = torch.randn(n, 1, frames, 3, 224, 224, generator=g)
         elif yuv:
-            self.video = torch.randint(0, 256, (n, 1, frames, raw_frames[0] * 3 // 2, raw_frames[1]), dtype=torch.uint8, generator=g)
+            self.video = yuv_frames(yuv, (n, 1, frames), raw_frames[0], raw_frames[1], g)
         else:
             self.video = torch.randint(0, 256, (n, 1, frames, raw_frames[0], raw_frames[1], 3), dtype=torch.uint8, generator=g)
         self.ids = torch.randint(1, 49405, (n, words), generator=g)
@@ -61,12 +77,12 @@ class RaggedRetrieval(torch.utils.data.Dataset):
     SIZES = ((224, 298), (224, 398), (398, 224), (240, 320))
 
     def __init__(self, n, frames=12, seed=0, yuv=None):
-        """yuv ("i420" / "nv12"): the clips before any colour conversion, uint8 [t, 3H/2, W]"""
+        """yuv (a layout name): the clips before any colour conversion, [t, rows, W]"""
         self.text, self.frames, self.yuv = SyntheticRetrieval(n, frames=1, seed=seed, raw_frames=(4, 4)), frames, yuv
         g = torch.Generator().manual_seed(seed + 1)
-        shape = lambda H, W: (H * 3 // 2, W) if yuv else (H, W, 3)
-        self.video = [torch.randint(0, 256, (frames - (i % 3) * 2,) + shape(*self.SIZES[i % len(self.SIZES)]), dtype=torch.uint8,
-                                    generator=g) for i in range(n)]
+        clip = lambda t, H, W: (yuv_frames(yuv, (t,), H, W, g) if yuv
+                                else torch.randint(0, 256, (t, H, W, 3), dtype=torch.uint8, generator=g))
+        self.video = [clip(frames - (i % 3) * 2, *self.SIZES[i % len(self.SIZES)]) for i in range(n)]
 
     def __len__(self):
         return len(self.video)
@@ -169,9 +185,10 @@ def main():
     ap.add_argument("--ragged", type=int, default=0,
                     help="1: the loader yields PackedClips - decoded clips of mixed H x W and lengths - and preprocess.ClipCollate "
                          "resizes, crops and zero-pads them into the uniform batch on the device, at most two launches per batch")
-    ap.add_argument("--yuv", default=None, choices=["i420", "nv12"],
-                    help="with --raw_frames or --ragged: the frames are 8-bit YUV 4:2:0 as a decoder leaves them (PyAV's "
-                         "to_ndarray() of yuv420p / nv12, [..., 3H/2, W]); the conversion to RGB runs inside the device transform")
+    ap.add_argument("--yuv", default=None, choices=YUV_LAYOUTS,
+                    help="with --raw_frames or --ragged: the frames are YUV as a decoder leaves them (PyAV's to_ndarray() of "
+                         "yuv420p / nv12 / yuv422p / yuv444p / yuv420p10le / p010le ..., [..., rows, W], uint16 above 8 bits); the "
+                         "conversion to RGB runs inside the device transform")
     a = ap.parse_args()
     if a.yuv and not (a.raw_frames or a.ragged):
         ap.error("--yuv describes decoded frames: give --raw_frames HxW or --ragged 1")

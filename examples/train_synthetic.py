@@ -35,7 +35,7 @@ augmented the same way.
 
     python examples/train_synthetic.py [--steps 4] [--batch 16] [--optim BertAdam|AdamW] [--optim-timing 1] [--precision amp]
                                        [--epochs 1] [--output_dir DIR] [--resume DIR/ckpt.pth.tar]
-                                       [--augment multiscale|random_resized] [--flip 1] [--raw_frames 240,320] [--yuv i420|nv12]
+                                       [--augment multiscale|random_resized] [--flip 1] [--raw_frames 240,320] [--yuv i420|nv12|p010|i444|...]
                                        [--freeze_layer_num 0] [--uint8 1] [--linear_patch 3d] [--camoe_dsl 1] [--quick_gelu 0] [--l14 1] [--lr 1e-3 --coef_lr 1 --same_batch 1]
     python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 examples/train_synthetic.py   (RCCL, bucketed)
 """
@@ -105,9 +105,11 @@ def build_parser():
     ap.add_argument("--ragged", type=int, default=0,
                     help="1: the loader yields PackedClips - decoded clips of mixed H x W and lengths - collated on the device by "
                          "preprocess.ClipCollate: the evaluation transform, or with --augment one box and one flip per clip")
-    ap.add_argument("--yuv", default=None, choices=["i420", "nv12"],
-                    help="with --augment or --ragged: the decoded frames are 8-bit YUV 4:2:0 ([..., 3H/2, W], PyAV's to_ndarray() of "
-                         "yuv420p / nv12); the conversion to RGB runs inside the device transform")
+    ap.add_argument("--yuv", default=None, choices=["i420", "nv12", "i422", "i444", "i420p10", "i422p10", "i444p10", "p010",
+                                                    "i420p12", "p012", "p016", "i444p16"],
+                    help="with --augment or --ragged: the decoded frames are YUV ([..., rows, W], PyAV's to_ndarray() of yuv420p / "
+                         "nv12 / yuv422p / yuv444p / yuv420p10le / p010le ..., uint16 above 8 bits); the conversion to RGB runs inside "
+                         "the device transform")
     return ap
 
 
@@ -160,8 +162,12 @@ def main():
     if a.augment is not None:
         if not a.uint8:                                     # frames as a decoder leaves them: uint8 [n, 1, T, H, W, 3]
             H, W = (int(v) for v in a.raw_frames.split(","))
-            data.video = torch.randint(0, 256, data.video.shape[:3] + ((H * 3 // 2, W) if a.yuv else (H, W, 3)), dtype=torch.uint8,
-                                       generator=torch.Generator().manual_seed(rank))
+            g = torch.Generator().manual_seed(rank)
+            if a.yuv:
+                from eval_synthetic import yuv_frames
+                data.video = yuv_frames(a.yuv, data.video.shape[:3], H, W, g)
+            else:
+                data.video = torch.randint(0, 256, data.video.shape[:3] + (H, W, 3), dtype=torch.uint8, generator=g)
         augment = TrainFrameTransform(224, crop=a.augment, flip=bool(a.flip), seed=rank)
         if a.yuv:
             augment = YuvTrainFrameTransform(224, layout=a.yuv, crop=a.augment, flip=bool(a.flip), seed=rank)

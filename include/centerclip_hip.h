@@ -825,8 +825,9 @@ int cc_collate_crop_flip_u8(const void* src, size_t src_bytes, int32_t fmt, cons
  * Every entry point takes src_bytes and checks, before any launch, that every address the descriptor can form for (F, H, W)
  * lies inside [0, src_bytes): a descriptor that fails, a negative field, a pitch shorter than its row, a c_step outside
  * {1, 2}, a matrix or range outside {0, 1}: CC_ERR_INVALID.  Sources may start at ANY byte address, H and W may be odd;
- * 4 <= H, W <= 8192, else CC_ERR_UNSUPPORTED (as the RGB entries).  Not taken (the check refuses what can be told): 4:2:2,
- * 4:4:4, 10-bit (P010), interlaced chroma siting, chroma interpolation, BT.2020, alpha.
+ * 4 <= H, W <= 8192, else CC_ERR_UNSUPPORTED (as the RGB entries).  Not taken by THESE entries: 4:2:2, 4:4:4 and samples
+ * of more than 8 bits (P010) - the cc_*_yuv_u8 entries below take them; by neither: interlaced chroma siting, chroma
+ * interpolation, BT.2020, alpha.
  *
  *   cc_yuv420_to_rgb_u8             the conversion alone -> [F, H, W, 3] / [F, 3, H, W] (dst_fmt); one launch.
  *   cc_resize_crop_yuv420_u8        cc_resize_crop_u8 with this source: the same plan, the same workspace
@@ -865,6 +866,95 @@ int cc_collate_resize_crop_yuv420_u8(const void* src, size_t src_bytes, int32_t 
 int cc_collate_crop_flip_yuv420_u8(const void* src, size_t src_bytes, int32_t kind, int32_t matrix, int32_t range,
                                    const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out,
                                    int32_t n_px, void* dst, int32_t dst_fmt, void* stream);
+
+/* YUV sources in general: the other pixel formats decoders emit - 4:2:2 and 4:4:4 sampling, and samples of 10, 12 or 16 bits in
+ * 16-bit words (a hardware decoder's pitched P010 / P016 surfaces, a software decoder's yuv420p10le, yuv422p, yuv444p, ...) -
+ * through the same fetch, so everything behind it is the code of the RGB and the 4:2:0 entries.  The cc_*_yuv420_u8 entries
+ * above are these with sub_x = sub_y = 1, depth 8, shift 0: one code path, the same bytes.  DESIGN.md, "YUV sources".
+ *
+ * THE CONVERSION for depth d in {8, 10, 12, 16}.  A sample is n = word >> shift.  d = 8: word is a byte and shift is 0.
+ * Otherwise word is a little-endian 16-bit word and 0 <= shift <= 16 - d: P010 is d = 10 with shift 6, yuv420p10le d = 10 with
+ * shift 0, P016 d = 16 with shift 0.  Bits below shift are discarded, whatever they hold.  Real formula, Kr, Kb, Kg as above:
+ *   limited range: oy = 16 2^(d-8), sy = 255 / (219 2^(d-8)), sc = 255 / (224 2^(d-8))
+ *   full range:    oy = 0, sy = sc = 255 / (2^d - 1)
+ *   chroma centre 2^(d-1);  R = sy (Y - oy) + 2 (1 - Kr) sc (V - centre)
+ *                           G = sy (Y - oy) - 2 Kb (1 - Kb) / Kg sc (U - centre) - 2 Kr (1 - Kr) / Kg sc (V - centre)
+ *                           B = sy (Y - oy) + 2 (1 - Kb) sc (U - centre)
+ * Integer definition: C = floor(c 2^Q + 0.5) computed in double, Q = 16 for d = 8 (the tables and bytes above) and Q = 20 for
+ * d > 8 (cc_yuv_coefficients_depth); each channel is clamp((sum + 2^(Q-1)) >> Q, 0, 255) in int32, >> an arithmetic shift.
+ *                       CY    CRV    CGU    CGV    CBU
+ *   d 10 601 limited  305236 418389 102698 213115 528805        d 16 601 limited  4769 6537 1605 3330 8263
+ *   d 10 601 full     261375 366448  89949 186658 463157        d 16 709 limited  4769 7343  873 2183 8652
+ *   d 10 709 limited  305236 469956  55902 139699 553753
+ *   d 10 709 full     261375 411614  48962 122356 485008
+ * For samples 0 .. 2^d - 1 the accumulator stays at or below 5.8e8 < 2^31 and every channel is within 1 LSB of
+ * clamp(floor(real + 0.5)); a larger n (possible only where shift < 16 - d) is outside the definition - no address depends on a
+ * sample.  Chroma is REPLICATED: luma (y, x) uses chroma (y >> sub_y, x >> sub_x); chroma planes have
+ * ceil(H / 2^sub_y) x ceil(W / 2^sub_x) samples, odd H and W are legal.
+ * OUT OF SCOPE: BT.2020 and any PQ / HLG tone mapping (10-bit frames are converted as the SDR signal their matrix describes);
+ * packed formats (YUYV, UYVY), big-endian words, 4:1:1, alpha planes; interpolated chroma siting and dithering.
+ *
+ * cc_yuv_layout, all positions in bytes from the source's first byte: frame f at f * frame_stride; in a frame Y(y, x) at
+ * y * y_pitch + x * B (B = bytes of a sample, 1 at depth 8, else 2), Cb(cy, cx) at u_offset + cy * c_pitch + cx * c_step and Cr
+ * the same from v_offset; c_step = B where the chroma planes are separate, 2 B where interleaved; sub_x, sub_y: log2 of the
+ * chroma subsampling, 0 or 1.  cc_yuv_layout_tight fills it for tight frames of a named format one behind the other (Y plane,
+ * then U and V planes, or one interleaved UV plane) and returns the bytes of one frame (0, and nothing written, for another
+ * format, a matrix / range outside {0, 1} or H, W outside 1 .. 8192):
+ *                 8-bit            10-bit (shift)                     12-bit (shift)           16-bit
+ *   planar        I420 I422 I444   I420P10 I422P10 I444P10 (0)        I420P12 (0)              I444P16
+ *   semi-planar   NV12             P010 (6)                           P012 (4)                 P016
+ *
+ * DESCRIPTOR CHECK before any launch.  CC_ERR_INVALID: a depth outside {8, 10, 12, 16}; a shift outside 0 .. 16 - depth, or
+ * nonzero at depth 8; sub_x / sub_y outside {0, 1}; a c_step other than one or two samples; a matrix / range outside {0, 1}.
+ * Then sizes outside 4 .. 8192: CC_ERR_UNSUPPORTED.  Then CC_ERR_INVALID again: a negative field; a pitch shorter than its row
+ * in bytes; for 16-bit samples an odd src address, offset, pitch or frame stride; any luma or chroma byte of (F, H, W) at or
+ * beyond src_bytes.  8-bit sources may start at ANY byte address.
+ *
+ *   cc_yuv_to_rgb_u8              the conversion alone -> [F, H, W, 3] / [F, 3, H, W] (dst_fmt); one launch.
+ *   cc_resize_crop_yuv_u8         cc_resize_crop_u8 with this source: the same plan and workspace, at most two launches.
+ *   cc_resized_crop_flip_yuv_u8   cc_resized_crop_flip_u8 with this source: one launch, the same box rules.
+ *   cc_collate_resize_crop_yuv_u8 / cc_collate_crop_flip_yuv_u8   the ragged forms: the packed buffer holds TIGHT frames of one
+ *                                 named format (another: CC_ERR_INVALID); the clip table's and the rows' byte offsets count in
+ *                                 those frames and, for 16-bit samples, are even (an odd clip offset: CC_ERR_INVALID; an odd
+ *                                 row offset: a zero frame); the same row tables, launch bound and zero-frame rule.
+ * CONTRACT of the four fused entries: dst is bit for bit what the RGB entry gives on cc_yuv_to_rgb_u8's output, and no
+ * source-sized RGB image is stored. */
+#define CC_YUV_I420 0          /* = CC_YUV420_I420 */
+#define CC_YUV_NV12 1          /* = CC_YUV420_NV12 */
+#define CC_YUV_I422 2
+#define CC_YUV_I444 3
+#define CC_YUV_I420P10 4
+#define CC_YUV_I422P10 5
+#define CC_YUV_I444P10 6
+#define CC_YUV_P010 7
+#define CC_YUV_I420P12 8
+#define CC_YUV_P012 9
+#define CC_YUV_P016 10
+#define CC_YUV_I444P16 11
+#define CC_YUV_FORMATS 12
+typedef struct cc_yuv_layout {
+    int64_t frame_stride, y_pitch, u_offset, v_offset, c_pitch;
+    int32_t c_step, sub_x, sub_y, depth, shift, matrix, range;
+} cc_yuv_layout;
+/* out5: (CY, CRV, CGU, CGV, CBU) of the depth; CC_ERR_INVALID for a matrix / range outside {0, 1} or a depth outside
+ * {8, 10, 12, 16}; no GPU needed */
+int cc_yuv_coefficients_depth(int32_t matrix, int32_t range, int32_t depth, int32_t* out5);
+size_t cc_yuv_layout_tight(int32_t format, int32_t H, int32_t W, int32_t matrix, int32_t range, cc_yuv_layout* out);
+int cc_yuv_to_rgb_u8(const void* src, size_t src_bytes, const cc_yuv_layout* layout, int32_t F, int32_t H, int32_t W, void* dst,
+                     int32_t dst_fmt, void* stream);
+int cc_resize_crop_yuv_u8(const void* src, size_t src_bytes, const cc_yuv_layout* layout, int32_t F, int32_t H, int32_t W,
+                          const void* plan_dev, int32_t n_px, int32_t resize, void* dst, int32_t dst_fmt, void* ws,
+                          size_t ws_bytes, void* stream);
+int cc_resized_crop_flip_yuv_u8(const void* src, size_t src_bytes, const cc_yuv_layout* layout, int32_t F, int32_t H, int32_t W,
+                                int32_t frames_per_clip, const int32_t* boxes_dev, int32_t n_px, int32_t interp, void* dst,
+                                int32_t dst_fmt, void* stream);
+int cc_collate_resize_crop_yuv_u8(const void* src, size_t src_bytes, int32_t format, int32_t matrix, int32_t range,
+                                  const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out,
+                                  const int32_t* plans_dev, size_t plans_ints, int32_t n_px, int32_t resize, void* dst,
+                                  int32_t dst_fmt, void* ws, size_t ws_bytes, void* stream);
+int cc_collate_crop_flip_yuv_u8(const void* src, size_t src_bytes, int32_t format, int32_t matrix, int32_t range,
+                                const int64_t* clips_host, int32_t n_clips, const int64_t* rows_dev, int32_t n_out, int32_t n_px,
+                                void* dst, int32_t dst_fmt, void* stream);
 
 /* S2 - the meanP similarity tail, CLIP4Clip._loose_similarity (modules/clip4clip.py:357-366) with
  * _mean_pooling_for_similarity_visual (:305-316):
