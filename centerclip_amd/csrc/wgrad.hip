@@ -174,7 +174,10 @@ __global__ __launch_bounds__(256, 2) void wgrad_tn_kernel(WgradArgs a) {
         __builtin_amdgcn_s_barrier();
     };
 
-    // prologue: stages 0 .. 2 requested, stage 0 landed
+    // prologue: stages 0 .. 2 requested, stage 0 landed.  nk <= 0 is an empty slice: rows_per_slice is rounded up to whole
+    // stages, so the last slices can begin behind row M (m_end = M < m_begin; M = 9,856 at 512 x 512: slice 31 of 32).  It must
+    // request nothing - stage() would clamp its rows to m_end - 1, a row of another slice - and runs no step: its zero
+    // accumulators are stored as the partial tile the reduce adds (tests/test_wgrad_gpu.py::test_slice_plans).
     if (nk > 0) stage(0, 0);
     if (nk > 1) stage(1, 1);
     if (nk > 2) stage(2, 2);
