@@ -143,38 +143,23 @@ def declare(lib):
     lib.cc_collate_resize_crop_u8.restype = c.c_int
     lib.cc_collate_crop_flip_u8.argtypes = [vp, sz, i32, vp, i32, vp, i32, i32, vp, i32, vp]
     lib.cc_collate_crop_flip_u8.restype = c.c_int
-    from ._lib import Yuv420Layout
-    lay = c.POINTER(Yuv420Layout)
     lib.cc_yuv_coefficients.argtypes = [i32, i32, vp]
     lib.cc_yuv_coefficients.restype = c.c_int
-    lib.cc_yuv420_layout_tight.argtypes = [i32, i32, i32, i32, i32, lay]
-    lib.cc_yuv420_layout_tight.restype = sz
-    lib.cc_yuv420_to_rgb_u8.argtypes = [vp, sz, lay, i32, i32, i32, vp, i32, vp]
-    lib.cc_yuv420_to_rgb_u8.restype = c.c_int
-    lib.cc_resize_crop_yuv420_u8.argtypes = [vp, sz, lay, i32, i32, i32, vp, i32, i32, vp, i32, vp, sz, vp]
-    lib.cc_resize_crop_yuv420_u8.restype = c.c_int
-    lib.cc_resized_crop_flip_yuv420_u8.argtypes = [vp, sz, lay, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp]
-    lib.cc_resized_crop_flip_yuv420_u8.restype = c.c_int
-    lib.cc_collate_resize_crop_yuv420_u8.argtypes = [vp, sz, i32, i32, i32, vp, i32, vp, i32, vp, sz, i32, i32, vp, i32, vp, sz, vp]
-    lib.cc_collate_resize_crop_yuv420_u8.restype = c.c_int
-    lib.cc_collate_crop_flip_yuv420_u8.argtypes = [vp, sz, i32, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp]
-    lib.cc_collate_crop_flip_yuv420_u8.restype = c.c_int
-    from ._lib import YuvLayout
-    glay = c.POINTER(YuvLayout)
     lib.cc_yuv_coefficients_depth.argtypes = [i32, i32, i32, vp]
     lib.cc_yuv_coefficients_depth.restype = c.c_int
-    lib.cc_yuv_layout_tight.argtypes = [i32, i32, i32, i32, i32, glay]
-    lib.cc_yuv_layout_tight.restype = sz
-    lib.cc_yuv_to_rgb_u8.argtypes = [vp, sz, glay, i32, i32, i32, vp, i32, vp]
-    lib.cc_yuv_to_rgb_u8.restype = c.c_int
-    lib.cc_resize_crop_yuv_u8.argtypes = [vp, sz, glay, i32, i32, i32, vp, i32, i32, vp, i32, vp, sz, vp]
-    lib.cc_resize_crop_yuv_u8.restype = c.c_int
-    lib.cc_resized_crop_flip_yuv_u8.argtypes = [vp, sz, glay, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp]
-    lib.cc_resized_crop_flip_yuv_u8.restype = c.c_int
-    lib.cc_collate_resize_crop_yuv_u8.argtypes = [vp, sz, i32, i32, i32, vp, i32, vp, i32, vp, sz, i32, i32, vp, i32, vp, sz, vp]
-    lib.cc_collate_resize_crop_yuv_u8.restype = c.c_int
-    lib.cc_collate_crop_flip_yuv_u8.argtypes = [vp, sz, i32, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp]
-    lib.cc_collate_crop_flip_yuv_u8.restype = c.c_int
+    from ._lib import Yuv420Layout, YuvLayout
+    for yuv, struct in (("yuv420", Yuv420Layout), ("yuv", YuvLayout)):          # the 4:2:0 entries and the general ones: one shape
+        lay = c.POINTER(struct)
+        getattr(lib, "cc_%s_layout_tight" % yuv).argtypes = [i32, i32, i32, i32, i32, lay]
+        getattr(lib, "cc_%s_layout_tight" % yuv).restype = sz
+        for entry, argtypes in (("cc_%s_to_rgb_u8", [vp, sz, lay, i32, i32, i32, vp, i32, vp]),
+                                ("cc_resize_crop_%s_u8", [vp, sz, lay, i32, i32, i32, vp, i32, i32, vp, i32, vp, sz, vp]),
+                                ("cc_resized_crop_flip_%s_u8", [vp, sz, lay, i32, i32, i32, i32, vp, i32, i32, vp, i32, vp]),
+                                ("cc_collate_resize_crop_%s_u8", [vp, sz, i32, i32, i32, vp, i32, vp, i32, vp, sz, i32, i32, vp, i32, vp,
+                                                                  sz, vp]),
+                                ("cc_collate_crop_flip_%s_u8", [vp, sz, i32, i32, i32, vp, i32, vp, i32, i32, vp, i32, vp])):
+            getattr(lib, entry % yuv).argtypes = argtypes
+            getattr(lib, entry % yuv).restype = c.c_int
     lib.cc_clip_encode_frames.argtypes = [c.POINTER(VitModel), c.POINTER(Frames), i32, i32, vp, vp, vp,
                                           c.POINTER(TextModel), vp, i32, i32, vp, vp, sz, vp]
     lib.cc_clip_encode_frames.restype = c.c_int

@@ -47,6 +47,14 @@ def _check(frames):
     return T._raw_frames_geometry(frames.shape)
 
 
+def _run(op, args, out, shape):
+    """The tail of every transform: torch.ops.centerclip.<op> as a fresh tensor viewed as ``shape``, or <op>_out into ``out``."""
+    if out is None:
+        return getattr(torch.ops.centerclip, op)(*args).view(shape)
+    getattr(torch.ops.centerclip, op + "_out")(*args, out)
+    return out
+
+
 def resize_center_crop(frames, n_px=224, resize=True):
     """uint8 [F,H,W,3] / [F,3,H,W] / 6-D video -> the same form at n_px x n_px (torch.ops.centerclip.resize_center_crop)."""
     _check(frames)
@@ -86,10 +94,7 @@ class FrameTransform:
                 raise ValueError("frames of the model's resolution pass through untouched: there is nothing to write to `out`")
             return frames
         self.plan(H, W, frames.device)
-        if out is None:
-            return torch.ops.centerclip.resize_center_crop(frames, self.n_px, self.resize)
-        torch.ops.centerclip.resize_center_crop_out(frames, self.n_px, self.resize, out)
-        return out
+        return _run("resize_center_crop", (frames, self.n_px, self.resize), out, self.output_shape(frames.shape))
 
 
 _INTERP = {"bilinear": 0, "bicubic": 1, 0: 0, 1: 1}
@@ -205,21 +210,23 @@ class TrainFrameTransform:
     def output_shape(self, shape):
         return T._resize_crop_shape(shape, self.n_px)
 
+    def _device_boxes(self, boxes, device):
+        """A host box table is uploaded (not inside a stream capture), a device tensor is used as it is."""
+        if boxes.is_cuda:
+            return boxes
+        if torch.cuda.is_current_stream_capturing():
+            raise L.CenterClipHipError("%s.apply: a host box table cannot be uploaded while the stream is being captured - pass a "
+                                       "device tensor and refill it between replays" % type(self).__name__)
+        return boxes.to(device=device, dtype=torch.int32)
+
     def apply(self, frames, boxes, out=None, frames_per_clip=None):
         """The device op on given boxes.  ``boxes``: the table of ``sample`` - a host tensor is uploaded (not inside a stream
         capture), a device tensor is used as it is: no upload, and a captured call follows what the buffer holds at replay.
         ``frames_per_clip``: from the shape by default (6-D: T; 4-D: all frames are one clip).  ``out`` as FrameTransform's."""
         _check(frames)
         fpc = self._clips(frames.shape)[1] if frames_per_clip is None else int(frames_per_clip)
-        if not boxes.is_cuda:
-            if torch.cuda.is_current_stream_capturing():
-                raise L.CenterClipHipError("TrainFrameTransform.apply: a host box table cannot be uploaded while the stream is "
-                                           "being captured - pass a device tensor and refill it between replays")
-            boxes = boxes.to(device=frames.device, dtype=torch.int32)
-        if out is None:
-            return torch.ops.centerclip.resized_crop_flip(frames, boxes, self.n_px, fpc, self.interp)
-        torch.ops.centerclip.resized_crop_flip_out(frames, boxes, self.n_px, fpc, self.interp, out)
-        return out
+        return _run("resized_crop_flip", (frames, self._device_boxes(boxes, frames.device), self.n_px, fpc, self.interp), out,
+                    self.output_shape(frames.shape))
 
     def __call__(self, frames, out=None):
         _, H, W = _check(frames)
@@ -436,11 +443,8 @@ class ClipCollate:
         return self._eval_op(packed, rows_dev, plans_dev, clips, out)
 
     def _eval_op(self, packed, rows_dev, plans_dev, clips, out):
-        if out is None:
-            return torch.ops.centerclip.collate_clips(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
-                                                      packed.chw).view(self.output_shape(packed))
-        torch.ops.centerclip.collate_clips_out(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize, packed.chw, out)
-        return out
+        return _run("collate_clips", (packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize, packed.chw), out,
+                    self.output_shape(packed))
 
     def sample(self, packed):
         """-> int32 [B, 5] on the host, rows (top, left, height, width, flip): for the clips in batch order, each the draws of
@@ -473,11 +477,7 @@ class ClipCollate:
         return self._train_op(packed, dev, tab.reshape(-1).tolist(), out)
 
     def _train_op(self, packed, rows_dev, clips, out):
-        if out is None:
-            return torch.ops.centerclip.collate_clips_crop_flip(packed.data, rows_dev, clips, self.n_px,
-                                                                packed.chw).view(self.output_shape(packed))
-        torch.ops.centerclip.collate_clips_crop_flip_out(packed.data, rows_dev, clips, self.n_px, packed.chw, out)
-        return out
+        return _run("collate_clips_crop_flip", (packed.data, rows_dev, clips, self.n_px, packed.chw), out, self.output_shape(packed))
 
     def __call__(self, packed, index=None, out=None):
         if self.train is None:
@@ -519,6 +519,11 @@ def _yuv_geometry(shape, layout="i420"):
     return tuple(shape[:-2]), H, int(shape[-1])
 
 
+def _yuv_frame_dtypes(layout):
+    """The dtypes of a named layout's frames: bytes at depth 8, 16-bit words (either signedness, the same bits) above."""
+    return (torch.uint8,) if T.YUV_FORMATS[layout][3] == 8 else (torch.uint16, torch.int16)
+
+
 class _YuvSource:
     """What the YUV transforms share: the colour description, the checks, the tight layout of a frame size."""
 
@@ -531,7 +536,7 @@ class _YuvSource:
     @property
     def frame_dtypes(self):
         """The dtypes of this layout's frames (what DeviceFeeder recognises as the video of a batch)."""
-        return (torch.uint8,) if T.YUV_FORMATS[self.layout][3] == 8 else (torch.uint16, torch.int16)
+        return _yuv_frame_dtypes(self.layout)
 
     def _source(self, frames):
         """-> (leading dimensions, F, H, W, the twelve layout integers) of device frames [..., rows, W]"""
@@ -581,11 +586,8 @@ class YuvFrameTransform(_YuvSource):
     def __call__(self, frames, out=None):
         lead, F, H, W, lay = self._source(frames)
         T.resize_plan(H, W, self.n_px, self.resize, frames.device)
-        if out is None:
-            return torch.ops.centerclip.resize_center_crop_yuv(frames, F, H, W, lay, self.n_px, self.resize,
-                                                               False).view(lead + (self.n_px, self.n_px, 3))
-        torch.ops.centerclip.resize_center_crop_yuv_out(frames, F, H, W, lay, self.n_px, self.resize, False, out)
-        return out
+        return _run("resize_center_crop_yuv", (frames, F, H, W, lay, self.n_px, self.resize, False), out,
+                    lead + (self.n_px, self.n_px, 3))
 
 
 class YuvTrainFrameTransform(_YuvSource, TrainFrameTransform):
@@ -600,16 +602,8 @@ class YuvTrainFrameTransform(_YuvSource, TrainFrameTransform):
     def apply(self, frames, boxes, out=None, frames_per_clip=None):
         lead, F, H, W, lay = self._source(frames)
         fpc = self._clips(lead + (H, W, 3))[1] if frames_per_clip is None else int(frames_per_clip)
-        if not boxes.is_cuda:
-            if torch.cuda.is_current_stream_capturing():
-                raise L.CenterClipHipError("YuvTrainFrameTransform.apply: a host box table cannot be uploaded while the stream is "
-                                           "being captured - pass a device tensor and refill it between replays")
-            boxes = boxes.to(device=frames.device, dtype=torch.int32)
-        if out is None:
-            return torch.ops.centerclip.resized_crop_flip_yuv(frames, F, H, W, lay, boxes, self.n_px, fpc, self.interp,
-                                                              False).view(lead + (self.n_px, self.n_px, 3))
-        torch.ops.centerclip.resized_crop_flip_yuv_out(frames, F, H, W, lay, boxes, self.n_px, fpc, self.interp, False, out)
-        return out
+        return _run("resized_crop_flip_yuv", (frames, F, H, W, lay, self._device_boxes(boxes, frames.device), self.n_px, fpc,
+                                              self.interp, False), out, lead + (self.n_px, self.n_px, 3))
 
     def __call__(self, frames, out=None):
         lead, _, H, W, _ = self._source(frames)
@@ -655,7 +649,7 @@ def pack_yuv_clips(clips, layout="i420"):
     ``YuvClipCollate``."""
     if layout not in T.YUV_FORMATS:
         raise ValueError("pack_yuv_clips: layout must be one of %s, got %r" % (", ".join(sorted(T.YUV_FORMATS)), layout))
-    dtypes = (torch.uint8,) if T.YUV_FORMATS[layout][3] == 8 else (torch.uint16, torch.int16)
+    dtypes = _yuv_frame_dtypes(layout)
     clips = [torch.from_numpy(np.ascontiguousarray(c)) if isinstance(c, np.ndarray) else c for c in clips]
     if not clips:
         raise ValueError("pack_yuv_clips: no clips")
@@ -690,8 +684,7 @@ class YuvClipCollate(_YuvSource, ClipCollate):
         ClipCollate.__init__(self, n_px, max_frames, resize, train)
         self._init_yuv(layout, matrix, full_range)
 
-    def output_shape(self, packed):
-        return ClipCollate.output_shape(self, packed)
+    output_shape = ClipCollate.output_shape          # of a PackedClips; _YuvSource's, first in the MRO, is the frame transforms'
 
     def _frame_bytes(self, tab):
         return _yuv_frame_bytes(self.layout, tab[:, 2], tab[:, 3])
@@ -710,19 +703,12 @@ class YuvClipCollate(_YuvSource, ClipCollate):
         return T.YUV_FORMATS[self.layout][0], T.YUV_MATRICES[self.matrix], self.full_range
 
     def _eval_op(self, packed, rows_dev, plans_dev, clips, out):
-        if out is None:
-            return torch.ops.centerclip.collate_clips_yuv(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize,
-                                                          *self._kind(), False).view(self.output_shape(packed))
-        torch.ops.centerclip.collate_clips_yuv_out(packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize, *self._kind(),
-                                                   False, out)
-        return out
+        return _run("collate_clips_yuv", (packed.data, rows_dev, plans_dev, clips, self.n_px, self.resize, *self._kind(), False), out,
+                    self.output_shape(packed))
 
     def _train_op(self, packed, rows_dev, clips, out):
-        if out is None:
-            return torch.ops.centerclip.collate_clips_crop_flip_yuv(packed.data, rows_dev, clips, self.n_px, *self._kind(),
-                                                                    False).view(self.output_shape(packed))
-        torch.ops.centerclip.collate_clips_crop_flip_yuv_out(packed.data, rows_dev, clips, self.n_px, *self._kind(), False, out)
-        return out
+        return _run("collate_clips_crop_flip_yuv", (packed.data, rows_dev, clips, self.n_px, *self._kind(), False), out,
+                    self.output_shape(packed))
 
 
 __all__ = ["resize_center_crop", "FrameTransform", "TrainFrameTransform", "PackedClips", "pack_clips", "ClipCollate",

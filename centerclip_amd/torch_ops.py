@@ -954,496 +954,16 @@ def resize_plan(H, W, n_px, resize, device):
     return plan
 
 
-def _resize_crop_shape(shape, n_px):
-    chw, _, _ = _raw_frames_geometry(shape)
-    return tuple(shape[:-3]) + ((3, n_px, n_px) if chw else (n_px, n_px, 3))
-
-
-def _resize_crop_into(frames, out, n_px, resize):
-    if frames.dtype != torch.uint8 or out.dtype != torch.uint8:
-        raise ValueError("resize_center_crop takes and gives uint8 frames, got %s -> %s" % (frames.dtype, out.dtype))
-    chw, H, W = _raw_frames_geometry(frames.shape)
-    if tuple(out.shape) != _resize_crop_shape(frames.shape, n_px) or not out.is_contiguous():
-        raise ValueError("resize_center_crop: out must be a contiguous %s, got %s"
-                         % (_resize_crop_shape(frames.shape, n_px), tuple(out.shape)))
-    frames = frames.contiguous()
-    F = math.prod(frames.shape[:-3])
-    if F == 0:
-        return
-    lib = L.lib()
-    plan = resize_plan(H, W, n_px, resize, frames.device)
-    nws = lib.cc_resize_crop_workspace_bytes(F, H, W, int(n_px), int(resize))
-    ws = L.workspace(nws, frames.device) if nws else None
-    fmt = 1 if chw else 2
-    L.check(lib.cc_resize_crop_u8(L.ptr(frames), fmt, F, H, W, L.ptr(plan), int(n_px), int(resize), L.ptr(out), fmt,
-                                  L.ptr(ws), ws.numel() if ws is not None else 0, _st(frames)), "cc_resize_crop_u8")
-
-
-@custom_op(NS + "::resize_center_crop", mutates_args=(), device_types="cuda")
-def resize_center_crop(frames: torch.Tensor, n_px: int, resize: bool) -> torch.Tensor:
-    """The loader transform in front of the encoders (cc_resize_crop_u8): uint8 frames [..., H, W, 3] or [..., 3, H, W] of any
-    size -> uint8 [..., n_px, n_px, 3] / [..., 3, n_px, n_px] (the input's layout), byte for byte Pillow's bicubic
-    Resize(n_px) + CenterCrop(n_px) (dataloaders/rawvideo_util.py:16-23); resize=False: the crop alone."""
-    out = _e(*_resize_crop_shape(frames.shape, n_px), like=frames, dtype=torch.uint8)
-    _resize_crop_into(frames, out, n_px, resize)
-    return out
-
-
-@resize_center_crop.register_fake
-def _(frames, n_px, resize):
-    return frames.new_empty(_resize_crop_shape(frames.shape, n_px), dtype=torch.uint8)
-
-
-@custom_op(NS + "::resize_center_crop_out", mutates_args=("out",), device_types="cuda")
-def resize_center_crop_out(frames: torch.Tensor, n_px: int, resize: bool, out: torch.Tensor) -> None:
-    """resize_center_crop into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay)."""
-    _resize_crop_into(frames, out, n_px, resize)
-
-
-@resize_center_crop_out.register_fake
-def _(frames, n_px, resize, out):
-    return None
-
-
-def _resized_crop_flip_check(frames, boxes, n_px, frames_per_clip, interp):
-    """The checks the real and the fake kernels share -> (channels_first, H, W, F)."""
-    if frames.dtype != torch.uint8:
-        raise ValueError("resized_crop_flip takes uint8 frames, got %s" % frames.dtype)
-    chw, H, W = _raw_frames_geometry(frames.shape)
-    F = math.prod(frames.shape[:-3])
-    if frames_per_clip < 1 or interp not in (0, 1) or n_px < 1:
-        raise ValueError("resized_crop_flip: frames_per_clip >= 1, n_px >= 1 and interp 0 (bilinear) / 1 (bicubic), got %d, %d, %d"
-                         % (frames_per_clip, n_px, interp))
-    clips = -(-F // frames_per_clip)
-    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (clips, 5):
-        raise ValueError("resized_crop_flip: boxes must be int32 [%d, 5] rows (top, left, height, width, flip) for %d frames in "
-                         "clips of %d, got %s %s" % (clips, F, frames_per_clip, boxes.dtype, tuple(boxes.shape)))
-    return chw, H, W, F
-
-
-def _resized_crop_flip_into(frames, boxes, out, n_px, frames_per_clip, interp):
-    chw, H, W, F = _resized_crop_flip_check(frames, boxes, n_px, frames_per_clip, interp)
-    L.require_device(frames, boxes, out)
-    if out.dtype != torch.uint8 or tuple(out.shape) != _resize_crop_shape(frames.shape, n_px) or not out.is_contiguous():
-        raise ValueError("resized_crop_flip: out must be a contiguous uint8 %s, got %s %s"
-                         % (_resize_crop_shape(frames.shape, n_px), out.dtype, tuple(out.shape)))
-    if F == 0:
-        return
-    frames, boxes = frames.contiguous(), boxes.contiguous()
-    fmt = 1 if chw else 2
-    L.check(L.lib().cc_resized_crop_flip_u8(L.ptr(frames), fmt, F, H, W, int(frames_per_clip), L.ptr(boxes), int(n_px),
-                                            int(interp), L.ptr(out), fmt, _st(frames)), "cc_resized_crop_flip_u8")
-
-
-@custom_op(NS + "::resized_crop_flip", mutates_args=(), device_types="cuda")
-def resized_crop_flip(frames: torch.Tensor, boxes: torch.Tensor, n_px: int, frames_per_clip: int, interp: int) -> torch.Tensor:
-    """Train-time augmentation (cc_resized_crop_flip_u8): uint8 frames [..., H, W, 3] or [..., 3, H, W] -> uint8
-    [..., n_px, n_px, 3] / [..., 3, n_px, n_px] (the input's layout); the frames count in clips of frames_per_clip and clip i
-    is cropped to boxes[i] = (top, left, height, width, flip) (int32, on the device - the kernel reads it, nothing is copied or
-    read back), resized to n_px x n_px with interp 0 bilinear / 1 bicubic (F.interpolate, align_corners=False, no antialias,
-    rounded to bytes) and mirrored where flip != 0.  A row outside the frame gives zeros for its clip."""
-    out = _e(*_resize_crop_shape(frames.shape, n_px), like=frames, dtype=torch.uint8)
-    _resized_crop_flip_into(frames, boxes, out, n_px, frames_per_clip, interp)
-    return out
-
-
-@resized_crop_flip.register_fake
-def _(frames, boxes, n_px, frames_per_clip, interp):
-    _resized_crop_flip_check(frames, boxes, n_px, frames_per_clip, interp)
-    return frames.new_empty(_resize_crop_shape(frames.shape, n_px), dtype=torch.uint8)
-
-
-@custom_op(NS + "::resized_crop_flip_out", mutates_args=("out",), device_types="cuda")
-def resized_crop_flip_out(frames: torch.Tensor, boxes: torch.Tensor, n_px: int, frames_per_clip: int, interp: int,
-                          out: torch.Tensor) -> None:
-    """resized_crop_flip into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay)."""
-    _resized_crop_flip_into(frames, boxes, out, n_px, frames_per_clip, interp)
-
-
-@resized_crop_flip_out.register_fake
-def _(frames, boxes, n_px, frames_per_clip, interp, out):
-    _resized_crop_flip_check(frames, boxes, n_px, frames_per_clip, interp)
-    return None
-
-
+# ------------------------------------------------------------------------------------------ frame ops
+# Four operations - resize + centre crop, resized crop + flip and the two ragged collates - and a conversion, on three kinds of
+# source.  A *source* (RGB, YUV420, YUV below) holds what differs between the kinds: how an op's arguments give the frames and
+# the C entry's source arguments, what is checked about them, the shape of the result, what ``out`` may be and the names of the
+# C entries.  An *operation* is written once, ``body(S, name, out, *args) -> (src, the result's shape, launch)``: every check,
+# then the launch as a closure.  ``_frame_ops`` registers a body for a source; the allocating op, its ``_out`` twin and both
+# fake kernels run that one body - the fake ones drop the launch - so a fake kernel checks exactly what its real kernel does.
 COLLATE_ROW, COLLATE_BOX_ROW, COLLATE_MAX_PLANES = 6, 10, 4096      # CC_COLLATE_ROW / _BOX_ROW / _MAX_PLANES of the header
-
-
-def _collate_shape(n_out, n_px, chw):
-    return (n_out, 3, n_px, n_px) if chw else (n_out, n_px, n_px, 3)
-
-
-def _collate_check(name, src, rows, clips, n_px, chw, row_ints, out=None):
-    """The checks the real and the fake kernels of the ragged-batch ops share -> n_out."""
-    if src.dtype != torch.uint8 or src.dim() != 1:
-        raise ValueError("%s: the packed clips are one 1-D uint8 buffer, got %s %s" % (name, src.dtype, tuple(src.shape)))
-    if rows.dtype != torch.int64 or rows.dim() != 2 or rows.shape[1] != row_ints or rows.shape[0] < 1:
-        raise ValueError("%s: the frame table is int64 [n_out >= 1, %d], got %s %s" % (name, row_ints, rows.dtype, tuple(rows.shape)))
-    if len(clips) == 0 or len(clips) % 4:
-        raise ValueError("%s: the clip table is B >= 1 rows of (byte offset, frames, H, W), got %d values" % (name, len(clips)))
-    if n_px < 1:
-        raise ValueError("%s: n_px >= 1, got %d" % (name, n_px))
-    n_out = int(rows.shape[0])
-    if out is not None and (out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() < 3
-                            or tuple(out.shape[-3:]) != _collate_shape(n_out, n_px, chw)[1:]
-                            or out.numel() != n_out * 3 * n_px * n_px):
-        raise ValueError("%s: out must be contiguous uint8 frames [..., %s] with %d frames in all, got %s %s"
-                         % (name, ", ".join(map(str, _collate_shape(n_out, n_px, chw)[1:])), n_out, out.dtype, tuple(out.shape)))
-    return n_out
-
-
-def _clips_host(clips):
-    return (ctypes.c_int64 * len(clips))(*clips)
-
-
-def _collate_into(src, rows, plans, clips, n_px, resize, chw, out):
-    n_out = _collate_check("collate_clips", src, rows, clips, n_px, chw, COLLATE_ROW, out)
-    if plans.dtype != torch.int32 or plans.dim() != 1:
-        raise ValueError("collate_clips: the plans are one 1-D int32 buffer, got %s %s" % (plans.dtype, tuple(plans.shape)))
-    L.require_device(src, rows, plans, out)
-    src, rows, plans = src.contiguous(), rows.contiguous(), plans.contiguous()
-    lib, table, fmt = L.lib(), _clips_host(clips), 1 if chw else 2
-    nws = lib.cc_collate_resize_crop_workspace_bytes(table, len(clips) // 4, n_out, int(n_px), int(resize))
-    ws = L.workspace(nws, src.device) if nws else None
-    L.check(lib.cc_collate_resize_crop_u8(L.ptr(src), src.numel(), fmt, table, len(clips) // 4, L.ptr(rows), n_out, L.ptr(plans),
-                                          plans.numel(), int(n_px), int(resize), L.ptr(out), fmt, L.ptr(ws), nws, _st(src)),
-            "cc_collate_resize_crop_u8")
-
-
-@custom_op(NS + "::collate_clips", mutates_args=(), device_types="cuda")
-def collate_clips(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
-                  chw: bool) -> torch.Tensor:
-    """A ragged batch of decoded clips -> uniform frames (cc_collate_resize_crop_u8, at most two launches whatever the batch
-    holds).  src: the packed uint8 bytes; clips: the HOST table, flat rows (byte offset, frames, H, W) - what is checked before
-    any launch; rows: int64 [n_out, 6] on the device, per output frame (kind 0 zero / 1 transform, byte offset, H, W, int32 offset
-    of the size's plan in ``plans``, byte offset of the frame's horizontal result in the workspace = i * the per-frame share of
-    cc_collate_resize_crop_workspace_bytes).  -> uint8 [n_out, n_px, n_px, 3] ([n_out, 3, n_px, n_px] with chw), each frame byte
-    for byte resize_center_crop of its source frame, zero frames zero.  preprocess.ClipCollate builds the tables."""
-    out = _e(*_collate_shape(_collate_check("collate_clips", src, rows, clips, n_px, chw, COLLATE_ROW), n_px, chw), like=src,
-             dtype=torch.uint8)
-    _collate_into(src, rows, plans, clips, n_px, resize, chw, out)
-    return out
-
-
-@collate_clips.register_fake
-def _(src, rows, plans, clips, n_px, resize, chw):
-    n_out = _collate_check("collate_clips", src, rows, clips, n_px, chw, COLLATE_ROW)
-    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::collate_clips_out", mutates_args=("out",), device_types="cuda")
-def collate_clips_out(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
-                      chw: bool, out: torch.Tensor) -> None:
-    """collate_clips into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay); every
-    frame of it is written, the zero frames included."""
-    _collate_into(src, rows, plans, clips, n_px, resize, chw, out)
-
-
-@collate_clips_out.register_fake
-def _(src, rows, plans, clips, n_px, resize, chw, out):
-    _collate_check("collate_clips", src, rows, clips, n_px, chw, COLLATE_ROW, out)
-    return None
-
-
-def _collate_crop_flip_into(src, rows, clips, n_px, chw, out):
-    n_out = _collate_check("collate_clips_crop_flip", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
-    L.require_device(src, rows, out)
-    src, rows = src.contiguous(), rows.contiguous()
-    fmt = 1 if chw else 2
-    L.check(L.lib().cc_collate_crop_flip_u8(L.ptr(src), src.numel(), fmt, _clips_host(clips), len(clips) // 4, L.ptr(rows), n_out,
-                                            int(n_px), L.ptr(out), fmt, _st(src)), "cc_collate_crop_flip_u8")
-
-
-@custom_op(NS + "::collate_clips_crop_flip", mutates_args=(), device_types="cuda")
-def collate_clips_crop_flip(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, chw: bool) -> torch.Tensor:
-    """The training form of collate_clips (cc_collate_crop_flip_u8, one launch): rows int64 [n_out, 10] on the device, per output
-    frame (kind, byte offset, H, W, top, left, height, width, flip, interp 0 bilinear / 1 bicubic); each frame byte for byte
-    resized_crop_flip of its source frame with that box, zero frames zero."""
-    out = _e(*_collate_shape(_collate_check("collate_clips_crop_flip", src, rows, clips, n_px, chw, COLLATE_BOX_ROW), n_px, chw),
-             like=src, dtype=torch.uint8)
-    _collate_crop_flip_into(src, rows, clips, n_px, chw, out)
-    return out
-
-
-@collate_clips_crop_flip.register_fake
-def _(src, rows, clips, n_px, chw):
-    n_out = _collate_check("collate_clips_crop_flip", src, rows, clips, n_px, chw, COLLATE_BOX_ROW)
-    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::collate_clips_crop_flip_out", mutates_args=("out",), device_types="cuda")
-def collate_clips_crop_flip_out(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, chw: bool,
-                                out: torch.Tensor) -> None:
-    """collate_clips_crop_flip into a buffer of the caller's; every frame of it is written."""
-    _collate_crop_flip_into(src, rows, clips, n_px, chw, out)
-
-
-@collate_clips_crop_flip_out.register_fake
-def _(src, rows, clips, n_px, chw, out):
-    _collate_check("collate_clips_crop_flip", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
-    return None
-
-
-# ---- YUV 4:2:0 sources (include/centerclip_hip.h, "YUV 4:2:0 sources").  The ops take the source as ANY contiguous uint8 tensor -
-# its bytes are what the layout's offsets count in - with the geometry spelled out: F frames of H x W and ``layout``, the eight
-# integers of cc_yuv420_layout (frame_stride, y_pitch, u_offset, v_offset, c_pitch, c_step, matrix, range).  preprocess.py
-# builds the tight layouts of a decoder's [..., 3H/2, W] arrays; a pitched or odd-sized surface is described by hand.
 YUV_KINDS = {"i420": 0, "nv12": 1}                  # CC_YUV420_I420 / CC_YUV420_NV12
 YUV_MATRICES = {"bt601": 0, "bt709": 1}             # CC_YUV_BT601 / CC_YUV_BT709
-
-
-def yuv420_tight_layout(kind, H, W, matrix, full_range):
-    """-> the eight integers of cc_yuv420_layout_tight for tight ``kind`` ("i420" / "nv12") frames of H x W one behind the
-    other; [0] is the bytes of a frame, H W + 2 ceil(H / 2) ceil(W / 2)."""
-    lay = L.Yuv420Layout()
-    if kind not in YUV_KINDS or matrix not in YUV_MATRICES:
-        raise ValueError("a 4:2:0 layout is 'i420' or 'nv12' and a matrix 'bt601' or 'bt709', got %r, %r" % (kind, matrix))
-    if not L.lib().cc_yuv420_layout_tight(YUV_KINDS[kind], int(H), int(W), YUV_MATRICES[matrix], int(bool(full_range)),
-                                          ctypes.byref(lay)):
-        raise ValueError("no tight %s layout for %s x %s frames (1 .. 8192)" % (kind, H, W))
-    return [getattr(lay, name) for name, _ in L.Yuv420Layout._fields_]
-
-
-def _yuv_source(name, src, F, H, W, layout):
-    """The checks the real and the fake kernels of the YUV ops share."""
-    if src.dtype != torch.uint8:
-        raise ValueError("%s takes the decoder's uint8 planes, got %s" % (name, src.dtype))
-    if len(layout) != 8:
-        raise ValueError("%s: layout is the eight integers of cc_yuv420_layout (frame_stride, y_pitch, u_offset, v_offset, c_pitch, "
-                         "c_step, matrix, range), got %d values" % (name, len(layout)))
-    if F < 0 or H < 1 or W < 1:
-        raise ValueError("%s: F >= 0 frames of H, W >= 1, got %d x %d x %d" % (name, F, H, W))
-
-
-def _yuv_layout(layout):
-    return L.Yuv420Layout(*(int(v) for v in layout))
-
-
-def _yuv_shape(F, n_rows, n_cols, chw):
-    return (F, 3, n_rows, n_cols) if chw else (F, n_rows, n_cols, 3)
-
-
-def _yuv_out_check(name, out, shape):
-    if out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() < 3 or tuple(out.shape[-3:]) != shape[1:] \
-            or out.numel() != math.prod(shape):
-        raise ValueError("%s: out must be contiguous uint8 frames [..., %s] with %d frames in all, got %s %s"
-                         % (name, ", ".join(map(str, shape[1:])), shape[0], out.dtype, tuple(out.shape)))
-
-
-@custom_op(NS + "::yuv420_to_rgb", mutates_args=(), device_types="cuda")
-def yuv420_to_rgb(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], chw: bool) -> torch.Tensor:
-    """The conversion alone (cc_yuv420_to_rgb_u8, one launch): F frames of H x W 8-bit 4:2:0 in ``src`` as ``layout`` describes
-    -> uint8 [F, H, W, 3] ([F, 3, H, W] with chw), the fixed integer conversion of the header, chroma replicated."""
-    _yuv_source("yuv420_to_rgb", src, F, H, W, layout)
-    L.require_device(src)
-    out = _e(*_yuv_shape(F, H, W, chw), like=src, dtype=torch.uint8)
-    if F:
-        src = src.contiguous()
-        L.check(L.lib().cc_yuv420_to_rgb_u8(L.ptr(src), src.numel(), ctypes.byref(_yuv_layout(layout)), F, H, W, L.ptr(out),
-                                            1 if chw else 2, _st(src)), "cc_yuv420_to_rgb_u8")
-    return out
-
-
-@yuv420_to_rgb.register_fake
-def _(src, F, H, W, layout, chw):
-    _yuv_source("yuv420_to_rgb", src, F, H, W, layout)
-    return src.new_empty(_yuv_shape(F, H, W, chw), dtype=torch.uint8)
-
-
-def _resize_crop_yuv420_into(src, F, H, W, layout, n_px, resize, chw, out):
-    _yuv_source("resize_center_crop_yuv420", src, F, H, W, layout)
-    _yuv_out_check("resize_center_crop_yuv420", out, _yuv_shape(F, n_px, n_px, chw))
-    L.require_device(src, out)
-    if F == 0:
-        return
-    src = src.contiguous()
-    lib = L.lib()
-    plan = resize_plan(H, W, n_px, resize, src.device)
-    nws = lib.cc_resize_crop_workspace_bytes(F, H, W, int(n_px), int(resize))
-    ws = L.workspace(nws, src.device) if nws else None
-    L.check(lib.cc_resize_crop_yuv420_u8(L.ptr(src), src.numel(), ctypes.byref(_yuv_layout(layout)), F, H, W, L.ptr(plan), int(n_px),
-                                         int(resize), L.ptr(out), 1 if chw else 2, L.ptr(ws),
-                                         ws.numel() if ws is not None else 0, _st(src)), "cc_resize_crop_yuv420_u8")
-
-
-@custom_op(NS + "::resize_center_crop_yuv420", mutates_args=(), device_types="cuda")
-def resize_center_crop_yuv420(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], n_px: int, resize: bool,
-                              chw: bool) -> torch.Tensor:
-    """resize_center_crop on a 4:2:0 source (cc_resize_crop_yuv420_u8): -> uint8 [F, n_px, n_px, 3] ([F, 3, n_px, n_px] with chw),
-    bit for bit resize_center_crop(yuv420_to_rgb(src)); the first pass converts its taps, no RGB frame of H x W is stored."""
-    out = _e(*_yuv_shape(F, n_px, n_px, chw), like=src, dtype=torch.uint8)
-    _resize_crop_yuv420_into(src, F, H, W, layout, n_px, resize, chw, out)
-    return out
-
-
-@resize_center_crop_yuv420.register_fake
-def _(src, F, H, W, layout, n_px, resize, chw):
-    _yuv_source("resize_center_crop_yuv420", src, F, H, W, layout)
-    return src.new_empty(_yuv_shape(F, n_px, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::resize_center_crop_yuv420_out", mutates_args=("out",), device_types="cuda")
-def resize_center_crop_yuv420_out(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], n_px: int, resize: bool,
-                                  chw: bool, out: torch.Tensor) -> None:
-    """resize_center_crop_yuv420 into a buffer of the caller's."""
-    _resize_crop_yuv420_into(src, F, H, W, layout, n_px, resize, chw, out)
-
-
-@resize_center_crop_yuv420_out.register_fake
-def _(src, F, H, W, layout, n_px, resize, chw, out):
-    return None
-
-
-def _crop_flip_yuv420_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp):
-    _yuv_source("resized_crop_flip_yuv420", src, F, H, W, layout)
-    if frames_per_clip < 1 or interp not in (0, 1) or n_px < 1:
-        raise ValueError("resized_crop_flip_yuv420: frames_per_clip >= 1, n_px >= 1 and interp 0 (bilinear) / 1 (bicubic), got "
-                         "%d, %d, %d" % (frames_per_clip, n_px, interp))
-    clips = -(-F // frames_per_clip)
-    if boxes.dtype != torch.int32 or tuple(boxes.shape) != (clips, 5):
-        raise ValueError("resized_crop_flip_yuv420: boxes must be int32 [%d, 5] rows (top, left, height, width, flip) for %d frames "
-                         "in clips of %d, got %s %s" % (clips, F, frames_per_clip, boxes.dtype, tuple(boxes.shape)))
-
-
-def _crop_flip_yuv420_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out):
-    _crop_flip_yuv420_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
-    _yuv_out_check("resized_crop_flip_yuv420", out, _yuv_shape(F, n_px, n_px, chw))
-    L.require_device(src, boxes, out)
-    if F == 0:
-        return
-    src, boxes = src.contiguous(), boxes.contiguous()
-    L.check(L.lib().cc_resized_crop_flip_yuv420_u8(L.ptr(src), src.numel(), ctypes.byref(_yuv_layout(layout)), F, H, W,
-                                                   int(frames_per_clip), L.ptr(boxes), int(n_px), int(interp), L.ptr(out),
-                                                   1 if chw else 2, _st(src)), "cc_resized_crop_flip_yuv420_u8")
-
-
-@custom_op(NS + "::resized_crop_flip_yuv420", mutates_args=(), device_types="cuda")
-def resized_crop_flip_yuv420(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], boxes: torch.Tensor, n_px: int,
-                             frames_per_clip: int, interp: int, chw: bool) -> torch.Tensor:
-    """resized_crop_flip on a 4:2:0 source (cc_resized_crop_flip_yuv420_u8, one launch): bit for bit
-    resized_crop_flip(yuv420_to_rgb(src), boxes, ...)."""
-    out = _e(*_yuv_shape(F, n_px, n_px, chw), like=src, dtype=torch.uint8)
-    _crop_flip_yuv420_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out)
-    return out
-
-
-@resized_crop_flip_yuv420.register_fake
-def _(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw):
-    _crop_flip_yuv420_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
-    return src.new_empty(_yuv_shape(F, n_px, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::resized_crop_flip_yuv420_out", mutates_args=("out",), device_types="cuda")
-def resized_crop_flip_yuv420_out(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], boxes: torch.Tensor, n_px: int,
-                                 frames_per_clip: int, interp: int, chw: bool, out: torch.Tensor) -> None:
-    """resized_crop_flip_yuv420 into a buffer of the caller's."""
-    _crop_flip_yuv420_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out)
-
-
-@resized_crop_flip_yuv420_out.register_fake
-def _(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out):
-    _crop_flip_yuv420_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
-    return None
-
-
-def _collate_yuv420_check(name, kind, matrix):
-    if kind not in (0, 1) or matrix not in (0, 1):
-        raise ValueError("%s: kind 0 (tight I420) / 1 (tight NV12) and matrix 0 (BT.601) / 1 (BT.709), got %d, %d" % (name, kind, matrix))
-
-
-def _collate_yuv420_into(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw, out):
-    _collate_yuv420_check("collate_clips_yuv420", kind, matrix)
-    n_out = _collate_check("collate_clips_yuv420", src, rows, clips, n_px, chw, COLLATE_ROW, out)
-    if plans.dtype != torch.int32 or plans.dim() != 1:
-        raise ValueError("collate_clips_yuv420: the plans are one 1-D int32 buffer, got %s %s" % (plans.dtype, tuple(plans.shape)))
-    L.require_device(src, rows, plans, out)
-    src, rows, plans = src.contiguous(), rows.contiguous(), plans.contiguous()
-    lib, table = L.lib(), _clips_host(clips)
-    nws = lib.cc_collate_resize_crop_workspace_bytes(table, len(clips) // 4, n_out, int(n_px), int(resize))
-    ws = L.workspace(nws, src.device) if nws else None
-    L.check(lib.cc_collate_resize_crop_yuv420_u8(L.ptr(src), src.numel(), int(kind), int(matrix), int(full_range), table,
-                                                 len(clips) // 4, L.ptr(rows), n_out, L.ptr(plans), plans.numel(), int(n_px),
-                                                 int(resize), L.ptr(out), 1 if chw else 2, L.ptr(ws), nws, _st(src)),
-            "cc_collate_resize_crop_yuv420_u8")
-
-
-@custom_op(NS + "::collate_clips_yuv420", mutates_args=(), device_types="cuda")
-def collate_clips_yuv420(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
-                         kind: int, matrix: int, full_range: bool, chw: bool) -> torch.Tensor:
-    """collate_clips on packed tight 4:2:0 frames (cc_collate_resize_crop_yuv420_u8): the same tables, byte offsets counting
-    frames of H W + 2 ceil(H / 2) ceil(W / 2) bytes; kind 0 I420 / 1 NV12; chw: the OUTPUT's layout."""
-    out = _e(*_collate_shape(_collate_check("collate_clips_yuv420", src, rows, clips, n_px, chw, COLLATE_ROW), n_px, chw), like=src,
-             dtype=torch.uint8)
-    _collate_yuv420_into(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw, out)
-    return out
-
-
-@collate_clips_yuv420.register_fake
-def _(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw):
-    _collate_yuv420_check("collate_clips_yuv420", kind, matrix)
-    n_out = _collate_check("collate_clips_yuv420", src, rows, clips, n_px, chw, COLLATE_ROW)
-    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::collate_clips_yuv420_out", mutates_args=("out",), device_types="cuda")
-def collate_clips_yuv420_out(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
-                             kind: int, matrix: int, full_range: bool, chw: bool, out: torch.Tensor) -> None:
-    """collate_clips_yuv420 into a buffer of the caller's; every frame of it is written."""
-    _collate_yuv420_into(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw, out)
-
-
-@collate_clips_yuv420_out.register_fake
-def _(src, rows, plans, clips, n_px, resize, kind, matrix, full_range, chw, out):
-    _collate_yuv420_check("collate_clips_yuv420", kind, matrix)
-    _collate_check("collate_clips_yuv420", src, rows, clips, n_px, chw, COLLATE_ROW, out)
-    return None
-
-
-def _collate_crop_flip_yuv420_into(src, rows, clips, n_px, kind, matrix, full_range, chw, out):
-    _collate_yuv420_check("collate_clips_crop_flip_yuv420", kind, matrix)
-    n_out = _collate_check("collate_clips_crop_flip_yuv420", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
-    L.require_device(src, rows, out)
-    src, rows = src.contiguous(), rows.contiguous()
-    L.check(L.lib().cc_collate_crop_flip_yuv420_u8(L.ptr(src), src.numel(), int(kind), int(matrix), int(full_range),
-                                                   _clips_host(clips), len(clips) // 4, L.ptr(rows), n_out, int(n_px), L.ptr(out),
-                                                   1 if chw else 2, _st(src)), "cc_collate_crop_flip_yuv420_u8")
-
-
-@custom_op(NS + "::collate_clips_crop_flip_yuv420", mutates_args=(), device_types="cuda")
-def collate_clips_crop_flip_yuv420(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, kind: int, matrix: int,
-                                   full_range: bool, chw: bool) -> torch.Tensor:
-    """collate_clips_crop_flip on packed tight 4:2:0 frames (cc_collate_crop_flip_yuv420_u8, one launch)."""
-    out = _e(*_collate_shape(_collate_check("collate_clips_crop_flip_yuv420", src, rows, clips, n_px, chw, COLLATE_BOX_ROW), n_px,
-                             chw), like=src, dtype=torch.uint8)
-    _collate_crop_flip_yuv420_into(src, rows, clips, n_px, kind, matrix, full_range, chw, out)
-    return out
-
-
-@collate_clips_crop_flip_yuv420.register_fake
-def _(src, rows, clips, n_px, kind, matrix, full_range, chw):
-    _collate_yuv420_check("collate_clips_crop_flip_yuv420", kind, matrix)
-    n_out = _collate_check("collate_clips_crop_flip_yuv420", src, rows, clips, n_px, chw, COLLATE_BOX_ROW)
-    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::collate_clips_crop_flip_yuv420_out", mutates_args=("out",), device_types="cuda")
-def collate_clips_crop_flip_yuv420_out(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, kind: int, matrix: int,
-                                       full_range: bool, chw: bool, out: torch.Tensor) -> None:
-    """collate_clips_crop_flip_yuv420 into a buffer of the caller's; every frame of it is written."""
-    _collate_crop_flip_yuv420_into(src, rows, clips, n_px, kind, matrix, full_range, chw, out)
-
-
-@collate_clips_crop_flip_yuv420_out.register_fake
-def _(src, rows, clips, n_px, kind, matrix, full_range, chw, out):
-    _collate_yuv420_check("collate_clips_crop_flip_yuv420", kind, matrix)
-    _collate_check("collate_clips_crop_flip_yuv420", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
-    return None
-
-
-# ---- YUV sources in general (include/centerclip_hip.h, "YUV sources in general"): 4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar,
-# samples of 8 bits or of 10 / 12 / 16 bits in 16-bit words.  The ops mirror the *_yuv420 ones with ``layout`` the twelve integers
-# of cc_yuv_layout (frame_stride, y_pitch, u_offset, v_offset, c_pitch, c_step, sub_x, sub_y, depth, shift, matrix, range), all
-# positions in BYTES; ``src`` is any contiguous uint8 tensor or, for 16-bit samples, a uint16 / int16 tensor with the same bits.
 # YUV_FORMATS is THE table of what a name means; nothing else branches on names.
 YUV_FORMATS = {                                     # name: (CC_YUV_* code, sub_x, sub_y, depth, shift, interleaved)
     "i420": (0, 1, 1, 8, 0, False), "nv12": (1, 1, 1, 8, 0, True), "i422": (2, 1, 0, 8, 0, False), "i444": (3, 0, 0, 8, 0, False),
@@ -1453,248 +973,360 @@ YUV_FORMATS = {                                     # name: (CC_YUV_* code, sub_
 _YUV_WORDS = (torch.uint16, torch.int16)
 
 
+def _pixels(n_rows, n_cols, chw):
+    return (3, n_rows, n_cols) if chw else (n_rows, n_cols, 3)
+
+
+def _fmt(chw):
+    return 1 if chw else 2                          # cc_frames formats: uint8 CHW / uint8 HWC
+
+
+def _resize_crop_shape(shape, n_px):
+    chw, _, _ = _raw_frames_geometry(shape)
+    return tuple(shape[:-3]) + _pixels(n_px, n_px, chw)
+
+
+def _frames_out_check(name, out, shape):
+    """The out-buffer rule of the YUV ops and of every collate: the result's frames under any leading dimensions (DeviceFeeder
+    hands in its [B, 1, T, ...] slots)."""
+    if out.dtype != torch.uint8 or not out.is_contiguous() or out.dim() < 3 or tuple(out.shape[-3:]) != shape[-3:] \
+            or out.numel() != math.prod(shape):
+        raise ValueError("%s: out must be contiguous uint8 frames [..., %s] with %d frames in all, got %s %s"
+                         % (name, ", ".join(map(str, shape[-3:])), math.prod(shape[:-3]), out.dtype, tuple(out.shape)))
+
+
+class _RgbSource:
+    """uint8 RGB frames [..., H, W, 3] or [..., 3, H, W]: layout and leading dimensions are the tensor's, the result keeps both
+    and ``out`` has exactly the result's shape.  Packed clips (the collates) say their layout with ``chw``."""
+    schema = dict(frames="Tensor frames", chw="", colour="")
+    entries = dict(resize_crop="cc_resize_crop_u8", crop_flip="cc_resized_crop_flip_u8", collate="cc_collate_resize_crop_u8",
+                   collate_crop_flip="cc_collate_crop_flip_u8")
+
+    def frames(self, name, frames, *rest):
+        """An op's arguments -> (src, F, H, W, chw, the result's leading dimensions, layout, the op's own arguments)."""
+        if frames.dtype != torch.uint8:
+            raise ValueError("%s takes uint8 frames, got %s" % (name, frames.dtype))
+        chw, H, W = _raw_frames_geometry(frames.shape)
+        lead = tuple(frames.shape[:-3])
+        return frames, math.prod(lead), H, W, chw, lead, None, rest
+
+    def c_frames(self, src, F, H, W, chw, layout):
+        """-> the source arguments every frame entry of this source begins with."""
+        return L.ptr(src), _fmt(chw), F, H, W
+
+    def out_check(self, name, out, shape):
+        if out.dtype != torch.uint8 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise ValueError("%s: out must be a contiguous uint8 %s, got %s %s" % (name, shape, out.dtype, tuple(out.shape)))
+
+    def colour(self, name, chw):
+        """A collate's arguments behind ``resize`` / ``n_px`` -> (chw of the result, the C arguments between src_bytes and the clip
+        table)."""
+        return chw, (_fmt(chw),)
+
+
+class _YuvSource:
+    """Decoder planes as ANY contiguous tensor - its bytes are what the layout's offsets count in - with the geometry spelled
+    out: F frames of H x W and ``layout``, the integers of the C descriptor ``struct`` in the order of its fields, all positions
+    in BYTES.  uint8, or uint16 / int16 words with the same bits where the descriptor has a depth and it is over 8.  The result
+    is [F, ...] in the layout ``chw`` asks for and ``out`` is any buffer of those frames.  Packed clips (the collates) are tight
+    frames of one format, named by a code below ``n_codes``; there ``chw`` is the OUTPUT's layout."""
+    out_check = staticmethod(_frames_out_check)
+
+    def __init__(self, struct, layout_doc, code_arg, codes_doc, n_codes, entries):
+        self.struct, self.layout_doc, self.codes_doc, self.n_codes, self.entries = struct, layout_doc, codes_doc, n_codes, entries
+        self.fields = [field for field, _ in struct._fields_]
+        self.depth_at = self.fields.index("depth") if "depth" in self.fields else None
+        self.schema = dict(frames="Tensor src, SymInt F, SymInt H, SymInt W, SymInt[] layout", chw=", bool chw",
+                           colour="SymInt %s, SymInt matrix, bool full_range, " % code_arg)
+
+    def frames(self, name, src, F, H, W, layout, *rest):
+        if len(layout) != len(self.fields):
+            raise ValueError("%s: layout is the %s (%s), got %d values" % (name, self.layout_doc, ", ".join(self.fields), len(layout)))
+        depth = 8 if self.depth_at is None else layout[self.depth_at]
+        if src.dtype != torch.uint8 and not (src.dtype in _YUV_WORDS and depth > 8):
+            raise ValueError("%s takes the decoder's planes as uint8 bytes or, for samples of more than 8 bits, uint16 / int16 words, "
+                             "got %s at depth %d" % (name, src.dtype, depth))
+        if F < 0 or H < 1 or W < 1:
+            raise ValueError("%s: F >= 0 frames of H, W >= 1, got %d x %d x %d" % (name, F, H, W))
+        return src, F, H, W, rest[-1], (F,), layout, rest[:-1]
+
+    def c_frames(self, src, F, H, W, chw, layout):
+        return L.ptr(src), src.numel() * src.element_size(), ctypes.byref(self.struct(*(int(v) for v in layout))), F, H, W
+
+    def colour(self, name, code, matrix, full_range, chw):
+        if not 0 <= code < self.n_codes or matrix not in (0, 1):
+            raise ValueError("%s: %s and matrix 0 (BT.601) / 1 (BT.709), got %d, %d" % (name, self.codes_doc, code, matrix))
+        return chw, (int(code), int(matrix), int(full_range))
+
+
+RGB = _RgbSource()
+# YUV 4:2:0 sources (include/centerclip_hip.h, "YUV 4:2:0 sources"): 8-bit samples, ``layout`` the eight integers of
+# cc_yuv420_layout.  preprocess.py builds the tight layouts of a decoder's [..., 3H/2, W] arrays; a pitched or odd-sized surface
+# is described by hand.  These ops keep the C entries of their own: the header folds them onto the general path.
+YUV420 = _YuvSource(L.Yuv420Layout, "eight integers of cc_yuv420_layout", "kind", "kind 0 (tight I420) / 1 (tight NV12)", 2,
+                    dict(to_rgb="cc_yuv420_to_rgb_u8", resize_crop="cc_resize_crop_yuv420_u8",
+                         crop_flip="cc_resized_crop_flip_yuv420_u8", collate="cc_collate_resize_crop_yuv420_u8",
+                         collate_crop_flip="cc_collate_crop_flip_yuv420_u8"))
+# YUV sources in general (include/centerclip_hip.h, "YUV sources in general"): 4:2:0 / 4:2:2 / 4:4:4, planar or semi-planar,
+# samples of 8 bits or of 10 / 12 / 16 bits in 16-bit words; ``layout`` the twelve integers of cc_yuv_layout.
+YUV = _YuvSource(L.YuvLayout, "twelve integers of cc_yuv_layout", "fmt",
+                 "format 0 .. %d (the CC_YUV_* codes of YUV_FORMATS)" % (len(YUV_FORMATS) - 1), len(YUV_FORMATS),
+                 dict(to_rgb="cc_yuv_to_rgb_u8", resize_crop="cc_resize_crop_yuv_u8", crop_flip="cc_resized_crop_flip_yuv_u8",
+                      collate="cc_collate_resize_crop_yuv_u8", collate_crop_flip="cc_collate_crop_flip_yuv_u8"))
+
+
+def _tight_layout(S, entry, codes, name, H, W, matrix, full_range):
+    if name not in codes or matrix not in YUV_MATRICES:
+        raise ValueError("a tight layout is one of %s and a matrix 'bt601' or 'bt709', got %r, %r" % (sorted(codes), name, matrix))
+    lay = S.struct()
+    if not getattr(L.lib(), entry)(codes[name], int(H), int(W), YUV_MATRICES[matrix], int(bool(full_range)), ctypes.byref(lay)):
+        raise ValueError("no tight %s layout for %s x %s frames (1 .. 8192)" % (name, H, W))
+    return [getattr(lay, field) for field in S.fields]
+
+
+def yuv420_tight_layout(kind, H, W, matrix, full_range):
+    """-> the eight integers of cc_yuv420_layout_tight for tight ``kind`` ("i420" / "nv12") frames of H x W one behind the
+    other; [0] is the bytes of a frame, H W + 2 ceil(H / 2) ceil(W / 2)."""
+    return _tight_layout(YUV420, "cc_yuv420_layout_tight", YUV_KINDS, kind, H, W, matrix, full_range)
+
+
 def yuv_tight_layout(name, H, W, matrix, full_range):
     """-> the twelve integers of cc_yuv_layout_tight for tight frames of the named format, H x W, one behind the other; [0] is
     the bytes of a frame."""
-    lay = L.YuvLayout()
-    if name not in YUV_FORMATS or matrix not in YUV_MATRICES:
-        raise ValueError("a YUV layout is one of %s and a matrix 'bt601' or 'bt709', got %r, %r" % (sorted(YUV_FORMATS), name, matrix))
-    if not L.lib().cc_yuv_layout_tight(YUV_FORMATS[name][0], int(H), int(W), YUV_MATRICES[matrix], int(bool(full_range)),
-                                       ctypes.byref(lay)):
-        raise ValueError("no tight %s layout for %s x %s frames (1 .. 8192)" % (name, H, W))
-    return [getattr(lay, field) for field, _ in L.YuvLayout._fields_]
+    return _tight_layout(YUV, "cc_yuv_layout_tight", {k: v[0] for k, v in YUV_FORMATS.items()}, name, H, W, matrix, full_range)
 
 
-def _yuv_general_source(name, src, F, H, W, layout):
-    """The checks the real and the fake kernels of the general YUV ops share."""
-    if len(layout) != 12:
-        raise ValueError("%s: layout is the twelve integers of cc_yuv_layout (frame_stride, y_pitch, u_offset, v_offset, c_pitch, "
-                         "c_step, sub_x, sub_y, depth, shift, matrix, range), got %d values" % (name, len(layout)))
-    if src.dtype != torch.uint8 and not (src.dtype in _YUV_WORDS and layout[8] > 8):
-        raise ValueError("%s takes the decoder's planes as uint8 bytes or, for samples of more than 8 bits, uint16 / int16 words, "
-                         "got %s at depth %d" % (name, src.dtype, layout[8]))
-    if F < 0 or H < 1 or W < 1:
-        raise ValueError("%s: F >= 0 frames of H, W >= 1, got %d x %d x %d" % (name, F, H, W))
+def _to_rgb(S, name, out, *args):
+    src, F, H, W, chw, lead, layout, _ = S.frames(name, *args)
+
+    def launch(out):
+        L.require_device(src)
+        if F:
+            s = src.contiguous()
+            fn = S.entries["to_rgb"]
+            L.check(getattr(L.lib(), fn)(*S.c_frames(s, F, H, W, chw, layout), L.ptr(out), _fmt(chw), _st(s)), fn)
+    return src, lead + _pixels(H, W, chw), launch
 
 
-def _yuv_general_layout(layout):
-    return L.YuvLayout(*(int(v) for v in layout))
+def _resize_crop(S, name, out, *args):
+    src, F, H, W, chw, lead, layout, (n_px, resize) = S.frames(name, *args)
+    shape = lead + _pixels(n_px, n_px, chw)
+    if out is not None:
+        S.out_check(name, out, shape)
+
+    def launch(out):
+        L.require_device(src, out)
+        if F == 0:
+            return
+        s = src.contiguous()
+        lib, fn = L.lib(), S.entries["resize_crop"]
+        plan = resize_plan(H, W, n_px, resize, s.device)
+        nws = lib.cc_resize_crop_workspace_bytes(F, H, W, int(n_px), int(resize))
+        ws = L.workspace(nws, s.device) if nws else None
+        L.check(getattr(lib, fn)(*S.c_frames(s, F, H, W, chw, layout), L.ptr(plan), int(n_px), int(resize), L.ptr(out), _fmt(chw),
+                                 L.ptr(ws), ws.numel() if ws is not None else 0, _st(s)), fn)
+    return src, shape, launch
 
 
-def _nbytes(t):
-    return t.numel() * t.element_size()
-
-
-@custom_op(NS + "::yuv_to_rgb", mutates_args=(), device_types="cuda")
-def yuv_to_rgb(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], chw: bool) -> torch.Tensor:
-    """The conversion alone (cc_yuv_to_rgb_u8, one launch): F frames of H x W in ``src`` as ``layout`` describes -> uint8
-    [F, H, W, 3] ([F, 3, H, W] with chw), the fixed integer conversion of the header for the layout's depth, chroma replicated."""
-    _yuv_general_source("yuv_to_rgb", src, F, H, W, layout)
-    L.require_device(src)
-    out = _e(*_yuv_shape(F, H, W, chw), like=src, dtype=torch.uint8)
-    if F:
-        src = src.contiguous()
-        L.check(L.lib().cc_yuv_to_rgb_u8(L.ptr(src), _nbytes(src), ctypes.byref(_yuv_general_layout(layout)), F, H, W, L.ptr(out),
-                                         1 if chw else 2, _st(src)), "cc_yuv_to_rgb_u8")
-    return out
-
-
-@yuv_to_rgb.register_fake
-def _(src, F, H, W, layout, chw):
-    _yuv_general_source("yuv_to_rgb", src, F, H, W, layout)
-    return src.new_empty(_yuv_shape(F, H, W, chw), dtype=torch.uint8)
-
-
-def _resize_crop_yuv_into(src, F, H, W, layout, n_px, resize, chw, out):
-    _yuv_general_source("resize_center_crop_yuv", src, F, H, W, layout)
-    _yuv_out_check("resize_center_crop_yuv", out, _yuv_shape(F, n_px, n_px, chw))
-    L.require_device(src, out)
-    if F == 0:
-        return
-    src = src.contiguous()
-    lib = L.lib()
-    plan = resize_plan(H, W, n_px, resize, src.device)
-    nws = lib.cc_resize_crop_workspace_bytes(F, H, W, int(n_px), int(resize))
-    ws = L.workspace(nws, src.device) if nws else None
-    L.check(lib.cc_resize_crop_yuv_u8(L.ptr(src), _nbytes(src), ctypes.byref(_yuv_general_layout(layout)), F, H, W, L.ptr(plan),
-                                      int(n_px), int(resize), L.ptr(out), 1 if chw else 2, L.ptr(ws),
-                                      ws.numel() if ws is not None else 0, _st(src)), "cc_resize_crop_yuv_u8")
-
-
-@custom_op(NS + "::resize_center_crop_yuv", mutates_args=(), device_types="cuda")
-def resize_center_crop_yuv(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], n_px: int, resize: bool,
-                           chw: bool) -> torch.Tensor:
-    """resize_center_crop on a YUV source (cc_resize_crop_yuv_u8): -> uint8 [F, n_px, n_px, 3] ([F, 3, n_px, n_px] with chw), bit
-    for bit resize_center_crop(yuv_to_rgb(src)); the first pass converts its taps, no RGB frame of H x W is stored."""
-    out = _e(*_yuv_shape(F, n_px, n_px, chw), like=src, dtype=torch.uint8)
-    _resize_crop_yuv_into(src, F, H, W, layout, n_px, resize, chw, out)
-    return out
-
-
-@resize_center_crop_yuv.register_fake
-def _(src, F, H, W, layout, n_px, resize, chw):
-    _yuv_general_source("resize_center_crop_yuv", src, F, H, W, layout)
-    return src.new_empty(_yuv_shape(F, n_px, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::resize_center_crop_yuv_out", mutates_args=("out",), device_types="cuda")
-def resize_center_crop_yuv_out(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], n_px: int, resize: bool, chw: bool,
-                               out: torch.Tensor) -> None:
-    """resize_center_crop_yuv into a buffer of the caller's."""
-    _resize_crop_yuv_into(src, F, H, W, layout, n_px, resize, chw, out)
-
-
-@resize_center_crop_yuv_out.register_fake
-def _(src, F, H, W, layout, n_px, resize, chw, out):
-    _yuv_general_source("resize_center_crop_yuv", src, F, H, W, layout)
-    return None
-
-
-def _crop_flip_yuv_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp):
-    _yuv_general_source("resized_crop_flip_yuv", src, F, H, W, layout)
+def _crop_flip(S, name, out, *args):
+    src, F, H, W, chw, lead, layout, (boxes, n_px, frames_per_clip, interp) = S.frames(name, *args)
     if frames_per_clip < 1 or interp not in (0, 1) or n_px < 1:
-        raise ValueError("resized_crop_flip_yuv: frames_per_clip >= 1, n_px >= 1 and interp 0 (bilinear) / 1 (bicubic), got "
-                         "%d, %d, %d" % (frames_per_clip, n_px, interp))
+        raise ValueError("%s: frames_per_clip >= 1, n_px >= 1 and interp 0 (bilinear) / 1 (bicubic), got %d, %d, %d"
+                         % (name, frames_per_clip, n_px, interp))
     clips = -(-F // frames_per_clip)
     if boxes.dtype != torch.int32 or tuple(boxes.shape) != (clips, 5):
-        raise ValueError("resized_crop_flip_yuv: boxes must be int32 [%d, 5] rows (top, left, height, width, flip) for %d frames "
-                         "in clips of %d, got %s %s" % (clips, F, frames_per_clip, boxes.dtype, tuple(boxes.shape)))
+        raise ValueError("%s: boxes must be int32 [%d, 5] rows (top, left, height, width, flip) for %d frames in clips of %d, got "
+                         "%s %s" % (name, clips, F, frames_per_clip, boxes.dtype, tuple(boxes.shape)))
+    shape = lead + _pixels(n_px, n_px, chw)
+    if out is not None:
+        S.out_check(name, out, shape)
+
+    def launch(out):
+        L.require_device(src, boxes, out)
+        if F == 0:
+            return
+        s, b = src.contiguous(), boxes.contiguous()
+        fn = S.entries["crop_flip"]
+        L.check(getattr(L.lib(), fn)(*S.c_frames(s, F, H, W, chw, layout), int(frames_per_clip), L.ptr(b), int(n_px), int(interp),
+                                     L.ptr(out), _fmt(chw), _st(s)), fn)
+    return src, shape, launch
 
 
-def _crop_flip_yuv_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out):
-    _crop_flip_yuv_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
-    _yuv_out_check("resized_crop_flip_yuv", out, _yuv_shape(F, n_px, n_px, chw))
-    L.require_device(src, boxes, out)
-    if F == 0:
-        return
-    src, boxes = src.contiguous(), boxes.contiguous()
-    L.check(L.lib().cc_resized_crop_flip_yuv_u8(L.ptr(src), _nbytes(src), ctypes.byref(_yuv_general_layout(layout)), F, H, W,
-                                                int(frames_per_clip), L.ptr(boxes), int(n_px), int(interp), L.ptr(out),
-                                                1 if chw else 2, _st(src)), "cc_resized_crop_flip_yuv_u8")
+def _collate_check(name, src, rows, clips, n_px, row_ints):
+    """What the two ragged-batch ops check about their tables -> n_out."""
+    if src.dtype != torch.uint8 or src.dim() != 1:
+        raise ValueError("%s: the packed clips are one 1-D uint8 buffer, got %s %s" % (name, src.dtype, tuple(src.shape)))
+    if rows.dtype != torch.int64 or rows.dim() != 2 or rows.shape[1] != row_ints or rows.shape[0] < 1:
+        raise ValueError("%s: the frame table is int64 [n_out >= 1, %d], got %s %s" % (name, row_ints, rows.dtype, tuple(rows.shape)))
+    if len(clips) == 0 or len(clips) % 4:
+        raise ValueError("%s: the clip table is B >= 1 rows of (byte offset, frames, H, W), got %d values" % (name, len(clips)))
+    if n_px < 1:
+        raise ValueError("%s: n_px >= 1, got %d" % (name, n_px))
+    return int(rows.shape[0])
 
 
-@custom_op(NS + "::resized_crop_flip_yuv", mutates_args=(), device_types="cuda")
-def resized_crop_flip_yuv(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], boxes: torch.Tensor, n_px: int,
-                          frames_per_clip: int, interp: int, chw: bool) -> torch.Tensor:
-    """resized_crop_flip on a YUV source (cc_resized_crop_flip_yuv_u8, one launch): bit for bit
-    resized_crop_flip(yuv_to_rgb(src), boxes, ...)."""
-    out = _e(*_yuv_shape(F, n_px, n_px, chw), like=src, dtype=torch.uint8)
-    _crop_flip_yuv_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out)
-    return out
+def _clips_host(clips):
+    return (ctypes.c_int64 * len(clips))(*clips)
 
 
-@resized_crop_flip_yuv.register_fake
-def _(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw):
-    _crop_flip_yuv_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
-    return src.new_empty(_yuv_shape(F, n_px, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::resized_crop_flip_yuv_out", mutates_args=("out",), device_types="cuda")
-def resized_crop_flip_yuv_out(src: torch.Tensor, F: int, H: int, W: int, layout: List[int], boxes: torch.Tensor, n_px: int,
-                              frames_per_clip: int, interp: int, chw: bool, out: torch.Tensor) -> None:
-    """resized_crop_flip_yuv into a buffer of the caller's."""
-    _crop_flip_yuv_into(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out)
-
-
-@resized_crop_flip_yuv_out.register_fake
-def _(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp, chw, out):
-    _crop_flip_yuv_check(src, F, H, W, layout, boxes, n_px, frames_per_clip, interp)
-    return None
-
-
-def _collate_yuv_check(name, fmt, matrix):
-    if not 0 <= fmt < len(YUV_FORMATS) or matrix not in (0, 1):
-        raise ValueError("%s: format 0 .. %d (the CC_YUV_* codes of YUV_FORMATS) and matrix 0 (BT.601) / 1 (BT.709), got %d, %d"
-                         % (name, len(YUV_FORMATS) - 1, fmt, matrix))
-
-
-def _collate_yuv_into(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw, out):
-    _collate_yuv_check("collate_clips_yuv", fmt, matrix)
-    n_out = _collate_check("collate_clips_yuv", src, rows, clips, n_px, chw, COLLATE_ROW, out)
+def _collate(S, name, out, src, rows, plans, clips, n_px, resize, *colour):
+    chw, c_colour = S.colour(name, *colour)
+    n_out = _collate_check(name, src, rows, clips, n_px, COLLATE_ROW)
     if plans.dtype != torch.int32 or plans.dim() != 1:
-        raise ValueError("collate_clips_yuv: the plans are one 1-D int32 buffer, got %s %s" % (plans.dtype, tuple(plans.shape)))
-    L.require_device(src, rows, plans, out)
-    src, rows, plans = src.contiguous(), rows.contiguous(), plans.contiguous()
-    lib, table = L.lib(), _clips_host(clips)
-    nws = lib.cc_collate_resize_crop_workspace_bytes(table, len(clips) // 4, n_out, int(n_px), int(resize))
-    ws = L.workspace(nws, src.device) if nws else None
-    L.check(lib.cc_collate_resize_crop_yuv_u8(L.ptr(src), src.numel(), int(fmt), int(matrix), int(full_range), table,
-                                              len(clips) // 4, L.ptr(rows), n_out, L.ptr(plans), plans.numel(), int(n_px),
-                                              int(resize), L.ptr(out), 1 if chw else 2, L.ptr(ws), nws, _st(src)),
-            "cc_collate_resize_crop_yuv_u8")
+        raise ValueError("%s: the plans are one 1-D int32 buffer, got %s %s" % (name, plans.dtype, tuple(plans.shape)))
+    shape = (n_out,) + _pixels(n_px, n_px, chw)
+    if out is not None:
+        _frames_out_check(name, out, shape)
+
+    def launch(out):
+        L.require_device(src, rows, plans, out)
+        s, r, p, table = src.contiguous(), rows.contiguous(), plans.contiguous(), _clips_host(clips)
+        lib, fn = L.lib(), S.entries["collate"]
+        nws = lib.cc_collate_resize_crop_workspace_bytes(table, len(clips) // 4, n_out, int(n_px), int(resize))
+        ws = L.workspace(nws, s.device) if nws else None
+        L.check(getattr(lib, fn)(L.ptr(s), s.numel(), *c_colour, table, len(clips) // 4, L.ptr(r), n_out, L.ptr(p), p.numel(),
+                                 int(n_px), int(resize), L.ptr(out), _fmt(chw), L.ptr(ws), nws, _st(s)), fn)
+    return src, shape, launch
 
 
-@custom_op(NS + "::collate_clips_yuv", mutates_args=(), device_types="cuda")
-def collate_clips_yuv(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
-                      fmt: int, matrix: int, full_range: bool, chw: bool) -> torch.Tensor:
+def _collate_crop_flip(S, name, out, src, rows, clips, n_px, *colour):
+    chw, c_colour = S.colour(name, *colour)
+    n_out = _collate_check(name, src, rows, clips, n_px, COLLATE_BOX_ROW)
+    shape = (n_out,) + _pixels(n_px, n_px, chw)
+    if out is not None:
+        _frames_out_check(name, out, shape)
+
+    def launch(out):
+        L.require_device(src, rows, out)
+        s, r = src.contiguous(), rows.contiguous()
+        fn = S.entries["collate_crop_flip"]
+        L.check(getattr(L.lib(), fn)(L.ptr(s), s.numel(), *c_colour, _clips_host(clips), len(clips) // 4, L.ptr(r), n_out,
+                                     int(n_px), L.ptr(out), _fmt(chw), _st(s)), fn)
+    return src, shape, launch
+
+
+FRAME_OPS = []                                      # every name _frame_ops registered; OPS takes them from here
+
+
+def _frame_ops(S, name, body, args, doc, out_doc=None):
+    """Register ``body`` for the source S as centerclip::<name> - ``args``: the schema's arguments, {frames} / {chw} / {colour}
+    standing for the source's - and, with ``out_doc``, as centerclip::<name>_out with a last argument ``out`` that is written
+    instead of a fresh tensor.  -> the CustomOpDef, or the pair."""
+    args = args.format(**S.schema)
+
+    def alloc(*a):
+        src, shape, launch = body(S, name, None, *a)
+        out = _e(*shape, like=src, dtype=torch.uint8)
+        launch(out)
+        return out
+
+    def alloc_fake(*a):
+        src, shape, _ = body(S, name, None, *a)
+        return src.new_empty(shape, dtype=torch.uint8)
+
+    def into(*a):
+        body(S, name, a[-1], *a[:-1])[2](a[-1])
+
+    def into_fake(*a):
+        body(S, name, a[-1], *a[:-1])
+
+    alloc.__doc__, into.__doc__ = doc, out_doc
+    plain = custom_op("%s::%s" % (NS, name), alloc, mutates_args=(), device_types="cuda", schema="(%s) -> Tensor" % args)
+    plain.register_fake(alloc_fake)
+    FRAME_OPS.append(name)
+    if out_doc is None:
+        return plain
+    twin = custom_op("%s::%s_out" % (NS, name), into, mutates_args=("out",), device_types="cuda",
+                     schema="(%s, Tensor(a%d!) out) -> ()" % (args, args.count(",") + 1))
+    twin.register_fake(into_fake)
+    FRAME_OPS.append(name + "_out")
+    return plain, twin
+
+
+_TO_RGB = (_to_rgb, "{frames}{chw}")
+_RESIZE_CROP = (_resize_crop, "{frames}, SymInt n_px, bool resize{chw}")
+_CROP_FLIP = (_crop_flip, "{frames}, Tensor boxes, SymInt n_px, SymInt frames_per_clip, SymInt interp{chw}")
+_COLLATE = (_collate, "Tensor src, Tensor rows, Tensor plans, SymInt[] clips, SymInt n_px, bool resize, {colour}bool chw")
+_COLLATE_CROP_FLIP = (_collate_crop_flip, "Tensor src, Tensor rows, SymInt[] clips, SymInt n_px, {colour}bool chw")
+
+resize_center_crop, resize_center_crop_out = _frame_ops(
+    RGB, "resize_center_crop", *_RESIZE_CROP,
+    """The loader transform in front of the encoders (cc_resize_crop_u8): uint8 frames [..., H, W, 3] or [..., 3, H, W] of any
+    size -> uint8 [..., n_px, n_px, 3] / [..., 3, n_px, n_px] (the input's layout), byte for byte Pillow's bicubic
+    Resize(n_px) + CenterCrop(n_px) (dataloaders/rawvideo_util.py:16-23); resize=False: the crop alone.""",
+    """resize_center_crop into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay).""")
+resized_crop_flip, resized_crop_flip_out = _frame_ops(
+    RGB, "resized_crop_flip", *_CROP_FLIP,
+    """Train-time augmentation (cc_resized_crop_flip_u8): uint8 frames [..., H, W, 3] or [..., 3, H, W] -> uint8
+    [..., n_px, n_px, 3] / [..., 3, n_px, n_px] (the input's layout); the frames count in clips of frames_per_clip and clip i
+    is cropped to boxes[i] = (top, left, height, width, flip) (int32, on the device - the kernel reads it, nothing is copied or
+    read back), resized to n_px x n_px with interp 0 bilinear / 1 bicubic (F.interpolate, align_corners=False, no antialias,
+    rounded to bytes) and mirrored where flip != 0.  A row outside the frame gives zeros for its clip.""",
+    """resized_crop_flip into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay).""")
+collate_clips, collate_clips_out = _frame_ops(
+    RGB, "collate_clips", *_COLLATE,
+    """A ragged batch of decoded clips -> uniform frames (cc_collate_resize_crop_u8, at most two launches whatever the batch
+    holds).  src: the packed uint8 bytes; clips: the HOST table, flat rows (byte offset, frames, H, W) - what is checked before
+    any launch; rows: int64 [n_out, 6] on the device, per output frame (kind 0 zero / 1 transform, byte offset, H, W, int32 offset
+    of the size's plan in ``plans``, byte offset of the frame's horizontal result in the workspace = i * the per-frame share of
+    cc_collate_resize_crop_workspace_bytes).  -> uint8 [n_out, n_px, n_px, 3] ([n_out, 3, n_px, n_px] with chw), each frame byte
+    for byte resize_center_crop of its source frame, zero frames zero.  preprocess.ClipCollate builds the tables.""",
+    """collate_clips into a buffer of the caller's (DeviceFeeder: one per slot, so the addresses a hipGraph saw stay); every
+    frame of it is written, the zero frames included.""")
+collate_clips_crop_flip, collate_clips_crop_flip_out = _frame_ops(
+    RGB, "collate_clips_crop_flip", *_COLLATE_CROP_FLIP,
+    """The training form of collate_clips (cc_collate_crop_flip_u8, one launch): rows int64 [n_out, 10] on the device, per output
+    frame (kind, byte offset, H, W, top, left, height, width, flip, interp 0 bilinear / 1 bicubic); each frame byte for byte
+    resized_crop_flip of its source frame with that box, zero frames zero.""",
+    """collate_clips_crop_flip into a buffer of the caller's; every frame of it is written.""")
+
+yuv420_to_rgb = _frame_ops(
+    YUV420, "yuv420_to_rgb", *_TO_RGB,
+    """The conversion alone (cc_yuv420_to_rgb_u8, one launch): F frames of H x W 8-bit 4:2:0 in ``src`` as ``layout`` describes
+    -> uint8 [F, H, W, 3] ([F, 3, H, W] with chw), the fixed integer conversion of the header, chroma replicated.""")
+resize_center_crop_yuv420, resize_center_crop_yuv420_out = _frame_ops(
+    YUV420, "resize_center_crop_yuv420", *_RESIZE_CROP,
+    """resize_center_crop on a 4:2:0 source (cc_resize_crop_yuv420_u8): -> uint8 [F, n_px, n_px, 3] ([F, 3, n_px, n_px] with chw),
+    bit for bit resize_center_crop(yuv420_to_rgb(src)); the first pass converts its taps, no RGB frame of H x W is stored.""",
+    """resize_center_crop_yuv420 into a buffer of the caller's.""")
+resized_crop_flip_yuv420, resized_crop_flip_yuv420_out = _frame_ops(
+    YUV420, "resized_crop_flip_yuv420", *_CROP_FLIP,
+    """resized_crop_flip on a 4:2:0 source (cc_resized_crop_flip_yuv420_u8, one launch): bit for bit
+    resized_crop_flip(yuv420_to_rgb(src), boxes, ...).""",
+    """resized_crop_flip_yuv420 into a buffer of the caller's.""")
+collate_clips_yuv420, collate_clips_yuv420_out = _frame_ops(
+    YUV420, "collate_clips_yuv420", *_COLLATE,
+    """collate_clips on packed tight 4:2:0 frames (cc_collate_resize_crop_yuv420_u8): the same tables, byte offsets counting
+    frames of H W + 2 ceil(H / 2) ceil(W / 2) bytes; kind 0 I420 / 1 NV12; chw: the OUTPUT's layout.""",
+    """collate_clips_yuv420 into a buffer of the caller's; every frame of it is written.""")
+collate_clips_crop_flip_yuv420, collate_clips_crop_flip_yuv420_out = _frame_ops(
+    YUV420, "collate_clips_crop_flip_yuv420", *_COLLATE_CROP_FLIP,
+    """collate_clips_crop_flip on packed tight 4:2:0 frames (cc_collate_crop_flip_yuv420_u8, one launch).""",
+    """collate_clips_crop_flip_yuv420 into a buffer of the caller's; every frame of it is written.""")
+
+yuv_to_rgb = _frame_ops(
+    YUV, "yuv_to_rgb", *_TO_RGB,
+    """The conversion alone (cc_yuv_to_rgb_u8, one launch): F frames of H x W in ``src`` as ``layout`` describes -> uint8
+    [F, H, W, 3] ([F, 3, H, W] with chw), the fixed integer conversion of the header for the layout's depth, chroma replicated.""")
+resize_center_crop_yuv, resize_center_crop_yuv_out = _frame_ops(
+    YUV, "resize_center_crop_yuv", *_RESIZE_CROP,
+    """resize_center_crop on a YUV source (cc_resize_crop_yuv_u8): -> uint8 [F, n_px, n_px, 3] ([F, 3, n_px, n_px] with chw), bit
+    for bit resize_center_crop(yuv_to_rgb(src)); the first pass converts its taps, no RGB frame of H x W is stored.""",
+    """resize_center_crop_yuv into a buffer of the caller's.""")
+resized_crop_flip_yuv, resized_crop_flip_yuv_out = _frame_ops(
+    YUV, "resized_crop_flip_yuv", *_CROP_FLIP,
+    """resized_crop_flip on a YUV source (cc_resized_crop_flip_yuv_u8, one launch): bit for bit
+    resized_crop_flip(yuv_to_rgb(src), boxes, ...).""",
+    """resized_crop_flip_yuv into a buffer of the caller's.""")
+collate_clips_yuv, collate_clips_yuv_out = _frame_ops(
+    YUV, "collate_clips_yuv", *_COLLATE,
     """collate_clips on packed tight YUV frames of one named format (cc_collate_resize_crop_yuv_u8): the same tables, byte
-    offsets counting tight frames of that format (even for 16-bit samples); fmt: the CC_YUV_* code; chw: the OUTPUT's layout."""
-    out = _e(*_collate_shape(_collate_check("collate_clips_yuv", src, rows, clips, n_px, chw, COLLATE_ROW), n_px, chw), like=src,
-             dtype=torch.uint8)
-    _collate_yuv_into(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw, out)
-    return out
-
-
-@collate_clips_yuv.register_fake
-def _(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw):
-    _collate_yuv_check("collate_clips_yuv", fmt, matrix)
-    n_out = _collate_check("collate_clips_yuv", src, rows, clips, n_px, chw, COLLATE_ROW)
-    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::collate_clips_yuv_out", mutates_args=("out",), device_types="cuda")
-def collate_clips_yuv_out(src: torch.Tensor, rows: torch.Tensor, plans: torch.Tensor, clips: List[int], n_px: int, resize: bool,
-                          fmt: int, matrix: int, full_range: bool, chw: bool, out: torch.Tensor) -> None:
-    """collate_clips_yuv into a buffer of the caller's; every frame of it is written."""
-    _collate_yuv_into(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw, out)
-
-
-@collate_clips_yuv_out.register_fake
-def _(src, rows, plans, clips, n_px, resize, fmt, matrix, full_range, chw, out):
-    _collate_yuv_check("collate_clips_yuv", fmt, matrix)
-    _collate_check("collate_clips_yuv", src, rows, clips, n_px, chw, COLLATE_ROW, out)
-    return None
-
-
-def _collate_crop_flip_yuv_into(src, rows, clips, n_px, fmt, matrix, full_range, chw, out):
-    _collate_yuv_check("collate_clips_crop_flip_yuv", fmt, matrix)
-    n_out = _collate_check("collate_clips_crop_flip_yuv", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
-    L.require_device(src, rows, out)
-    src, rows = src.contiguous(), rows.contiguous()
-    L.check(L.lib().cc_collate_crop_flip_yuv_u8(L.ptr(src), src.numel(), int(fmt), int(matrix), int(full_range), _clips_host(clips),
-                                                len(clips) // 4, L.ptr(rows), n_out, int(n_px), L.ptr(out), 1 if chw else 2,
-                                                _st(src)), "cc_collate_crop_flip_yuv_u8")
-
-
-@custom_op(NS + "::collate_clips_crop_flip_yuv", mutates_args=(), device_types="cuda")
-def collate_clips_crop_flip_yuv(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, fmt: int, matrix: int,
-                                full_range: bool, chw: bool) -> torch.Tensor:
-    """collate_clips_crop_flip on packed tight YUV frames of one named format (cc_collate_crop_flip_yuv_u8, one launch)."""
-    out = _e(*_collate_shape(_collate_check("collate_clips_crop_flip_yuv", src, rows, clips, n_px, chw, COLLATE_BOX_ROW), n_px, chw),
-             like=src, dtype=torch.uint8)
-    _collate_crop_flip_yuv_into(src, rows, clips, n_px, fmt, matrix, full_range, chw, out)
-    return out
-
-
-@collate_clips_crop_flip_yuv.register_fake
-def _(src, rows, clips, n_px, fmt, matrix, full_range, chw):
-    _collate_yuv_check("collate_clips_crop_flip_yuv", fmt, matrix)
-    n_out = _collate_check("collate_clips_crop_flip_yuv", src, rows, clips, n_px, chw, COLLATE_BOX_ROW)
-    return src.new_empty(_collate_shape(n_out, n_px, chw), dtype=torch.uint8)
-
-
-@custom_op(NS + "::collate_clips_crop_flip_yuv_out", mutates_args=("out",), device_types="cuda")
-def collate_clips_crop_flip_yuv_out(src: torch.Tensor, rows: torch.Tensor, clips: List[int], n_px: int, fmt: int, matrix: int,
-                                    full_range: bool, chw: bool, out: torch.Tensor) -> None:
-    """collate_clips_crop_flip_yuv into a buffer of the caller's; every frame of it is written."""
-    _collate_crop_flip_yuv_into(src, rows, clips, n_px, fmt, matrix, full_range, chw, out)
-
-
-@collate_clips_crop_flip_yuv_out.register_fake
-def _(src, rows, clips, n_px, fmt, matrix, full_range, chw, out):
-    _collate_yuv_check("collate_clips_crop_flip_yuv", fmt, matrix)
-    _collate_check("collate_clips_crop_flip_yuv", src, rows, clips, n_px, chw, COLLATE_BOX_ROW, out)
-    return None
+    offsets counting tight frames of that format (even for 16-bit samples); fmt: the CC_YUV_* code; chw: the OUTPUT's layout.""",
+    """collate_clips_yuv into a buffer of the caller's; every frame of it is written.""")
+collate_clips_crop_flip_yuv, collate_clips_crop_flip_yuv_out = _frame_ops(
+    YUV, "collate_clips_crop_flip_yuv", *_COLLATE_CROP_FLIP,
+    """collate_clips_crop_flip on packed tight YUV frames of one named format (cc_collate_crop_flip_yuv_u8, one launch).""",
+    """collate_clips_crop_flip_yuv into a buffer of the caller's; every frame of it is written.""")
 
 
 @custom_op(NS + "::clip_encode_out", mutates_args=("vfeat", "tfeat", "medoids_out"), device_types="cuda")
@@ -2690,15 +2322,10 @@ OPS = ("contrastive_loss", "contrastive_loss_grad", "contrastive_loss_grad_dev",
        "loose_similarity", "video_pool_normalize", "normalize_rows", "scaled_dot_nt", "scaled_dot_nt_out", "rank_counts",
        "rank_counts_cols", "rank_counts_ref", "group_max_rows", "normalize_rows_planes", "video_pool_normalize_planes",
        "scaled_dot_planes", "key_masked_attention", "key_masked_attention_backward", "seqtransf_forward", "linear_ln_act_f16",
-       "resize_center_crop", "resize_center_crop_out", "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
+       "similarity_topk", "dsl_col_stats_planes", "similarity_topk_dsl",
        "similarity_topk_grouped", "similarity_topk_grouped_dsl", "similarity_topk_masked", "dsl_col_stats_planes_masked",
        "pack_row_mask", "similarity_rank", "similarity_topk_deep", "similarity_topk_merge", "similarity_target_score",
-       "similarity_count", "resized_crop_flip", "resized_crop_flip_out", "video_window_pool_planes",
-       "yuv420_to_rgb", "resize_center_crop_yuv420", "resize_center_crop_yuv420_out", "resized_crop_flip_yuv420",
-       "resized_crop_flip_yuv420_out", "collate_clips_yuv420", "collate_clips_yuv420_out", "collate_clips_crop_flip_yuv420",
-       "collate_clips_crop_flip_yuv420_out", "yuv_to_rgb", "resize_center_crop_yuv", "resize_center_crop_yuv_out",
-       "resized_crop_flip_yuv", "resized_crop_flip_yuv_out", "collate_clips_yuv", "collate_clips_yuv_out",
-       "collate_clips_crop_flip_yuv", "collate_clips_crop_flip_yuv_out")
+       "similarity_count", "video_window_pool_planes") + tuple(FRAME_OPS)
 
 
 def logit_multiplier(logit_scale):
